@@ -7,7 +7,14 @@ Nothing is skipped inside the timed region.  N > 1: one process per GPU -- `pyth
 (torch.distributed.run on 127.0.0.1; under a launcher it reads RANK / LOCAL_RANK / WORLD_SIZE instead) -- batch sharded by image
 (weak scaling: 64 images per GPU), SUM all-reduce of gradients over RCCL overlapped with the backward segments.
 
-Prints ONE JSON line on rank 0 (contract in the task statement), extended with
+Prints ONE JSON line on rank 0: metric, value (images/s), unit, higher_is_better, dtype, ms_per_step (one timed step), loss_items of
+the last timed step.  A plain run does only that: set up, warm up, time --steps steps, print.
+  --dump-outputs DIR  after the timed steps, what the last one handed its caller as DIR/<name>.npy (float32): loss_items, the head
+                      outputs of its forward (boxes, scores, ...) and the model state after its AdamW update (state); an array above
+                      its share of 64 MB is a fixed seeded sample of its elements.  Inputs and weights are seeded: the same arguments
+                      give the same inputs on every run, so two builds can be compared output for output.
+  --full              the secondary figures below as well (untimed extra work after the timed region; `--dump-launches` needs it),
+                      and for N > 1 the `dist` split of the step (exposed all-reduce time against a local step timed right after):
   roofline     -- the DOMINANT KERNEL of the step (largest summed launch time; conv_p2_kernel on config 2, conv_gemm_kernel on
                   config 5): algorithmic bytes (HBM-bound) or flop (MFMA-bound, by the kernel's own arithmetic intensity against
                   the ridge) of its launches / their HIP-event durations, measured live on the engine's stream in extra untimed
@@ -165,6 +172,30 @@ def spawn_probe(backend="torch", expect=0):
         raise SystemExit("bench.py: the unique-id broadcast of the C-ABI path did not reach every rank")
 
 
+DUMP_BYTES = 64 << 20      # --dump-outputs budget over all files
+HEAD_OUTPUTS = {"detect": ("boxes", "scores"), "segment": ("boxes", "scores", "mask_coefficient", "proto"), "obb": ("boxes", "scores", "angle"),
+                "pose": ("boxes", "scores", "kpts")}
+
+
+def dump_outputs(path, model, items, task):
+    """--dump-outputs: what the timed step returns to its caller, read after the last timed step -- loss.detach() items, the head outputs of
+    its training forward (preds; the step's backward / AdamW / zero_grad leave them in place) and the model state (parameters and BatchNorm
+    statistics, state_dict order, flattened) after its AdamW update.  Every array above its share of DUMP_BYTES is replaced by the same
+    seeded, sorted sample of its elements on every run."""
+    os.makedirs(path, exist_ok=True)
+    big = {k: model.get_output(k) for k in HEAD_OUTPUTS[task]}
+    big["state"] = np.concatenate([a.ravel() for a in model.state_dict().values()])
+    cap = (DUMP_BYTES - 4096) // 4 // len(big)
+    arrays = {"loss_items": np.asarray(items, np.float32)}
+    for k, a in big.items():
+        a = a.ravel()
+        if a.size > cap:
+            a = a[np.sort(np.random.default_rng(0).choice(a.size, cap, replace=False))]
+        arrays[k] = a
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), np.ascontiguousarray(a, np.float32))
+
+
 def check_rank_count(ranks, n_gpus):
     """A multi-rank line is only a line of record when as many ranks took part in the collective as --gpus promised (round-5 verdict item 9)."""
     if ranks != n_gpus:
@@ -195,7 +226,15 @@ def main():
     ap.add_argument("--dump-launches", default="", help="write a per-launch CSV (class,label,us) of the profiled conv launches (triage)")
     ap.add_argument("--spawn-probe", action="store_true", help="self-test of the --gpus N launch path on CPU (gloo): no GPU work")
     ap.add_argument("--cpu-batch", type=int, default=64, help="batch of the cpu_baseline train sample (SURVEY 8d: 64; smaller = faster)")
+    ap.add_argument("--full", action="store_true", help="also measure the secondary figures (roofline / per-kernel profile, infer, nms, cpu_baseline, dist split); "
+                                                         "a plain run only times the steps")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="write what the last timed step computed (loss items, head outputs, model state) "
+                                                                      "as DIR/<name>.npy, float32, at most 64 MB")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_launches and not args.full:
+        ap.error("--dump-launches writes the launches of the --full profile steps: add --full")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # no launcher around us: the bench contract is `bench.py --gpus N`, so start the N ranks here (one process per GPU)
@@ -329,8 +368,9 @@ def main():
     rccl_ranks = 1
     dist_info = None
     items = crit.read()[1]                          # loss items of the last TIMED step (before the untimed diagnostic steps below)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, model, items, args.task)
     if distributed:
-        own = elapsed
         t = torch.tensor([elapsed], device=rdev, dtype=torch.float64)
         tmin = t.clone()
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -339,95 +379,38 @@ def main():
         ones = torch.ones(1, device=rdev, dtype=torch.float32)
         dist.all_reduce(ones)                      # SUM over the process group (RCCL, or gloo with --dist-backend c): how many ranks really took part
         rccl_ranks = int(ones.item())
-        # what the exchange costs this step: the same ranks run the LOCAL step (no all-reduce) for a short timed region right after, between the same
-        # barriers -- exposed all-reduce time = distributed step - local step (max over ranks of each)
-        n_loc = max(5, min(args.steps, 20))
-        for _ in range(3):
-            local_step()
-        barrier()
-        t1 = time.perf_counter()
-        for _ in range(n_loc):
-            local_step()
-        barrier()
-        tl = torch.tensor([(time.perf_counter() - t1) / n_loc], device=rdev, dtype=torch.float64)
-        dist.all_reduce(tl, op=dist.ReduceOp.MAX)
-        ms_local = float(tl.item()) * 1e3
-        dist_info = {"backend": "c (ys_dist_* in libyolosharp_hip.so)" if c_dist else "torch.distributed (nccl = RCCL)",
-                     "rank_ms_per_step_min": round(float(tmin.item()) / args.steps * 1e3, 3), "rank_ms_per_step_max": round(elapsed / args.steps * 1e3, 3),
-                     "local_step_ms": round(ms_local, 3), "allreduce_exposed_ms": round(elapsed / args.steps * 1e3 - ms_local, 3),
-                     "segment_allreduce_bytes": [int(c) * 4 for _, c in seg_ranges], "allreduce_bytes_per_step": int(sum(c for _, c in seg_ranges)) * 4,
-                     "note": "allreduce_exposed_ms = ms_per_step (max over ranks) - the same ranks' local step (forward + criterion + backward + AdamW, no exchange) timed right after; "
-                             "segments in backward order (head, neck, late backbone, stem): each all-reduce is issued when its segment's gradients are complete and overlaps the next segment"}
+        if args.full:
+            # what the exchange costs this step: the same ranks run the LOCAL step (no all-reduce) for a short timed region right after, between the same
+            # barriers -- exposed all-reduce time = distributed step - local step (max over ranks of each)
+            n_loc = max(5, min(args.steps, 20))
+            for _ in range(3):
+                local_step()
+            barrier()
+            t1 = time.perf_counter()
+            for _ in range(n_loc):
+                local_step()
+            barrier()
+            tl = torch.tensor([(time.perf_counter() - t1) / n_loc], device=rdev, dtype=torch.float64)
+            dist.all_reduce(tl, op=dist.ReduceOp.MAX)
+            ms_local = float(tl.item()) * 1e3
+            dist_info = {"backend": "c (ys_dist_* in libyolosharp_hip.so)" if c_dist else "torch.distributed (nccl = RCCL)",
+                         "rank_ms_per_step_min": round(float(tmin.item()) / args.steps * 1e3, 3), "rank_ms_per_step_max": round(elapsed / args.steps * 1e3, 3),
+                         "local_step_ms": round(ms_local, 3), "allreduce_exposed_ms": round(elapsed / args.steps * 1e3 - ms_local, 3),
+                         "segment_allreduce_bytes": [int(c) * 4 for _, c in seg_ranges], "allreduce_bytes_per_step": int(sum(c for _, c in seg_ranges)) * 4,
+                         "note": "allreduce_exposed_ms = ms_per_step (max over ranks) - the same ranks' local step (forward + criterion + backward + AdamW, no exchange) timed right after; "
+                                 "segments in backward order (head, neck, late backbone, stem): each all-reduce is issued when its segment's gradients are complete and overlaps the next segment"}
     ms = elapsed / args.steps * 1e3
     value = B * world * args.steps / elapsed
 
     out = None
     if rank == 0:
-        es = 2 if args.dtype in ("bf16", "fp8") else 4      # fp8 mode stores activations in bf16 (f8.hip)
-        wk = step_work(args.size, nc, H, W, es) if headline else None
-        # ---- per-kernel roofline, HIP events on the engine stream around every convolution launch, untimed extra steps
-        from yolosharp_amd import roofline as RL
-        import tempfile
-        steps_prof = 2
-        model.set_overlap(False)   # per-kernel durations: every kernel alone on the chip (the timed region ran with the weight-gradient stream on)
-        eng.kernel_profile(True)
-        for _ in range(steps_prof):
-            local_step()        # rank 0 only: no collective may be issued here (the other ranks are already at the final barrier)
-        eng.synchronize()
-        model.set_overlap(True)
-        n_ig, ms_ig = eng.kernel_profile_read("conv_igemm")
-        n_wg, ms_wg = eng.kernel_profile_read("conv_wgrad")
-        dump = args.dump_launches or os.path.join(tempfile.gettempdir(), f"ys_launches_{os.getpid()}.csv")
-        eng.kernel_profile_dump(dump)
-        eng.kernel_profile(False)
-        agg = RL.per_kernel(dump, steps_prof, es)
-        if not args.dump_launches:
-            os.remove(dump)
-        dom = max(agg, key=lambda k: agg[k]["ms"])
-        roofline = RL.roofline_of(dom, agg[dom])
-        roofline["what"] = ("dominant kernel = largest summed launch time of the step (profile steps run with the second weight-gradient stream off, every kernel alone on the chip); achieved = its launches' algorithmic "
-                            + ("bytes" if roofline["bound"] == "hbm" else "flop") + " (launch geometry: input tensor + output tensor once, SURVEY 8d) / their HIP-event durations")
-        # HBM bytes per launch of that kernel from the committed PMC passes (rocprofv3 cannot run inside the timed process): only when
-        # the file was measured on THIS source tree and configuration
-        traffic, traffic_note = None, None
-        cfg_key = f"YOLOv{args.family}{args.size}{'-' + args.task if args.task != 'detect' else ''} B={B} {H}x{W} {args.dtype}"
-        import glob
-        tfiles = sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_hbm_traffic.json")), reverse=True)   # newest round first
-        for tf in tfiles:
-            tname = "profiles/" + os.path.basename(tf)
-            try:
-                ent = json.load(open(tf)).get("configs", {}).get(cfg_key)
-                if ent is None:
-                    traffic_note = traffic_note or "no PMC passes committed for this configuration"
-                elif ent.get("source_sha") != RL.source_sha(ROOT):
-                    traffic_note = f"{tname} was measured on source {ent.get('source_sha')}, this tree is {RL.source_sha(ROOT)}: not reported"
-                    break
-                else:
-                    traffic = ent["kernels"][dom.split("<")[0]]["hbm_bytes_per_launch_corrected"]
-                    traffic_note = None
-                    break
-            except Exception as e:
-                traffic_note = f"{tname} unreadable ({type(e).__name__})"
-        roofline["traffic"] = traffic
-        if traffic_note:
-            roofline["traffic_note"] = traffic_note
-        roofline["kernels"] = {k: {f: v for f, v in RL.roofline_of(k, a).items() if f in ("bound", "achieved", "unit", "frac", "launches_per_step", "avg_launch_ms", "kernel_ms_per_step")}
-                               for k, a in sorted(agg.items(), key=lambda kv: -kv[1]["ms"])}
-        roofline["class_ms_per_step"] = {"conv_igemm": round(ms_ig / steps_prof, 3), "conv_wgrad": round(ms_wg / steps_prof, 3)}
-        # whole step: SURVEY 8d totals (headline graph: yolosharp_amd/workload.py; other graphs: the launches actually made -- conv units only)
-        step_bytes = wk["train_bytes"] * B if headline else sum(a["bytes"] for a in agg.values())
-        step_flop = wk["train_flop"] * B if headline else sum(a["flop"] for a in agg.values())
-        roofline["step_algorithmic_GBps"] = round(step_bytes / (ms * 1e-3) / 1e9, 1)
-        roofline["step_frac"] = round(step_bytes / (ms * 1e-3) / 1e9 / RL.HBM_PEAK_GBS, 4)
-        roofline["step_TFLOPs"] = round(step_flop / (ms * 1e-3) / 1e12, 2)
-        roofline["step_mfma_frac"] = round(step_flop / (ms * 1e-3) / 1e12 / RL.MFMA_PEAK_TF["fp8" if args.dtype == "fp8" else ("bf16" if args.dtype == "bf16" else "f32")], 4)
         gname = f"YOLOv{args.family}{args.size}" + {"segment": "-seg", "obb": "-obb", "pose": "-pose"}.get(args.task, "")
         out = {"metric": f"train images/sec {gname} {W}x{H} bs={B}/GPU", "value": round(value, 2), "unit": "images/s",
                "n_gpus": world, "rccl_ranks": rccl_ranks, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms, 3),
                "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
                "config": {"workload": f"{gname} {args.task} train step (fwd+loss+bwd+AdamW), {B}x3x{H}x{W} per GPU, {'COCO-80' if nc == 80 else str(nc) + '-class'} synthetic labels" + {"segment": " + instance masks", "obb": " (oriented)", "pose": " + 17x3 keypoints"}.get(args.task, ""),
                           "global_batch": B * world, "parallelism": f"dp{world}"},
-               "loss_items": [round(float(v), 5) for v in items], "roofline": roofline,
+               "loss_items": [round(float(v), 5) for v in items],
                "host_enqueue_ms_per_step": round(t_enq / args.steps * 1e3, 3)}
         if dist_info is not None:
             out["dist"] = dist_info
@@ -435,50 +418,110 @@ def main():
             out["triage_lib"] = args.lib          # not the product library: never a bench line of record
         if os.environ.get("BENCH_WG_FORCE"):
             out["triage_wg_force"] = os.environ["BENCH_WG_FORCE"]
-        # ---- secondary metric: inference images/s = eval forward (BN folded into the conv epilogues) + Detect decode
-        model.eval()
-        for _ in range(0 if args.no_infer else 3):
-            model.forward_device(d_img, B)
-        eng.synchronize()
-        t1 = time.perf_counter()
-        n_inf = 10
-        for _ in range(0 if args.no_infer else n_inf):
-            model.forward_device(d_img, B)
-        eng.synchronize()
-        t_inf = (time.perf_counter() - t1) / n_inf
-        out["infer"] = None if args.no_infer else {"images_per_s": round(B / t_inf, 1), "ms_per_batch": round(t_inf * 1e3, 3), "batch": B,
-                        "what": "eval forward + decode to pred [B,4+nc(+nm),A], inputs resident in HBM"}
-        model.train()
-        # ---- secondary metric: NMS boxes/s on [64, 84, 8400]
-        nms_pred_host = None
-        if not args.no_nms and nc == 80:      # the NMS line is quoted on the COCO-80 shape
-            prng = np.random.default_rng(3)
-            A = 8400
-            wh = prng.uniform(0.03, 0.6, (64, 2, A)) * 640; c = prng.uniform(0, 640, (64, 2, A))
-            sc = 1 / (1 + np.exp(-prng.normal(-3, 1.5, (64, nc, A))))
-            sc[:, :, prng.random(A) < 0.92] *= 0.05                      # ~8 % of anchors pass conf 0.25
-            pred = np.concatenate([c, wh, sc], 1).astype(np.float32)
-            nms_pred_host = pred
-            ncand = int(((pred[:, 4:].max(1)) > 0.25).sum())
-            d_pred = eng.malloc(pred.nbytes)
-            d_rows = eng.malloc(64 * 300 * 6 * 4); d_keep = eng.malloc(64 * 300 * 8); d_cnt = eng.malloc(64 * 4)
-            import ctypes as C
-            times = []
-            for it in range(6):
-                # restore the xywh input (NMS converts boxes in place), untimed
-                eng.lib.ys_memcpy_h2d(eng.ctx, d_pred, pred.ctypes.data_as(C.c_void_p), pred.nbytes)
-                eng.synchronize()
-                t1 = time.perf_counter()
-                eng.nms_device(d_pred, 64, 84, A, 0.25, 0.45, 300, 0, d_rows, d_keep, d_cnt)
-                eng.synchronize()
-                times.append(time.perf_counter() - t1)
-            tn = float(np.median(times[1:]))
-            out["nms"] = {"boxes_per_s": round(ncand / tn, 1), "candidates": ncand, "ms": round(tn * 1e3, 3),
-                          "shape": [64, 84, A], "conf": 0.25, "iou": 0.45}
-        if world == 1 and not args.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline(nc, H, W, sample_b=args.cpu_batch, nms_pred=nms_pred_host)
-        else:
-            out["cpu_baseline"] = None
+        if args.full:
+            es = 2 if args.dtype in ("bf16", "fp8") else 4      # fp8 mode stores activations in bf16 (f8.hip)
+            wk = step_work(args.size, nc, H, W, es) if headline else None
+            # ---- per-kernel roofline, HIP events on the engine stream around every convolution launch, untimed extra steps
+            from yolosharp_amd import roofline as RL
+            import tempfile
+            steps_prof = 2
+            model.set_overlap(False)   # per-kernel durations: every kernel alone on the chip (the timed region ran with the weight-gradient stream on)
+            eng.kernel_profile(True)
+            for _ in range(steps_prof):
+                local_step()        # rank 0 only: no collective may be issued here (the other ranks are already at the final barrier)
+            eng.synchronize()
+            model.set_overlap(True)
+            n_ig, ms_ig = eng.kernel_profile_read("conv_igemm")
+            n_wg, ms_wg = eng.kernel_profile_read("conv_wgrad")
+            dump = args.dump_launches or os.path.join(tempfile.gettempdir(), f"ys_launches_{os.getpid()}.csv")
+            eng.kernel_profile_dump(dump)
+            eng.kernel_profile(False)
+            agg = RL.per_kernel(dump, steps_prof, es)
+            if not args.dump_launches:
+                os.remove(dump)
+            dom = max(agg, key=lambda k: agg[k]["ms"])
+            roofline = RL.roofline_of(dom, agg[dom])
+            roofline["what"] = ("dominant kernel = largest summed launch time of the step (profile steps run with the second weight-gradient stream off, every kernel alone on the chip); achieved = its launches' algorithmic "
+                                + ("bytes" if roofline["bound"] == "hbm" else "flop") + " (launch geometry: input tensor + output tensor once, SURVEY 8d) / their HIP-event durations")
+            # HBM bytes per launch of that kernel from the committed PMC passes (rocprofv3 cannot run inside the timed process): only when
+            # the file was measured on THIS source tree and configuration
+            traffic, traffic_note = None, None
+            cfg_key = f"YOLOv{args.family}{args.size}{'-' + args.task if args.task != 'detect' else ''} B={B} {H}x{W} {args.dtype}"
+            import glob
+            tfiles = sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_hbm_traffic.json")), reverse=True)   # newest round first
+            for tf in tfiles:
+                tname = "profiles/" + os.path.basename(tf)
+                try:
+                    ent = json.load(open(tf)).get("configs", {}).get(cfg_key)
+                    if ent is None:
+                        traffic_note = traffic_note or "no PMC passes committed for this configuration"
+                    elif ent.get("source_sha") != RL.source_sha(ROOT):
+                        traffic_note = f"{tname} was measured on source {ent.get('source_sha')}, this tree is {RL.source_sha(ROOT)}: not reported"
+                        break
+                    else:
+                        traffic = ent["kernels"][dom.split("<")[0]]["hbm_bytes_per_launch_corrected"]
+                        traffic_note = None
+                        break
+                except Exception as e:
+                    traffic_note = f"{tname} unreadable ({type(e).__name__})"
+            roofline["traffic"] = traffic
+            if traffic_note:
+                roofline["traffic_note"] = traffic_note
+            roofline["kernels"] = {k: {f: v for f, v in RL.roofline_of(k, a).items() if f in ("bound", "achieved", "unit", "frac", "launches_per_step", "avg_launch_ms", "kernel_ms_per_step")}
+                                   for k, a in sorted(agg.items(), key=lambda kv: -kv[1]["ms"])}
+            roofline["class_ms_per_step"] = {"conv_igemm": round(ms_ig / steps_prof, 3), "conv_wgrad": round(ms_wg / steps_prof, 3)}
+            # whole step: SURVEY 8d totals (headline graph: yolosharp_amd/workload.py; other graphs: the launches actually made -- conv units only)
+            step_bytes = wk["train_bytes"] * B if headline else sum(a["bytes"] for a in agg.values())
+            step_flop = wk["train_flop"] * B if headline else sum(a["flop"] for a in agg.values())
+            roofline["step_algorithmic_GBps"] = round(step_bytes / (ms * 1e-3) / 1e9, 1)
+            roofline["step_frac"] = round(step_bytes / (ms * 1e-3) / 1e9 / RL.HBM_PEAK_GBS, 4)
+            roofline["step_TFLOPs"] = round(step_flop / (ms * 1e-3) / 1e12, 2)
+            roofline["step_mfma_frac"] = round(step_flop / (ms * 1e-3) / 1e12 / RL.MFMA_PEAK_TF["fp8" if args.dtype == "fp8" else ("bf16" if args.dtype == "bf16" else "f32")], 4)
+            out["roofline"] = roofline
+            # ---- secondary metric: inference images/s = eval forward (BN folded into the conv epilogues) + Detect decode
+            model.eval()
+            for _ in range(0 if args.no_infer else 3):
+                model.forward_device(d_img, B)
+            eng.synchronize()
+            t1 = time.perf_counter()
+            n_inf = 10
+            for _ in range(0 if args.no_infer else n_inf):
+                model.forward_device(d_img, B)
+            eng.synchronize()
+            t_inf = (time.perf_counter() - t1) / n_inf
+            out["infer"] = None if args.no_infer else {"images_per_s": round(B / t_inf, 1), "ms_per_batch": round(t_inf * 1e3, 3), "batch": B,
+                            "what": "eval forward + decode to pred [B,4+nc(+nm),A], inputs resident in HBM"}
+            model.train()
+            # ---- secondary metric: NMS boxes/s on [64, 84, 8400]
+            nms_pred_host = None
+            if not args.no_nms and nc == 80:      # the NMS line is quoted on the COCO-80 shape
+                prng = np.random.default_rng(3)
+                A = 8400
+                wh = prng.uniform(0.03, 0.6, (64, 2, A)) * 640; c = prng.uniform(0, 640, (64, 2, A))
+                sc = 1 / (1 + np.exp(-prng.normal(-3, 1.5, (64, nc, A))))
+                sc[:, :, prng.random(A) < 0.92] *= 0.05                      # ~8 % of anchors pass conf 0.25
+                pred = np.concatenate([c, wh, sc], 1).astype(np.float32)
+                nms_pred_host = pred
+                ncand = int(((pred[:, 4:].max(1)) > 0.25).sum())
+                d_pred = eng.malloc(pred.nbytes)
+                d_rows = eng.malloc(64 * 300 * 6 * 4); d_keep = eng.malloc(64 * 300 * 8); d_cnt = eng.malloc(64 * 4)
+                import ctypes as C
+                times = []
+                for it in range(6):
+                    # restore the xywh input (NMS converts boxes in place), untimed
+                    eng.lib.ys_memcpy_h2d(eng.ctx, d_pred, pred.ctypes.data_as(C.c_void_p), pred.nbytes)
+                    eng.synchronize()
+                    t1 = time.perf_counter()
+                    eng.nms_device(d_pred, 64, 84, A, 0.25, 0.45, 300, 0, d_rows, d_keep, d_cnt)
+                    eng.synchronize()
+                    times.append(time.perf_counter() - t1)
+                tn = float(np.median(times[1:]))
+                out["nms"] = {"boxes_per_s": round(ncand / tn, 1), "candidates": ncand, "ms": round(tn * 1e3, 3),
+                              "shape": [64, 84, A], "conf": 0.25, "iou": 0.45}
+            if world == 1 and not args.no_cpu_baseline:
+                out["cpu_baseline"] = cpu_baseline(nc, H, W, sample_b=args.cpu_batch, nms_pred=nms_pred_host)
+            else:
+                out["cpu_baseline"] = None
         # the JSON line must be the LAST line of rank 0's stdout: libraries (RCCL prints "Librccl path : ..." through C stdio,
         # block-buffered when piped) would otherwise land after it at exit.  Flush C stdio first, print, then close fd 1.
         try:

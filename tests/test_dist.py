@@ -330,11 +330,12 @@ def test_c_abi_rccl_world1():
 @pytest.mark.gpu
 def test_bench_force_dist_world1():
     """bench.py's torch.distributed (RCCL) code path -- engine on torch's stream, GradSync over the segmented backward -- executed
-    on the GPU box with a one-rank process group; the JSON contract line must come out and agree with a plain run's loss."""
+    on the GPU box with a one-rank process group; the JSON contract line must come out and agree with a plain run's loss.  --full: the line
+    carries the roofline of the profile steps and the `dist` split checked below."""
     import json
     import subprocess
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_free_port()), RANK="0", LOCAL_RANK="0", WORLD_SIZE="1")
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--batch", "8", "--no-cpu-baseline", "--no-nms", "--no-infer"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--batch", "8", "--full", "--no-cpu-baseline", "--no-nms", "--no-infer"]
     outs = []
     for extra in (["--force-dist"], [], ["--force-dist", "--dist-backend", "c"]):
         r = subprocess.run(cmd + extra, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)

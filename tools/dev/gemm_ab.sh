@@ -1,9 +1,9 @@
 #!/bin/bash
 # A/B of the blocked-GEMM convolution kernel (YS_NO_GEMM=1 = previous kernels) on the wide-layer configurations + the headline one
-mkdir -p gpurun_out/gemm
+O=${TRIAGE_OUT:-triage_out}/gemm; mkdir -p $O
 run() { # name, env, args
-  env $2 python bench.py --steps 6 --warmup 3 --no-cpu-baseline --no-nms --no-infer $3 --dump-launches gpurun_out/gemm/l_$1.csv 2>gpurun_out/gemm/$1.err | tail -1 > gpurun_out/gemm/$1.json
-  python -c "import sys,json; d=json.loads(open('gpurun_out/gemm/$1.json').read()); print('$1', d['value'], d['ms_per_step'], d['roofline']['class_ms_per_step'], d['loss_items'])"
+  env $2 python bench.py --full --steps 6 --warmup 3 --no-cpu-baseline --no-nms --no-infer $3 --dump-launches $O/l_$1.csv 2>$O/$1.err | tail -1 > $O/$1.json
+  python -c "import sys,json; d=json.loads(open('$O/$1.json').read()); print('$1', d['value'], d['ms_per_step'], d['roofline']['class_ms_per_step'], d['loss_items'])"
 }
 run c5_gemm "A=1" "--size x --imgsz 1280 --batch 16"
 run c5_old "YS_NO_GEMM=1" "--size x --imgsz 1280 --batch 16"

@@ -1,11 +1,11 @@
 #!/bin/bash
 # usage: knob_sweep.sh "ENV1=.. ENV2=.." ...   -> per config: step ms + class ms + a few key layers
-mkdir -p gpurun_out/r2/sweep
+O=${TRIAGE_OUT:-triage_out}/sweep; mkdir -p $O
 i=0
 for cfg in "$@"; do
   i=$((i+1))
-  env $cfg python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-nms --no-infer --dump-launches gpurun_out/r2/sweep/l_$i.csv > gpurun_out/r2/sweep/b_$i.json 2>/dev/null
-  python - "$cfg" gpurun_out/r2/sweep/b_$i.json gpurun_out/r2/sweep/l_$i.csv <<'PY'
+  env $cfg python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-nms --no-infer --dump-launches $O/l_$i.csv > $O/b_$i.json 2>/dev/null
+  python - "$cfg" $O/b_$i.json $O/l_$i.csv <<'PY'
 import sys, json, csv, collections, re
 cfg, bj, lc = sys.argv[1:4]
 d = json.loads(open(bj).read().strip().splitlines()[-1])

@@ -1,9 +1,9 @@
 #!/bin/bash
 # A/B of the blocked-GEMM wgrad kernel: YS_NO_WGEMM=1 = previous kernels; K-tile and workgroups-per-CU variants
-mkdir -p gpurun_out/wgemm
+O=${TRIAGE_OUT:-triage_out}/wgemm; mkdir -p $O
 run() { # name, env, args
-  env $2 python bench.py --steps 6 --warmup 3 --no-cpu-baseline --no-nms --no-infer $3 --dump-launches gpurun_out/wgemm/l_$1.csv 2>gpurun_out/wgemm/$1.err | tail -1 > gpurun_out/wgemm/$1.json
-  python -c "import sys,json; d=json.loads(open('gpurun_out/wgemm/$1.json').read()); print('$1', d['value'], d['ms_per_step'], d['roofline']['class_ms_per_step'], d['loss_items'])"
+  env $2 python bench.py --full --steps 6 --warmup 3 --no-cpu-baseline --no-nms --no-infer $3 --dump-launches $O/l_$1.csv 2>$O/$1.err | tail -1 > $O/$1.json
+  python -c "import sys,json; d=json.loads(open('$O/$1.json').read()); print('$1', d['value'], d['ms_per_step'], d['roofline']['class_ms_per_step'], d['loss_items'])"
 }
 C5="--size x --imgsz 1280 --batch 16"
 run c5_new "A=1" "$C5"
