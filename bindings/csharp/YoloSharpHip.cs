@@ -12,7 +12,7 @@ namespace YoloSharp.Native
     internal struct YsHeadDesc
     {
         public int family;     // 8 = Detect(legacy), 11 = depthwise + 1x1 class tower (Modules/Head.cs:50)
-        public int task;       // 0 Detect, 1 Segment, 2 Obb, 3 Pose
+        public int task;       // 0 Detect, 1 Segment, 2 Obb, 3 Pose, 4 Classify (ch[0] = c1 of one [height/32, width/32] map)
         public int nc, reg_max;
         [MarshalAs(UnmanagedType.ByValArray, SizeConst = 3)] public int[] ch;   // channels of P3, P4, P5
         public int height, width;   // input IMAGE size; level i sees [height / s_i, width / s_i], s = 8, 16, 32 (Head.cs:43)
@@ -24,7 +24,7 @@ namespace YoloSharp.Native
     {
         public int family;     // 8 = Yolov8 (Models/Yolo.cs:10), 11 = Yolov11
         public int size;       // YoloSize n,s,m,l,x = 0..4 (Types/YoloTypes.cs)
-        public int task;       // 0 detect, 1 segment, 2 obb, 3 pose
+        public int task;       // 0 detect, 1 segment, 2 obb, 3 pose, 4 classify (Yolov8Classify / Yolov11Classify; Float32 or BFloat16)
         public int nc, reg_max, height, width, max_batch;
         public int dtype;      // 0 = Float32 (parity path), 1 = BFloat16 (performance path), 2 = bf16 + fp8 MFMA convolutions
         public int max_labels; // INITIAL ground-truth capacity per image (0 -> 64); host-label loss calls grow it, see ys_model_reserve_labels
@@ -68,6 +68,10 @@ namespace YoloSharp.Native
         // Augment.LetterBox / Augment.Rectangle (Data/Augment.cs:698-857) on the device; uint8 planes (isFloat = 0) or fp32 masks
         [DllImport(Lib)] internal static extern int ys_letterbox(IntPtr ctx, byte[] src, int isFloat, int onDevice, int C, int h, int w, int fitW, int fitH,
                                                                  int outW, int outH, int color, [Out] byte[] dst, out int padL, out int padU);
+        // Classify task (Head.Classify / v8ClassificationLoss / Classifier.Val, Models/Classifier.cs): outputs "cls" / "logits" / "dcls" [B,nc]
+        // through ys_model_get_output; one loss item (the mean) through ys_loss_read_items
+        [DllImport(Lib)] internal static extern int ys_loss_classify(IntPtr model, float[] cls, int batch, int onDevice);
+        [DllImport(Lib)] internal static extern int ys_cls_topk(IntPtr ctx, float[] scores, int onDevice, int rows, int cols, int k, [Out] int[] idx);
         // Obb / Pose tasks (Head.Obb / v8OBBLoss, Head.Pose / v8PoseLoss)
         [DllImport(Lib)] internal static extern int ys_loss_obb(IntPtr model, float[] batchIdx, float[] cls, float[] bboxes5, int n, int onDevice);
         [DllImport(Lib)] internal static extern int ys_loss_pose(IntPtr model, float[] batchIdx, float[] cls, float[] bboxes, int n, float[] keypoints, int onDevice);

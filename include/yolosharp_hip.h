@@ -41,7 +41,12 @@ enum ys_status {
 enum ys_dtype { YS_F32 = 0, YS_BF16 = 1, YS_FP8 = 2 };
 enum ys_family { YS_YOLOV8 = 8, YS_YOLOV11 = 11 };   /* Models/Yolo.cs:10-135, :200-258 */
 enum ys_size { YS_N = 0, YS_S = 1, YS_M = 2, YS_L = 3, YS_X = 4 }; /* Types/YoloTypes.cs YoloSize; Yolo.cs:43-51 */
-enum ys_task { YS_DETECT = 0, YS_SEGMENT = 1, YS_OBB = 2, YS_POSE = 3 };   /* Config.cs TaskType */
+enum ys_task { YS_DETECT = 0, YS_SEGMENT = 1, YS_OBB = 2, YS_POSE = 3,
+               YS_CLASSIFY = 4 };   /* Config.cs TaskType.  YS_CLASSIFY: Yolov8Classify / Yolov11Classify (Models/Yolo.cs:537-573),
+                                       the Yolov8 list without its last 14 modules (model.0-8, no SPPF) / the Yolov11 list without its last
+                                       13 (model.0-10) + Head.Classify (Modules/Head.cs:612-644) as model.9 / model.11: Conv(c1, 1280, 1),
+                                       AdaptiveAvgPool2d(1), flatten, Dropout(0), Linear(1280, nc).  YS_F32 and YS_BF16 only (YS_FP8 is
+                                       refused with YS_ERR_UNSUPPORTED); reg_max is not used */
 
 YS_API const char* ys_last_error(void);
 YS_API int ys_version(void);
@@ -93,7 +98,7 @@ YS_API int ys_model_get_grad(ys_model* m, const char* name, float* host, size_t 
  * biases, BN gamma=1 beta=0, running stats 0/1) from a 64-bit seed (deterministic, host-side). */
 YS_API int ys_model_init_weights(ys_model* m, uint64_t seed);
 YS_API int ys_model_set_training(ys_model* m, int training);   /* Module.train()/eval() */
-YS_API int ys_model_num_anchors(ys_model* m);                  /* A = sum_l (H/s_l)(W/s_l) */
+YS_API int ys_model_num_anchors(ys_model* m);                  /* A = sum_l (H/s_l)(W/s_l); 0 for a classify model */
 YS_API int64_t ys_model_num_params(ys_model* m);
 
 /* Yolov8.forward (Yolo.cs:92-134).  images: fp32 NCHW [B,3,H,W] in [0,1].
@@ -107,6 +112,9 @@ YS_API int ys_model_forward_u8(ys_model* m, const uint8_t* images, int on_device
  * Segment models (Head.cs:283-313) add "mask_coefficient" [B,nm,A] and "proto" [B,nm,H/4,W/4], and their eval
  * "pred" is [B,4+nc+nm,A] (raw mask coefficients appended).  "dboxes" | "dscores" | "dmask_coefficient" | "dproto"
  * return the loss gradients w.r.t. those outputs after a loss call. */
+/* Classify models (Head.cs:635-643) have their own keys, all [B, nc]: "cls" = the logits after a training forward, softmax(logits, 1)
+ * after an eval forward; "logits" = the logits in both modes; "dcls" = d(loss)/d(logits) after ys_loss_classify.  Every other key
+ * is refused on a classify model (YS_ERR_INVALID_ARG), and these keys on the other tasks. */
 YS_API int ys_model_get_output(ys_model* m, const char* key, float* host, size_t count);
 /* The criterion's `preds` argument supplied by the caller (Utils/Loss.cs:411 `forward(preds, batch)`): host fp32 head outputs in the
  * reference layout -- boxes [B,4*reg_max,A], scores [B,nc,A], and for Segment models mask_coefficient [B,nm,A] + proto
@@ -115,7 +123,7 @@ YS_API int ys_model_get_output(ys_model* m, const char* key, float* host, size_t
  * is refused (there is no graph state behind such preds). */
 YS_API int ys_model_set_preds(ys_model* m, int batch, const float* boxes, const float* scores,
                               const float* mask_coefficient, const float* proto);
-/* Device pointer of the eval prediction [B,4+nc,A] fp32 (input of ys_nms_batched). */
+/* Device pointer of the eval prediction [B,4+nc,A] fp32 (input of ys_nms_batched); classify models: the eval probabilities [B,nc]. */
 YS_API int ys_model_pred_device(ys_model* m, float** dptr);
 
 /* v8DetectionLoss.forward (Utils/Loss.cs:411-484) + TaskAlignedAssigner (Utils/Tal.cs:13-258)
@@ -160,10 +168,16 @@ YS_API int ys_loss_obb(ys_model* m, const float* batch_idx, const float* cls, co
  * [B, nk, A] in the mask_coefficient argument; ys_model_get_output("dkpts") returns the gradient. */
 YS_API int ys_loss_pose(ys_model* m, const float* batch_idx, const float* cls, const float* bboxes,
                         int n_labels, const float* keypoints, int on_device);
-/* Loss items in the criterion's own order: detect n_items = 3 (box, cls, dfl; Loss.cs:414);
+/* v8ClassificationLoss.forward (Utils/Loss.cs:1073-1091) for task = YS_CLASSIFY models: cross_entropy(preds["cls"], batch["cls"].view(-1))
+ * with mean reduction -- NOT multiplied by the batch size, unlike the detection losses -- and d(loss)/d(logits) = (softmax - onehot) / B.
+ * cls: fp32 class ids [batch]; batch must equal the last forward's.  Works after a training forward (the step) and after an eval forward
+ * (Classifier.Val's loss, Models/Classifier.cs:90-93).  A host label outside [0, nc) (or not integral) is refused at once with
+ * YS_ERR_INVALID_ARG; device labels are checked on the device and the refusal comes from ys_loss_read_items.  Other tasks: refused. */
+YS_API int ys_loss_classify(ys_model* m, const float* cls, int batch, int on_device);
+/* Loss items in the criterion's own order: detect n_items = 3 (box, cls, dfl; Loss.cs:414); classify n_items = 1 (Loss.cs:1088);
  * segment n_items = 5 (box, seg, cls, dfl, semseg = 0; Loss.cs:719); pose n_items = 5 (box, pose, kobj, cls, dfl; Loss.cs:923);
  * obb n_items = 4 (box, cls, dfl, angle; Loss.cs:546).
- * *loss_sum = sum(items)*B. */
+ * *loss_sum = sum(items)*B (classify: the mean loss itself, the scalar the reference calls backward() on). */
 YS_API int ys_loss_read_items(ys_model* m, float* loss_items, int n_items, float* loss_sum);
 
 /* autograd backward of sum(loss*B) through the whole graph (Amp.cs:348,370). Gradients accumulate
@@ -284,6 +298,11 @@ YS_API int ys_kpt_iou(ys_ctx* ctx, const float* kpt1, int n, const float* kpt2, 
 YS_API int ys_match_predictions(ys_ctx* ctx, const float* pred_cls, int n, const float* true_cls, int nl, const float* iou,
                                 int on_device, uint8_t* correct);
 
+/* Classifier.Val's ranking (Models/Classifier.cs:95-100: softmax scores argsort descending, first 5): idx[rows, k] int32 = the indices
+ * of the k largest scores of each row of scores[rows, cols] fp32, in descending order; ties go to the lower index, NaN scores are never
+ * picked (-1 fills a row with fewer than k comparable entries).  1 <= k <= min(16, cols).  `on_device` applies to scores and idx. */
+YS_API int ys_cls_topk(ys_ctx* ctx, const float* scores, int on_device, int rows, int cols, int k, int32_t* idx);
+
 /* Ops.process_mask (Utils/Ops.cs:462-489), used by Segmenter post-processing (Models/Segmenter.cs:131-160 region):
  * masks = masks_in[n,nm] @ protos[nm,mh,mw], cropped to boxes (xyxy, image pixels) scaled to the mask grid,
  * optionally bilinearly upsampled (align_corners = false) to (ih, iw), thresholded > 0.
@@ -356,7 +375,7 @@ YS_API int ys_block_forward(ys_model* block, const float* x_nchw, int on_device,
 YS_API int ys_block_backward(ys_model* block, const float* dy_nchw, int on_device, float* dx_nchw);
 
 /* ---- the heads as standalone modules (Detect / Segment handles; round 3).
- * Modules/Head.cs:8-236 Detect, :238-374 Segment, :376-482 Obb, :484-606 Pose: the three neck feature maps in, the criterion's
+ * Modules/Head.cs:8-236 Detect, :238-374 Segment, :376-482 Obb, :484-606 Pose, :612-644 Classify: the three neck feature maps in, the criterion's
  * `preds` (training) / the decoded predictions (eval) out.  The handle is a ys_model without a backbone: the state_dict surface
  * (module-relative names "cv2.0.0.conv.weight", "cv3...", "dfl.conv.weight", "proto...", "cv4..."; Head.cs registration order),
  * ys_model_set_training, ys_model_get_output ("boxes", "scores", "pred", "mask_coefficient", "proto", "kpts", "angle" and their
@@ -365,16 +384,18 @@ typedef struct ys_head_desc {
   int32_t family;        /* ys_family: YS_YOLOV8 = Detect(legacy: 3x3 cls tower), YS_YOLOV11 = depthwise + 1x1 cls tower (Head.cs:50) */
   int32_t task;          /* ys_task: which head */
   int32_t nc, reg_max;
-  int32_t ch[3];         /* channels of P3, P4, P5 (multiples of 4 for f32, 8 for bf16) */
+  int32_t ch[3];         /* channels of P3, P4, P5 (multiples of 4 for f32, 8 for bf16).  YS_CLASSIFY: ch[0] = c1, ch[1] / ch[2] ignored */
   int32_t height, width; /* INPUT IMAGE size (multiple of 32): level i sees [height / s_i, width / s_i], s = 8, 16, 32 (Head.cs:43) */
   int32_t max_batch, dtype;
   int32_t kpt_num, kpt_dim;   /* YS_POSE (0 = 17 x 3) */
 } ys_head_desc;
 YS_API int ys_head_create(ys_ctx* ctx, const ys_head_desc* desc, ys_model** out);
-/* x[i]: fp32 NCHW [batch, ch[i], height / s_i, width / s_i], host arrays (on_device = 0) or device pointers (1) */
+/* x[i]: fp32 NCHW [batch, ch[i], height / s_i, width / s_i], host arrays (on_device = 0) or device pointers (1).
+ * YS_CLASSIFY: x[0] only, [batch, c1, height / 32, width / 32]; the head's outputs are ys_model_get_output's "cls" / "logits". */
 YS_API int ys_head_forward(ys_model* head, const float* const x[3], int on_device, int batch);
 /* Gradients of the head outputs supplied by the caller instead of a ys_loss_* call: [B, 4*reg_max, A], [B, nc, A], the task's
- * extra output ([B, nm | 1 | nk, A]; NULL for Detect) and the prototypes ([B, nm, mh, mw]; Segment only); fp32 host arrays. */
+ * extra output ([B, nm | 1 | nk, A]; NULL for Detect) and the prototypes ([B, nm, mh, mw]; Segment only); fp32 host arrays.
+ * YS_CLASSIFY: dscores = d(loss)/d(logits) [B, nc]; the other three are ignored. */
 YS_API int ys_head_set_grads(ys_model* head, const float* dboxes, const float* dscores, const float* dextra, const float* dproto);
 /* autograd of the last training-mode ys_head_forward from the gradients the criterion (or ys_head_set_grads) left on the head outputs:
  * accumulates the parameter gradients and writes dx[i] (shape of x[i]; entries / the array may be NULL). */

@@ -72,9 +72,11 @@ struct ConvL {
   int stage = -1, group = -1;
   long gstat_off = -1;                   // floats into ys_model::stat_group
   void* dy_own = nullptr;
+  bool linear = false;     // Classify's Linear(1280, nc) run as a 1x1 convolution on a 1 x 1 map (M = B): state_dict weight [nc, 1280]
+  bool pool_next = false;  // Classify's Conv unit: in training its BN + SiLU apply is left to the pool op that follows (OP_POOL reads y)
 };
 
-enum OpType { OP_CONV = 0, OP_MAXPOOL = 1, OP_UPSAMPLE = 2, OP_ATTN = 3, OP_VCOPY = 4, OP_COPY = 5 };
+enum OpType { OP_CONV = 0, OP_MAXPOOL = 1, OP_UPSAMPLE = 2, OP_ATTN = 3, OP_VCOPY = 4, OP_COPY = 5, OP_POOL = 6 };   // OP_POOL: Classify's AdaptiveAvgPool2d(1) (op.conv = its Conv unit)
 struct Op { int type; int conv = -1; View in, out; int H = 0, W = 0; long aux_off = 0; int seg = 0; int heads = 0, kd = 0, hd = 0; };
 
 struct TensorRec {
@@ -118,6 +120,9 @@ struct ys_model {
   bool is_block = false; int blk_out = -1, blk_c1 = 3, blk_c2 = 0;   // standalone block handle (ys_block_create)
   bool is_head = false; int head_in[3] = {-1, -1, -1}, head_ch[3] = {0, 0, 0};   // standalone head handle (ys_head_create): P3 / P4 / P5 input buffers
   int ld_pd = 0, ld_ps = 0;
+  // Classify (Head.cs:612-644): pooled [B][1280] and logits [B][ld_cls] buffers (1 x 1 maps), per-row losses + invalid-label flags [2B]
+  bool cls = false; int cls_conv = -1, pool_buf = -1, logit_buf = -1, ld_cls = 0;
+  float *cls_rows = nullptr, *cls_lab = nullptr;
   // flat fp32 parameter state
   long n_params = 0, n_params_real = 0;          // flat length incl. the zero rows of padded towers / the reference's parameter count
   float *params = nullptr, *grads = nullptr, *adam_m = nullptr, *adam_v = nullptr;
@@ -518,29 +523,88 @@ int add_detect(ys_model* m, const std::string& hp, const int* pv, const int* ch,
   return YS_OK;
 }
 
-int build_v8_detect(ys_model* m) {
-  const ys_model_desc& d = m->d;
+// Classify (Head.cs:612-644): Conv(c1, 1280, 1) -> AdaptiveAvgPool2d(1) -> flatten -> Dropout(0) -> Linear(1280, nc), all in segment `seg`.
+// The pool is an op of its own (OP_POOL); in training it also applies the Conv unit's BN + SiLU, so the activated 1280-channel map is never
+// written.  Linear is a plain 1x1 convolution with bias on a 1 x 1 map: M = B rows, nc output channels padded to the 16-byte unit like the
+// Detect class towers -- its forward, weight / input gradients, weight shadows and optimizer groups are the convolution machinery's.
+int add_classify(ys_model* m, const std::string& hp, View in, int c1, int H, int W, int seg) {
+  const int c_ = 1280;   // efficientnet_b0 size (Head.cs:622)
+  m->cls = true; m->n_items = 1; m->head_prefix = hp; m->nl = 0; m->A = 0;
+  m->ld_cls = (m->d.nc + m->epl - 1) / m->epl * m->epl;
+  const int cb = new_buf(m, H, W, c_);
+  m->bufs[cb].need_grad = false;   // its gradient dpooled / HW is never materialised (run_conv_bwd, pool_next)
+  m->pool_buf = new_buf(m, 1, 1, c_);
+  m->logit_buf = new_buf(m, 1, 1, m->ld_cls);
+  m->cls_conv = add_conv_reg(m, hp + ".conv", in, View{cb, 0, c_}, c1, c_, 1, 1, true, true, H, W, seg);
+  m->convs[m->cls_conv].pool_next = true;
+  { Op op; op.type = OP_POOL; op.conv = m->cls_conv; op.in = View{cb, 0, c_}; op.out = View{m->pool_buf, 0, c_}; op.H = H; op.W = W; op.seg = seg; m->ops.push_back(op); }
+  const int li = add_conv_reg(m, hp + ".linear", View{m->pool_buf, 0, c_}, View{m->logit_buf, 0, m->d.nc}, c_, m->d.nc, 1, 1, false, false, 1, 1, seg);
+  m->convs[li].linear = true;
+  return YS_OK;
+}
+
+// ---- size tables (Yolo.cs:43-55 / :200-215), shared by the detect and classify graphs
+static int v8_widths(ys_model* m, int w[5], int dep[3]) {
   static const float dm[5] = {0.34f, 0.34f, 0.67f, 1.0f, 1.0f};
   static const float wm[5] = {0.25f, 0.5f, 0.75f, 1.0f, 1.25f};
   static const int mc[5] = {1024, 1024, 576, 512, 640};
   const int base_w[5] = {64, 128, 256, 512, 1024};
-  int w[5];
-  for (int i = 0; i < 5; i++) w[i] = std::min((int)(base_w[i] * wm[d.size]), mc[d.size]);   // Yolo.cs:53
-  const int dep[3] = {(int)(3 * dm[d.size]), (int)(6 * dm[d.size]), (int)(9 * dm[d.size])};  // Yolo.cs:54
-  const int H = d.height, W = d.width;
-  const int H2 = H / 2, W2 = W / 2, H4 = H / 4, W4 = W / 4, H8 = H / 8, W8 = W / 8, H16 = H / 16, W16 = W / 16, H32 = H / 32, W32 = W / 32;
+  const int sz = m->d.size;
+  for (int i = 0; i < 5; i++) w[i] = std::min((int)(base_w[i] * wm[sz]), mc[sz]);   // Yolo.cs:53
+  dep[0] = (int)(3 * dm[sz]); dep[1] = (int)(6 * dm[sz]); dep[2] = (int)(9 * dm[sz]);   // Yolo.cs:54
   for (int i = 0; i < 5; i++)
     if (w[i] % m->epl || ((int)(w[i] * 0.5f)) % m->epl) { ys_set_error("model: width %d not a multiple of %d", w[i], m->epl); return YS_ERR_UNSUPPORTED; }
+  return YS_OK;
+}
 
-  m->in_buf = new_buf(m, H, W, m->epl);
+static void new_input_buf(ys_model* m) {
+  m->in_buf = new_buf(m, m->d.height, m->d.width, m->epl);
   m->bufs[m->in_buf].need_grad = false;
+}
+
+// Yolov8 model.0 - model.8 (Yolo.cs:56-66) from the input buffer; model.4 / model.6 / model.8 write the given views.  Backward segments:
+// s04 for model.0-4, s56 for model.5-6, s78 for model.7-8
+static void v8_backbone(ys_model* m, const int* w, const int* dep, View v4, View v6, View v8, int s04, int s56, int s78) {
+  const int H = m->d.height, W = m->d.width;
+  const int H2 = H / 2, W2 = W / 2, H4 = H / 4, W4 = W / 4, H8 = H / 8, W8 = W / 8, H16 = H / 16, W16 = W / 16, H32 = H / 32, W32 = W / 32;
+  const int b0 = new_buf(m, H2, W2, w[0]), b1 = new_buf(m, H4, W4, w[1]), b2 = new_buf(m, H4, W4, w[1]);
+  const int b3 = new_buf(m, H8, W8, w[2]), b5 = new_buf(m, H16, W16, w[3]), b7 = new_buf(m, H32, W32, w[4]);
+  int ci = add_conv_reg(m, "model.0", View{m->in_buf, 0, m->epl}, View{b0, 0, w[0]}, 3, w[0], 3, 2, true, true, H, W, s04);
+  m->convs[ci].first = true;
+  add_conv_reg(m, "model.1", View{b0, 0, w[0]}, View{b1, 0, w[1]}, w[0], w[1], 3, 2, true, true, H2, W2, s04);
+  add_c2f(m, "model.2", View{b1, 0, w[1]}, View{b2, 0, w[1]}, w[1], w[1], dep[0], true, H4, W4, s04);
+  add_conv_reg(m, "model.3", View{b2, 0, w[1]}, View{b3, 0, w[2]}, w[1], w[2], 3, 2, true, true, H4, W4, s04);
+  add_c2f(m, "model.4", View{b3, 0, w[2]}, v4, w[2], w[2], dep[1], true, H8, W8, s04);
+  add_conv_reg(m, "model.5", v4, View{b5, 0, w[3]}, w[2], w[3], 3, 2, true, true, H8, W8, s56);
+  add_c2f(m, "model.6", View{b5, 0, w[3]}, v6, w[3], w[3], dep[1], true, H16, W16, s56);
+  add_conv_reg(m, "model.7", v6, View{b7, 0, w[4]}, w[3], w[4], 3, 2, true, true, H16, W16, s78);
+  add_c2f(m, "model.8", View{b7, 0, w[4]}, v8, w[4], w[4], dep[0], true, H32, W32, s78);
+}
+
+// Yolov8Classify (Yolo.cs:537-554): the Yolov8 list without its last 14 modules -- model.0 - model.8, no SPPF -- then Classify(widths[4], nc)
+int build_v8_classify(ys_model* m) {
+  int w[5], dep[3];
+  YS_TRY(v8_widths(m, w, dep));
+  const int H8 = m->d.height / 8, W8 = m->d.width / 8, H16 = m->d.height / 16, W16 = m->d.width / 16, H32 = m->d.height / 32, W32 = m->d.width / 32;
+  new_input_buf(m);
+  const int b4 = new_buf(m, H8, W8, w[2]), b6 = new_buf(m, H16, W16, w[3]), b8 = new_buf(m, H32, W32, w[4]);
+  // backward segments: head (1280-channel Conv, pool, Linear), model.7-8, model.5-6, stem (model.0-4)
+  v8_backbone(m, w, dep, View{b4, 0, w[2]}, View{b6, 0, w[3]}, View{b8, 0, w[4]}, 3, 2, 1);
+  return add_classify(m, "model.9", View{b8, 0, w[4]}, w[4], H32, W32, 0);
+}
+
+int build_v8_detect(ys_model* m) {
+  const ys_model_desc& d = m->d;
+  int w[5], dep[3];
+  YS_TRY(v8_widths(m, w, dep));
+  const int H = d.height, W = d.width;
+  const int H8 = H / 8, W8 = W / 8, H16 = H / 16, W16 = W / 16, H32 = H / 32, W32 = W / 32;
+  new_input_buf(m);
   // concat buffers of the neck (Yolo.cs:70-84; concat order [x, skip], Yolo.cs:107)
   const int cat11 = new_buf(m, H16, W16, w[4] + w[3]);
   const int cat14 = new_buf(m, H8, W8, w[3] + w[2]);
   const int cat17 = new_buf(m, H16, W16, w[2] + w[3]);
   const int cat20 = new_buf(m, H32, W32, w[3] + w[4]);
-  const int b0 = new_buf(m, H2, W2, w[0]), b1 = new_buf(m, H4, W4, w[1]), b2 = new_buf(m, H4, W4, w[1]);
-  const int b3 = new_buf(m, H8, W8, w[2]), b5 = new_buf(m, H16, W16, w[3]), b7 = new_buf(m, H32, W32, w[4]);
   const int b8 = new_buf(m, H32, W32, w[4]);
   const int b15 = new_buf(m, H8, W8, w[2]), b18 = new_buf(m, H16, W16, w[3]), b21 = new_buf(m, H32, W32, w[4]);
   const View v4{cat14, w[3], w[2]}, v6{cat11, w[4], w[3]}, v9{cat20, w[3], w[4]}, v12{cat17, w[2], w[3]};
@@ -548,16 +612,7 @@ int build_v8_detect(ys_model* m) {
   // backward left to hide behind, so it should be the smallest (model.0-4: 2.5 % of YOLOv8n's parameters, 4 % of YOLOv8s')
   const int SB = 2, SN = 1, SH = 0, SS = 3;
 
-  int ci = add_conv_reg(m, "model.0", View{m->in_buf, 0, m->epl}, View{b0, 0, w[0]}, 3, w[0], 3, 2, true, true, H, W, SS);
-  m->convs[ci].first = true;
-  add_conv_reg(m, "model.1", View{b0, 0, w[0]}, View{b1, 0, w[1]}, w[0], w[1], 3, 2, true, true, H2, W2, SS);
-  add_c2f(m, "model.2", View{b1, 0, w[1]}, View{b2, 0, w[1]}, w[1], w[1], dep[0], true, H4, W4, SS);
-  add_conv_reg(m, "model.3", View{b2, 0, w[1]}, View{b3, 0, w[2]}, w[1], w[2], 3, 2, true, true, H4, W4, SS);
-  add_c2f(m, "model.4", View{b3, 0, w[2]}, v4, w[2], w[2], dep[1], true, H8, W8, SS);
-  add_conv_reg(m, "model.5", v4, View{b5, 0, w[3]}, w[2], w[3], 3, 2, true, true, H8, W8, SB);
-  add_c2f(m, "model.6", View{b5, 0, w[3]}, v6, w[3], w[3], dep[1], true, H16, W16, SB);
-  add_conv_reg(m, "model.7", v6, View{b7, 0, w[4]}, w[3], w[4], 3, 2, true, true, H16, W16, SB);
-  add_c2f(m, "model.8", View{b7, 0, w[4]}, View{b8, 0, w[4]}, w[4], w[4], dep[0], true, H32, W32, SB);
+  v8_backbone(m, w, dep, v4, v6, View{b8, 0, w[4]}, SS, SB, SB);
   add_sppf(m, "model.9", View{b8, 0, w[4]}, v9, w[4], H32, W32, SB);
   { Op op; op.type = OP_UPSAMPLE; op.in = v9; op.out = View{cat11, 0, w[4]}; op.H = H32; op.W = W32; op.seg = SN; m->ops.push_back(op); }
   add_c2f(m, "model.12", View{cat11, 0, w[4] + w[3]}, v12, w[4] + w[3], w[3], dep[0], false, H16, W16, SN);
@@ -574,36 +629,33 @@ int build_v8_detect(ys_model* m) {
 }
 
 // Yolov11 detect (Yolo.cs:200-258): C3k2 backbone/neck (shortcut=true everywhere: C3k2's default), SPPF, C2PSA, Detect(legacy=false)
-int build_v11_detect(ys_model* m) {
-  const ys_model_desc& d = m->d;
+static int v11_widths(ys_model* m, int w[5], int* n, bool* uc) {
   static const float dm[5] = {0.5f, 0.5f, 0.5f, 1.0f, 1.0f};
   static const float wm[5] = {0.25f, 0.5f, 1.0f, 1.0f, 1.5f};
   static const int mc[5] = {1024, 1024, 512, 512, 768};
   static const bool c3k_sz[5] = {false, false, true, true, true};
   const int base_w[5] = {64, 128, 256, 512, 1024};
-  int w[5];
-  for (int i = 0; i < 5; i++) w[i] = std::min((int)(base_w[i] * wm[d.size]), mc[d.size]);
-  const int n = (int)(2 * dm[d.size]);
-  const bool uc = c3k_sz[d.size];
-  const int H = d.height, W = d.width;
-  const int H2 = H / 2, W2 = W / 2, H4 = H / 4, W4 = W / 4, H8 = H / 8, W8 = W / 8, H16 = H / 16, W16 = W / 16, H32 = H / 32, W32 = W / 32;
+  const int sz = m->d.size;
+  for (int i = 0; i < 5; i++) w[i] = std::min((int)(base_w[i] * wm[sz]), mc[sz]);
+  *n = (int)(2 * dm[sz]);
+  *uc = c3k_sz[sz];
   if (((int)(w[2] * 0.25f) / 2) % m->epl) {
-    ys_set_error("model: YOLOv11 size %d needs hidden widths that are multiples of %d (use the f32 model for n)", d.size, m->epl);
+    ys_set_error("model: YOLOv11 size %d needs hidden widths that are multiples of %d (use the f32 model for n)", sz, m->epl);
     return YS_ERR_UNSUPPORTED;
   }
   if ((w[4] / 2) % 64) { ys_set_error("model: C2PSA needs c %% 64 == 0"); return YS_ERR_UNSUPPORTED; }
-  m->in_buf = new_buf(m, H, W, m->epl);
-  m->bufs[m->in_buf].need_grad = false;
-  const int cat12 = new_buf(m, H16, W16, w[4] + w[3]);   // [up(L10) | L6]
-  const int cat15 = new_buf(m, H8, W8, w[3] + w[3]);     // [up(L13) | L4]
-  const int cat18 = new_buf(m, H16, W16, w[2] + w[3]);   // [L17 | L13]
-  const int cat21 = new_buf(m, H32, W32, w[3] + w[4]);   // [L20 | L10]
+  return YS_OK;
+}
+
+// Yolov11 model.0 - model.10 (Yolo.cs:216-227): C3k2 backbone, SPPF, C2PSA.  model.4 / model.6 / model.10 write the given views;
+// backward segments s04 for model.0-4, s58 for model.5-8, s910 for model.9-10
+static void v11_backbone(ys_model* m, const int* w, int n, bool uc, View v4, View v6, View v10, int s04, int s58, int s910) {
+  const int H = m->d.height, W = m->d.width;
+  const int H2 = H / 2, W2 = W / 2, H4 = H / 4, W4 = W / 4, H8 = H / 8, W8 = W / 8, H16 = H / 16, W16 = W / 16, H32 = H / 32, W32 = W / 32;
+  const int SS = s04, SB = s58;
   const int b0 = new_buf(m, H2, W2, w[0]), b1 = new_buf(m, H4, W4, w[1]), b2 = new_buf(m, H4, W4, w[2]);
   const int b3 = new_buf(m, H8, W8, w[2]), b5 = new_buf(m, H16, W16, w[3]), b7 = new_buf(m, H32, W32, w[4]);
   const int b8 = new_buf(m, H32, W32, w[4]), b9 = new_buf(m, H32, W32, w[4]);
-  const int b16 = new_buf(m, H8, W8, w[2]), b19 = new_buf(m, H16, W16, w[3]), b22 = new_buf(m, H32, W32, w[4]);
-  const View v4{cat15, w[3], w[3]}, v6{cat12, w[4], w[3]}, v10{cat21, w[3], w[4]}, v13{cat18, w[2], w[3]};
-  const int SB = 2, SN = 1, SH = 0, SS = 3;   // stem segment: see build_v8_detect
   int ci = add_conv_reg(m, "model.0", View{m->in_buf, 0, m->epl}, View{b0, 0, w[0]}, 3, w[0], 3, 2, true, true, H, W, SS);
   m->convs[ci].first = true;
   add_conv_reg(m, "model.1", View{b0, 0, w[0]}, View{b1, 0, w[1]}, w[0], w[1], 3, 2, true, true, H2, W2, SS);
@@ -614,8 +666,38 @@ int build_v11_detect(ys_model* m) {
   add_c3k2(m, "model.6", View{b5, 0, w[3]}, v6, w[3], w[3], n, true, 0.5f, H16, W16, SB);
   add_conv_reg(m, "model.7", v6, View{b7, 0, w[4]}, w[3], w[4], 3, 2, true, true, H16, W16, SB);
   add_c3k2(m, "model.8", View{b7, 0, w[4]}, View{b8, 0, w[4]}, w[4], w[4], n, true, 0.5f, H32, W32, SB);
-  add_sppf(m, "model.9", View{b8, 0, w[4]}, View{b9, 0, w[4]}, w[4], H32, W32, SB);
-  add_c2psa(m, "model.10", View{b9, 0, w[4]}, v10, w[4], n, H32, W32, SB);
+  add_sppf(m, "model.9", View{b8, 0, w[4]}, View{b9, 0, w[4]}, w[4], H32, W32, s910);
+  add_c2psa(m, "model.10", View{b9, 0, w[4]}, v10, w[4], n, H32, W32, s910);
+}
+
+// Yolov11Classify (Yolo.cs:556-573): the Yolov11 list without its last 13 modules -- model.0 - model.10, SPPF and C2PSA kept -- then
+// Classify(widths[4], nc) as model.11
+int build_v11_classify(ys_model* m) {
+  int w[5], n; bool uc;
+  YS_TRY(v11_widths(m, w, &n, &uc));
+  const int H8 = m->d.height / 8, W8 = m->d.width / 8, H16 = m->d.height / 16, W16 = m->d.width / 16, H32 = m->d.height / 32, W32 = m->d.width / 32;
+  new_input_buf(m);
+  const int b4 = new_buf(m, H8, W8, w[3]), b6 = new_buf(m, H16, W16, w[3]), b10 = new_buf(m, H32, W32, w[4]);
+  // backward segments: head (1280-channel Conv, pool, Linear), model.9-10, model.5-8, stem (model.0-4)
+  v11_backbone(m, w, n, uc, View{b4, 0, w[3]}, View{b6, 0, w[3]}, View{b10, 0, w[4]}, 3, 2, 1);
+  return add_classify(m, "model.11", View{b10, 0, w[4]}, w[4], H32, W32, 0);
+}
+
+int build_v11_detect(ys_model* m) {
+  int w[5], n; bool uc;
+  YS_TRY(v11_widths(m, w, &n, &uc));
+  const ys_model_desc& d = m->d;
+  const int H = d.height, W = d.width;
+  const int H8 = H / 8, W8 = W / 8, H16 = H / 16, W16 = W / 16, H32 = H / 32, W32 = W / 32;
+  new_input_buf(m);
+  const int cat12 = new_buf(m, H16, W16, w[4] + w[3]);   // [up(L10) | L6]
+  const int cat15 = new_buf(m, H8, W8, w[3] + w[3]);     // [up(L13) | L4]
+  const int cat18 = new_buf(m, H16, W16, w[2] + w[3]);   // [L17 | L13]
+  const int cat21 = new_buf(m, H32, W32, w[3] + w[4]);   // [L20 | L10]
+  const int b16 = new_buf(m, H8, W8, w[2]), b19 = new_buf(m, H16, W16, w[3]), b22 = new_buf(m, H32, W32, w[4]);
+  const View v4{cat15, w[3], w[3]}, v6{cat12, w[4], w[3]}, v10{cat21, w[3], w[4]}, v13{cat18, w[2], w[3]};
+  const int SB = 2, SN = 1, SH = 0, SS = 3;   // stem segment: see build_v8_detect
+  v11_backbone(m, w, n, uc, v4, v6, v10, SS, SB, SB);
   { Op op; op.type = OP_UPSAMPLE; op.in = v10; op.out = View{cat12, 0, w[4]}; op.H = H32; op.W = W32; op.seg = SN; m->ops.push_back(op); }
   add_c3k2(m, "model.13", View{cat12, 0, w[4] + w[3]}, v13, w[4] + w[3], w[3], n, uc, 0.5f, H16, W16, SN);
   { Op op; op.type = OP_UPSAMPLE; op.in = v13; op.out = View{cat15, 0, w[3]}; op.H = H16; op.W = W16; op.seg = SN; m->ops.push_back(op); }
@@ -756,6 +838,7 @@ int layout_params(ys_model* m) {
       add_tensor(m, nm + ".bn.bias", 1, i, c.b_off + r0, {nr}, true);
     } else {
       if (c.ct) add_tensor(m, nm + ".weight", 5, i, c.w_off, {c.cin, c.cout, 2, 2}, true);   // ConvTranspose2d: [Cin][Cout][kh][kw]
+      else if (c.linear) add_tensor(m, nm + ".weight", 0, i, c.w_off + r0 * wrow, {nr, c.cin}, true);   // nn.Linear: [out, in]
       else add_tensor(m, nm + ".weight", 0, i, c.w_off + r0 * wrow, {nr, c.cin, c.k, c.k}, true);
       add_tensor(m, nm + ".bias", 1, i, c.g_off + r0, {nr}, true);
     }
@@ -1218,9 +1301,14 @@ int allocate(ys_model* m) {
   if (!m->red_host.empty()) YS_TRY(dev_alloc(m, (void**)&m->red_dev, m->red_host.size() * sizeof(WgRedDesc)));
   const ys_model_desc& d = m->d;
   YS_TRY(dev_alloc(m, (void**)&m->img_dev, (size_t)B * std::max(3, m->blk_c1) * d.height * d.width * 4));
-  YS_TRY(dev_alloc(m, (void**)&m->pred, (size_t)B * (4 + d.nc + m->nm) * m->A * 4));
+  YS_TRY(dev_alloc(m, (void**)&m->pred, (size_t)B * (m->cls ? d.nc : (4 + d.nc + m->nm) * m->A) * 4));   // Classify: eval probabilities [B][nc]
+  if (m->cls) {
+    YS_TRY(dev_alloc(m, (void**)&m->cls_rows, (size_t)2 * B * 4));
+    YS_TRY(dev_alloc(m, (void**)&m->cls_lab, (size_t)B * 4));
+  }
   m->n_out_stage = std::max((long)B * m->A * std::max(std::max(m->ld_pd, m->ld_ps), 4 + d.nc + m->nm), (long)B * m->mh * m->mw * std::max(m->ld_pr, 1));
   if (m->is_block) { const Buf& ob = m->bufs[m->blk_out]; m->n_out_stage = std::max(m->n_out_stage, (long)B * ob.rows_per_b * ob.ldc); }
+  if (m->cls) m->n_out_stage = std::max(m->n_out_stage, (long)B * m->ld_cls);
   if (m->xkind == 3) {   // v8PoseLoss: foreground list + per-workgroup partials
     YS_TRY(dev_alloc(m, (void**)&m->seg_cnt, (size_t)B * 4));
     YS_TRY(dev_alloc(m, (void**)&m->seg_off, (size_t)(B + 1) * 4));
@@ -1376,7 +1464,8 @@ int run_conv_fwd(ys_model* m, const ConvL& c, int B, const ConvL* next = nullptr
     void* y = (char*)m->y_all + (size_t)c.y_off * m->es;
     a.y = y; a.out_ldc = c.cout; a.out_coff = 0; a.out_bstride = (long)c.Hout * c.Wout; a.vec_ok = (c.cout % 4 == 0);
     a.stats = stat_partial;
-    const bool atomic = m->bn_atomic && c.acc_off >= 0 && !a.f8;
+    // Classify's Conv unit: statistics rows + bn_finalize here, the BN + SiLU apply inside the pool op (OP_POOL) -- no activated map
+    const bool atomic = m->bn_atomic && c.acc_off >= 0 && !a.f8 && !c.pool_next;
     if (atomic) a.stat_acc = m->stat_acc_all + c.acc_off;
     YS_TRY(ys_conv_launch(st, m->dtype, a));
     const void* res = nullptr; int rl = 0, rc = 0;
@@ -1389,6 +1478,7 @@ int run_conv_fwd(ys_model* m, const ConvL& c, int B, const ConvL* next = nullptr
     YS_TRY(ys_bn_finalize_launch(st, stat_partial, gm, c.cout, M, m->params + c.g_off, m->params + c.b_off, 1e-3f, 0.03f,
                                  m->state + c.rm_off, m->state + c.rv_off, m->state + c.nbt_off, chan_ptr(m, c, 0),
                                  chan_ptr(m, c, 1), chan_ptr(m, c, 2), chan_ptr(m, c, 3)));
+    if (c.pool_next) return YS_OK;
     // fp8 mode: the next convolution of the schedule reads exactly this output and will run the fp8 blocked-GEMM kernel -> this pass also writes
     // the e4m3 image it consumes (the consumer's delayed scale) into the scratch and records its maximum
     bool q8_out = false;
@@ -1518,8 +1608,20 @@ int forward_impl(ys_model* m, int B) {
       YS_TRY(ys_attn_v_copy_launch(st, m->dtype, ib.act, ob.act, (long)B * op.H * op.W, ib.ldc, op.heads, op.kd, op.hd, ob.ldc, 0));
     } else if (op.type == OP_COPY) {
       YS_TRY(ys_copy_view_launch(st, m->dtype, ib.act, ib.ldc, op.in.coff, (long)B * op.H * op.W, op.in.C, ob.act, ob.ldc, op.out.coff, 0));
+    } else if (op.type == OP_POOL) {
+      // AdaptiveAvgPool2d(1) + flatten (Head.cs:637): training applies the Conv unit's batch-statistics BN + SiLU to its pre-BN output y on
+      // the way; eval averages the map the folded-BN epilogue wrote
+      const ConvL& c = m->convs[op.conv];
+      const int HW = op.H * op.W;
+      if (m->training)
+        YS_TRY(ys_cls_pool_fwd_launch(st, m->dtype, (char*)m->y_all + (size_t)c.y_off * m->es, c.cout, 0, HW, B, HW, c.cout, chan_ptr(m, c, 0),
+                                      chan_ptr(m, c, 1), c.act ? 1 : 0, ob.act, ob.ldc));
+      else
+        YS_TRY(ys_cls_pool_fwd_launch(st, m->dtype, ib.act, ib.ldc, op.in.coff, ib.rows_per_b, B, HW, op.in.C, nullptr, nullptr, 0, ob.act, ob.ldc));
     }
   }
+  if (!m->training && m->cls)   // Classify eval: inference["cls"] = softmax(logits, 1) (Head.cs:640)
+    YS_TRY(ys_cls_xent_launch(st, m->dtype, m->bufs[m->logit_buf].act, m->ld_cls, B, m->d.nc, nullptr, nullptr, m->pred, nullptr, nullptr));
   if (m->f8) m->f8_sx_valid = true;        // every fp8 candidate has recorded an input maximum (bootstrap pass or its own kernel)
   if (!m->training && m->pd_buf >= 0) {
     YS_TRY(ys_detect_decode_launch(st, m->dtype, m->bufs[m->pd_buf].act, m->ld_pd, m->bufs[m->ps_buf].act, m->ld_ps, B, m->A,
@@ -1830,6 +1932,19 @@ int run_conv_bwd(ys_model* m, ConvL& c, int B) {
     }
     // sum(du), sum(du * y): from the epilogues of the dgrad launches that completed dz (fused BN-backward reduction), else a pass of its own
     const bool fused = c.red_ok && c.red_seen == (int)c.red_src.size() && !c.red_src.empty();
+    if (c.pool_next) {   // Classify: dz = dpooled / HW (OP_POOL) is never materialised -- reduction and apply read the pooled gradient
+      const Buf& pb = m->bufs[m->pool_buf];
+      const int HW = c.Hout * c.Wout;
+      if ((long)B * 2 * c.cout > m->n_stat) { ys_set_error("backward: batch %d too large for the Classify statistics rows", B); return YS_ERR_STATE; }
+      YS_TRY(ys_cls_bn_bwd_reduce_launch(st, m->dtype, pb.grad, pb.ldc, y, B, HW, c.cout, chan_ptr(m, c, 0), chan_ptr(m, c, 1), c.act ? 1 : 0,
+                                         m->stat_partial));
+      YS_TRY(ys_bn_bwd_finalize_launch(st, m->stat_partial, B, c.cout, M, m->grads + c.g_off, m->grads + c.b_off,
+                                       chan_ptr(m, c, 4), chan_ptr(m, c, 5), chan_ptr(m, c, 0), chan_ptr(m, c, 2), chan_ptr(m, c, 3)));
+      void* dyb = (m->overlap && c.dy_own) ? c.dy_own : m->dy_scratch;
+      YS_TRY(ys_cls_bn_bwd_apply_launch(st, m->dtype, pb.grad, pb.ldc, y, B, HW, c.cout, chan_ptr(m, c, 0), chan_ptr(m, c, 1), chan_ptr(m, c, 4),
+                                        chan_ptr(m, c, 5), c.act ? 1 : 0, dyb));
+      dy = dyb; dy_ldc = c.cout; dy_coff = 0;
+    } else {
     c.red_seen = 0;
     void* rg_apply = nullptr;                    // the shortcut's residual-gradient accumulation rides on the reduction pass; without one, on the apply pass
     if (fused) {
@@ -1867,6 +1982,7 @@ int run_conv_bwd(ys_model* m, ConvL& c, int B) {
                                     chan_ptr(m, c, 4), chan_ptr(m, c, 5), c.act ? 1 : 0, dyb, nullptr, rg_apply, rgl, rgc));
     }
     dy = dyb; dy_ldc = c.cout; dy_coff = 0;
+    }
   } else {
     // plain Conv2d with bias (head outputs): dy is the loss gradient itself
     dy = view_ptr(m, ob.grad, ob, c.out_rowoff); dy_ldc = ob.ldc; dy_coff = c.out.coff; dy_bstride = ob.rows_per_b;
@@ -2037,6 +2153,9 @@ int backward_range(ys_model* m, int seg_lo, int seg_hi, bool async_end = false, 
       const int mode = grad_mode(m, op.in);
       if (mode < 0) { ys_set_error("backward: inconsistent gradient slice state at op %d", i); return YS_ERR_STATE; }
       YS_TRY(ys_copy_view_launch(st, m->dtype, ob.grad, ob.ldc, op.out.coff, (long)B * op.H * op.W, op.in.C, ib.grad, ib.ldc, op.in.coff, mode));
+    } else if (op.type == OP_POOL) {
+      // nothing to launch: the Classify Conv unit's BN / SiLU backward (run_conv_bwd, pool_next) reads dpooled itself
+      if (grad_mode(m, op.in) != 0) { ys_set_error("backward: the Classify map has a second gradient writer (op %d)", i); return YS_ERR_STATE; }
     } else {
       const Buf& ib = m->bufs[op.in.buf];
       const Buf& ob = m->bufs[op.out.buf];
@@ -2105,6 +2224,7 @@ void reset_grad_state(ys_model* m) {
   for (auto& b : m->bufs) std::fill(b.gw.begin(), b.gw.end(), 0);
   for (auto& c : m->convs) c.red_seen = 0;
   if (m->is_block) { std::fill(m->bufs[m->blk_out].gw.begin(), m->bufs[m->blk_out].gw.end(), 1); return; }   // the caller's dy
+  if (m->cls) { std::fill(m->bufs[m->logit_buf].gw.begin(), m->bufs[m->logit_buf].gw.end(), 1); return; }   // dlogits (ys_loss_classify)
   // the loss wrote the head gradients
   std::fill(m->bufs[m->pd_buf].gw.begin(), m->bufs[m->pd_buf].gw.end(), 1);
   std::fill(m->bufs[m->ps_buf].gw.begin(), m->bufs[m->ps_buf].gw.end(), 1);
@@ -2134,12 +2254,16 @@ extern "C" {
 int ys_model_create(ys_ctx* ctx, const ys_model_desc* desc, ys_model** out) {
   YS_REQUIRE(ctx && desc && out, "ys_model_create: null argument");
   YS_REQUIRE(desc->dtype == YS_F32 || desc->dtype == YS_BF16 || desc->dtype == YS_FP8, "ys_model_create: dtype %d unsupported", desc->dtype);
-  if ((desc->family != YS_YOLOV8 && desc->family != YS_YOLOV11) || desc->task < YS_DETECT || desc->task > YS_POSE) {
-    ys_set_error("ys_model_create: YOLOv8 / YOLOv11 detect, segment, obb and pose are built (family %d task %d)", desc->family, desc->task);
+  if ((desc->family != YS_YOLOV8 && desc->family != YS_YOLOV11) || desc->task < YS_DETECT || desc->task > YS_CLASSIFY) {
+    ys_set_error("ys_model_create: YOLOv8 / YOLOv11 detect, segment, obb, pose and classify are built (family %d task %d)", desc->family, desc->task);
+    return YS_ERR_UNSUPPORTED;
+  }
+  if (desc->task == YS_CLASSIFY && desc->dtype == YS_FP8) {
+    ys_set_error("ys_model_create: the classify graphs run in YS_F32 or YS_BF16; YS_FP8 is not built for them");
     return YS_ERR_UNSUPPORTED;
   }
   YS_REQUIRE(desc->size >= 0 && desc->size <= 4, "ys_model_create: size %d out of range", desc->size);
-  YS_REQUIRE(desc->nc > 0 && desc->reg_max > 1 && desc->reg_max <= 32, "ys_model_create: nc=%d reg_max=%d", desc->nc, desc->reg_max);
+  YS_REQUIRE(desc->nc > 0 && (desc->task == YS_CLASSIFY || (desc->reg_max > 1 && desc->reg_max <= 32)), "ys_model_create: nc=%d reg_max=%d", desc->nc, desc->reg_max);
   YS_REQUIRE(desc->height > 0 && desc->width > 0 && desc->height % 32 == 0 && desc->width % 32 == 0,
              "ys_model_create: image size %dx%d must be a positive multiple of 32", desc->height, desc->width);
   YS_REQUIRE(desc->max_batch > 0, "ys_model_create: max_batch %d", desc->max_batch);
@@ -2151,7 +2275,8 @@ int ys_model_create(ys_ctx* ctx, const ys_model_desc* desc, ys_model** out) {
   m->ctx = ctx; m->d = *desc; m->dtype = store; m->epl = store == YS_BF16 ? 8 : 4; m->es = store == YS_BF16 ? 2 : 4;
   m->maxB = desc->max_batch;
   for (int j = 0; j < 64; j++) m->dfl_w[j] = (float)j;
-  int st = desc->family == YS_YOLOV11 ? build_v11_detect(m) : build_v8_detect(m);
+  int st = desc->task == YS_CLASSIFY ? (desc->family == YS_YOLOV11 ? build_v11_classify(m) : build_v8_classify(m))
+                                     : (desc->family == YS_YOLOV11 ? build_v11_detect(m) : build_v8_detect(m));
   if (st == YS_OK) st = layout_params(m);
   if (st == YS_OK) st = allocate(m);
   if (st != YS_OK) { ys_model_destroy(m); return st; }
@@ -2360,7 +2485,25 @@ int ys_model_get_output(ys_model* m, const char* key, float* host, size_t count)
   hipStream_t st = m->ctx->stream;
   const int B = m->B;
   const std::string k(key);
-  if (k == "boxes" || k == "scores") {
+  const bool cls_key = k == "cls" || k == "dcls" || k == "logits";
+  if (m->cls != cls_key) {
+    ys_set_error(m->cls ? "ys_model_get_output: a classify model has the outputs \"cls\", \"logits\" and \"dcls\" (not '%s')"
+                        : "ys_model_get_output: '%s' is an output of classify models only", key);
+    return YS_ERR_INVALID_ARG;
+  }
+  if (cls_key) {
+    // Classify.forward (Head.cs:635-643): "cls" = logits in training, softmax(logits, 1) in eval; "logits" = the logits in both modes;
+    // "dcls" = d(loss) / d(logits) after ys_loss_classify.  All [B, nc].
+    YS_REQUIRE(count == (size_t)B * m->d.nc, "ys_model_get_output(%s): expected %zu elements", key, (size_t)B * m->d.nc);
+    YS_REQUIRE(k != "dcls" || m->have_loss, "ys_model_get_output(dcls): no loss has run");
+    if (k == "cls" && !m->fwd_training) {
+      YS_CHECK_HIP(hipMemcpyAsync(host, m->pred, count * 4, hipMemcpyDeviceToHost, st));
+    } else {
+      const Buf& b = m->bufs[m->logit_buf];
+      YS_TRY(ys_unpack_nchw_launch(st, m->dtype, k == "dcls" ? b.grad : b.act, b.ldc, 0, B, m->d.nc, 1, m->out_stage));
+      YS_CHECK_HIP(hipMemcpyAsync(host, m->out_stage, count * 4, hipMemcpyDeviceToHost, st));
+    }
+  } else if (k == "boxes" || k == "scores") {
     const bool bx = k == "boxes";
     const int C = bx ? 4 * m->d.reg_max : m->d.nc;
     YS_REQUIRE(count == (size_t)B * C * m->A, "ys_model_get_output(%s): expected %zu elements", key, (size_t)B * C * m->A);
@@ -2422,6 +2565,7 @@ int ys_model_get_output(ys_model* m, const char* key, float* host, size_t count)
 // "dboxes" / "dscores" / ... gradient outputs then work on them; ys_model_backward is refused (no graph state behind these preds).
 int ys_model_set_preds(ys_model* m, int batch, const float* boxes, const float* scores, const float* mask_coefficient, const float* proto) {
   YS_REQUIRE(m && !m->is_block && boxes && scores, "ys_model_set_preds: null argument or block handle");
+  YS_REQUIRE(!m->cls, "ys_model_set_preds: a classify model has no detection outputs (its criterion is ys_loss_classify)");
   YS_REQUIRE(batch > 0 && batch <= m->maxB, "ys_model_set_preds: batch %d outside (0, %d]", batch, m->maxB);
   YS_REQUIRE(!m->segment || (mask_coefficient && proto), "ys_model_set_preds: a Segment model needs mask_coefficient and proto");
   YS_REQUIRE(m->xkind < 2 || mask_coefficient, "ys_model_set_preds: a Pose / Obb model takes its raw kpts [B,nk,A] / angle LOGITS [B,1,A] in the mask_coefficient argument");
@@ -2469,6 +2613,7 @@ static int loss_detect_core(ys_model* m, const float* batch_idx, const float* cl
   // Training forward -> the criterion feeds backward (Amp.cs:338-348).  Eval forward -> validation loss on the eval-mode preds
   // (Detector.cs:94-97): the head logits are produced in both modes; only backward needs the training-mode state.
   YS_REQUIRE(!m->is_block && m->have_fwd, "ys_loss_detect: needs a forward of a full model first");
+  YS_REQUIRE(!m->cls, "ys_loss_detect: a classify model's criterion is ys_loss_classify (Loss.cs:1073-1091)");
   YS_REQUIRE(m->xkind != 2 || aux_follows, "ys_loss_detect: an OBB model's criterion is ys_loss_obb (oriented labels, Loss.cs:486-684)");
   YS_REQUIRE(m->xkind != 3 || aux_follows, "ys_loss_detect: a Pose model's criterion is ys_loss_pose (keypoint terms, Loss.cs:870-1071)");
   const bool rot = m->xkind == 2;
@@ -2589,6 +2734,30 @@ int ys_loss_pose(ys_model* m, const float* batch_idx, const float* cls, const fl
   return YS_OK;
 }
 
+// v8ClassificationLoss (Loss.cs:1073-1091): cross_entropy(preds["cls"], batch["cls"].view(-1)), mean reduction, and d(loss)/d(logits)
+// = (softmax - onehot) / B into the logits' gradient buffer.  cls: fp32 class ids [batch].  Works after a training forward (the step) and
+// after an eval forward (Classifier.Val's loss on the eval logits, Classifier.cs:90-93).
+int ys_loss_classify(ys_model* m, const float* cls, int batch, int on_device) {
+  YS_REQUIRE(m && cls, "ys_loss_classify: null argument");
+  YS_REQUIRE(m->cls, "ys_loss_classify: the model has no Classify head (task %d)", m->d.task);
+  YS_REQUIRE(m->have_fwd, "ys_loss_classify: needs a forward first");
+  YS_REQUIRE(batch == m->B, "ys_loss_classify: batch %d differs from the last forward's %d", batch, m->B);
+  if (!on_device)
+    for (int i = 0; i < batch; i++)
+      YS_REQUIRE(cls[i] >= 0.f && cls[i] < (float)m->d.nc && cls[i] == floorf(cls[i]), "ys_loss_classify: label %g of image %d is not a class id in [0, %d)",
+                 (double)cls[i], i, m->d.nc);
+  YS_CHECK_HIP(hipSetDevice(m->ctx->device));
+  hipStream_t st = m->ctx->stream;
+  const float* lab = cls;
+  if (!on_device) { YS_CHECK_HIP(hipMemcpyAsync(m->cls_lab, cls, (size_t)batch * 4, hipMemcpyHostToDevice, st)); lab = m->cls_lab; }
+  YsTimer timer(m->ctx, "loss");
+  const Buf& lb = m->bufs[m->logit_buf];
+  YS_TRY(ys_cls_xent_launch(st, m->dtype, lb.act, m->ld_cls, batch, m->d.nc, lab, lb.grad, nullptr, m->cls_rows, m->scalars));
+  YS_CHECK_HIP(hipGetLastError());
+  m->have_loss = true; m->have_seg_loss = true;
+  return YS_OK;
+}
+
 // device-resident labels cannot size the workspace without a host sync: the prep kernel records the batch's largest per-image
 // label count and the first synchronising read refuses a truncated assignment instead of returning it
 static int check_label_overflow(ys_model* m, float max_count) {
@@ -2607,6 +2776,16 @@ int ys_loss_read_items(ys_model* m, float* items, int n_items, float* loss_sum) 
   float h[16];
   YS_CHECK_HIP(hipMemcpyAsync(h, m->scalars, sizeof(h), hipMemcpyDeviceToHost, m->ctx->stream));
   YS_CHECK_HIP(hipStreamSynchronize(m->ctx->stream));
+  if (m->cls) {                // v8ClassificationLoss: one item, the batch mean, which is also the scalar backward() runs on (Loss.cs:1086-1088)
+    if (h[14] != 0.f) {
+      m->have_loss = false;
+      ys_set_error("ys_loss_classify: %d label(s) of this batch are not class ids in [0, %d)", (int)h[14], m->d.nc);
+      return YS_ERR_INVALID_ARG;
+    }
+    items[0] = h[1];
+    if (loss_sum) *loss_sum = h[4];
+    return YS_OK;
+  }
   YS_TRY(check_label_overflow(m, h[15]));
   if (m->segment) {
     YS_REQUIRE(m->have_seg_loss, "ys_loss_read_items: the Segment model needs ys_loss_segment");
@@ -2625,6 +2804,7 @@ int ys_loss_read_items(ys_model* m, float* items, int n_items, float* loss_sum) 
 
 int ys_loss_read(ys_model* m, float loss_items[3], float* loss_sum) {
   YS_REQUIRE(m && m->have_loss, "ys_loss_read: no loss has run");
+  YS_REQUIRE(!m->cls, "ys_loss_read: a classify model has one loss item (ys_loss_read_items with n_items = 1)");
   float h[16];
   YS_CHECK_HIP(hipMemcpyAsync(h, m->scalars, sizeof(h), hipMemcpyDeviceToHost, m->ctx->stream));
   YS_CHECK_HIP(hipStreamSynchronize(m->ctx->stream));
@@ -2856,8 +3036,9 @@ int ys_block_backward(ys_model* m, const float* dy, int on_device, float* dx) {
 int ys_head_create(ys_ctx* ctx, const ys_head_desc* hd, ys_model** out) {
   YS_REQUIRE(ctx && hd && out, "ys_head_create: null argument");
   YS_REQUIRE(hd->dtype == YS_F32 || hd->dtype == YS_BF16 || hd->dtype == YS_FP8, "ys_head_create: dtype %d unsupported", hd->dtype);
-  YS_REQUIRE((hd->family == YS_YOLOV8 || hd->family == YS_YOLOV11) && hd->task >= YS_DETECT && hd->task <= YS_POSE, "ys_head_create: family %d task %d", hd->family, hd->task);
-  YS_REQUIRE(hd->nc > 0 && hd->reg_max > 1 && hd->reg_max <= 32, "ys_head_create: nc=%d reg_max=%d", hd->nc, hd->reg_max);
+  YS_REQUIRE((hd->family == YS_YOLOV8 || hd->family == YS_YOLOV11) && hd->task >= YS_DETECT && hd->task <= YS_CLASSIFY, "ys_head_create: family %d task %d", hd->family, hd->task);
+  YS_REQUIRE(hd->nc > 0 && (hd->task == YS_CLASSIFY || (hd->reg_max > 1 && hd->reg_max <= 32)), "ys_head_create: nc=%d reg_max=%d", hd->nc, hd->reg_max);
+  if (hd->task == YS_CLASSIFY && hd->dtype == YS_FP8) { ys_set_error("ys_head_create: the Classify head runs in YS_F32 or YS_BF16; YS_FP8 is not built for it"); return YS_ERR_UNSUPPORTED; }
   YS_REQUIRE(hd->height > 0 && hd->width > 0 && hd->height % 32 == 0 && hd->width % 32 == 0, "ys_head_create: image size %dx%d must be a positive multiple of 32", hd->height, hd->width);
   YS_REQUIRE(hd->max_batch > 0, "ys_head_create: max_batch %d", hd->max_batch);
   YS_CHECK_HIP(hipSetDevice(ctx->device));
@@ -2871,6 +3052,24 @@ int ys_head_create(ys_ctx* ctx, const ys_head_desc* hd, ys_model** out) {
   m->d.kpt_num = hd->kpt_num; m->d.kpt_dim = hd->kpt_dim;
   for (int j = 0; j < 64; j++) m->dfl_w[j] = (float)j;
   int st = YS_OK;
+  if (hd->task == YS_CLASSIFY) {   // Classify(c1 = ch[0], nc) on one [height / 32, width / 32] map; ch[1], ch[2] are ignored
+    const int c1 = hd->ch[0], h = hd->height / 32, w = hd->width / 32;
+    if (c1 <= 0 || c1 % m->epl) { ys_set_error("ys_head_create: ch[0] = %d must be a positive multiple of %d for this dtype", c1, m->epl); st = YS_ERR_UNSUPPORTED; }
+    if (st == YS_OK) {
+      m->head_in[0] = new_buf(m, h, w, c1); m->head_ch[0] = c1; m->in_buf = m->head_in[0];
+      st = add_classify(m, "head", View{m->head_in[0], 0, c1}, c1, h, w, 0);
+    }
+    if (st == YS_OK) st = layout_params(m);
+    if (st == YS_OK) {
+      for (auto& t : m->tensors) if (t.name.compare(0, 5, "head.") == 0) t.name.erase(0, 5);
+      m->blk_c1 = (c1 + 1023) / 1024;                                                       // c1 * (H / 32) * (W / 32) <= blk_c1 * H * W
+      st = allocate(m);
+    }
+    if (st == YS_OK) st = ys_model_init_weights(m, 0);
+    if (st != YS_OK) { ys_model_destroy(m); return st; }
+    *out = m;
+    return YS_OK;
+  }
   int hh[3], ww[3], ch[3];
   for (int i = 0; i < 3 && st == YS_OK; i++) {
     hh[i] = hd->height / (8 << i); ww[i] = hd->width / (8 << i); ch[i] = hd->ch[i];
@@ -2895,7 +3094,7 @@ int ys_head_create(ys_ctx* ctx, const ys_head_desc* hd, ys_model** out) {
 }
 
 int ys_head_forward(ys_model* m, const float* const x[3], int on_device, int batch) {
-  YS_REQUIRE(m && m->is_head && x && x[0] && x[1] && x[2], "ys_head_forward: null argument or not a head handle");
+  YS_REQUIRE(m && m->is_head && x && x[0] && (m->cls || (x[1] && x[2])), "ys_head_forward: null argument or not a head handle");
   YS_REQUIRE(batch > 0 && batch <= m->maxB, "ys_head_forward: batch %d outside (0, %d]", batch, m->maxB);
   YS_CHECK_HIP(hipSetDevice(m->ctx->device));
   hipStream_t st = m->ctx->stream;
@@ -2903,6 +3102,7 @@ int ys_head_forward(ys_model* m, const float* const x[3], int on_device, int bat
   m->B = batch;
   YS_TRY(join_wgrad_stream(m));   // the level inputs are rewritten below; the previous backward's weight-gradient kernels read them
   for (int i = 0; i < 3; i++) {
+    if (m->head_in[i] < 0) continue;                                 // Classify: one input
     const Buf& ib = m->bufs[m->head_in[i]];
     const float* src = x[i];
     if (!on_device) {
@@ -2918,8 +3118,18 @@ int ys_head_forward(ys_model* m, const float* const x[3], int on_device, int bat
 }
 
 int ys_head_set_grads(ys_model* m, const float* dboxes, const float* dscores, const float* dextra, const float* dproto) {
-  YS_REQUIRE(m && m->is_head && dboxes && dscores, "ys_head_set_grads: null argument or not a head handle");
+  YS_REQUIRE(m && m->is_head && dscores && (m->cls || dboxes), "ys_head_set_grads: null argument or not a head handle");
   YS_REQUIRE(m->have_fwd && m->fwd_training, "ys_head_set_grads: needs a training-mode ys_head_forward first");
+  if (m->cls) {                    // Classify: dscores = d(loss) / d(logits) [B, nc]; the other arguments are ignored
+    YS_CHECK_HIP(hipSetDevice(m->ctx->device));
+    hipStream_t st = m->ctx->stream;
+    const Buf& b = m->bufs[m->logit_buf];
+    YS_CHECK_HIP(hipMemcpyAsync(m->out_stage, dscores, (size_t)m->B * m->d.nc * 4, hipMemcpyHostToDevice, st));
+    YS_TRY(ys_pack_input_launch(st, m->dtype, m->out_stage, m->B, m->d.nc, 1, 1, b.ldc, b.grad));
+    YS_CHECK_HIP(hipStreamSynchronize(st));
+    m->have_loss = true; m->have_seg_loss = true;
+    return YS_OK;
+  }
   YS_REQUIRE(!m->segment || (dextra && dproto), "ys_head_set_grads: a Segment head needs dmask_coefficient and dproto");
   YS_REQUIRE(m->xkind < 2 || dextra, "ys_head_set_grads: an Obb / Pose head needs the gradient of its angle logits / keypoints");
   YS_CHECK_HIP(hipSetDevice(m->ctx->device));
@@ -2951,7 +3161,7 @@ int ys_head_backward(ys_model* m, int on_device, float* const dx[3]) {
   reset_grad_state(m);
   YS_TRY(backward_range(m, 0, ys_model::NSEG - 1));
   for (int i = 0; i < 3 && dx; i++) {
-    if (!dx[i]) continue;
+    if (!dx[i] || m->head_in[i] < 0) continue;
     const Buf& ib = m->bufs[m->head_in[i]];
     const size_t n = (size_t)m->B * m->head_ch[i] * ib.rows_per_b;
     float* dst = on_device ? dx[i] : m->img_dev;

@@ -365,5 +365,16 @@ struct PoseArgs {
 };
 int ys_loss_pose_grid(int B, int A);
 int ys_loss_pose_launch(hipStream_t st, int dtype, const PoseArgs& a, int* cnt, int* off, int* list);
+// Classify head (classify.hip): BN + SiLU + spatial mean (scale = null: mean only), its backward fused with the BN / SiLU backward, softmax / cross entropy
+// (labels = null: eval softmax into probs), top-k
+int ys_cls_pool_fwd_launch(hipStream_t st, int dtype, const void* x, int ldc, int coff, long bstride, int B, int HW, int C,
+                           const float* scale, const float* shift, int act, void* out, int ldo);
+int ys_cls_bn_bwd_reduce_launch(hipStream_t st, int dtype, const void* dpooled, int ldp, const void* y, int B, int HW, int C, const float* scale,
+                                const float* shift, int act, float* partial);
+int ys_cls_bn_bwd_apply_launch(hipStream_t st, int dtype, const void* dpooled, int ldp, const void* y, int B, int HW, int C, const float* scale,
+                               const float* shift, const float* k2, const float* k3, int act, void* dy);
+int ys_cls_xent_launch(hipStream_t st, int dtype, const void* logits, int ld, int B, int nc, const float* labels, void* dlogits,
+                       float* probs, float* row_loss, float* scalars);
+int ys_cls_topk_launch(hipStream_t st, const float* x, int rows, int cols, int k, int32_t* idx);
 int ys_process_mask_launch(hipStream_t st, const float* protos, const float* masks_in, const float* boxes, int n, int nm, int mh,
                            int mw, int ih, int iw, int upsample, int trunc_crop, unsigned char* out);

@@ -299,3 +299,54 @@ class PoseDetector(Detector):
         box = M.val_summary(M.ap_per_class(np.concatenate(tps), conf, pc, tc))
         pose = M.val_summary(M.ap_per_class(np.concatenate(tpps), conf, pc, tc))
         return loss_sum, box, pose
+
+
+class ClassifyResult:
+    """Types/YoloResult as Classifier.ImagePredict fills it (Classifier.cs:47-55): class id and score only."""
+    __slots__ = ("ClassID", "Score")
+
+    def __init__(self, cls_id, score):
+        self.ClassID, self.Score = int(cls_id), float(score)
+
+    def __repr__(self):
+        return f"ClassifyResult(cls={self.ClassID}, score={self.Score:.4f})"
+
+
+class Classifier:
+    """Host mirror of Models/Classifier.cs on the engine: ImagePredict (:28-58) and Val (:61-120)."""
+
+    def __init__(self, model):
+        from .model import v8ClassificationLoss
+        self.model, self.engine = model, model.engine
+        self.amp = AMPWrapper(model)
+        self.loss = v8ClassificationLoss(model)
+
+    def ImagePredict(self, image_chw_u8, predict_threshold=0.25, iou_threshold=0.5):
+        """image: uint8 / float [3,H,W] in 0..255.  Pad to a multiple of 32 with 114, / 255, eval forward; every class sorted by score
+        (descending; the thresholds are unused, as in the reference)."""
+        x = pad_to_32(np.asarray(image_chw_u8, np.float32))[None]
+        assert x.shape[2:] == (self.model.height, self.model.width), "create the model with the padded image size"
+        inference, _ = self.amp.Evaluate(x)
+        p = inference["cls"][0]
+        order = np.argsort(-p, kind="stable")                        # results.Sort by descending score (Classifier.cs:56)
+        return [ClassifyResult(i, p[i]) for i in order]
+
+    def Val(self, batches):
+        """batches: iterable of dicts (images [B,3,H,W] in [0,1], batch_idx, cls [B]).  Returns (summed loss items [1], [top1, top5]):
+        eval forward, the criterion on the eval logits, the top-min(nc, 5) classes of the softmax per image (ys_cls_topk), then top-1 /
+        top-5 accuracy over the set.  Batches with an empty batch_idx are skipped (Classifier.cs:83-86)."""
+        loss_sum, tops, targets = None, [], []
+        k = min(self.model.nc, 5)
+        for data in batches:
+            if np.asarray(data["batch_idx"]).size < 1:
+                continue
+            inference, _ = self.amp.Evaluate(np.ascontiguousarray(data["images"], np.float32))
+            _, items = self.loss.forward(None, data)
+            loss_sum = items if loss_sum is None else loss_sum + items
+            tops.append(self.engine.cls_topk(inference["cls"], k))
+            targets.append(np.asarray(data["cls"], np.float32).reshape(-1))
+        if not tops:
+            return np.zeros(1, np.float32), [0.0, 0.0]
+        pred, tgt = np.concatenate(tops), np.concatenate(targets)
+        correct = (tgt[:, None] == pred).astype(np.float32)
+        return loss_sum, [float(correct[:, 0].mean()), float(correct.max(1).mean())]

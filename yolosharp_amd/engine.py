@@ -149,6 +149,15 @@ class Engine:
     def dist_destroy(self):
         _lib.check(self.lib, self.lib.ys_dist_destroy(self.ctx))
 
+    def cls_topk(self, scores, k=5):
+        """Classifier.Val's argsort(1, descending)[:, :k] (Classifier.cs:95-100) on the device: scores [rows, cols] fp32 -> int32 [rows, k];
+        ties go to the lower index."""
+        x = np.ascontiguousarray(scores, np.float32)
+        rows, cols = x.shape
+        out = np.zeros((rows, k), np.int32)
+        _lib.check(self.lib, self.lib.ys_cls_topk(self.ctx, _ptr(x), 0, rows, cols, k, _ptr(out)))
+        return out
+
     # ---- validation (Detector.cs:103-120): box_iou + match_predictions per image, batched on the device
     def box_iou(self, box1, box2, eps=1e-7):
         """Metrics.box_iou (Metrics.cs:16-34): xyxy [n,4] x [m,4] -> [n,m] fp32."""

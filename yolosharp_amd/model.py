@@ -319,6 +319,49 @@ class Yolov11Pose(_PoseMixin, Yolov11):
     """Models/Yolo.cs:486-500."""
 
 
+class _ClassifyMixin:
+    """Head.Classify (Head.cs:612-644) after the Yolov8 backbone without SPPF (Yolov8Classify, Yolo.cs:537-554: model.0-8, head model.9) or
+    the Yolov11 backbone with SPPF and C2PSA (Yolov11Classify, :556-573: model.0-10, head model.11).  forward() returns (None, {"cls":
+    logits [B,nc]}) in training and ({"cls": softmax probabilities}, {"cls": logits}) in eval.  Criterion: v8ClassificationLoss."""
+    TASK = 4
+    NM = 0
+
+    def forward(self, x, fetch=True):
+        x = np.ascontiguousarray(x, np.float32)
+        B = x.shape[0]
+        assert x.shape == (B, 3, self.height, self.width), x.shape
+        _lib.check(self.lib, self.lib.ys_model_forward(self.handle, _ptr(x), 0, B))
+        self._batch = B
+        return self._outputs() if fetch else (None, None)
+
+    __call__ = forward
+
+    def forward_u8(self, images_u8):
+        x = np.ascontiguousarray(images_u8, np.uint8)
+        B, c, h, w = x.shape
+        assert c == 3
+        _lib.check(self.lib, self.lib.ys_model_forward_u8(self.handle, _ptr(x), 0, B, h, w))
+        self._batch = B
+        return self._outputs()
+
+    def _outputs(self):
+        preds = {"cls": self.get_output("logits")}
+        return (None, preds) if self.training else ({"cls": self.get_output("cls")}, preds)
+
+    def get_output(self, key):
+        a = np.empty((self._batch, self.nc), np.float32)
+        _lib.check(self.lib, self.lib.ys_model_get_output(self.handle, key.encode(), _ptr(a), a.size))
+        return a
+
+
+class Yolov8Classify(_ClassifyMixin, Yolov8):
+    """Models/Yolo.cs:537-554."""
+
+
+class Yolov11Classify(_ClassifyMixin, Yolov11):
+    """Models/Yolo.cs:556-573."""
+
+
 class v8DetectionLoss:
     """Loss.cs:328-484.  forward(preds, batch): `preds` is implicit (the model's last training forward stays on the
     device); batch = {"batch_idx": [N], "cls": [N], "bboxes": [N,4] normalised cxcywh} (YoloDataLoader.cs:18-44)."""
@@ -425,6 +468,33 @@ class v8PoseLoss(v8SegmentationLoss):
         return self.read() if read else None
 
     __call__ = forward
+
+
+class v8ClassificationLoss:
+    """Loss.cs:1073-1091: cross_entropy(preds["cls"], batch["cls"].view(-1)) with mean reduction.  batch = {"cls": [B] class ids} (plus
+    whatever else the loader carries).  Returns (loss [1], loss_detach [1]): the reference's loss is the mean itself, NOT multiplied by the
+    batch size like the detection losses."""
+    N_ITEMS = 1
+
+    def __init__(self, model):
+        self.model, self.lib = model, model.lib
+
+    def forward_device(self, cls_dev, batch):
+        _lib.check(self.lib, self.lib.ys_loss_classify(self.model.handle, cls_dev, batch, 1))
+
+    def forward(self, preds, batch, read=True):
+        cl = np.ascontiguousarray(np.asarray(batch["cls"], np.float32).reshape(-1))
+        _lib.check(self.lib, self.lib.ys_loss_classify(self.model.handle, _ptr(cl), cl.shape[0], 0))
+        return self.read() if read else None
+
+    __call__ = forward
+
+    def read(self):
+        items = (C.c_float * 1)()
+        total = C.c_float()
+        _lib.check(self.lib, self.lib.ys_loss_read_items(self.model.handle, items, 1, C.byref(total)))
+        loss = np.array([total.value], np.float32)
+        return loss, np.array(list(items), np.float32)
 
 
 class AMPWrapper:

@@ -77,10 +77,10 @@ class Trainer:
         self.amp = AMPWrapper(model)
         # criterion and validator of the model's task (YoloBaseTaskModel's subclasses Detector / Segmenter / Obber / PoseDetector)
         from . import detector as D
-        from .model import v8OBBLoss, v8PoseLoss
+        from .model import v8ClassificationLoss, v8OBBLoss, v8PoseLoss
         task = 1 if segment else getattr(model, "TASK", 0)
-        self.crit = {0: v8DetectionLoss, 1: v8SegmentationLoss, 2: v8OBBLoss, 3: v8PoseLoss}[task](model)
-        self.validator = {0: D.Detector, 1: D.Segmenter, 2: D.Obber, 3: D.PoseDetector}[task]
+        self.crit = {0: v8DetectionLoss, 1: v8SegmentationLoss, 2: v8OBBLoss, 3: v8PoseLoss, 4: v8ClassificationLoss}[task](model)
+        self.validator = {0: D.Detector, 1: D.Segmenter, 2: D.Obber, 3: D.PoseDetector, 4: D.Classifier}[task]
         self.sched = LrSchedule(model.nc, epochs, nb, **sched)
         self.best_fitness = -float("inf")
 
