@@ -1,7 +1,8 @@
-"""The C-ABI library loads and exports every symbol include/yolosharp_hip.h declares (no compute calls)."""
+"""The C-ABI library loads and exports exactly the symbols include/yolosharp_hip.h declares (no compute calls)."""
 import ctypes
 import os
 import re
+import subprocess
 
 import pytest
 
@@ -11,6 +12,20 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def declared_symbols():
     txt = open(os.path.join(ROOT, "include", "yolosharp_hip.h")).read()
     return sorted(set(re.findall(r"YS_API\s+[\w\s\*]+?\b(ys_\w+)\s*\(", txt)))
+
+
+def exported_ys_symbols(path):
+    """The defined dynamic symbols matching ^ys_ of a shared library: llvm-readelf --dyn-syms of the ROCm toolchain, nm -D --defined-only where that is absent."""
+    readelf = "/opt/rocm/lib/llvm/bin/llvm-readelf"
+    if os.path.exists(readelf):
+        out = subprocess.run([readelf, "--dyn-syms", "-W", path], check=True, stdout=subprocess.PIPE, text=True).stdout
+        # Num: Value Size Type Bind Vis Ndx Name -- Ndx UND = imported, not exported
+        rows = [l.split() for l in out.splitlines()]
+        names = [r[7] for r in rows if len(r) >= 8 and r[0].endswith(":") and r[6] != "UND" and r[4] in ("GLOBAL", "WEAK")]
+    else:
+        out = subprocess.run(["nm", "-D", "--defined-only", path], check=True, stdout=subprocess.PIPE, text=True).stdout
+        names = [l.split()[-1] for l in out.splitlines() if l.split()]
+    return sorted(set(n.split("@")[0] for n in names if re.match(r"^ys_", n)))
 
 
 def test_header_declares_symbols():
@@ -24,6 +39,8 @@ def test_device_library_exports_every_declared_symbol():
     lib = ctypes.CDLL(path)
     missing = [s for s in declared_symbols() if not hasattr(lib, s)]
     assert not missing, missing
+    # ... and nothing else: the header IS the boundary (triage hooks live in build/libyolosharp_hip_triage.so only)
+    assert exported_ys_symbols(path) == declared_symbols()
     lib.ys_is_device_build.restype = ctypes.c_int
     assert lib.ys_is_device_build() == 1
 
@@ -59,7 +76,7 @@ def test_c_consumer_runs_on_interpreter_build():
     """tests/c/abi_smoke.c -- plain C, compiled with -Wall -Wextra -Werror against the public header only -- drives the whole hot
     path (create, state_dict listing, train step, AdamW, eval, NMS) through the same ABI on the test-only interpreter build."""
     from yolosharp_amd import build
-    build.build_emu()
+    assert exported_ys_symbols(build.build_emu()) == declared_symbols()
     dev, emu = build.build_abi_smoke()
     rc, out = _run_smoke(emu)
     assert rc == 0 and "abi_smoke OK: device_build=0" in out, out

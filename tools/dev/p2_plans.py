@@ -1,8 +1,11 @@
 """Print conv_p2_kernel's plan (tile, LDS bytes, pitches, modelled ds_read_b128 cycles) for the forward convolutions of YOLOv8n
-B=64 640x640 -- host-only, uses the emulator build of the library (no device).  YS_P2_PITCH=0 YS_P2_ROWPAD=0 YS_P2_WPITCH=0 = round-2 rules."""
+B=64 640x640 -- host-only (no device needed), through the triage build of the library.  YS_P2_PITCH=0 YS_P2_ROWPAD=0 YS_P2_WPITCH=0 = round-2 rules."""
 import ctypes, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-lib = ctypes.CDLL(os.path.join(ROOT, "tools", "hipemu", "libyolosharp_emu.so"))
+TRIAGE = os.path.join(ROOT, "build", "libyolosharp_hip_triage.so")   # the product plus the ys_debug_* plan hooks
+if not os.path.exists(TRIAGE):
+    sys.exit("build the triage library first: python -m yolosharp_amd.build triage")
+lib = ctypes.CDLL(TRIAGE)
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 64
 shapes = [  # (H, W, cin, cout, k, s, in_ldc)
     (640, 640, 8, 16, 3, 2, 8), (320, 320, 16, 32, 3, 2, 16), (160, 160, 32, 32, 1, 1, 32), (160, 160, 16, 16, 3, 1, 48), (160, 160, 48, 32, 1, 1, 48),

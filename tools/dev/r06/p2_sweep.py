@@ -5,7 +5,10 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 sys.path.insert(0, ROOT)
 from yolosharp_amd import Engine
-eng = Engine(0)
+TRIAGE = os.path.join(ROOT, "build", "libyolosharp_hip_triage.so")   # the product plus the ys_debug_* plan hooks
+if not os.path.exists(TRIAGE):
+    sys.exit("build the triage library first: python -m yolosharp_amd.build triage")
+eng = Engine(0, lib_path=TRIAGE)
 force = eng.lib.ys_debug_p2_force
 force.argtypes = [ctypes.c_int] * 3
 rng = np.random.default_rng(0)

@@ -1,5 +1,5 @@
 #!/bin/bash
-# One parameterised GPU session (replaces the per-session scripts of round 3, now under tools/dev/r03_sessions/).
+# One parameterised GPU session (replaces the per-session scripts of round 3, which live in git history).
 #   gpurun --timeout 900 -- 'bash tools/gpu_session.sh <tag> "<pytest args or ->" "<ab list>" [profile]'
 # <ab list>: space-separated name:ENV=VAL[,ENV=VAL] items, each one `bench.py --steps 30` run (same box, back to back, order as given).
 # profile: after the A/B runs, a rocprofv3 kernel-trace --stats pass of the default configuration (kernel table into gpurun_out/<tag>/).

@@ -24,6 +24,7 @@ NO_CONTRACT = {"nms.hip", "valmetrics.hip"}
 LIB_DEVICE = os.path.join(ROOT, "yolosharp_amd", "libyolosharp_hip.so")
 LIB_EMU = os.path.join(EMU, "libyolosharp_emu.so")
 LIB_ORACLE = os.path.join(ROOT, "oracle", "libys_oracle.so")
+LIB_TRIAGE = os.path.join(BUILD, "libyolosharp_hip_triage.so")
 
 
 def _sources():
@@ -53,8 +54,9 @@ def _run(cmd):
 
 
 def build_device(verbose=False, variant="dev", defines=(), out=None):
-    """variant "dev" is the product.  Triage variants (e.g. build_device(variant="tl", defines=["-DYS_P2_TIMELINE"],
-    out="build/libyolosharp_hip_tl.so")) compile the same sources with extra defines into their own object directory."""
+    """variant "dev" is the product.  Measurement and triage variants compile the same sources with extra defines into their own object
+    directory and library under build/ (see __main__: timeline, p2ablate, ablate, and triage = the product plus the ys_debug_* plan hooks
+    that tools/dev/p2_plans.py and the tools/dev/r06 plan sweeps load)."""
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     os.makedirs(os.path.join(BUILD, variant), exist_ok=True)
     hdrs = _headers()
@@ -141,8 +143,8 @@ if __name__ == "__main__":
         build_oracle(True)
     if "timeline" in what:
         build_device(True, variant="tl", defines=["-DYS_P2_TIMELINE"], out=os.path.join(BUILD, "libyolosharp_hip_tl.so"))
-    if "epi0" in what:     # A/B: the LDS-staged 16-byte-store epilogue of rounds 1-2 instead of the direct one
-        build_device(True, variant="epi0", defines=["-DYS_P2_EPI_DIRECT=0"], out=os.path.join(BUILD, "libyolosharp_hip_epi0.so"))
+    if "triage" in what:   # the product plus the process-global plan overrides ys_debug_p2_force / _p2_plan / _wgrad_force
+        build_device(True, variant="triage", defines=["-DYS_TRIAGE"], out=LIB_TRIAGE)
     if "p2ablate" in what:
         build_device(True, variant="p2abl", defines=["-DYS_P2_ABLATE"], out=os.path.join(BUILD, "libyolosharp_hip_p2abl.so"))
     if "ablate" in what:

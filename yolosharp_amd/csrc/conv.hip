@@ -488,9 +488,7 @@ conv3x3_tile_kernel(ConvArgs a, int ntiles, int nchunks, int wres, int wpitch, i
 //  * 256 threads, <= 128 VGPRs: register pressure no longer caps occupancy.
 // Handles forward (stride 1 and 2) and stride-1 dgrad (same gather, flipped weights); DIV = 2 dgrads stay on the old path.
 #include "conv_epi.h"
-#ifndef YS_EPI_BATCH_P2
-#define YS_EPI_BATCH_P2(NPU_) 4
-#endif
+constexpr int YS_EPI_BATCH_P2 = 4;   // store-loop iterations whose accumulate operands p2_epilogue requests ahead (BMAX): what the register budget affords
 
 // ablation switches (YS_DBG bits) cost scalar checks in the hot loops: compiled in only for triage builds (-DYS_P2_ABLATE)
 #ifdef YS_P2_ABLATE
@@ -498,39 +496,7 @@ conv3x3_tile_kernel(ConvArgs a, int ntiles, int nchunks, int wres, int wpitch, i
 #else
 #define P2_DBG(bit) false
 #endif
-#ifndef YS_P2_GROUP_COPY
-#define YS_P2_GROUP_COPY 1
-#endif
-#ifndef YS_P2_G1_MIN
-#define YS_P2_G1_MIN 12        // register tiles of >= this many MFMAs per K-step run one K-step per LDS wait (12: two K-steps for the 2 x 5 tile -- spills at 256 registers)
-#endif
-#ifndef YS_P2_LATE_PFETCH
-#define YS_P2_LATE_PFETCH 0    // 1: streamed-weight dgrad variants request the next patch inside the epilogue and run two K-steps per LDS wait (2 x 5 tile).
-                               // Built, verified and measured (round 4, same box, alternating): grouped head launches 0.68 -> 0.67 ms, step 9.51 = 9.51 -- off
-#endif
-#ifndef YS_P2_RING3
-#define YS_P2_RING3 0          // 1: streamed weights fetched three groups ahead, next patch requested after the K loop.  Built and measured (round 4, same box,
-                               // alternating): grouped head launches 1.00 -> 0.96 ms, plain launches 2.96 -> 3.00 (more spills in the non-grouped variants), step 9.75 = 9.75:
-                               // the K loop of the streamed layers is bound by its LDS round trips per K-step, not by the weight fetch -- off
-#endif
-#ifndef YS_P2_DMA_RING
-#define YS_P2_DMA_RING 1       // 1: streamed bf16 weights go global -> LDS by DMA into a ring of three group slots, two groups ahead (no registers, no ds_write,
-                               // no wait for the fetch inside the group) -- see DMAW in conv_p2_body
-#endif
-#ifndef YS_P2_DMA_G2
-#define YS_P2_DMA_G2 1
-#endif
-#ifndef YS_P2_COUNTED_WAIT
-#define YS_P2_COUNTED_WAIT 1   // the tile loop opens with s_waitcnt vmcnt(N), N = the epilogue's stores (0: vmcnt(0), rounds 1-3).  Relies on loads and stores
-                               // retiring in issue order on the shared counter -- what hipcc's own wait insertion assumes on gfx9-family parts (it derives
-                               // vmcnt(3), (2) from store counts itself when the store loop is rolled).  This switch was suspected and withdrawn once in
-                               // round 4, when the config-5 determinism test failed with it -- the bisection (profiles/README.md) cleared it: counted wait +
-                               // rolled store loop is bit-stable, full unroll WITHOUT it is not (packed-FP32 statistics), and with the convolution sources
-                               // compiled -fno-slp-vectorize the combination is stable in 8 / 8 model-level rounds and every layer rerun.
-#endif
-#ifndef P2_KG
-#define P2_KG 2            // K-steps (32 K each) per streamed weight group
-#endif
+constexpr int P2_KG = 2;   // K-steps (32 K each) per streamed weight group
 #define P2_NPU 12          // max patch units (16 B) a thread keeps in flight: 12 x 256 x 16 B = 48 KB per workgroup (small layers: 6)
 struct P2Tag0 { static constexpr int value = 0; };
 struct P2Tag1 { static constexpr int value = 1; };
@@ -538,8 +504,8 @@ struct P2Tag1 { static constexpr int value = 1; };
 // G K-steps share one LDS wait: about 16 MFMAs per group, so that a group's MFMA time matches the LDS round trip the SIMD's other
 // waves have to cover -- bounded by the fragment registers a group keeps live, 4 * G * (MR + NR): <= 64 in the 256-register
 // variants, <= 32 in the `tight` ones (compiled for three waves per SIMD, 168 registers).  G is 1, 2 or 4 (one table read).
-__host__ __device__ constexpr int p2_reg_group(int mr, int nr, bool tight = false, bool late = false) {
-  const int want = mr * nr >= (late ? YS_P2_G1_MIN : 10) ? 1 : (mr * nr >= 6 ? 2 : 4);
+__host__ __device__ constexpr int p2_reg_group(int mr, int nr, bool tight = false) {
+  const int want = mr * nr >= 10 ? 1 : (mr * nr >= 6 ? 2 : 4);
   const int cap = (tight ? 8 : 16) / (mr + nr);
   const int g = want < cap ? want : cap;
   return g >= 4 ? 4 : (g >= 2 ? 2 : 1);
@@ -628,33 +594,27 @@ __device__ __forceinline__ void conv_p2_body(const ConvArgs& a, const P2Args& g,
   constexpr int KG = P2_KG;                    // K-steps per streamed weight group
   constexpr int GU = KG * UPS;                 // 16-byte units per weight row and group
   constexpr bool TIGHT = NT == 256 && NPU <= 6 && MR * NR <= 8 && !F8;                    // 168-register variants
-  constexpr int G0 = F8 ? 1 : p2_reg_group(MR, NR, TIGHT, !WRES && RED != 0 && YS_P2_LATE_PFETCH != 0 && !YS_P2_RING3);   // fp8: one K-step is already 128 K (32-byte fragments)
+  constexpr int G0 = F8 ? 1 : p2_reg_group(MR, NR, TIGHT);   // fp8: one K-step is already 128 K (32-byte fragments)
   // streamed bf16 weights by DMA leave the dgrad variants (no bias / BatchNorm / residual epilogue paths) room for both K-steps of a weight
   // group per LDS wait: with two waves per SIMD the one-step form is a chain of two LDS round trips per 10-16 MFMAs
-  constexpr bool DMAW_G2 = !WRES && !F8 && NT == 256 && !YS_P2_RING3 && YS_P2_DMA_RING != 0 && RED != 0 && MR * NR <= 12 && YS_P2_DMA_G2 != 0;   // (4 x 4: spills)
+  constexpr bool DMAW_G2 = !WRES && !F8 && NT == 256 && RED != 0 && MR * NR <= 12;   // (4 x 4: spills)
   constexpr int G = DMAW_G2 ? KG : ((WRES || G0 < KG) ? G0 : KG);   // K-steps per register group of the K loop
   const int ngroups = WRES ? 1 : (g.nsteps + KG - 1) / KG;
-  // RING3 (round 4): streamed weights are fetched THREE groups ahead (three register sets in rotation, two LDS slots as before).  One
-  // group ahead -- the rounds 1-3 form: fetch at the top of a group, store at its end -- gives the L2 round trip one group's MFMAs to
-  // hide behind (20-32 MFMAs = 320-512 cycles against ~1.5 thousand): s_memtime stamps of the 80 -> 80 and 64 -> 144 3x3 layers of the
-  // Detect towers put their K loop at 21-24 thousand cycles per tile for 3.7 thousand cycles of MFMA.  The next tile's patch is then
-  // requested AFTER the K loop (its registers would not fit next to three weight sets) and lands under the epilogue.
-  constexpr bool RING3 = !WRES && YS_P2_RING3 != 0;
-  // LATE (round 4): streamed-weight variants request the next tile's patch after the K loop (it lands under the epilogue) -- the 48
-  // registers of a 12-unit patch are then free during the K loop, which pays for two K-steps of fragments per LDS wait (YS_P2_G1_MIN)
-  // (dgrad variants only: the forward variants' epilogue -- bias, eval BatchNorm, residual paths -- leaves no room and spilled the patch)
-  constexpr bool LATE = RING3 || (!WRES && !F8 && RED != 0 && YS_P2_LATE_PFETCH != 0);
+  // (Two round-4 alternatives for the streamed weights, both built, measured on the same box in alternation and dropped, profiles/README.md: weights fetched
+  // through registers THREE groups ahead with the next patch requested after the K loop -- grouped head launches 1.00 -> 0.96 ms, plain launches 2.96 -> 3.00,
+  // step 9.75 = 9.75: the K loop of the streamed layers is bound by its LDS round trips per K-step, not by the weight fetch; and the dgrad variants' next patch
+  // requested inside the epilogue to pay for two K-steps per LDS wait on the 2 x 5 tile -- grouped head launches 0.68 -> 0.67 ms, step 9.51 = 9.51.)
   // DMAW (round 4): streamed bf16 weights by LDS DMA.  A weight group (KG = 2 K-steps = 64 K = 128 bytes per output channel) is BN rows of
   // eight 16-byte units; a wave instruction moves eight rows (1 KB), lane l -> row l / 8, LDS unit l % 8, which holds the row's logical unit
   // (l % 8) ^ ((row / 2) % 8) -- the blocked-GEMM kernel's swizzle: the K loop's fragment reads (16 rows x 4 units) are conflict-free.  Three
   // slots: at group g the workgroup waits for its own requests of g (issued two groups earlier), meets at ONE barrier, requests g + 2 into
   // the slot group g - 1 was read from, and multiplies.  The register form costs 12 registers, three ds_write_b128 and -- the expensive
   // part -- a wait for loads issued only one group (~1 thousand cycles) earlier, per thread and group.
-  constexpr bool DMAW = !WRES && !F8 && NT == 256 && !RING3 && YS_P2_DMA_RING != 0;
+  constexpr bool DMAW = !WRES && !F8 && NT == 256;
   static_assert(!DMAW || (KG == 2 && UPS == 4), "the DMA weight ring hard-codes 128-byte rows per group (two K-steps of four 16-byte units): offsets, slot stride and the host plan's wbytes");
   constexpr int NBP = BN / 8;                  // 1 KB requests per weight group
   constexpr int NPW = (NBP + NWV - 1) / NWV;   // ... per wave (the last round may be partial)
-  uint4 rwA[NWU], rwB[RING3 ? NWU : 1], rwC[RING3 ? NWU : 1];
+  uint4 rwA[NWU];
   // this thread's (row, unit-in-group) of the streamed weight tile never changes: keep the row's byte offset (32 bits, through a buffer
   // descriptor of the weight shadow: a unit past the row's real K, a row past Cout or an idle thread carries the out-of-range offset and
   // arrives as zeros -- no 64-bit row pointers to keep (they were spilled next to three register sets), no select after the load)
@@ -785,7 +745,6 @@ __device__ __forceinline__ void conv_p2_body(const ConvArgs& a, const P2Args& g,
   TL_STAMP();                                            // tables requested
   if (t_first < t_end) okm_next = pfetch(txi, tyi, b);   // the first patch is in flight while the weights are staged
   TL_STAMP();                                            // first patch requested
-  if constexpr (RING3) { wfetch(rwA, 0); wfetch(rwB, 1); wfetch(rwC, 2); }
   if (WRES) {
     // resident weights: rows padded with zeros to a multiple of 4 K-steps (the pipelined K loop runs whole register groups).
     // LDS DMA (buffer_load ... lds, 1 KB per wave instruction): all of a wave's requests are in flight at once and no VGPR is
@@ -809,10 +768,9 @@ __device__ __forceinline__ void conv_p2_body(const ConvArgs& a, const P2Args& g,
   }
   TL_STAMP();
   if (P2_DBG(128)) return;                     // ablation: prologue only (tables, resident weights, first patch fetch)
-  constexpr int P2_NS = YS_P2_EPI_DIRECT ? 4 * NR : 8;
-  float st1[P2_NS], st2[P2_NS];                // BN statistics of this workgroup's tiles (per-lane column sums)
+  float st1[8], st2[8];                        // BN statistics of this workgroup's tiles (per-lane column sums)
 #pragma unroll
-  for (int e = 0; e < P2_NS; e++) { st1[e] = 0.f; st2[e] = 0.f; }
+  for (int e = 0; e < 8; e++) { st1[e] = 0.f; st2[e] = 0.f; }
 
   // Counted waits (round 4).  vmcnt counts loads AND stores on this part and retires them in issue order.  The tile loop used to open
   // with s_waitcnt vmcnt(0): besides the prefetched patch that also drained the previous tile's output stores, which a CU retires at
@@ -822,8 +780,10 @@ __device__ __forceinline__ void conv_p2_body(const ConvArgs& a, const P2Args& g,
   // are unconditional, masked lanes carry the out-of-range offset), means the patch has landed while the stores keep draining under the
   // LDS writes, the next prefetch and the K loop.  Anything else the epilogue issued (accumulate / residual / y loads) only makes the
   // number outstanding larger, i.e. the wait longer -- never too short.  The weight / table DMA (inline asm, invisible to the
-  // compiler) is waited for once, in front of the loop.
-  constexpr int NST = (YS_P2_EPI_DIRECT || !YS_P2_COUNTED_WAIT) ? 0 : p2_epi_stores(MR, NR);
+  // compiler) is waited for once, in front of the loop.  This relies on loads and stores retiring in issue order on the shared counter -- what hipcc's own
+  // wait insertion assumes on gfx9-family parts.  (Suspected and withdrawn once in round 4 when the config-5 determinism test failed with it; the bisection,
+  // profiles/README.md, cleared it: the cause was packed-FP32 statistics, and with -fno-slp-vectorize the combination is stable in 8 / 8 model-level rounds.)
+  constexpr int NST = p2_epi_stores(MR, NR);
   YS_WAIT_VM0();
   for (int tile = t_first; tile < t_end; tile += t_step) {
     const int oy0 = tyi * g.TH, ox0 = txi * g.TW;
@@ -832,7 +792,7 @@ __device__ __forceinline__ void conv_p2_body(const ConvArgs& a, const P2Args& g,
     TL_STAMP2();
     ys_barrier_lds();                         // previous tile's epilogue staging (patch region) and tables are settled
     TL_STAMP2();
-    if (!WRES && !RING3 && !DMAW) wfetch(rwA, 0);
+    if (!WRES && !DMAW) wfetch(rwA, 0);
 #pragma unroll
     for (int k = 0; k < NPU; k++) {
       unsigned d = pdesc[k];
@@ -864,7 +824,7 @@ __device__ __forceinline__ void conv_p2_body(const ConvArgs& a, const P2Args& g,
     ys_wait_vm<NST>();                        // (without it -- the epilogue's stores are unconditional now -- the class is 3 % slower: 5.10 -> 5.25 ms)
     const bool more = tile + t_step < t_end;
     if constexpr (DMAW) { wdma(0, 0); if (ngroups > 1) wdma(1, 1); }   // BEFORE the patch requests: the first groups' waits then leave the patch in flight
-    if (!LATE && more) okm_next = pfetch(ntx, nty, nb);
+    if (more) okm_next = pfetch(ntx, nty, nb);
 
     // resident weights: the accumulators start as the first K-step's products (MFMA with a zero C operand -- an inline constant, no
     // registers cleared: 4 * MR * NR v_mov per tile in a kernel whose busiest pipe is the VALU); streamed weights enter the K loop
@@ -943,21 +903,6 @@ __device__ __forceinline__ void conv_p2_body(const ConvArgs& a, const P2Args& g,
     const bool in_bf8 = F8 && a.f8 == 2;      // uniform: the input operand is a gradient quantised to e5m2
     if (WRES) {
       if (in_bf8) kloop(sW, 0, (g.nsteps + G - 1) / G, P2Tag1{}); else kloop(sW, 0, (g.nsteps + G - 1) / G, P2Tag0{});
-    } else if constexpr (RING3) {
-      constexpr int NGS = KG / G;               // register groups per streamed weight slot
-      // invariant at a group g = 0 (mod 3): rwA holds group g (already in LDS slot g & 1), rwB group g + 1, rwC group g + 2
-      auto ring_step = [&](uint4 (&rf)[NWU], uint4 (&rs)[NWU], const int grp) {
-        wfetch(rf, grp + 3);                    // unconditional (past the end: zeros); three groups of MFMAs to land
-        if (in_bf8) kloop(sW + (grp & 1) * BN * g.wpitch, grp * KG, NGS, P2Tag1{}); else kloop(sW + (grp & 1) * BN * g.wpitch, grp * KG, NGS, P2Tag0{});
-        wstore(rs, (grp + 1) & 1);
-        ys_barrier_lds();
-      };
-      int grp = 0;
-#pragma unroll 1
-      for (; grp + 3 <= ngroups; grp += 3) { ring_step(rwA, rwB, grp); ring_step(rwB, rwC, grp + 1); ring_step(rwC, rwA, grp + 2); }
-      if (grp < ngroups) { ring_step(rwA, rwB, grp); if (grp + 1 < ngroups) ring_step(rwB, rwC, grp + 1); }
-      // the next tile: its patch and its first three weight groups are requested now and land under the epilogue
-      if (tile + t_step < t_end) { wfetch(rwA, 0); wfetch(rwB, 1); wfetch(rwC, 2); }
     } else if constexpr (DMAW) {
       constexpr int NGS = KG / G;
       // Counted waits: vmcnt(N) with N = the requests of THIS wave known to be younger than group grp's -- group grp + 1's (issued one
@@ -966,7 +911,7 @@ __device__ __forceinline__ void conv_p2_body(const ConvArgs& a, const P2Args& g,
       int slot = 0;
 #pragma unroll 1
       for (int grp = 0; grp < ngroups; grp++) {
-        ys_wait_vm_dyn((grp + 1 < ngroups ? nmine : 0) + ((grp < 2 && more && !LATE) ? NPU : 0));
+        ys_wait_vm_dyn((grp + 1 < ngroups ? nmine : 0) + ((grp < 2 && more) ? NPU : 0));
         if (grp < 3) TL_STAMP2();
         ys_barrier_lds();                       // group grp is in LDS for every wave; nobody still reads the slot of group grp - 1
         if (grp < 3) TL_STAMP2();
@@ -1015,33 +960,16 @@ __device__ __forceinline__ void conv_p2_body(const ConvArgs& a, const P2Args& g,
 #pragma unroll
           for (int r = 0; r < 4; r++) acc[mf][nf][r] *= dq;
     }
-#if YS_P2_EPI_DIRECT
-    (void)stg;
 #ifdef YS_P2_TIMELINE
-    if (!P2_DBG(4)) p2_epilogue_direct<MR, NR, RED>(a, acc, orow, pv, n0, st1, st2, [&]() { TL_STAMP(); });
+    if (!P2_DBG(4)) p2_epilogue<MR, NR, RED, YS_EPI_BATCH_P2>(a, acc, orow, pv, n0, stg, st1, st2, [&]() { TL_STAMP(); });
 #else
-    if (!P2_DBG(4)) p2_epilogue_direct<MR, NR, RED>(a, acc, orow, pv, n0, st1, st2);
-#endif
-#else
-    // LATE: the next tile's patch is requested inside the epilogue, right after the accumulators have been staged (their registers are
-    // free then; requested straight after the K loop the forward variants spilled five patch units to scratch -- each spill a wait
-    // for its own load, five exposed HBM round trips per tile)
-    auto late_fetch = [&]() { if (LATE && tile + t_step < t_end) okm_next = pfetch(ntx, nty, nb); };
-#ifdef YS_P2_TIMELINE
-    if (!P2_DBG(4)) p2_epilogue<MR, NR, RED, YS_EPI_BATCH_P2(NPU)>(a, acc, orow, pv, n0, stg, st1, st2, [&]() { TL_STAMP(); }, late_fetch);
-#else
-    if (!P2_DBG(4)) p2_epilogue<MR, NR, RED, YS_EPI_BATCH_P2(NPU)>(a, acc, orow, pv, n0, stg, st1, st2, YsNoStamp(), late_fetch);
-#endif
+    if (!P2_DBG(4)) p2_epilogue<MR, NR, RED, YS_EPI_BATCH_P2>(a, acc, orow, pv, n0, stg, st1, st2);
 #endif
     TL_STAMP();
     txi = ntx; tyi = nty; b = nb;
   }
   YS_WAIT_VM0();                               // a workgroup without tiles still has its table / weight DMA in flight: it must land before the LDS is released
-#if YS_P2_EPI_DIRECT
-  if (RED ? a.nred > 0 : a.stats != nullptr) p2_stats_flush_direct<NR, NWV, 1>(a, n0, st1, st2, (float*)sPb, (long)vbx);
-#else
   if (RED ? a.nred > 0 : a.stats != nullptr) p2_stats_flush<NR, NWV>(a, n0, st1, st2, (float*)sPb, (long)vbx);
-#endif
   if (F8 && a.amax && blockIdx.y == 0) ys_amax_update(a.amax, amx);
   TL_STAMP();
 #ifdef YS_P2_TIMELINE
@@ -1073,7 +1001,6 @@ conv_p2_group_kernel(P2Group grp) {
   for (int k = 0; k + 1 < YS_GROUP_MAX; k++) pi += (int)(k + 1 < grp.n && bx >= grp.end[k]);
   const int start = pi ? grp.end[pi - 1] : 0;
   const P2Prob& pr = grp.p[pi];
-#if YS_P2_GROUP_COPY
   // The problem's arguments are copied into registers once (round 4).  Read in place -- a dynamically indexed slot of the kernel-argument
   // segment -- hipcc re-loads fields where they are used: 81-109 s_load instructions per variant against 36-44 in conv_p2_kernel, many
   // of them inside the K loop, and every one is followed by s_waitcnt lgkmcnt(0), which drains the wave's LDS reads as well (the
@@ -1082,9 +1009,6 @@ conv_p2_group_kernel(P2Group grp) {
   const P2Args g = pr.g;
   const int* const tab = pr.tab;
   conv_p2_body<MR, NR, WRES, NPU, NT, 0, RED>(a, g, tab, bx - start, grp.end[pi] - start);
-#else
-  conv_p2_body<MR, NR, WRES, NPU, NT, 0, RED>(pr.a, pr.g, pr.tab, bx - start, grp.end[pi] - start);
-#endif
 }
 
 
@@ -1177,9 +1101,13 @@ static bool p2_f8_tile_ok(int mr, int nr, int wres, int npu) {
 }
 // force_mr / force_npu (0 = free): grouped launches need every problem on the kernel variant of the group's largest problem
 // plan sweep (tools/dev/r06/p2_sweep.py through ys_debug_p2_force): a register-tile height, a tile width and an output-channel split imposed on every plan of the
-// process; 0 = the cost model's own choice.  Triage only -- nothing in the package sets them.
+// process; 0 = the cost model's own choice.  Triage library only (-DYS_TRIAGE, `build.py triage`): unsynchronised process-global state; the product sees constants.
+#ifdef YS_TRIAGE
 static int g_p2_force_mr = 0, g_p2_force_tw = 0, g_p2_force_nr = 0;
 extern "C" __attribute__((visibility("default"))) int ys_debug_p2_force(int mr, int tw, int nr) { g_p2_force_mr = mr; g_p2_force_tw = tw; g_p2_force_nr = nr; return 0; }
+#else
+constexpr int g_p2_force_mr = 0, g_p2_force_tw = 0, g_p2_force_nr = 0;
+#endif
 static P2Plan conv_p2_plan(const ConvArgs& a, int force_mr = 0, int force_npu = 0, bool want_full = true, int force_nr = 0) {
   P2Plan p{};
   if (g_p2_force_mr && !force_mr) force_mr = g_p2_force_mr;
@@ -1237,7 +1165,7 @@ static P2Plan conv_p2_plan(const ConvArgs& a, int force_mr = 0, int force_npu = 
   g.kg = wres ? g.nsteps : P2_KG;     // conv_p2_kernel::KG
   if (!wres && g.kg > g.nsteps) g.kg = g.nsteps;
   g.wpitch = wres ? wp(nsteps4 * ups) : wp(g.kg * ups);
-  const bool dmaw = !wres && !f8 && YS_P2_DMA_RING != 0;   // conv_p2_body::DMAW (every streamed bf16 variant has 256 threads): three ring slots of bn 128-byte rows
+  const bool dmaw = !wres && !f8;   // conv_p2_body::DMAW (every streamed bf16 variant has 256 threads): three ring slots of bn 128-byte rows
   const size_t wbytes = wres ? (wres_bytes + 1023) / 1024 * 1024 : (dmaw ? (size_t)3 * bn * 128 : (size_t)2 * bn * g.wpitch * 16);   // resident set: whole 1 KB LDS-DMA requests
   const size_t tab = ((size_t)g.nsp * 16 + 15) / 16 * 16;
   const int gy = ys_cdiv(a.Cout, bn);
@@ -1446,7 +1374,7 @@ static int conv_p2_dispatch(hipStream_t st, const ConvArgs& a, const P2Plan& p) 
 #define P2F(M_, N_, F_, R_) { \
     if (p.wres) return p.npu == 6 ? conv_p2_launch_t<M_, N_, 1, 6, 256, F_, R_>(st, a, p) : conv_p2_launch_t<M_, N_, 1, 12, 256, F_, R_>(st, a, p); \
     return p.npu == 6 ? conv_p2_launch_t<M_, N_, 0, 6, 256, F_, R_>(st, a, p) : conv_p2_launch_t<M_, N_, 0, 12, 256, F_, R_>(st, a, p); }
-#define P2(M_, N_) if (p.mr == M_ && p.nr == N_) { if (a.f8) P2F(M_, N_, 1, 0) else if (a.nred > 0 || (a.accumulate && YS_P2_EPI_DIRECT)) P2F(M_, N_, 0, 1) else P2F(M_, N_, 0, 0) }
+#define P2(M_, N_) if (p.mr == M_ && p.nr == N_) { if (a.f8) P2F(M_, N_, 1, 0) else if (a.nred > 0) P2F(M_, N_, 0, 1) else P2F(M_, N_, 0, 0) }
     if (a.f8 && a.nred > 0) { ys_set_error("conv p2: the fused BN-backward reduction has no fp8 variant"); return YS_ERR_UNSUPPORTED; }
 #ifdef YS_P2_ONE          // compile-time triage: a single register tile (seconds instead of minutes per resource-usage experiment)
 #ifndef YS_P2_ONE_M
@@ -1510,7 +1438,7 @@ static int conv_p2_group_launch_t(hipStream_t st, const ConvArgs* a, const P2Pla
 
 // variant dispatch of a grouped launch (n >= 1 problems already planned on ONE variant; gxs = workgroups per problem)
 static int conv_p2_group_dispatch(hipStream_t st, const ConvArgs* a, const P2Plan* p, int n, const int* gxs, size_t lds) {
-  const bool red = a[0].nred > 0 || (a[0].accumulate && YS_P2_EPI_DIRECT);
+  const bool red = a[0].nred > 0;
 #define P2GF(M_, N_, R_) { \
     if (p[0].wres) return p[0].npu == 6 ? conv_p2_group_launch_t<M_, N_, 1, 6, 256, R_>(st, a, p, n, gxs, lds) : conv_p2_group_launch_t<M_, N_, 1, 12, 256, R_>(st, a, p, n, gxs, lds); \
     return p[0].npu == 6 ? conv_p2_group_launch_t<M_, N_, 0, 6, 256, R_>(st, a, p, n, gxs, lds) : conv_p2_group_launch_t<M_, N_, 0, 12, 256, R_>(st, a, p, n, gxs, lds); }
@@ -1900,7 +1828,8 @@ int ys_conv_launch(hipStream_t st, int dtype, const ConvArgs& a) {
   return conv_launch_dtype<float>(st, a);
 }
 
-// Development aid (tools/dev/p2_plans.py): the P2 plan of a forward convolution geometry as text -- no device needed.
+// Development aid (tools/dev/p2_plans.py, triage library only): the P2 plan of a forward convolution geometry as text -- no device needed.
+#ifdef YS_TRIAGE
 extern "C" __attribute__((visibility("default"))) int ys_debug_p2_plan(int B, int Hin, int Win, int Cin, int Cout, int k, int s, int in_ldc, char* buf, int cap) {
   ConvArgs a{};
   a.B = B; a.Hin = Hin; a.Win = Win; a.Cin = Cin; a.Cout = Cout; a.KH = a.KW = k; a.SA = s; a.PAD = k / 2;
@@ -1914,3 +1843,4 @@ extern "C" __attribute__((visibility("default"))) int ys_debug_p2_plan(int B, in
            p.gx, p.gy, p.lds, p.g.ppb, p.g.prb, (p.g.prb - p.g.PW * p.g.ppb) / 16, p.g.wpitch, cyc);
   return 1;
 }
+#endif

@@ -63,27 +63,11 @@ __device__ inline void ys_bnred_put(const ConvArgs& a, int c, int which, long ro
 // conv_p2_body waits for "all but the last p2_epi_stores() vector-memory operations" at the top of a tile, i.e. for the prefetched
 // patch but NOT for the previous tile's output stores (gfx9-family parts count loads and stores on one in-order vmcnt).
 __host__ __device__ constexpr int p2_epi_stores(int mr, int nr) { return (16 * mr + 64 / (nr * 2) - 1) / (64 / (nr * 2)); }
-#ifndef YS_EPI_ACC_PREFETCH
-#define YS_EPI_ACC_PREFETCH 1   // 1: the dgrad (RED) variants; 2: every variant that may accumulate (measured equal: forward variants do not accumulate in a training step)
-#endif
-#ifndef YS_EPI_SCALAR_STATS
-#define YS_EPI_SCALAR_STATS 0
-#endif
-#ifndef YS_EPI_LDS_NOALIAS
-#define YS_EPI_LDS_NOALIAS 0
-#endif
-#ifndef YS_EPI_FULL_UNROLL
-#define YS_EPI_FULL_UNROLL 1   // forward store loop fully unrolled: hipcc then SEES the NITER stores in a row, which is what lets conv_p2_body wait with vmcnt(NITER)
-                               // (behind a rolled loop it credits one trip and re-drains).  REQUIRES -fno-slp-vectorize (yolosharp_amd/build.py): with SLP-packed
-                               // statistics the unrolled form is the reproducer of the run-to-run nondeterminism (profiles/README.md, round 4); 0 = `unroll 2`
-#endif
 template <int M> struct EpiMode { static constexpr int value = M; };
 struct YsNoStamp { __device__ inline void operator()() const {} };   // timeline hook of triage builds (-DYS_P2_TIMELINE): nothing in the product
-// after_stage: called once the accumulators have been rounded into the staging rows (they are dead from there on) -- conv_p2_body's
-// streamed-weight variants request the next tile's patch there, into the registers the accumulators just freed
-template <int MR, int NR, int RED = 0, int BMAX = 4 /* most store-loop iterations whose accumulate operands are requested ahead */, class SF = YsNoStamp, class AF = YsNoStamp>
+template <int MR, int NR, int RED = 0, int BMAX = 4 /* most store-loop iterations whose accumulate operands are requested ahead */, class SF = YsNoStamp>
 __device__ inline void p2_epilogue(const ConvArgs& a, f32x4 (&acc)[MR][NR], const int (&orow)[MR], const bool (&pv)[MR],
-                                   int n0, char* stg, float (&s1)[8], float (&s2)[8], SF stamp = SF(), AF after_stage = AF()) {
+                                   int n0, char* stg, float (&s1)[8], float (&s2)[8], SF stamp = SF()) {
   typedef bf16_t T;
   constexpr int BN = NR * 16;
   constexpr int PITCH = (BN + 8) * 2;         // bytes per staged pixel row
@@ -133,8 +117,9 @@ __device__ inline void p2_epilogue(const ConvArgs& a, f32x4 (&acc)[MR][NR], cons
   // iterations are requested here too (round 4).  Loaded inside the store loop each iteration was load -> s_waitcnt vmcnt(0) -> add ->
   // store, i.e. NITER dependent memory round trips per tile, each also draining the previous iteration's store: accumulate launches ran
   // 1.15-1.9x their overwrite twins (per-launch records: 3x3 32 -> 32 at 160 x 160: 40.6 us against 26.6).  Every lane re-reads exactly the
-  // 16 bytes it will overwrite, so the order of load and store per address is program order.
-  constexpr bool ACC_PRE = (RED != 0 || YS_EPI_ACC_PREFETCH == 2) && YS_EPI_ACC_PREFETCH != 0 && NITER <= BMAX;   // BMAX: what the caller's register budget affords (conv_p2: 4 vectors; conv_gemm: all)
+  // 16 bytes it will overwrite, so the order of load and store per address is program order.  Only the dgrad (RED) variants: extending it
+  // to every variant that may accumulate measured equal -- forward variants do not accumulate in a training step.
+  constexpr bool ACC_PRE = RED != 0 && NITER <= BMAX;   // BMAX: what the caller's register budget affords (conv_p2: 4 vectors; conv_gemm: all)
   uint4 ov[ACC_PRE ? NITER : 1];
   if (ACC_PRE && a.accumulate) {
     const ys_rsrcv_t rsO = ys_make_rsrcv(a.y, 0x7ffffff0u);
@@ -179,7 +164,6 @@ __device__ inline void p2_epilogue(const ConvArgs& a, f32x4 (&acc)[MR][NR], cons
   }
   stamp();
   ys_wave_sync_lds();                          // the staged rows (written by other lanes of this wave) are IN LDS before the reads below are issued
-  after_stage();
   stamp();
   const bool do_stats_rt = !RED && a.stats != nullptr && !EPI_DBG(512);
   // eval-mode BatchNorm folded into the conv (Convs.cs:48 with running statistics): applied on the wide path to the
@@ -221,32 +205,12 @@ __device__ inline void p2_epilogue(const ConvArgs& a, f32x4 (&acc)[MR][NR], cons
     uint4 val = ys_zero16();
     {
       if (rofs != YS_BUF_OOB) {
-#if YS_EPI_LDS_NOALIAS && !defined(YS_EMU_BUILD)
-        {   // triage (round-4 determinism bisection): the staged vector through an LDS read whose destination registers cannot be the address register
-          const unsigned sa = (unsigned)(uintptr_t)(stg + px * PITCH + cv * 16);
-#if YS_EPI_LDS_NOALIAS == 2
-          asm volatile("ds_read_b128 %0, %1\n\ts_waitcnt lgkmcnt(0)\n\ts_nop 7\n\ts_nop 7\n\ts_nop 7\n\ts_nop 7" : "=&v"(val) : "v"(sa) : "memory");
-#else
-          asm volatile("ds_read_b128 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=&v"(val) : "v"(sa) : "memory");
-#endif
-        }
-#else
         val = *(const uint4*)(stg + px * PITCH + cv * 16);
-#endif
         float f[8];
         ys_unpack<T>(val, f);
         if (do_stats) {
-#if YS_EPI_SCALAR_STATS && !defined(YS_EMU_BUILD)
-          // triage (round-4 determinism bisection): the sums through single v_add_f32 / v_fmac_f32 (inline asm: hipcc cannot pair them into v_pk_*_f32)
-#pragma unroll
-          for (int e = 0; e < 8; e++) {
-            asm volatile("v_add_f32 %0, %0, %1" : "+v"(s1[e]) : "v"(f[e]));
-            asm volatile("v_fmac_f32 %0, %1, %1" : "+v"(s2[e]) : "v"(f[e]));
-          }
-#else
 #pragma unroll
           for (int e = 0; e < 8; e++) { s1[e] += f[e]; s2[e] += f[e] * f[e]; }
-#endif
         }
         if (bn_eval) {
 #pragma unroll
@@ -292,41 +256,32 @@ __device__ inline void p2_epilogue(const ConvArgs& a, f32x4 (&acc)[MR][NR], cons
     ys_bufst16(rsY, (rofs != YS_BUF_OOB && !EPI_DBG(256)) ? rofs + (unsigned)c * 2u : YS_BUF_OOB, val);
   };
   if (EPI_DBG(1024)) { ys_wave_sync(); return; }
-  if (RED) {
-#pragma unroll                                // fully: yv[it] must be a register, not an indexed (scratch) array
-    for (int it = 0; it < NITER; it++) store_iter(it, EpiMode<2>{});
-  } else {
-#if YS_EPI_FULL_UNROLL
+  // Fully unrolled.  RED: yv[it] must be a register, not an indexed (scratch) array.  Forward: hipcc then SEES the NITER stores in a row, which is
+  // what lets conv_p2_body wait with vmcnt(NITER) (behind a rolled loop it credits one trip and re-drains).  REQUIRES -fno-slp-vectorize
+  // (yolosharp_amd/build.py): with SLP-packed statistics the unrolled form was the reproducer of the run-to-run nondeterminism (profiles/README.md,
+  // round 4; tests/test_isa.py guards the conclusion).
 #pragma unroll
-    for (int it = 0; it < NITER; it++) store_iter(it, EpiMode<2>{});
-#else
-#pragma unroll 2
-    for (int it = 0; it < NITER; it++) store_iter(it, EpiMode<2>{});
-#endif
-  }
+  for (int it = 0; it < NITER; it++) store_iter(it, EpiMode<2>{});
   stamp();
   ys_wave_sync();
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
-// Direct epilogue (round 3, default: YS_P2_EPI_DIRECT = 1).  After the MFMA a lane (li, q) already owns 4 CONSECUTIVE channels
+// Direct epilogue (round 3).  conv_halo_kernel (conv_halo.h) is its only caller: one wave per SIMD with registers to spare, no LDS left for a staging slice.
+// For conv_p2_kernel and conv_gemm_kernel it lost the A/B (round 3, MI355X, config 2: staged 10.19-10.21 ms/step; direct with 8-byte stores 10.93, against
+// 10.65 then; direct with the 16-lane row swap 10.58-10.60 -- the 4*NR-per-lane statistics and the masked selects cost the 168-register variants more, 12-160 B
+// of scratch, than the LDS round trip; profiles/README.md).  After the MFMA a lane (li, q) already owns 4 CONSECUTIVE channels
 // (n0 + nf*16 + 4q ..) of pixel mf*16 + li for every (mf, nf) fragment, i.e. 8 contiguous bytes of the bf16 NHWC row.  The staged
 // epilogue above transposes through LDS to reach 16-byte stores: s_memtime stamps put that at 3.0-4.9 thousand cycles per tile
 // (row table ~1k, staging writes 0.5-0.9k, two LDS round trips + the store loop 1.3-2.3k) against 2.5-3.5k for the whole K loop,
 // and phase ablation at 1.8 of conv_p2_kernel's 3.9 ms per YOLOv8n step, of which the stores themselves are 0.43 ms
 // (profiles/README.md, round 3).  Here the accumulators are rounded, reduced into the statistics and stored straight from registers
-// as 8-byte buffer stores -- no LDS, no row table, no wave rendezvous; the four q-lanes of a pixel write one contiguous 32-byte
-// sector per fragment.  Statistics are per-lane sums for the lane's own 4*NR channels (st[nf*4 + r]); the 16 pixel lanes of a DPP row
+// -- no LDS, no row table, no wave rendezvous: fragment pairs trade 16-lane rows (ys_row_swap) so that every lane stores 16 contiguous
+// bytes.  Statistics are per-lane sums for the lane's own 4*NR channels (st[nf*4 + r]); the 16 pixel lanes of a DPP row
 // are combined once per launch (p2_stats_flush_direct).
 // RED = 1 (backward form): gradient accumulation and the fused BN-backward reduction, operands prefetched for all fragments before
 // the first is consumed.  RED = 0 (forward / eval form): bias, eval-BN, SiLU, residual, BN statistics (+ an in-loop accumulate for
 // the launches that have no RED variant).
-#ifndef YS_P2_EPI_DIRECT
-#define YS_P2_EPI_DIRECT 0     // measured (round 3, MI355X, config 2): staged 10.19-10.21 ms/step; direct with 8-byte stores 10.93 (against 10.65 then); direct with the 16-lane row swap (YS_EPI_SWAP16, 16-byte stores from registers) 10.58-10.60 -- the 4*NR-per-lane statistics and the masked selects cost the 168-register variants more (12-160 B of scratch) than the LDS round trip
-#endif
-#ifndef YS_EPI_SWAP16
-#define YS_EPI_SWAP16 1        // direct epilogue: fragment pairs trade 16-lane rows (v_permlane16_swap_b32) so that every lane stores 16 contiguous bytes
-#endif
 __device__ inline uint2 ys_ld8(const void* p) { return *(const uint2*)p; }
 // v_permlane16_swap_b32 (gfx950): the odd 16-lane rows of `a` trade places with the even rows of `b`:
 //   a' = [a.row0, b.row0, a.row2, b.row2],  b' = [a.row1, b.row1, a.row3, b.row3]      (probe: tools/dev/permlane_swap_probe.hip)
@@ -432,8 +387,7 @@ __device__ inline void p2_epilogue_direct(const ConvArgs& a, f32x4 (&acc)[MR][NR
 #pragma unroll
           for (int r = 0; r < 4; r++) { const float du = ok ? g[r] : 0.f; s1[nf * 4 + r] += du; s2[nf * 4 + r] += ok ? du * yf[r] : 0.f; }
         }
-        if constexpr (!YS_EPI_SWAP16) ys_bufst8(rsY, (ok && !EPI_DBG(256)) ? roff[mf] + (unsigned)c * 2u : YS_BUF_OOB, pk);
-        else if constexpr ((nf & 1) == 0 && nf + 1 < NR) pkE[mf] = pk;
+        if constexpr ((nf & 1) == 0 && nf + 1 < NR) pkE[mf] = pk;
         else if constexpr (nf & 1) store_pair(pkE[mf], pk, roff[mf], roff[mf], n0 + (nf - 1) * 16, n0 + nf * 16);
         else {                                 // last, unpaired column: pixel rows mf / mf + 1 pair up instead
           if ((mf & 1) == 0 && mf + 1 < MR) pkE[mf] = pk;
@@ -541,8 +495,7 @@ __device__ inline void p2_epilogue_direct(const ConvArgs& a, f32x4 (&acc)[MR][NR
           pk.x = ys_pack_bf16x2(f[0], f[1]); pk.y = ys_pack_bf16x2(f[2], f[3]);
         }
       }
-      if (!YS_EPI_SWAP16) ys_bufst8(rsY, (ok && !EPI_DBG(256)) ? roff[mf] + (unsigned)c * 2u : YS_BUF_OOB, pk);
-      else if ((nf & 1) == 0 && nf + 1 < NR) pkE[mf] = pk;
+      if ((nf & 1) == 0 && nf + 1 < NR) pkE[mf] = pk;
       else if (nf & 1) store_pair(pkE[mf], pk, roff[mf], roff[mf], n0 + (nf - 1) * 16, n0 + nf * 16);
       else {                                   // last, unpaired column: pixel rows mf / mf + 1 pair up instead
         if ((mf & 1) == 0 && mf + 1 < MR) pkE[mf] = pk;

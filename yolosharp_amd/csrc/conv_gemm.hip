@@ -24,20 +24,8 @@
 #include "conv_epi.h"
 #include "conv_halo.h"
 #include <atomic>
-#ifndef YS_GEMM_EPI_DIRECT
-#define YS_GEMM_EPI_DIRECT 0   // 1: this kernel's epilogue goes straight from the accumulator registers (16-byte stores after a 16-lane row swap, conv_epi.h
-                               // p2_epilogue_direct) and the NEXT tile's first operand requests are issued before it (no LDS staging to alias the stages).
-                               // Built and measured in round 4 (same box, alternating, config 2): conv_gemm_kernel 1.23 -> 1.27-1.28 ms/step -- a wave's
-                               // direct store covers 16 pixel rows x 64 B (half lines), the staged form 8 rows x 128 B, and the store path is what this
-                               // epilogue is bound by -- so the staged form stays
-#endif
-#ifndef YS_EPI_BATCH_GEMM
-#define YS_EPI_BATCH_GEMM 16
-#endif
-#ifndef YS_GEMM_READ_AHEAD
-#define YS_GEMM_READ_AHEAD 0   // measured (round 3, MI355X): no difference -- config 5 bf16 88.51 vs 88.57 ms/step, config 4 32.62 vs 32.71, config 2 10.24 vs 10.22; the K-tile is bound by LDS bytes (operand DMA + fragment reads ~220 KB per K-tile pair and CU), not by the exposed round trip
-#endif
 #include <cstdlib>
+constexpr int YS_EPI_BATCH_GEMM = 16;   // store-loop iterations whose accumulate operands p2_epilogue requests ahead (BMAX): all of them
 
 // ablation switches for performance triage (YS_GEMM_DBG bits; compiled in only with -DYS_GEMM_ABLATE = `build.py ablate`):
 // 1 = A operand requests out of range, 2 = B operand requests out of range (zeros, no L2 traffic), 4 = no MFMAs, 8 = no epilogue;
@@ -168,10 +156,9 @@ conv_gemm_kernel(ConvArgs a, GemmArgs g) {
   const int t_first = xcd_order ? (int)(blockIdx.x & 7) * t_per_xcd + (int)(blockIdx.x >> 3) : (int)blockIdx.x;
   const int t_end = xcd_order ? (((int)(blockIdx.x & 7) + 1) * t_per_xcd < g.mtiles ? ((int)(blockIdx.x & 7) + 1) * t_per_xcd : g.mtiles) : g.mtiles;
 
-  constexpr int NS = YS_GEMM_EPI_DIRECT ? 4 * NR : 8;
-  float st1[NS], st2[NS];
+  float st1[8], st2[8];
 #pragma unroll
-  for (int e = 0; e < NS; e++) { st1[e] = 0.f; st2[e] = 0.f; }
+  for (int e = 0; e < 8; e++) { st1[e] = 0.f; st2[e] = 0.f; }
 
   // row coordinates of a tile's A pieces + the requests of its first nstage - 1 K-tiles
   auto open_tile = [&](const int tile) {
@@ -186,18 +173,15 @@ conv_gemm_kernel(ConvArgs a, GemmArgs g) {
         abase[j] = (int)((((long)b * bstride + (long)aiy[j] * a.Win + aix[j]) * ldu) << 4);
       } else { aiy[j] = -(1 << 20); aix[j] = 0; abase[j] = 0; }
     }
-    ys_barrier_lds();                         // the tap table is written; every wave is done with the stages (and, staged epilogue, with the staging area)
+    ys_barrier_lds();                         // the tap table is written; every wave is done with the stages and with the epilogue's staging area
     for (int p = 0; p < g.nstage - 1 && p < g.nkt; p++) issue(p, p);
   };
-  // Direct epilogue (YS_GEMM_EPI_DIRECT): a tile is OPENED before the previous tile's epilogue runs -- its first K-tiles are in flight
-  // while the accumulators are rounded, reduced into the statistics and stored (~8 thousand cycles per 128 x 128 tile in the round-3
-  // stamps, during which the operand pipeline was empty, and then another DMA round trip before the first MFMA).  The epilogue's stores
-  // are younger than those requests, so the first waits of the next K loop also wait for them -- which the staged form did anyway.
-  constexpr bool EARLY = YS_GEMM_EPI_DIRECT != 0;
-  if (EARLY && t_first < t_end) open_tile(t_first);
+  // (The direct epilogue of conv_epi.h with the next tile opened before it -- no staging to alias the stages -- was built and measured in round 4, same box,
+  // alternating, config 2: conv_gemm_kernel 1.23 -> 1.27-1.28 ms/step.  A wave's direct store covers 16 pixel rows x 64 B, half lines, the staged form 8 rows x
+  // 128 B, and the store path is what this epilogue is bound by.)
   for (int tile = t_first; tile < t_end; tile += t_step) {
     const int m0 = tile * BM;
-    if (!EARLY) open_tile(tile);
+    open_tile(tile);
     GTL_STAMP();
     f32x4 acc[MR][NR];
 #pragma unroll
@@ -243,27 +227,9 @@ conv_gemm_kernel(ConvArgs a, GemmArgs g) {
         }
         continue;
       }
-      constexpr bool AHEAD = YS_GEMM_READ_AHEAD && !(WM == 4 && NR == 5 && !RED);   // 256x80 forward: 36 more live registers spill
-      if constexpr (AHEAD) {
-      // both K-steps' fragments are requested before the first MFMA: the second step's LDS round trip runs under the first step's
-      // MFMAs (ds_reads return in order, the compiler waits with lgkmcnt(N)), one exposed round trip per K-tile instead of two
-      uint4 fw[2][NR], fx[2][MR];
-#pragma unroll
-      for (int ks = 0; ks < 2; ks++) {
-        const int ko = ks ? koff1 : koff0;
-#pragma unroll
-        for (int nf = 0; nf < NR; nf++) fw[ks][nf] = *(const uint4*)(sb + brow0 + nf * 2048 + ko);
-#pragma unroll
-        for (int mf = 0; mf < MR; mf++) fx[ks][mf] = *(const uint4*)(sb + arow0 + mf * 2048 + ko);
-      }
-      YS_SCHED_FENCE();
-#pragma unroll
-      for (int ks = 0; ks < 2; ks++)
-#pragma unroll
-        for (int nf = 0; nf < NR; nf++)
-#pragma unroll
-          for (int mf = 0; mf < MR; mf++) acc[mf][nf] = ys_mma<T>(fw[ks][nf], fx[ks][mf], acc[mf][nf]);
-      } else {
+      // one K-step's fragments at a time.  (Both K-steps' fragments requested before the first MFMA, round 3, MI355X: no difference -- config 5 bf16 88.51 vs
+      // 88.57 ms/step, config 4 32.62 vs 32.71, config 2 10.24 vs 10.22; the K-tile is bound by LDS bytes, operand DMA + fragment reads ~220 KB per K-tile
+      // pair and CU, not by the exposed round trip.)
 #pragma unroll
       for (int ks = 0; ks < 2; ks++) {
         const int ko = ks ? koff1 : koff0;
@@ -278,11 +244,9 @@ conv_gemm_kernel(ConvArgs a, GemmArgs g) {
 #pragma unroll
           for (int mf = 0; mf < MR; mf++) acc[mf][nf] = ys_mma<T>(fw[nf], fx[mf], acc[mf][nf]);
       }
-      }
     }
     GTL_STAMP();
-    if (EARLY) { if (tile + t_step < t_end) open_tile(tile + t_step); }   // (its barrier: every wave finished reading this tile's stages)
-    else ys_barrier_lds();                    // every wave finished reading the stages: they become the epilogue staging area
+    ys_barrier_lds();                         // every wave finished reading the stages: they become the epilogue staging area
 
     int orow[MR];                             // row indices / byte offsets of a launch fit 31 bits (conv_gemm_plan)
     bool pv[MR];
@@ -305,19 +269,10 @@ conv_gemm_kernel(ConvArgs a, GemmArgs g) {
           for (int r = 0; r < 4; r++) acc[mf][nf][r] *= dq;
     }
     char* stg = sStage + wave * (16 * MR * (NR * 16 + 8) * 2 + 16 * MR * 16);
-#if YS_GEMM_EPI_DIRECT
-    (void)stg;
-    if (!GEMM_DBG(8)) p2_epilogue_direct<MR, NR, RED>(a, acc, orow, pv, n0 + wn * NR * 16, st1, st2);
-#else
     if (!GEMM_DBG(8)) p2_epilogue<MR, NR, RED, YS_EPI_BATCH_GEMM>(a, acc, orow, pv, n0 + wn * NR * 16, stg, st1, st2);
-#endif
     GTL_STAMP();
   }
-#if YS_GEMM_EPI_DIRECT
-  if (RED ? a.nred > 0 : a.stats != nullptr) p2_stats_flush_direct<NR, WM, WN>(a, n0, st1, st2, (float*)sStage, (long)blockIdx.x);
-#else
   if (RED ? a.nred > 0 : a.stats != nullptr) conv_stats_flush_grid<NR, WM, WN>(a, n0, st1, st2, (float*)sStage, (long)blockIdx.x);
-#endif
   GTL_STAMP();
 #ifdef YS_P2_TIMELINE
   if (tl_p) tl_p[0] = (unsigned long long)tl_n;
@@ -532,7 +487,7 @@ int ys_conv_gemm_launch(hipStream_t st, const ConvArgs& a) {
   if (p.halo) return conv_halo_launch(st, a, p);
   if (a.f8 == 1 && a.nred > 0) { ys_set_error("conv gemm: the fused BN-backward reduction belongs to dgrad launches (e5m2 input)"); return YS_ERR_UNSUPPORTED; }
   // RED variants: bf16 and e5m2-input (fp8-mode dgrad) launches that carry BN-backward segments
-#define GM(A_, B_, C_, D_) if (p.wm == A_ && p.wn == B_ && p.mr == C_ && p.nr == D_) return a.f8 == 2 ? (a.nred > 0 ? conv_gemm_launch_t<A_, B_, C_, D_, 2, 1>(st, a, p) : conv_gemm_launch_t<A_, B_, C_, D_, 2>(st, a, p)) : (a.f8 ? conv_gemm_launch_t<A_, B_, C_, D_, 1>(st, a, p) : ((a.nred > 0 || (a.accumulate && YS_GEMM_EPI_DIRECT)) ? conv_gemm_launch_t<A_, B_, C_, D_, 0, 1>(st, a, p) : conv_gemm_launch_t<A_, B_, C_, D_, 0>(st, a, p)));
+#define GM(A_, B_, C_, D_) if (p.wm == A_ && p.wn == B_ && p.mr == C_ && p.nr == D_) return a.f8 == 2 ? (a.nred > 0 ? conv_gemm_launch_t<A_, B_, C_, D_, 2, 1>(st, a, p) : conv_gemm_launch_t<A_, B_, C_, D_, 2>(st, a, p)) : (a.f8 ? conv_gemm_launch_t<A_, B_, C_, D_, 1>(st, a, p) : (a.nred > 0 ? conv_gemm_launch_t<A_, B_, C_, D_, 0, 1>(st, a, p) : conv_gemm_launch_t<A_, B_, C_, D_, 0>(st, a, p)));
   GM(2, 2, 4, 5) GM(2, 2, 4, 4) GM(4, 1, 4, 5) GM(4, 1, 4, 4)
 #undef GM
   return YS_ERR_UNSUPPORTED;

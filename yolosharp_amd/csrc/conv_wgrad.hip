@@ -203,9 +203,7 @@ wgrad_reduce_kernel(const float* __restrict__ partial, int splits, long n, int c
 //   TAPS == 1: 4 waves split the 32-pixel K-blocks and are combined through LDS at the end.
 // K order inside a tile is the tile-local pixel index p = ty*TW + tx for both operands; pixels outside the image (or the
 // tile's 32-pixel rounding) read a zero dy row.  Partials go to partial[blockIdx.x][Cout][taps][Cin] (fixed-order reduce).
-#ifndef YS_WG_TWO_MAX
 #define YS_WG_TWO_MAX 2        // 9-wave weight-gradient tiles of up to this many MFMA fragments run two workgroups per CU (96 registers).  4 measured (round 4): the 2 x 2 tile spills 32 B and the 32 -> 32 layers go 29.4 -> 42.0 us (400 partial slabs instead of 229) -- stays 2
-#endif
 template <int MRA, int NRB, int TAPS>
 __global__ void __launch_bounds__(TAPS == 9 ? 576 : 256, (TAPS == 9 && MRA * NRB <= YS_WG_TWO_MAX) ? 5 : 1)   // small 9-wave tiles: 96 registers = two workgroups per CU
 conv_wgrad_tr_kernel(WgradArgs a) {
@@ -398,9 +396,13 @@ static bool wgrad_view_bytes(const WgradArgs& a, unsigned& dyb, unsigned& xb) {
   return true;
 }
 // plan sweep (tools/dev/r06/wg_sweep.py through ys_debug_wgrad_force): tile height / log2 width / workgroups per CU imposed on every plan of the process; 0 = the
-// cost model's own choice.  Triage only.
+// cost model's own choice.  Triage library only (-DYS_TRIAGE, `build.py triage`): unsynchronised process-global state; the product sees constants.
+#ifdef YS_TRIAGE
 static int g_wg_force_th = 0, g_wg_force_tws = 0, g_wg_force_percu = 0;
 extern "C" __attribute__((visibility("default"))) int ys_debug_wgrad_force(int th, int tws, int per_cu) { g_wg_force_th = th; g_wg_force_tws = tws; g_wg_force_percu = per_cu; return 0; }
+#else
+constexpr int g_wg_force_th = 0, g_wg_force_tws = 0, g_wg_force_percu = 0;
+#endif
 static WgPlan wgrad_tr_plan(const WgradArgs& a) {
   WgPlan p{};
   { unsigned d0, x0; if (!wgrad_view_bytes(a, d0, x0)) return p; }

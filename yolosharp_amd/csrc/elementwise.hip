@@ -430,9 +430,7 @@ int ys_bn_fin_apply_launch(hipStream_t st, int dtype, const void* y, long rows, 
 // ------------------------------------------------------------------ per-channel reductions over rows
 // thread t owns channel vector cv = t % CG and row lane t / CG; workgroup blk owns a contiguous row range.
 // MODE 0: BN backward (sum du, sum du*xhat), optional res_grad += dz.   MODE 1: plain column sum.
-#ifndef CR_U
-#define CR_U 2
-#endif
+constexpr int CR_U = 2;   // rows per software-pipelined trip of chan_reduce_kernel
 template <class T, int MODE, bool RG = false, bool ACT = false>
 __global__ void __launch_bounds__(EW_THREADS)
 chan_reduce_kernel(const T* __restrict__ dz, int dz_ldc, int dz_coff, const T* __restrict__ y, long rows, int C,

@@ -18,9 +18,7 @@
 
 #define LS_THREADS 256
 #define TAL_LIST_CAP 8192   // in-box anchors of one (image, box) pair walked through an LDS list (16 KB of 16-bit indices; A <= 65535 on that path)
-#ifndef TAL_T
 #define TAL_T 256           // threads of a tal_metrics_kernel workgroup.  Measured (round 4, ~550 pairs, flat grid): 128 threads 74 us, 256 64 us, 512 105 us, 1024 119 us
-#endif
 #define TAL_REGS ((8448 + TAL_T - 1) / TAL_T)   // assigner top-k: metrics per thread kept in registers (covers the 8400 anchors of 640x640)
 #define CIOU_EPS 1e-7f
 
@@ -395,9 +393,6 @@ __device__ inline void tal_metrics_pair(const LossArgs& a, const int* __restrict
     if (ingt) atomicOr(&s_ingt[ai >> 5], 1u << (ai & 31));
   }
   __syncthreads();
-#if defined(TAL_ABLATE) && TAL_ABLATE == 1
-  return;
-#endif
   if (valid) {
     // compaction: thread t owns the words [t * wpt, (t + 1) * wpt) -- ascending anchor order in the list, so the result does not depend on timing
     const int wpt = (nw + TAL_T - 1) / TAL_T;
@@ -450,9 +445,6 @@ __device__ inline void tal_metrics_pair(const LossArgs& a, const int* __restrict
     }
   }
   __syncthreads();                                                  // the top-k rounds read other threads' alr entries (global, same workgroup)
-#if defined(TAL_ABLATE) && TAL_ABLATE == 2
-  return;
-#endif
   // select_topk_candidates (Tal.cs:144-168): 10 largest align values; ties -> lowest anchor index
   if (a.A <= TAL_REGS * TAL_T) {
     // every BASELINE shape (A = 8400 <= 33 * 256): a thread's metrics (anchors tid + j * 256) stay in registers for the ten rounds --
