@@ -332,6 +332,33 @@ YS_API int ys_conv_bwd(ys_ctx* ctx, int dtype, const float* x_nchw, int B, int C
                        const float* w_oihw, int Cout, int k, int stride, const float* dy_nchw,
                        float* dx_nchw, float* dw_oihw);
 
+/* ---- YOLOv11-only operators, one stateless call per kernel family (unit parity of csrc/attn_dw.hip against float64).
+ * fp32 HOST arrays at the edge in the reference's layouts; dtype = YS_F32 or YS_BF16 is the storage type on the device.  Every
+ * operand is placed inside a WIDER NHWC device buffer the way the model's shared activation buffers hold it: `*_pad` extra
+ * channels behind the tensor (attention) or a row pitch `*_ldc` >= C and a first channel `*_coff` (depthwise; 0, 0 = dense).
+ * The rest of each buffer the kernels write to -- and a guard behind the probability matrices -- is pre-filled with a sentinel;
+ * *view_intact (may be NULL) is 1 when every sentinel element survived the call, 0 when a kernel wrote outside its view.
+ * Unsupported geometry (N > 1600, kd > 128, hd > 256, C not a multiple of the 16-byte vector, C / vector > 256 for the weight
+ * gradient) returns the launcher's YS_ERR_UNSUPPORTED before any kernel is started.
+ *
+ * Attention core of Block.Attention (Block.cs:763-805), per head: P = softmax(q^T k * kd^-0.5), ao = v P^T.
+ * qkv [B, heads*(2*kd+hd), N] in the reference's view(B, heads, 2*kd+hd, N) order; ao [B, heads*hd, N];
+ * P (optional, may be NULL) [B*heads, N, N] fp32 probabilities, row = query. */
+YS_API int ys_attn_fwd(ys_ctx* ctx, int dtype, const float* qkv, int B, int N, int heads, int kd, int hd, int ldq_pad, int ldo_pad,
+                       float* ao, float* P, int32_t* view_intact);
+/* its backward: runs the forward for P, then dq | dk | dv in the qkv layout.  dv_in [B, heads*hd, N] (may be NULL = zeros) is the
+ * gradient that already sits in the v slice (it arrived through pe(v)); the kernels ADD P^T dO to it. */
+YS_API int ys_attn_bwd(ys_ctx* ctx, int dtype, const float* qkv, int B, int N, int heads, int kd, int hd, int ldq_pad, int ldo_pad,
+                       const float* dao, const float* dv_in, float* dqkv, int32_t* view_intact);
+/* Depthwise 3x3 / stride 1 / pad 1 (Convs.DWConv, Convs.cs:108-114; groups = C): x, y [B,C,H,W], w [C,1,3,3]. */
+YS_API int ys_dwconv3x3_fwd(ys_ctx* ctx, int dtype, const float* x, int B, int C, int H, int W, const float* w,
+                            int x_ldc, int x_coff, int y_ldc, int y_coff, float* y, int32_t* view_intact);
+/* its autograd given dy [B,C,H,W]: dx [B,C,H,W] (may be NULL; with accumulate != 0 it holds the gradient already in the
+ * buffer on entry and receives dx_in + dx, one rounding) and dw [C,1,3,3] (may be NULL; fp32 for both dtypes). */
+YS_API int ys_dwconv3x3_bwd(ys_ctx* ctx, int dtype, const float* x, int B, int C, int H, int W, const float* w, const float* dy,
+                            int x_ldc, int x_coff, int dx_ldc, int dx_coff, int accumulate, float* dx, float* dw,
+                            int32_t* view_intact);
+
 /* ---- per-block entry points: a TorchSharp-free body for the reference's block modules, one stateful handle per
  *      module instance (SURVEY 8b "ys_c2f_fwd/bwd, ys_c3k2_fwd/bwd, ys_sppf_fwd/bwd, ys_proto_fwd/bwd").  The handle IS a
  *      ys_model: ys_model_num_tensors / tensor_info / set_tensor / get_tensor / get_grad / init_weights / set_training /

@@ -42,8 +42,31 @@ class _RoundSTE(torch.autograd.Function):
 rste = _RoundSTE.apply
 
 
+class _RoundFwd(torch.autograd.Function):
+    """Rounded on the way forward only (an MFMA operand that is rounded in registers: its gradient is never stored)."""
+    @staticmethod
+    def forward(ctx, x):
+        return bf16r(x)
+
+    @staticmethod
+    def backward(ctx, g):
+        return g
+
+
+class _RoundBwd(torch.autograd.Function):
+    """Identity forward; the gradient is rounded (dS enters the dq / dk products of the MFMA kernels as bf16)."""
+    @staticmethod
+    def forward(ctx, x):
+        return x.clone()
+
+    @staticmethod
+    def backward(ctx, g):
+        return bf16r(g)
+
+
 def _conv_forward(self, x, fuse_residual=None):
-    w = bf16r(self.conv.weight)
+    # (a depthwise layer -- Attention.pe, the DWConv towers of Detect -- reads its fp32 master weights: csrc/attn_dw.hip has no bf16 weight shadow)
+    w = self.conv.weight if self.conv.groups > 1 else bf16r(self.conv.weight)
     y = F.conv2d(x, w, None, self.conv.stride, self.conv.padding, self.conv.dilation, self.conv.groups)
     y = rste(y)                                   # raw conv output stored bf16; the batch statistics see the rounded values
     z = self.act(self.bn(y))
@@ -66,16 +89,18 @@ def _plain_conv_forward(self, x):
 
 def _attention_forward(self, x):
     """C2PSA attention (Block.cs:719-810) with the engine's storage points (csrc/model.hip add_c2psa, csrc/attn_dw.hip): q / k / v are the
-    stored (bf16) qkv output; softmax probabilities are rounded to bf16 for the second product (the MFMA kernels' P operand); the attention
-    output is stored bf16; `attention + pe(v)` is one rounding inside pe's BatchNorm + SiLU pass.  Returns the INPUT of proj: proj carries
+    stored (bf16) qkv output; softmax probabilities are rounded to bf16 for the second product (the MFMA kernels' P operand) while dP = dO^T v
+    stays fp32 on the way back (rounding it, as a straight-through rounding of P would, is amplified by the cancellation in dS = P (dP - t) and is
+    not what the kernels do); dS is rounded to bf16 in front of the dq / dk products; the attention output is stored bf16; `attention + pe(v)` is one rounding inside pe's BatchNorm + SiLU pass.  Returns the INPUT of proj: proj carries
     the PSABlock shortcut in its own apply pass (see _psablock_forward)."""
     B, C, H, W = x.shape
     N = H * W
     qkv = self.qkv(x)
     q, k, v = qkv.view(B, self.num_heads, self.key_dim * 2 + self.head_dim, N).split([self.key_dim, self.key_dim, self.head_dim], dim=2)
-    attn = rste(((q.transpose(-2, -1) @ k) * self.scale).softmax(dim=-1))
+    attn = _RoundFwd.apply(_RoundBwd.apply((q.transpose(-2, -1) @ k) * self.scale).softmax(dim=-1))
     a = rste((v @ attn.transpose(-2, -1)).view(B, C, H, W))
-    return _conv_forward(self.pe, v.reshape(B, C, H, W), fuse_residual=a)
+    # pe's input gradient is stored (bf16) in the v copy's buffer before the attention backward adds P^T dO to it: rounded on its own
+    return _conv_forward(self.pe, _RoundBwd.apply(v.reshape(B, C, H, W)), fuse_residual=a)
 
 
 def _psablock_forward(self, x):

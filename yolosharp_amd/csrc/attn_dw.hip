@@ -74,10 +74,17 @@ dwconv3x3_kernel(const T* __restrict__ x, int x_ldc, int x_coff, int B, int H, i
   }
 }
 
+int ys_dwconv_supported(int dtype, int C) {
+  const int epl = dtype == YS_BF16 ? 8 : 4;
+  if (C % epl) { ys_set_error("dwconv: C=%d must be a multiple of %d", C, epl); return YS_ERR_UNSUPPORTED; }
+  return YS_OK;
+}
+
 int ys_dwconv_launch(hipStream_t st, int dtype, int flip, const void* x, int x_ldc, int x_coff, int B, int H, int W, int C,
                      const float* w, void* y, int y_ldc, int y_coff, int accumulate) {
   const int epl = dtype == YS_BF16 ? 8 : 4;
-  if (C % epl) { ys_set_error("dwconv: C=%d must be a multiple of %d", C, epl); return YS_ERR_UNSUPPORTED; }
+  YS_TRY(ys_dwconv_supported(dtype, C));
+  YsKprofScope prof(st, flip ? "dwconv_dgrad" : "dwconv_fwd");
   const long n = (long)B * H * ((W + DW_PX - 1) / DW_PX) * (C / epl);
   const int g = ys_cdiv(n, AD_THREADS);
 #define DW(TT, FL) YS_LAUNCH((dwconv3x3_kernel<TT, FL>), g, AD_THREADS, st, (const TT*)x, x_ldc, x_coff, B, H, W, C, w, (TT*)y, y_ldc, y_coff, accumulate)
@@ -189,13 +196,19 @@ int ys_dwconv_wgrad_blocks(long rows, int C, int dtype) {
   return (int)nb;
 }
 
-int ys_dwconv_wgrad_launch(hipStream_t st, int dtype, const void* x, int x_ldc, int x_coff, const void* dy, int B, int H, int W,
-                           int C, float* partial, float* grad) {
+int ys_dwconv_wgrad_supported(int dtype, int C) {
   const int epl = dtype == YS_BF16 ? 8 : 4;
   if (C % epl || C / epl > AD_THREADS) { ys_set_error("dwconv wgrad: unsupported C=%d", C); return YS_ERR_UNSUPPORTED; }
+  return YS_OK;
+}
+
+int ys_dwconv_wgrad_launch(hipStream_t st, int dtype, const void* x, int x_ldc, int x_coff, const void* dy, int B, int H, int W,
+                           int C, float* partial, float* grad) {
+  YS_TRY(ys_dwconv_wgrad_supported(dtype, C));
   const int nb = ys_dwconv_wgrad_blocks((long)B * H * W, C, dtype);
   const long xb = ((long)B * H * W * x_ldc - x_coff) * (dtype == YS_BF16 ? 2L : 4L);     // bytes of the x view from its first channel
   if (xb <= 0 || xb >= (1L << 31)) { ys_set_error("dwconv wgrad: input view of %ld bytes exceeds the 2 GB descriptor range", xb); return YS_ERR_UNSUPPORTED; }
+  YsKprofScope prof(st, "dwconv_wgrad");
   if (dtype == YS_BF16) YS_LAUNCH((dwconv_wgrad_kernel<bf16_t>), nb, AD_THREADS, st, (const bf16_t*)x, x_ldc, x_coff, (const bf16_t*)dy, B, H, W, C, partial, (unsigned)xb);
   else YS_LAUNCH((dwconv_wgrad_kernel<float>), nb, AD_THREADS, st, (const float*)x, x_ldc, x_coff, (const float*)dy, B, H, W, C, partial, (unsigned)xb);
   YS_LAUNCH(dwconv_wgrad_finalize_kernel, ys_cdiv(9 * C, 32), AD_THREADS, st, (const float*)partial, nb, 9 * C, grad);
@@ -630,17 +643,25 @@ static int attn_bwd_kv_dispatch(hipStream_t st, const T* qkv, int ldq, int B, in
   return YS_ERR_UNSUPPORTED;
 }
 
+// the range both launchers serve: ATT_NMAX tokens (the LDS row of the scalar kernels), kd <= 128 (sQ), hd <= 256 (sO, the widest attn_bwd_kv_kernel instantiation)
+int ys_attn_supported(int N, int kd, int hd) {
+  if (N < 1 || N > ATT_NMAX || kd < 1 || kd > 128 || hd < 1 || hd > 256) { ys_set_error("attention: N=%d kd=%d hd=%d outside the supported range", N, kd, hd); return YS_ERR_UNSUPPORTED; }
+  return YS_OK;
+}
+
 int ys_attn_fwd_launch(hipStream_t st, int dtype, const void* qkv, int ldq, int B, int N, int heads, int kd, int hd,
                        void* ao, int ldo, float* P) {
-  if (N > ATT_NMAX || kd > 128 || hd > 256) { ys_set_error("attention: N=%d kd=%d hd=%d outside the supported range", N, kd, hd); return YS_ERR_UNSUPPORTED; }
+  YS_TRY(ys_attn_supported(N, kd, hd));
   const float scale = 1.0f / sqrtf((float)kd);   // Math.Pow(key_dim, -0.5) (Block.cs:733)
   if (attn_mfma_ok(dtype, ldq, ldo, N, heads, kd, hd)) {
+    YsKprofScope prof(st, "attn_fwd", "mfma");
     const size_t lb = (size_t)att_np16(N) * ATT_KP + (size_t)(64 + 64) * att_tp(N);
     static std::atomic<unsigned> attr_f{0};
     YS_TRY(attn_lds_attr(attn_fwd_mfma_kernel, lb, attr_f));
     YS_LAUNCH_LDS(attn_fwd_mfma_kernel, dim3(ys_cdiv(N, ATT_QB), B * heads), AD_THREADS, lb, st, (const bf16_t*)qkv, ldq, B, N, heads, scale, (bf16_t*)ao, ldo, P);
     return YS_OK;
   }
+  YsKprofScope prof(st, "attn_fwd", "scalar");
   dim3 grid(ys_cdiv(N, AD_THREADS / 64), B * heads);
   if (dtype == YS_BF16) YS_LAUNCH((attn_fwd_kernel<bf16_t>), grid, AD_THREADS, st, (const bf16_t*)qkv, ldq, B, N, heads, kd, hd, scale, (bf16_t*)ao, ldo, P);
   else YS_LAUNCH((attn_fwd_kernel<float>), grid, AD_THREADS, st, (const float*)qkv, ldq, B, N, heads, kd, hd, scale, (float*)ao, ldo, P);
@@ -649,8 +670,10 @@ int ys_attn_fwd_launch(hipStream_t st, int dtype, const void* qkv, int ldq, int 
 
 int ys_attn_bwd_launch(hipStream_t st, int dtype, const void* qkv, int ldq, int B, int N, int heads, int kd, int hd,
                        const void* dao, int ldo, const float* P, float* dS, void* dqkv) {
+  YS_TRY(ys_attn_supported(N, kd, hd));      // (had no check of its own: N > ATT_NMAX would have run attn_bwd_q_kernel past its LDS row)
   const float scale = 1.0f / sqrtf((float)kd);
   if (attn_mfma_ok(dtype, ldq, ldo, N, heads, kd, hd)) {
+    YsKprofScope prof(st, "attn_bwd", "mfma");
     const size_t lb = (size_t)att_np16(N) * ATT_VP + (size_t)(32 + 64) * att_tp(N);
     static std::atomic<unsigned> attr_q{0}, attr_kv{0};
     YS_TRY(attn_lds_attr(attn_bwd_q_mfma_kernel, lb, attr_q));
@@ -660,6 +683,7 @@ int ys_attn_bwd_launch(hipStream_t st, int dtype, const void* qkv, int ldq, int 
     YS_LAUNCH_LDS(attn_bwd_kv_mfma_kernel, dim3(ys_cdiv(N, ATT_QB), B * heads), AD_THREADS, lk, st, (const bf16_t*)qkv, ldq, B, N, heads, scale, (const bf16_t*)dao, ldo, P, (const float*)dS, (bf16_t*)dqkv);
     return YS_OK;
   }
+  YsKprofScope prof(st, "attn_bwd", "scalar");
   dim3 grid(ys_cdiv(N, AD_THREADS / 64), B * heads);
   if (dtype == YS_BF16) {
     YS_LAUNCH((attn_bwd_q_kernel<bf16_t>), grid, AD_THREADS, st, (const bf16_t*)qkv, ldq, B, N, heads, kd, hd, scale, (const bf16_t*)dao, ldo, P, dS, (bf16_t*)dqkv);

@@ -1,6 +1,7 @@
 // ops_api.hip -- per-operator entry points of the C ABI (unit parity; a TorchSharp-free Conv wrapper).
 #include "ys_internal.h"
 #include "ys_kernels.h"
+#include <cstring>
 #include <vector>
 
 namespace {
@@ -217,5 +218,263 @@ extern "C" int ys_conv_bwd(ys_ctx* ctx, int dtype, const float* x_nchw, int B, i
     for (int ci = 0; ci < Cin; ci++)
       for (int t = 0; t < taps; t++) dw_oihw[((size_t)co * Cin + ci) * taps + t] = gw[((size_t)co * taps + t) * Cin + ci];
   YS_CHECK_HIP(hipGetLastError());
+  return YS_OK;
+}
+
+// ------------------------------------------------------------------ YOLOv11-only operators (attn_dw.hip), one call per kernel family
+// The operands sit inside WIDER NHWC device buffers, as in the model's shared activation buffers; everything outside the views is a
+// sentinel that must survive the call.
+namespace {
+constexpr int kSentinelByte = 0x4E;          // bf16 0x4E4E = fp32 0x4E4E4E4E = 8.65e8: finite, and ruinous when a kernel reads it as data
+constexpr size_t kGuardFloats = 64;          // sentinel floats behind the [B*heads][N][N] matrices
+inline int ys_epl(int dtype) { return dtype == YS_BF16 ? 8 : 4; }
+inline size_t ys_es(int dtype) { return dtype == YS_BF16 ? 2 : 4; }
+
+int alloc_filled(DevBuf& b, size_t bytes, hipStream_t st) {
+  YS_TRY(b.alloc(bytes));
+  YS_CHECK_HIP(hipMemsetAsync(b.p, kSentinelByte, bytes ? bytes : 16, st));
+  return YS_OK;
+}
+
+// fp32 NCHW host tensor [B][C][rpb] -> channels [coff, coff + C) of the pre-filled [B*rpb][ld] device buffer `wide`
+int stage_view(hipStream_t st, int dtype, const float* host, int B, int C, long rpb, void* wide, int ld, int coff) {
+  const int epl = ys_epl(dtype);
+  const size_t es = ys_es(dtype);
+  const long rows = (long)B * rpb;
+  DevBuf d32, compact;
+  YS_TRY(d32.alloc((size_t)rows * C * 4));
+  YS_TRY(compact.alloc((size_t)rows * C * es));
+  YS_CHECK_HIP(hipMemcpyAsync(d32.p, host, (size_t)rows * C * 4, hipMemcpyHostToDevice, st));
+  YS_TRY(ys_pack_input_launch(st, dtype, (const float*)d32.p, B, C, 1, (int)rpb, C, compact.p));
+  if (ld % epl == 0 && coff % epl == 0) {
+    YS_TRY(ys_copy_view_launch(st, dtype, compact.p, C, 0, rows, C, wide, ld, coff, 0));
+  } else {
+    // a pitch off the 16-byte grid (the scalar attention kernels accept it; ys_copy_view_launch moves 16-byte vectors): rows placed by the host
+    std::vector<char> hc((size_t)rows * C * es), hw((size_t)rows * ld * es);
+    YS_CHECK_HIP(hipMemcpyAsync(hc.data(), compact.p, hc.size(), hipMemcpyDeviceToHost, st));
+    YS_CHECK_HIP(hipMemcpyAsync(hw.data(), wide, hw.size(), hipMemcpyDeviceToHost, st));
+    YS_CHECK_HIP(hipStreamSynchronize(st));
+    for (long r = 0; r < rows; r++) memcpy(hw.data() + ((size_t)r * ld + coff) * es, hc.data() + (size_t)r * C * es, (size_t)C * es);
+    YS_CHECK_HIP(hipMemcpyAsync(wide, hw.data(), hw.size(), hipMemcpyHostToDevice, st));
+  }
+  YS_CHECK_HIP(hipStreamSynchronize(st));      // d32 / compact are temporaries of this scope
+  return YS_OK;
+}
+
+// channels [coff, coff + C) of a [B*rpb][ld] device buffer -> fp32 NCHW host tensor
+int fetch_view(hipStream_t st, int dtype, const void* wide, int ld, int coff, int B, int C, long rpb, float* host) {
+  DevBuf d32;
+  const size_t n = (size_t)B * C * rpb;
+  YS_TRY(d32.alloc(n * 4));
+  YS_TRY(ys_unpack_nchw_launch(st, dtype, wide, ld, coff, B, C, rpb, (float*)d32.p));
+  YS_CHECK_HIP(hipMemcpyAsync(host, d32.p, n * 4, hipMemcpyDeviceToHost, st));
+  YS_CHECK_HIP(hipStreamSynchronize(st));
+  return YS_OK;
+}
+
+// *ok &= every byte of the [rows][ld] buffer outside channels [coff, coff + C) is still the sentinel
+int check_sentinel(hipStream_t st, const void* wide, long rows, int ld, int coff, int C, size_t es, int* ok) {
+  if (ld == C) return YS_OK;
+  std::vector<unsigned char> h((size_t)rows * ld * es);
+  YS_CHECK_HIP(hipMemcpyAsync(h.data(), wide, h.size(), hipMemcpyDeviceToHost, st));
+  YS_CHECK_HIP(hipStreamSynchronize(st));
+  const size_t lo = (size_t)coff * es, hi = (size_t)(coff + C) * es, pitch = (size_t)ld * es;
+  for (long r = 0; r < rows; r++)
+    for (size_t i = 0; i < pitch; i++) {
+      if (i == lo) i = hi;
+      if (i < pitch && h[(size_t)r * pitch + i] != kSentinelByte) { *ok = 0; return YS_OK; }
+    }
+  return YS_OK;
+}
+// ... and the kGuardFloats behind the `n` floats of a workspace matrix
+int check_guard(hipStream_t st, const void* base, size_t n, int* ok) {
+  unsigned char h[kGuardFloats * 4];
+  YS_CHECK_HIP(hipMemcpyAsync(h, (const float*)base + n, sizeof h, hipMemcpyDeviceToHost, st));
+  YS_CHECK_HIP(hipStreamSynchronize(st));
+  for (size_t i = 0; i < sizeof h; i++)
+    if (h[i] != kSentinelByte) *ok = 0;
+  return YS_OK;
+}
+
+struct AttnBufs {
+  DevBuf qkv, ao, P;
+  int Cq = 0, Co = 0, ldq = 0, ldo = 0;
+  long rows = 0;
+  size_t pp = 0;     // elements of a [B*heads][N][N] matrix
+};
+
+int attn_args(const char* who, ys_ctx* ctx, int dtype, const float* qkv, int B, int N, int heads, int kd, int hd, int ldq_pad, int ldo_pad) {
+  YS_REQUIRE(ctx && qkv, "%s: null argument", who);
+  YS_REQUIRE(dtype == YS_F32 || dtype == YS_BF16, "%s: bad dtype %d", who, dtype);
+  YS_REQUIRE(B >= 1 && heads >= 1 && ldq_pad >= 0 && ldo_pad >= 0, "%s: B=%d heads=%d ldq_pad=%d ldo_pad=%d", who, B, heads, ldq_pad, ldo_pad);
+  YS_TRY(ys_attn_supported(N, kd, hd));           // the launchers' own refusal, before anything is staged
+  YS_REQUIRE((2 * kd + hd) % ys_epl(dtype) == 0 && hd % ys_epl(dtype) == 0, "%s: kd=%d hd=%d: channel counts must be multiples of %d", who, kd, hd, ys_epl(dtype));
+  return YS_OK;
+}
+
+// qkv staged into its padded view, ao / P pre-filled, ys_attn_fwd_launch
+int attn_forward_staged(hipStream_t st, int dtype, const float* qkv, int B, int N, int heads, int kd, int hd, int ldq_pad, int ldo_pad, AttnBufs& b) {
+  const size_t es = ys_es(dtype);
+  b.Cq = heads * (2 * kd + hd); b.Co = heads * hd; b.ldq = b.Cq + ldq_pad; b.ldo = b.Co + ldo_pad;
+  b.rows = (long)B * N; b.pp = (size_t)B * heads * N * N;
+  YS_TRY(alloc_filled(b.qkv, (size_t)b.rows * b.ldq * es, st));
+  YS_TRY(alloc_filled(b.ao, (size_t)b.rows * b.ldo * es, st));
+  YS_TRY(alloc_filled(b.P, (b.pp + kGuardFloats) * 4, st));
+  YS_TRY(stage_view(st, dtype, qkv, B, b.Cq, N, b.qkv.p, b.ldq, 0));
+  return ys_attn_fwd_launch(st, dtype, b.qkv.p, b.ldq, B, N, heads, kd, hd, b.ao.p, b.ldo, (float*)b.P.p);
+}
+}  // namespace
+
+extern "C" int ys_attn_fwd(ys_ctx* ctx, int dtype, const float* qkv, int B, int N, int heads, int kd, int hd, int ldq_pad, int ldo_pad,
+                           float* ao, float* P, int32_t* view_intact) {
+  YS_TRY(attn_args("ys_attn_fwd", ctx, dtype, qkv, B, N, heads, kd, hd, ldq_pad, ldo_pad));
+  YS_REQUIRE(ao, "ys_attn_fwd: null argument");
+  YS_CHECK_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  const size_t es = ys_es(dtype);
+  AttnBufs b;
+  YS_TRY(attn_forward_staged(st, dtype, qkv, B, N, heads, kd, hd, ldq_pad, ldo_pad, b));
+  YS_TRY(fetch_view(st, dtype, b.ao.p, b.ldo, 0, B, b.Co, N, ao));
+  if (P) YS_CHECK_HIP(hipMemcpyAsync(P, b.P.p, b.pp * 4, hipMemcpyDeviceToHost, st));
+  int ok = 1;
+  YS_TRY(check_sentinel(st, b.ao.p, b.rows, b.ldo, 0, b.Co, es, &ok));
+  YS_TRY(check_sentinel(st, b.qkv.p, b.rows, b.ldq, 0, b.Cq, es, &ok));
+  YS_TRY(check_guard(st, b.P.p, b.pp, &ok));
+  YS_CHECK_HIP(hipStreamSynchronize(st));
+  YS_CHECK_HIP(hipGetLastError());
+  if (view_intact) *view_intact = ok;
+  return YS_OK;
+}
+
+extern "C" int ys_attn_bwd(ys_ctx* ctx, int dtype, const float* qkv, int B, int N, int heads, int kd, int hd, int ldq_pad, int ldo_pad,
+                           const float* dao, const float* dv_in, float* dqkv, int32_t* view_intact) {
+  YS_TRY(attn_args("ys_attn_bwd", ctx, dtype, qkv, B, N, heads, kd, hd, ldq_pad, ldo_pad));
+  YS_REQUIRE(dao && dqkv, "ys_attn_bwd: null argument");
+  YS_CHECK_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  const size_t es = ys_es(dtype);
+  AttnBufs b;
+  YS_TRY(attn_forward_staged(st, dtype, qkv, B, N, heads, kd, hd, ldq_pad, ldo_pad, b));
+  DevBuf ddao, dgrad, dS;
+  YS_TRY(alloc_filled(ddao, (size_t)b.rows * b.ldo * es, st));
+  YS_TRY(alloc_filled(dgrad, (size_t)b.rows * b.ldq * es, st));
+  YS_TRY(alloc_filled(dS, (b.pp + kGuardFloats) * 4, st));
+  YS_TRY(stage_view(st, dtype, dao, B, b.Co, N, ddao.p, b.ldo, 0));
+  // the gradient buffer on entry: dv_in in the v slices (the kernels add to it); the q / k slices hold the sentinel value, so an
+  // element the kernels fail to write shows in the result
+  const int hs = 2 * kd + hd;
+  std::vector<float> init((size_t)b.rows * b.Cq);
+  float sent; { sent = ys_u2f(0x01010101u * (unsigned)kSentinelByte); }
+  for (int bi = 0; bi < B; bi++)
+    for (int c = 0; c < b.Cq; c++) {
+      const int h = c / hs, j = c - h * hs;
+      float* dst = init.data() + ((size_t)bi * b.Cq + c) * N;
+      const float* src = (j >= 2 * kd && dv_in) ? dv_in + ((size_t)bi * b.Co + h * hd + (j - 2 * kd)) * N : nullptr;
+      for (int n = 0; n < N; n++) dst[n] = j < 2 * kd ? sent : (src ? src[n] : 0.f);
+    }
+  YS_TRY(stage_view(st, dtype, init.data(), B, b.Cq, N, dgrad.p, b.ldq, 0));
+  YS_TRY(ys_attn_bwd_launch(st, dtype, b.qkv.p, b.ldq, B, N, heads, kd, hd, ddao.p, b.ldo, (const float*)b.P.p, (float*)dS.p, dgrad.p));
+  YS_TRY(fetch_view(st, dtype, dgrad.p, b.ldq, 0, B, b.Cq, N, dqkv));
+  int ok = 1;
+  YS_TRY(check_sentinel(st, dgrad.p, b.rows, b.ldq, 0, b.Cq, es, &ok));
+  YS_TRY(check_sentinel(st, ddao.p, b.rows, b.ldo, 0, b.Co, es, &ok));
+  YS_TRY(check_sentinel(st, b.qkv.p, b.rows, b.ldq, 0, b.Cq, es, &ok));
+  YS_TRY(check_sentinel(st, b.ao.p, b.rows, b.ldo, 0, b.Co, es, &ok));
+  YS_TRY(check_guard(st, b.P.p, b.pp, &ok));
+  YS_TRY(check_guard(st, dS.p, b.pp, &ok));
+  YS_CHECK_HIP(hipStreamSynchronize(st));
+  YS_CHECK_HIP(hipGetLastError());
+  if (view_intact) *view_intact = ok;
+  return YS_OK;
+}
+
+namespace {
+int dwconv_args(const char* who, ys_ctx* ctx, int dtype, const float* x, int B, int C, int H, int W, const float* w, int x_ldc, int x_coff,
+                int o_ldc, int o_coff) {
+  YS_REQUIRE(ctx && x && w, "%s: null argument", who);
+  YS_REQUIRE(dtype == YS_F32 || dtype == YS_BF16, "%s: bad dtype %d", who, dtype);
+  YS_REQUIRE(B >= 1 && C >= 1 && H >= 1 && W >= 1, "%s: B=%d C=%d H=%d W=%d", who, B, C, H, W);
+  YS_TRY(ys_dwconv_supported(dtype, C));
+  const int epl = ys_epl(dtype);
+  YS_REQUIRE(x_coff >= 0 && o_coff >= 0 && x_ldc >= x_coff + C && o_ldc >= o_coff + C && x_ldc % epl == 0 && x_coff % epl == 0 && o_ldc % epl == 0 && o_coff % epl == 0,
+             "%s: views (ldc %d coff %d), (ldc %d coff %d) must hold C=%d channels on the %d-element vector grid", who, x_ldc, x_coff, o_ldc, o_coff, C, epl);
+  return YS_OK;
+}
+// [C][1][3][3] host -> tap-major [9][C] device
+int dw_weights(hipStream_t st, const float* w, int C, DevBuf& d) {
+  std::vector<float> wt((size_t)9 * C);
+  for (int c = 0; c < C; c++)
+    for (int t = 0; t < 9; t++) wt[(size_t)t * C + c] = w[(size_t)c * 9 + t];
+  YS_TRY(d.alloc(wt.size() * 4));
+  YS_CHECK_HIP(hipMemcpyAsync(d.p, wt.data(), wt.size() * 4, hipMemcpyHostToDevice, st));
+  YS_CHECK_HIP(hipStreamSynchronize(st));
+  return YS_OK;
+}
+}  // namespace
+
+extern "C" int ys_dwconv3x3_fwd(ys_ctx* ctx, int dtype, const float* x, int B, int C, int H, int W, const float* w,
+                                int x_ldc, int x_coff, int y_ldc, int y_coff, float* y, int32_t* view_intact) {
+  YS_TRY(dwconv_args("ys_dwconv3x3_fwd", ctx, dtype, x, B, C, H, W, w, x_ldc, x_coff, y_ldc, y_coff));
+  YS_REQUIRE(y, "ys_dwconv3x3_fwd: null argument");
+  YS_CHECK_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  const size_t es = ys_es(dtype);
+  const long rows = (long)B * H * W;
+  DevBuf dx, dy, dw;
+  YS_TRY(alloc_filled(dx, (size_t)rows * x_ldc * es, st));
+  YS_TRY(alloc_filled(dy, (size_t)rows * y_ldc * es, st));
+  YS_TRY(stage_view(st, dtype, x, B, C, (long)H * W, dx.p, x_ldc, x_coff));
+  YS_TRY(dw_weights(st, w, C, dw));
+  YS_TRY(ys_dwconv_launch(st, dtype, 0, dx.p, x_ldc, x_coff, B, H, W, C, (const float*)dw.p, dy.p, y_ldc, y_coff, 0));
+  YS_TRY(fetch_view(st, dtype, dy.p, y_ldc, y_coff, B, C, (long)H * W, y));
+  int ok = 1;
+  YS_TRY(check_sentinel(st, dy.p, rows, y_ldc, y_coff, C, es, &ok));
+  YS_TRY(check_sentinel(st, dx.p, rows, x_ldc, x_coff, C, es, &ok));
+  YS_CHECK_HIP(hipGetLastError());
+  if (view_intact) *view_intact = ok;
+  return YS_OK;
+}
+
+extern "C" int ys_dwconv3x3_bwd(ys_ctx* ctx, int dtype, const float* x, int B, int C, int H, int W, const float* w, const float* dy,
+                                int x_ldc, int x_coff, int dx_ldc, int dx_coff, int accumulate, float* dx, float* dw,
+                                int32_t* view_intact) {
+  YS_TRY(dwconv_args("ys_dwconv3x3_bwd", ctx, dtype, x, B, C, H, W, w, x_ldc, x_coff, dx_ldc, dx_coff));
+  YS_REQUIRE(dy && (dx || dw), "ys_dwconv3x3_bwd: null argument");
+  if (dw) YS_TRY(ys_dwconv_wgrad_supported(dtype, C));
+  YS_CHECK_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  const size_t es = ys_es(dtype);
+  const long rows = (long)B * H * W;
+  DevBuf bx, bdy, bdx, bw, bpart, bgrad;
+  YS_TRY(alloc_filled(bx, (size_t)rows * x_ldc * es, st));
+  YS_TRY(bdy.alloc((size_t)rows * C * es));           // the incoming gradient is dense in the model too (the depthwise layer's own buffer)
+  YS_TRY(stage_view(st, dtype, x, B, C, (long)H * W, bx.p, x_ldc, x_coff));
+  YS_TRY(stage_view(st, dtype, dy, B, C, (long)H * W, bdy.p, C, 0));
+  int ok = 1;
+  if (dx) {
+    YS_TRY(alloc_filled(bdx, (size_t)rows * dx_ldc * es, st));      // without `accumulate` the view itself starts as the sentinel: an unwritten element shows
+    if (accumulate) YS_TRY(stage_view(st, dtype, dx, B, C, (long)H * W, bdx.p, dx_ldc, dx_coff));
+    YS_TRY(dw_weights(st, w, C, bw));
+    YS_TRY(ys_dwconv_launch(st, dtype, 1, bdy.p, C, 0, B, H, W, C, (const float*)bw.p, bdx.p, dx_ldc, dx_coff, accumulate ? 1 : 0));
+    YS_TRY(fetch_view(st, dtype, bdx.p, dx_ldc, dx_coff, B, C, (long)H * W, dx));
+    YS_TRY(check_sentinel(st, bdx.p, rows, dx_ldc, dx_coff, C, es, &ok));
+  }
+  if (dw) {
+    const size_t np = (size_t)ys_dwconv_wgrad_blocks(rows, C, dtype) * 9 * C;
+    YS_TRY(alloc_filled(bpart, (np + kGuardFloats) * 4, st));
+    YS_TRY(bgrad.alloc((size_t)9 * C * 4));
+    YS_CHECK_HIP(hipMemsetAsync(bgrad.p, 0, (size_t)9 * C * 4, st));
+    YS_TRY(ys_dwconv_wgrad_launch(st, dtype, bx.p, x_ldc, x_coff, bdy.p, B, H, W, C, (float*)bpart.p, (float*)bgrad.p));
+    std::vector<float> g((size_t)9 * C);
+    YS_CHECK_HIP(hipMemcpyAsync(g.data(), bgrad.p, g.size() * 4, hipMemcpyDeviceToHost, st));
+    YS_CHECK_HIP(hipStreamSynchronize(st));
+    for (int c = 0; c < C; c++)
+      for (int t = 0; t < 9; t++) dw[(size_t)c * 9 + t] = g[(size_t)t * C + c];
+    YS_TRY(check_guard(st, bpart.p, np, &ok));
+  }
+  YS_TRY(check_sentinel(st, bx.p, rows, x_ldc, x_coff, C, es, &ok));
+  YS_CHECK_HIP(hipStreamSynchronize(st));
+  YS_CHECK_HIP(hipGetLastError());
+  if (view_intact) *view_intact = ok;
   return YS_OK;
 }

@@ -279,6 +279,9 @@ int ys_f8_quant_weights_launch(hipStream_t st, const void* w_bf16, long n, const
 int ys_dwconv_launch(hipStream_t st, int dtype, int flip, const void* x, int x_ldc, int x_coff, int B, int H, int W, int C,
                      const float* w /*[9][C]*/, void* y, int y_ldc, int y_coff, int accumulate);
 int ys_dwconv_wgrad_blocks(long rows, int C, int dtype);
+int ys_dwconv_supported(int dtype, int C);             // YS_OK, or the launcher's own refusal (error text set) -- no kernel started
+int ys_dwconv_wgrad_supported(int dtype, int C);
+int ys_attn_supported(int N, int kd, int hd);
 int ys_dwconv_wgrad_launch(hipStream_t st, int dtype, const void* x, int x_ldc, int x_coff, const void* dy, int B, int H, int W,
                            int C, float* partial /*[blocks][9][C]*/, float* grad /*[9][C] +=*/);
 int ys_attn_fwd_launch(hipStream_t st, int dtype, const void* qkv, int ldq, int B, int N, int heads, int kd, int hd,
