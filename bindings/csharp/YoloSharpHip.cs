@@ -63,6 +63,12 @@ namespace YoloSharp.Native
         // criterion on caller-supplied preds (Loss.cs:411 forward(preds, batch)); device-label callers reserve the per-image label capacity
         [DllImport(Lib)] internal static extern int ys_model_set_preds(IntPtr model, int batch, float[] boxes, float[] scores, float[] maskCoefficient, float[] proto);
         [DllImport(Lib)] internal static extern int ys_model_reserve_labels(IntPtr model, int perImage);
+        // End2End (Config.End2End = true, the reference's default): YoloBaseTaskModel.One2one_Init; outputs "one2one_boxes" / "one2one_scores" / "one2one_dboxes" /
+        // "one2one_dscores" / "det" through ys_model_get_output; ys_loss_detect is then E2EDetectLoss; rows [B,k,6] of the eval forward stay on the device
+        [DllImport(Lib)] internal static extern int ys_model_one2one_init(IntPtr model, int maxDet);
+        [DllImport(Lib)] internal static extern int ys_model_det_device(IntPtr model, out IntPtr rows, out int k);
+        [DllImport(Lib)] internal static extern int ys_e2e_topk(IntPtr ctx, float[] pred, int onDevice, int batch, int nc, int anchors, int maxDet, [Out] float[] rows, [Out] long[] anchor);
+        [DllImport(Lib)] internal static extern int ys_e2e_select(IntPtr ctx, float[] rows, int onDevice, int batch, int k, float confThres, int maxDet, [Out] int[] count);
         // 0 = disjoint AdamW groups, 1 = the overlapping groups of YoloBaseTaskModel.cs:144-151 exactly as written
         [DllImport(Lib)] internal static extern int ys_optim_set_param_groups(IntPtr model, int mode);
         // Augment.LetterBox / Augment.Rectangle (Data/Augment.cs:698-857) on the device; uint8 planes (isFloat = 0) or fp32 masks

@@ -143,6 +143,36 @@ YS_API int ys_loss_read(ys_model* m, float loss_items[3], float* loss_sum);
 /* Grow the per-image ground-truth capacity of the loss workspace ahead of device-label calls (no-op when already large enough). */
 YS_API int ys_model_reserve_labels(ys_model* m, int per_image);
 
+/* ---- End2End detection (Config.End2End, Data/Config.cs:239; Models/Detector.cs:17-23).
+ * ys_model_one2one_init = YoloBaseTaskModel.One2one_Init -> Detect.one2one_init (Modules/Head.cs:152-167): the one2one towers are the SAME
+ * modules as cv2 / cv3 (the reference copies references, SaveWeight drops the one2one keys), so the model gains NO tensor: ys_model_num_tensors /
+ * tensor_info / num_params are unchanged and weight files move freely between End2End and plain models.  max_det: rows of the post-process
+ * (0 = 300, Head.cs:13).  YS_DETECT models of both families and every dtype; Segment / OBB / Pose / Classify models and the standalone block /
+ * head handles return YS_ERR_UNSUPPORTED.  Call it once, after ys_model_create.  From then on:
+ *   training forward (Head.cs:89-106): "one2one_boxes" / "one2one_scores" are outputs (the same values as "boxes" / "scores": same modules,
+ *     same input values); the BatchNorm units of the towers update their running statistics twice, num_batches_tracked += 2.
+ *   ys_loss_detect = E2EDetectLoss (Utils/Loss.cs:1094-1118): v8DetectionLoss(tal_topk 10) on one2many + v8DetectionLoss(tal_topk 1) on
+ *     one2one; ys_loss_read / ys_loss_read_items return the SUM of the two item triples and losses; "dboxes" / "dscores" are the one2many
+ *     gradients, "one2one_dboxes" / "one2one_dscores" the one2one ones.  ys_model_set_preds feeds both branches.
+ *   ys_model_backward and its segment / async / all-reduce forms: tower parameters receive the gradients of both branches, the three feature
+ *     maps (and everything below) the one2many gradient only (the one2one branch reads x.detach()).
+ *   eval forward (Head.cs:107-127, 199-202): "pred" [B, 4+nc, A] holds xyxy boxes (x stride); "det" [B, k, 6] = (x1, y1, x2, y2, score,
+ *     class), k = min(max_det, A), is ys_e2e_topk of it.  ys_model_det_device: the device pointer of "det" and k. */
+YS_API int ys_model_one2one_init(ys_model* m, int max_det);
+YS_API int ys_model_det_device(ys_model* m, float** rows, int* k);
+/* Detect.postprocess / get_topk_index with agnostic_nms = false (Head.cs:117-127, 175-196) over pred [B, 4+nc, A] fp32 (boxes in any
+ * format, class scores): k = min(max_det, A); stage 1 = the k anchors with the largest max-over-classes score; stage 2 = the k largest of the
+ * k * nc gathered scores, flattened [stage-1 rank][class]; out_rows [B, k, 6] = (box[0..3], score, class), out_anchor [B, k] = the anchor
+ * index, ordered by score descending.  TIES: ATen leaves the order among equal values unspecified; here the lower index comes first -- the
+ * anchor index in stage 1, the flattened [stage-1 rank][class] index in stage 2.  +0 = -0; NaN counts as the largest value.  The result is
+ * a pure function of the input (no floating-point atomics).  Any A, nc, max_det >= 1 with k * nc < 2^30.  `on_device` applies to all pointers. */
+YS_API int ys_e2e_topk(ys_ctx* ctx, const float* pred, int on_device, int batch, int nc, int anchors, int max_det,
+                       float* out_rows, int64_t* out_anchor);
+/* Ops.non_max_suppression(end2end: true) (Utils/Ops.cs:258-267): rows [B, k, 6] ordered by score (ys_e2e_topk) -> out_count[b] = the number
+ * of leading rows with score > conf_thres, at most max_det; the rows are not moved (the kept set is a prefix).  conf_thres outside [0,1] ->
+ * YS_ERR_INVALID_ARG (ArgumentException in the reference).  `on_device` applies to rows and out_count. */
+YS_API int ys_e2e_select(ys_ctx* ctx, const float* rows, int on_device, int batch, int k, float conf_thres, int max_det, int32_t* out_count);
+
 /* v8SegmentationLoss.forward (Utils/Loss.cs:688-863) for task = YS_SEGMENT models: the detection terms and
  * assignment above, then calculate_segmentation_loss / single_mask_loss (:794-863) with Ops.crop_mask
  * (Utils/Ops.cs:409-449) and the gradients w.r.t. "mask_coefficient" and "proto".

@@ -1,0 +1,183 @@
+"""End2End cost on one device: prints ONE JSON line.
+
+  python tools/e2e_bench.py [--batch 64] [--imgsz 640] [--nc 80] [--steps 20] [--warmup 5] [--repeats 3]
+
+Four measurements, each in a child process of its own under its own time limit (a leg that fails or runs out of time ends the run):
+  step_off / step_on   ms per train step of YOLOv8n bf16 (forward, criterion, backward, AdamW, zero_grad; device-resident images and labels)
+                       without and with End2End on the same build -- the difference is one criterion pass (tal_topk 1), the one2one pass
+                       through the head towers' backward and the towers' second running-statistics update
+  topk                 ys_e2e_topk on a device-resident [B, 4+nc, A] tensor (A = the model's anchors at --imgsz), max_det 300
+  torch_topk           a torch restatement of Detect.get_topk_index + gather (Modules/Head.cs:117-127, 175-196) on the same tensor and GPU
+Every figure is the median over --repeats timed blocks of --steps calls after --warmup calls.
+"""
+import argparse
+import json
+import os
+import subprocess
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+LEGS = ("step_off", "step_on", "topk", "torch_topk")
+
+
+def _labels(B, nc, rng, kmax=16):
+    bi, cl, bb = [], [], []
+    for b in range(B):
+        k = int(rng.integers(1, kmax + 1))
+        wh = rng.random((k, 2)) * 0.57 + 0.03
+        c = wh / 2 + rng.random((k, 2)) * (1 - wh)
+        bi.append(np.full(k, b)); cl.append(rng.integers(0, nc, k)); bb.append(np.concatenate((c, wh), 1))
+    return np.concatenate(bi).astype(np.float32), np.concatenate(cl).astype(np.float32), np.concatenate(bb).astype(np.float32)
+
+
+def _timed(fn, sync, a):
+    for _ in range(a.warmup):
+        fn()
+    sync()
+    ms = []
+    for _ in range(a.repeats):
+        t0 = time.perf_counter()
+        for _ in range(a.steps):
+            fn()
+        sync()
+        ms.append((time.perf_counter() - t0) * 1e3 / a.steps)
+    return float(np.median(ms)), [round(v, 4) for v in ms]
+
+
+def _anchors(S):
+    return (S // 8) ** 2 + (S // 16) ** 2 + (S // 32) ** 2
+
+
+def _pred(B, nc, A, rng):
+    p = rng.random((B, 4 + nc, A), dtype=np.float32)
+    p[:, 4:] = p[:, 4:] ** 8                       # most scores small, a few large: the shape of sigmoid outputs early in training
+    return p
+
+
+def leg_step(a, end2end):
+    from yolosharp_amd import Engine
+    from yolosharp_amd.model import AMPWrapper, Yolov8, v8DetectionLoss
+    eng = Engine(0)
+    B, S, nc = a.batch, a.imgsz, a.nc
+    m = Yolov8(eng, nc=nc, size="n", height=S, width=S, max_batch=B, dtype="bf16", end2end=end2end)
+    m.init_weights(1)
+    rng = np.random.default_rng(0)
+    x_dev = eng.to_device(rng.random((B, 3, S, S), dtype=np.float32))
+    bi, cl, bb = _labels(B, nc, rng)
+    m.reserve_labels(16)
+    d = [eng.to_device(v) for v in (bi, cl, bb)]
+    crit, amp = v8DetectionLoss(m), AMPWrapper(m)
+    m.train()
+
+    def step():
+        m.forward_device(x_dev, B)
+        crit.forward_device(d[0], d[1], d[2], bi.shape[0])
+        amp.Step()
+
+    ms, runs = _timed(step, eng.synchronize, a)
+    _, items = crit.read()
+    # launches the library's own profiler sees per step (untimed; the weight-gradient stream off so that the order is the issue order)
+    m.set_overlap(False)
+    eng.kernel_profile(True)
+    step(); eng.synchronize()
+    path = os.path.join(a.tmp, "e2e_bench_launches_%d.csv" % int(end2end))
+    eng.kernel_profile_dump(path)
+    eng.kernel_profile(False)
+    with open(path) as f:
+        launches = max(0, sum(1 for _ in f) - 1)
+    os.remove(path)
+    for p in d + [x_dev]:
+        eng.free(p)
+    m.close()
+    return {"ms_per_step": round(ms, 4), "runs": runs, "loss_items": [float(v) for v in items], "profiled_launches_per_step": launches}
+
+
+def leg_topk(a):
+    from yolosharp_amd import Engine, _lib
+    eng = Engine(0)
+    B, nc, A = a.batch, a.nc, _anchors(a.imgsz)
+    k = min(300, A)
+    p_dev = eng.to_device(_pred(B, nc, A, np.random.default_rng(1)))
+    rows, anc = eng.malloc(B * k * 6 * 4), eng.malloc(B * k * 8)
+
+    def call():
+        _lib.check(eng.lib, eng.lib.ys_e2e_topk(eng.ctx, p_dev, 1, B, nc, A, 300, rows, anc))
+
+    ms, runs = _timed(call, eng.synchronize, a)
+    eng.kernel_profile(True)
+    call(); eng.synchronize()
+    n, kernel_ms = eng.kernel_profile_read("e2e_topk")
+    eng.kernel_profile(False)
+    for p in (p_dev, rows, anc):
+        eng.free(p)
+    # kernels_ms: the two launches alone, between HIP events on the stream
+    return {"ms_per_call": round(ms, 4), "runs": runs, "kernels_ms": round(kernel_ms / max(n, 1), 4), "B": B, "A": A, "nc": nc, "k": k}
+
+
+def leg_torch_topk(a):
+    import torch
+    B, nc, A = a.batch, a.nc, _anchors(a.imgsz)
+    pred = torch.from_numpy(_pred(B, nc, A, np.random.default_rng(1))).cuda()
+    k = min(300, A)
+    ar = torch.arange(B, device="cuda")[:, None]
+
+    def call():
+        p = pred.permute(0, 2, 1)
+        boxes, scores = p.split((4, nc), dim=-1)
+        ori = scores.amax(-1).topk(k).indices.unsqueeze(-1)
+        sc = scores.gather(1, ori.expand(-1, -1, nc))
+        sc, index = sc.flatten(1).topk(k)
+        idx = ori[ar, torch.div(index, nc, rounding_mode="floor")]
+        bx = boxes.gather(1, idx.expand(-1, -1, 4))
+        return torch.cat((bx, sc[..., None], (index % nc)[..., None].float()), -1)
+
+    ms, runs = _timed(call, torch.cuda.synchronize, a)
+    return {"ms_per_call": round(ms, 4), "runs": runs}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", type=int, default=64)
+    ap.add_argument("--imgsz", type=int, default=640)
+    ap.add_argument("--nc", type=int, default=80)
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--leg-timeout", type=int, default=240, help="seconds per child process")
+    ap.add_argument("--tmp", default=os.environ.get("TMPDIR", "/tmp"))
+    ap.add_argument("--leg", choices=LEGS, help="run one measurement in this process (what the driver starts)")
+    a = ap.parse_args()
+    if a.leg:
+        out = {"step_off": lambda: leg_step(a, False), "step_on": lambda: leg_step(a, True), "topk": lambda: leg_topk(a),
+               "torch_topk": lambda: leg_torch_topk(a)}[a.leg]()
+        print(json.dumps(out))
+        return 0
+    res = {"metric": "e2e_cost", "model": "yolov8n", "dtype": "bf16", "batch": a.batch, "imgsz": a.imgsz, "nc": a.nc}
+    fwd = [x for kv in (("--batch", a.batch), ("--imgsz", a.imgsz), ("--nc", a.nc), ("--steps", a.steps), ("--warmup", a.warmup),
+                        ("--repeats", a.repeats), ("--tmp", a.tmp)) for x in (kv[0], str(kv[1]))]
+    for leg in LEGS:
+        try:
+            r = subprocess.run([sys.executable, os.path.abspath(__file__), "--leg", leg] + fwd, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
+                               text=True, timeout=a.leg_timeout, stdin=subprocess.DEVNULL)
+        except subprocess.TimeoutExpired:
+            res["failed"] = {"leg": leg, "why": "time limit of %d s" % a.leg_timeout}
+            break                                   # nothing more is started on the device after a leg that hung
+        if r.returncode != 0:
+            res["failed"] = {"leg": leg, "rc": r.returncode, "stderr": r.stderr[-2000:]}
+            break                                   # ... or that failed
+        res[leg] = json.loads(r.stdout.strip().splitlines()[-1])
+    if "step_off" in res and "step_on" in res:
+        res["e2e_extra_ms"] = round(res["step_on"]["ms_per_step"] - res["step_off"]["ms_per_step"], 4)
+        res["e2e_extra_launches"] = res["step_on"]["profiled_launches_per_step"] - res["step_off"]["profiled_launches_per_step"]
+    print(json.dumps(res))
+    return 1 if "failed" in res else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

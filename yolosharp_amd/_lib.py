@@ -124,6 +124,10 @@ PROTOTYPES = {
     "ys_block_output_shape": (C.c_int, [C.c_void_p, c_i32_p]),
     "ys_model_set_preds": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ys_model_reserve_labels": (C.c_int, [C.c_void_p, C.c_int]),
+    "ys_model_one2one_init": (C.c_int, [C.c_void_p, C.c_int]),
+    "ys_model_det_device": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int)]),
+    "ys_e2e_topk": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "ys_e2e_select": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_void_p]),
     "ys_optim_set_param_groups": (C.c_int, [C.c_void_p, C.c_int]),
     "ys_letterbox": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, c_i32_p, c_i32_p]),
     "ys_block_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),

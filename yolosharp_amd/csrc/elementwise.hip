@@ -1068,7 +1068,7 @@ template <class T>
 __global__ void __launch_bounds__(EW_THREADS)
 detect_decode_kernel(const T* __restrict__ pd, int ld_pd, const T* __restrict__ ps, int ld_ps, int B, int A, int nc,
                      int reg_max, int nl, int o0, int o1, int o2, int w0, int w1, int w2, int s0, int s1, int s2,
-                     float* __restrict__ pred, int pred_C, const T* __restrict__ px, int ld_px, int xkind, int nx, int kdim) {
+                     float* __restrict__ pred, int pred_C, const T* __restrict__ px, int ld_px, int xkind, int nx, int kdim, int xyxy) {
   // One workgroup decodes DEC_ANCH consecutive rows of the [B*A][ld] head outputs: the rows are staged in LDS with
   // coalesced 16-byte loads, (anchor, side) threads take the DFL expectation, and the class probabilities are written
   // channel-major so that consecutive lanes store consecutive anchors of pred[b][c][:].
@@ -1156,6 +1156,11 @@ detect_decode_kernel(const T* __restrict__ pd, int ld_pd, const T* __restrict__ 
       o[2 * (long)A] = (d[0] + d[2]) * st;
       o[3 * (long)A] = (d[1] + d[3]) * st;
       o[(long)(4 + nc) * A] = ang;
+    } else if (xyxy) {   // End2End: dist2bbox(xywh = false) * stride (Head.cs:199-202, Tal.cs:345-346)
+      o[0] = x1 * st;
+      o[(long)A] = y1 * st;
+      o[2 * (long)A] = x2 * st;
+      o[3 * (long)A] = y2 * st;
     } else {
       o[0] = (x1 + x2) / 2.0f * st;
       o[(long)A] = (y1 + y2) / 2.0f * st;
@@ -1203,7 +1208,7 @@ int ys_obb_angle_launch(hipStream_t st, float* p, long n) {
 }
 int ys_detect_decode_launch(hipStream_t st, int dtype, const void* pd, int ld_pd, const void* ps, int ld_ps, int B, int A,
                             int nc, int reg_max, int nl, const int* lo, const int* lw, const int* ls, float* pred, int pred_C,
-                            const void* px, int ld_px, int xkind, int nx, int kdim) {
+                            const void* px, int ld_px, int xkind, int nx, int kdim, int xyxy) {
   const long n = (long)B * A;
   const int o1 = nl > 1 ? lo[1] : 0, o2 = nl > 2 ? lo[2] : 0, w1 = nl > 1 ? lw[1] : 1, w2 = nl > 2 ? lw[2] : 1;
   const int s1 = nl > 1 ? ls[1] : 1, s2 = nl > 2 ? ls[2] : 1;
@@ -1212,9 +1217,9 @@ int ys_detect_decode_launch(hipStream_t st, int dtype, const void* pd, int ld_pd
   const size_t lds_bytes = (size_t)DEC_ANCH * ((4 * reg_max + 1) + (nc | 1) + 4 + (nx | 1)) * 4;
   if (lds_bytes > 60 * 1024 || DEC_ANCH * 4 > EW_THREADS) { ys_set_error("detect decode: nc=%d reg_max=%d too large", nc, reg_max); return YS_ERR_UNSUPPORTED; }
   if (dtype == YS_BF16)
-    YS_LAUNCH_LDS((detect_decode_kernel<bf16_t>), ys_cdiv(n, DEC_ANCH), EW_THREADS, lds_bytes, st, (const bf16_t*)pd, ld_pd, (const bf16_t*)ps, ld_ps, B, A, nc, reg_max, nl, lo[0], o1, o2, lw[0], w1, w2, ls[0], s1, s2, pred, pred_C, (const bf16_t*)px, ld_px, xkind, nx, kdim);
+    YS_LAUNCH_LDS((detect_decode_kernel<bf16_t>), ys_cdiv(n, DEC_ANCH), EW_THREADS, lds_bytes, st, (const bf16_t*)pd, ld_pd, (const bf16_t*)ps, ld_ps, B, A, nc, reg_max, nl, lo[0], o1, o2, lw[0], w1, w2, ls[0], s1, s2, pred, pred_C, (const bf16_t*)px, ld_px, xkind, nx, kdim, xyxy);
   else
-    YS_LAUNCH_LDS((detect_decode_kernel<float>), ys_cdiv(n, DEC_ANCH), EW_THREADS, lds_bytes, st, (const float*)pd, ld_pd, (const float*)ps, ld_ps, B, A, nc, reg_max, nl, lo[0], o1, o2, lw[0], w1, w2, ls[0], s1, s2, pred, pred_C, (const float*)px, ld_px, xkind, nx, kdim);
+    YS_LAUNCH_LDS((detect_decode_kernel<float>), ys_cdiv(n, DEC_ANCH), EW_THREADS, lds_bytes, st, (const float*)pd, ld_pd, (const float*)ps, ld_ps, B, A, nc, reg_max, nl, lo[0], o1, o2, lw[0], w1, w2, ls[0], s1, s2, pred, pred_C, (const float*)px, ld_px, xkind, nx, kdim, xyxy);
   return YS_OK;
 }
 

@@ -194,6 +194,14 @@ struct ys_model {
   int* gt_count = nullptr; float* gt_box = nullptr; int* gt_cls = nullptr; float* pbox = nullptr;
   float *ov = nullptr, *align = nullptr; unsigned char* mpos = nullptr; unsigned *pos_align = nullptr, *pos_ov = nullptr;
   int* fg_gt = nullptr; float* tnorm = nullptr; float* loss_partial = nullptr; float* scalars = nullptr;
+  // End2End (ys_model_one2one_init; Head.cs:89-127, 152-167): the one2one towers ALIAS cv2 / cv3 -- no tensors of their own.  Their
+  // criterion pass (tal_topk 1) writes its gradients and scalars here; the eval forward adds the top-k rows "det" [B][k][6]
+  bool e2e = false; int max_det = 300;
+  void *o2o_dpd = nullptr, *o2o_dps = nullptr; float* scalars2 = nullptr;
+  float* det_rows = nullptr; long long* det_anchor = nullptr; void* det_ws = nullptr;
+  int head_conv0 = 0, det_in[3] = {-1, -1, -1};       // first tower unit in `convs`; the three feature maps the head reads
+  long hstate0 = 0, n_hstate = 0; float* hstate_snap = nullptr; unsigned char* hstate_count = nullptr;   // the towers' running statistics [hstate0, n_state)
+  bool e2e_pass = false;                              // backward: the one2one pass through the towers is running (no gradient into det_in)
   bool have_fwd = false, have_loss = false;
   bool fwd_training = false;   // the last forward kept what backward needs (training-mode BN statistics, pre-BN outputs)
   std::vector<void*> allocs;
@@ -389,6 +397,8 @@ int add_detect(ys_model* m, const std::string& hp, const int* pv, const int* ch,
   const int c3 = std::max(ch[0], std::min(d.nc, 100));
   if (c2 % m->epl || c3 % m->epl) { ys_set_error("model: head widths c2=%d c3=%d must be multiples of %d", c2, c3, m->epl); return YS_ERR_UNSUPPORTED; }
   m->head_prefix = hp;
+  m->head_conv0 = (int)m->convs.size();
+  for (int i = 0; i < 3; i++) m->det_in[i] = pv[i];
   m->nl = 3; m->A = 0;
   for (int i = 0; i < 3; i++) { m->lvl_off[i] = m->A; m->lvl_w[i] = ww[i]; m->lvl_h[i] = hh[i]; m->A += hh[i] * ww[i]; }
   m->ld_pd = (4 * d.reg_max + m->epl - 1) / m->epl * m->epl;
@@ -1575,6 +1585,8 @@ int forward_impl(ys_model* m, int B) {
     m->eval_coeffs_dirty = false;
   }
   m->q8_fwd_ready = -1;
+  const bool e2e_stats = m->e2e && m->training && m->n_hstate > 0;
+  if (e2e_stats) YS_CHECK_HIP(hipMemcpyAsync(m->hstate_snap, m->state + m->hstate0, (size_t)m->n_hstate * 4, hipMemcpyDeviceToDevice, st));
   for (size_t oi = 0; oi < m->ops.size(); oi++) {
     const Op& op = m->ops[oi];
     const Buf& ib = m->bufs[op.in.buf];
@@ -1623,10 +1635,14 @@ int forward_impl(ys_model* m, int B) {
   if (!m->training && m->cls)   // Classify eval: inference["cls"] = softmax(logits, 1) (Head.cs:640)
     YS_TRY(ys_cls_xent_launch(st, m->dtype, m->bufs[m->logit_buf].act, m->ld_cls, B, m->d.nc, nullptr, nullptr, m->pred, nullptr, nullptr));
   if (m->f8) m->f8_sx_valid = true;        // every fp8 candidate has recorded an input maximum (bootstrap pass or its own kernel)
+  if (e2e_stats)   // the one2one branch runs the same tower modules again on the same values: their running statistics move twice (e2e.hip)
+    YS_TRY(ys_e2e_bn_second_update_launch(st, m->state + m->hstate0, m->hstate_snap, m->hstate_count, m->n_hstate, 0.03f));
   if (!m->training && m->pd_buf >= 0) {
     YS_TRY(ys_detect_decode_launch(st, m->dtype, m->bufs[m->pd_buf].act, m->ld_pd, m->bufs[m->ps_buf].act, m->ld_ps, B, m->A,
                                    m->d.nc, m->d.reg_max, m->nl, m->lvl_off, m->lvl_w, m->lvl_stride, m->pred, 4 + m->d.nc + m->nm,
-                                   m->xkind >= 2 ? m->bufs[m->mc_buf].act : nullptr, m->ld_mc, m->xkind, m->nm, m->kdim));
+                                   m->xkind >= 2 ? m->bufs[m->mc_buf].act : nullptr, m->ld_mc, m->xkind, m->nm, m->kdim, m->e2e ? 1 : 0));
+    if (m->e2e)       // Detect.postprocess on the one2one branch (same values as the one2many branch): [B][k][6] (Head.cs:107-127)
+      YS_TRY(ys_e2e_topk_launch(st, m->pred, B, m->d.nc, m->A, m->max_det, m->det_ws, m->det_rows, m->det_anchor));
     if (m->segment)   // Segment._inference: cat(preds, mask_coefficient) (Head.cs:309-313), raw coefficients
       YS_TRY(ys_unpack_nchw_strided_launch(st, m->dtype, m->bufs[m->mc_buf].act, m->ld_mc, 0, B, m->nm, m->A, m->pred,
                                            (long)(4 + m->d.nc + m->nm) * m->A, (long)(4 + m->d.nc) * m->A));
@@ -1989,8 +2005,11 @@ int run_conv_bwd(ys_model* m, ConvL& c, int B) {
     YS_TRY(ys_colsum_launch(st, m->dtype, dy, dy_ldc, dy_coff, M, (long)c.Hout * c.Wout, dy_bstride, c.cout, m->stat_partial,
                             m->grads + c.g_off));
   }
+  // End2End, one2one pass: the branch reads x.detach() (Head.cs:94) -- parameter gradients only for the units that read a feature map
+  const bool no_dx = m->e2e_pass && (c.in.buf == m->det_in[0] || c.in.buf == m->det_in[1] || c.in.buf == m->det_in[2]);
   if (c.dw) {
     YS_TRY(ys_dwconv_wgrad_launch(st, m->dtype, ib.act, ib.ldc, c.in.coff, dy, B, c.Hin, c.Win, c.cout, m->stat_partial, m->grads + c.w_off));
+    if (no_dx) return YS_OK;
     const int mode = grad_mode(m, c.in);
     if (mode < 0) { ys_set_error("backward: inconsistent gradient slice state at %s", c.name.c_str()); return YS_ERR_STATE; }
     YS_TRY(ys_dwconv_launch(st, m->dtype, 1, dy, c.cout, 0, B, c.Hin, c.Win, c.cout, m->params + c.w_off, ib.grad, ib.ldc, c.in.coff, mode));
@@ -2000,7 +2019,7 @@ int run_conv_bwd(ys_model* m, ConvL& c, int B) {
   if (c.bn && m->overlap && dy != c.dy_own) { ys_set_error("backward: %s has no dy buffer of its own", c.name.c_str()); return YS_ERR_STATE; }
   YS_TRY(queue_wgrad(m, c, B, dy, dy_ldc, dy_coff, dy_bstride));
   // ---- dgrad (gather form with flipped/transposed weights)
-  if (!c.first) {
+  if (!c.first && !no_dx) {
     const int mode = grad_mode(m, c.in);
     if (mode < 0) { ys_set_error("backward: inconsistent gradient slice state at %s", c.name.c_str()); return YS_ERR_STATE; }
     ConvArgs a = dgrad_args(m, c, B, dy, dy_ldc, dy_coff, dy_bstride);
@@ -2036,6 +2055,7 @@ int run_conv_bwd_group(ys_model* m, ConvL* const* cs, int n, int B) {
   bool ok = n >= 2 && n <= YS_GROUP_MAX && !m->f8;
   for (int i = 0; i < n && ok; i++) {
     const ConvL& c = *cs[i];
+    if (m->e2e_pass && (c.in.buf == m->det_in[0] || c.in.buf == m->det_in[1] || c.in.buf == m->det_in[2])) { ok = false; break; }   // one2one pass: no input gradient (run_conv_bwd)
     ok = !c.dw && !c.ct && !c.has_res && !c.first && c.gstat_off >= 0 && c.bn == cs[0]->bn && c.act == cs[0]->act && (!c.bn || (c.dy_own && c.cout_ld == c.cout));
     if (ok && c.bn) ok = c.red_ok && c.red_seen == (int)c.red_src.size() && !c.red_src.empty();   // sums already produced by the consumers' dgrads
   }
@@ -2116,11 +2136,27 @@ static int join_wgrad_stream(ys_model* m) {
   return YS_OK;
 }
 
+void reset_grad_state(ys_model* m);
 // async_end: leave the weight-gradient stream unjoined (its split reduction runs there too) and record the segment's completion events
 int backward_range(ys_model* m, int seg_lo, int seg_hi, bool async_end = false, bool seg_events = true) {
   hipStream_t st = m->ctx->stream;
   const int B = m->B;
   YS_TRY(plan_bnred(m, B));
+  if (m->e2e && seg_lo == 0 && !m->e2e_pass) {
+    // End2End (Head.cs:89-106): the towers ran twice on the same values with the same parameters -- on x (one2many) and on x.detach()
+    // (one2one).  Backprop is linear in the upstream gradient, so two passes through the towers with the SAME saved activations give
+    // the sum: this pass carries the one2one gradients (parameter gradients and the inner input gradients, nothing into the feature
+    // maps), the regular pass below the one2many gradients.  The head's split partials are reduced and the weight-gradient stream is
+    // joined in between: the second pass reuses every dy buffer and partial region.
+    Buf &pb = m->bufs[m->pd_buf], &sb = m->bufs[m->ps_buf];
+    std::swap(pb.grad, m->o2o_dpd); std::swap(sb.grad, m->o2o_dps);
+    m->e2e_pass = true;
+    const int rc = backward_range(m, 0, 0, false, false);
+    m->e2e_pass = false;
+    std::swap(pb.grad, m->o2o_dpd); std::swap(sb.grad, m->o2o_dps);
+    YS_TRY(rc);
+    reset_grad_state(m);
+  }
   for (int i = (int)m->ops.size() - 1; i >= 0; i--) {
     const Op& op = m->ops[i];
     if (op.seg < seg_lo || op.seg > seg_hi) continue;
@@ -2518,6 +2554,25 @@ int ys_model_get_output(ys_model* m, const char* key, float* host, size_t count)
     const Buf& b = m->bufs[bx ? m->pd_buf : m->ps_buf];
     YS_TRY(ys_unpack_nchw_launch(st, m->dtype, b.grad, b.ldc, 0, B, C, m->A, m->out_stage));
     YS_CHECK_HIP(hipMemcpyAsync(host, m->out_stage, count * 4, hipMemcpyDeviceToHost, st));
+  } else if (k == "one2one_boxes" || k == "one2one_scores" || k == "one2one_dboxes" || k == "one2one_dscores") {
+    // End2End: the one2one towers alias cv2 / cv3 and read the same values (Head.cs:94-96, 152-167), so their outputs are the one2many
+    // buffers; their criterion pass (tal_topk 1) has gradient buffers of its own
+    YS_REQUIRE(m->e2e, "ys_model_get_output(%s): not an End2End model (ys_model_one2one_init)", key);
+    const bool g = k[8] == 'd', bx = k.find("boxes") != std::string::npos;
+    const int C = bx ? 4 * m->d.reg_max : m->d.nc;
+    YS_REQUIRE(!g || m->have_loss, "ys_model_get_output(%s): no loss has run", key);
+    YS_REQUIRE(count == (size_t)B * C * m->A, "ys_model_get_output(%s): expected %zu elements", key, (size_t)B * C * m->A);
+    const Buf& b = m->bufs[bx ? m->pd_buf : m->ps_buf];
+    const void* src = g ? (bx ? m->o2o_dpd : m->o2o_dps) : b.act;
+    YS_TRY(ys_unpack_nchw_launch(st, m->dtype, src, b.ldc, 0, B, C, m->A, m->out_stage));
+    YS_CHECK_HIP(hipMemcpyAsync(host, m->out_stage, count * 4, hipMemcpyDeviceToHost, st));
+  } else if (k == "det") {
+    // End2End eval forward: Detect.postprocess (Head.cs:117-127) -> [B, k, 6] = (x1, y1, x2, y2, score, class), k = min(max_det, A)
+    YS_REQUIRE(m->e2e, "ys_model_get_output(det): not an End2End model (ys_model_one2one_init)");
+    YS_REQUIRE(!m->fwd_training && !m->training, "ys_model_get_output(det): the last forward ran in training mode");
+    const size_t kk = (size_t)std::min(m->max_det, m->A);
+    YS_REQUIRE(count == (size_t)B * kk * 6, "ys_model_get_output(det): expected %zu elements", (size_t)B * kk * 6);
+    YS_CHECK_HIP(hipMemcpyAsync(host, m->det_rows, count * 4, hipMemcpyDeviceToHost, st));
   } else if (m->segment && (k == "mask_coefficient" || k == "dmask_coefficient")) {   // Head.cs:290-296: [B][nm][A]
     const bool g = k[0] == 'd';
     YS_REQUIRE(!g || m->have_seg_loss, "ys_model_get_output(%s): no segment loss has run", key);
@@ -2593,6 +2648,54 @@ int ys_model_pred_device(ys_model* m, float** dptr) {
   return YS_OK;
 }
 
+// YoloBaseTaskModel.One2one_Init -> Detect.one2one_init (Head.cs:152-167): the one2one towers are the SAME Sequential objects as cv2 / cv3
+// (CopyTo copies references), so the model gains no tensor -- only the second criterion pass's gradient / scalar buffers, the snapshot of
+// the towers' running statistics (their second momentum update) and the top-k output of the eval forward.
+int ys_model_one2one_init(ys_model* m, int max_det) {
+  YS_REQUIRE(m, "ys_model_one2one_init: null model");
+  YS_REQUIRE(max_det >= 0, "ys_model_one2one_init: max_det = %d", max_det);
+  if (m->is_block || m->is_head || m->cls || m->d.task != YS_DETECT || m->pd_buf < 0) {
+    ys_set_error("ys_model_one2one_init: End2End is built for full Detect models (Segment / OBB / Pose End2End and the standalone heads are follow-ups)");
+    return YS_ERR_UNSUPPORTED;
+  }
+  if (m->e2e) { ys_set_error("ys_model_one2one_init: already initialised"); return YS_ERR_STATE; }
+  YS_CHECK_HIP(hipSetDevice(m->ctx->device));
+  const int B = m->maxB;
+  m->max_det = max_det > 0 ? max_det : 300;     // Detect.max_det (Head.cs:13)
+  const int k = std::min(m->max_det, m->A);
+  const Buf &pb = m->bufs[m->pd_buf], &sb = m->bufs[m->ps_buf];
+  YS_TRY(dev_alloc(m, &m->o2o_dpd, (size_t)B * pb.rows_per_b * pb.ldc * m->es));
+  YS_TRY(dev_alloc(m, &m->o2o_dps, (size_t)B * sb.rows_per_b * sb.ldc * m->es));
+  YS_TRY(dev_alloc(m, (void**)&m->scalars2, 64 * 4 + 64 * 8 * 8));
+  YS_TRY(dev_alloc(m, (void**)&m->det_rows, (size_t)B * k * 6 * 4));
+  YS_TRY(dev_alloc(m, (void**)&m->det_anchor, (size_t)B * k * 8));
+  YS_TRY(dev_alloc(m, &m->det_ws, ys_e2e_topk_ws_bytes(B, m->d.nc, m->A, m->max_det)));
+  // the towers' BatchNorm state: the tail of `state` (the head's units are the last of `convs`)
+  long s0 = m->n_state;
+  for (size_t i = (size_t)m->head_conv0; i < m->convs.size(); i++) if (m->convs[i].bn) s0 = std::min(s0, m->convs[i].rm_off);
+  for (int i = 0; i < m->head_conv0; i++)
+    if (m->convs[i].bn && m->convs[i].rm_off >= s0) { ys_set_error("ys_model_one2one_init: internal: the towers' statistics are not the tail of the state"); return YS_ERR_STATE; }
+  m->hstate0 = s0; m->n_hstate = m->n_state - s0;
+  if (m->n_hstate > 0) {
+    std::vector<unsigned char> isc((size_t)m->n_hstate, 0);
+    for (size_t i = (size_t)m->head_conv0; i < m->convs.size(); i++) if (m->convs[i].bn) isc[(size_t)(m->convs[i].nbt_off - s0)] = 1;
+    YS_TRY(dev_alloc(m, (void**)&m->hstate_snap, (size_t)m->n_hstate * 4));
+    YS_TRY(dev_alloc(m, (void**)&m->hstate_count, (size_t)m->n_hstate));
+    YS_CHECK_HIP(hipMemcpyAsync(m->hstate_count, isc.data(), isc.size(), hipMemcpyHostToDevice, m->ctx->stream));
+    YS_CHECK_HIP(hipStreamSynchronize(m->ctx->stream));
+  }
+  m->e2e = true;
+  m->have_fwd = false; m->have_loss = false;      // "pred" changes its box format: a forward from before the switch is not an End2End one
+  return YS_OK;
+}
+
+int ys_model_det_device(ys_model* m, float** rows, int* k) {
+  YS_REQUIRE(m && rows && k, "ys_model_det_device: null argument");
+  YS_REQUIRE(m->e2e, "ys_model_det_device: not an End2End model (ys_model_one2one_init)");
+  *rows = m->det_rows; *k = std::min(m->max_det, m->A);
+  return YS_OK;
+}
+
 int ys_model_reserve_labels(ys_model* m, int per_image) {
   YS_REQUIRE(m && !m->is_block, "ys_model_reserve_labels: needs a full model");
   YS_REQUIRE(per_image > 0, "ys_model_reserve_labels: per_image = %d", per_image);
@@ -2658,8 +2761,26 @@ static int loss_detect_core(ys_model* m, const float* batch_idx, const float* cl
     a.rot = 1; a.pa = ab.act; a.dpa = ab.grad; a.ld_pa = m->ld_mc; a.hyp_angle = 1.0f;
   }
   YS_TRY(ys_loss_detect_launch(st, m->dtype, a));
+  if (m->e2e) {
+    // E2EDetectLoss (Loss.cs:1094-1118): v8DetectionLoss(tal_topk 10) on one2many + v8DetectionLoss(tal_topk 1) on one2one, unweighted.
+    // The one2one head outputs ARE the one2many ones (aliased towers, same input values), so the second pass reads the same pd / ps and
+    // differs only in the assigner's topk.  It reuses the first pass's assignment workspaces: the stream is in order, and nothing after
+    // the first pass reads them again -- what outlives a pass are its gradients and its scalars, and those get buffers of their own.
+    a.topk = 1; a.dpd = m->o2o_dpd; a.dps = m->o2o_dps; a.scalars = m->scalars2;
+    YS_TRY(ys_loss_detect_launch(st, m->dtype, a));
+  }
   YS_CHECK_HIP(hipGetLastError());
   m->have_loss = true;
+  return YS_OK;
+}
+
+// End2End: the items / loss of the one2one criterion pass are added to the one2many ones (Loss.cs:1113-1117)
+static int add_o2o_items(ys_model* m, float h[16]) {
+  if (!m->e2e) return YS_OK;
+  float g[16];
+  YS_CHECK_HIP(hipMemcpyAsync(g, m->scalars2, sizeof(g), hipMemcpyDeviceToHost, m->ctx->stream));
+  YS_CHECK_HIP(hipStreamSynchronize(m->ctx->stream));
+  for (int i = 1; i <= 4; i++) h[i] += g[i];
   return YS_OK;
 }
 
@@ -2787,6 +2908,7 @@ int ys_loss_read_items(ys_model* m, float* items, int n_items, float* loss_sum) 
     return YS_OK;
   }
   YS_TRY(check_label_overflow(m, h[15]));
+  YS_TRY(add_o2o_items(m, h));
   if (m->segment) {
     YS_REQUIRE(m->have_seg_loss, "ys_loss_read_items: the Segment model needs ys_loss_segment");
     items[0] = h[1]; items[1] = h[8]; items[2] = h[2]; items[3] = h[3]; items[4] = 0.f;
@@ -2809,6 +2931,7 @@ int ys_loss_read(ys_model* m, float loss_items[3], float* loss_sum) {
   YS_CHECK_HIP(hipMemcpyAsync(h, m->scalars, sizeof(h), hipMemcpyDeviceToHost, m->ctx->stream));
   YS_CHECK_HIP(hipStreamSynchronize(m->ctx->stream));
   YS_TRY(check_label_overflow(m, h[15]));
+  YS_TRY(add_o2o_items(m, h));
   if (loss_items) { loss_items[0] = h[1]; loss_items[1] = h[2]; loss_items[2] = h[3]; }
   if (loss_sum) *loss_sum = h[4];
   return YS_OK;

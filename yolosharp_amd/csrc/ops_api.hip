@@ -478,3 +478,48 @@ extern "C" int ys_dwconv3x3_bwd(ys_ctx* ctx, int dtype, const float* x, int B, i
   if (view_intact) *view_intact = ok;
   return YS_OK;
 }
+
+// ---- End2End post-process (e2e.hip): Detect.postprocess / get_topk_index (Modules/Head.cs:117-127, 175-196) on a [B, 4+nc, A] tensor and the
+//      thresholding of Ops.non_max_suppression(end2end: true) (Utils/Ops.cs:258-267)
+extern "C" int ys_e2e_topk(ys_ctx* ctx, const float* pred, int on_device, int batch, int nc, int anchors, int max_det, float* out_rows,
+                           int64_t* out_anchor) {
+  YS_REQUIRE(ctx && pred && out_rows && out_anchor, "ys_e2e_topk: null argument");
+  YS_REQUIRE(batch > 0 && nc > 0 && anchors > 0 && max_det > 0, "ys_e2e_topk: bad shape B=%d nc=%d A=%d max_det=%d", batch, nc, anchors, max_det);
+  YS_CHECK_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  const size_t k = (size_t)(max_det < anchors ? max_det : anchors);
+  const size_t n_pred = (size_t)batch * (4 + nc) * anchors, n_rows = (size_t)batch * k * 6, n_anc = (size_t)batch * k;
+  DevBuf dp, dr, da;
+  const size_t need = ys_e2e_topk_ws_bytes(batch, nc, anchors, max_det);
+  if (need > ctx->e2e_ws_bytes) {               // the context keeps the workspace (like the NMS one): device-resident calls stay asynchronous
+    if (ctx->e2e_ws) { YS_CHECK_HIP(hipStreamSynchronize(st)); YS_CHECK_HIP(hipFree(ctx->e2e_ws)); ctx->e2e_ws = nullptr; ctx->e2e_ws_bytes = 0; }
+    if (hipMalloc(&ctx->e2e_ws, need) != hipSuccess) { ys_set_error("ys_e2e_topk: out of device memory (%zu bytes)", need); return YS_ERR_OOM; }
+    ctx->e2e_ws_bytes = need;
+  }
+  YsTimer timer(ctx, "e2e_topk");
+  if (on_device) return ys_e2e_topk_launch(st, pred, batch, nc, anchors, max_det, ctx->e2e_ws, out_rows, (long long*)out_anchor);
+  YS_TRY(dp.alloc(n_pred * 4)); YS_TRY(dr.alloc(n_rows * 4)); YS_TRY(da.alloc(n_anc * 8));
+  YS_CHECK_HIP(hipMemcpyAsync(dp.p, pred, n_pred * 4, hipMemcpyHostToDevice, st));
+  YS_TRY(ys_e2e_topk_launch(st, (const float*)dp.p, batch, nc, anchors, max_det, ctx->e2e_ws, (float*)dr.p, (long long*)da.p));
+  YS_CHECK_HIP(hipMemcpyAsync(out_rows, dr.p, n_rows * 4, hipMemcpyDeviceToHost, st));
+  YS_CHECK_HIP(hipMemcpyAsync(out_anchor, da.p, n_anc * 8, hipMemcpyDeviceToHost, st));
+  YS_CHECK_HIP(hipStreamSynchronize(st));
+  return YS_OK;
+}
+
+extern "C" int ys_e2e_select(ys_ctx* ctx, const float* rows, int on_device, int batch, int k, float conf_thres, int max_det, int32_t* out_count) {
+  YS_REQUIRE(ctx && rows && out_count, "ys_e2e_select: null argument");
+  // Ops.cs:248-251: ArgumentException for a threshold outside [0,1]
+  YS_REQUIRE(conf_thres >= 0.f && conf_thres <= 1.f, "Invalid Confidence threshold %g, valid values are between 0.0 and 1.0", conf_thres);
+  YS_REQUIRE(batch > 0 && k > 0 && max_det > 0, "ys_e2e_select: bad shape B=%d k=%d max_det=%d", batch, k, max_det);
+  YS_CHECK_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  if (on_device) return ys_e2e_select_launch(st, rows, batch, k, conf_thres, max_det, out_count);
+  DevBuf dr, dc;
+  YS_TRY(dr.alloc((size_t)batch * k * 6 * 4)); YS_TRY(dc.alloc((size_t)batch * 4));
+  YS_CHECK_HIP(hipMemcpyAsync(dr.p, rows, (size_t)batch * k * 6 * 4, hipMemcpyHostToDevice, st));
+  YS_TRY(ys_e2e_select_launch(st, (const float*)dr.p, batch, k, conf_thres, max_det, (int*)dc.p));
+  YS_CHECK_HIP(hipMemcpyAsync(out_count, dc.p, (size_t)batch * 4, hipMemcpyDeviceToHost, st));
+  YS_CHECK_HIP(hipStreamSynchronize(st));
+  return YS_OK;
+}

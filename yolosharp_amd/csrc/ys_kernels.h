@@ -336,7 +336,8 @@ size_t ys_loss_partial_floats(int B, int A);
 // ---- decode (Head.cs:204-223)
 int ys_detect_decode_launch(hipStream_t st, int dtype, const void* pd, int ld_pd, const void* ps, int ld_ps, int B, int A,
                             int nc, int reg_max, int nl, const int* lvl_off, const int* lvl_w, const int* lvl_stride,
-                            float* pred, int pred_C, const void* px, int ld_px, int xkind, int nx, int kdim);
+                            float* pred, int pred_C, const void* px, int ld_px, int xkind, int nx, int kdim, int xyxy = 0);
+// xyxy != 0 (End2End, Head.cs:199-202: decode_bboxes with xywh = false): plain Detect boxes as (x1, y1, x2, y2) * stride.
 // xkind 2: Obb decode (dist2rbox with the angle logit px[.][0], Head.cs:435-438, Tal.cs:389-408); 3: Pose.kpts_decode of the nx
 // keypoint outputs (Head.cs:590-605); 0/1: plain Detect decode.  In place (sigmoid(p) - 0.25) * pi (Head.cs:429):
 int ys_obb_angle_launch(hipStream_t st, float* p, long n);
@@ -379,5 +380,11 @@ int ys_cls_bn_bwd_apply_launch(hipStream_t st, int dtype, const void* dpooled, i
 int ys_cls_xent_launch(hipStream_t st, int dtype, const void* logits, int ld, int B, int nc, const float* labels, void* dlogits,
                        float* probs, float* row_loss, float* scalars);
 int ys_cls_topk_launch(hipStream_t st, const float* x, int rows, int cols, int k, int32_t* idx);
+// ---- e2e.hip: End2End post-process (Head.cs:117-127, 175-196; Ops.cs:258-267) and the aliased towers' second BatchNorm update
+// ws: ys_e2e_topk_ws_bytes(B, nc, A, max_det) bytes; rows [B][k][6], anchors [B][k], k = min(max_det, A)
+size_t ys_e2e_topk_ws_bytes(int B, int nc, int A, int max_det);
+int ys_e2e_topk_launch(hipStream_t st, const float* pred, int B, int nc, int A, int max_det, void* ws, float* rows, long long* anchors);
+int ys_e2e_select_launch(hipStream_t st, const float* rows, int B, int k, float conf, int max_det, int* count);
+int ys_e2e_bn_second_update_launch(hipStream_t st, float* state, const float* snap, const unsigned char* is_count, long n, float momentum);
 int ys_process_mask_launch(hipStream_t st, const float* protos, const float* masks_in, const float* boxes, int n, int nm, int mh,
                            int mw, int ih, int iw, int upsample, int trunc_crop, unsigned char* out);

@@ -44,16 +44,21 @@ def clip_boxes(boxes, shape):
 
 
 class Detector:
-    def __init__(self, model):
+    def __init__(self, model, end2end=None):
+        """end2end (default: the model's own flag): Config.End2End (Config.cs:239) -- the model was built with end2end=True, predictions come
+        from the head's own top-k rows and are only thresholded (Ops.cs:258-267), no NMS (Detector.cs:17-23, 44, 99)."""
         self.model, self.engine = model, model.engine
         self.amp = AMPWrapper(model)
+        self.end2end = bool(getattr(model, "end2end", False)) if end2end is None else bool(end2end)
+        if self.end2end and not getattr(model, "end2end", False):
+            raise ValueError("Detector(end2end=True) needs a model created with end2end=True")
 
     def ImagePredict(self, image_chw_u8, predict_threshold=0.25, iou_threshold=0.5):
         """image: uint8 / float [3,H,W] in 0..255 (RGB).  Returns a list of YoloResult."""
         x = pad_to_32(np.asarray(image_chw_u8, np.float32))[None]
         assert x.shape[2:] == (self.model.height, self.model.width), "create the model with the padded image size"
         inference, _ = self.amp.Evaluate(x)
-        output, _ = self.engine.non_max_suppression(inference["boxes"], predict_threshold, iou_threshold)
+        output, _ = self.engine.non_max_suppression(inference["boxes"], predict_threshold, iou_threshold, end2end=self.end2end)
         return [YoloResult(r) for r in output[0]]
 
     def Val(self, batches, conf_thres=0.1, iou_thres=0.7, max_det=300):
@@ -69,6 +74,10 @@ class Detector:
         nc = m.nc
         Cc = 4 + nc + m.NM
         stride = Cc - nc + 2
+        if self.end2end:          # the rows are the head's own [B, k, 6] (ys_model_det_device); the thresholding keeps a prefix of them
+            d_det, max_rows = m.det_device()
+        else:
+            max_rows = max_det
         d_rows = d_keep = d_cnt = d_cor = None
         cap_b = 0
         try:
@@ -86,10 +95,16 @@ class Detector:
                     for p_ in (d_rows, d_keep, d_cnt, d_cor):
                         if p_ is not None:
                             eng.free(p_)
-                    d_rows, d_keep = eng.malloc(B * max_det * stride * 4), eng.malloc(B * max_det * 8)
-                    d_cnt, d_cor = eng.malloc(B * 4), eng.malloc(B * max_det * 10)
+                    if not self.end2end:
+                        d_rows, d_keep = eng.malloc(B * max_det * stride * 4), eng.malloc(B * max_det * 8)
+                    d_cnt, d_cor = eng.malloc(B * 4), eng.malloc(B * max_rows * 10)
                     cap_b = B
-                eng.nms_device(m.pred_device(), B, Cc, m.A, conf_thres, iou_thres, max_det, nc, d_rows, d_keep, d_cnt)
+                if self.end2end:
+                    _lib.check(eng.lib, eng.lib.ys_e2e_select(eng.ctx, d_det, 1, B, max_rows, float(conf_thres), int(max_det), d_cnt))
+                    rows_dev = d_det
+                else:
+                    eng.nms_device(m.pred_device(), B, Cc, m.A, conf_thres, iou_thres, max_det, nc, d_rows, d_keep, d_cnt)
+                    rows_dev = d_rows
                 bi = np.ascontiguousarray(np.asarray(data["batch_idx"], np.float32).reshape(-1))
                 cl = np.ascontiguousarray(np.asarray(data["cls"], np.float32).reshape(-1))
                 bb = np.ascontiguousarray(np.asarray(data["bboxes"], np.float32).reshape(-1, 4))
@@ -97,11 +112,11 @@ class Detector:
                 try:                       # the per-batch label buffers are released on the error paths too
                     for a in (bi, cl, bb):
                         d_lab.append(eng.to_device(a))
-                    _lib.check(eng.lib, eng.lib.ys_val_match_batched(eng.ctx, d_rows, d_cnt, 1, B, max_det, stride, d_lab[0], d_lab[1], d_lab[2],
+                    _lib.check(eng.lib, eng.lib.ys_val_match_batched(eng.ctx, rows_dev, d_cnt, 1, B, max_rows, stride, d_lab[0], d_lab[1], d_lab[2],
                                                                      bi.shape[0], float(images.shape[3]), float(images.shape[2]), d_cor))
-                    rows = eng.from_device(d_rows, (B, max_det, stride), np.float32)
+                    rows = eng.from_device(rows_dev, (B, max_rows, stride), np.float32)
                     cnt = eng.from_device(d_cnt, (B,), np.int32)
-                    cor = eng.from_device(d_cor, (B, max_det, 10), np.uint8)
+                    cor = eng.from_device(d_cor, (B, max_rows, 10), np.uint8)
                 finally:
                     for p_ in d_lab:
                         eng.free(p_)

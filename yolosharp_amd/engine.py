@@ -158,6 +158,27 @@ class Engine:
         _lib.check(self.lib, self.lib.ys_cls_topk(self.ctx, _ptr(x), 0, rows, cols, k, _ptr(out)))
         return out
 
+    # ---- End2End post-process (Head.cs:117-127, 175-196; Ops.cs:258-267)
+    def e2e_topk(self, pred, max_det=300):
+        """Detect.postprocess on pred [B, 4+nc, A] fp32: (rows [B, k, 6] = (box, score, class) ordered by score, anchor [B, k] int64),
+        k = min(max_det, A); equal scores keep the lower index first (include/yolosharp_hip.h ys_e2e_topk)."""
+        p = np.ascontiguousarray(pred, np.float32)
+        B, Cc, A = p.shape
+        k = min(int(max_det), A)
+        rows = np.zeros((B, k, 6), np.float32)
+        anchor = np.zeros((B, k), np.int64)
+        _lib.check(self.lib, self.lib.ys_e2e_topk(self.ctx, _ptr(p), 0, B, Cc - 4, A, int(max_det), _ptr(rows), _ptr(anchor)))
+        return rows, anchor
+
+    def e2e_select(self, rows, conf_thres=0.25, max_det=300):
+        """non_max_suppression(end2end: true): the number of leading rows of rows [B, k, 6] with score > conf_thres, at most max_det -> int32 [B]."""
+        r = np.ascontiguousarray(rows, np.float32)
+        B, k, six = r.shape
+        assert six == 6, r.shape
+        cnt = np.zeros((B,), np.int32)
+        _lib.check(self.lib, self.lib.ys_e2e_select(self.ctx, _ptr(r), 0, B, k, float(conf_thres), int(max_det), _ptr(cnt)))
+        return cnt
+
     # ---- validation (Detector.cs:103-120): box_iou + match_predictions per image, batched on the device
     def box_iou(self, box1, box2, eps=1e-7):
         """Metrics.box_iou (Metrics.cs:16-34): xyxy [n,4] x [m,4] -> [n,m] fp32."""
@@ -248,8 +269,10 @@ class Engine:
         `agnostic` flag is accepted but ignored (Ops.cs:345), and invalid thresholds raise (YsError status 1).
         rotated=True (Ops.cs:286,349-353): oriented boxes, angle = last channel, boxes stay xywh, Ops.nms_rotated's
         "any earlier box overlaps" rule on Metrics.batch_probiou."""
-        if end2end:
-            raise NotImplementedError("end2end NMS is outside the hot path (SURVEY.md 8a)")
+        if end2end:        # Ops.cs:258-267: prediction [B, k, 6] rows ordered by score -> rows with score > conf_thres, at most max_det; no keep indices
+            rows = np.ascontiguousarray(prediction, np.float32)
+            cnt = self.e2e_select(rows, conf_thres, max_det)
+            return [rows[b, :cnt[b]].copy() for b in range(rows.shape[0])], [np.zeros((0,), np.float32)]
         pred = prediction if in_place else prediction.copy()
         if pred.dtype != np.float32 or not pred.flags["C_CONTIGUOUS"]:
             raise TypeError("prediction must be a C-contiguous float32 array [B, C, A]")

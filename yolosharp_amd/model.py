@@ -26,7 +26,7 @@ class Yolov8:
     NM = 0              # extra outputs per anchor after the class scores (Segment: 32 mask coefficients, Obb: 1 angle, Pose: nk)
 
     def __init__(self, engine: Engine, nc=80, reg_max=16, size="n", height=640, width=640, max_batch=1, dtype="bf16",
-                 max_labels=0, kpt_num=17, kpt_dim=3):
+                 max_labels=0, kpt_num=17, kpt_dim=3, end2end=False, max_det=300):
         self.engine, self.lib = engine, engine.lib
         self.nc, self.reg_max, self.height, self.width, self.max_batch = nc, reg_max, height, width, max_batch
         self.dtype = dtype
@@ -40,6 +40,11 @@ class Yolov8:
         self.A = self.lib.ys_model_num_anchors(self.handle)
         self._batch = 0
         self._info = None
+        # Config.End2End (Config.cs:239) -> YoloBaseTaskModel.One2one_Init: the one2one towers alias cv2 / cv3 (Head.cs:152-167), no new tensors.
+        # Detect models only; the library refuses the other tasks (YsError status 4)
+        self.end2end, self.max_det = False, int(max_det)
+        if end2end:
+            self.one2one_init(max_det)
 
     def close(self):
         if self.handle:
@@ -56,6 +61,28 @@ class Yolov8:
             self.close()
         except Exception:
             pass
+
+    def one2one_init(self, max_det=300):
+        _lib.check(self.lib, self.lib.ys_model_one2one_init(self.handle, int(max_det)))
+        self.end2end, self.max_det = True, int(max_det) if max_det else 300
+
+    def det_device(self):
+        """Device pointer of the End2End eval output "det" [B, k, 6] and k = min(max_det, A)."""
+        p, k = C.c_void_p(), C.c_int()
+        _lib.check(self.lib, self.lib.ys_model_det_device(self.handle, C.byref(p), C.byref(k)))
+        return p, k.value
+
+    def _outputs(self):
+        """(inference, preds) of the last forward in the reference's shape.  End2End (Head.cs:89-115): preds = {"one2many": ..., "one2one": ...},
+        inference["boxes"] = the post-processed rows [B, k, 6]; "pred" keeps the [B, 4+nc, A] tensor (xyxy boxes) they were taken from."""
+        preds = {"boxes": self.get_output("boxes"), "scores": self.get_output("scores")}
+        if self.end2end:
+            preds = {"one2many": preds, "one2one": {"boxes": self.get_output("one2one_boxes"), "scores": self.get_output("one2one_scores")}}
+        if self.training:
+            return None, preds
+        if self.end2end:
+            return {"boxes": self.get_output("det"), "pred": self.get_output("pred")}, preds
+        return {"boxes": self.get_output("pred")}, preds
 
     # ---- state_dict surface
     def tensor_info(self):
@@ -131,10 +158,7 @@ class Yolov8:
         self._batch = B
         if not fetch:
             return None, None
-        preds = {"boxes": self.get_output("boxes"), "scores": self.get_output("scores")}
-        if self.training:
-            return None, preds
-        return {"boxes": self.get_output("pred")}, preds
+        return Yolov8._outputs(self)
 
     __call__ = forward
 
@@ -146,15 +170,18 @@ class Yolov8:
         assert c == 3
         _lib.check(self.lib, self.lib.ys_model_forward_u8(self.handle, _ptr(x), 0, B, h, w))
         self._batch = B
-        preds = {"boxes": self.get_output("boxes"), "scores": self.get_output("scores")}
-        return (None, preds) if self.training else ({"boxes": self.get_output("pred")}, preds)
+        return Yolov8._outputs(self)
 
     def get_output(self, key):
         B = self._batch
         C_ = {"boxes": 4 * self.reg_max, "scores": self.nc, "pred": 4 + self.nc + self.NM, "dboxes": 4 * self.reg_max,
               "dscores": self.nc, "mask_coefficient": self.NM, "dmask_coefficient": self.NM, "angle": self.NM, "kpts": self.NM, "dkpts": self.NM, "dangle": self.NM}.get(key)
+        if key.startswith("one2one_"):
+            C_ = 4 * self.reg_max if key.endswith("boxes") else self.nc
         if key in ("proto", "dproto"):
             a = np.empty((B, self.NM, self.height // 4, self.width // 4), np.float32)
+        elif key == "det":
+            a = np.empty((B, min(self.max_det, self.A), 6), np.float32)
         else:
             a = np.empty((B, C_, self.A), np.float32)
         _lib.check(self.lib, self.lib.ys_model_get_output(self.handle, key.encode(), _ptr(a), a.size))
@@ -364,7 +391,9 @@ class Yolov11Classify(_ClassifyMixin, Yolov11):
 
 class v8DetectionLoss:
     """Loss.cs:328-484.  forward(preds, batch): `preds` is implicit (the model's last training forward stays on the
-    device); batch = {"batch_idx": [N], "cls": [N], "bboxes": [N,4] normalised cxcywh} (YoloDataLoader.cs:18-44)."""
+    device); batch = {"batch_idx": [N], "cls": [N], "bboxes": [N,4] normalised cxcywh} (YoloDataLoader.cs:18-44).
+    On an End2End model the same call is E2EDetectLoss (Loss.cs:1094-1118): the one2many (tal_topk 10) and one2one (tal_topk 1) criteria
+    run in the library and the returned items / loss are their sums."""
 
     def __init__(self, model: Yolov8):
         self.model, self.lib = model, model.lib

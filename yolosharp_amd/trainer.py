@@ -81,6 +81,8 @@ class Trainer:
         task = 1 if segment else getattr(model, "TASK", 0)
         self.crit = {0: v8DetectionLoss, 1: v8SegmentationLoss, 2: v8OBBLoss, 3: v8PoseLoss, 4: v8ClassificationLoss}[task](model)
         self.validator = {0: D.Detector, 1: D.Segmenter, 2: D.Obber, 3: D.PoseDetector, 4: D.Classifier}[task]
+        # Config.End2End travels with the model (Yolov8(..., end2end=True)): ys_loss_detect is then E2EDetectLoss and D.Detector validates without NMS
+        self.end2end = bool(getattr(model, "end2end", False))
         self.sched = LrSchedule(model.nc, epochs, nb, **sched)
         self.best_fitness = -float("inf")
 
