@@ -74,6 +74,16 @@ namespace YoloSharp.Native
         // Augment.LetterBox / Augment.Rectangle (Data/Augment.cs:698-857) on the device; uint8 planes (isFloat = 0) or fp32 masks
         [DllImport(Lib)] internal static extern int ys_letterbox(IntPtr ctx, byte[] src, int isFloat, int onDevice, int C, int h, int w, int fitW, int fitH,
                                                                  int outW, int outH, int color, [Out] byte[] dst, out int padL, out int padU);
+        // Training input on the device (Data/YoloDataset.cs:57-151: Mosaic4 + RandomPerspective + FlipLR / FlipUD + Normalize + mul(1/255) + collate): the sources live in
+        // one uint8 arena, an item carries what the reference draws per output image.  Device-resident callers pass IntPtr (on_device = 1) for every pointer.
+        // Quirk kept: a flipped box keeps x1 > x2 (negative w after cxcywh) unless flags has YS_AUG_SORT_FLIPPED (1).  Not built: RandomHSV, OBB corners, the no-mosaic branch.
+        [StructLayout(LayoutKind.Sequential)] internal struct YsAugSrc { public long imgOff, maskOff; public int h, w, mh, mw; }
+        [StructLayout(LayoutKind.Sequential)] internal struct YsAugItem { public int src0, src1, src2, src3, xc, yc; public float m00, m01, m02, m10, m11, m12, m20, m21, m22; public int flipLr, flipUd; }
+        [DllImport(Lib)] internal static extern int ys_augment_mosaic(IntPtr ctx, IntPtr arena, IntPtr srcs, int nSrc, IntPtr items, int batch, int onDevice, int imgsz,
+                                                                      int maskRatio, int perspective, IntPtr images, IntPtr masks);
+        [DllImport(Lib)] internal static extern int ys_augment_labels(IntPtr ctx, IntPtr srcs, IntPtr labOff, IntPtr cls, IntPtr boxes, IntPtr keypoints, int kptNum, int kptDim,
+                                                                      IntPtr items, int batch, int onDevice, int imgsz, int perspective, int flags, int capacity,
+                                                                      IntPtr outBatchIdx, IntPtr outCls, IntPtr outBboxes, IntPtr outKeypoints, IntPtr outCount);
         // Classify task (Head.Classify / v8ClassificationLoss / Classifier.Val, Models/Classifier.cs): outputs "cls" / "logits" / "dcls" [B,nc]
         // through ys_model_get_output; one loss item (the mean) through ys_loss_read_items
         [DllImport(Lib)] internal static extern int ys_loss_classify(IntPtr model, float[] cls, int batch, int onDevice);

@@ -348,6 +348,55 @@ YS_API int ys_process_mask(ys_ctx* ctx, const float* protos, const float* masks_
 YS_API int ys_letterbox(ys_ctx* ctx, const void* src, int is_float, int on_device, int C, int h, int w, int fit_w, int fit_h,
                         int out_w, int out_h, int color, void* dst, int32_t* pad_l, int32_t* pad_u);
 
+/* ---- training input on the device: the reference's default training pipeline (ImageProcessType.Mosiac,
+ * Data/YoloDataset.cs:57-151) -- Augment.Mosaic._mosaic4 (Data/Augment.cs:158-274), Augment.RandomPerspective (:315-695), FlipLR / FlipUD
+ * (:860-966), Normalize (Data/Struct.cs:99-121), mul(1/255) and the collate (Data/YoloDataLoader.cs:18-44) -- as one call per batch for the
+ * images and one for the labels.  The random draws stay on the host: an item carries the parameters the reference draws (four source indices,
+ * the mosaic centre, the forward matrix exactly as affine_transform returns it, the two flip decisions).
+ * The sources live in one uint8 `arena`: source k has its RGB planes [3][h][w] at byte offset img_off and, optionally, its overlap-encoded
+ * instance-id mask [mh][mw] at mask_off (-1 = none).  The library cannot see the arena's size: offsets and sizes are the caller's
+ * responsibility.
+ *
+ * ys_augment_mosaic: images fp32 [batch, 3, imgsz, imgsz] in [0, 1]; masks (may be NULL) fp32 [batch, imgsz / mask_ratio, imgsz / mask_ratio],
+ * the layout ys_loss_segment reads.  The 2s x 2s canvas of _mosaic4 is never materialised: canvas pixel (Y, X) is 114 (masks 0) or the pixel of
+ * the tile whose rectangle (:184-203; masks: every bound / mask_ratio, :207-209) holds it.  The warp restates Warp{Affine,Perspective}WithGridSample:
+ * src = M_inv (x, y, 1) / w; outside 0 <= src <= in - 1 the border value (114; masks 0); inside grid_sample(bilinear, border, align_corners = false)
+ * at grid = src / (in - 1) * 2 - 1 -- i.e. at src * in / (in - 1) - 0.5, NOT at src -- then clamp(0, 255) and truncation to a byte; masks take the
+ * same BILINEAR path on their id bytes with M_mask = S_inv M S (:371-389).  perspective != 0 selects the perspective form (all of M, divide by w;
+ * the reference's `perspective > 0`), 0 the affine form (rows 0-1 of M over (0, 0, 1)).  M is inverted, the source position evaluated and the
+ * four bytes blended in double (the reference: fp32), the blend as a nested interpolation that is exact on constant regions.  Flips are folded into the output coordinate; a byte b becomes
+ * (float)b * (1 / 255.0f).
+ *
+ * ys_augment_labels: per-source label tables -- lab_off [n_src + 1] (labels of source k = [lab_off[k], lab_off[k + 1])), cls [n], boxes [n, 4]
+ * pixel xyxy in the source's own frame, keypoints [n, kpt_num, 3] pixels + visibility (NULL = none) -- become the collate's rows for the same
+ * items: per image, tiles in order, labels in order: + (padw, padh), clip to [0, 2s], keep if area > 0 && area > 0.7 * org_area (:238-256);
+ * apply_bboxes (:546-568), clip_boxes to [0, s], keep if area > 0 (:681-692); apply_keypoints (:581-601, always divides by w) + clip_keypoints
+ * (Utils/Ops.cs:166-183); the flips; cxcywh / s, keypoints x, y / s.  Rows are COMPACTED in collate order (batch_idx non-decreasing, stable within
+ * an image) into arrays of `capacity` rows: out_batch_idx [capacity], out_cls [capacity], out_bboxes [capacity, 4], out_keypoints
+ * [capacity, kpt_num, 3] (NULL iff keypoints is NULL); rows [*out_count, capacity) hold batch_idx -1 and zeros, which ys_loss_* skip -- a caller
+ * passes n_labels = capacity with on_device = 1 and never reads *out_count on the host.
+ * QUIRK kept by default: FlipLR / FlipUD set x <- s - x on columns 0 and 2 (y: 1 and 3) WITHOUT swapping them (:890-891, :945-946), so a flipped
+ * box has a negative width / height after cxcywh.  flags & YS_AUG_SORT_FLIPPED writes (min, max) instead.
+ *
+ * on_device applies to every pointer of a call; with device pointers both calls are asynchronous on the context's stream.  With host pointers
+ * (on_device = 0) the items are validated and YS_ERR_INVALID_ARG is returned for: a src outside [0, n_src), imgsz odd or < 2, xc / yc outside
+ * [0, 2 * imgsz], a singular M, and a capacity below the sum of the four tiles' label counts of some image.  Device items cannot be read by the
+ * host: an item that fails those checks yields an all-114 image (zero masks) and no labels; if more rows are kept than `capacity`, *out_count holds
+ * the true total (> capacity) and the rows past capacity are not written.  Nothing is truncated silently.
+ * Scope: kpt_dim must be 3 (apply_keypoints reads column 2; 2 -> YS_ERR_INVALID_ARG).  Not built: OBB corner labels (xyxyxyxy2xywhr is host code in
+ * the reference), RandomHSV (TorchVision.NET ColorJitter, not part of the reference tree), the no-mosaic branch (rand > p: the reference then yields
+ * images of unequal sizes its own collate cannot stack).  Deviations: a label-free sample is still warped (RandomPerspective.Apply returns the
+ * unwarped 2s x 2s canvas, :666-669); where the reference's mask slice would run past the source mask (it throws) the kernel reads 0. */
+typedef struct ys_aug_src { int64_t img_off, mask_off; int32_t h, w, mh, mw; } ys_aug_src;
+typedef struct ys_aug_item { int32_t src[4]; int32_t xc, yc; float M[9]; int32_t flip_lr, flip_ud; } ys_aug_item;
+#define YS_AUG_SORT_FLIPPED 1
+YS_API int ys_augment_mosaic(ys_ctx* ctx, const uint8_t* arena, const ys_aug_src* srcs, int n_src, const ys_aug_item* items, int batch,
+                             int on_device, int imgsz, int mask_ratio, int perspective, float* images, float* masks);
+YS_API int ys_augment_labels(ys_ctx* ctx, const ys_aug_src* srcs, const int32_t* lab_off, const float* cls, const float* boxes,
+                             const float* keypoints, int kpt_num, int kpt_dim, const ys_aug_item* items, int batch, int on_device,
+                             int imgsz, int perspective, int flags, int capacity, float* out_batch_idx, float* out_cls, float* out_bboxes,
+                             float* out_keypoints, int32_t* out_count);
+
 /* ---- per-operator entry points (unit parity; a TorchSharp-free C# Conv wrapper) ---------------
  * Convs.Conv.forward (Convs.cs:36-62): y = act(BN(conv2d(x))) on fp32 NCHW / OIHW HOST arrays at the
  * edge (the call stages them through HBM).  training != 0 uses batch statistics and updates running stats (momentum 0.03, eps 1e-3). */

@@ -1,0 +1,218 @@
+"""Cost of the device-side training input (csrc/augment.hip) on one device: prints ONE JSON line.
+
+  python tools/aug_bench.py [--batch 64] [--imgsz 640] [--sources 128] [--steps 20] [--warmup 5] [--repeats 3]
+
+Four measurements, each in a child process of its own under its own time limit (a leg that fails or runs out of time ends the run):
+  augment          ms per batch of ys_augment_mosaic + ys_augment_labels on a device-resident arena and item table (and of the image call alone);
+                   bytes from shapes -- the fp32 batch written plus the tiles' source bytes, each read once -- over that time as a share of
+                   the 6.3 TB/s this project measured for HBM.  The bound of the kernel is HBM: it is a gather with a streaming write.
+  torch_augment    a torch restatement of the reference's op sequence (Data/Augment.cs:158-274, 395-538, 860-966) for the IMAGES on the same GPU:
+                   per image the uint8 canvas paste and grid_sample, the flips, then the stack and mul(1/255).  Written here, not imported from tests/.
+  step_static      the YOLOv8n bf16 train step (forward, criterion, backward, AdamW, zero_grad) on one fixed device batch
+  step_augmented   the same step fed by MosaicAugmenter.batch() -- host draws, item upload, both kernels -- every iteration
+Every figure is the median over --repeats timed blocks of --steps calls after --warmup calls, with a synchronise inside the window.
+"""
+import argparse
+import json
+import os
+import subprocess
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+LEGS = ("augment", "torch_augment", "step_static", "step_augmented")
+HBM_TBPS = 6.3
+HYP = dict(degrees=10.0, translate=0.1, scale=0.5, shear=2.0, perspective=0.0)
+
+
+def _dataset(a):
+    """--sources synthetic images (letterboxed-to-imgsz shapes like a resized COCO: one side = imgsz) with 8 labels each."""
+    g = np.random.default_rng(0)
+    S = a.imgsz
+    imgs, labels = [], []
+    for k in range(a.sources):
+        short = int(g.integers(S // 2, S + 1))
+        h, w = (S, short) if k % 2 else (short, S)
+        imgs.append(g.integers(0, 256, (3, h, w), dtype=np.uint8))
+        n = 8
+        x1, y1 = g.random(n) * w * 0.7, g.random(n) * h * 0.7
+        labels.append(dict(cls=g.integers(0, a.nc, n).astype(np.float32),
+                           bboxes=np.stack([x1, y1, x1 + (0.05 + 0.25 * g.random(n)) * w, y1 + (0.05 + 0.25 * g.random(n)) * h], 1).astype(np.float32)))
+    return imgs, labels
+
+
+def _timed(fn, sync, a):
+    for _ in range(a.warmup):
+        fn()
+    sync()
+    ms = []
+    for _ in range(a.repeats):
+        t0 = time.perf_counter()
+        for _ in range(a.steps):
+            fn()
+        sync()
+        ms.append((time.perf_counter() - t0) * 1e3 / a.steps)
+    return float(np.median(ms)), [round(v, 4) for v in ms]
+
+
+def _augmenter(eng, a):
+    from yolosharp_amd.augment import MosaicAugmenter
+    imgs, labels = _dataset(a)
+    return MosaicAugmenter(eng, imgs, labels, a.imgsz, seed=1, max_batch=a.batch, **HYP), imgs
+
+
+def leg_augment(a):
+    from yolosharp_amd import Engine, _lib
+    from yolosharp_amd.augment import mosaic4_rects
+    eng = Engine(0)
+    aug, imgs = _augmenter(eng, a)
+    B, S = a.batch, a.imgsz
+    items = aug.draw(np.arange(B) % aug.count)
+    aug.run(items)                                                    # uploads the item table; the timed calls below reuse it on the device
+    lib = eng.lib
+
+    def images():
+        _lib.check(lib, lib.ys_augment_mosaic(eng.ctx, aug.d_arena, aug.d_srcs, aug.count, aug.d_items, B, 1, S, aug.r, 0, aug.d_images, None))
+
+    def both():
+        images()
+        _lib.check(lib, lib.ys_augment_labels(eng.ctx, aug.d_srcs, aug.d_lab_off, aug.d_cls, aug.d_boxes, None, 0, 3, aug.d_items, B, 1, S, 0, 0, aug.capacity,
+                                              aug.d_bidx, aug.d_ocls, aug.d_obox, None, aug.d_cnt))
+
+    ms, runs = _timed(both, eng.synchronize, a)
+    ms_img, runs_img = _timed(images, eng.synchronize, a)
+    written = B * 3 * S * S * 4
+    read = 0
+    for it in items:
+        shapes = [imgs[k].shape[1:] for k in it["src"]]
+        read += sum(3 * (r[0][2] - r[0][0]) * (r[0][3] - r[0][1]) for r in mosaic4_rects(int(it["xc"]), int(it["yc"]), shapes, S))
+    kept = int(eng.from_device(aug.d_cnt, (1,), np.int32)[0])
+    aug.close()
+    return {"ms_per_batch": round(ms, 4), "runs": runs, "images_only_ms": round(ms_img, 4), "images_only_runs": runs_img, "bytes_written": written,
+            "bytes_read_at_most": read, "hbm_share_of_%.1f_TBps" % HBM_TBPS: round((written + read) / (ms_img * 1e-3) / (HBM_TBPS * 1e12), 4),
+            "bound": "HBM (streaming fp32 write + gather)", "labels_kept": kept, "B": B, "imgsz": S, "sources": a.sources}
+
+
+def leg_torch_augment(a):
+    import torch
+    import torch.nn.functional as F
+    from yolosharp_amd.augment import draw_items, mosaic4_rects
+    imgs, labels = _dataset(a)
+    B, S = a.batch, a.imgsz
+    items = draw_items(np.random.default_rng(1), np.arange(B) % len(imgs), S, len(imgs), HYP, 0.5, 0.0)   # same seed, same item table as the augment leg
+    dimgs = [torch.from_numpy(im).cuda() for im in imgs]
+    gx = torch.arange(S, dtype=torch.float32, device="cuda").view(1, S).repeat(S, 1)
+    gy = torch.arange(S, dtype=torch.float32, device="cuda").view(S, 1).repeat(1, S)
+    flat = torch.stack([gx, gy, torch.ones_like(gx)], 0).view(3, -1)
+    border = torch.full((3, 1, 1), 114.0, device="cuda")
+    Ms = [torch.from_numpy(it["M"].reshape(3, 3).copy()).cuda() for it in items]
+
+    def one(it, M):
+        img4 = torch.full((3, 2 * S, 2 * S), 114, dtype=torch.uint8, device="cuda")
+        shapes = [imgs[k].shape[1:] for k in it["src"]]
+        for k, (ra, rb) in zip(it["src"], mosaic4_rects(int(it["xc"]), int(it["yc"]), shapes, S)):
+            img4[:, ra[1]:ra[3], ra[0]:ra[2]] = dimgs[k][:, rb[1]:rb[3], rb[0]:rb[2]]
+        img = img4.to(torch.float32)
+        M3 = torch.eye(3, device="cuda")
+        M3[:2] = M[:2]
+        sf = torch.linalg.inv(M3).mm(flat)
+        src = (sf[:2] / sf[2:3]).view(2, S, S)
+        grid = torch.zeros(1, S, S, 2, device="cuda")
+        grid[0, :, :, 0] = src[0] / (2 * S - 1) * 2 - 1
+        grid[0, :, :, 1] = src[1] / (2 * S - 1) * 2 - 1
+        smp = F.grid_sample(img[None], grid, mode="bilinear", padding_mode="border", align_corners=False)[0]
+        valid = (src[0] >= 0) & (src[0] <= 2 * S - 1) & (src[1] >= 0) & (src[1] <= 2 * S - 1)
+        out = torch.clamp(torch.where(valid[None], smp, border.expand_as(smp)), 0, 255).to(torch.uint8)
+        if it["flip_lr"]:
+            out = out.flip(-1)
+        if it["flip_ud"]:
+            out = out.flip(-2)
+        return out[None].mul(1 / 255.0)
+
+    def call():
+        return torch.cat([one(it, M) for it, M in zip(items, Ms)], 0)
+
+    ms, runs = _timed(call, torch.cuda.synchronize, a)
+    return {"ms_per_batch": round(ms, 4), "runs": runs, "what": "images only (canvas paste + grid_sample per image, flips, stack, mul 1/255)"}
+
+
+def leg_step(a, augmented):
+    from yolosharp_amd import Engine
+    from yolosharp_amd.model import AMPWrapper, Yolov8, v8DetectionLoss
+    eng = Engine(0)
+    B, S = a.batch, a.imgsz
+    aug, _ = _augmenter(eng, a)
+    m = Yolov8(eng, nc=a.nc, size="n", height=S, width=S, max_batch=B, dtype="bf16")
+    m.init_weights(1)
+    m.reserve_labels(aug.max_per_image)
+    crit, amp = v8DetectionLoss(m), AMPWrapper(m)
+    m.train()
+    db = aug.batch(np.arange(B) % aug.count)
+    state = {"i": 0}
+
+    def step():
+        d = db
+        if augmented:
+            state["i"] += 1
+            d = aug.batch((np.arange(B) + state["i"] * B) % aug.count)
+        m.forward_device(d.images, B)
+        crit.forward_device(d.batch_idx, d.cls, d.bboxes, d.capacity)
+        amp.Step()
+
+    ms, runs = _timed(step, eng.synchronize, a)
+    _, items = crit.read()
+    t0 = time.perf_counter()
+    for _ in range(5):
+        aug.draw(np.arange(B))
+    draw_ms = (time.perf_counter() - t0) * 1e3 / 5
+    m.close(); aug.close()
+    return {"ms_per_step": round(ms, 4), "runs": runs, "loss_items": [float(v) for v in items], "label_rows": db.capacity, "host_draw_ms": round(draw_ms, 4)}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", type=int, default=64)
+    ap.add_argument("--imgsz", type=int, default=640)
+    ap.add_argument("--sources", type=int, default=128)
+    ap.add_argument("--nc", type=int, default=80)
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--leg-timeout", type=int, default=240, help="seconds per child process")
+    ap.add_argument("--leg", choices=LEGS, help="run one measurement in this process (what the driver starts)")
+    a = ap.parse_args()
+    if a.leg:
+        out = {"augment": lambda: leg_augment(a), "torch_augment": lambda: leg_torch_augment(a), "step_static": lambda: leg_step(a, False),
+               "step_augmented": lambda: leg_step(a, True)}[a.leg]()
+        print(json.dumps(out))
+        return 0
+    res = {"metric": "augment_cost", "model": "yolov8n", "dtype": "bf16", "batch": a.batch, "imgsz": a.imgsz, "sources": a.sources}
+    fwd = [x for kv in (("--batch", a.batch), ("--imgsz", a.imgsz), ("--sources", a.sources), ("--nc", a.nc), ("--steps", a.steps), ("--warmup", a.warmup),
+                        ("--repeats", a.repeats)) for x in (kv[0], str(kv[1]))]
+    for leg in LEGS:
+        try:
+            r = subprocess.run([sys.executable, os.path.abspath(__file__), "--leg", leg] + fwd, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
+                               text=True, timeout=a.leg_timeout, stdin=subprocess.DEVNULL)
+        except subprocess.TimeoutExpired:
+            res["failed"] = {"leg": leg, "why": "time limit of %d s" % a.leg_timeout}
+            break                                   # nothing more is started on the device after a leg that hung
+        if r.returncode != 0:
+            res["failed"] = {"leg": leg, "rc": r.returncode, "stderr": r.stderr[-2000:]}
+            break                                   # ... or that failed
+        res[leg] = json.loads(r.stdout.strip().splitlines()[-1])
+    if "augment" in res and "torch_augment" in res:
+        res["torch_over_augment_images"] = round(res["torch_augment"]["ms_per_batch"] / res["augment"]["images_only_ms"], 2)
+    if "step_static" in res and "step_augmented" in res:
+        res["augment_extra_ms_per_step"] = round(res["step_augmented"]["ms_per_step"] - res["step_static"]["ms_per_step"], 4)
+        res["augment_extra_share_of_step"] = round(res["augment_extra_ms_per_step"] / res["step_static"]["ms_per_step"], 4)
+    print(json.dumps(res))
+    return 1 if "failed" in res else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

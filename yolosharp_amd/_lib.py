@@ -36,6 +36,16 @@ class HeadDesc(C.Structure):
                 ("kpt_num", C.c_int32), ("kpt_dim", C.c_int32)]
 
 
+class AugSrc(C.Structure):
+    """ys_aug_src: one source of the augmenter's arena (byte offsets; mask_off = -1: no mask)."""
+    _fields_ = [("img_off", C.c_int64), ("mask_off", C.c_int64), ("h", C.c_int32), ("w", C.c_int32), ("mh", C.c_int32), ("mw", C.c_int32)]
+
+
+class AugItem(C.Structure):
+    """ys_aug_item: the draws of one output image."""
+    _fields_ = [("src", C.c_int32 * 4), ("xc", C.c_int32), ("yc", C.c_int32), ("M", C.c_float * 9), ("flip_lr", C.c_int32), ("flip_ud", C.c_int32)]
+
+
 # name -> (restype, argtypes); must list every symbol of include/yolosharp_hip.h
 PROTOTYPES = {
     "ys_last_error": (C.c_char_p, []),
@@ -130,6 +140,9 @@ PROTOTYPES = {
     "ys_e2e_select": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_void_p]),
     "ys_optim_set_param_groups": (C.c_int, [C.c_void_p, C.c_int]),
     "ys_letterbox": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, c_i32_p, c_i32_p]),
+    "ys_augment_mosaic": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "ys_augment_labels": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
+                                   C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ys_block_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "ys_block_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "ys_device_malloc": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]),

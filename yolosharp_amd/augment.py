@@ -1,0 +1,257 @@
+"""The reference's default training input (ImageProcessType.Mosiac, Data/YoloDataset.cs:57-151) with the pixels and labels produced on the
+device (csrc/augment.hip; include/yolosharp_hip.h ys_augment_mosaic / ys_augment_labels).  The host keeps what is random: per output
+image it draws what Augment.Mosaic (Data/Augment.cs:153-164), RandomPerspective.affine_transform (:323-356) and FlipLR / FlipUD (:869, :926)
+draw, and uploads one 68-byte item.  TorchSharp's torch.rand streams cannot be reproduced: the drawn PARAMETERS are the interface.
+
+Not built: RandomHSV (TorchVision.NET ColorJitter), OBB corner labels, the no-mosaic branch (rand > p).  kpt_dim = 3 only."""
+import ctypes as C
+import math
+
+import numpy as np
+
+from . import _lib
+
+SRC_DTYPE = np.dtype([("img_off", "<i8"), ("mask_off", "<i8"), ("h", "<i4"), ("w", "<i4"), ("mh", "<i4"), ("mw", "<i4")])
+ITEM_DTYPE = np.dtype([("src", "<i4", (4,)), ("xc", "<i4"), ("yc", "<i4"), ("M", "<f4", (9,)), ("flip_lr", "<i4"), ("flip_ud", "<i4")])
+assert SRC_DTYPE.itemsize == C.sizeof(_lib.AugSrc) == 32 and ITEM_DTYPE.itemsize == C.sizeof(_lib.AugItem) == 68
+YS_AUG_SORT_FLIPPED = 1
+
+
+def _ptr(a):
+    return a.ctypes.data_as(C.c_void_p) if a is not None else None
+
+
+def mosaic4_rects(xc, yc, shapes, s):
+    """Augment.Mosaic._mosaic4's rectangles (:184-203) for the four (h, w) of `shapes`: a list of ((x1a, y1a, x2a, y2a), (x1b, y1b, x2b, y2b)) --
+    canvas rectangle of the 2s x 2s image, source rectangle of the tile.  padw = x1a - x1b, padh = y1a - y1b (:211-212)."""
+    out = []
+    for i, (h, w) in enumerate(shapes):
+        if i == 0:
+            a = (max(xc - w, 0), max(yc - h, 0), xc, yc)
+            b = (w - (a[2] - a[0]), h - (a[3] - a[1]), w, h)
+        elif i == 1:
+            a = (xc, max(yc - h, 0), min(xc + w, s * 2), yc)
+            b = (0, h - (a[3] - a[1]), min(w, a[2] - a[0]), h)
+        elif i == 2:
+            a = (max(xc - w, 0), yc, xc, min(s * 2, yc + h))
+            b = (w - (a[2] - a[0]), 0, w, min(a[3] - a[1], h))
+        else:
+            a = (xc, yc, min(xc + w, s * 2), min(s * 2, yc + h))
+            b = (0, 0, min(w, a[2] - a[0]), min(a[3] - a[1], h))
+        out.append((a, b))
+    return out
+
+
+def perspective_matrices(u, s, degrees=0.0, translate=0.1, scale=0.5, shear=0.0, perspective=0.0):
+    """RandomPerspective.affine_transform's M (:323-356) for n images at once from their uniform draws u [n, 8] in [0, 1) -- in the reference's
+    draw order: perspective x, y; angle; scale; shear x, y; translate x, y -- for the 2s x 2s mosaic canvas and the s x s output.
+    M = T @ S @ R @ P @ C with C at minus half the canvas, fp32 like the reference.  -> [n, 3, 3] float32."""
+    f = np.float32
+    d = np.asarray(u, f).reshape(-1, 8) * f(2) - f(1)
+    n = d.shape[0]
+    Cm, P, R, S, T = (np.tile(np.eye(3, dtype=f), (n, 1, 1)) for _ in range(5))
+    Cm[:, 0, 2] = Cm[:, 1, 2] = -(2 * s) // 2
+    P[:, 2, 0] = d[:, 0] * f(perspective)
+    P[:, 2, 1] = d[:, 1] * f(perspective)
+    sc = f(1) + d[:, 3] * f(scale)
+    rad = (d[:, 2] * f(degrees) * f(math.pi) / f(180.0)).astype(f)
+    alpha, beta = np.cos(rad).astype(f) * sc, np.sin(rad).astype(f) * sc            # GetRotationMatrix2D(0, 0, a, sc), :645-662
+    R[:, 0, 0], R[:, 0, 1], R[:, 1, 0], R[:, 1, 1] = alpha, beta, -beta, alpha
+    S[:, 0, 1] = np.tan(d[:, 4].astype(np.float64) * shear * math.pi / 180.0)
+    S[:, 1, 0] = np.tan(d[:, 5].astype(np.float64) * shear * math.pi / 180.0)
+    T[:, 0, 2] = (0.5 + d[:, 6].astype(np.float64) * translate) * s
+    T[:, 1, 2] = (0.5 + d[:, 7].astype(np.float64) * translate) * s
+    return (T @ (S @ (R @ (P @ Cm)))).astype(f)
+
+
+def random_perspective_matrix(rng, s, degrees=0.0, translate=0.1, scale=0.5, shear=0.0, perspective=0.0):
+    """One matrix from eight draws of `rng` (anything with .random(), e.g. a numpy Generator) in the reference's order (perspective_matrices)."""
+    u = [rng.random() for _ in range(8)]
+    return perspective_matrices([u], s, degrees, translate, scale, shear, perspective)[0]
+
+
+def make_items(n):
+    return np.zeros((n,), ITEM_DTYPE)
+
+
+def pack_sources(images_u8, masks=None):
+    """One uint8 arena for the sources' RGB planes (and id masks): (arena, srcs[SRC_DTYPE])."""
+    srcs = np.zeros((len(images_u8),), SRC_DTYPE)
+    parts, off = [], 0
+    for k, im in enumerate(images_u8):
+        im = np.ascontiguousarray(im, np.uint8)
+        assert im.ndim == 3 and im.shape[0] == 3, im.shape
+        srcs[k]["img_off"], srcs[k]["h"], srcs[k]["w"], srcs[k]["mask_off"] = off, im.shape[1], im.shape[2], -1
+        parts.append(im.reshape(-1)); off += im.size
+        if masks is not None and masks[k] is not None:
+            mk = np.ascontiguousarray(masks[k], np.uint8)
+            assert mk.ndim == 2, mk.shape
+            srcs[k]["mask_off"], srcs[k]["mh"], srcs[k]["mw"] = off, mk.shape[0], mk.shape[1]
+            parts.append(mk.reshape(-1)); off += mk.size
+    return np.ascontiguousarray(np.concatenate(parts)), srcs
+
+
+def pack_labels(labels):
+    """Per-source label dicts {cls [n], bboxes [n, 4] pixel xyxy in the source's frame, keypoints [n, K, 3] (optional)} -> (lab_off [n_src + 1],
+    cls, boxes, keypoints or None)."""
+    cnt = [int(np.asarray(l["cls"]).reshape(-1).shape[0]) for l in labels]
+    lab_off = np.concatenate([[0], np.cumsum(cnt)]).astype(np.int32)
+    cls = np.concatenate([np.asarray(l["cls"], np.float32).reshape(-1) for l in labels]) if labels else np.zeros((0,), np.float32)
+    boxes = np.concatenate([np.asarray(l["bboxes"], np.float32).reshape(-1, 4) for l in labels])
+    kp = None
+    if labels and labels[0].get("keypoints") is not None:
+        K = np.asarray(labels[0]["keypoints"]).shape[1]
+        kp = np.ascontiguousarray(np.concatenate([np.asarray(l["keypoints"], np.float32).reshape(-1, K, 3) for l in labels]))
+    return lab_off, np.ascontiguousarray(cls), np.ascontiguousarray(boxes), kp
+
+
+def augment_mosaic(engine, arena, srcs, items, imgsz, mask_ratio=4, perspective=False, with_masks=False):
+    """ys_augment_mosaic on HOST arrays: -> (images fp32 [B, 3, s, s], masks fp32 [B, s/r, s/r] or None)."""
+    arena = np.ascontiguousarray(arena, np.uint8)
+    srcs, items = np.ascontiguousarray(srcs, SRC_DTYPE), np.ascontiguousarray(items, ITEM_DTYPE)
+    B, s = items.shape[0], int(imgsz)
+    images = np.empty((B, 3, max(s, 0), max(s, 0)), np.float32)
+    masks = np.empty((B, s // mask_ratio, s // mask_ratio), np.float32) if with_masks else None
+    _lib.check(engine.lib, engine.lib.ys_augment_mosaic(engine.ctx, _ptr(arena), _ptr(srcs), srcs.shape[0], _ptr(items), B, 0, s, int(mask_ratio),
+                                                        int(bool(perspective)), _ptr(images), _ptr(masks)))
+    return images, masks
+
+
+def augment_labels(engine, srcs, lab_off, cls, boxes, keypoints, items, imgsz, perspective=False, flags=0, capacity=None, kpt_dim=3):
+    """ys_augment_labels on HOST arrays: -> dict(batch_idx, cls, bboxes, keypoints (or None), count), all `capacity` rows long."""
+    srcs, items = np.ascontiguousarray(srcs, SRC_DTYPE), np.ascontiguousarray(items, ITEM_DTYPE)
+    lab_off = np.ascontiguousarray(lab_off, np.int32)
+    cls, boxes = np.ascontiguousarray(cls, np.float32), np.ascontiguousarray(boxes, np.float32)
+    kp = np.ascontiguousarray(keypoints, np.float32) if keypoints is not None else None
+    K = kp.shape[1] if kp is not None else 0
+    cap = int(capacity if capacity is not None else max(1, int(lab_off[-1])))
+    n = max(cap, 0)
+    out = dict(batch_idx=np.empty((n,), np.float32), cls=np.empty((n,), np.float32), bboxes=np.empty((n, 4), np.float32),
+               keypoints=np.empty((n, K, 3), np.float32) if kp is not None else None)
+    cnt = C.c_int32(-1)
+    _lib.check(engine.lib, engine.lib.ys_augment_labels(engine.ctx, _ptr(srcs), _ptr(lab_off), _ptr(cls), _ptr(boxes), _ptr(kp), K, int(kpt_dim), _ptr(items),
+                                                        items.shape[0], 0, int(imgsz), int(bool(perspective)), int(flags), cap, _ptr(out["batch_idx"]),
+                                                        _ptr(out["cls"]), _ptr(out["bboxes"]), _ptr(out["keypoints"]), C.byref(cnt)))
+    out["count"] = cnt.value
+    return out
+
+
+def draw_items(rng, indices, s, count, hyp, fliplr=0.5, flipud=0.0):
+    """The item table of one batch: per primary index of `indices`, in the reference's per-image order, the three mixed indices as
+    randint(0, count - 1) (:155), yc, then xc, in [s/2, 3s/2) (:163-164), the eight uniforms of the matrix, FlipLR then FlipUD as `rand > p -> skip`
+    (drawn only when p > 0).  hyp: degrees / translate / scale / shear / perspective.  The matrices are built for the whole batch at once."""
+    items = make_items(len(indices))
+    u = np.empty((len(indices), 8), np.float64)
+    for b, idx in enumerate(indices):
+        mix = rng.integers(0, count - 1, size=3)
+        yc = int(rng.integers(s // 2, 2 * s - s // 2))
+        xc = int(rng.integers(s // 2, 2 * s - s // 2))
+        u[b] = rng.random(8)
+        flr = fliplr > 0 and not (rng.random() > fliplr)
+        fud = flipud > 0 and not (rng.random() > flipud)
+        items[b] = ((int(idx), int(mix[0]), int(mix[1]), int(mix[2])), xc, yc, 0.0, int(flr), int(fud))
+    items["M"] = perspective_matrices(u, s, **hyp).reshape(-1, 9)
+    return items
+
+
+class DeviceBatch:
+    """One collated training batch that lives in HBM: device pointers to images fp32 [B, 3, s, s], batch_idx / cls [capacity], bboxes [capacity, 4],
+    masks [B, s/r, s/r] and keypoints [capacity, K, 3] (None when absent) and the device int `count`.  Rows [count, capacity) carry batch_idx -1,
+    which the criteria skip: n_labels = capacity, no host read.  n_input = the labels of the batch's tiles BEFORE the filters (a host number)."""
+
+    def __init__(self, engine, batch, imgsz, capacity, images, batch_idx, cls, bboxes, count, masks=None, keypoints=None, kpt_num=0, mask_ratio=4,
+                 n_input=0, max_per_image=64):
+        self.engine, self.batch, self.imgsz, self.capacity = engine, batch, imgsz, capacity
+        self.images, self.batch_idx, self.cls, self.bboxes, self.count = images, batch_idx, cls, bboxes, count
+        self.masks, self.keypoints, self.kpt_num, self.mask_ratio, self.n_input = masks, keypoints, kpt_num, mask_ratio, n_input
+        self.max_per_image = max_per_image      # upper bound of one image's label count (the criterion's per-image workspace is reserved for it)
+
+    def to_host(self):
+        """The same batch as the numpy dict the host path takes (synchronises): the first `count` rows."""
+        e, s, cap = self.engine, self.imgsz, self.capacity
+        n = int(e.from_device(self.count, (1,), np.int32)[0])
+        if n > cap:
+            raise _lib.YsError(1, "augmenter kept %d labels, capacity is %d" % (n, cap))
+        out = dict(images=e.from_device(self.images, (self.batch, 3, s, s), np.float32),
+                   batch_idx=e.from_device(self.batch_idx, (cap,), np.float32)[:n], cls=e.from_device(self.cls, (cap,), np.float32)[:n],
+                   bboxes=e.from_device(self.bboxes, (cap, 4), np.float32)[:n])
+        if self.masks is not None:
+            out["masks"] = e.from_device(self.masks, (self.batch, s // self.mask_ratio, s // self.mask_ratio), np.float32)
+        if self.keypoints is not None:
+            out["keypoints"] = e.from_device(self.keypoints, (cap, self.kpt_num, 3), np.float32)[:n]
+        return out
+
+
+class MosaicAugmenter:
+    """Mosaic4 + RandomPerspective + FlipLR / FlipUD + Normalize + collate per batch on the device.  The dataset -- uint8 RGB planes [3, h, w], optional
+    id masks [mh, mw], per-image labels {cls, bboxes pixel xyxy, keypoints [n, K, 3]} -- is uploaded ONCE; a batch uploads its item table only.
+    Draws per output image, in the reference's order, from one numpy Generator: the three mixed indices as randint(0, Count - 1) (:155: the upper bound is
+    exclusive, so the LAST image is never mixed in -- kept); yc, then xc, in [s/2, 3s/2) (:163-164); the matrix (random_perspective_matrix); FlipLR then
+    FlipUD as `rand > p -> skip`, drawn only when p > 0 (YoloDataset.cs:76-85).  The output buffers are reused by the next batch."""
+
+    def __init__(self, engine, images_u8, labels, imgsz, masks=None, mask_ratio=4, degrees=0.0, translate=0.1, scale=0.5, shear=0.0, perspective=0.0,
+                 fliplr=0.5, flipud=0.0, seed=0, flags=0, max_batch=64):
+        assert len(images_u8) == len(labels) and len(images_u8) >= 2
+        self.engine, self.s, self.r, self.flags = engine, int(imgsz), int(mask_ratio), int(flags)
+        self.hyp = dict(degrees=degrees, translate=translate, scale=scale, shear=shear, perspective=perspective)
+        self.fliplr, self.flipud = float(fliplr), float(flipud)
+        self.rng = np.random.default_rng(seed)
+        arena, self.srcs = pack_sources(images_u8, masks)
+        self.lab_off, cls, boxes, kp = pack_labels(labels)
+        self.count = len(images_u8)
+        self.with_masks, self.K = masks is not None, (kp.shape[1] if kp is not None else 0)
+        e = engine
+        self._static = [e.to_device(arena), e.to_device(self.srcs), e.to_device(self.lab_off), e.to_device(cls if cls.size else np.zeros(1, np.float32)),
+                        e.to_device(boxes if boxes.size else np.zeros(4, np.float32))]
+        self.d_arena, self.d_srcs, self.d_lab_off, self.d_cls, self.d_boxes = self._static
+        self.d_kp = e.to_device(kp if kp.size else np.zeros(3, np.float32)) if kp is not None else None
+        per_src = np.diff(self.lab_off)
+        self.max_batch = int(max_batch)
+        self.max_per_image = max(1, int(np.sort(per_src)[::-1][:4].sum()))                  # four tiles per image
+        self.capacity = self.max_per_image * self.max_batch                                 # no batch can exceed it
+        s, cap, B = self.s, self.capacity, self.max_batch
+        self.d_items = e.malloc(B * ITEM_DTYPE.itemsize)
+        self.d_images = e.malloc(B * 3 * s * s * 4)
+        self.d_masks = e.malloc(B * (s // self.r) ** 2 * 4) if self.with_masks else None
+        self.d_bidx, self.d_ocls, self.d_obox, self.d_cnt = e.malloc(cap * 4), e.malloc(cap * 4), e.malloc(cap * 16), e.malloc(4)
+        self.d_okp = e.malloc(cap * self.K * 12) if self.K else None
+
+    def close(self):
+        e = self.engine
+        for p in self._static + [self.d_kp, self.d_items, self.d_images, self.d_masks, self.d_bidx, self.d_ocls, self.d_obox, self.d_cnt, self.d_okp]:
+            if p is not None:
+                e.free(p)
+        self._static = []
+        self.d_kp = self.d_items = self.d_images = self.d_masks = self.d_bidx = self.d_ocls = self.d_obox = self.d_cnt = self.d_okp = None
+
+    def draw(self, indices):
+        """The item table for the primary dataset indices `indices` (what the data loader's shuffler hands to GetTensor)."""
+        return draw_items(self.rng, indices, self.s, self.count, self.hyp, self.fliplr, self.flipud)
+
+    def run(self, items):
+        """Upload `items` and launch both kernels on the engine's stream (asynchronous) -> DeviceBatch."""
+        e, lib, B = self.engine, self.engine.lib, int(items.shape[0])
+        assert 0 < B <= self.max_batch
+        items = np.ascontiguousarray(items, ITEM_DTYPE)
+        if items["src"].min() < 0 or items["src"].max() >= self.count:      # ys_augment_labels has no source count to check device items against
+            raise ValueError("item source index outside [0, %d)" % self.count)
+        persp = int(self.hyp["perspective"] > 0)
+        _lib.check(lib, lib.ys_memcpy_h2d(e.ctx, self.d_items, _ptr(items), items.nbytes))
+        _lib.check(lib, lib.ys_augment_mosaic(e.ctx, self.d_arena, self.d_srcs, self.count, self.d_items, B, 1, self.s, self.r, persp, self.d_images, self.d_masks))
+        _lib.check(lib, lib.ys_augment_labels(e.ctx, self.d_srcs, self.d_lab_off, self.d_cls, self.d_boxes, self.d_kp, self.K, 3, self.d_items, B, 1, self.s, persp,
+                                              self.flags, self.capacity, self.d_bidx, self.d_ocls, self.d_obox, self.d_okp, self.d_cnt))
+        n_input = int(sum(int(self.lab_off[k + 1] - self.lab_off[k]) for k in items["src"].reshape(-1)))
+        return DeviceBatch(e, B, self.s, self.capacity, self.d_images, self.d_bidx, self.d_ocls, self.d_obox, self.d_cnt, masks=self.d_masks,
+                           keypoints=self.d_okp, kpt_num=self.K, mask_ratio=self.r, n_input=n_input, max_per_image=self.max_per_image)
+
+    def batch(self, indices):
+        return self.run(self.draw(indices))
+
+    def batches(self, batch_size, shuffle=True, drop_last=True):
+        """One epoch: the primary indices in (shuffled) order, `batch_size` at a time."""
+        order = self.rng.permutation(self.count) if shuffle else np.arange(self.count)
+        for i in range(0, self.count, batch_size):
+            idx = order[i:i + batch_size]
+            if len(idx) < batch_size and drop_last:
+                break
+            yield self.batch(idx)

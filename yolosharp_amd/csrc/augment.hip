@@ -1,0 +1,464 @@
+// augment.hip -- the training input on the device: Mosaic4 + RandomPerspective + FlipLR / FlipUD + Normalize + collate
+// of the reference's default training pipeline (ImageProcessType.Mosiac, Data/YoloDataset.cs:57-151) as three kernels.
+//
+//   aug_prep_kernel          one thread per output image: the four tile rectangles of Augment.Mosaic._mosaic4 (Data/Augment.cs:184-203,
+//                            mask rectangles :207-209) and the inverse of the forward matrix, in double (the reference inverts in fp32 with
+//                            torch.linalg.inv, :409 / :486; parity is judged against a float64 restatement; a deviation, see below).  The mask inverse is
+//                            S_inv * M_inv * S -- the inverse of M_mask = S_inv * M * S (:371-376) without a second inversion.
+//   aug_mosaic_warp_kernel   Mosaic4 + WarpAffine/PerspectiveWithGridSample (:395-538) + flips (:879, :936) + mul(1/255) (YoloDataset.cs:140)
+//                            in one pass: a gather from the four source images with a streaming fp32 NCHW write.  The 2s x 2s canvas never
+//                            exists: canvas pixel (Y, X) is 114 or a pixel of the tile whose quadrant (X >= xc, Y >= yc) it lies in.
+//                            aug_mask_warp_kernel is the same for the overlap-encoded instance-id masks ([B, s/r, s/r] fp32, what
+//                            ys_loss_segment reads): BILINEAR on the id bytes like the reference (:383-388), border 0.
+//   aug_labels_kernel        one workgroup per image: the label filter of _mosaic4 (:238-256), apply_bboxes (:546-568), clip_boxes + area > 0
+//                            (:681-692), apply_keypoints (:581-601), clip_keypoints (Utils/Ops.cs:166-183), the flips' label arithmetic
+//                            (:890-891, :905, :945-946, :955), box_convert(xyxy -> cxcywh), Normalize (Data/Struct.cs:99-121) and the collate
+//                            (Data/YoloDataLoader.cs:18-44) into compacted rows: a scan over the workgroup, then an exclusive scan over the B
+//                            counts.  No floating-point atomics: the output is a pure function of the input.
+//
+// Sampling restated exactly: src = M_inv (x, y, 1) / w; valid = 0 <= src <= in - 1 on both axes (else 114 / 0); the value is
+// grid_sample(bilinear, border, align_corners = false) at grid = src / (in - 1) * 2 - 1, i.e. at the position src * in / (in - 1) - 0.5 (NOT src),
+// clamp(0, 255), truncation to a byte.
+// DEVIATION in precision, on purpose: the inverse stays in double and the source position and the blend are evaluated in double PER PIXEL (an fp32
+// inverse and fp32 pixel arithmetic would be the cheaper kernel).  That is what keeps the result closer to a float64 restatement than the reference's own
+// fp32 is (see aug_blend_u8), and it has a price: measured at B = 64 / 640 px the kernel reaches 17 % of the HBM rate -- it is bound by its instruction
+// stream, about 5x above the HBM estimate of its bytes (DESIGN.md "Training input on the device").
+//
+// Scope (include/yolosharp_hip.h lists the same): kpt_dim = 3 only (apply_keypoints reads column 2); no OBB corner labels (xyxyxyxy2xywhr is host
+// code in the reference); no RandomHSV (TorchVision.NET ColorJitter, not in the reference tree); no no-mosaic branch.  Deviations: a label-free
+// sample is still warped (RandomPerspective.Apply returns the unwarped canvas, :666-669); where the reference's mask slice would run past the
+// source mask (it throws) the kernel reads 0.
+#include "ys_internal.h"
+#include "ys_kernels.h"
+#include <cmath>
+
+#define AUG_T 256
+
+// tile i of _mosaic4 (:184-203): canvas rectangle [x1a, x2a) x [y1a, y2a), source origin (x1b, y1b)
+__host__ __device__ inline void aug_tile_rect(int i, int xc, int yc, int h, int w, int s, int* x1a, int* y1a, int* x2a, int* y2a, int* x1b, int* y1b) {
+  const int s2 = 2 * s;
+  if (i == 0) {
+    *x1a = xc - w > 0 ? xc - w : 0; *y1a = yc - h > 0 ? yc - h : 0; *x2a = xc; *y2a = yc;
+    *x1b = w - (*x2a - *x1a); *y1b = h - (*y2a - *y1a);
+  } else if (i == 1) {
+    *x1a = xc; *y1a = yc - h > 0 ? yc - h : 0; *x2a = xc + w < s2 ? xc + w : s2; *y2a = yc;
+    *x1b = 0; *y1b = h - (*y2a - *y1a);
+  } else if (i == 2) {
+    *x1a = xc - w > 0 ? xc - w : 0; *y1a = yc; *x2a = xc; *y2a = yc + h < s2 ? yc + h : s2;
+    *x1b = w - (*x2a - *x1a); *y1b = 0;
+  } else {
+    *x1a = xc; *y1a = yc; *x2a = xc + w < s2 ? xc + w : s2; *y2a = yc + h < s2 ? yc + h : s2;
+    *x1b = 0; *y1b = 0;
+  }
+}
+
+// o = m^-1 by cofactors in double; false for a singular (or non-finite) matrix
+__host__ __device__ inline bool aug_invert3(const double* m, double* o) {
+  const double c00 = m[4] * m[8] - m[5] * m[7], c01 = m[5] * m[6] - m[3] * m[8], c02 = m[3] * m[7] - m[4] * m[6];
+  const double det = m[0] * c00 + m[1] * c01 + m[2] * c02;
+  // singular = the three terms of the expansion cancel (or vanish): |det| against the sum of their magnitudes, which carries the matrix's own scale --
+  // a translation of thousands of pixels does not turn a sound matrix into a "singular" one
+  const double t0 = m[0] * c00, t1 = m[1] * c01, t2 = m[2] * c02;
+  const double mag = (t0 < 0 ? -t0 : t0) + (t1 < 0 ? -t1 : t1) + (t2 < 0 ? -t2 : t2);
+  const double ad = det < 0 ? -det : det;
+  if (!(ad > 1e-12 * mag) || !(ad < 1e300)) return false;
+  const double r = 1.0 / det;
+  o[0] = c00 * r; o[1] = (m[2] * m[7] - m[1] * m[8]) * r; o[2] = (m[1] * m[5] - m[2] * m[4]) * r;
+  o[3] = c01 * r; o[4] = (m[0] * m[8] - m[2] * m[6]) * r; o[5] = (m[2] * m[3] - m[0] * m[5]) * r;
+  o[6] = c02 * r; o[7] = (m[1] * m[6] - m[0] * m[7]) * r; o[8] = (m[0] * m[4] - m[1] * m[3]) * r;
+  return true;
+}
+
+// the matrix the warp inverts: M itself (perspective form, :364) or its first two rows over (0, 0, 1) (affine form, :368, :479-486)
+__host__ __device__ inline void aug_warp_matrix(const float* M, int perspective, double* m) {
+  for (int i = 0; i < 9; i++) m[i] = (double)M[i];
+  if (!perspective) { m[6] = 0.0; m[7] = 0.0; m[8] = 1.0; }
+}
+
+// an item the kernels can run: sources in range, centre inside the canvas, invertible matrix
+__host__ __device__ inline int aug_item_ok(const ys_aug_item& it, const ys_aug_src* srcs, int n_src, int s, int perspective) {
+  for (int i = 0; i < 4; i++) {
+    if (it.src[i] < 0 || it.src[i] >= n_src) return 0;
+    const ys_aug_src& sr = srcs[it.src[i]];
+    if (sr.h < 1 || sr.w < 1 || sr.img_off < 0) return 0;
+  }
+  if (it.xc < 0 || it.xc > 2 * s || it.yc < 0 || it.yc > 2 * s) return 0;
+  double m[9], o[9];
+  aug_warp_matrix(it.M, perspective, m);
+  return aug_invert3(m, o) ? 1 : 0;
+}
+
+__global__ void __launch_bounds__(64)
+aug_prep_kernel(const ys_aug_src* __restrict__ srcs, int n_src, const ys_aug_item* __restrict__ items, int B, int s, int r, int perspective,
+                AugParams* __restrict__ params) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  const ys_aug_item it = items[b];
+  AugParams P;
+  P.valid = aug_item_ok(it, srcs, n_src, s, perspective);
+  P.xc = it.xc; P.yc = it.yc; P.flip_lr = it.flip_lr != 0; P.flip_ud = it.flip_ud != 0;
+  P.pad_ = 0;
+  for (int i = 0; i < 9; i++) { P.inv[i] = (i % 4 == 0) ? 1.0 : 0.0; P.minv[i] = P.inv[i]; }
+  for (int i = 0; i < 4; i++) {
+    AugTile& t = P.t[i];
+    t.img_off = 0; t.mask_off = -1; t.h = 0; t.w = 0; t.mh = 0; t.mw = 0; t.padw = 0; t.padh = 0;     // a refused item: every canvas pixel is 114, nothing is read
+    t.mx1a = t.my1a = t.mx2a = t.my2a = t.mx1b = t.my1b = 0;
+  }
+  if (P.valid) {
+    double m[9];
+    aug_warp_matrix(it.M, perspective, m);
+    aug_invert3(m, P.inv);
+    const double rr = (double)r;
+    for (int i = 0; i < 9; i++) P.minv[i] = P.inv[i];
+    P.minv[2] /= rr; P.minv[5] /= rr; P.minv[6] *= rr; P.minv[7] *= rr;                                // S_inv * M_inv * S, S = diag(r, r, 1)
+    for (int i = 0; i < 4; i++) {
+      const ys_aug_src sr = srcs[it.src[i]];
+      AugTile& t = P.t[i];
+      int x1a, y1a, x2a, y2a, x1b, y1b;
+      aug_tile_rect(i, it.xc, it.yc, sr.h, sr.w, s, &x1a, &y1a, &x2a, &y2a, &x1b, &y1b);
+      t.img_off = sr.img_off; t.mask_off = sr.mask_off; t.h = sr.h; t.w = sr.w; t.mh = sr.mh; t.mw = sr.mw;
+      t.padw = x1a - x1b; t.padh = y1a - y1b;
+      t.mx1a = x1a / r; t.my1a = y1a / r; t.mx2a = x2a / r; t.my2a = y2a / r; t.mx1b = x1b / r; t.my1b = y1b / r;
+    }
+  }
+  params[b] = P;
+}
+
+// source position of output pixel (x, y): inv * (x, y, 1), divided by w in the perspective form (in the affine form w is exactly 1)
+__device__ __forceinline__ void aug_src_pos(const double* inv, int perspective, int x, int y, double* sx, double* sy) {
+  const double dx = (double)x, dy = (double)y;
+  double X = fma(inv[0], dx, fma(inv[1], dy, inv[2]));
+  double Y = fma(inv[3], dx, fma(inv[4], dy, inv[5]));
+  if (perspective) {
+    const double W = fma(inv[6], dx, fma(inv[7], dy, inv[8]));
+    X /= W; Y /= W;
+  }
+  *sx = X; *sy = Y;
+}
+
+// grid_sample's bilinear set-up on an in x in input at source position (X, Y) (valid, i.e. inside [0, in - 1]): the four corner indices
+// (clamped: a corner past the edge has weight 0) and the two fractions, in double
+__device__ __forceinline__ void aug_bilinear(double X, double Y, int in, int* x0, int* y0, int* x1, int* y1, double* wx, double* wy) {
+  const double k = (double)in / (double)(in - 1);
+  double ix = X * k - 0.5, iy = Y * k - 0.5;
+  const double hi = (double)(in - 1);
+  ix = ix < 0.0 ? 0.0 : (ix > hi ? hi : ix);
+  iy = iy < 0.0 ? 0.0 : (iy > hi ? hi : iy);
+  const double fx = floor(ix), fy = floor(iy);
+  *wx = ix - fx; *wy = iy - fy;
+  *x0 = (int)fx; *y0 = (int)fy;
+  *x1 = *x0 + 1 < in ? *x0 + 1 : in - 1;
+  *y1 = *y0 + 1 < in ? *y0 + 1 : in - 1;
+}
+
+// the blend, clamp(0, 255) and the truncation to uint8 (:454, :529).  ATen sums nw * (1-wy)(1-wx) + ne * (1-wy) wx + sw * wy (1-wx) + se * wy wx; four
+// rounded weights need not sum to 1, so that form returns 113.99999 -> 113 for some pixels of a constant 114 region, and WHICH pixels depends on the
+// last bits of the weights (the float32 and float64 restatements disagree on 2-10 % of the bytes of an image with large fill regions for this reason
+// alone).  The nested interpolation in double is exact on constant regions and within 1e-13 levels of the real value elsewhere: the kernel adds no
+// truncation flips of its own to those of whatever it is compared with.
+__device__ __forceinline__ float aug_blend_u8(float a, float b, float c, float d, double wx, double wy) {
+  const double top = (double)a + wx * ((double)b - (double)a), bot = (double)c + wx * ((double)d - (double)c);
+  double v = top + wy * (bot - top);
+  v = v < 0.0 ? 0.0 : (v > 255.0 ? 255.0 : v);
+  return (float)(int)v;
+}
+
+// the four tiles' geometry as wave-uniform scalars; a canvas pixel picks its tile with two comparisons and three selects per field
+// (passed as SCALARS: selects between the fields of a struct in memory are turned into an indexed load by hipcc, which then parks the struct in LDS)
+#define AUG_T4_PARAMS int w0, int w1, int w2, int w3, int h0, int h1, int h2, int h3, long long off0, long long off1, long long off2, long long off3, int xc, int yc
+#define AUG_T4_ARGS w0, w1, w2, w3, h0, h1, h2, h3, off0, off1, off2, off3, xc, yc
+
+__device__ __forceinline__ void aug_canvas_fetch(const unsigned char* __restrict__ arena, AUG_T4_PARAMS, int X, int Y, float* v) {
+  const bool right = X >= xc, bottom = Y >= yc;
+  const int w = right ? (bottom ? w3 : w1) : (bottom ? w2 : w0);
+  const int h = right ? (bottom ? h3 : h1) : (bottom ? h2 : h0);
+  const long long off = right ? (bottom ? off3 : off1) : (bottom ? off2 : off0);
+  // tile 0 / 2: x1a = max(xc - w, 0), x1b = w - (xc - x1a) -> source column X - xc + w; tile 1 / 3: X - xc.  Inside the rectangle <=> 0 <= column < w
+  const int px = X - xc + (right ? 0 : w), py = Y - yc + (bottom ? 0 : h);
+  if ((unsigned)px < (unsigned)w && (unsigned)py < (unsigned)h) {
+    const long long plane = (long long)h * w;
+    const unsigned char* p = arena + off + (long long)py * w + px;
+    v[0] = (float)p[0]; v[1] = (float)p[plane]; v[2] = (float)p[2 * plane];
+  } else {
+    v[0] = 114.0f; v[1] = 114.0f; v[2] = 114.0f;
+  }
+}
+
+// one output pixel (logical coordinates after the flips): three channels as fp32 in [0, 1]
+struct AugPx { float c0, c1, c2; };
+__device__ __forceinline__ AugPx aug_pixel(const unsigned char* __restrict__ arena, AUG_T4_PARAMS, const double* __restrict__ inv, int perspective, int in,
+                                           bool live, int lx, int ly) {
+  float b0 = 114.0f, b1 = 114.0f, b2 = 114.0f;
+  double X, Y;
+  aug_src_pos(inv, perspective, lx, ly, &X, &Y);
+  const double hi = (double)(in - 1);
+  if (live && X >= 0.0 && X <= hi && Y >= 0.0 && Y <= hi) {
+    int xa, ya, xb, yb; double wx, wy;
+    aug_bilinear(X, Y, in, &xa, &ya, &xb, &yb, &wx, &wy);
+    float nw[3], ne[3], sw[3], se[3];
+    aug_canvas_fetch(arena, AUG_T4_ARGS, xa, ya, nw);
+    aug_canvas_fetch(arena, AUG_T4_ARGS, xb, ya, ne);
+    aug_canvas_fetch(arena, AUG_T4_ARGS, xa, yb, sw);
+    aug_canvas_fetch(arena, AUG_T4_ARGS, xb, yb, se);
+    b0 = aug_blend_u8(nw[0], ne[0], sw[0], se[0], wx, wy);
+    b1 = aug_blend_u8(nw[1], ne[1], sw[1], se[1], wx, wy);
+    b2 = aug_blend_u8(nw[2], ne[2], sw[2], se[2], wx, wy);
+  }
+  const float q = 1 / 255.0f;                             // mul(1 / 255.0f), YoloDataset.cs:140: a multiply, bit-exact per byte
+  AugPx r; r.c0 = b0 * q; r.c1 = b1 * q; r.c2 = b2 * q;
+  return r;
+}
+
+// one thread: 4 consecutive x of one output row, three channels -> three 16-byte stores (vec: s % 4 == 0, rows 16-byte aligned)
+__global__ void __launch_bounds__(AUG_T)
+aug_mosaic_warp_kernel(const unsigned char* __restrict__ arena, const AugParams* __restrict__ params, int s, int perspective, int vec,
+                       float* __restrict__ images) {
+  const AugParams& P = params[blockIdx.z];
+  const int qpr = (s + 3) >> 2;
+  const unsigned i = blockIdx.x * AUG_T + threadIdx.x;
+  if (i >= (unsigned)qpr * (unsigned)s) return;
+  const int y = (int)(i / (unsigned)qpr), x0 = (int)(i - (unsigned)y * (unsigned)qpr) * 4;
+  const int w0 = P.t[0].w, w1 = P.t[1].w, w2 = P.t[2].w, w3 = P.t[3].w, h0 = P.t[0].h, h1 = P.t[1].h, h2 = P.t[2].h, h3 = P.t[3].h;
+  const long long off0 = P.t[0].img_off, off1 = P.t[1].img_off, off2 = P.t[2].img_off, off3 = P.t[3].img_off;
+  const int xc = P.xc, yc = P.yc;
+  const double* __restrict__ inv = P.inv;                 // wave-uniform: scalar loads
+  const int in = 2 * s;
+  // the flips are folded into the output coordinate: out[y][x] = warped[ly][lx]
+  const int ly = P.flip_ud ? s - 1 - y : y;
+  const int lx0 = P.flip_lr ? s - 1 - x0 : x0, dx = P.flip_lr ? -1 : 1;
+  const AugPx p0 = aug_pixel(arena, AUG_T4_ARGS, inv, perspective, in, x0 < s, lx0, ly);
+  const AugPx p1 = aug_pixel(arena, AUG_T4_ARGS, inv, perspective, in, x0 + 1 < s, lx0 + dx, ly);
+  const AugPx p2 = aug_pixel(arena, AUG_T4_ARGS, inv, perspective, in, x0 + 2 < s, lx0 + 2 * dx, ly);
+  const AugPx p3 = aug_pixel(arena, AUG_T4_ARGS, inv, perspective, in, x0 + 3 < s, lx0 + 3 * dx, ly);
+  const long long plane = (long long)s * s;
+  float* dst = images + (long long)blockIdx.z * 3 * plane + (long long)y * s + x0;
+  if (vec) {
+    ys_st16(dst, make_uint4(ys_f2u(p0.c0), ys_f2u(p1.c0), ys_f2u(p2.c0), ys_f2u(p3.c0)));
+    ys_st16(dst + plane, make_uint4(ys_f2u(p0.c1), ys_f2u(p1.c1), ys_f2u(p2.c1), ys_f2u(p3.c1)));
+    ys_st16(dst + 2 * plane, make_uint4(ys_f2u(p0.c2), ys_f2u(p1.c2), ys_f2u(p2.c2), ys_f2u(p3.c2)));
+  } else {
+    if (x0 < s) { dst[0] = p0.c0; dst[plane] = p0.c1; dst[2 * plane] = p0.c2; }
+    if (x0 + 1 < s) { dst[1] = p1.c0; dst[plane + 1] = p1.c1; dst[2 * plane + 1] = p1.c2; }
+    if (x0 + 2 < s) { dst[2] = p2.c0; dst[plane + 2] = p2.c1; dst[2 * plane + 2] = p2.c2; }
+    if (x0 + 3 < s) { dst[3] = p3.c0; dst[plane + 3] = p3.c1; dst[2 * plane + 3] = p3.c2; }
+  }
+}
+
+// mask canvas pixel (Y, X) of the (2s / r)^2 id canvas: 0, or the byte of the tile whose rectangle (bounds / r, :207-209) holds it
+__device__ inline float aug_mask_fetch(const unsigned char* __restrict__ arena, const AugParams& P, int r, int X, int Y) {
+  const int q = (Y >= P.yc / r ? 2 : 0) + (X >= P.xc / r ? 1 : 0);
+  const AugTile& t = P.t[q];
+  if (t.mask_off < 0 || X < t.mx1a || X >= t.mx2a || Y < t.my1a || Y >= t.my2a) return 0.0f;
+  const int px = X - t.mx1a + t.mx1b, py = Y - t.my1a + t.my1b;
+  if (px >= t.mw || py >= t.mh) return 0.0f;              // past the source mask: the reference's slice assignment throws here
+  return (float)arena[t.mask_off + (long long)py * t.mw + px];
+}
+
+__global__ void __launch_bounds__(AUG_T)
+aug_mask_warp_kernel(const unsigned char* __restrict__ arena, const AugParams* __restrict__ params, int s, int r, int perspective,
+                     float* __restrict__ masks) {
+  const AugParams& P = params[blockIdx.z];
+  const int ms = s / r, in = 2 * s / r;
+  const unsigned i = blockIdx.x * AUG_T + threadIdx.x;
+  if (i >= (unsigned)ms * (unsigned)ms) return;
+  const int y = (int)(i / (unsigned)ms), x = (int)(i - (unsigned)y * (unsigned)ms);
+  const int lx = P.flip_lr ? ms - 1 - x : x, ly = P.flip_ud ? ms - 1 - y : y;
+  const double* __restrict__ inv = P.minv;
+  double X, Y;
+  aug_src_pos(inv, perspective, lx, ly, &X, &Y);
+  const double hi = (double)(in - 1);
+  float v = 0.0f;
+  if (X >= 0.0 && X <= hi && Y >= 0.0 && Y <= hi) {
+    int xa, ya, xb, yb; double wx, wy;
+    aug_bilinear(X, Y, in, &xa, &ya, &xb, &yb, &wx, &wy);
+    v = aug_blend_u8(aug_mask_fetch(arena, P, r, xa, ya), aug_mask_fetch(arena, P, r, xb, ya), aug_mask_fetch(arena, P, r, xa, yb),
+                     aug_mask_fetch(arena, P, r, xb, yb), wx, wy);
+  }
+  masks[(long long)blockIdx.z * ms * ms + i] = v;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- labels
+struct AugLabelOut { float cls, box[4]; };
+
+// label l of tile (padw, padh) through the two filters and the matrix; returns the keep decision, fills the cxcywh / s row
+__device__ inline bool aug_label_box(const float* __restrict__ boxes, int l, float padw, float padh, const float* M, int s, int perspective, int flip_lr,
+                                     int flip_ud, int sort_flipped, float* out) {
+  const float S2 = (float)(2 * s), S = (float)s;
+  float x1 = boxes[4 * l + 0] + padw, y1 = boxes[4 * l + 1] + padh, x2 = boxes[4 * l + 2] + padw, y2 = boxes[4 * l + 3] + padh;
+  const float org_area = (x2 - x1) * (y2 - y1);
+  x1 = fminf(fmaxf(x1, 0.0f), S2); y1 = fminf(fmaxf(y1, 0.0f), S2); x2 = fminf(fmaxf(x2, 0.0f), S2); y2 = fminf(fmaxf(y2, 0.0f), S2);
+  const float area = (x2 - x1) * (y2 - y1);
+  bool keep = area > 0.0f && area > 0.7f * org_area;                              // :245
+  // apply_bboxes (:557-566): corners x1y1, x2y2, x1y2, x2y1 through M, divide only when perspective > 0, min / max
+  const float cx[4] = {x1, x2, x1, x2}, cy[4] = {y1, y2, y2, y1};
+  float xmin = 0.f, xmax = 0.f, ymin = 0.f, ymax = 0.f;
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    float px = (cx[k] * M[0] + cy[k] * M[1]) + M[2], py = (cx[k] * M[3] + cy[k] * M[4]) + M[5];
+    if (perspective) { const float pw = (cx[k] * M[6] + cy[k] * M[7]) + M[8]; px /= pw; py /= pw; }
+    xmin = k == 0 ? px : fminf(xmin, px); xmax = k == 0 ? px : fmaxf(xmax, px);
+    ymin = k == 0 ? py : fminf(ymin, py); ymax = k == 0 ? py : fmaxf(ymax, py);
+  }
+  xmin = fminf(fmaxf(xmin, 0.0f), S); ymin = fminf(fmaxf(ymin, 0.0f), S); xmax = fminf(fmaxf(xmax, 0.0f), S); ymax = fminf(fmaxf(ymax, 0.0f), S);
+  keep = keep && (xmax - xmin) * (ymax - ymin) > 0.0f;                            // :683-684
+  // FlipLR / FlipUD as written (:890-891, :945-946): columns 0 and 2 (1 and 3) become s - x, NOT swapped -> a flipped box has x1 > x2
+  if (flip_lr) { xmin = S - xmin; xmax = S - xmax; }
+  if (flip_ud) { ymin = S - ymin; ymax = S - ymax; }
+  if (sort_flipped) {
+    const float a = fminf(xmin, xmax), b = fmaxf(xmin, xmax), c = fminf(ymin, ymax), d = fmaxf(ymin, ymax);
+    xmin = a; xmax = b; ymin = c; ymax = d;
+  }
+  const float inv = 1.0f / S;                                                     // Normalize: mul by 1f / w (Struct.cs:107-110)
+  out[0] = ((xmin + xmax) / 2.0f) * inv; out[1] = ((ymin + ymax) / 2.0f) * inv; out[2] = (xmax - xmin) * inv; out[3] = (ymax - ymin) * inv;
+  return keep;
+}
+
+// keypoints [K][3] of label l: + pad, apply_keypoints (always divides; visibility 0 outside [0, s]), clip_keypoints, flips, / s
+__device__ inline void aug_label_kpts(const float* __restrict__ kin, int K, float padw, float padh, const float* M, int s, int flip_lr, int flip_ud,
+                                      float* __restrict__ kout) {
+  const float S = (float)s, inv = 1.0f / S;
+  for (int k = 0; k < K; k++) {
+    const float x = kin[3 * k] + padw, y = kin[3 * k + 1] + padh;
+    float vis = kin[3 * k + 2];
+    const float pw = (x * M[6] + y * M[7]) + M[8];
+    float px = ((x * M[0] + y * M[1]) + M[2]) / pw, py = ((x * M[3] + y * M[4]) + M[5]) / pw;
+    if (px < 0.0f || py < 0.0f || px > S || py > S) vis = 0.0f;                   // :597-598 and Ops.cs:173-178: the same test twice
+    px = fminf(fmaxf(px, 0.0f), S); py = fminf(fmaxf(py, 0.0f), S);
+    if (flip_lr) px = S - px;
+    if (flip_ud) py = S - py;
+    kout[3 * k] = px * inv; kout[3 * k + 1] = py * inv; kout[3 * k + 2] = vis;
+  }
+}
+
+// offs[b] = counts[0] + ... + counts[b - 1], offs[B] = the total: one workgroup, chunks of AUG_T with a carry (Hillis-Steele in LDS, fixed order)
+__global__ void __launch_bounds__(AUG_T)
+aug_count_scan_kernel(const int* __restrict__ counts, int B, int* __restrict__ offs) {
+  __shared__ int s_scan[AUG_T];
+  const int tid = threadIdx.x;
+  int carry = 0;
+  for (int k0 = 0; k0 < B; k0 += AUG_T) {
+    const int k = k0 + tid;
+    const int c = k < B ? counts[k] : 0;
+    s_scan[tid] = c;
+    __syncthreads();
+    for (int d = 1; d < AUG_T; d <<= 1) {
+      const int v = tid >= d ? s_scan[tid - d] : 0;
+      __syncthreads();
+      s_scan[tid] += v;
+      __syncthreads();
+    }
+    if (k < B) offs[k] = carry + s_scan[tid] - c;
+    carry += s_scan[AUG_T - 1];
+    __syncthreads();
+  }
+  if (tid == 0) offs[B] = carry;
+}
+
+// pass 0: counts[b] = kept labels of image b.  pass 1: rows [base(b), base(b) + counts[b]) with base = the exclusive scan of counts (counts[B + b], written by aug_count_scan_kernel between the passes), the tail
+// [total, capacity) = (batch_idx -1, zeros), *out_count = total (a total above capacity is reported as it is; rows past capacity are not written).
+__global__ void __launch_bounds__(AUG_T)
+aug_labels_kernel(const ys_aug_src* __restrict__ srcs, int n_src, const int* __restrict__ lab_off, const float* __restrict__ cls,
+                  const float* __restrict__ boxes, const float* __restrict__ kpts, int K, const ys_aug_item* __restrict__ items, int B, int s,
+                  int perspective, int flags, int capacity, int pass, int* __restrict__ counts, float* __restrict__ o_bidx, float* __restrict__ o_cls,
+                  float* __restrict__ o_box, float* __restrict__ o_kpt, int* __restrict__ o_count) {
+  __shared__ int s_scan[AUG_T];
+  __shared__ int s_n[4], s_first[4], s_padw[4], s_padh[4];
+  __shared__ int s_base, s_total;
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const ys_aug_item it = items[b];
+  if (tid < 4) {
+    int n = 0, first = 0, padw = 0, padh = 0;
+    if (aug_item_ok(it, srcs, n_src, s, perspective)) {
+      const int sr = it.src[tid];
+      first = lab_off[sr]; n = lab_off[sr + 1] - first;
+      int x1a, y1a, x2a, y2a, x1b, y1b;
+      aug_tile_rect(tid, it.xc, it.yc, srcs[sr].h, srcs[sr].w, s, &x1a, &y1a, &x2a, &y2a, &x1b, &y1b);
+      padw = x1a - x1b; padh = y1a - y1b;
+    }
+    s_n[tid] = n > 0 ? n : 0; s_first[tid] = first; s_padw[tid] = padw; s_padh[tid] = padh;
+  }
+  if (tid == 0 && pass == 1) { s_base = counts[B + b]; s_total = counts[2 * B]; }      // aug_count_scan_kernel's offsets
+  __syncthreads();
+  const int c0 = s_n[0], c1 = c0 + s_n[1], c2 = c1 + s_n[2], n_img = c2 + s_n[3];
+  float M[9];
+#pragma unroll
+  for (int k = 0; k < 9; k++) M[k] = it.M[k];
+  int done = 0;                                                                    // kept labels of the chunks before this one
+  for (int j0 = 0; j0 < n_img; j0 += AUG_T) {
+    const int j = j0 + tid;
+    bool keep = false;
+    int l = 0, t = 0;
+    float row[4] = {0.f, 0.f, 0.f, 0.f};
+    if (j < n_img) {
+      t = j < c0 ? 0 : (j < c1 ? 1 : (j < c2 ? 2 : 3));
+      l = s_first[t] + j - (t == 0 ? 0 : (t == 1 ? c0 : (t == 2 ? c1 : c2)));
+      keep = aug_label_box(boxes, l, (float)s_padw[t], (float)s_padh[t], M, s, perspective, it.flip_lr != 0, it.flip_ud != 0,
+                           (flags & YS_AUG_SORT_FLIPPED) != 0, row);
+    }
+    // inclusive scan of the keep flags over the workgroup (Hillis-Steele in LDS: a fixed order, 8 steps)
+    s_scan[tid] = keep ? 1 : 0;
+    __syncthreads();
+    for (int d = 1; d < AUG_T; d <<= 1) {
+      const int v = tid >= d ? s_scan[tid - d] : 0;
+      __syncthreads();
+      s_scan[tid] += v;
+      __syncthreads();
+    }
+    const int rank = done + s_scan[tid] - 1;
+    const int chunk = s_scan[AUG_T - 1];
+    if (pass == 1 && keep) {
+      const long long rowi = (long long)s_base + rank;
+      if (rowi < capacity) {
+        o_bidx[rowi] = (float)b; o_cls[rowi] = cls[l];
+        o_box[4 * rowi] = row[0]; o_box[4 * rowi + 1] = row[1]; o_box[4 * rowi + 2] = row[2]; o_box[4 * rowi + 3] = row[3];
+        if (o_kpt) aug_label_kpts(kpts + (long long)l * K * 3, K, (float)s_padw[t], (float)s_padh[t], M, s, it.flip_lr != 0, it.flip_ud != 0,
+                                  o_kpt + rowi * K * 3);
+      }
+    }
+    done += chunk;
+    __syncthreads();
+  }
+  if (pass == 0) {
+    if (tid == 0) counts[b] = done;
+    return;
+  }
+  if (b == 0 && tid == 0) *o_count = s_total;
+  for (long long rowi = (long long)s_total + (long long)b * AUG_T + tid; rowi < capacity; rowi += (long long)B * AUG_T) {
+    o_bidx[rowi] = -1.0f; o_cls[rowi] = 0.0f;
+    o_box[4 * rowi] = 0.f; o_box[4 * rowi + 1] = 0.f; o_box[4 * rowi + 2] = 0.f; o_box[4 * rowi + 3] = 0.f;
+    if (o_kpt) for (int k = 0; k < K * 3; k++) o_kpt[rowi * K * 3 + k] = 0.f;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------- launchers
+size_t ys_aug_ws_bytes(int B) { return (size_t)B * sizeof(AugParams) + ((size_t)2 * B + 1) * sizeof(int) + 64; }   // params | counts [B] | offsets [B + 1]
+
+int ys_aug_item_ok_host(const ys_aug_item* it, const ys_aug_src* srcs, int n_src, int s, int perspective) {
+  return aug_item_ok(*it, srcs, n_src, s, perspective);
+}
+
+int ys_aug_mosaic_launch(hipStream_t st, const unsigned char* arena, const ys_aug_src* srcs, int n_src, const ys_aug_item* items, int B, int s,
+                         int r, int perspective, void* ws, float* images, float* masks) {
+  AugParams* params = (AugParams*)ws;
+  YS_LAUNCH(aug_prep_kernel, ys_cdiv(B, 64), 64, st, srcs, n_src, items, B, s, r, perspective, params);
+  const long quads = (long)((s + 3) / 4) * s;
+  YS_LAUNCH(aug_mosaic_warp_kernel, dim3(ys_cdiv(quads, AUG_T), 1, B), AUG_T, st, arena, (const AugParams*)params, s, perspective,
+            (s % 4 == 0 && ((size_t)images & 15) == 0) ? 1 : 0, images);
+  if (masks) {
+    const long n = (long)(s / r) * (s / r);
+    YS_LAUNCH(aug_mask_warp_kernel, dim3(ys_cdiv(n, AUG_T), 1, B), AUG_T, st, arena, (const AugParams*)params, s, r, perspective, masks);
+  }
+  return YS_OK;
+}
+
+int ys_aug_labels_launch(hipStream_t st, const ys_aug_src* srcs, int n_src, const int* lab_off, const float* cls, const float* boxes,
+                         const float* kpts, int K, const ys_aug_item* items, int B, int s, int perspective, int flags, int capacity, void* ws,
+                         float* o_bidx, float* o_cls, float* o_box, float* o_kpt, int* o_count) {
+  int* counts = (int*)((char*)ws + (size_t)B * sizeof(AugParams));
+  for (int pass = 0; pass < 2; pass++) {
+    if (pass == 1) YS_LAUNCH(aug_count_scan_kernel, 1, AUG_T, st, (const int*)counts, B, counts + B);
+    YS_LAUNCH(aug_labels_kernel, B, AUG_T, st, srcs, n_src, lab_off, cls, boxes, kpts, K, items, B, s, perspective, flags, capacity, pass, counts,
+              o_bidx, o_cls, o_box, o_kpt, o_count);
+  }
+  return YS_OK;
+}

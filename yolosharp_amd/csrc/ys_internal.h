@@ -59,6 +59,9 @@ struct ys_ctx {
   // ys_e2e_topk workspace (grown on demand)
   void* e2e_ws = nullptr;
   size_t e2e_ws_bytes = 0;
+  // ys_augment_* workspace (per-image parameters + label counts; grown on demand)
+  void* aug_ws = nullptr;
+  size_t aug_ws_bytes = 0;
   // scratch for per-operator entry points
   std::map<std::string, float> last_ms;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;

@@ -388,3 +388,25 @@ int ys_e2e_select_launch(hipStream_t st, const float* rows, int B, int k, float 
 int ys_e2e_bn_second_update_launch(hipStream_t st, float* state, const float* snap, const unsigned char* is_count, long n, float momentum);
 int ys_process_mask_launch(hipStream_t st, const float* protos, const float* masks_in, const float* boxes, int n, int nm, int mh,
                            int mw, int ih, int iw, int upsample, int trunc_crop, unsigned char* out);
+// ---- augment.hip: Mosaic4 + RandomPerspective + flips + Normalize + collate on the device (Data/Augment.cs:158-274, 315-695, 860-966)
+struct ys_aug_src;
+struct ys_aug_item;
+// per output image, written by aug_prep_kernel: the inverse matrices (image, mask) in double and the four tiles' geometry
+struct AugTile {
+  long long img_off, mask_off;          // byte offsets into the arena (mask_off < 0: no mask)
+  int h, w, mh, mw;                     // source image / source mask size (0 x 0 for a refused item: the canvas is all 114)
+  int padw, padh;                       // x1a - x1b, y1a - y1b (Augment.cs:211-212)
+  int mx1a, my1a, mx2a, my2a, mx1b, my1b;   // the rectangle bounds / mask_ratio (:207-209)
+};
+struct AugParams {
+  double inv[9], minv[9];
+  AugTile t[4];
+  int xc, yc, flip_lr, flip_ud, valid, pad_;
+};
+size_t ys_aug_ws_bytes(int B);
+int ys_aug_item_ok_host(const ys_aug_item* it, const ys_aug_src* srcs, int n_src, int s, int perspective);
+int ys_aug_mosaic_launch(hipStream_t st, const unsigned char* arena, const ys_aug_src* srcs, int n_src, const ys_aug_item* items, int B, int s,
+                         int r, int perspective, void* ws, float* images, float* masks);
+int ys_aug_labels_launch(hipStream_t st, const ys_aug_src* srcs, int n_src, const int* lab_off, const float* cls, const float* boxes,
+                         const float* kpts, int K, const ys_aug_item* items, int B, int s, int perspective, int flags, int capacity, void* ws,
+                         float* o_bidx, float* o_cls, float* o_box, float* o_kpt, int* o_count);

@@ -246,6 +246,16 @@ class Engine:
                                                    _ptr(out), C.byref(pl), C.byref(pu)))
         return out, pl.value, pu.value
 
+    # ---- Mosaic4 + RandomPerspective + flips + Normalize + collate (Data/Augment.cs:158-274, 315-695, 860-966) on host arrays; the
+    #      device-resident form is augment.MosaicAugmenter
+    def augment_mosaic(self, arena, srcs, items, imgsz, mask_ratio=4, perspective=False, with_masks=False):
+        from . import augment
+        return augment.augment_mosaic(self, arena, srcs, items, imgsz, mask_ratio, perspective, with_masks)
+
+    def augment_labels(self, srcs, lab_off, cls, boxes, keypoints, items, imgsz, perspective=False, flags=0, capacity=None):
+        from . import augment
+        return augment.augment_labels(self, srcs, lab_off, cls, boxes, keypoints, items, imgsz, perspective, flags, capacity)
+
     # ---- Ops.process_mask (Ops.cs:462-489)
     def process_mask(self, protos, masks_in, bboxes, shape, upsample=False, cpu_crop_branch=False):
         """protos [nm,mh,mw], masks_in [n,nm], bboxes [n,4] xyxy (image pixels), shape=(ih,iw) -> bool [n,oh,ow]."""

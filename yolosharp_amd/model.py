@@ -546,6 +546,26 @@ class AMPWrapper:
         self.Step()
         return loss, items
 
+    def TrainStepDevice(self, batch, loss_func: v8DetectionLoss):
+        """TrainStep on an augment.DeviceBatch: images and labels are already in HBM, nothing is copied to the device.  The criterion reads all
+        `capacity` rows (those behind the batch's count carry batch_idx -1 and are skipped)."""
+        m = self.model
+        assert batch.imgsz == m.height == m.width, (batch.imgsz, m.height, m.width)
+        m.train()
+        m.reserve_labels(batch.max_per_image)
+        m.forward_device(batch.images, batch.batch)
+        args = [batch.batch_idx, batch.cls, batch.bboxes, batch.capacity]
+        if m.TASK == 1:
+            args.append(batch.masks)
+        elif m.TASK == 3:
+            args.append(batch.keypoints)
+        elif m.TASK != 0:
+            raise ValueError("TrainStepDevice: the device augmenter produces Detect, Segment and Pose batches")
+        loss_func.forward_device(*args)
+        loss, items = loss_func.read()
+        self.Step()
+        return loss, items
+
     def Step(self):
         self.model.backward()
         self.model.adamw_step(self.lrs, self.betas[0], self.betas[1], self.eps, self.wd)

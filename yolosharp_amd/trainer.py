@@ -88,13 +88,21 @@ class Trainer:
 
     def train_epoch(self, batches, epoch):
         """TrainEpoch (:291-356): returns the SUM of the per-step loss items like the reference (zeros when no step ran).  The
-        warm-up index i only advances on batches that trained: the reference's `continue` on an empty batch skips its i++."""
+        warm-up index i only advances on batches that trained: the reference's `continue` on an empty batch skips its i++.
+        A batch is a numpy dict or an augment.DeviceBatch (images and labels already in HBM).  A device batch's label count is a device number the
+        loop does not read: it is skipped only when its INPUT label count (the labels of its tiles before the filters) is 0."""
+        from .augment import DeviceBatch
         items_sum, i = None, 0
         for data in batches:
             self.amp.lrs = self.sched.begin_iteration(epoch, i)
-            if np.asarray(data["batch_idx"]).size < 1:                            # :322-325
+            if isinstance(data, DeviceBatch):
+                if data.n_input < 1:
+                    continue
+                _, items = self.amp.TrainStepDevice(data, self.crit)
+            elif np.asarray(data["batch_idx"]).size < 1:                          # :322-325
                 continue
-            _, items = self.amp.TrainStep(np.ascontiguousarray(data["images"], np.float32), data, self.crit)
+            else:
+                _, items = self.amp.TrainStep(np.ascontiguousarray(data["images"], np.float32), data, self.crit)
             items_sum = items if items_sum is None else items_sum + items
             i += 1
         self.steps_run = i
