@@ -69,6 +69,14 @@ namespace YoloSharp.Native
         [DllImport(Lib)] internal static extern int ys_model_det_device(IntPtr model, out IntPtr rows, out int k);
         [DllImport(Lib)] internal static extern int ys_e2e_topk(IntPtr ctx, float[] pred, int onDevice, int batch, int nc, int anchors, int maxDet, [Out] float[] rows, [Out] long[] anchor);
         [DllImport(Lib)] internal static extern int ys_e2e_select(IntPtr ctx, float[] rows, int onDevice, int batch, int k, float confThres, int maxDet, [Out] int[] count);
+        // End2End Segment (Segmenter.cs:17-24): One2one_Init for Detect and Segment models; ys_loss_segment is then E2ESegmentLoss (gains 0.8 / 0.2; ys_model_e2e_update =
+        // E2ESegmentLoss.update(), which the reference's loop never calls for Segment); outputs "one2one_mask_coefficient" / "one2one_dmask_coefficient"; "det" rows [B,k,6+nm]
+        [DllImport(Lib)] internal static extern int ys_model_e2e_init(IntPtr model, int maxDet, int epochs);
+        [DllImport(Lib)] internal static extern int ys_model_e2e_update(IntPtr model);
+        [DllImport(Lib)] internal static extern int ys_model_e2e_gains(IntPtr model, out float o2m, out float o2o);
+        [DllImport(Lib)] internal static extern int ys_e2e_topk_ex(IntPtr ctx, float[] pred, int onDevice, int batch, int nc, int extra, int anchors, int maxDet, [Out] float[] rows, [Out] long[] anchor);
+        [DllImport(Lib)] internal static extern int ys_e2e_select_ex(IntPtr ctx, float[] rows, int onDevice, int batch, int k, int rowLen, float confThres, int maxDet, [Out] int[] count);
+        [DllImport(Lib)] internal static extern int ys_tal_keep_best(IntPtr ctx, float[] align, [In, Out] byte[] maskPos, int[] gtCount, int onDevice, int batch, int boxes, int anchors);
         // 0 = disjoint AdamW groups, 1 = the overlapping groups of YoloBaseTaskModel.cs:144-151 exactly as written
         [DllImport(Lib)] internal static extern int ys_optim_set_param_groups(IntPtr model, int mode);
         // Augment.LetterBox / Augment.Rectangle (Data/Augment.cs:698-857) on the device; uint8 planes (isFloat = 0) or fp32 masks

@@ -148,7 +148,7 @@ YS_API int ys_model_reserve_labels(ys_model* m, int per_image);
  * modules as cv2 / cv3 (the reference copies references, SaveWeight drops the one2one keys), so the model gains NO tensor: ys_model_num_tensors /
  * tensor_info / num_params are unchanged and weight files move freely between End2End and plain models.  max_det: rows of the post-process
  * (0 = 300, Head.cs:13).  YS_DETECT models of both families and every dtype; Segment / OBB / Pose / Classify models and the standalone block /
- * head handles return YS_ERR_UNSUPPORTED.  Call it once, after ys_model_create.  From then on:
+ * head handles return YS_ERR_UNSUPPORTED (Segment models take ys_model_e2e_init below; OBB / Pose End2End is a follow-up).  Call it once, after ys_model_create.  From then on:
  *   training forward (Head.cs:89-106): "one2one_boxes" / "one2one_scores" are outputs (the same values as "boxes" / "scores": same modules,
  *     same input values); the BatchNorm units of the towers update their running statistics twice, num_batches_tracked += 2.
  *   ys_loss_detect = E2EDetectLoss (Utils/Loss.cs:1094-1118): v8DetectionLoss(tal_topk 10) on one2many + v8DetectionLoss(tal_topk 1) on
@@ -160,6 +160,30 @@ YS_API int ys_model_reserve_labels(ys_model* m, int per_image);
  *     class), k = min(max_det, A), is ys_e2e_topk of it.  ys_model_det_device: the device pointer of "det" and k. */
 YS_API int ys_model_one2one_init(ys_model* m, int max_det);
 YS_API int ys_model_det_device(ys_model* m, float** rows, int* k);
+/* ---- End2End for Segment models (Models/Segmenter.cs:17-24; Segment.one2one_init, Modules/Head.cs:245-357; E2ESegmentLoss, Utils/Loss.cs:1179-1236).
+ * ys_model_e2e_init is One2one_Init for YS_DETECT models (identical to ys_model_one2one_init; `epochs` ignored) AND for YS_SEGMENT models of both
+ * families and every dtype; OBB / Pose / Classify models and the block / head handles return YS_ERR_UNSUPPORTED, a second call YS_ERR_STATE.
+ * max_det 0 = 300; epochs 0 = 100 (the length of the criterion's gain schedule).  ys_model_one2one_init keeps refusing Segment models.  The towers
+ * cv2, cv3 AND cv4 are aliased, so again NO tensor is added and `.bin` files move freely between plain and End2End Segment models.  From then on:
+ *   training forward (Head.cs:89-106, 283-307): the one2one branch = the three towers again on x.detach(); Proto runs ONCE (one2one["proto"] =
+ *     proto.detach()).  "one2one_boxes" / "one2one_scores" / "one2one_mask_coefficient" are the one2many values; the BatchNorm units of cv2 / cv3 / cv4
+ *     move their running statistics twice per forward (num_batches_tracked += 2), Proto's once.
+ *   ys_loss_segment = E2ESegmentLoss: v8SegmentationLoss(tal_topk 10) on one2many and v8SegmentationLoss(tal_topk 7, tal_topk2 1) on one2one,
+ *     combined as o2m * L_one2many + o2o * L_one2one -- ys_loss_read_items returns the weighted 5 items, *loss_sum their sum * B.  ys_loss_segment is the
+ *     only criterion entry of such a model: ys_loss_detect on it returns YS_ERR_INVALID_ARG.  tal_topk2 = 1
+ *     (Utils/Tal.cs:242-250): after anchors claimed by several boxes are resolved, every box keeps its single best positive (ys_tal_keep_best).
+ *     "dboxes" / "dscores" / "dmask_coefficient" / "dproto" are the one2many gradients (x o2m), "one2one_dboxes" / "one2one_dscores" /
+ *     "one2one_dmask_coefficient" the one2one ones (x o2o); the one2one branch sends nothing into the prototypes.
+ *   gains: o2m = 0.8, o2o = 0.2 at creation.  ys_model_e2e_update = E2ESegmentLoss.update(): updates += 1; o2m = max(1 - updates /
+ *     max(epochs - 1, 1), 0) * 0.7 + 0.1; o2o = max(1 - o2m, 0).  The reference's training loop calls update() for E2EOBBLoss only
+ *     (YoloBaseTaskModel.cs:350-353), so ITS Segment runs stay at 0.8 / 0.2; call it once per epoch to get the schedule.  On a Detect End2End
+ *     model the gains are 1 / 1 (E2EDetectLoss is unweighted) and ys_model_e2e_update does nothing.
+ *   backward (all forms): towers receive o2m * g_one2many + o2o * g_one2one; the feature maps, Proto and everything below o2m * g_one2many.
+ *   eval forward (Head.cs:107-127, 309-339): "pred" [B, 4+nc+nm, A] with xyxy boxes; "det" [B, k, 6+nm] = (x1, y1, x2, y2, score, class,
+ *     mc[0..nm)) = ys_e2e_topk_ex(pred, extra = nm); ys_model_det_device returns its pointer and k (row length 6 + nm). */
+YS_API int ys_model_e2e_init(ys_model* m, int max_det, int epochs);
+YS_API int ys_model_e2e_update(ys_model* m);
+YS_API int ys_model_e2e_gains(ys_model* m, float* o2m, float* o2o);
 /* Detect.postprocess / get_topk_index with agnostic_nms = false (Head.cs:117-127, 175-196) over pred [B, 4+nc, A] fp32 (boxes in any
  * format, class scores): k = min(max_det, A); stage 1 = the k anchors with the largest max-over-classes score; stage 2 = the k largest of the
  * k * nc gathered scores, flattened [stage-1 rank][class]; out_rows [B, k, 6] = (box[0..3], score, class), out_anchor [B, k] = the anchor
@@ -172,6 +196,20 @@ YS_API int ys_e2e_topk(ys_ctx* ctx, const float* pred, int on_device, int batch,
  * of leading rows with score > conf_thres, at most max_det; the rows are not moved (the kept set is a prefix).  conf_thres outside [0,1] ->
  * YS_ERR_INVALID_ARG (ArgumentException in the reference).  `on_device` applies to rows and out_count. */
 YS_API int ys_e2e_select(ys_ctx* ctx, const float* rows, int on_device, int batch, int k, float conf_thres, int max_det, int32_t* out_count);
+/* ys_e2e_topk over pred [B, 4+nc+extra, A] (Segment.postprocess, Head.cs:321-339): the same two-stage selection and tie rule on the nc class
+ * scores; out_rows [B, k, 6+extra] additionally carries the `extra` trailing channels pred[b, 4+nc+j, anchor] of the selected anchor (the mask
+ * coefficients).  extra = 0 is ys_e2e_topk, bit for bit.  ys_e2e_select_ex: ys_e2e_select on rows of row_len >= 6 floats. */
+YS_API int ys_e2e_topk_ex(ys_ctx* ctx, const float* pred, int on_device, int batch, int nc, int extra, int anchors, int max_det,
+                          float* out_rows, int64_t* out_anchor);
+YS_API int ys_e2e_select_ex(ys_ctx* ctx, const float* rows, int on_device, int batch, int k, int row_len, float conf_thres, int max_det,
+                            int32_t* out_count);
+/* The assigner's second stage, tal_topk2 = 1 (Utils/Tal.cs:242-250), on its own -- the kernel the End2End Segment criterion runs.  align
+ * [B, G, A] fp32, mask_pos [B, G, A] uint8 (in / out), gt_count [B] in [0, G]: in every row g < gt_count[b] only the anchor that comes first in
+ * (align * mask_pos descending, anchor index ascending) order over ALL A anchors keeps its mask bit.  So among equal positives the lower index
+ * stays, and a row whose positives all carry align = 0 ties with every other anchor: it keeps anchor 0 if that is a positive of the row and ends
+ * empty otherwise (what a stable descending sort of the reference's expression gives).  Rows >= gt_count[b] are untouched.  No atomics. */
+YS_API int ys_tal_keep_best(ys_ctx* ctx, const float* align, uint8_t* mask_pos, const int32_t* gt_count, int on_device, int batch, int boxes,
+                            int anchors);
 
 /* v8SegmentationLoss.forward (Utils/Loss.cs:688-863) for task = YS_SEGMENT models: the detection terms and
  * assignment above, then calculate_segmentation_loss / single_mask_loss (:794-863) with Ops.crop_mask

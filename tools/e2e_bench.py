@@ -1,6 +1,6 @@
 """End2End cost on one device: prints ONE JSON line.
 
-  python tools/e2e_bench.py [--batch 64] [--imgsz 640] [--nc 80] [--steps 20] [--warmup 5] [--repeats 3]
+  python tools/e2e_bench.py [--task detect|segment] [--batch 64] [--imgsz 640] [--nc 80] [--steps 20] [--warmup 5] [--repeats 3]
 
 Four measurements, each in a child process of its own under its own time limit (a leg that fails or runs out of time ends the run):
   step_off / step_on   ms per train step of YOLOv8n bf16 (forward, criterion, backward, AdamW, zero_grad; device-resident images and labels)
@@ -8,6 +8,10 @@ Four measurements, each in a child process of its own under its own time limit (
                        through the head towers' backward and the towers' second running-statistics update
   topk                 ys_e2e_topk on a device-resident [B, 4+nc, A] tensor (A = the model's anchors at --imgsz), max_det 300
   torch_topk           a torch restatement of Detect.get_topk_index + gather (Modules/Head.cs:117-127, 175-196) on the same tensor and GPU
+--task segment measures the YOLOv11m-seg bf16 step at --batch 32 by default (BASELINE config 4's shape) with model.e2e_init() off and on -- the
+difference is the second criterion pass (tal_topk 7 + the keep-best stage + the one2one mask term without its prototype gradient), the one2one pass
+through the cv2 / cv3 / cv4 backward and the towers' second statistics update -- and ys_e2e_topk_ex (extra = 32 mask coefficients) against a torch
+restatement of Segment.postprocess (Head.cs:321-339).
 Every figure is the median over --repeats timed blocks of --steps calls after --warmup calls.
 """
 import argparse
@@ -54,30 +58,49 @@ def _anchors(S):
     return (S // 8) ** 2 + (S // 16) ** 2 + (S // 32) ** 2
 
 
-def _pred(B, nc, A, rng):
-    p = rng.random((B, 4 + nc, A), dtype=np.float32)
-    p[:, 4:] = p[:, 4:] ** 8                       # most scores small, a few large: the shape of sigmoid outputs early in training
+def _pred(B, nc, A, rng, extra=0):
+    p = rng.random((B, 4 + nc + extra, A), dtype=np.float32)
+    p[:, 4:4 + nc] = p[:, 4:4 + nc] ** 8           # most scores small, a few large: the shape of sigmoid outputs early in training
     return p
+
+
+def _masks(bi, bb, B, mh, mw):
+    """Overlap-encoded instance masks [B, H/4, W/4] (YoloDataset.cs:265-267): every label's box painted with its 1-based per-image index."""
+    masks = np.zeros((B, mh, mw), np.float32)
+    per = [0] * B
+    for j in range(len(bi)):
+        b = int(bi[j]); per[b] += 1
+        cx, cy, w, h = bb[j] * np.array([mw, mh, mw, mh], np.float32)
+        masks[b, max(int(cy - h / 2), 0):int(cy + h / 2) + 1, max(int(cx - w / 2), 0):int(cx + w / 2) + 1] = per[b]
+    return masks
 
 
 def leg_step(a, end2end):
     from yolosharp_amd import Engine
-    from yolosharp_amd.model import AMPWrapper, Yolov8, v8DetectionLoss
+    from yolosharp_amd.model import AMPWrapper, Yolov8, Yolov11Segment, v8DetectionLoss, v8SegmentationLoss
     eng = Engine(0)
     B, S, nc = a.batch, a.imgsz, a.nc
-    m = Yolov8(eng, nc=nc, size="n", height=S, width=S, max_batch=B, dtype="bf16", end2end=end2end)
+    seg = a.task == "segment"
+    if seg:
+        m = Yolov11Segment(eng, nc=nc, size="m", height=S, width=S, max_batch=B, dtype="bf16")
+        if end2end:
+            m.e2e_init()
+    else:
+        m = Yolov8(eng, nc=nc, size="n", height=S, width=S, max_batch=B, dtype="bf16", end2end=end2end)
     m.init_weights(1)
     rng = np.random.default_rng(0)
     x_dev = eng.to_device(rng.random((B, 3, S, S), dtype=np.float32))
     bi, cl, bb = _labels(B, nc, rng)
     m.reserve_labels(16)
     d = [eng.to_device(v) for v in (bi, cl, bb)]
-    crit, amp = v8DetectionLoss(m), AMPWrapper(m)
+    if seg:
+        d.append(eng.to_device(_masks(bi, bb, B, S // 4, S // 4)))
+    crit, amp = (v8SegmentationLoss if seg else v8DetectionLoss)(m), AMPWrapper(m)
     m.train()
 
     def step():
         m.forward_device(x_dev, B)
-        crit.forward_device(d[0], d[1], d[2], bi.shape[0])
+        crit.forward_device(d[0], d[1], d[2], bi.shape[0], *d[3:])
         amp.Step()
 
     ms, runs = _timed(step, eng.synchronize, a)
@@ -102,12 +125,16 @@ def leg_topk(a):
     from yolosharp_amd import Engine, _lib
     eng = Engine(0)
     B, nc, A = a.batch, a.nc, _anchors(a.imgsz)
+    extra = 32 if a.task == "segment" else 0
     k = min(300, A)
-    p_dev = eng.to_device(_pred(B, nc, A, np.random.default_rng(1)))
-    rows, anc = eng.malloc(B * k * 6 * 4), eng.malloc(B * k * 8)
+    p_dev = eng.to_device(_pred(B, nc, A, np.random.default_rng(1), extra))
+    rows, anc = eng.malloc(B * k * (6 + extra) * 4), eng.malloc(B * k * 8)
 
     def call():
-        _lib.check(eng.lib, eng.lib.ys_e2e_topk(eng.ctx, p_dev, 1, B, nc, A, 300, rows, anc))
+        if extra:
+            _lib.check(eng.lib, eng.lib.ys_e2e_topk_ex(eng.ctx, p_dev, 1, B, nc, extra, A, 300, rows, anc))
+        else:
+            _lib.check(eng.lib, eng.lib.ys_e2e_topk(eng.ctx, p_dev, 1, B, nc, A, 300, rows, anc))
 
     ms, runs = _timed(call, eng.synchronize, a)
     eng.kernel_profile(True)
@@ -117,25 +144,29 @@ def leg_topk(a):
     for p in (p_dev, rows, anc):
         eng.free(p)
     # kernels_ms: the two launches alone, between HIP events on the stream
-    return {"ms_per_call": round(ms, 4), "runs": runs, "kernels_ms": round(kernel_ms / max(n, 1), 4), "B": B, "A": A, "nc": nc, "k": k}
+    return {"ms_per_call": round(ms, 4), "runs": runs, "kernels_ms": round(kernel_ms / max(n, 1), 4), "B": B, "A": A, "nc": nc, "extra": extra, "k": k}
 
 
 def leg_torch_topk(a):
     import torch
     B, nc, A = a.batch, a.nc, _anchors(a.imgsz)
-    pred = torch.from_numpy(_pred(B, nc, A, np.random.default_rng(1))).cuda()
+    extra = 32 if a.task == "segment" else 0
+    pred = torch.from_numpy(_pred(B, nc, A, np.random.default_rng(1), extra)).cuda()
     k = min(300, A)
     ar = torch.arange(B, device="cuda")[:, None]
 
     def call():
         p = pred.permute(0, 2, 1)
-        boxes, scores = p.split((4, nc), dim=-1)
+        boxes, scores, mc = p.split((4, nc, extra), dim=-1)
         ori = scores.amax(-1).topk(k).indices.unsqueeze(-1)
         sc = scores.gather(1, ori.expand(-1, -1, nc))
         sc, index = sc.flatten(1).topk(k)
         idx = ori[ar, torch.div(index, nc, rounding_mode="floor")]
         bx = boxes.gather(1, idx.expand(-1, -1, 4))
-        return torch.cat((bx, sc[..., None], (index % nc)[..., None].float()), -1)
+        out = [bx, sc[..., None], (index % nc)[..., None].float()]
+        if extra:                                   # Segment.postprocess: the coefficients by the same anchor index
+            out.append(mc.gather(1, idx.expand(-1, -1, extra)))
+        return torch.cat(out, -1)
 
     ms, runs = _timed(call, torch.cuda.synchronize, a)
     return {"ms_per_call": round(ms, 4), "runs": runs}
@@ -143,7 +174,8 @@ def leg_torch_topk(a):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--batch", type=int, default=64)
+    ap.add_argument("--task", choices=("detect", "segment"), default="detect")
+    ap.add_argument("--batch", type=int, default=0, help="0 = 64 (detect, YOLOv8n) / 32 (segment, YOLOv11m-seg: config 4's shape)")
     ap.add_argument("--imgsz", type=int, default=640)
     ap.add_argument("--nc", type=int, default=80)
     ap.add_argument("--steps", type=int, default=20)
@@ -153,13 +185,16 @@ def main():
     ap.add_argument("--tmp", default=os.environ.get("TMPDIR", "/tmp"))
     ap.add_argument("--leg", choices=LEGS, help="run one measurement in this process (what the driver starts)")
     a = ap.parse_args()
+    if a.batch <= 0:
+        a.batch = 32 if a.task == "segment" else 64
     if a.leg:
         out = {"step_off": lambda: leg_step(a, False), "step_on": lambda: leg_step(a, True), "topk": lambda: leg_topk(a),
                "torch_topk": lambda: leg_torch_topk(a)}[a.leg]()
         print(json.dumps(out))
         return 0
-    res = {"metric": "e2e_cost", "model": "yolov8n", "dtype": "bf16", "batch": a.batch, "imgsz": a.imgsz, "nc": a.nc}
-    fwd = [x for kv in (("--batch", a.batch), ("--imgsz", a.imgsz), ("--nc", a.nc), ("--steps", a.steps), ("--warmup", a.warmup),
+    res = {"metric": "e2e_cost", "task": a.task, "model": "yolov11m-seg" if a.task == "segment" else "yolov8n", "dtype": "bf16", "batch": a.batch,
+           "imgsz": a.imgsz, "nc": a.nc}
+    fwd = [x for kv in (("--task", a.task), ("--batch", a.batch), ("--imgsz", a.imgsz), ("--nc", a.nc), ("--steps", a.steps), ("--warmup", a.warmup),
                         ("--repeats", a.repeats), ("--tmp", a.tmp)) for x in (kv[0], str(kv[1]))]
     for leg in LEGS:
         try:

@@ -3,6 +3,7 @@
 //
 // Restates (reference file:line under YoloSharp/):
 //   Modules/Head.cs:117-127  postprocess: split boxes / scores, get_topk_index, gather the boxes, cat -> [B, k, 6]
+//   Modules/Head.cs:321-339  Segment.postprocess: the same selection, plus the nm mask coefficients of the selected anchors -> [B, k, 6 + nm]
 //   Modules/Head.cs:175-196  get_topk_index (agnostic_nms = false): k = min(max_det, A); stage 1 = the k anchors with the largest
 //                            max-over-classes score; stage 2 = the k largest of the k * nc gathered scores, flattened;
 //                            anchor = stage1[idx / nc], class = idx % nc
@@ -46,11 +47,11 @@ __device__ inline unsigned e2e_comp_idx(e2e_u64 c) { return ~(unsigned)(c & 0xFF
 
 // ------------------------------------------------------------------ max over classes per anchor (scores.max(dim: -1), Head.cs:190)
 __global__ void __launch_bounds__(E2E_CM_T)
-e2e_classmax_kernel(const float* __restrict__ pred, int nc, int A, float* __restrict__ amax) {
+e2e_classmax_kernel(const float* __restrict__ pred, int nc, int extra, int A, float* __restrict__ amax) {
   const int a = blockIdx.x * E2E_CM_T + threadIdx.x;
   const long b = blockIdx.y;
   if (a >= A) return;
-  const float* p = pred + (b * (4 + nc) + 4) * (long)A + a;
+  const float* p = pred + (b * (4 + nc + extra) + 4) * (long)A + a;
   float m = p[0];
 #pragma unroll 8
   for (int c = 1; c < nc; c++) {
@@ -146,13 +147,14 @@ __device__ inline const e2e_u64* e2e_select_sorted(const float* __restrict__ val
 
 // ------------------------------------------------------------------ get_topk_index + gather (Head.cs:117-127, 175-196), one workgroup per image
 __global__ void __launch_bounds__(E2E_T)
-e2e_topk_kernel(const float* __restrict__ pred, int nc, int A, int k, int kp2, const float* __restrict__ amax, float* __restrict__ cand,
+e2e_topk_kernel(const float* __restrict__ pred, int nc, int extra, int A, int k, int kp2, const float* __restrict__ amax, float* __restrict__ cand,
                 int* __restrict__ stage1, e2e_u64* __restrict__ gsort, float* __restrict__ rows, long long* __restrict__ anchors) {
   __shared__ e2e_u64 s_buf[E2E_RANK_MAX];
   __shared__ e2e_u64 s_out[E2E_RANK_MAX];
   const int tid = threadIdx.x;
   const long b = blockIdx.x;
-  const float* pb = pred + b * (4 + nc) * (long)A;
+  const float* pb = pred + b * (4 + nc + extra) * (long)A;
+  const int rl = 6 + extra;                       // row length: (box, score, class) + the `extra` trailing channels of the anchor
   e2e_u64* buf = k <= E2E_RANK_MAX ? s_buf : gsort + b * kp2;
   int* st1 = stage1 + b * k;
   const int N2 = k * nc;
@@ -171,10 +173,18 @@ e2e_topk_kernel(const float* __restrict__ pred, int nc, int A, int k, int kp2, c
     const int i = (int)e2e_comp_idx(res[r]);
     const int j = i / nc, c = i - j * nc;
     const int a = st1[j];
-    float* o = rows + (b * k + r) * 6;
+    float* o = rows + (b * k + r) * rl;
     o[0] = pb[a]; o[1] = pb[(long)A + a]; o[2] = pb[2L * A + a]; o[3] = pb[3L * A + a];
     o[4] = cd[i]; o[5] = (float)c;
     anchors[b * k + r] = (long long)a;
+  }
+  if (extra > 0) {
+    // Segment.postprocess (Head.cs:321-339): the nm mask coefficients gathered by the same anchor index (written above by this workgroup)
+    __syncthreads();
+    for (int i = tid; i < k * extra; i += E2E_T) {
+      const int r = i / extra, j = i - r * extra;
+      rows[(b * k + r) * rl + 6 + j] = pb[(long)(4 + nc + j) * A + (long)anchors[b * k + r]];
+    }
   }
 }
 
@@ -186,10 +196,10 @@ size_t ys_e2e_topk_ws_bytes(int B, int nc, int A, int max_det) {
   return n;
 }
 
-int ys_e2e_topk_launch(hipStream_t st, const float* pred, int B, int nc, int A, int max_det, void* ws, float* rows, long long* anchors) {
-  if (B < 1 || nc < 1 || A < 1 || max_det < 1) { ys_set_error("ys_e2e_topk: B=%d nc=%d A=%d max_det=%d", B, nc, A, max_det); return YS_ERR_INVALID_ARG; }
+int ys_e2e_topk_launch(hipStream_t st, const float* pred, int B, int nc, int A, int max_det, void* ws, float* rows, long long* anchors, int extra) {
+  if (B < 1 || nc < 1 || A < 1 || max_det < 1 || extra < 0) { ys_set_error("e2e top-k (ys_e2e_topk / ys_e2e_topk_ex): B=%d nc=%d A=%d max_det=%d extra=%d", B, nc, A, max_det, extra); return YS_ERR_INVALID_ARG; }
   const int k = max_det < A ? max_det : A;
-  if ((long)k * nc >= (1L << 30) || B > 65535) { ys_set_error("ys_e2e_topk: k * nc = %ld candidates / batch %d out of range", (long)k * nc, B); return YS_ERR_UNSUPPORTED; }
+  if ((long)k * nc >= (1L << 30) || B > 65535) { ys_set_error("e2e top-k (ys_e2e_topk / ys_e2e_topk_ex): k * nc = %ld candidates / batch %d out of range", (long)k * nc, B); return YS_ERR_UNSUPPORTED; }
   int kp2 = 1; while (kp2 < k) kp2 <<= 1;
   YsKprofScope prof(st, "e2e_topk");
   char* w = (char*)ws;
@@ -198,30 +208,30 @@ int ys_e2e_topk_launch(hipStream_t st, const float* pred, int B, int nc, int A, 
   int* stage1 = (int*)w; w += (size_t)B * k * 4;
   w = (char*)ws + ((size_t)(w - (char*)ws) + 63) / 64 * 64;
   e2e_u64* gsort = (e2e_u64*)w;
-  YS_LAUNCH(e2e_classmax_kernel, dim3(ys_cdiv(A, E2E_CM_T), B), E2E_CM_T, st, pred, nc, A, amax);
-  YS_LAUNCH(e2e_topk_kernel, B, E2E_T, st, pred, nc, A, k, kp2, (const float*)amax, cand, stage1, gsort, rows, anchors);
+  YS_LAUNCH(e2e_classmax_kernel, dim3(ys_cdiv(A, E2E_CM_T), B), E2E_CM_T, st, pred, nc, extra, A, amax);
+  YS_LAUNCH(e2e_topk_kernel, B, E2E_T, st, pred, nc, extra, A, k, kp2, (const float*)amax, cand, stage1, gsort, rows, anchors);
   return YS_OK;
 }
 
 // ------------------------------------------------------------------ non_max_suppression(end2end: true) (Ops.cs:258-267)
-// rows [B][k][6] ordered by score: count[b] = the leading rows with score > conf_thres, at most max_det
+// rows [B][k][row_len] (6, or 6 + nm for Segment rows) ordered by score: count[b] = the leading rows with score > conf_thres, at most max_det
 __global__ void __launch_bounds__(256)
-e2e_select_kernel(const float* __restrict__ rows, int k, float conf, int max_det, int* __restrict__ count) {
+e2e_select_kernel(const float* __restrict__ rows, int k, int row_len, float conf, int max_det, int* __restrict__ count) {
   __shared__ int s_first;
   const long b = blockIdx.x;
   if (threadIdx.x == 0) s_first = k;
   __syncthreads();
   int first = k;                                  // first row that fails the test
   for (int r = threadIdx.x; r < k; r += 256)
-    if (!(rows[(b * k + r) * 6 + 4] > conf)) { first = r; break; }
+    if (!(rows[(b * k + r) * row_len + 4] > conf)) { first = r; break; }
   if (first < k) atomicMin(&s_first, first);
   __syncthreads();
   if (threadIdx.x == 0) count[b] = s_first < max_det ? s_first : max_det;
 }
 
-int ys_e2e_select_launch(hipStream_t st, const float* rows, int B, int k, float conf, int max_det, int* count) {
-  if (B < 1 || k < 1 || max_det < 1) { ys_set_error("ys_e2e_select: B=%d k=%d max_det=%d", B, k, max_det); return YS_ERR_INVALID_ARG; }
-  YS_LAUNCH(e2e_select_kernel, B, 256, st, rows, k, conf, max_det, count);
+int ys_e2e_select_launch(hipStream_t st, const float* rows, int B, int k, float conf, int max_det, int* count, int row_len) {
+  if (B < 1 || k < 1 || max_det < 1 || row_len < 6) { ys_set_error("e2e select (ys_e2e_select / ys_e2e_select_ex): B=%d k=%d max_det=%d row length %d", B, k, max_det, row_len); return YS_ERR_INVALID_ARG; }
+  YS_LAUNCH(e2e_select_kernel, B, 256, st, rows, k, row_len, conf, max_det, count);
   return YS_OK;
 }
 

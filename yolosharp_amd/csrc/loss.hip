@@ -5,6 +5,7 @@
 //   Utils/Loss.cs:363-390   preprocess (pad GT per image, cxcywh*imgsz -> xyxy pixels)
 //   Utils/Loss.cs:398-409   bbox_decode (softmax . arange(reg_max), dist2bbox xyxy)
 //   Utils/Tal.cs:50-255     TaskAlignedAssigner (topk 10, alpha 0.5, beta 6, eps 1e-9)
+//   Utils/Tal.cs:242-250    its second stage, tal_topk2 = 1 (the one2one criterion of E2ESegmentLoss): LossArgs::topk2, tal_keep_best_kernel
 //   Utils/Loss.cs:94-167    DFLoss / BboxLoss
 //   Utils/Metrics.cs:36-111 bbox_iou(CIoU), eps 1e-7, alpha NOT detached
 //   Utils/Tal.cs:313-379    make_anchors / dist2bbox / bbox2dist
@@ -521,6 +522,31 @@ __device__ inline void tal_metrics_pair(const LossArgs& a, const int* __restrict
 // of the 3.5 thousand that exit at once (SQ_WAVE_CYCLES / SQ_WAVES: the waves that work live ~9 us).  Flat form: every workgroup scans the B
 // counts (one wave, LDS), then walks the pairs p = blockIdx.x, + gridDim.x, ...; (image, slot) of pair p by binary search.
 #define TAL_FLAT_MAXB 1024
+// s_pref [B + 1] (LDS) = exclusive prefix sums of the per-image counts; returns the number of live pairs.  Whole workgroup of TAL_T threads.
+__device__ inline int tal_pair_prefix(const int* __restrict__ gt_count, const int B, int* s_pref) {
+  const int tid = threadIdx.x;
+  for (int i = tid; i < B; i += TAL_T) s_pref[i + 1] = gt_count[i];
+  __syncthreads();
+  if (tid < 64) {                                                 // inclusive scan: lane l owns entries [16 l, 16 l + 16)
+    int loc[16], sum = 0;
+#pragma unroll
+    for (int k = 0; k < 16; k++) { const int idx = tid * 16 + k; sum += idx < B ? s_pref[idx + 1] : 0; loc[k] = sum; }
+    int incl = sum;
+    for (int m = 1; m < 64; m <<= 1) { const int v = __shfl_up(incl, m); if (tid >= m) incl += v; }
+    const int base = incl - sum;
+#pragma unroll
+    for (int k = 0; k < 16; k++) { const int idx = tid * 16 + k; if (idx < B) s_pref[idx + 1] = base + loc[k]; }
+    if (tid == 0) s_pref[0] = 0;
+  }
+  __syncthreads();
+  return s_pref[B];
+}
+// image of pair p: the largest b with s_pref[b] <= p
+__device__ inline int tal_pair_image(const int* s_pref, const int B, const int p) {
+  int lo = 0, hi = B;
+  while (lo + 1 < hi) { const int mid = (lo + hi) >> 1; if (s_pref[mid] <= p) lo = mid; else hi = mid; }
+  return lo;
+}
 template <class T, bool ROT>
 __global__ void __launch_bounds__(TAL_T)
 tal_metrics_kernel(LossArgs a, const int* __restrict__ gt_valid) {
@@ -530,31 +556,17 @@ tal_metrics_kernel(LossArgs a, const int* __restrict__ gt_valid) {
     return;
   }
   __shared__ int s_pref[TAL_FLAT_MAXB + 1];
-  const int tid = threadIdx.x;
-  for (int i = tid; i < a.B; i += TAL_T) s_pref[i + 1] = a.gt_count[i];
-  __syncthreads();
-  if (tid < 64) {                                                 // inclusive scan: lane l owns entries [16 l, 16 l + 16)
-    int loc[16], sum = 0;
-#pragma unroll
-    for (int k = 0; k < 16; k++) { const int idx = tid * 16 + k; sum += idx < a.B ? s_pref[idx + 1] : 0; loc[k] = sum; }
-    int incl = sum;
-    for (int m = 1; m < 64; m <<= 1) { const int v = __shfl_up(incl, m); if (tid >= m) incl += v; }
-    const int base = incl - sum;
-#pragma unroll
-    for (int k = 0; k < 16; k++) { const int idx = tid * 16 + k; if (idx < a.B) s_pref[idx + 1] = base + loc[k]; }
-    if (tid == 0) s_pref[0] = 0;
-  }
-  __syncthreads();
-  const int total = s_pref[a.B];
+  const int total = tal_pair_prefix(a.gt_count, a.B, s_pref);
   for (int p = blockIdx.x; p < total; p += gridDim.x) {
-    int lo = 0, hi = a.B;                                          // largest b with s_pref[b] <= p
-    while (lo + 1 < hi) { const int mid = (lo + hi) >> 1; if (s_pref[mid] <= p) lo = mid; else hi = mid; }
+    const int lo = tal_pair_image(s_pref, a.B, p);
     tal_metrics_pair<T, ROT>(a, gt_valid, p - s_pref[lo], lo);
     __syncthreads();                                              // the next pair re-initialises the bit sets the last top-k round still reads
   }
 }
 
 // ------------------------------------------------------------------ K3: select_highest_overlaps (Tal.cs:225-255)
+// PRUNE (tal_topk2, the second assigner stage below follows): pos_align / pos_ov belong to the pruned mask, so they are left to that stage
+template <bool PRUNE>
 __global__ void __launch_bounds__(LS_THREADS)
 tal_resolve_kernel(LossArgs a) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -577,12 +589,71 @@ tal_resolve_kernel(LossArgs a) {
     for (int g = 0; g < n; g++) a.mpos[((long)b * a.gcap + g) * a.A + ai] = (g == sel) ? 1 : 0;
   }
   a.fg_gt[i] = sel;  // -1 = background
-  if (sel >= 0) {
+  if (!PRUNE && sel >= 0) {
     const long gi = (long)b * a.gcap + sel;
     // pos_align_metrics / pos_overlaps: amax over anchors of (metric * mask_pos) (Tal.cs:83-85);
     // non-negative floats order like their bit patterns
     atomicMax(&a.pos_align[gi], ys_f2u(a.align[gi * a.A + ai]));
     atomicMax(&a.pos_ov[gi], ys_f2u(a.ov[gi * a.A + ai]));
+  }
+}
+
+// ------------------------------------------------------------------ K3b: second assigner stage, tal_topk2 = 1 (Tal.cs:242-250)
+// After select_highest_overlaps: align_metric * mask_pos, topk(1) over the anchors of every (image, box) row, mask_pos *= scatter(index),
+// fg_mask = mask_pos.sum(-2) -- each box keeps its single best positive.  One workgroup per LIVE pair (the flat walk of tal_metrics_kernel).
+// Order among equal values: value descending, index ascending over ALL A anchors, so a row whose positives all carry metric 0 ties with every
+// other anchor and keeps anchor 0 -- which survives only if it was a positive of the row (otherwise the row ends empty).  What follows the
+// stage reads the pruned mask (Tal.cs:77-87): fg_gt loses the cleared anchors (after the resolve stage an anchor belongs to one row only, so
+// no two workgroups write the same word), pos_align / pos_ov of the row are the kept anchor's values.  No atomics, no float is added.
+__device__ inline void tal_keep_best_pair(const TalKeepArgs& k, const int g, const int b) {
+  __shared__ float s_v[TAL_T / 64];
+  __shared__ int s_i[TAL_T / 64];
+  const int tid = threadIdx.x;
+  const long gi = (long)b * k.G + g;
+  const float* alr = k.align + gi * k.A;
+  unsigned char* mp = k.mpos + gi * k.A;
+  float bv = -INFINITY;
+  int bi = 0x7fffffff;
+  for (int ai = tid; ai < k.A; ai += TAL_T) {                      // increasing index: strict '>' keeps the lowest among equals
+    const float v = mp[ai] ? alr[ai] : 0.f;
+    if (v > bv || bi == 0x7fffffff) { bv = v; bi = ai; }
+  }
+  for (int m = 32; m >= 1; m >>= 1) {
+    const float ov_ = __shfl_xor(bv, m);
+    const int oi = __shfl_xor(bi, m);
+    if (ov_ > bv || (ov_ == bv && oi < bi)) { bv = ov_; bi = oi; }
+  }
+  if ((tid & 63) == 0) { s_v[tid >> 6] = bv; s_i[tid >> 6] = bi; }
+  __syncthreads();
+  float fv = s_v[0]; int fi = s_i[0];
+  for (int wv = 1; wv < TAL_T / 64; wv++)
+    if (s_v[wv] > fv || (s_v[wv] == fv && s_i[wv] < fi)) { fv = s_v[wv]; fi = s_i[wv]; }
+  // mp[fi] is never written below, so every thread may read it while others clear their anchors
+  const bool kept = fi < k.A && mp[fi] != 0;
+  for (int ai = tid; ai < k.A; ai += TAL_T) {
+    if (ai != fi && mp[ai]) {
+      mp[ai] = 0;
+      if (k.fg_gt) k.fg_gt[(long)b * k.A + ai] = -1;
+    }
+  }
+  if (tid == 0 && k.pos_align) {
+    k.pos_align[gi] = kept ? ys_f2u(alr[fi]) : 0u;
+    k.pos_ov[gi] = kept ? ys_f2u(k.ov[gi * k.A + fi]) : 0u;
+  }
+  __syncthreads();                                                  // s_v / s_i are rewritten by the next pair
+}
+__global__ void __launch_bounds__(TAL_T)
+tal_keep_best_kernel(TalKeepArgs k) {
+  if (gridDim.y > 1) {                                            // [G][B] form (B > TAL_FLAT_MAXB)
+    if ((int)blockIdx.x >= k.gt_count[blockIdx.y]) return;
+    tal_keep_best_pair(k, (int)blockIdx.x, (int)blockIdx.y);
+    return;
+  }
+  __shared__ int s_pref[TAL_FLAT_MAXB + 1];
+  const int total = tal_pair_prefix(k.gt_count, k.B, s_pref);
+  for (int p = blockIdx.x; p < total; p += gridDim.x) {
+    const int lo = tal_pair_image(s_pref, k.B, p);
+    tal_keep_best_pair(k, p - s_pref[lo], lo);
   }
 }
 
@@ -870,6 +941,7 @@ static int loss_launch_t(hipStream_t st, const LossArgs& a) {
   if (a.reg_max > 32) { ys_set_error("loss: reg_max %d > 32 unsupported", a.reg_max); return YS_ERR_UNSUPPORTED; }
   if (a.A > 1056 * 32) { ys_set_error("loss: %d anchors exceed the assigner capacity", a.A); return YS_ERR_UNSUPPORTED; }
   if (a.ld_ps % EPL) { ys_set_error("loss: ld_ps %d must be a multiple of %d", a.ld_ps, EPL); return YS_ERR_INVALID_ARG; }
+  if (a.topk2 != 0 && (a.topk2 != 1 || a.rot)) { ys_set_error("loss: tal_topk2 = %d%s is not built (the reference uses 1; OBB End2End is a follow-up)", a.topk2, a.rot ? " on rotated boxes" : ""); return YS_ERR_UNSUPPORTED; }
   // gt_valid lives behind gt_cls ([B][gcap] ints each)
   int* gt_valid = a.gt_cls + (long)a.B * a.gcap;
   const int nb_a = anc_blocks(a), nb_c = cls_blocks(a, EPL), nb_b = box_blocks(a);
@@ -887,7 +959,13 @@ static int loss_launch_t(hipStream_t st, const LossArgs& a) {
   const dim3 tgrid = a.B <= TAL_FLAT_MAXB ? dim3((unsigned)flat) : dim3(a.gmax > 0 ? a.gmax : a.gcap, a.B);
   if (a.rot) YS_LAUNCH((tal_metrics_kernel<T, true>), tgrid, TAL_T, st, a, (const int*)gt_valid);
   else YS_LAUNCH((tal_metrics_kernel<T, false>), tgrid, TAL_T, st, a, (const int*)gt_valid);
-  YS_LAUNCH(tal_resolve_kernel, nb_a, LS_THREADS, st, a);
+  if (a.topk2) {   // resolve first, prune second (Tal.cs:231-250)
+    TalKeepArgs kb{a.align, a.mpos, a.gt_count, a.ov, a.pos_align, a.pos_ov, a.fg_gt, a.B, a.gcap, a.A};
+    YS_LAUNCH(tal_resolve_kernel<true>, nb_a, LS_THREADS, st, a);
+    YS_LAUNCH(tal_keep_best_kernel, tgrid, TAL_T, st, kb);
+  } else {
+    YS_LAUNCH(tal_resolve_kernel<false>, nb_a, LS_THREADS, st, a);
+  }
   YS_LAUNCH(tal_targets_kernel, nb_a, LS_THREADS, st, a);
   YS_LAUNCH((loss_cls_kernel<T>), nb_c, LS_THREADS, st, a);
   if (a.rot) {
@@ -904,4 +982,14 @@ static int loss_launch_t(hipStream_t st, const LossArgs& a) {
 int ys_loss_detect_launch(hipStream_t st, int dtype, const LossArgs& a) {
   if (dtype == YS_BF16) return loss_launch_t<bf16_t>(st, a);
   return loss_launch_t<float>(st, a);
+}
+
+// the second assigner stage on its own (ys_tal_keep_best): gt_count must already lie in [0, G]
+int ys_tal_keep_best_launch(hipStream_t st, const TalKeepArgs& k) {
+  if (k.B < 1 || k.G < 1 || k.A < 1) { ys_set_error("ys_tal_keep_best: B=%d G=%d A=%d", k.B, k.G, k.A); return YS_ERR_INVALID_ARG; }
+  long flat = (long)k.B * 12 > 256 ? (long)k.B * 12 : 256;
+  if (flat > (long)k.G * k.B) flat = (long)k.G * k.B;
+  const dim3 grid = k.B <= TAL_FLAT_MAXB ? dim3((unsigned)flat) : dim3(k.G, k.B);
+  YS_LAUNCH(tal_keep_best_kernel, grid, TAL_T, st, k);
+  return YS_OK;
 }

@@ -54,6 +54,7 @@ struct ConvL {
   int idx = -1, prep_idx = -1;           // own index in ys_model::convs; first PrepDesc (weight-amax slot)
   long wgp_off = -1; int wgp_splits = 0; // own region of the weight-gradient partial workspace (floats) and the splits it holds; -1 = shared scratch + immediate reduce
   int red_slot = -1;                     // index into ys_model::red_host (deferred split reduction)
+  bool proto = false;    // a unit of Segment's Proto: runs ONCE per End2End forward (Head.cs:283-307) -- no second statistics update, no one2one backward pass
   bool ct = false;       // ConvTranspose2d(k=2,s=2,bias) = four 1x1 phase GEMMs (Proto.upsample, Block.cs:69); weights [4][Cout][Cin]
   // fused BN-backward reduction (BnRedSeg, ys_kernels.h).  As a consumer: the producers whose dz this layer's dgrad completes
   // (it is their first reader in forward order = last gradient writer in backward order).  As a producer: where its sums come from.
@@ -178,7 +179,7 @@ struct ys_model {
   float* stat_group = nullptr;                  // statistics rows of the grouped head stages (one region per unit, ConvL::gstat_off)
   float* wg_partial = nullptr; long n_wgp = 0;   // [shared scratch (ConvTranspose phases) | one region per convolution]
   // deferred split reduction of the weight gradients: one batched launch per backward_range call instead of one per layer
-  std::vector<WgRedDesc> red_host, red_uploaded; WgRedDesc* red_dev = nullptr; int red_first[NSEG + 1] = {0, 0, 0, 0, 0};
+  std::vector<WgRedDesc> red_host, red_uploaded; WgRedDesc* red_dev = nullptr; int red_first[NSEG + 1] = {0, 0, 0, 0, 0}; int red_proto0 = 0;   // red_proto0: first descriptor of Proto's units in segment 0 (they sort last there)
   bool defer_wgred = true;
   // fused BN-backward reduction: planned per batch size (plan_bnred), partial rows of every (producer, consumer) pair
   bool bnred_on = true; int bnred_B = -1; float* bnred_part = nullptr; long n_bnred = 0;
@@ -198,9 +199,17 @@ struct ys_model {
   // criterion pass (tal_topk 1) writes its gradients and scalars here; the eval forward adds the top-k rows "det" [B][k][6]
   bool e2e = false; int max_det = 300;
   void *o2o_dpd = nullptr, *o2o_dps = nullptr; float* scalars2 = nullptr;
+  // End2End Segment (ys_model_e2e_init; Head.cs:245-357, Loss.cs:1179-1236): cv4 is aliased as well, Proto runs once.  E2ESegmentLoss weights its
+  // two criteria with the gains o2m / o2o (0.8 / 0.2 until ys_model_e2e_update moves them); a Detect End2End model keeps 1 / 1 (E2EDetectLoss is unweighted).
+  // det_rows is then [B][k][6 + nm]; seg_pass2 = the first criterion pass's arguments, kept for the second one (ys_loss_segment)
+  bool e2e_seg = false; float o2m = 1.0f, o2o = 1.0f; int e2e_updates = 0, e2e_epochs = 100;
+  void* o2o_dmc = nullptr; LossArgs seg_pass2{};
   float* det_rows = nullptr; long long* det_anchor = nullptr; void* det_ws = nullptr;
   int head_conv0 = 0, det_in[3] = {-1, -1, -1};       // first tower unit in `convs`; the three feature maps the head reads
-  long hstate0 = 0, n_hstate = 0; float* hstate_snap = nullptr; unsigned char* hstate_count = nullptr;   // the towers' running statistics [hstate0, n_state)
+  // the towers' running statistics as contiguous runs of `state` (Detect: one, the tail; Segment: Proto's units lie between cv3 and cv4 and are left out);
+  // snapshot and num_batches_tracked mask hold the runs back to back (n_hstate words)
+  long n_hstate = 0; float* hstate_snap = nullptr; unsigned char* hstate_count = nullptr;
+  Range hstate_rng[4]; int n_hstate_rng = 0;
   bool e2e_pass = false;                              // backward: the one2one pass through the towers is running (no gradient into det_in)
   bool have_fwd = false, have_loss = false;
   bool fwd_training = false;   // the last forward kept what backward needs (training-mode BN statistics, pre-BN outputs)
@@ -467,7 +476,7 @@ int add_detect(ys_model* m, const std::string& hp, const int* pv, const int* ch,
     {
       const size_t pc0 = m->convs.size();
       m->pr_buf = add_proto(m, hp + ".proto", View{pv[0], 0, ch[0]}, ch[0], npr, nm, hh[0], ww[0], seg);
-      for (size_t k = pc0; k < m->convs.size(); k++) m->convs[k].stage = 2 * 4 + (int)(k - pc0);   // a chain: one unit per stage
+      for (size_t k = pc0; k < m->convs.size(); k++) { m->convs[k].stage = 2 * 4 + (int)(k - pc0); m->convs[k].proto = true; }   // a chain: one unit per stage
     }
     m->mc_buf = new_buf(m, 1, m->A, m->ld_mc);
     for (int i = 0; i < 3; i++) {
@@ -1294,14 +1303,23 @@ int allocate(ys_model* m) {
   }
   {
     long off = (wgp + 63) / 64 * 64;
-    // descriptor order = backward-segment order, so that a backward_range call reduces one contiguous run of descriptors
+    // descriptor order = backward-segment order, so that a backward_range call reduces one contiguous run of descriptors.  Within a segment Proto's units
+    // come LAST: the one2one pass of an End2End Segment backward launches no weight gradient for them, so it reduces the prefix [red_first[0], red_proto0)
+    // only -- their descriptors and partial regions still hold the previous step's values, and the reduction accumulates.  A prefix keeps every blk0 of
+    // the full run, so the two reductions of a step share one uploaded table.
     for (int seg = 0; seg < ys_model::NSEG; seg++) {
       m->red_first[seg] = (int)m->red_host.size();
       for (auto& c : m->convs) {
         if (c.seg != seg || c.dw || c.ct || !m->defer_wgred) continue;
         c.wgp_off = off; off += (need[c.idx] + 63) / 64 * 64;
-        c.red_slot = (int)m->red_host.size();
-        m->red_host.push_back(WgRedDesc{});
+      }
+      for (int last = 0; last < 2; last++) {
+        if (seg == 0 && last == 1) m->red_proto0 = (int)m->red_host.size();
+        for (auto& c : m->convs) {
+          if (c.seg != seg || c.dw || c.ct || !m->defer_wgred || (int)c.proto != last) continue;
+          c.red_slot = (int)m->red_host.size();
+          m->red_host.push_back(WgRedDesc{});
+        }
       }
     }
     m->red_first[ys_model::NSEG] = (int)m->red_host.size();
@@ -1586,7 +1604,13 @@ int forward_impl(ys_model* m, int B) {
   }
   m->q8_fwd_ready = -1;
   const bool e2e_stats = m->e2e && m->training && m->n_hstate > 0;
-  if (e2e_stats) YS_CHECK_HIP(hipMemcpyAsync(m->hstate_snap, m->state + m->hstate0, (size_t)m->n_hstate * 4, hipMemcpyDeviceToDevice, st));
+  if (e2e_stats) {
+    long so = 0;
+    for (int r = 0; r < m->n_hstate_rng; r++) {
+      YS_CHECK_HIP(hipMemcpyAsync(m->hstate_snap + so, m->state + m->hstate_rng[r].off, (size_t)m->hstate_rng[r].count * 4, hipMemcpyDeviceToDevice, st));
+      so += m->hstate_rng[r].count;
+    }
+  }
   for (size_t oi = 0; oi < m->ops.size(); oi++) {
     const Op& op = m->ops[oi];
     const Buf& ib = m->bufs[op.in.buf];
@@ -1635,17 +1659,24 @@ int forward_impl(ys_model* m, int B) {
   if (!m->training && m->cls)   // Classify eval: inference["cls"] = softmax(logits, 1) (Head.cs:640)
     YS_TRY(ys_cls_xent_launch(st, m->dtype, m->bufs[m->logit_buf].act, m->ld_cls, B, m->d.nc, nullptr, nullptr, m->pred, nullptr, nullptr));
   if (m->f8) m->f8_sx_valid = true;        // every fp8 candidate has recorded an input maximum (bootstrap pass or its own kernel)
-  if (e2e_stats)   // the one2one branch runs the same tower modules again on the same values: their running statistics move twice (e2e.hip)
-    YS_TRY(ys_e2e_bn_second_update_launch(st, m->state + m->hstate0, m->hstate_snap, m->hstate_count, m->n_hstate, 0.03f));
+  if (e2e_stats) {   // the one2one branch runs the same tower modules again on the same values: their running statistics move twice (e2e.hip)
+    long so = 0;
+    for (int r = 0; r < m->n_hstate_rng; r++) {
+      YS_TRY(ys_e2e_bn_second_update_launch(st, m->state + m->hstate_rng[r].off, m->hstate_snap + so, m->hstate_count + so, m->hstate_rng[r].count, 0.03f));
+      so += m->hstate_rng[r].count;
+    }
+  }
   if (!m->training && m->pd_buf >= 0) {
     YS_TRY(ys_detect_decode_launch(st, m->dtype, m->bufs[m->pd_buf].act, m->ld_pd, m->bufs[m->ps_buf].act, m->ld_ps, B, m->A,
                                    m->d.nc, m->d.reg_max, m->nl, m->lvl_off, m->lvl_w, m->lvl_stride, m->pred, 4 + m->d.nc + m->nm,
                                    m->xkind >= 2 ? m->bufs[m->mc_buf].act : nullptr, m->ld_mc, m->xkind, m->nm, m->kdim, m->e2e ? 1 : 0));
-    if (m->e2e)       // Detect.postprocess on the one2one branch (same values as the one2many branch): [B][k][6] (Head.cs:107-127)
+    if (m->e2e && !m->e2e_seg)   // Detect.postprocess on the one2one branch (same values as the one2many branch): [B][k][6] (Head.cs:107-127)
       YS_TRY(ys_e2e_topk_launch(st, m->pred, B, m->d.nc, m->A, m->max_det, m->det_ws, m->det_rows, m->det_anchor));
     if (m->segment)   // Segment._inference: cat(preds, mask_coefficient) (Head.cs:309-313), raw coefficients
       YS_TRY(ys_unpack_nchw_strided_launch(st, m->dtype, m->bufs[m->mc_buf].act, m->ld_mc, 0, B, m->nm, m->A, m->pred,
                                            (long)(4 + m->d.nc + m->nm) * m->A, (long)(4 + m->d.nc) * m->A));
+    if (m->e2e_seg)   // Segment.postprocess (Head.cs:321-339): the same selection, the nm coefficients gathered by the same anchor index: [B][k][6 + nm]
+      YS_TRY(ys_e2e_topk_launch(st, m->pred, B, m->d.nc, m->A, m->max_det, m->det_ws, m->det_rows, m->det_anchor, m->nm));
   }
   YS_CHECK_HIP(hipGetLastError());
   return YS_OK;
@@ -2150,16 +2181,19 @@ int backward_range(ys_model* m, int seg_lo, int seg_hi, bool async_end = false, 
     // joined in between: the second pass reuses every dy buffer and partial region.
     Buf &pb = m->bufs[m->pd_buf], &sb = m->bufs[m->ps_buf];
     std::swap(pb.grad, m->o2o_dpd); std::swap(sb.grad, m->o2o_dps);
+    if (m->e2e_seg) std::swap(m->bufs[m->mc_buf].grad, m->o2o_dmc);     // cv4 is aliased too (Head.cs:245-357); Proto ran once and gets no one2one gradient
     m->e2e_pass = true;
     const int rc = backward_range(m, 0, 0, false, false);
     m->e2e_pass = false;
     std::swap(pb.grad, m->o2o_dpd); std::swap(sb.grad, m->o2o_dps);
+    if (m->e2e_seg) std::swap(m->bufs[m->mc_buf].grad, m->o2o_dmc);
     YS_TRY(rc);
     reset_grad_state(m);
   }
   for (int i = (int)m->ops.size() - 1; i >= 0; i--) {
     const Op& op = m->ops[i];
     if (op.seg < seg_lo || op.seg > seg_hi) continue;
+    if (m->e2e_pass && op.type == OP_CONV && m->convs[op.conv].proto) continue;   // one2one["proto"] = proto.detach() (Head.cs:297)
     if (op.type == OP_CONV && m->convs[op.conv].group >= 0) {
       ConvL* gc[YS_GROUP_MAX]; int gn = 0;
       const int gid = m->convs[op.conv].group;
@@ -2221,7 +2255,8 @@ int backward_range(ys_model* m, int seg_lo, int seg_hi, bool async_end = false, 
     }
     return ys_wgrad_reduce_batched_launch(sr, m->red_dev + lo, hi - lo, blk);
   };
-  const int rlo = m->red_first[seg_lo], rhi = m->red_first[seg_hi + 1];
+  // one2one pass: Proto's units were skipped above, so their descriptors (the tail of the head segment's run) are left out of this reduction
+  const int rlo = m->red_first[seg_lo], rhi = m->e2e_pass ? m->red_proto0 : m->red_first[seg_hi + 1];
   // The step's LAST dependency chain is dgrad(model.1) -> BN backward of model.0 -> stem weight gradient -> split reduction -> AdamW (round-6 trace: 200 us with the
   // main stream idle).  In the one-call backward the stem's weight gradient is therefore handed over on its own, AFTER the reduction of everything else in its
   // segment has been queued on the second stream: that reduction (48 us) then runs while the main stream is still in the BatchNorm backward of model.0, and only
@@ -2571,8 +2606,18 @@ int ys_model_get_output(ys_model* m, const char* key, float* host, size_t count)
     YS_REQUIRE(m->e2e, "ys_model_get_output(det): not an End2End model (ys_model_one2one_init)");
     YS_REQUIRE(!m->fwd_training && !m->training, "ys_model_get_output(det): the last forward ran in training mode");
     const size_t kk = (size_t)std::min(m->max_det, m->A);
-    YS_REQUIRE(count == (size_t)B * kk * 6, "ys_model_get_output(det): expected %zu elements", (size_t)B * kk * 6);
+    const size_t rl = (size_t)(6 + (m->e2e_seg ? m->nm : 0));      // End2End Segment: + the nm mask coefficients of the anchor (Head.cs:321-339)
+    YS_REQUIRE(count == (size_t)B * kk * rl, "ys_model_get_output(det): expected %zu elements", (size_t)B * kk * rl);
     YS_CHECK_HIP(hipMemcpyAsync(host, m->det_rows, count * 4, hipMemcpyDeviceToHost, st));
+  } else if (m->segment && (k == "one2one_mask_coefficient" || k == "one2one_dmask_coefficient")) {
+    // End2End Segment: cv4 is aliased like cv2 / cv3, so the one2one coefficients ARE the one2many ones; the second criterion pass has its own gradient
+    YS_REQUIRE(m->e2e_seg, "ys_model_get_output(%s): not an End2End Segment model (ys_model_e2e_init)", key);
+    const bool g = k[8] == 'd';
+    YS_REQUIRE(!g || m->have_seg_loss, "ys_model_get_output(%s): no segment loss has run", key);
+    YS_REQUIRE(count == (size_t)B * m->nm * m->A, "ys_model_get_output(%s): expected %zu elements", key, (size_t)B * m->nm * m->A);
+    const Buf& b = m->bufs[m->mc_buf];
+    YS_TRY(ys_unpack_nchw_launch(st, m->dtype, g ? m->o2o_dmc : b.act, b.ldc, 0, B, m->nm, m->A, m->out_stage));
+    YS_CHECK_HIP(hipMemcpyAsync(host, m->out_stage, count * 4, hipMemcpyDeviceToHost, st));
   } else if (m->segment && (k == "mask_coefficient" || k == "dmask_coefficient")) {   // Head.cs:290-296: [B][nm][A]
     const bool g = k[0] == 'd';
     YS_REQUIRE(!g || m->have_seg_loss, "ys_model_get_output(%s): no segment loss has run", key);
@@ -2651,14 +2696,7 @@ int ys_model_pred_device(ys_model* m, float** dptr) {
 // YoloBaseTaskModel.One2one_Init -> Detect.one2one_init (Head.cs:152-167): the one2one towers are the SAME Sequential objects as cv2 / cv3
 // (CopyTo copies references), so the model gains no tensor -- only the second criterion pass's gradient / scalar buffers, the snapshot of
 // the towers' running statistics (their second momentum update) and the top-k output of the eval forward.
-int ys_model_one2one_init(ys_model* m, int max_det) {
-  YS_REQUIRE(m, "ys_model_one2one_init: null model");
-  YS_REQUIRE(max_det >= 0, "ys_model_one2one_init: max_det = %d", max_det);
-  if (m->is_block || m->is_head || m->cls || m->d.task != YS_DETECT || m->pd_buf < 0) {
-    ys_set_error("ys_model_one2one_init: End2End is built for full Detect models (Segment / OBB / Pose End2End and the standalone heads are follow-ups)");
-    return YS_ERR_UNSUPPORTED;
-  }
-  if (m->e2e) { ys_set_error("ys_model_one2one_init: already initialised"); return YS_ERR_STATE; }
+static int e2e_init_impl(ys_model* m, int max_det, bool seg) {
   YS_CHECK_HIP(hipSetDevice(m->ctx->device));
   const int B = m->maxB;
   m->max_det = max_det > 0 ? max_det : 300;     // Detect.max_det (Head.cs:13)
@@ -2666,32 +2704,108 @@ int ys_model_one2one_init(ys_model* m, int max_det) {
   const Buf &pb = m->bufs[m->pd_buf], &sb = m->bufs[m->ps_buf];
   YS_TRY(dev_alloc(m, &m->o2o_dpd, (size_t)B * pb.rows_per_b * pb.ldc * m->es));
   YS_TRY(dev_alloc(m, &m->o2o_dps, (size_t)B * sb.rows_per_b * sb.ldc * m->es));
+  if (seg) { const Buf& cb = m->bufs[m->mc_buf]; YS_TRY(dev_alloc(m, &m->o2o_dmc, (size_t)B * cb.rows_per_b * cb.ldc * m->es)); }
   YS_TRY(dev_alloc(m, (void**)&m->scalars2, 64 * 4 + 64 * 8 * 8));
-  YS_TRY(dev_alloc(m, (void**)&m->det_rows, (size_t)B * k * 6 * 4));
+  YS_TRY(dev_alloc(m, (void**)&m->det_rows, (size_t)B * k * (6 + (seg ? m->nm : 0)) * 4));
   YS_TRY(dev_alloc(m, (void**)&m->det_anchor, (size_t)B * k * 8));
   YS_TRY(dev_alloc(m, &m->det_ws, ys_e2e_topk_ws_bytes(B, m->d.nc, m->A, m->max_det)));
-  // the towers' BatchNorm state: the tail of `state` (the head's units are the last of `convs`)
-  long s0 = m->n_state;
-  for (size_t i = (size_t)m->head_conv0; i < m->convs.size(); i++) if (m->convs[i].bn) s0 = std::min(s0, m->convs[i].rm_off);
-  for (int i = 0; i < m->head_conv0; i++)
-    if (m->convs[i].bn && m->convs[i].rm_off >= s0) { ys_set_error("ys_model_one2one_init: internal: the towers' statistics are not the tail of the state"); return YS_ERR_STATE; }
-  m->hstate0 = s0; m->n_hstate = m->n_state - s0;
+  // the towers' BatchNorm state as contiguous runs of `state`.  A Detect head's units are the last of `convs` and their state is the tail of `state`: one
+  // run.  In a Segment head Proto's units sit between cv3 and cv4; Proto runs once per forward (Head.cs:283-307), so its words are in no run.
+  std::vector<std::pair<long, long>> iv;        // [begin, end) words of every tower unit
+  for (size_t i = (size_t)m->head_conv0; i < m->convs.size(); i++) {
+    const ConvL& c = m->convs[i];
+    if (!c.bn || c.proto) continue;
+    iv.push_back({c.rm_off, c.rm_off + c.cout}); iv.push_back({c.rv_off, c.rv_off + c.cout}); iv.push_back({c.nbt_off, c.nbt_off + 1});
+  }
+  std::sort(iv.begin(), iv.end());
+  m->n_hstate_rng = 0; m->n_hstate = 0;
+  for (auto& v : iv) {
+    if (m->n_hstate_rng > 0 && m->hstate_rng[m->n_hstate_rng - 1].off + m->hstate_rng[m->n_hstate_rng - 1].count == v.first) { m->hstate_rng[m->n_hstate_rng - 1].count += v.second - v.first; }
+    else {
+      if (m->n_hstate_rng == 4) { ys_set_error("ys_model_e2e_init: internal: the towers' statistics lie in more than 4 runs of the state"); return YS_ERR_STATE; }
+      m->hstate_rng[m->n_hstate_rng++] = ys_model::Range{v.first, v.second - v.first};
+    }
+    m->n_hstate += v.second - v.first;
+  }
+  for (int i = 0; i < (int)m->convs.size(); i++) {          // no other unit's state inside a run
+    const ConvL& c = m->convs[i];
+    if (!c.bn || (i >= m->head_conv0 && !c.proto)) continue;
+    for (int r = 0; r < m->n_hstate_rng; r++)
+      if (c.rm_off < m->hstate_rng[r].off + m->hstate_rng[r].count && c.nbt_off >= m->hstate_rng[r].off) { ys_set_error("ys_model_e2e_init: internal: %s lies inside the towers' statistics", c.name.c_str()); return YS_ERR_STATE; }
+  }
   if (m->n_hstate > 0) {
     std::vector<unsigned char> isc((size_t)m->n_hstate, 0);
-    for (size_t i = (size_t)m->head_conv0; i < m->convs.size(); i++) if (m->convs[i].bn) isc[(size_t)(m->convs[i].nbt_off - s0)] = 1;
+    long so = 0;
+    for (int r = 0; r < m->n_hstate_rng; r++) {
+      for (size_t i = (size_t)m->head_conv0; i < m->convs.size(); i++) {
+        const ConvL& c = m->convs[i];
+        if (c.bn && !c.proto && c.nbt_off >= m->hstate_rng[r].off && c.nbt_off < m->hstate_rng[r].off + m->hstate_rng[r].count) isc[(size_t)(so + c.nbt_off - m->hstate_rng[r].off)] = 1;
+      }
+      so += m->hstate_rng[r].count;
+    }
     YS_TRY(dev_alloc(m, (void**)&m->hstate_snap, (size_t)m->n_hstate * 4));
     YS_TRY(dev_alloc(m, (void**)&m->hstate_count, (size_t)m->n_hstate));
     YS_CHECK_HIP(hipMemcpyAsync(m->hstate_count, isc.data(), isc.size(), hipMemcpyHostToDevice, m->ctx->stream));
     YS_CHECK_HIP(hipStreamSynchronize(m->ctx->stream));
   }
-  m->e2e = true;
-  m->have_fwd = false; m->have_loss = false;      // "pred" changes its box format: a forward from before the switch is not an End2End one
+  m->e2e = true; m->e2e_seg = seg;
+  m->have_fwd = false; m->have_loss = false; m->have_seg_loss = false;      // "pred" changes its box format: a forward from before the switch is not an End2End one
+  return YS_OK;
+}
+
+int ys_model_one2one_init(ys_model* m, int max_det) {
+  YS_REQUIRE(m, "ys_model_one2one_init: null model");
+  YS_REQUIRE(max_det >= 0, "ys_model_one2one_init: max_det = %d", max_det);
+  if (m->is_block || m->is_head || m->cls || m->d.task != YS_DETECT || m->pd_buf < 0) {
+    ys_set_error("ys_model_one2one_init: End2End through this entry is built for full Detect models (Segment models: ys_model_e2e_init; OBB / Pose End2End and the standalone heads are follow-ups)");
+    return YS_ERR_UNSUPPORTED;
+  }
+  if (m->e2e) { ys_set_error("ys_model_one2one_init: already initialised"); return YS_ERR_STATE; }
+  return e2e_init_impl(m, max_det, false);
+}
+
+// One2one_Init for Detect AND Segment models (Models/Segmenter.cs:17-24; Segment.one2one_init, Head.cs:245-357: cv2, cv3 and cv4 aliased).  epochs:
+// the length of E2ESegmentLoss's gain schedule (Loss.cs:1192-1210); ignored by Detect models, whose criterion is unweighted.
+int ys_model_e2e_init(ys_model* m, int max_det, int epochs) {
+  YS_REQUIRE(m, "ys_model_e2e_init: null model");
+  YS_REQUIRE(max_det >= 0 && epochs >= 0, "ys_model_e2e_init: max_det = %d, epochs = %d", max_det, epochs);
+  const bool det = !m->is_block && !m->is_head && !m->cls && m->d.task == YS_DETECT && m->pd_buf >= 0;
+  const bool seg = !m->is_block && !m->is_head && !m->cls && m->d.task == YS_SEGMENT && m->segment && m->pd_buf >= 0 && m->mc_buf >= 0;
+  if (!det && !seg) {
+    ys_set_error("ys_model_e2e_init: End2End is built for full Detect and Segment models (OBB / Pose End2End and the standalone heads are follow-ups)");
+    return YS_ERR_UNSUPPORTED;
+  }
+  if (m->e2e) { ys_set_error("ys_model_e2e_init: already initialised"); return YS_ERR_STATE; }
+  YS_TRY(e2e_init_impl(m, max_det, seg));
+  if (seg) { m->e2e_epochs = epochs > 0 ? epochs : 100; m->e2e_updates = 0; m->o2m = 0.8f; m->o2o = 1.0f - 0.8f; }   // Loss.cs:1197-1207
+  return YS_OK;
+}
+
+// E2ESegmentLoss.update() (Loss.cs:1225-1235).  The reference's training loop calls update() for E2EOBBLoss only (YoloBaseTaskModel.cs:350-353), so a
+// Segment run of the reference keeps 0.8 / 0.2 for its whole life; callers that want the schedule call this once per epoch.
+int ys_model_e2e_update(ys_model* m) {
+  YS_REQUIRE(m, "ys_model_e2e_update: null model");
+  YS_REQUIRE(m->e2e, "ys_model_e2e_update: not an End2End model (ys_model_e2e_init)");
+  if (!m->e2e_seg) return YS_OK;                 // E2EDetectLoss has no gains
+  m->e2e_updates += 1;
+  const int den = m->e2e_epochs - 1 > 1 ? m->e2e_epochs - 1 : 1;
+  const float r = 1.0f - (float)m->e2e_updates / (float)den;
+  m->o2m = (r > 0.f ? r : 0.f) * (0.8f - 0.1f) + 0.1f;
+  const float o = 1.0f - m->o2m;
+  m->o2o = o > 0.f ? o : 0.f;
+  return YS_OK;
+}
+
+int ys_model_e2e_gains(ys_model* m, float* o2m, float* o2o) {
+  YS_REQUIRE(m && o2m && o2o, "ys_model_e2e_gains: null argument");
+  YS_REQUIRE(m->e2e, "ys_model_e2e_gains: not an End2End model (ys_model_e2e_init)");
+  *o2m = m->o2m; *o2o = m->o2o;
   return YS_OK;
 }
 
 int ys_model_det_device(ys_model* m, float** rows, int* k) {
   YS_REQUIRE(m && rows && k, "ys_model_det_device: null argument");
-  YS_REQUIRE(m->e2e, "ys_model_det_device: not an End2End model (ys_model_one2one_init)");
+  YS_REQUIRE(m->e2e, "ys_model_det_device: not an End2End model (ys_model_one2one_init / ys_model_e2e_init)");
   *rows = m->det_rows; *k = std::min(m->max_det, m->A);
   return YS_OK;
 }
@@ -2719,6 +2833,7 @@ static int loss_detect_core(ys_model* m, const float* batch_idx, const float* cl
   YS_REQUIRE(!m->cls, "ys_loss_detect: a classify model's criterion is ys_loss_classify (Loss.cs:1073-1091)");
   YS_REQUIRE(m->xkind != 2 || aux_follows, "ys_loss_detect: an OBB model's criterion is ys_loss_obb (oriented labels, Loss.cs:486-684)");
   YS_REQUIRE(m->xkind != 3 || aux_follows, "ys_loss_detect: a Pose model's criterion is ys_loss_pose (keypoint terms, Loss.cs:870-1071)");
+  YS_REQUIRE(!m->e2e_seg || aux_follows, "ys_loss_detect: an End2End Segment model's criterion is ys_loss_segment (E2ESegmentLoss: two detect passes and two mask terms, Loss.cs:1179-1236)");
   const bool rot = m->xkind == 2;
   const size_t lbytes = rot ? 20 : 16;
   YS_REQUIRE(n >= 0, "ys_loss_detect: n_labels = %d", n);
@@ -2756,12 +2871,16 @@ static int loss_detect_core(ys_model* m, const float* batch_idx, const float* cl
   a.mpos = m->mpos; a.pos_align = m->pos_align; a.pos_ov = m->pos_ov; a.fg_gt = m->fg_gt; a.tnorm = m->tnorm;
   a.partial = m->loss_partial; a.scalars = m->scalars;
   a.hyp_box = 7.5f; a.hyp_cls = 0.5f; a.hyp_dfl = 1.5f; a.topk = 10;   // Loss.cs:344,357
+  // E2ESegmentLoss (Loss.cs:1222): loss = o2m * L_one2many + o2o * L_one2one.  Items and gradients are linear in the hyp_* factors, so the gain rides on
+  // them: no scale pass over any buffer
+  if (m->e2e_seg) { a.hyp_box *= m->o2m; a.hyp_cls *= m->o2m; a.hyp_dfl *= m->o2m; }
   if (rot) {                                                             // Loss.cs:489: hyp_angle = 1
     const Buf& ab = m->bufs[m->mc_buf];
     a.rot = 1; a.pa = ab.act; a.dpa = ab.grad; a.ld_pa = m->ld_mc; a.hyp_angle = 1.0f;
   }
   YS_TRY(ys_loss_detect_launch(st, m->dtype, a));
-  if (m->e2e) {
+  if (m->e2e_seg) m->seg_pass2 = a;        // ys_loss_segment runs the mask term on this assignment first, then the second pass
+  if (m->e2e && !m->e2e_seg) {
     // E2EDetectLoss (Loss.cs:1094-1118): v8DetectionLoss(tal_topk 10) on one2many + v8DetectionLoss(tal_topk 1) on one2one, unweighted.
     // The one2one head outputs ARE the one2many ones (aliased towers, same input values), so the second pass reads the same pd / ps and
     // differs only in the assigner's topk.  It reuses the first pass's assignment workspaces: the stream is in order, and nothing after
@@ -2781,6 +2900,7 @@ static int add_o2o_items(ys_model* m, float h[16]) {
   YS_CHECK_HIP(hipMemcpyAsync(g, m->scalars2, sizeof(g), hipMemcpyDeviceToHost, m->ctx->stream));
   YS_CHECK_HIP(hipStreamSynchronize(m->ctx->stream));
   for (int i = 1; i <= 4; i++) h[i] += g[i];
+  if (m->e2e_seg) h[8] += g[8];            // the mask term (both already carry their gain)
   return YS_OK;
 }
 
@@ -2790,7 +2910,7 @@ int ys_loss_segment(ys_model* m, const float* batch_idx, const float* cls, const
                     int crop_mode) {
   YS_REQUIRE(m && m->segment, "ys_loss_segment: model has no Segment head");
   YS_REQUIRE(masks, "ys_loss_segment: null masks");
-  YS_TRY(ys_loss_detect(m, batch_idx, cls, bboxes, n, on_device));
+  YS_TRY(loss_detect_core(m, batch_idx, cls, bboxes, n, on_device, true));
   m->have_loss = false;
   hipStream_t st = m->ctx->stream;
   const float* mk = masks;
@@ -2803,7 +2923,19 @@ int ys_loss_segment(ys_model* m, const float* batch_idx, const float* cls, const
   const Buf& pr = m->bufs[m->pr_buf];
   YS_TRY(ys_loss_segment_launch(st, m->dtype, mc.act, mc.grad, m->ld_mc, pr.act, pr.grad, m->ld_pr, mk, m->fg_gt, m->gt_box, m->seg_cnt,
                                 m->seg_off, m->seg_list, m->seg_ent, m->seg_part, m->scalars, m->B, m->A, m->nm, m->mh, m->mw, m->gcap,
-                                m->d.height, m->d.width, crop_mode));
+                                m->d.height, m->d.width, crop_mode, m->e2e_seg ? m->o2m : 1.0f));
+  if (m->e2e_seg) {
+    // E2ESegmentLoss (Loss.cs:1179-1236): the one2one criterion = v8SegmentationLoss(tal_topk 7, tal_topk2 1) on the same head outputs (aliased towers).
+    // The mask term above has read the first assignment (fg_gt, gt_box, seg_*); the second detect pass may now overwrite those workspaces.  Its gradients
+    // and scalars have buffers of their own; its mask term writes the one2one coefficient gradient and NO prototype gradient (proto.detach(), Head.cs:297).
+    LossArgs a = m->seg_pass2;
+    a.topk = 7; a.topk2 = 1; a.dpd = m->o2o_dpd; a.dps = m->o2o_dps; a.scalars = m->scalars2;
+    a.hyp_box = 7.5f * m->o2o; a.hyp_cls = 0.5f * m->o2o; a.hyp_dfl = 1.5f * m->o2o;
+    YS_TRY(ys_loss_detect_launch(st, m->dtype, a));
+    YS_TRY(ys_loss_segment_launch(st, m->dtype, mc.act, m->o2o_dmc, m->ld_mc, pr.act, nullptr, m->ld_pr, mk, m->fg_gt, m->gt_box, m->seg_cnt,
+                                  m->seg_off, m->seg_list, m->seg_ent, m->seg_part, m->scalars2, m->B, m->A, m->nm, m->mh, m->mw, m->gcap,
+                                  m->d.height, m->d.width, crop_mode, m->o2o));
+  }
   YS_CHECK_HIP(hipGetLastError());
   m->have_loss = true; m->have_seg_loss = true;
   return YS_OK;

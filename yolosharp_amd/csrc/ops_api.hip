@@ -481,45 +481,90 @@ extern "C" int ys_dwconv3x3_bwd(ys_ctx* ctx, int dtype, const float* x, int B, i
 
 // ---- End2End post-process (e2e.hip): Detect.postprocess / get_topk_index (Modules/Head.cs:117-127, 175-196) on a [B, 4+nc, A] tensor and the
 //      thresholding of Ops.non_max_suppression(end2end: true) (Utils/Ops.cs:258-267)
-extern "C" int ys_e2e_topk(ys_ctx* ctx, const float* pred, int on_device, int batch, int nc, int anchors, int max_det, float* out_rows,
-                           int64_t* out_anchor) {
-  YS_REQUIRE(ctx && pred && out_rows && out_anchor, "ys_e2e_topk: null argument");
-  YS_REQUIRE(batch > 0 && nc > 0 && anchors > 0 && max_det > 0, "ys_e2e_topk: bad shape B=%d nc=%d A=%d max_det=%d", batch, nc, anchors, max_det);
+static int e2e_topk_impl(const char* fn, ys_ctx* ctx, const float* pred, int on_device, int batch, int nc, int extra, int anchors, int max_det, float* out_rows,
+                         int64_t* out_anchor) {
+  YS_REQUIRE(ctx && pred && out_rows && out_anchor, "%s: null argument", fn);
+  YS_REQUIRE(batch > 0 && nc > 0 && extra >= 0 && anchors > 0 && max_det > 0, "%s: bad shape B=%d nc=%d extra=%d A=%d max_det=%d", fn, batch, nc, extra, anchors, max_det);
   YS_CHECK_HIP(hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
   const size_t k = (size_t)(max_det < anchors ? max_det : anchors);
-  const size_t n_pred = (size_t)batch * (4 + nc) * anchors, n_rows = (size_t)batch * k * 6, n_anc = (size_t)batch * k;
+  const size_t n_pred = (size_t)batch * (4 + nc + extra) * anchors, n_rows = (size_t)batch * k * (6 + extra), n_anc = (size_t)batch * k;
   DevBuf dp, dr, da;
   const size_t need = ys_e2e_topk_ws_bytes(batch, nc, anchors, max_det);
   if (need > ctx->e2e_ws_bytes) {               // the context keeps the workspace (like the NMS one): device-resident calls stay asynchronous
     if (ctx->e2e_ws) { YS_CHECK_HIP(hipStreamSynchronize(st)); YS_CHECK_HIP(hipFree(ctx->e2e_ws)); ctx->e2e_ws = nullptr; ctx->e2e_ws_bytes = 0; }
-    if (hipMalloc(&ctx->e2e_ws, need) != hipSuccess) { ys_set_error("ys_e2e_topk: out of device memory (%zu bytes)", need); return YS_ERR_OOM; }
+    if (hipMalloc(&ctx->e2e_ws, need) != hipSuccess) { ys_set_error("%s: out of device memory (%zu bytes)", fn, need); return YS_ERR_OOM; }
     ctx->e2e_ws_bytes = need;
   }
   YsTimer timer(ctx, "e2e_topk");
-  if (on_device) return ys_e2e_topk_launch(st, pred, batch, nc, anchors, max_det, ctx->e2e_ws, out_rows, (long long*)out_anchor);
+  if (on_device) return ys_e2e_topk_launch(st, pred, batch, nc, anchors, max_det, ctx->e2e_ws, out_rows, (long long*)out_anchor, extra);
   YS_TRY(dp.alloc(n_pred * 4)); YS_TRY(dr.alloc(n_rows * 4)); YS_TRY(da.alloc(n_anc * 8));
   YS_CHECK_HIP(hipMemcpyAsync(dp.p, pred, n_pred * 4, hipMemcpyHostToDevice, st));
-  YS_TRY(ys_e2e_topk_launch(st, (const float*)dp.p, batch, nc, anchors, max_det, ctx->e2e_ws, (float*)dr.p, (long long*)da.p));
+  YS_TRY(ys_e2e_topk_launch(st, (const float*)dp.p, batch, nc, anchors, max_det, ctx->e2e_ws, (float*)dr.p, (long long*)da.p, extra));
   YS_CHECK_HIP(hipMemcpyAsync(out_rows, dr.p, n_rows * 4, hipMemcpyDeviceToHost, st));
   YS_CHECK_HIP(hipMemcpyAsync(out_anchor, da.p, n_anc * 8, hipMemcpyDeviceToHost, st));
   YS_CHECK_HIP(hipStreamSynchronize(st));
   return YS_OK;
 }
 
-extern "C" int ys_e2e_select(ys_ctx* ctx, const float* rows, int on_device, int batch, int k, float conf_thres, int max_det, int32_t* out_count) {
-  YS_REQUIRE(ctx && rows && out_count, "ys_e2e_select: null argument");
+extern "C" int ys_e2e_topk(ys_ctx* ctx, const float* pred, int on_device, int batch, int nc, int anchors, int max_det, float* out_rows,
+                           int64_t* out_anchor) {
+  return e2e_topk_impl("ys_e2e_topk", ctx, pred, on_device, batch, nc, 0, anchors, max_det, out_rows, out_anchor);
+}
+
+extern "C" int ys_e2e_topk_ex(ys_ctx* ctx, const float* pred, int on_device, int batch, int nc, int extra, int anchors, int max_det, float* out_rows,
+                              int64_t* out_anchor) {
+  return e2e_topk_impl("ys_e2e_topk_ex", ctx, pred, on_device, batch, nc, extra, anchors, max_det, out_rows, out_anchor);
+}
+
+static int e2e_select_impl(const char* fn, ys_ctx* ctx, const float* rows, int on_device, int batch, int k, int row_len, float conf_thres, int max_det, int32_t* out_count) {
+  YS_REQUIRE(ctx && rows && out_count, "%s: null argument", fn);
   // Ops.cs:248-251: ArgumentException for a threshold outside [0,1]
   YS_REQUIRE(conf_thres >= 0.f && conf_thres <= 1.f, "Invalid Confidence threshold %g, valid values are between 0.0 and 1.0", conf_thres);
-  YS_REQUIRE(batch > 0 && k > 0 && max_det > 0, "ys_e2e_select: bad shape B=%d k=%d max_det=%d", batch, k, max_det);
+  YS_REQUIRE(batch > 0 && k > 0 && max_det > 0 && row_len >= 6, "%s: bad shape B=%d k=%d max_det=%d row length %d", fn, batch, k, max_det, row_len);
   YS_CHECK_HIP(hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
-  if (on_device) return ys_e2e_select_launch(st, rows, batch, k, conf_thres, max_det, out_count);
+  if (on_device) return ys_e2e_select_launch(st, rows, batch, k, conf_thres, max_det, out_count, row_len);
   DevBuf dr, dc;
-  YS_TRY(dr.alloc((size_t)batch * k * 6 * 4)); YS_TRY(dc.alloc((size_t)batch * 4));
-  YS_CHECK_HIP(hipMemcpyAsync(dr.p, rows, (size_t)batch * k * 6 * 4, hipMemcpyHostToDevice, st));
-  YS_TRY(ys_e2e_select_launch(st, (const float*)dr.p, batch, k, conf_thres, max_det, (int*)dc.p));
+  const size_t nb = (size_t)batch * k * row_len * 4;
+  YS_TRY(dr.alloc(nb)); YS_TRY(dc.alloc((size_t)batch * 4));
+  YS_CHECK_HIP(hipMemcpyAsync(dr.p, rows, nb, hipMemcpyHostToDevice, st));
+  YS_TRY(ys_e2e_select_launch(st, (const float*)dr.p, batch, k, conf_thres, max_det, (int*)dc.p, row_len));
   YS_CHECK_HIP(hipMemcpyAsync(out_count, dc.p, (size_t)batch * 4, hipMemcpyDeviceToHost, st));
+  YS_CHECK_HIP(hipStreamSynchronize(st));
+  return YS_OK;
+}
+
+extern "C" int ys_e2e_select(ys_ctx* ctx, const float* rows, int on_device, int batch, int k, float conf_thres, int max_det, int32_t* out_count) {
+  return e2e_select_impl("ys_e2e_select", ctx, rows, on_device, batch, k, 6, conf_thres, max_det, out_count);
+}
+
+extern "C" int ys_e2e_select_ex(ys_ctx* ctx, const float* rows, int on_device, int batch, int k, int row_len, float conf_thres, int max_det, int32_t* out_count) {
+  return e2e_select_impl("ys_e2e_select_ex", ctx, rows, on_device, batch, k, row_len, conf_thres, max_det, out_count);
+}
+
+// ---- the assigner's second stage on its own (loss.hip tal_keep_best_kernel, the kernel the End2End Segment criterion runs; Utils/Tal.cs:242-250)
+extern "C" int ys_tal_keep_best(ys_ctx* ctx, const float* align, uint8_t* mask_pos, const int32_t* gt_count, int on_device, int batch, int boxes, int anchors) {
+  YS_REQUIRE(ctx && align && mask_pos && gt_count, "ys_tal_keep_best: null argument");
+  YS_REQUIRE(batch > 0 && boxes > 0 && anchors > 0, "ys_tal_keep_best: bad shape B=%d G=%d A=%d", batch, boxes, anchors);
+  YS_CHECK_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  const size_t n = (size_t)batch * boxes * anchors;
+  TalKeepArgs k{};
+  k.B = batch; k.G = boxes; k.A = anchors;
+  if (on_device) {      // the caller vouches for 0 <= gt_count[b] <= boxes
+    k.align = align; k.mpos = mask_pos; k.gt_count = gt_count;
+    return ys_tal_keep_best_launch(st, k);
+  }
+  for (int b = 0; b < batch; b++) YS_REQUIRE(gt_count[b] >= 0 && gt_count[b] <= boxes, "ys_tal_keep_best: gt_count[%d] = %d outside [0, %d]", b, gt_count[b], boxes);
+  DevBuf da, dm, dc;
+  YS_TRY(da.alloc(n * 4)); YS_TRY(dm.alloc(n)); YS_TRY(dc.alloc((size_t)batch * 4));
+  YS_CHECK_HIP(hipMemcpyAsync(da.p, align, n * 4, hipMemcpyHostToDevice, st));
+  YS_CHECK_HIP(hipMemcpyAsync(dm.p, mask_pos, n, hipMemcpyHostToDevice, st));
+  YS_CHECK_HIP(hipMemcpyAsync(dc.p, gt_count, (size_t)batch * 4, hipMemcpyHostToDevice, st));
+  k.align = (const float*)da.p; k.mpos = (unsigned char*)dm.p; k.gt_count = (const int*)dc.p;
+  YS_TRY(ys_tal_keep_best_launch(st, k));
+  YS_CHECK_HIP(hipMemcpyAsync(mask_pos, dm.p, n, hipMemcpyDeviceToHost, st));
   YS_CHECK_HIP(hipStreamSynchronize(st));
   return YS_OK;
 }

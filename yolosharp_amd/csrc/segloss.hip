@@ -9,6 +9,8 @@
 // integer-truncation branch (Ops.cs:421-435) is selectable with `trunc_crop` for CPU-parity runs.
 // Gradients w.r.t. the mask coefficients and the prototypes are produced analytically (two deterministic passes,
 // fixed-order reductions, no atomics).  The detection part (box/cls/dfl + assignment) is loss.hip and runs first.
+// E2ESegmentLoss (Loss.cs:1179-1236) calls the term twice per step, once per assignment: `gain` (o2m / o2o) multiplies hyp_box, and the
+// one2one call passes no prototype gradient buffer (one2one["proto"] = proto.detach(), Head.cs:297), which skips pass 2.
 #include "ys_internal.h"
 #include "ys_kernels.h"
 
@@ -258,13 +260,13 @@ seg_finalize_kernel(SegArgs a) {
 
 int ys_loss_segment_launch(hipStream_t st, int dtype, const void* mc, void* dmc, int ld_mc, const void* proto, void* dproto, int ld_pr,
                            const float* masks, const int* fg_gt, const float* gt_box, int* cnt, int* off, int* list, float* ent,
-                           float* part, float* scalars, int B, int A, int nm, int mh, int mw, int gcap, int H, int W, int trunc_crop) {
+                           float* part, float* scalars, int B, int A, int nm, int mh, int mw, int gcap, int H, int W, int trunc_crop, float gain) {
   if (nm > SG_NM_MAX) { ys_set_error("segment loss: nm=%d > %d", nm, SG_NM_MAX); return YS_ERR_UNSUPPORTED; }
   SegArgs a{};
   a.mc = mc; a.dmc = dmc; a.proto = proto; a.dproto = dproto; a.masks = masks; a.fg_gt = fg_gt; a.gt_box = gt_box;
   a.cnt = cnt; a.off = off; a.list = list; a.ent = ent; a.part = part; a.scalars = scalars;
   a.B = B; a.A = A; a.nm = nm; a.ld_mc = ld_mc; a.ld_pr = ld_pr; a.mh = mh; a.mw = mw; a.gcap = gcap; a.H = H; a.W = W;
-  a.trunc_crop = trunc_crop; a.hyp_box = 7.5f;
+  a.trunc_crop = trunc_crop; a.hyp_box = 7.5f * gain;   // gain 1 (every plain model): the value itself
   const size_t es = dtype == YS_BF16 ? 2 : 4;
   YS_CHECK_HIP(hipMemsetAsync(dmc, 0, (size_t)B * A * ld_mc * es, st));   // background anchors get no mask gradient
   YS_TRY(ys_fg_list_launch(st, fg_gt, B, A, cnt, off, list));
@@ -272,11 +274,11 @@ int ys_loss_segment_launch(hipStream_t st, int dtype, const void* mc, void* dmc,
   dim3 g2(ys_cdiv(mh * mw, SG_THREADS), B);
   const bool fast = nm == 32 && ld_mc % 8 == 0 && ld_pr % 8 == 0;      // Proto / Segment default (Head.cs:238): compile-time nm, 16-byte rows
   if (dtype == YS_BF16) {
-    if (fast) { YS_LAUNCH((seg_anchor_kernel<bf16_t, 32>), g1, SG_THREADS, st, a); YS_LAUNCH((seg_proto_grad_kernel<bf16_t, 32>), g2, SG_THREADS, st, a); }
-    else { YS_LAUNCH((seg_anchor_kernel<bf16_t, 0>), g1, SG_THREADS, st, a); YS_LAUNCH((seg_proto_grad_kernel<bf16_t, 0>), g2, SG_THREADS, st, a); }
+    if (fast) { YS_LAUNCH((seg_anchor_kernel<bf16_t, 32>), g1, SG_THREADS, st, a); if (dproto) YS_LAUNCH((seg_proto_grad_kernel<bf16_t, 32>), g2, SG_THREADS, st, a); }
+    else { YS_LAUNCH((seg_anchor_kernel<bf16_t, 0>), g1, SG_THREADS, st, a); if (dproto) YS_LAUNCH((seg_proto_grad_kernel<bf16_t, 0>), g2, SG_THREADS, st, a); }
   } else {
-    if (fast) { YS_LAUNCH((seg_anchor_kernel<float, 32>), g1, SG_THREADS, st, a); YS_LAUNCH((seg_proto_grad_kernel<float, 32>), g2, SG_THREADS, st, a); }
-    else { YS_LAUNCH((seg_anchor_kernel<float, 0>), g1, SG_THREADS, st, a); YS_LAUNCH((seg_proto_grad_kernel<float, 0>), g2, SG_THREADS, st, a); }
+    if (fast) { YS_LAUNCH((seg_anchor_kernel<float, 32>), g1, SG_THREADS, st, a); if (dproto) YS_LAUNCH((seg_proto_grad_kernel<float, 32>), g2, SG_THREADS, st, a); }
+    else { YS_LAUNCH((seg_anchor_kernel<float, 0>), g1, SG_THREADS, st, a); if (dproto) YS_LAUNCH((seg_proto_grad_kernel<float, 0>), g2, SG_THREADS, st, a); }
   }
   YS_LAUNCH(seg_finalize_kernel, 1, SG_THREADS, st, a);
   return YS_OK;

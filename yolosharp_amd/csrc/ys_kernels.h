@@ -322,6 +322,7 @@ struct LossArgs {
   float* scalars;      // [8]: tss, loss_box, loss_cls, loss_dfl, total
   float hyp_box, hyp_cls, hyp_dfl;
   int topk;
+  int topk2;           // 0 = off; 1 = the assigner's second stage (Tal.cs:242-250): every box keeps its single best positive
   // v8OBBLoss (Loss.cs:486-684): rot = 1 -> labels carry (cx, cy, w, h, angle), gt_box / pbox rows are 5 floats (xywh + angle),
   // the assigner uses probiou and the rotated in-box test, the box term is 1 - probiou, plus the angle term (scalars[12..13])
   int rot;
@@ -331,6 +332,14 @@ struct LossArgs {
   float hyp_angle;
 };
 int ys_loss_detect_launch(hipStream_t st, int dtype, const LossArgs& a);
+// second assigner stage (tal_topk2 = 1, Tal.cs:242-250) over align / mpos [B][G][A], rows [0, gt_count[b]) of every image; ov / pos_align /
+// pos_ov / fg_gt may be null (the stand-alone op): then only the mask is pruned
+struct TalKeepArgs {
+  const float* align; unsigned char* mpos; const int* gt_count;
+  const float* ov; unsigned* pos_align; unsigned* pos_ov; int* fg_gt;
+  int B, G, A;
+};
+int ys_tal_keep_best_launch(hipStream_t st, const TalKeepArgs& k);
 size_t ys_loss_partial_floats(int B, int A);
 
 // ---- decode (Head.cs:204-223)
@@ -346,7 +355,9 @@ int ys_unpack_nchw_strided_launch(hipStream_t st, int dtype, const void* x, int 
 // ---- segloss.hip
 int ys_loss_segment_launch(hipStream_t st, int dtype, const void* mc, void* dmc, int ld_mc, const void* proto, void* dproto, int ld_pr,
                            const float* masks, const int* fg_gt, const float* gt_box, int* cnt, int* off, int* list, float* ent,
-                           float* part, float* scalars, int B, int A, int nm, int mh, int mw, int gcap, int H, int W, int trunc_crop);
+                           float* part, float* scalars, int B, int A, int nm, int mh, int mw, int gcap, int H, int W, int trunc_crop, float gain = 1.0f);
+// dproto == nullptr: no prototype gradient (the one2one branch of E2ESegmentLoss reads proto.detach(), Head.cs:297); gain multiplies the
+// term's item and gradients (E2ESegmentLoss's o2m / o2o, Loss.cs:1214-1222)
 // foreground anchors of the last assignment, ordered by image then anchor: cnt [B], off [B+1], list [off[B]]
 int ys_fg_list_launch(hipStream_t st, const int* fg_gt, int B, int A, int* cnt, int* off, int* list);
 // ---- poseloss.hip: keypoint terms of v8PoseLoss (Loss.cs:870-1071) after ys_loss_detect_launch
@@ -381,10 +392,11 @@ int ys_cls_xent_launch(hipStream_t st, int dtype, const void* logits, int ld, in
                        float* probs, float* row_loss, float* scalars);
 int ys_cls_topk_launch(hipStream_t st, const float* x, int rows, int cols, int k, int32_t* idx);
 // ---- e2e.hip: End2End post-process (Head.cs:117-127, 175-196; Ops.cs:258-267) and the aliased towers' second BatchNorm update
-// ws: ys_e2e_topk_ws_bytes(B, nc, A, max_det) bytes; rows [B][k][6], anchors [B][k], k = min(max_det, A)
+// ws: ys_e2e_topk_ws_bytes(B, nc, A, max_det) bytes; pred [B][4+nc+extra][A]; rows [B][k][6+extra] (the `extra` trailing channels of the
+// selected anchor follow the class: Segment's mask coefficients), anchors [B][k], k = min(max_det, A); select: rows of row_len floats
 size_t ys_e2e_topk_ws_bytes(int B, int nc, int A, int max_det);
-int ys_e2e_topk_launch(hipStream_t st, const float* pred, int B, int nc, int A, int max_det, void* ws, float* rows, long long* anchors);
-int ys_e2e_select_launch(hipStream_t st, const float* rows, int B, int k, float conf, int max_det, int* count);
+int ys_e2e_topk_launch(hipStream_t st, const float* pred, int B, int nc, int A, int max_det, void* ws, float* rows, long long* anchors, int extra = 0);
+int ys_e2e_select_launch(hipStream_t st, const float* rows, int B, int k, float conf, int max_det, int* count, int row_len = 6);
 int ys_e2e_bn_second_update_launch(hipStream_t st, float* state, const float* snap, const unsigned char* is_count, long n, float momentum);
 int ys_process_mask_launch(hipStream_t st, const float* protos, const float* masks_in, const float* boxes, int n, int nm, int mh,
                            int mw, int ih, int iw, int upsample, int trunc_crop, unsigned char* out);

@@ -138,7 +138,8 @@ class Segmenter(Detector):
     """Models/Segmenter.cs:28-84: ImagePredict with instance masks -- eval forward (pred carries the 32 mask coefficients
     per anchor), NMS (the coefficients ride along as extra columns), Ops.process_mask on the device with upsample=True, boxes
     clipped to the original image and masks cropped to it (the padded region is bottom / right, so the resize of
-    Segmenter.cs:56-57 is an identity crop here)."""
+    Segmenter.cs:56-57 is an identity crop here).  On an End2End model (model.e2e_init; Segmenter.cs:17-24, 44-57) the head's own top-k rows
+    [B, k, 6+32] are only thresholded (Ops.cs:258-267, ys_e2e_select_ex) and the kept prefix feeds the same process_mask / mask_iou path."""
 
     def ImagePredict(self, image_chw_u8, predict_threshold=0.25, iou_threshold=0.5):
         img = np.asarray(image_chw_u8)
@@ -146,7 +147,7 @@ class Segmenter(Detector):
         self.model.eval()
         inference, preds = self.model.forward_u8(np.ascontiguousarray(img, np.uint8)[None])
         proto = self.model.get_output("proto")[0]
-        output, _ = self.engine.non_max_suppression(inference["boxes"], predict_threshold, iou_threshold, nc=self.model.nc)
+        output, _ = self.engine.non_max_suppression(inference["boxes"], predict_threshold, iou_threshold, nc=self.model.nc, end2end=self.end2end)
         rows = output[0]
         results = []
         if len(rows):
@@ -179,7 +180,7 @@ class Segmenter(Detector):
             loss_sum = items if loss_sum is None else loss_sum + items
             proto = self.model.get_output("proto")
             mh, mw = proto.shape[2:]
-            output, _ = self.engine.non_max_suppression(inference["boxes"], conf_thres, iou_thres, max_det=max_det, nc=nc)
+            output, _ = self.engine.non_max_suppression(inference["boxes"], conf_thres, iou_thres, max_det=max_det, nc=nc, end2end=self.end2end)
             bi = np.asarray(data["batch_idx"], np.float32).reshape(-1)
             cl = np.asarray(data["cls"], np.float32).reshape(-1)
             bb = np.asarray(data["bboxes"], np.float32).reshape(-1, 4)

@@ -159,25 +159,44 @@ class Engine:
         return out
 
     # ---- End2End post-process (Head.cs:117-127, 175-196; Ops.cs:258-267)
-    def e2e_topk(self, pred, max_det=300):
-        """Detect.postprocess on pred [B, 4+nc, A] fp32: (rows [B, k, 6] = (box, score, class) ordered by score, anchor [B, k] int64),
-        k = min(max_det, A); equal scores keep the lower index first (include/yolosharp_hip.h ys_e2e_topk)."""
+    def e2e_topk(self, pred, max_det=300, extra=0):
+        """Detect.postprocess on pred [B, 4+nc+extra, A] fp32: (rows [B, k, 6+extra] = (box, score, class, the anchor's `extra` trailing channels)
+        ordered by score, anchor [B, k] int64), k = min(max_det, A); equal scores keep the lower index first (include/yolosharp_hip.h ys_e2e_topk /
+        ys_e2e_topk_ex).  extra = nm is Segment.postprocess (Head.cs:321-339)."""
         p = np.ascontiguousarray(pred, np.float32)
         B, Cc, A = p.shape
+        extra = int(extra)
         k = min(int(max_det), A)
-        rows = np.zeros((B, k, 6), np.float32)
+        rows = np.zeros((B, k, 6 + extra), np.float32)
         anchor = np.zeros((B, k), np.int64)
-        _lib.check(self.lib, self.lib.ys_e2e_topk(self.ctx, _ptr(p), 0, B, Cc - 4, A, int(max_det), _ptr(rows), _ptr(anchor)))
+        if extra:
+            _lib.check(self.lib, self.lib.ys_e2e_topk_ex(self.ctx, _ptr(p), 0, B, Cc - 4 - extra, extra, A, int(max_det), _ptr(rows), _ptr(anchor)))
+        else:
+            _lib.check(self.lib, self.lib.ys_e2e_topk(self.ctx, _ptr(p), 0, B, Cc - 4, A, int(max_det), _ptr(rows), _ptr(anchor)))
         return rows, anchor
 
     def e2e_select(self, rows, conf_thres=0.25, max_det=300):
-        """non_max_suppression(end2end: true): the number of leading rows of rows [B, k, 6] with score > conf_thres, at most max_det -> int32 [B]."""
+        """non_max_suppression(end2end: true): the number of leading rows of rows [B, k, 6 (+ extra)] with score > conf_thres, at most max_det -> int32 [B]."""
         r = np.ascontiguousarray(rows, np.float32)
-        B, k, six = r.shape
-        assert six == 6, r.shape
+        B, k, rl = r.shape
+        assert rl >= 6, r.shape
         cnt = np.zeros((B,), np.int32)
-        _lib.check(self.lib, self.lib.ys_e2e_select(self.ctx, _ptr(r), 0, B, k, float(conf_thres), int(max_det), _ptr(cnt)))
+        if rl == 6:
+            _lib.check(self.lib, self.lib.ys_e2e_select(self.ctx, _ptr(r), 0, B, k, float(conf_thres), int(max_det), _ptr(cnt)))
+        else:
+            _lib.check(self.lib, self.lib.ys_e2e_select_ex(self.ctx, _ptr(r), 0, B, k, rl, float(conf_thres), int(max_det), _ptr(cnt)))
         return cnt
+
+    def tal_keep_best(self, align, mask_pos, gt_count):
+        """The assigner's second stage (tal_topk2 = 1, Tal.cs:242-250) on align [B, G, A] fp32, mask_pos [B, G, A] (bool / uint8), gt_count [B]: the
+        pruned mask as uint8 -- every row below gt_count[b] keeps only the first anchor in (align * mask_pos descending, index ascending) order."""
+        al = np.ascontiguousarray(align, np.float32)
+        mp = np.ascontiguousarray(np.asarray(mask_pos).astype(np.uint8))
+        gc = np.ascontiguousarray(gt_count, np.int32)
+        B, G, A = al.shape
+        assert mp.shape == al.shape and gc.shape == (B,), (mp.shape, gc.shape)
+        _lib.check(self.lib, self.lib.ys_tal_keep_best(self.ctx, _ptr(al), _ptr(mp), _ptr(gc), 0, B, G, A))
+        return mp
 
     # ---- validation (Detector.cs:103-120): box_iou + match_predictions per image, batched on the device
     def box_iou(self, box1, box2, eps=1e-7):
@@ -279,7 +298,7 @@ class Engine:
         `agnostic` flag is accepted but ignored (Ops.cs:345), and invalid thresholds raise (YsError status 1).
         rotated=True (Ops.cs:286,349-353): oriented boxes, angle = last channel, boxes stay xywh, Ops.nms_rotated's
         "any earlier box overlaps" rule on Metrics.batch_probiou."""
-        if end2end:        # Ops.cs:258-267: prediction [B, k, 6] rows ordered by score -> rows with score > conf_thres, at most max_det; no keep indices
+        if end2end:        # Ops.cs:258-267: prediction [B, k, 6 (+ nm)] rows ordered by score -> rows with score > conf_thres, at most max_det; no keep indices
             rows = np.ascontiguousarray(prediction, np.float32)
             cnt = self.e2e_select(rows, conf_thres, max_det)
             return [rows[b, :cnt[b]].copy() for b in range(rows.shape[0])], [np.zeros((0,), np.float32)]

@@ -66,8 +66,24 @@ class Yolov8:
         _lib.check(self.lib, self.lib.ys_model_one2one_init(self.handle, int(max_det)))
         self.end2end, self.max_det = True, int(max_det) if max_det else 300
 
+    def e2e_init(self, max_det=300, epochs=100):
+        """One2one_Init for Detect and Segment models (ys_model_e2e_init).  Segment (Segmenter.cs:17-24): cv2 / cv3 / cv4 aliased, the criterion becomes
+        E2ESegmentLoss with a gain schedule of `epochs` steps (e2e_update / e2e_gains)."""
+        _lib.check(self.lib, self.lib.ys_model_e2e_init(self.handle, int(max_det), int(epochs)))
+        self.end2end, self.max_det = True, int(max_det) if max_det else 300
+
+    def e2e_update(self):
+        """E2ESegmentLoss.update() (Loss.cs:1225-1230); nothing on a Detect End2End model."""
+        _lib.check(self.lib, self.lib.ys_model_e2e_update(self.handle))
+
+    def e2e_gains(self):
+        """(o2m, o2o): the current weights of the one2many / one2one criteria (Detect: 1, 1)."""
+        a, b = C.c_float(), C.c_float()
+        _lib.check(self.lib, self.lib.ys_model_e2e_gains(self.handle, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
     def det_device(self):
-        """Device pointer of the End2End eval output "det" [B, k, 6] and k = min(max_det, A)."""
+        """Device pointer of the End2End eval output "det" [B, k, 6] (Segment: [B, k, 6+nm]) and k = min(max_det, A)."""
         p, k = C.c_void_p(), C.c_int()
         _lib.check(self.lib, self.lib.ys_model_det_device(self.handle, C.byref(p), C.byref(k)))
         return p, k.value
@@ -177,11 +193,11 @@ class Yolov8:
         C_ = {"boxes": 4 * self.reg_max, "scores": self.nc, "pred": 4 + self.nc + self.NM, "dboxes": 4 * self.reg_max,
               "dscores": self.nc, "mask_coefficient": self.NM, "dmask_coefficient": self.NM, "angle": self.NM, "kpts": self.NM, "dkpts": self.NM, "dangle": self.NM}.get(key)
         if key.startswith("one2one_"):
-            C_ = 4 * self.reg_max if key.endswith("boxes") else self.nc
+            C_ = 4 * self.reg_max if key.endswith("boxes") else (self.NM if key.endswith("mask_coefficient") else self.nc)
         if key in ("proto", "dproto"):
             a = np.empty((B, self.NM, self.height // 4, self.width // 4), np.float32)
         elif key == "det":
-            a = np.empty((B, min(self.max_det, self.A), 6), np.float32)
+            a = np.empty((B, min(self.max_det, self.A), 6 + (self.NM if self.TASK == 1 else 0)), np.float32)
         else:
             a = np.empty((B, C_, self.A), np.float32)
         _lib.check(self.lib, self.lib.ys_model_get_output(self.handle, key.encode(), _ptr(a), a.size))
@@ -274,19 +290,30 @@ class Yolov11(Yolov8):
 
 class _SegmentMixin:
     """Head.Segment (Head.cs:238-324): preds gain "mask_coefficient" [B,32,A] and "proto" [B,32,H/4,W/4]; the eval
-    inference dict is {"boxes": [B,4+nc+32,A], "proto": ...} (Head.cs:303-313)."""
+    inference dict is {"boxes": [B,4+nc+32,A], "proto": ...} (Head.cs:303-313).
+    After e2e_init (End2End, Head.cs:283-339): preds = {"one2many": {boxes, scores, mask_coefficient, proto}, "one2one": {the same values}} and the eval
+    inference dict is {"boxes": det [B,k,6+32], "pred": [B,4+nc+32,A] with xyxy boxes, "proto"}."""
     TASK = 1
     NM = 32
+
+    def _with_masks(self, inf, preds):
+        proto = self.get_output("proto")
+        if self.end2end:
+            preds["one2many"]["mask_coefficient"] = self.get_output("mask_coefficient")
+            preds["one2one"]["mask_coefficient"] = self.get_output("one2one_mask_coefficient")
+            preds["one2many"]["proto"] = preds["one2one"]["proto"] = proto          # one2one["proto"] = proto.detach(): the same values
+        else:
+            preds["mask_coefficient"] = self.get_output("mask_coefficient")
+            preds["proto"] = proto
+        if inf is not None:
+            inf["proto"] = proto
+        return inf, preds
 
     def forward(self, x, fetch=True):
         inf, preds = Yolov8.forward(self, x, fetch)
         if not fetch:
             return inf, preds
-        preds["mask_coefficient"] = self.get_output("mask_coefficient")
-        preds["proto"] = self.get_output("proto")
-        if inf is not None:
-            inf["proto"] = preds["proto"]
-        return inf, preds
+        return self._with_masks(inf, preds)
 
     __call__ = forward
 
@@ -422,7 +449,9 @@ class v8DetectionLoss:
 class v8SegmentationLoss(v8DetectionLoss):
     """Loss.cs:688-863.  batch additionally carries "masks" [B, H/4, W/4] (overlap-encoded instance ids,
     YoloDataset.cs:265-267).  Returns (loss*B [5], loss_detach [5]) in the order box, seg, cls, dfl, semseg.
-    cpu_crop_branch selects Ops.crop_mask's CPU-only integer branch (Ops.cs:421-435) instead of the broadcast form."""
+    cpu_crop_branch selects Ops.crop_mask's CPU-only integer branch (Ops.cs:421-435) instead of the broadcast form.
+    On an End2End Segment model (model.e2e_init) the same call is E2ESegmentLoss (Loss.cs:1179-1236): the returned items are
+    o2m * items(one2many, tal_topk 10) + o2o * items(one2one, tal_topk 7, tal_topk2 1) with the model's current gains (model.e2e_gains())."""
 
     def __init__(self, model, cpu_crop_branch=False):
         super().__init__(model)
