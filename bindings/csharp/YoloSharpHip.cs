@@ -72,6 +72,11 @@ namespace YoloSharp.Native
         // End2End Segment (Segmenter.cs:17-24): One2one_Init for Detect and Segment models; ys_loss_segment is then E2ESegmentLoss (gains 0.8 / 0.2; ys_model_e2e_update =
         // E2ESegmentLoss.update(), which the reference's loop never calls for Segment); outputs "one2one_mask_coefficient" / "one2one_dmask_coefficient"; "det" rows [B,k,6+nm]
         [DllImport(Lib)] internal static extern int ys_model_e2e_init(IntPtr model, int maxDet, int epochs);
+        // End2End OBB (Obber.cs:18-24): One2one_Init for OBB models; ys_loss_obb is then E2EOBBLoss, whose update() the training loop calls after every epoch
+        // (YoloBaseTaskModel.cs:350-353) = ys_model_e2e_update; outputs "one2one_angle" / "one2one_dangle"; "det" rows [B,k,7] = (cx, cy, w, h, score, class, angle)
+        [DllImport(Lib)] internal static extern int ys_model_e2e_obb_init(IntPtr model, int maxDet, int epochs);
+        // Obber.Val's per-image part (Obber.cs:102-114) for a batch: rows [B,maxDet,rowStride] (device or host), correct [B,maxDet,10]
+        [DllImport(Lib)] internal static extern int ys_val_match_rotated_batched(IntPtr ctx, IntPtr rows, IntPtr count, int onDevice, int batch, int maxDet, int rowStride, int angleCol, IntPtr batchIdx, IntPtr cls, IntPtr bboxes, int nLabels, float imgW, float imgH, IntPtr correct);
         [DllImport(Lib)] internal static extern int ys_model_e2e_update(IntPtr model);
         [DllImport(Lib)] internal static extern int ys_model_e2e_gains(IntPtr model, out float o2m, out float o2o);
         [DllImport(Lib)] internal static extern int ys_e2e_topk_ex(IntPtr ctx, float[] pred, int onDevice, int batch, int nc, int extra, int anchors, int maxDet, [Out] float[] rows, [Out] long[] anchor);

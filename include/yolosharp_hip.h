@@ -148,7 +148,7 @@ YS_API int ys_model_reserve_labels(ys_model* m, int per_image);
  * modules as cv2 / cv3 (the reference copies references, SaveWeight drops the one2one keys), so the model gains NO tensor: ys_model_num_tensors /
  * tensor_info / num_params are unchanged and weight files move freely between End2End and plain models.  max_det: rows of the post-process
  * (0 = 300, Head.cs:13).  YS_DETECT models of both families and every dtype; Segment / OBB / Pose / Classify models and the standalone block /
- * head handles return YS_ERR_UNSUPPORTED (Segment models take ys_model_e2e_init below; OBB / Pose End2End is a follow-up).  Call it once, after ys_model_create.  From then on:
+ * head handles return YS_ERR_UNSUPPORTED (Segment models take ys_model_e2e_init, OBB models ys_model_e2e_obb_init below; Pose End2End is a follow-up).  Call it once, after ys_model_create.  From then on:
  *   training forward (Head.cs:89-106): "one2one_boxes" / "one2one_scores" are outputs (the same values as "boxes" / "scores": same modules,
  *     same input values); the BatchNorm units of the towers update their running statistics twice, num_batches_tracked += 2.
  *   ys_loss_detect = E2EDetectLoss (Utils/Loss.cs:1094-1118): v8DetectionLoss(tal_topk 10) on one2many + v8DetectionLoss(tal_topk 1) on
@@ -184,6 +184,24 @@ YS_API int ys_model_det_device(ys_model* m, float** rows, int* k);
 YS_API int ys_model_e2e_init(ys_model* m, int max_det, int epochs);
 YS_API int ys_model_e2e_update(ys_model* m);
 YS_API int ys_model_e2e_gains(ys_model* m, float* o2m, float* o2o);
+/* ---- End2End for OBB models (Models/Obber.cs:18-24; Obb.one2one_init, Modules/Head.cs:454-469; E2EOBBLoss, Utils/Loss.cs:1120-1177).
+ * One2one_Init for YS_OBB models of both families and every dtype.  max_det 0 = 300; epochs 0 = 100.  Every other task, a block handle or a head handle
+ * returns YS_ERR_UNSUPPORTED, a second call YS_ERR_STATE; ys_model_one2one_init and ys_model_e2e_init keep refusing OBB models.  cv2, cv3 and cv4
+ * are aliased (no Proto), so NO tensor is added and `.bin` files move freely between plain and End2End OBB models.  From then on:
+ *   training forward: "one2one_boxes" / "one2one_scores" / "one2one_angle" are the one2many values; the BatchNorm units of cv2 / cv3 / cv4 move
+ *     their running statistics twice per forward (num_batches_tracked += 2), the trunk once.
+ *   ys_loss_obb = E2EOBBLoss: v8OBBLoss(tal_topk 10) on one2many and v8OBBLoss(tal_topk 7, tal_topk2 1) on one2one (the rotated assigner followed by
+ *     ys_tal_keep_best's stage), combined as o2m * L_one2many + o2o * L_one2one; ys_loss_read_items returns the weighted 4 items (box, cls, dfl,
+ *     angle), *loss_sum their sum * B.  It also runs after an eval forward (the Val loss, Obber.cs:94-95).  "dboxes" / "dscores" / "dangle" are the
+ *     one2many gradients (x o2m), "one2one_dboxes" / "one2one_dscores" / "one2one_dangle" the one2one ones (x o2o; angle: with respect to the logit).
+ *   gains: 0.8 / 0.2 at creation; ys_model_e2e_update = E2EOBBLoss.update() (the chain given above), ys_model_e2e_gains reads them.  This is the
+ *     one criterion whose schedule the reference's loop steps (YoloBaseTaskModel.cs:350-353): once after every epoch.
+ *   backward (all forms): towers receive o2m * g_one2many + o2o * g_one2one; the feature maps and everything below o2m * g_one2many.
+ *   eval forward: Obb.decode_bboxes ignores end2end (Head.cs:434-437), so "pred" [B, 4+nc+1, A] stays (xywh of dist2rbox * stride, probabilities,
+ *     angle), bit for bit a plain OBB model's; "det" [B, k, 7] = (cx, cy, w, h, score, class, angle) = ys_e2e_topk_ex(pred, extra = 1)
+ *     (Obb.postprocess, Head.cs:439-452), k = min(max_det, A); ys_model_det_device returns its pointer and k.
+ *   YS_FP8 models are accepted like fp8 Segment / Detect models by ys_model_e2e_init (the criterion and the one2one pass are dtype-agnostic). */
+YS_API int ys_model_e2e_obb_init(ys_model* m, int max_det, int epochs);
 /* Detect.postprocess / get_topk_index with agnostic_nms = false (Head.cs:117-127, 175-196) over pred [B, 4+nc, A] fp32 (boxes in any
  * format, class scores): k = min(max_det, A); stage 1 = the k anchors with the largest max-over-classes score; stage 2 = the k largest of the
  * k * nc gathered scores, flattened [stage-1 rank][class]; out_rows [B, k, 6] = (box[0..3], score, class), out_anchor [B, k] = the anchor
@@ -203,7 +221,7 @@ YS_API int ys_e2e_topk_ex(ys_ctx* ctx, const float* pred, int on_device, int bat
                           float* out_rows, int64_t* out_anchor);
 YS_API int ys_e2e_select_ex(ys_ctx* ctx, const float* rows, int on_device, int batch, int k, int row_len, float conf_thres, int max_det,
                             int32_t* out_count);
-/* The assigner's second stage, tal_topk2 = 1 (Utils/Tal.cs:242-250), on its own -- the kernel the End2End Segment criterion runs.  align
+/* The assigner's second stage, tal_topk2 = 1 (Utils/Tal.cs:242-250), on its own -- the kernel the End2End Segment and OBB criteria run.  align
  * [B, G, A] fp32, mask_pos [B, G, A] uint8 (in / out), gt_count [B] in [0, G]: in every row g < gt_count[b] only the anchor that comes first in
  * (align * mask_pos descending, anchor index ascending) order over ALL A anchors keeps its mask bit.  So among equal positives the lower index
  * stays, and a row whose positives all carry align = 0 ties with every other anchor: it keeps anchor 0 if that is a positive of the row and ends
@@ -347,6 +365,15 @@ YS_API int ys_batch_probiou(ys_ctx* ctx, const float* obb1, int n, const float* 
 YS_API int ys_val_match_batched(ys_ctx* ctx, const float* rows, const int32_t* count, int on_device, int batch, int max_det,
                                 int row_stride, const float* batch_idx, const float* cls, const float* bboxes, int n_labels,
                                 float img_w, float img_h, uint8_t* correct);
+/* Obber.Val (Models/Obber.cs:102-114) for a whole batch: per image b, GT = bboxes[batch_idx == b] as (cx*W, cy*H, w*W, h*H, angle),
+ * predictions = rows[b, 0:count[b]] columns 0..3 + column angle_col; iou = Metrics.batch_probiou(GT, pred) (eps 1e-7);
+ * correct[b] = match_predictions(rows[:, 5], cls, iou) for linspace(0.5, 0.95, 10).  rows [B, max_det, row_stride], bboxes [n, 5].
+ * One launch, one workgroup per image; the same probiou function as ys_batch_probiou, so `correct` equals ys_batch_probiou +
+ * ys_match_predictions per image bit for bit.  row_stride >= 7, 6 <= angle_col < row_stride.  Like ys_val_match_batched the label workspace holds
+ * n_labels entries per image, so no image can exceed it. */
+YS_API int ys_val_match_rotated_batched(ys_ctx* ctx, const float* rows, const int32_t* count, int on_device, int batch, int max_det,
+                                        int row_stride, int angle_col, const float* batch_idx, const float* cls, const float* bboxes,
+                                        int n_labels, float img_w, float img_h, uint8_t* correct);
 /* Metrics.box_iou (Utils/Metrics.cs:16-34): iou [n, m] of xyxy boxes, fp32, eps as given (reference default 1e-7). */
 YS_API int ys_box_iou(ys_ctx* ctx, const float* box1, int n, const float* box2, int m, float eps, int on_device, float* iou);
 

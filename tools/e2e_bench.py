@@ -1,6 +1,6 @@
 """End2End cost on one device: prints ONE JSON line.
 
-  python tools/e2e_bench.py [--task detect|segment] [--batch 64] [--imgsz 640] [--nc 80] [--steps 20] [--warmup 5] [--repeats 3]
+  python tools/e2e_bench.py [--task detect|segment|obb] [--batch 64] [--imgsz 640] [--nc 80] [--steps 20] [--warmup 5] [--repeats 3]
 
 Four measurements, each in a child process of its own under its own time limit (a leg that fails or runs out of time ends the run):
   step_off / step_on   ms per train step of YOLOv8n bf16 (forward, criterion, backward, AdamW, zero_grad; device-resident images and labels)
@@ -12,6 +12,11 @@ Four measurements, each in a child process of its own under its own time limit (
 difference is the second criterion pass (tal_topk 7 + the keep-best stage + the one2one mask term without its prototype gradient), the one2one pass
 through the cv2 / cv3 / cv4 backward and the towers' second statistics update -- and ys_e2e_topk_ex (extra = 32 mask coefficients) against a torch
 restatement of Segment.postprocess (Head.cs:321-339).
+--task obb measures the YOLOv8n-obb bf16 step at --batch 64, nc 15 with model.e2e_obb_init() off and on -- the difference is the second criterion pass
+(the rotated assigner with tal_topk 7 + the keep-best stage), the one2one pass through the cv2 / cv3 / cv4 backward and the towers' second statistics
+update -- ys_e2e_topk_ex (extra = 1, the angle) against a torch restatement of Obb.postprocess (Head.cs:439-452), and one more leg, val_match: the
+per-image part of Obber.Val on the End2End rows of a B = 16 eval forward, as the one launch ys_val_match_rotated_batched and as the per-image
+ys_batch_probiou + ys_match_predictions loop (median of 20 calls each; both include fetching the rows, which Val needs anyway).
 Every figure is the median over --repeats timed blocks of --steps calls after --warmup calls.
 """
 import argparse
@@ -28,6 +33,8 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 LEGS = ("step_off", "step_on", "topk", "torch_topk")
+OBB_LEGS = LEGS + ("val_match",)
+EXTRA = {"detect": 0, "segment": 32, "obb": 1}      # trailing channels of a "det" row: mask coefficients / the angle
 
 
 def _labels(B, nc, rng, kmax=16):
@@ -77,11 +84,15 @@ def _masks(bi, bb, B, mh, mw):
 
 def leg_step(a, end2end):
     from yolosharp_amd import Engine
-    from yolosharp_amd.model import AMPWrapper, Yolov8, Yolov11Segment, v8DetectionLoss, v8SegmentationLoss
+    from yolosharp_amd.model import AMPWrapper, Yolov8, Yolov8Obb, Yolov11Segment, v8DetectionLoss, v8OBBLoss, v8SegmentationLoss
     eng = Engine(0)
     B, S, nc = a.batch, a.imgsz, a.nc
-    seg = a.task == "segment"
-    if seg:
+    seg, obb = a.task == "segment", a.task == "obb"
+    if obb:
+        m = Yolov8Obb(eng, nc=nc, size="n", height=S, width=S, max_batch=B, dtype="bf16")
+        if end2end:
+            m.e2e_obb_init()
+    elif seg:
         m = Yolov11Segment(eng, nc=nc, size="m", height=S, width=S, max_batch=B, dtype="bf16")
         if end2end:
             m.e2e_init()
@@ -91,11 +102,13 @@ def leg_step(a, end2end):
     rng = np.random.default_rng(0)
     x_dev = eng.to_device(rng.random((B, 3, S, S), dtype=np.float32))
     bi, cl, bb = _labels(B, nc, rng)
+    if obb:                                         # oriented labels: + an angle in [-pi/4, 3pi/4)
+        bb = np.concatenate((bb, (rng.random((len(bb), 1)) * np.pi - np.pi / 4)), 1).astype(np.float32)
     m.reserve_labels(16)
     d = [eng.to_device(v) for v in (bi, cl, bb)]
     if seg:
         d.append(eng.to_device(_masks(bi, bb, B, S // 4, S // 4)))
-    crit, amp = (v8SegmentationLoss if seg else v8DetectionLoss)(m), AMPWrapper(m)
+    crit, amp = (v8OBBLoss if obb else v8SegmentationLoss if seg else v8DetectionLoss)(m), AMPWrapper(m)
     m.train()
 
     def step():
@@ -125,7 +138,7 @@ def leg_topk(a):
     from yolosharp_amd import Engine, _lib
     eng = Engine(0)
     B, nc, A = a.batch, a.nc, _anchors(a.imgsz)
-    extra = 32 if a.task == "segment" else 0
+    extra = EXTRA[a.task]
     k = min(300, A)
     p_dev = eng.to_device(_pred(B, nc, A, np.random.default_rng(1), extra))
     rows, anc = eng.malloc(B * k * (6 + extra) * 4), eng.malloc(B * k * 8)
@@ -150,7 +163,7 @@ def leg_topk(a):
 def leg_torch_topk(a):
     import torch
     B, nc, A = a.batch, a.nc, _anchors(a.imgsz)
-    extra = 32 if a.task == "segment" else 0
+    extra = EXTRA[a.task]
     pred = torch.from_numpy(_pred(B, nc, A, np.random.default_rng(1), extra)).cuda()
     k = min(300, A)
     ar = torch.arange(B, device="cuda")[:, None]
@@ -164,7 +177,7 @@ def leg_torch_topk(a):
         idx = ori[ar, torch.div(index, nc, rounding_mode="floor")]
         bx = boxes.gather(1, idx.expand(-1, -1, 4))
         out = [bx, sc[..., None], (index % nc)[..., None].float()]
-        if extra:                                   # Segment.postprocess: the coefficients by the same anchor index
+        if extra:                                   # Segment / Obb.postprocess: the coefficients / the angle by the same anchor index
             out.append(mc.gather(1, idx.expand(-1, -1, extra)))
         return torch.cat(out, -1)
 
@@ -172,31 +185,86 @@ def leg_torch_topk(a):
     return {"ms_per_call": round(ms, 4), "runs": runs}
 
 
+def leg_val_match(a):
+    """The per-image part of Obber.Val on the End2End rows of one eval forward (B = 16): one launch against the per-image loop."""
+    from yolosharp_amd import Engine, _lib
+    from yolosharp_amd.model import Yolov8Obb
+    eng = Engine(0)
+    B, S, nc = 16, a.imgsz, a.nc
+    m = Yolov8Obb(eng, nc=nc, size="n", height=S, width=S, max_batch=B, dtype="bf16")
+    m.e2e_obb_init()
+    m.init_weights(1)
+    rng = np.random.default_rng(0)
+    m.eval()
+    m.forward(rng.random((B, 3, S, S), dtype=np.float32), fetch=False)
+    d_det, k = m.det_device()
+    bi, cl, bb = _labels(B, nc, rng)
+    bb = np.concatenate((bb, (rng.random((len(bb), 1)) * np.pi - np.pi / 4)), 1).astype(np.float32)
+    d_cnt, d_cor = eng.malloc(B * 4), eng.malloc(B * k * 10)
+    d_lab = [eng.to_device(v) for v in (bi, cl, bb)]
+    _lib.check(eng.lib, eng.lib.ys_e2e_select_ex(eng.ctx, d_det, 1, B, k, 7, 0.001, 300, d_cnt))
+    cnt = eng.from_device(d_cnt, (B,), np.int32)
+    scale = np.array([S, S, S, S], np.float32)
+    out = {}
+
+    def batched():
+        _lib.check(eng.lib, eng.lib.ys_val_match_rotated_batched(eng.ctx, d_det, d_cnt, 1, B, k, 7, 6, d_lab[0], d_lab[1], d_lab[2], bi.shape[0],
+                                                                 float(S), float(S), d_cor))
+        rows = eng.from_device(d_det, (B, k, 7), np.float32)
+        cor = eng.from_device(d_cor, (B, k, 10), np.uint8)
+        out["batched"] = [cor[b, :cnt[b]].astype(bool) for b in range(B)]
+        return rows
+
+    def per_image():
+        rows = eng.from_device(d_det, (B, k, 7), np.float32)
+        res = []
+        for b in range(B):
+            sel = bi == b
+            r = rows[b, :cnt[b]]
+            gt = np.concatenate((bb[sel, :4] * scale, bb[sel, 4:5]), 1).astype(np.float32)
+            pred = np.concatenate((r[:, :4], r[:, 6:7]), 1).astype(np.float32)
+            iou = eng.batch_probiou(gt, pred) if len(gt) and len(pred) else np.zeros((len(gt), len(pred)), np.float32)
+            res.append(eng.match_predictions(r[:, 5], cl[sel], iou))
+        out["per_image"] = res
+
+    a.steps, a.repeats = 1, 20                       # median of 20 single calls
+    ms_b, _ = _timed(batched, eng.synchronize, a)
+    ms_p, _ = _timed(per_image, eng.synchronize, a)
+    same = all(np.array_equal(x, y) for x, y in zip(out["batched"], out["per_image"]))
+    for p in d_lab + [d_cnt, d_cor]:
+        eng.free(p)
+    m.close()
+    return {"batched_ms": round(ms_b, 4), "per_image_ms": round(ms_p, 4), "identical": bool(same), "B": B, "k": k, "rows_kept": int(cnt.sum()),
+            "labels": int(bi.shape[0])}
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--task", choices=("detect", "segment"), default="detect")
-    ap.add_argument("--batch", type=int, default=0, help="0 = 64 (detect, YOLOv8n) / 32 (segment, YOLOv11m-seg: config 4's shape)")
+    ap.add_argument("--task", choices=("detect", "segment", "obb"), default="detect")
+    ap.add_argument("--batch", type=int, default=0, help="0 = 64 (detect, YOLOv8n; obb, YOLOv8n-obb) / 32 (segment, YOLOv11m-seg: config 4's shape)")
     ap.add_argument("--imgsz", type=int, default=640)
-    ap.add_argument("--nc", type=int, default=80)
+    ap.add_argument("--nc", type=int, default=0, help="0 = 80 (detect, segment) / 15 (obb)")
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--leg-timeout", type=int, default=240, help="seconds per child process")
     ap.add_argument("--tmp", default=os.environ.get("TMPDIR", "/tmp"))
-    ap.add_argument("--leg", choices=LEGS, help="run one measurement in this process (what the driver starts)")
+    ap.add_argument("--leg", choices=OBB_LEGS, help="run one measurement in this process (what the driver starts)")
     a = ap.parse_args()
     if a.batch <= 0:
         a.batch = 32 if a.task == "segment" else 64
+    if a.nc <= 0:
+        a.nc = 15 if a.task == "obb" else 80
     if a.leg:
         out = {"step_off": lambda: leg_step(a, False), "step_on": lambda: leg_step(a, True), "topk": lambda: leg_topk(a),
-               "torch_topk": lambda: leg_torch_topk(a)}[a.leg]()
+               "torch_topk": lambda: leg_torch_topk(a), "val_match": lambda: leg_val_match(a)}[a.leg]()
         print(json.dumps(out))
         return 0
-    res = {"metric": "e2e_cost", "task": a.task, "model": "yolov11m-seg" if a.task == "segment" else "yolov8n", "dtype": "bf16", "batch": a.batch,
+    res = {"metric": "e2e_cost", "task": a.task, "model": {"segment": "yolov11m-seg", "obb": "yolov8n-obb"}.get(a.task, "yolov8n"), "dtype": "bf16", "batch": a.batch,
            "imgsz": a.imgsz, "nc": a.nc}
     fwd = [x for kv in (("--task", a.task), ("--batch", a.batch), ("--imgsz", a.imgsz), ("--nc", a.nc), ("--steps", a.steps), ("--warmup", a.warmup),
                         ("--repeats", a.repeats), ("--tmp", a.tmp)) for x in (kv[0], str(kv[1]))]
-    for leg in LEGS:
+    for leg in (OBB_LEGS if a.task == "obb" else LEGS):
         try:
             r = subprocess.run([sys.executable, os.path.abspath(__file__), "--leg", leg] + fwd, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
                                text=True, timeout=a.leg_timeout, stdin=subprocess.DEVNULL)

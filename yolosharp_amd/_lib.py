@@ -136,7 +136,10 @@ PROTOTYPES = {
     "ys_model_reserve_labels": (C.c_int, [C.c_void_p, C.c_int]),
     "ys_model_one2one_init": (C.c_int, [C.c_void_p, C.c_int]),
     "ys_model_e2e_init": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    "ys_model_e2e_obb_init": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "ys_model_e2e_update": (C.c_int, [C.c_void_p]),
+    "ys_val_match_rotated_batched": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                               C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_void_p]),
     "ys_model_e2e_gains": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "ys_e2e_topk_ex": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "ys_e2e_select_ex": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_void_p]),

@@ -5,7 +5,7 @@
 //   Utils/Loss.cs:363-390   preprocess (pad GT per image, cxcywh*imgsz -> xyxy pixels)
 //   Utils/Loss.cs:398-409   bbox_decode (softmax . arange(reg_max), dist2bbox xyxy)
 //   Utils/Tal.cs:50-255     TaskAlignedAssigner (topk 10, alpha 0.5, beta 6, eps 1e-9)
-//   Utils/Tal.cs:242-250    its second stage, tal_topk2 = 1 (the one2one criterion of E2ESegmentLoss): LossArgs::topk2, tal_keep_best_kernel
+//   Utils/Tal.cs:242-250    its second stage, tal_topk2 = 1 (the one2one criterion of E2ESegmentLoss / E2EOBBLoss): LossArgs::topk2, tal_keep_best_kernel
 //   Utils/Loss.cs:94-167    DFLoss / BboxLoss
 //   Utils/Metrics.cs:36-111 bbox_iou(CIoU), eps 1e-7, alpha NOT detached
 //   Utils/Tal.cs:313-379    make_anchors / dist2bbox / bbox2dist
@@ -941,7 +941,8 @@ static int loss_launch_t(hipStream_t st, const LossArgs& a) {
   if (a.reg_max > 32) { ys_set_error("loss: reg_max %d > 32 unsupported", a.reg_max); return YS_ERR_UNSUPPORTED; }
   if (a.A > 1056 * 32) { ys_set_error("loss: %d anchors exceed the assigner capacity", a.A); return YS_ERR_UNSUPPORTED; }
   if (a.ld_ps % EPL) { ys_set_error("loss: ld_ps %d must be a multiple of %d", a.ld_ps, EPL); return YS_ERR_INVALID_ARG; }
-  if (a.topk2 != 0 && (a.topk2 != 1 || a.rot)) { ys_set_error("loss: tal_topk2 = %d%s is not built (the reference uses 1; OBB End2End is a follow-up)", a.topk2, a.rot ? " on rotated boxes" : ""); return YS_ERR_UNSUPPORTED; }
+  // rotated boxes take the same second stage: it reads mpos / align / ov only (ov = the clamped probiou of tal_metrics_pair<ROT>), never a box
+  if (a.topk2 != 0 && a.topk2 != 1) { ys_set_error("loss: tal_topk2 = %d is not built (the reference uses 1)", a.topk2); return YS_ERR_UNSUPPORTED; }
   // gt_valid lives behind gt_cls ([B][gcap] ints each)
   int* gt_valid = a.gt_cls + (long)a.B * a.gcap;
   const int nb_a = anc_blocks(a), nb_c = cls_blocks(a, EPL), nb_b = box_blocks(a);

@@ -204,6 +204,10 @@ struct ys_model {
   // det_rows is then [B][k][6 + nm]; seg_pass2 = the first criterion pass's arguments, kept for the second one (ys_loss_segment)
   bool e2e_seg = false; float o2m = 1.0f, o2o = 1.0f; int e2e_updates = 0, e2e_epochs = 100;
   void* o2o_dmc = nullptr; LossArgs seg_pass2{};
+  // End2End OBB (ys_model_e2e_obb_init; Head.cs:454-469, Loss.cs:1120-1177): cv2 / cv3 / cv4 aliased, no Proto.  ys_loss_obb = E2EOBBLoss with the same gains
+  // (the one criterion whose schedule the reference's loop steps); o2o_dmc holds the one2one gradient of the angle logits; "pred" keeps its xywh + angle
+  // form (Obb.decode_bboxes ignores end2end, Head.cs:434-437) and det_rows is [B][k][7]
+  bool e2e_obb = false;
   float* det_rows = nullptr; long long* det_anchor = nullptr; void* det_ws = nullptr;
   int head_conv0 = 0, det_in[3] = {-1, -1, -1};       // first tower unit in `convs`; the three feature maps the head reads
   // the towers' running statistics as contiguous runs of `state` (Detect: one, the tail; Segment: Proto's units lie between cv3 and cv4 and are left out);
@@ -1669,13 +1673,14 @@ int forward_impl(ys_model* m, int B) {
   if (!m->training && m->pd_buf >= 0) {
     YS_TRY(ys_detect_decode_launch(st, m->dtype, m->bufs[m->pd_buf].act, m->ld_pd, m->bufs[m->ps_buf].act, m->ld_ps, B, m->A,
                                    m->d.nc, m->d.reg_max, m->nl, m->lvl_off, m->lvl_w, m->lvl_stride, m->pred, 4 + m->d.nc + m->nm,
-                                   m->xkind >= 2 ? m->bufs[m->mc_buf].act : nullptr, m->ld_mc, m->xkind, m->nm, m->kdim, m->e2e ? 1 : 0));
-    if (m->e2e && !m->e2e_seg)   // Detect.postprocess on the one2one branch (same values as the one2many branch): [B][k][6] (Head.cs:107-127)
+                                   m->xkind >= 2 ? m->bufs[m->mc_buf].act : nullptr, m->ld_mc, m->xkind, m->nm, m->kdim, m->e2e && !m->e2e_obb ? 1 : 0));
+    if (m->e2e && !m->e2e_seg && !m->e2e_obb)   // Detect.postprocess on the one2one branch (same values as the one2many branch): [B][k][6] (Head.cs:107-127)
       YS_TRY(ys_e2e_topk_launch(st, m->pred, B, m->d.nc, m->A, m->max_det, m->det_ws, m->det_rows, m->det_anchor));
     if (m->segment)   // Segment._inference: cat(preds, mask_coefficient) (Head.cs:309-313), raw coefficients
       YS_TRY(ys_unpack_nchw_strided_launch(st, m->dtype, m->bufs[m->mc_buf].act, m->ld_mc, 0, B, m->nm, m->A, m->pred,
                                            (long)(4 + m->d.nc + m->nm) * m->A, (long)(4 + m->d.nc) * m->A));
-    if (m->e2e_seg)   // Segment.postprocess (Head.cs:321-339): the same selection, the nm coefficients gathered by the same anchor index: [B][k][6 + nm]
+    if (m->e2e_seg || m->e2e_obb)   // Segment.postprocess (Head.cs:321-339): the same selection, the nm coefficients gathered by the same anchor index: [B][k][6 + nm];
+                                    // Obb.postprocess (Head.cs:439-452): the angle channel rides the same way, rows (cx, cy, w, h, score, class, angle)
       YS_TRY(ys_e2e_topk_launch(st, m->pred, B, m->d.nc, m->A, m->max_det, m->det_ws, m->det_rows, m->det_anchor, m->nm));
   }
   YS_CHECK_HIP(hipGetLastError());
@@ -2181,12 +2186,12 @@ int backward_range(ys_model* m, int seg_lo, int seg_hi, bool async_end = false, 
     // joined in between: the second pass reuses every dy buffer and partial region.
     Buf &pb = m->bufs[m->pd_buf], &sb = m->bufs[m->ps_buf];
     std::swap(pb.grad, m->o2o_dpd); std::swap(sb.grad, m->o2o_dps);
-    if (m->e2e_seg) std::swap(m->bufs[m->mc_buf].grad, m->o2o_dmc);     // cv4 is aliased too (Head.cs:245-357); Proto ran once and gets no one2one gradient
+    if (m->o2o_dmc) std::swap(m->bufs[m->mc_buf].grad, m->o2o_dmc);     // cv4 is aliased too (Segment, Head.cs:245-357: Proto ran once and gets no one2one gradient; Obb, Head.cs:454-469: the angle logits)
     m->e2e_pass = true;
     const int rc = backward_range(m, 0, 0, false, false);
     m->e2e_pass = false;
     std::swap(pb.grad, m->o2o_dpd); std::swap(sb.grad, m->o2o_dps);
-    if (m->e2e_seg) std::swap(m->bufs[m->mc_buf].grad, m->o2o_dmc);
+    if (m->o2o_dmc) std::swap(m->bufs[m->mc_buf].grad, m->o2o_dmc);
     YS_TRY(rc);
     reset_grad_state(m);
   }
@@ -2606,7 +2611,7 @@ int ys_model_get_output(ys_model* m, const char* key, float* host, size_t count)
     YS_REQUIRE(m->e2e, "ys_model_get_output(det): not an End2End model (ys_model_one2one_init)");
     YS_REQUIRE(!m->fwd_training && !m->training, "ys_model_get_output(det): the last forward ran in training mode");
     const size_t kk = (size_t)std::min(m->max_det, m->A);
-    const size_t rl = (size_t)(6 + (m->e2e_seg ? m->nm : 0));      // End2End Segment: + the nm mask coefficients of the anchor (Head.cs:321-339)
+    const size_t rl = (size_t)(6 + (m->e2e_seg || m->e2e_obb ? m->nm : 0));      // End2End Segment: + the nm mask coefficients of the anchor (Head.cs:321-339); OBB: + the angle (Head.cs:439-452)
     YS_REQUIRE(count == (size_t)B * kk * rl, "ys_model_get_output(det): expected %zu elements", (size_t)B * kk * rl);
     YS_CHECK_HIP(hipMemcpyAsync(host, m->det_rows, count * 4, hipMemcpyDeviceToHost, st));
   } else if (m->segment && (k == "one2one_mask_coefficient" || k == "one2one_dmask_coefficient")) {
@@ -2617,6 +2622,16 @@ int ys_model_get_output(ys_model* m, const char* key, float* host, size_t count)
     YS_REQUIRE(count == (size_t)B * m->nm * m->A, "ys_model_get_output(%s): expected %zu elements", key, (size_t)B * m->nm * m->A);
     const Buf& b = m->bufs[m->mc_buf];
     YS_TRY(ys_unpack_nchw_launch(st, m->dtype, g ? m->o2o_dmc : b.act, b.ldc, 0, B, m->nm, m->A, m->out_stage));
+    YS_CHECK_HIP(hipMemcpyAsync(host, m->out_stage, count * 4, hipMemcpyDeviceToHost, st));
+  } else if (m->xkind == 2 && (k == "one2one_angle" || k == "one2one_dangle")) {
+    // End2End OBB: cv4 is aliased like cv2 / cv3 (Head.cs:454-469), so the one2one angle IS the one2many one; the second criterion pass has its own gradient
+    YS_REQUIRE(m->e2e_obb, "ys_model_get_output(%s): not an End2End OBB model (ys_model_e2e_obb_init)", key);
+    const bool g = k[8] == 'd';
+    YS_REQUIRE(!g || m->have_seg_loss, "ys_model_get_output(%s): the model's criterion has not run", key);
+    YS_REQUIRE(count == (size_t)B * m->nm * m->A, "ys_model_get_output(%s): expected %zu elements", key, (size_t)B * m->nm * m->A);
+    const Buf& b = m->bufs[m->mc_buf];
+    YS_TRY(ys_unpack_nchw_launch(st, m->dtype, g ? m->o2o_dmc : b.act, b.ldc, 0, B, m->nm, m->A, m->out_stage));
+    if (!g) YS_TRY(ys_obb_angle_launch(st, m->out_stage, (long)count));
     YS_CHECK_HIP(hipMemcpyAsync(host, m->out_stage, count * 4, hipMemcpyDeviceToHost, st));
   } else if (m->segment && (k == "mask_coefficient" || k == "dmask_coefficient")) {   // Head.cs:290-296: [B][nm][A]
     const bool g = k[0] == 'd';
@@ -2696,7 +2711,7 @@ int ys_model_pred_device(ys_model* m, float** dptr) {
 // YoloBaseTaskModel.One2one_Init -> Detect.one2one_init (Head.cs:152-167): the one2one towers are the SAME Sequential objects as cv2 / cv3
 // (CopyTo copies references), so the model gains no tensor -- only the second criterion pass's gradient / scalar buffers, the snapshot of
 // the towers' running statistics (their second momentum update) and the top-k output of the eval forward.
-static int e2e_init_impl(ys_model* m, int max_det, bool seg) {
+static int e2e_init_impl(ys_model* m, int max_det, bool seg, bool obb = false) {
   YS_CHECK_HIP(hipSetDevice(m->ctx->device));
   const int B = m->maxB;
   m->max_det = max_det > 0 ? max_det : 300;     // Detect.max_det (Head.cs:13)
@@ -2704,9 +2719,9 @@ static int e2e_init_impl(ys_model* m, int max_det, bool seg) {
   const Buf &pb = m->bufs[m->pd_buf], &sb = m->bufs[m->ps_buf];
   YS_TRY(dev_alloc(m, &m->o2o_dpd, (size_t)B * pb.rows_per_b * pb.ldc * m->es));
   YS_TRY(dev_alloc(m, &m->o2o_dps, (size_t)B * sb.rows_per_b * sb.ldc * m->es));
-  if (seg) { const Buf& cb = m->bufs[m->mc_buf]; YS_TRY(dev_alloc(m, &m->o2o_dmc, (size_t)B * cb.rows_per_b * cb.ldc * m->es)); }
+  if (seg || obb) { const Buf& cb = m->bufs[m->mc_buf]; YS_TRY(dev_alloc(m, &m->o2o_dmc, (size_t)B * cb.rows_per_b * cb.ldc * m->es)); }
   YS_TRY(dev_alloc(m, (void**)&m->scalars2, 64 * 4 + 64 * 8 * 8));
-  YS_TRY(dev_alloc(m, (void**)&m->det_rows, (size_t)B * k * (6 + (seg ? m->nm : 0)) * 4));
+  YS_TRY(dev_alloc(m, (void**)&m->det_rows, (size_t)B * k * (6 + (seg || obb ? m->nm : 0)) * 4));
   YS_TRY(dev_alloc(m, (void**)&m->det_anchor, (size_t)B * k * 8));
   YS_TRY(dev_alloc(m, &m->det_ws, ys_e2e_topk_ws_bytes(B, m->d.nc, m->A, m->max_det)));
   // the towers' BatchNorm state as contiguous runs of `state`.  A Detect head's units are the last of `convs` and their state is the tail of `state`: one
@@ -2748,7 +2763,7 @@ static int e2e_init_impl(ys_model* m, int max_det, bool seg) {
     YS_CHECK_HIP(hipMemcpyAsync(m->hstate_count, isc.data(), isc.size(), hipMemcpyHostToDevice, m->ctx->stream));
     YS_CHECK_HIP(hipStreamSynchronize(m->ctx->stream));
   }
-  m->e2e = true; m->e2e_seg = seg;
+  m->e2e = true; m->e2e_seg = seg; m->e2e_obb = obb;
   m->have_fwd = false; m->have_loss = false; m->have_seg_loss = false;      // "pred" changes its box format: a forward from before the switch is not an End2End one
   return YS_OK;
 }
@@ -2781,12 +2796,27 @@ int ys_model_e2e_init(ys_model* m, int max_det, int epochs) {
   return YS_OK;
 }
 
-// E2ESegmentLoss.update() (Loss.cs:1225-1235).  The reference's training loop calls update() for E2EOBBLoss only (YoloBaseTaskModel.cs:350-353), so a
+// One2one_Init for OBB models (Models/Obber.cs:18-24; Obb.one2one_init, Head.cs:454-469: cv2, cv3 and cv4 aliased, no Proto; E2EOBBLoss, Loss.cs:1120-1177).
+// An entry of its own: ys_model_one2one_init and ys_model_e2e_init keep refusing OBB models.
+int ys_model_e2e_obb_init(ys_model* m, int max_det, int epochs) {
+  YS_REQUIRE(m, "ys_model_e2e_obb_init: null model");
+  YS_REQUIRE(max_det >= 0 && epochs >= 0, "ys_model_e2e_obb_init: max_det = %d, epochs = %d", max_det, epochs);
+  if (m->is_block || m->is_head || m->cls || m->d.task != YS_OBB || m->xkind != 2 || m->pd_buf < 0 || m->mc_buf < 0) {
+    ys_set_error("ys_model_e2e_obb_init: this entry is One2one_Init for full OBB models (Detect: ys_model_one2one_init; Segment: ys_model_e2e_init; Pose End2End is a follow-up)");
+    return YS_ERR_UNSUPPORTED;
+  }
+  if (m->e2e) { ys_set_error("ys_model_e2e_obb_init: already initialised"); return YS_ERR_STATE; }
+  YS_TRY(e2e_init_impl(m, max_det, false, true));
+  m->e2e_epochs = epochs > 0 ? epochs : 100; m->e2e_updates = 0; m->o2m = 0.8f; m->o2o = 1.0f - 0.8f;   // Loss.cs:1138-1148
+  return YS_OK;
+}
+
+// E2ESegmentLoss.update() (Loss.cs:1225-1235) and E2EOBBLoss.update() (Loss.cs:1166-1176), the same chain.  The reference's training loop calls update() for E2EOBBLoss only (YoloBaseTaskModel.cs:350-353), so a
 // Segment run of the reference keeps 0.8 / 0.2 for its whole life; callers that want the schedule call this once per epoch.
 int ys_model_e2e_update(ys_model* m) {
   YS_REQUIRE(m, "ys_model_e2e_update: null model");
   YS_REQUIRE(m->e2e, "ys_model_e2e_update: not an End2End model (ys_model_e2e_init)");
-  if (!m->e2e_seg) return YS_OK;                 // E2EDetectLoss has no gains
+  if (!m->e2e_seg && !m->e2e_obb) return YS_OK;  // E2EDetectLoss has no gains
   m->e2e_updates += 1;
   const int den = m->e2e_epochs - 1 > 1 ? m->e2e_epochs - 1 : 1;
   const float r = 1.0f - (float)m->e2e_updates / (float)den;
@@ -2873,14 +2903,22 @@ static int loss_detect_core(ys_model* m, const float* batch_idx, const float* cl
   a.hyp_box = 7.5f; a.hyp_cls = 0.5f; a.hyp_dfl = 1.5f; a.topk = 10;   // Loss.cs:344,357
   // E2ESegmentLoss (Loss.cs:1222): loss = o2m * L_one2many + o2o * L_one2one.  Items and gradients are linear in the hyp_* factors, so the gain rides on
   // them: no scale pass over any buffer
-  if (m->e2e_seg) { a.hyp_box *= m->o2m; a.hyp_cls *= m->o2m; a.hyp_dfl *= m->o2m; }
+  if (m->e2e_seg || m->e2e_obb) { a.hyp_box *= m->o2m; a.hyp_cls *= m->o2m; a.hyp_dfl *= m->o2m; }
   if (rot) {                                                             // Loss.cs:489: hyp_angle = 1
     const Buf& ab = m->bufs[m->mc_buf];
-    a.rot = 1; a.pa = ab.act; a.dpa = ab.grad; a.ld_pa = m->ld_mc; a.hyp_angle = 1.0f;
+    a.rot = 1; a.pa = ab.act; a.dpa = ab.grad; a.ld_pa = m->ld_mc; a.hyp_angle = m->e2e_obb ? m->o2m : 1.0f;
   }
   YS_TRY(ys_loss_detect_launch(st, m->dtype, a));
   if (m->e2e_seg) m->seg_pass2 = a;        // ys_loss_segment runs the mask term on this assignment first, then the second pass
-  if (m->e2e && !m->e2e_seg) {
+  if (m->e2e_obb) {
+    // E2EOBBLoss (Loss.cs:1120-1177): o2m * v8OBBLoss(tal_topk 10)(one2many) + o2o * v8OBBLoss(tal_topk 7, tal_topk2 1)(one2one) on the same head outputs
+    // (aliased towers).  The second pass pads its own GT again (loss_prep_body: the thin-box widening of Tal.cs:283-287 lands in a fresh tensor, as in the
+    // reference where each criterion calls preprocess itself), reuses the assignment workspaces and writes gradients and scalars of its own.
+    a.topk = 7; a.topk2 = 1; a.dpd = m->o2o_dpd; a.dps = m->o2o_dps; a.dpa = m->o2o_dmc; a.scalars = m->scalars2;
+    a.hyp_box = 7.5f * m->o2o; a.hyp_cls = 0.5f * m->o2o; a.hyp_dfl = 1.5f * m->o2o; a.hyp_angle = m->o2o;
+    YS_TRY(ys_loss_detect_launch(st, m->dtype, a));
+  }
+  if (m->e2e && !m->e2e_seg && !m->e2e_obb) {
     // E2EDetectLoss (Loss.cs:1094-1118): v8DetectionLoss(tal_topk 10) on one2many + v8DetectionLoss(tal_topk 1) on one2one, unweighted.
     // The one2one head outputs ARE the one2many ones (aliased towers, same input values), so the second pass reads the same pd / ps and
     // differs only in the assigner's topk.  It reuses the first pass's assignment workspaces: the stream is in order, and nothing after
@@ -2901,6 +2939,7 @@ static int add_o2o_items(ys_model* m, float h[16]) {
   YS_CHECK_HIP(hipStreamSynchronize(m->ctx->stream));
   for (int i = 1; i <= 4; i++) h[i] += g[i];
   if (m->e2e_seg) h[8] += g[8];            // the mask term (both already carry their gain)
+  if (m->e2e_obb) h[13] += g[13];          // the angle term
   return YS_OK;
 }
 

@@ -535,6 +535,14 @@ nms_rot_pick_kernel(const float* __restrict__ pred, int C, int A, int nc, int ma
   if (tid == 0) out_count[b] = kept;
 }
 
+// covariance terms of an oriented box (cx, cy, w, h, angle) -- _get_covariance_matrix (Metrics.cs:260-276), operation for operation in fp32
+__device__ inline void nms_obb_cov(const float* q, float& a, float& b, float& c) {
+  const float ga = q[2] * q[2] / 12.0f, gb = q[3] * q[3] / 12.0f;
+  const float cs = cosf(q[4]), sn = sinf(q[4]);
+  const float cos2 = cs * cs, sin2 = sn * sn;
+  a = ga * cos2 + gb * sin2; b = ga * sin2 + gb * cos2; c = (ga - gb) * cs * sn;
+}
+
 // Metrics.probiou (pairwise, Metrics.cs:137-177; CIoU adds only the aspect-ratio term) and Metrics.batch_probiou (N x M)
 __global__ void __launch_bounds__(256)
 probiou_kernel(const float* __restrict__ o1, const float* __restrict__ o2, long n, long m, int pairwise, int ciou, float eps, float* __restrict__ out) {
@@ -543,14 +551,8 @@ probiou_kernel(const float* __restrict__ o1, const float* __restrict__ o2, long 
   if (idx >= total) return;
   const long i = pairwise ? idx : idx / m, j = pairwise ? idx : idx - i * m;
   const float* p1 = o1 + i * 5; const float* p2 = o2 + j * 5;
-  auto cov = [](const float* q, float& a, float& b, float& c) {
-    const float ga = q[2] * q[2] / 12.0f, gb = q[3] * q[3] / 12.0f;
-    const float cs = cosf(q[4]), sn = sinf(q[4]);
-    const float cos2 = cs * cs, sin2 = sn * sn;
-    a = ga * cos2 + gb * sin2; b = ga * sin2 + gb * cos2; c = (ga - gb) * cs * sn;
-  };
   float a1, b1, c1, a2, b2, c2;
-  cov(p1, a1, b1, c1); cov(p2, a2, b2, c2);
+  nms_obb_cov(p1, a1, b1, c1); nms_obb_cov(p2, a2, b2, c2);
   float iou = nms_probiou(p1[0], p1[1], a1, b1, c1, p2[0], p2[1], a2, b2, c2, eps);
   if (pairwise && ciou) {
     const float d = atanf(p2[2] / p2[3]) - atanf(p1[2] / p1[3]);
@@ -559,6 +561,84 @@ probiou_kernel(const float* __restrict__ o1, const float* __restrict__ o2, long 
     iou = iou - v * alpha;
   }
   out[idx] = iou;
+}
+
+// ------------------------------------------------------------------ the per-image part of Obber.Val (Models/Obber.cs:102-114) for a whole batch
+// val_match_kernel (valmetrics.hip) with Metrics.batch_probiou in place of box_iou: one workgroup per image; GT = bboxes[batch_idx == b] as
+// (cx W, cy H, w W, h H, angle) in collate order, prediction d = rows[b][d] columns 0..3 + column angle_col; obb1 = GT, obb2 = prediction
+// (Obber.cs:112).  The kernel lives here because it must evaluate the SAME nms_obb_cov / nms_probiou as probiou_kernel: `correct` then equals
+// ys_batch_probiou + ys_match_predictions per image bit for bit.  Each label's covariance terms are computed once into ws_gt (a pure function of
+// the label, so staging changes no value).  match_predictions restated as in valmetrics.hip: best(d) = the class-matching label with the largest IoU
+// (lower label index among equals), label l is credited at threshold t to the smallest d with best(d) == l and iou >= t.
+#define VMR_THREADS 256
+#define VMR_NT 10
+struct VmrThr { float t[VMR_NT]; };
+__global__ void __launch_bounds__(VMR_THREADS)
+val_match_rot_kernel(const float* __restrict__ rows, const int* __restrict__ count, int max_det, int row_stride, int angle_col,
+                     const float* __restrict__ batch_idx, const float* __restrict__ cls, const float* __restrict__ bboxes, int n_labels,
+                     float img_w, float img_h, VmrThr thr, int lcap, int* __restrict__ ws_lab /*[B][lcap]*/, float* __restrict__ ws_gt /*[B][lcap][5]*/,
+                     float* __restrict__ ws_best /*[B][max_det][2]*/, unsigned char* __restrict__ correct /*[B][max_det][10]*/, int* __restrict__ overflow) {
+  __shared__ int s_nl;
+  const int b = blockIdx.x, tid = threadIdx.x;
+  int* lab = ws_lab + (long)b * lcap;
+  float* gtc = ws_gt + (long)b * lcap * 5;
+  float* best = ws_best + (long)b * max_det * 2;
+  unsigned char* cor = correct + (long)b * max_det * VMR_NT;
+  const int D = count[b] < max_det ? count[b] : max_det;
+  for (int i = tid; i < max_det * VMR_NT; i += VMR_THREADS) cor[i] = 0;
+  // labels of this image, in collate order (boolean-mask indexing keeps the order, Obber.cs:104-108)
+  if (tid == 0) {
+    int k = 0;
+    for (int j = 0; j < n_labels; j++)
+      if ((int)batch_idx[j] == b) { if (k < lcap) lab[k] = j; k++; }
+    if (k > lcap) { atomicMax(overflow, k); k = lcap; }
+    s_nl = k;
+  }
+  __syncthreads();
+  const int L = s_nl;
+  for (int k = tid; k < L; k += VMR_THREADS) {
+    const int j = lab[k];
+    const float g[5] = {bboxes[5 * j] * img_w, bboxes[5 * j + 1] * img_h, bboxes[5 * j + 2] * img_w, bboxes[5 * j + 3] * img_h, bboxes[5 * j + 4]};
+    float a, bq, c;
+    nms_obb_cov(g, a, bq, c);
+    gtc[5 * k] = g[0]; gtc[5 * k + 1] = g[1]; gtc[5 * k + 2] = a; gtc[5 * k + 3] = bq; gtc[5 * k + 4] = c;
+  }
+  __syncthreads();
+  // best class-matching label per detection
+  for (int d = tid; d < D; d += VMR_THREADS) {
+    const float* pr = rows + ((long)b * max_det + d) * row_stride;
+    const float p[5] = {pr[0], pr[1], pr[2], pr[3], pr[angle_col]};
+    const float pc = pr[5];
+    float a2, b2, c2;
+    nms_obb_cov(p, a2, b2, c2);
+    float bi = -1.f; int bl = -1;
+    for (int k = 0; k < L; k++) {
+      if (cls[lab[k]] != pc) continue;
+      const float* g = gtc + 5 * k;
+      const float iou = nms_probiou(g[0], g[1], g[2], g[3], g[4], p[0], p[1], a2, b2, c2, 1e-7f);
+      if (iou > bi) { bi = iou; bl = k; }
+    }
+    best[2 * d] = bi;
+    best[2 * d + 1] = (float)bl;
+  }
+  __syncthreads();
+  // every (label, threshold): the first detection that chose this label and clears the threshold
+  for (int e = tid; e < L * VMR_NT; e += VMR_THREADS) {
+    const int k = e / VMR_NT, ti = e - k * VMR_NT;
+    const float t = thr.t[ti];
+    for (int d = 0; d < D; d++)
+      if ((int)best[2 * d + 1] == k && best[2 * d] >= t) { cor[d * VMR_NT + ti] = 1; break; }
+  }
+}
+
+int ys_val_match_rot_launch(hipStream_t st, const float* rows, const int* count, int B, int max_det, int row_stride, int angle_col,
+                            const float* batch_idx, const float* cls, const float* bboxes, int n_labels, float img_w, float img_h,
+                            const float* thr10, int lcap, int* ws_lab, float* ws_gt, float* ws_best, unsigned char* correct, int* overflow) {
+  VmrThr thr;
+  for (int i = 0; i < VMR_NT; i++) thr.t[i] = thr10[i];
+  YS_LAUNCH(val_match_rot_kernel, B, VMR_THREADS, st, rows, count, max_det, row_stride, angle_col, batch_idx, cls, bboxes, n_labels, img_w, img_h, thr,
+            lcap, ws_lab, ws_gt, ws_best, correct, overflow);
+  return YS_OK;
 }
 
 int ys_probiou_launch(hipStream_t st, const float* o1, const float* o2, long n, long m, int pairwise, int ciou, float eps, float* out) {

@@ -345,4 +345,37 @@ int ys_val_match_batched(ys_ctx* ctx, const float* rows, const int32_t* count, i
   return rc;
 }
 
+// Obber.Val's per-image part (Models/Obber.cs:102-114) for a batch: val_match_rot_kernel (nms.hip, beside the probiou it shares with ys_batch_probiou)
+int ys_val_match_rotated_batched(ys_ctx* ctx, const float* rows, const int32_t* count, int on_device, int batch, int max_det, int row_stride,
+                                 int angle_col, const float* batch_idx, const float* cls, const float* bboxes, int n_labels, float img_w,
+                                 float img_h, uint8_t* correct) {
+  YS_REQUIRE(ctx && rows && count && correct, "ys_val_match_rotated_batched: null argument");
+  YS_REQUIRE(batch > 0 && max_det > 0 && row_stride >= 7 && n_labels >= 0, "ys_val_match_rotated_batched: bad shape");
+  YS_REQUIRE(angle_col >= 6 && angle_col < row_stride, "ys_val_match_rotated_batched: angle column %d outside [6, %d)", angle_col, row_stride);
+  YS_REQUIRE(n_labels == 0 || (batch_idx && cls && bboxes), "ys_val_match_rotated_batched: null label arrays");
+  YS_CHECK_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  const int lcap = n_labels > 0 ? n_labels : 1;          // an image can hold all labels of the batch
+  const size_t nrow = (size_t)batch * max_det * row_stride, ncor = (size_t)batch * max_det * VM_NT;
+  VmStage sg(st, on_device);
+  int* d_lab = (int*)sg.alloc((size_t)batch * lcap * 4);
+  float* d_gt = (float*)sg.alloc((size_t)batch * lcap * 20);
+  float* d_best = (float*)sg.alloc((size_t)batch * max_det * 8);
+  int* d_ovf = (int*)sg.alloc(4);
+  const float* d_rows = (const float*)sg.in(rows, nrow * 4);
+  const int* d_cnt = (const int*)sg.in(count, (size_t)batch * 4);
+  const float* d_bi = (const float*)sg.in(batch_idx, (size_t)n_labels * 4);
+  const float* d_cl = (const float*)sg.in(cls, (size_t)n_labels * 4);
+  const float* d_bb = (const float*)sg.in(bboxes, (size_t)n_labels * 20);
+  unsigned char* d_cor = (unsigned char*)sg.out(correct, ncor);
+  if (!sg.ok) { ys_set_error("ys_val_match_rotated_batched: out of device memory"); return YS_ERR_OOM; }
+  YS_CHECK_HIP(hipMemsetAsync(d_ovf, 0, 4, st));
+  const VmThr thr = vm_thresholds();
+  YS_TRY(ys_val_match_rot_launch(st, d_rows, d_cnt, batch, max_det, row_stride, angle_col, d_bi, d_cl, d_bb, n_labels, img_w, img_h, thr.t, lcap,
+                                 d_lab, d_gt, d_best, d_cor, d_ovf));
+  if (!on_device) YS_CHECK_HIP(hipMemcpyAsync(correct, d_cor, ncor, hipMemcpyDeviceToHost, st));
+  YS_CHECK_HIP(hipStreamSynchronize(st));      // the scratch buffers are released on return
+  return YS_OK;
+}
+
 }  // extern "C"

@@ -206,13 +206,18 @@ class Segmenter(Detector):
 class Obber(Detector):
     """Models/Obber.cs: ImagePredict (:28-68) = eval forward (pred = dist2rbox boxes, probabilities, angle) + rotated NMS, result =
     truncated centre / size + Radian; Val (:70-163) = eval forward + v8OBBLoss on the eval preds, rotated NMS (conf 0.01, IoU 0.7),
-    Metrics.batch_probiou(labels xywh * scale + angle, predictions xywh + angle) -> match_predictions -> ap_per_class."""
+    Metrics.batch_probiou(labels xywh * scale + angle, predictions xywh + angle) -> match_predictions -> ap_per_class.
+    On an End2End model (model.e2e_obb_init; Obber.cs:18-24) the head's own top-k rows [B, k, 7] are only thresholded (Ops.cs:258-267) and Val keeps
+    them on the device: ys_model_det_device -> ys_e2e_select_ex -> ys_val_match_rotated_batched (one launch for the per-image part)."""
 
     def ImagePredict(self, image_chw_u8, predict_threshold=0.25, iou_threshold=0.5):
         x = pad_to_32(np.asarray(image_chw_u8, np.float32))[None]
         assert x.shape[2:] == (self.model.height, self.model.width), "create the model with the padded image size"
         inference, _ = self.amp.Evaluate(x)
-        output, _ = self.engine.non_max_suppression(inference["boxes"], predict_threshold, iou_threshold, nc=self.model.nc, rotated=True)
+        if self.end2end:
+            output, _ = self.engine.non_max_suppression(inference["boxes"], predict_threshold, iou_threshold, nc=self.model.nc, end2end=True)
+        else:
+            output, _ = self.engine.non_max_suppression(inference["boxes"], predict_threshold, iou_threshold, nc=self.model.nc, rotated=True)
         results = []
         for r in output[0]:                                        # Obber.cs:55-63: the rotated rows stay xywh
             res = YoloResult.__new__(YoloResult)
@@ -223,6 +228,8 @@ class Obber(Detector):
 
     def Val(self, batches, conf_thres=0.01, iou_thres=0.7, max_det=300):
         from .model import v8OBBLoss
+        if self.end2end:
+            return self._val_end2end(batches, conf_thres, max_det)
         crit = v8OBBLoss(self.model)
         tps, confs, pcls, tcls = [], [], [], []
         loss_sum = None
@@ -246,6 +253,62 @@ class Obber(Detector):
                 iou = self.engine.batch_probiou(gt, pred) if len(gt) and len(pred) else np.zeros((len(gt), len(pred)), np.float32)
                 tps.append(self.engine.match_predictions(rows[:, 5], cl[sel], iou))
                 confs.append(rows[:, 4]); pcls.append(rows[:, 5]); tcls.append(cl[sel])
+        if not tps:
+            return np.zeros(4, np.float32), (0.0, 0.0, 0.0, 0.0)
+        stats = M.ap_per_class(np.concatenate(tps), np.concatenate(confs), np.concatenate(pcls), np.concatenate(tcls))
+        return loss_sum, M.val_summary(stats)
+
+    def _val_end2end(self, batches, conf_thres, max_det):
+        """Val on an End2End model: the rows are the head's own [B, k, 7] (ys_model_det_device); thresholding keeps a prefix of them and the per-image
+        probiou + match_predictions run as one launch on the device pointers.  Only rows, counts and `correct` come back per batch."""
+        from .model import v8OBBLoss
+        crit = v8OBBLoss(self.model)
+        eng, m = self.engine, self.model
+        tps, confs, pcls, tcls = [], [], [], []
+        loss_sum = None
+        d_det, k = m.det_device()
+        d_cnt = d_cor = None
+        cap_b = 0
+        try:
+            for data in batches:
+                if np.asarray(data["batch_idx"]).size < 1:
+                    continue
+                images = np.ascontiguousarray(data["images"], np.float32)
+                B, _, H, W = images.shape
+                m.eval()
+                m.forward(images, fetch=False)
+                _, items = crit.forward(None, data)                 # Obber.cs:94-95: E2EOBBLoss on the eval preds
+                loss_sum = items if loss_sum is None else loss_sum + items
+                if B > cap_b:
+                    for p_ in (d_cnt, d_cor):
+                        if p_ is not None:
+                            eng.free(p_)
+                    d_cnt = d_cor = None
+                    d_cnt, d_cor = eng.malloc(B * 4), eng.malloc(B * k * 10)
+                    cap_b = B
+                _lib.check(eng.lib, eng.lib.ys_e2e_select_ex(eng.ctx, d_det, 1, B, k, 7, float(conf_thres), int(max_det), d_cnt))
+                bi = np.ascontiguousarray(np.asarray(data["batch_idx"], np.float32).reshape(-1))
+                cl = np.ascontiguousarray(np.asarray(data["cls"], np.float32).reshape(-1))
+                bb = np.ascontiguousarray(np.asarray(data["bboxes"], np.float32).reshape(-1, 5))
+                d_lab = []
+                try:
+                    for a in (bi, cl, bb):
+                        d_lab.append(eng.to_device(a))
+                    _lib.check(eng.lib, eng.lib.ys_val_match_rotated_batched(eng.ctx, d_det, d_cnt, 1, B, k, 7, 6, d_lab[0], d_lab[1], d_lab[2],
+                                                                             bi.shape[0], float(W), float(H), d_cor))
+                    rows = eng.from_device(d_det, (B, k, 7), np.float32)
+                    cnt = eng.from_device(d_cnt, (B,), np.int32)
+                    cor = eng.from_device(d_cor, (B, k, 10), np.uint8)
+                finally:
+                    for p_ in d_lab:
+                        eng.free(p_)
+                for b in range(B):
+                    tps.append(cor[b, :cnt[b]].astype(bool)); confs.append(rows[b, :cnt[b], 4]); pcls.append(rows[b, :cnt[b], 5])
+                    tcls.append(cl[bi == b])
+        finally:
+            for p_ in (d_cnt, d_cor):
+                if p_ is not None:
+                    eng.free(p_)
         if not tps:
             return np.zeros(4, np.float32), (0.0, 0.0, 0.0, 0.0)
         stats = M.ap_per_class(np.concatenate(tps), np.concatenate(confs), np.concatenate(pcls), np.concatenate(tcls))

@@ -232,6 +232,21 @@ class Engine:
                                                            _ptr(bb), bi.shape[0], float(img_w), float(img_h), _ptr(cor)))
         return [cor[b, :count[b]].astype(bool) for b in range(B)]
 
+    def val_match_rotated(self, rows, count, batch, img_w, img_h, angle_col=6):
+        """Obber.Val's per-image part (Obber.cs:102-114) in one launch: rows [B,max_det,7+] / count [B] = oriented rows (cx,cy,w,h,conf,cls,angle);
+        batch = collate dict (batch_idx, cls, bboxes [N,5] normalised cxcywh + angle).  Returns a list of bool [count[b], 10]: match_predictions on
+        Metrics.batch_probiou(GT, prediction) per image, bit for bit what batch_probiou + match_predictions below give (ys_val_match_rotated_batched)."""
+        rows = np.ascontiguousarray(rows, np.float32)
+        count = np.ascontiguousarray(count, np.int32)
+        B, max_det, stride = rows.shape
+        bi = np.ascontiguousarray(np.asarray(batch["batch_idx"], np.float32).reshape(-1))
+        cl = np.ascontiguousarray(np.asarray(batch["cls"], np.float32).reshape(-1))
+        bb = np.ascontiguousarray(np.asarray(batch["bboxes"], np.float32).reshape(-1, 5))
+        cor = np.zeros((B, max_det, 10), np.uint8)
+        _lib.check(self.lib, self.lib.ys_val_match_rotated_batched(self.ctx, _ptr(rows), _ptr(count), 0, B, max_det, stride, int(angle_col), _ptr(bi),
+                                                                   _ptr(cl), _ptr(bb), bi.shape[0], float(img_w), float(img_h), _ptr(cor)))
+        return [cor[b, :count[b]].astype(bool) for b in range(B)]
+
     def mask_iou(self, gt_ids, nl, pred_masks, eps=1e-7):
         """Metrics.mask_iou (Metrics.cs:120-125) on (gt_ids == k+1), k < nl, vs pred_masks bool/uint8 [n, h, w] -> [nl, n] fp32."""
         ids = np.ascontiguousarray(gt_ids, np.float32).reshape(-1)
@@ -298,7 +313,7 @@ class Engine:
         `agnostic` flag is accepted but ignored (Ops.cs:345), and invalid thresholds raise (YsError status 1).
         rotated=True (Ops.cs:286,349-353): oriented boxes, angle = last channel, boxes stay xywh, Ops.nms_rotated's
         "any earlier box overlaps" rule on Metrics.batch_probiou."""
-        if end2end:        # Ops.cs:258-267: prediction [B, k, 6 (+ nm)] rows ordered by score -> rows with score > conf_thres, at most max_det; no keep indices
+        if end2end:        # Ops.cs:258-267: prediction [B, k, 6 (+ nm | + angle)] rows ordered by score -> rows with score > conf_thres, at most max_det; no keep indices
             rows = np.ascontiguousarray(prediction, np.float32)
             cnt = self.e2e_select(rows, conf_thres, max_det)
             return [rows[b, :cnt[b]].copy() for b in range(rows.shape[0])], [np.zeros((0,), np.float32)]

@@ -73,7 +73,7 @@ class Yolov8:
         self.end2end, self.max_det = True, int(max_det) if max_det else 300
 
     def e2e_update(self):
-        """E2ESegmentLoss.update() (Loss.cs:1225-1230); nothing on a Detect End2End model."""
+        """E2ESegmentLoss.update() (Loss.cs:1225-1230) / E2EOBBLoss.update() (Loss.cs:1166-1176); nothing on a Detect End2End model."""
         _lib.check(self.lib, self.lib.ys_model_e2e_update(self.handle))
 
     def e2e_gains(self):
@@ -83,7 +83,7 @@ class Yolov8:
         return a.value, b.value
 
     def det_device(self):
-        """Device pointer of the End2End eval output "det" [B, k, 6] (Segment: [B, k, 6+nm]) and k = min(max_det, A)."""
+        """Device pointer of the End2End eval output "det" [B, k, 6] (Segment: [B, k, 6+nm]; OBB: [B, k, 7]) and k = min(max_det, A)."""
         p, k = C.c_void_p(), C.c_int()
         _lib.check(self.lib, self.lib.ys_model_det_device(self.handle, C.byref(p), C.byref(k)))
         return p, k.value
@@ -193,11 +193,11 @@ class Yolov8:
         C_ = {"boxes": 4 * self.reg_max, "scores": self.nc, "pred": 4 + self.nc + self.NM, "dboxes": 4 * self.reg_max,
               "dscores": self.nc, "mask_coefficient": self.NM, "dmask_coefficient": self.NM, "angle": self.NM, "kpts": self.NM, "dkpts": self.NM, "dangle": self.NM}.get(key)
         if key.startswith("one2one_"):
-            C_ = 4 * self.reg_max if key.endswith("boxes") else (self.NM if key.endswith("mask_coefficient") else self.nc)
+            C_ = 4 * self.reg_max if key.endswith("boxes") else (self.NM if key.endswith(("mask_coefficient", "angle")) else self.nc)
         if key in ("proto", "dproto"):
             a = np.empty((B, self.NM, self.height // 4, self.width // 4), np.float32)
         elif key == "det":
-            a = np.empty((B, min(self.max_det, self.A), 6 + (self.NM if self.TASK == 1 else 0)), np.float32)
+            a = np.empty((B, min(self.max_det, self.A), 6 + (self.NM if self.TASK in (1, 2) else 0)), np.float32)
         else:
             a = np.empty((B, C_, self.A), np.float32)
         _lib.check(self.lib, self.lib.ys_model_get_output(self.handle, key.encode(), _ptr(a), a.size))
@@ -329,14 +329,26 @@ class Yolov11Segment(_SegmentMixin, Yolov11):
 class _ObbMixin:
     """Head.Obb (Head.cs:376-482): preds gain "angle" [B,1,A] = (sigmoid(cv4) - 0.25) * pi; the eval inference tensor is
     [B, 4+nc+1, A] = (xywh of dist2rbox * stride, class probabilities, angle) (Head.cs:411-418), the layout
-    Engine.non_max_suppression(rotated=True) reads.  Criterion: v8OBBLoss below."""
+    Engine.non_max_suppression(rotated=True) reads.  Criterion: v8OBBLoss below.
+    After e2e_obb_init (End2End, Head.cs:434-469): preds = {"one2many": {boxes, scores, angle}, "one2one": {the same values}} and the eval inference
+    dict is {"boxes": det [B,k,7] = (cx, cy, w, h, score, class, angle), "pred": the unchanged [B,4+nc+1,A] tensor (Obb.decode_bboxes ignores end2end)}."""
     TASK = 2
     NM = 1
+
+    def e2e_obb_init(self, max_det=300, epochs=100):
+        """One2one_Init for OBB models (ys_model_e2e_obb_init; Obber.cs:18-24): cv2 / cv3 / cv4 aliased, the criterion becomes E2EOBBLoss with a gain
+        schedule of `epochs` steps (e2e_update / e2e_gains) -- the one schedule Trainer steps, like the reference's loop."""
+        _lib.check(self.lib, self.lib.ys_model_e2e_obb_init(self.handle, int(max_det), int(epochs)))
+        self.end2end, self.max_det = True, int(max_det) if max_det else 300
 
     def forward(self, x, fetch=True):
         inf, preds = Yolov8.forward(self, x, fetch)
         if fetch:
-            preds["angle"] = self.get_output("angle")
+            if self.end2end:
+                preds["one2many"]["angle"] = self.get_output("angle")
+                preds["one2one"]["angle"] = self.get_output("one2one_angle")
+            else:
+                preds["angle"] = self.get_output("angle")
         return inf, preds
 
     __call__ = forward
@@ -484,7 +496,9 @@ class v8SegmentationLoss(v8DetectionLoss):
 
 class v8OBBLoss(v8SegmentationLoss):
     """Loss.cs:486-684.  batch["bboxes"] is [N, 5] = normalised cx, cy, w, h + angle (radians).  Returns (loss*B [4],
-    loss_detach [4]) in the order box, cls, dfl, angle."""
+    loss_detach [4]) in the order box, cls, dfl, angle.
+    On an End2End OBB model (model.e2e_obb_init) the same call is E2EOBBLoss (Loss.cs:1120-1177): the returned items are
+    o2m * items(one2many, tal_topk 10) + o2o * items(one2one, tal_topk 7, tal_topk2 1) with the model's current gains (model.e2e_gains())."""
     N_ITEMS = 4
 
     def __init__(self, model):

@@ -82,7 +82,7 @@ class Trainer:
         self.crit = {0: v8DetectionLoss, 1: v8SegmentationLoss, 2: v8OBBLoss, 3: v8PoseLoss, 4: v8ClassificationLoss}[task](model)
         self.validator = {0: D.Detector, 1: D.Segmenter, 2: D.Obber, 3: D.PoseDetector, 4: D.Classifier}[task]
         # Config.End2End travels with the model (Yolov8(..., end2end=True) / model.e2e_init()): ys_loss_detect is then E2EDetectLoss, ys_loss_segment
-        # E2ESegmentLoss, and D.Detector / D.Segmenter validate without NMS
+        # E2ESegmentLoss, ys_loss_obb E2EOBBLoss (model.e2e_obb_init()), and D.Detector / D.Segmenter / D.Obber validate without NMS
         self.end2end = bool(getattr(model, "end2end", False))
         self.sched = LrSchedule(model.nc, epochs, nb, **sched)
         self.best_fitness = -float("inf")
@@ -107,6 +107,11 @@ class Trainer:
             items_sum = items if items_sum is None else items_sum + items
             i += 1
         self.steps_run = i
+        # TrainEpoch ends with `if (loss is Loss.E2EOBBLoss) loss.update()` (YoloBaseTaskModel.cs:350-353): after the loop, so also after an epoch in which
+        # no batch trained.  E2ESegmentLoss is another class and E2EDetectLoss has no gains: their models are not stepped.
+        model = getattr(self, "model", None)
+        if getattr(model, "end2end", False) and getattr(model, "TASK", 0) == 2:
+            model.e2e_update()
         n_items = getattr(self.crit, "N_ITEMS", 3)
         return items_sum if items_sum is not None else np.zeros(n_items, np.float32)
 
@@ -116,8 +121,8 @@ class Trainer:
         for epoch in range(1, self.epochs + 1):
             tr = self.train_epoch(train_batches(), epoch)
             self.sched.end_epoch()
-            # The reference steps the End2End gain schedule here only `if (loss is Loss.E2EOBBLoss)` (YoloBaseTaskModel.cs:350-353).  E2ESegmentLoss is another
-            # class, so a Segment run keeps o2m / o2o = 0.8 / 0.2 for its whole life: model.e2e_update() is deliberately NOT called (E2EDetectLoss has no gains).
+            # The reference steps the End2End gain schedule only `if (loss is Loss.E2EOBBLoss)` (YoloBaseTaskModel.cs:350-353): train_epoch does that for an
+            # End2End OBB model.  E2ESegmentLoss is another class, so a Segment run keeps o2m / o2o = 0.8 / 0.2 for its whole life, and E2EDetectLoss has no gains.
             rec = {"epoch": epoch, "train_loss": tr, "lr": list(self.sched.lrs)}
             if val_batches is not None:
                 vloss, metrics, *more = self.validator(self.model).Val(val_batches())   # Segmenter / PoseDetector add mask / pose metrics
