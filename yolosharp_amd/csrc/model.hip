@@ -1,4 +1,5 @@
-// model.hip -- graph builder and step orchestration behind the ys_model_* / ys_loss_* / ys_optim_* ABI.
+// model.hip -- graph builder and step orchestration behind the ys_model_* / ys_optim_* / ys_block_* / ys_head_* ABI (the handle: ys_model.h; the criterion,
+// End2End setup and output accessors: criterion.hip).
 //
 // Builds the reference's Yolov8 detect graph (Models/Yolo.cs:41-89: widths/depths table :43-55, layer list
 // :56-87, skip router :92-134) out of Conv units (Modules/Convs.cs:36-62), C2f/Bottleneck
@@ -9,220 +10,12 @@
 //   * Detect towers write straight into [B, A, C] (= the permuted layout the loss consumes)
 // Training forward keeps the raw conv output y per Conv unit (BN backward needs it); backward walks the op
 // list in reverse, gradient buffers mirror activation buffers, "first writer writes, later writers accumulate".
-#include "ys_internal.h"
-#include "ys_kernels.h"
+#include "ys_model.h"
 #include <cmath>
 #include <cstring>
 #include <algorithm>
 
-namespace {
-
-struct View { int buf = -1; int coff = 0; int C = 0; };
-
-struct Buf {
-  int H = 0, W = 0, ldc = 0;
-  long rows_per_b = 0;   // H*W (or A for head outputs)
-  void* act = nullptr;
-  void* grad = nullptr;
-  bool need_grad = true;
-  std::vector<char> gw;  // per-channel "gradient already written in this backward pass"
-};
-
-struct ConvL {
-  std::string name;      // state_dict prefix
-  int cin = 0, cout = 0, k = 1, s = 1;
-  int cin_pad = 0;       // channels of the input view (first layer: 3 -> EPL)
-  int cout_ld = 0;       // channels incl. padding in the dgrad weight matrix / dy rows
-  int cout_real = 0;     // output channels of the reference module.  cout > cout_real only for the Pose towers (51 -> next 16-byte
-                         // multiple): the extra rows of every parameter stay zero, so the extra channels are exactly 0 in both BN modes,
-                         // receive zero gradients, and the state_dict surface lists the cout_real prefix
-  bool bn = true, act = true;
-  View in, out, res;
-  bool has_res = false;
-  int Hin = 0, Win = 0, Hout = 0, Wout = 0;
-  long out_rowoff = 0;   // head outputs: first row of this level inside [B][A]
-  long w_off = -1, g_off = -1, b_off = -1;   // flat parameter offsets (floats): weight, bn.weight|bias, bn.bias
-  long rm_off = -1, rv_off = -1, nbt_off = -1;  // running stats in `state`
-  long wf_off = 0, wd_off = 0;               // element offsets into wf_all / wd_all
-  long y_off = 0;                             // element offset into y_all (bn layers)
-  long acc_off = -1;                          // BatchNorm unit: offset (64-bit words) of its statistics accumulators in ys_model::stat_acc_all
-  long ch_off = 0;                            // offset into per-channel scratch (scale.. c2), floats
-  int seg = 0;
-  bool first = false;
-  bool dw = false;       // depthwise 3x3 (groups = channels): weights [9][C] fp32, no MFMA path
-  bool f8_fwd = false, f8_bwd = false;   // fp8 mode: forward / dgrad of this layer may run the fp8 kernel (f8.hip recipe)
-  int idx = -1, prep_idx = -1;           // own index in ys_model::convs; first PrepDesc (weight-amax slot)
-  long wgp_off = -1; int wgp_splits = 0; // own region of the weight-gradient partial workspace (floats) and the splits it holds; -1 = shared scratch + immediate reduce
-  int red_slot = -1;                     // index into ys_model::red_host (deferred split reduction)
-  bool proto = false;    // a unit of Segment's Proto: runs ONCE per End2End forward (Head.cs:283-307) -- no second statistics update, no one2one backward pass
-  bool ct = false;       // ConvTranspose2d(k=2,s=2,bias) = four 1x1 phase GEMMs (Proto.upsample, Block.cs:69); weights [4][Cout][Cin]
-  // fused BN-backward reduction (BnRedSeg, ys_kernels.h).  As a consumer: the producers whose dz this layer's dgrad completes
-  // (it is their first reader in forward order = last gradient writer in backward order).  As a producer: where its sums come from.
-  struct RedFeed { int prod; int c0, c1, yc0; long part_off; int rows_cap, rows; };
-  struct RedSrc { int cons, feed; };
-  std::vector<RedFeed> feeds;
-  std::vector<RedSrc> red_src;           // sorted by producer channel
-  bool red_ok = false; int red_seen = 0; // every source is a supported dgrad launch / sources attached in the current backward pass
-  // Several reference modules executed as ONE convolution (shared-input fusion, add_detect): member k owns output rows
-  // [row0, row0 + rows) of this layer's weight / BN vectors and appears in the state_dict under its own module name.  Empty = one module.
-  struct Member { std::string name; int row0, rows; };
-  std::vector<Member> members;
-  // Level-parallel execution of the head (round 4): `stage` orders the head's ops stage-major (all pyramid levels of one tower layer next
-  // to each other); ops of one `group` (>= 0) are consecutive in ys_model::ops, mutually independent, and run as grouped launches
-  // (run_conv_fwd_group / run_conv_bwd_group).  Grouped units own their statistics rows and dy buffer (no shared scratch between problems).
-  int stage = -1, group = -1;
-  long gstat_off = -1;                   // floats into ys_model::stat_group
-  void* dy_own = nullptr;
-  bool linear = false;     // Classify's Linear(1280, nc) run as a 1x1 convolution on a 1 x 1 map (M = B): state_dict weight [nc, 1280]
-  bool pool_next = false;  // Classify's Conv unit: in training its BN + SiLU apply is left to the pool op that follows (OP_POOL reads y)
-};
-
-enum OpType { OP_CONV = 0, OP_MAXPOOL = 1, OP_UPSAMPLE = 2, OP_ATTN = 3, OP_VCOPY = 4, OP_COPY = 5, OP_POOL = 6 };   // OP_POOL: Classify's AdaptiveAvgPool2d(1) (op.conv = its Conv unit)
-struct Op { int type; int conv = -1; View in, out; int H = 0, W = 0; long aux_off = 0; int seg = 0; int heads = 0, kd = 0, hd = 0; };
-
-struct TensorRec {
-  std::string name;
-  int ndim = 1; int64_t shape[4] = {1, 1, 1, 1};
-  bool is_param = true;
-  int kind = 0;     // 0 conv weight (OIHW at the edge), 1 vector in flat params, 2 vector in state, 3 dfl weight
-  int conv = -1;
-  long off = 0, count = 0;
-};
-
-struct PrepDesc { long w_off, wf_off, wd_off, nf_start, nd_start; int cout, taps, cin_real, cin_pad, cout_pad, has_wd, phase;
-                  long tile_start; int tiles_ci, tiles_co, layer, pad_; };   // round 5 (weight_prep_fast_kernel): 64 x 64 transpose tiles of the dgrad shadow, prefix over the table; layer = index in the full table (weight-amax slot)
-
-}  // namespace
-
-struct ys_model {
-  ys_ctx* ctx = nullptr;
-  ys_model_desc d{};
-  int dtype = 0, epl = 4; size_t es = 4;
-  int maxB = 0, B = 0;
-  int A = 0, nl = 3;
-  int lvl_off[4] = {0}, lvl_w[4] = {0}, lvl_h[4] = {0}, lvl_stride[4] = {8, 16, 32, 64};
-  bool training = true;
-  std::vector<Buf> bufs;
-  std::vector<ConvL> convs;
-  std::vector<Op> ops;
-  std::vector<TensorRec> tensors;
-  std::vector<int> reg;          // conv indices in the reference's module REGISTRATION order (state_dict order)
-  std::string head_prefix;       // "model.22" (v8) / "model.23" (v11)
-  float* attn_ws = nullptr; long n_attn = 0;   // softmax probabilities + dS of the C2PSA attention ops
-  // segmentation (Head.cs:238-324): mask coefficients [B][A][ld_mc], prototypes [B][mh*mw][ld_pr]
-  bool segment = false; int nm = 0, mc_buf = -1, pr_buf = -1, ld_mc = 0, ld_pr = 0, mh = 0, mw = 0;
-  // Obb (Head.cs:376-482) / Pose (Head.cs:484-606) reuse the cv4 output buffer: nm = ne (1) / nk (kpt_num * kpt_dim) channels
-  float* kp_dev = nullptr;       // Pose: staged keypoint labels [max_labels][K][D] (grows with the label workspace)
-  int xkind = 0, kdim = 3;       // 0 none, 1 mask coefficients, 2 angle logit, 3 keypoints (argument of ys_detect_decode_launch)
-  float* masks_dev = nullptr; int *seg_cnt = nullptr, *seg_off = nullptr, *seg_list = nullptr; float *seg_ent = nullptr, *seg_part = nullptr;
-  int n_items = 3; bool have_seg_loss = false;
-  int dfl_after_conv = -1;   // the DFL weight registers right after Detect's cv2/cv3 (Head.cs:52-56), before Segment's proto/cv4
-  int in_buf = -1, pd_buf = -1, ps_buf = -1;
-  bool is_block = false; int blk_out = -1, blk_c1 = 3, blk_c2 = 0;   // standalone block handle (ys_block_create)
-  bool is_head = false; int head_in[3] = {-1, -1, -1}, head_ch[3] = {0, 0, 0};   // standalone head handle (ys_head_create): P3 / P4 / P5 input buffers
-  int ld_pd = 0, ld_ps = 0;
-  // Classify (Head.cs:612-644): pooled [B][1280] and logits [B][ld_cls] buffers (1 x 1 maps), per-row losses + invalid-label flags [2B]
-  bool cls = false; int cls_conv = -1, pool_buf = -1, logit_buf = -1, ld_cls = 0;
-  float *cls_rows = nullptr, *cls_lab = nullptr;
-  // flat fp32 parameter state
-  long n_params = 0, n_params_real = 0;          // flat length incl. the zero rows of padded towers / the reference's parameter count
-  float *params = nullptr, *grads = nullptr, *adam_m = nullptr, *adam_v = nullptr;
-  float* state = nullptr; long n_state = 0;     // running_mean / running_var / num_batches_tracked
-  float dfl_w[64];
-  struct Range { long off, count; };
-  static constexpr int NSEG = 4;                 // backward segments: head, neck, late backbone, stem (the last, exposed all-reduce is the smallest)
-  Range seg_group[NSEG][3];                      // [segment][adamw group]
-  long step = 0;
-  // fp8 mode (ys_dtype YS_FP8: bf16 storage + fp8 MFMA convolutions, f8.hip)
-  bool f8 = false, f8_sx_valid = false, f8_sg_valid = false, f8_bwd_done = false;
-  unsigned char *wf8_all = nullptr, *wd8_all = nullptr;
-  int q8_fwd_ready = -1;                  // forward: conv index whose input image already sits in q8 (written by its producer's BN pass)
-  unsigned char* q8 = nullptr;            // scratch: fp8 image of one convolution input (blocked-GEMM fp8 kernel, quantised by ys_conv_launch)
-  float *amax_w = nullptr, *f8_scales = nullptr; unsigned *amax_act = nullptr, *amax_dy = nullptr;
-  F8Layer* f8_layers = nullptr; F8Conv* f8_convs = nullptr; int n_f8_convs = 0; long n_wf_pending = 0, n_wd_pending = 0;
-  int group_mode = 0;                            // 0 = disjoint groups, 1 = the reference's overlapping groups as written
-  unsigned char* bn_mask = nullptr;              // [n_params] 1 = BatchNorm weight / bias (listed twice in the reference's groups)
-  // T weights
-  void *wf_all = nullptr, *wd_all = nullptr; long n_wf = 0, n_wd = 0;
-  PrepDesc* prep_dev = nullptr; int n_prep = 0; long prep_nf = 0, prep_nd = 0;
-  bool prep_fast = false;
-  PrepDesc* prep_tile_dev = nullptr; int n_prep_tile = 0; long prep_tiles = 0;          // layers whose dgrad shadow is a plain transpose (tile_start prefix)
-  PrepDesc* prep_phase_dev = nullptr; int n_prep_phase = 0; long prep_nd_phase = 0;     // stride-2 layers with phase-major dgrad shadows (nd_start = compact prefix)
-  bool weights_dirty = true, eval_coeffs_dirty = true;
-  // activations
-  void* y_all = nullptr; long n_y = 0;
-  void* dy_scratch = nullptr; long n_dy = 0;
-  // weight gradients run on a second stream, concurrently with the BN-backward / dgrad chain of the following layers
-  // (both mostly latency-bound); dy lives in a ring of DY_RING buffers guarded by events
-  static constexpr int DY_RING = 4;
-  // round 6: weight gradients are handed to the second stream in BATCHES.  Every BatchNorm unit keeps its own dy buffer (ConvL::dy_own: no ring slot to wait for),
-  // a unit's weight-gradient launch is queued instead of issued, and ONE event record / wait pair hands a whole batch over (flush_wgrads).  A rocprofv3 trace of
-  // config 2 showed what the per-layer hand-off cost: every hipEventRecord between two kernels of the main stream is a ~6.6 us bubble (29 + 10 + 5 of them per step
-  // between bn_bwd_apply and the dgrad that follows) and every ring-slot wait another ~6 us (21 per step): 0.6 ms of an 8.7 ms step with no kernel running on
-  // the main stream, all of it in the backward pass (the forward has none).
-  struct PendWg { int conv; const void* dy; int ldc, coff; long bstride; };
-  std::vector<PendWg> pend_wg; double pend_mb = 0.0; int ev_hand = 0;
-  bool hold_stem = false;                      // one-call backward: model.0's weight gradient stays queued until the segment end (backward_range: stem_split)
-  // head lanes (round 3): the towers of the three pyramid levels are independent chains (own buffers, own rows of the prediction buffers);
-  // the P4 / P5 chains are short, latency-bound launches (100-400 workgroups) that run beside the P3 chain on two side streams
-  // asynchronous segment ends (data-parallel step): the weight-gradient stream is NOT joined into the main stream when a backward segment
-  // ends; the segment's completion is two events (main stream, weight-gradient stream) a communication stream waits on (ys_model_segment_fence)
-  hipEvent_t ev_seg_m[NSEG] = {nullptr, nullptr, nullptr, nullptr}, ev_seg_w[NSEG] = {nullptr, nullptr, nullptr, nullptr};
-  bool seg_on_st2[NSEG] = {false, false, false, false};
-  bool overlap = false, overlap_built = false; hipStream_t st2 = nullptr;   // overlap_built: second stream / dy ring exist; overlap: in use (ys_model_set_overlap)
-  hipEvent_t ev_dy[DY_RING + 1] = {nullptr}, ev_join = nullptr;     // hand-over events (rotated; a wait binds to the record that preceded it)
-  bool st2_dirty = false;
-  float* chan = nullptr; long n_chan = 0;       // per conv: scale, shift, mean, rstd, c1, c2 (6*cout)
-  float* stat_partial = nullptr; long n_stat = 0;
-  unsigned long long* stat_acc_all = nullptr; long n_stat_acc = 0;   // round 5: [unit][YS_STAT_SHARDS][cout][2] fixed-point statistics sums, cleared by ONE memset per training forward
-  bool bn_atomic = false;                                            // BatchNorm units take their statistics through them and finalize inside the apply pass
-  float* stat_group = nullptr;                  // statistics rows of the grouped head stages (one region per unit, ConvL::gstat_off)
-  float* wg_partial = nullptr; long n_wgp = 0;   // [shared scratch (ConvTranspose phases) | one region per convolution]
-  // deferred split reduction of the weight gradients: one batched launch per backward_range call instead of one per layer
-  std::vector<WgRedDesc> red_host, red_uploaded; WgRedDesc* red_dev = nullptr; int red_first[NSEG + 1] = {0, 0, 0, 0, 0}; int red_proto0 = 0;   // red_proto0: first descriptor of Proto's units in segment 0 (they sort last there)
-  bool defer_wgred = true;
-  // fused BN-backward reduction: planned per batch size (plan_bnred), partial rows of every (producer, consumer) pair
-  bool bnred_on = true; int bnred_B = -1; float* bnred_part = nullptr; long n_bnred = 0;
-  unsigned char* argmax = nullptr; long n_argmax = 0;
-  float* img_dev = nullptr;                      // staging for host images
-  bool stem_on = true;                           // YS_STEM_DIRECT=0 at creation: model.0 reads the packed bf16 copy like every other layer
-  const float* in_f32 = nullptr;                 // the fp32 NCHW image of the current step when model.0 reads it directly (conv_stem.hip); null = the packed input buffer holds it
-  float* pred = nullptr;                         // [B][4+nc][A] fp32 (eval)
-  float* out_stage = nullptr; long n_out_stage = 0;
-  // loss
-  int gcap = 64; int max_labels = 0;
-  float *lab_bidx = nullptr, *lab_cls = nullptr, *lab_box = nullptr;
-  int* gt_count = nullptr; float* gt_box = nullptr; int* gt_cls = nullptr; float* pbox = nullptr;
-  float *ov = nullptr, *align = nullptr; unsigned char* mpos = nullptr; unsigned *pos_align = nullptr, *pos_ov = nullptr;
-  int* fg_gt = nullptr; float* tnorm = nullptr; float* loss_partial = nullptr; float* scalars = nullptr;
-  // End2End (ys_model_one2one_init; Head.cs:89-127, 152-167): the one2one towers ALIAS cv2 / cv3 -- no tensors of their own.  Their
-  // criterion pass (tal_topk 1) writes its gradients and scalars here; the eval forward adds the top-k rows "det" [B][k][6]
-  bool e2e = false; int max_det = 300;
-  void *o2o_dpd = nullptr, *o2o_dps = nullptr; float* scalars2 = nullptr;
-  // End2End Segment (ys_model_e2e_init; Head.cs:245-357, Loss.cs:1179-1236): cv4 is aliased as well, Proto runs once.  E2ESegmentLoss weights its
-  // two criteria with the gains o2m / o2o (0.8 / 0.2 until ys_model_e2e_update moves them); a Detect End2End model keeps 1 / 1 (E2EDetectLoss is unweighted).
-  // det_rows is then [B][k][6 + nm]; seg_pass2 = the first criterion pass's arguments, kept for the second one (ys_loss_segment)
-  bool e2e_seg = false; float o2m = 1.0f, o2o = 1.0f; int e2e_updates = 0, e2e_epochs = 100;
-  void* o2o_dmc = nullptr; LossArgs seg_pass2{};
-  // End2End OBB (ys_model_e2e_obb_init; Head.cs:454-469, Loss.cs:1120-1177): cv2 / cv3 / cv4 aliased, no Proto.  ys_loss_obb = E2EOBBLoss with the same gains
-  // (the one criterion whose schedule the reference's loop steps); o2o_dmc holds the one2one gradient of the angle logits; "pred" keeps its xywh + angle
-  // form (Obb.decode_bboxes ignores end2end, Head.cs:434-437) and det_rows is [B][k][7]
-  bool e2e_obb = false;
-  float* det_rows = nullptr; long long* det_anchor = nullptr; void* det_ws = nullptr;
-  int head_conv0 = 0, det_in[3] = {-1, -1, -1};       // first tower unit in `convs`; the three feature maps the head reads
-  // the towers' running statistics as contiguous runs of `state` (Detect: one, the tail; Segment: Proto's units lie between cv3 and cv4 and are left out);
-  // snapshot and num_batches_tracked mask hold the runs back to back (n_hstate words)
-  long n_hstate = 0; float* hstate_snap = nullptr; unsigned char* hstate_count = nullptr;
-  Range hstate_rng[4]; int n_hstate_rng = 0;
-  bool e2e_pass = false;                              // backward: the one2one pass through the towers is running (no gradient into det_in)
-  bool have_fwd = false, have_loss = false;
-  bool fwd_training = false;   // the last forward kept what backward needs (training-mode BN statistics, pre-BN outputs)
-  std::vector<void*> allocs;
-};
-
-namespace {
-
-int dev_alloc(ys_model* m, void** p, size_t bytes, bool zero = true) {
+int dev_alloc(ys_model* m, void** p, size_t bytes, bool zero) {
   if (bytes == 0) bytes = 16;
   hipError_t e = hipMalloc(p, bytes);
   if (e != hipSuccess) { ys_set_error("hipMalloc(%zu bytes) failed: %s", bytes, hipGetErrorString(e)); return YS_ERR_OOM; }
@@ -230,6 +23,8 @@ int dev_alloc(ys_model* m, void** p, size_t bytes, bool zero = true) {
   if (zero) { e = hipMemsetAsync(*p, 0, bytes, m->ctx->stream); if (e != hipSuccess) { ys_set_error("hipMemset failed"); return YS_ERR_HIP; } }
   return YS_OK;
 }
+
+namespace {
 
 int new_buf(ys_model* m, int H, int W, int C) {
   Buf b; b.H = H; b.W = W; b.ldc = C; b.rows_per_b = (long)H * W; b.gw.assign(C, 0);
@@ -1069,6 +864,7 @@ void dev_free_tracked(ys_model* m, void* p) {
   for (size_t i = 0; i < m->allocs.size(); i++) if (m->allocs[i] == p) { m->allocs.erase(m->allocs.begin() + i); break; }
   hipFree(p);
 }
+}  // namespace
 
 // Ground-truth workspace for `gcap` labels PER IMAGE (the reference pads every image to the batch's largest label count,
 // Loss.cs:363-390, without a cap): raw label staging, padded GT arrays and the [B][gcap][A] assignment matrices.
@@ -1096,6 +892,8 @@ int alloc_label_ws(ys_model* m, int gcap) {
   if (m->xkind == 3) YS_TRY(dev_alloc(m, (void**)&m->kp_dev, (size_t)m->max_labels * m->nm * 4));
   return YS_OK;
 }
+
+namespace {
 
 // fp8 mode: which convolutions may run the fp8 kernel, the e4m3 weight shadows and the amax / scale slots (recipe: f8.hip)
 int alloc_f8(ys_model* m, const std::vector<PrepDesc>& pd) {
@@ -1673,14 +1471,13 @@ int forward_impl(ys_model* m, int B) {
   if (!m->training && m->pd_buf >= 0) {
     YS_TRY(ys_detect_decode_launch(st, m->dtype, m->bufs[m->pd_buf].act, m->ld_pd, m->bufs[m->ps_buf].act, m->ld_ps, B, m->A,
                                    m->d.nc, m->d.reg_max, m->nl, m->lvl_off, m->lvl_w, m->lvl_stride, m->pred, 4 + m->d.nc + m->nm,
-                                   m->xkind >= 2 ? m->bufs[m->mc_buf].act : nullptr, m->ld_mc, m->xkind, m->nm, m->kdim, m->e2e && !m->e2e_obb ? 1 : 0));
-    if (m->e2e && !m->e2e_seg && !m->e2e_obb)   // Detect.postprocess on the one2one branch (same values as the one2many branch): [B][k][6] (Head.cs:107-127)
-      YS_TRY(ys_e2e_topk_launch(st, m->pred, B, m->d.nc, m->A, m->max_det, m->det_ws, m->det_rows, m->det_anchor));
+                                   m->xkind >= 2 ? m->bufs[m->mc_buf].act : nullptr, m->ld_mc, m->xkind, m->nm, m->kdim, m->e2e && m->xkind != 2 ? 1 : 0));
     if (m->segment)   // Segment._inference: cat(preds, mask_coefficient) (Head.cs:309-313), raw coefficients
       YS_TRY(ys_unpack_nchw_strided_launch(st, m->dtype, m->bufs[m->mc_buf].act, m->ld_mc, 0, B, m->nm, m->A, m->pred,
                                            (long)(4 + m->d.nc + m->nm) * m->A, (long)(4 + m->d.nc) * m->A));
-    if (m->e2e_seg || m->e2e_obb)   // Segment.postprocess (Head.cs:321-339): the same selection, the nm coefficients gathered by the same anchor index: [B][k][6 + nm];
-                                    // Obb.postprocess (Head.cs:439-452): the angle channel rides the same way, rows (cx, cy, w, h, score, class, angle)
+    if (m->e2e)   // Detect.postprocess on the one2one branch (same values as the one2many branch): [B][k][6] (Head.cs:107-127).  Segment.postprocess (Head.cs:321-339):
+                  // the same selection, the nm coefficients gathered by the same anchor index: [B][k][6 + nm]; Obb.postprocess (Head.cs:439-452): the angle channel
+                  // rides the same way, rows (cx, cy, w, h, score, class, angle).  A Detect model has nm = 0
       YS_TRY(ys_e2e_topk_launch(st, m->pred, B, m->d.nc, m->A, m->max_det, m->det_ws, m->det_rows, m->det_anchor, m->nm));
   }
   YS_CHECK_HIP(hipGetLastError());
@@ -1759,12 +1556,10 @@ static ConvArgs dgrad_args(ys_model* m, const ConvL& c, int B, const void* dy, i
   return a;
 }
 
-
 // Fused BN-backward reduction, host side.  For every BN Conv unit L find, per output channel, the FIRST op in forward order that
 // reads it: that op's backward is the last writer of the channel's gradient dz.  When all of L's channels are completed by the
 // dgrad launches of plain convolutions (reading them as their input view, not as a residual) whose kernels carry the fused
 // epilogue (ys_conv_bnred_rows), those launches produce L's sums and L's backward skips chan_reduce_kernel.
-static ConvArgs dgrad_args(ys_model* m, const ConvL& c, int B, const void* dy, int dy_ldc, int dy_coff, long dy_bstride);
 static ConvArgs dgrad_plan_args(ys_model* m, const ConvL& c, int B, bool f8) {
   const Buf& ob = m->bufs[c.out.buf];
   ConvArgs a = c.bn ? dgrad_args(m, c, B, m->dy_scratch, c.cout, 0, (long)c.Hout * c.Wout)
@@ -2551,560 +2346,6 @@ int ys_model_forward_u8(ys_model* m, const uint8_t* images, int on_device, int b
   YS_TRY(ys_pack_input_u8_launch(st, m->dtype, src, batch, 3, h, w, m->d.height, m->d.width, m->epl, m->bufs[m->in_buf].act));
   YS_TRY(forward_impl(m, batch));
   m->have_fwd = true; m->fwd_training = m->training; m->have_loss = false; m->have_seg_loss = false;
-  return YS_OK;
-}
-
-int ys_model_get_output(ys_model* m, const char* key, float* host, size_t count) {
-  YS_REQUIRE(m && key && host, "ys_model_get_output: null argument");
-  YS_REQUIRE(!m->is_block, "ys_model_get_output: this handle is a block (use ys_block_forward / ys_block_backward)");
-  YS_REQUIRE(m->have_fwd, "ys_model_get_output: no forward has run");
-  hipStream_t st = m->ctx->stream;
-  const int B = m->B;
-  const std::string k(key);
-  const bool cls_key = k == "cls" || k == "dcls" || k == "logits";
-  if (m->cls != cls_key) {
-    ys_set_error(m->cls ? "ys_model_get_output: a classify model has the outputs \"cls\", \"logits\" and \"dcls\" (not '%s')"
-                        : "ys_model_get_output: '%s' is an output of classify models only", key);
-    return YS_ERR_INVALID_ARG;
-  }
-  if (cls_key) {
-    // Classify.forward (Head.cs:635-643): "cls" = logits in training, softmax(logits, 1) in eval; "logits" = the logits in both modes;
-    // "dcls" = d(loss) / d(logits) after ys_loss_classify.  All [B, nc].
-    YS_REQUIRE(count == (size_t)B * m->d.nc, "ys_model_get_output(%s): expected %zu elements", key, (size_t)B * m->d.nc);
-    YS_REQUIRE(k != "dcls" || m->have_loss, "ys_model_get_output(dcls): no loss has run");
-    if (k == "cls" && !m->fwd_training) {
-      YS_CHECK_HIP(hipMemcpyAsync(host, m->pred, count * 4, hipMemcpyDeviceToHost, st));
-    } else {
-      const Buf& b = m->bufs[m->logit_buf];
-      YS_TRY(ys_unpack_nchw_launch(st, m->dtype, k == "dcls" ? b.grad : b.act, b.ldc, 0, B, m->d.nc, 1, m->out_stage));
-      YS_CHECK_HIP(hipMemcpyAsync(host, m->out_stage, count * 4, hipMemcpyDeviceToHost, st));
-    }
-  } else if (k == "boxes" || k == "scores") {
-    const bool bx = k == "boxes";
-    const int C = bx ? 4 * m->d.reg_max : m->d.nc;
-    YS_REQUIRE(count == (size_t)B * C * m->A, "ys_model_get_output(%s): expected %zu elements", key, (size_t)B * C * m->A);
-    const Buf& b = m->bufs[bx ? m->pd_buf : m->ps_buf];
-    YS_TRY(ys_unpack_nchw_launch(st, m->dtype, b.act, b.ldc, 0, B, C, m->A, m->out_stage));
-    YS_CHECK_HIP(hipMemcpyAsync(host, m->out_stage, count * 4, hipMemcpyDeviceToHost, st));
-  } else if (k == "dboxes" || k == "dscores") {
-    const bool bx = k == "dboxes";
-    const int C = bx ? 4 * m->d.reg_max : m->d.nc;
-    YS_REQUIRE(m->have_loss, "ys_model_get_output(%s): no loss has run", key);
-    YS_REQUIRE(count == (size_t)B * C * m->A, "ys_model_get_output(%s): expected %zu elements", key, (size_t)B * C * m->A);
-    const Buf& b = m->bufs[bx ? m->pd_buf : m->ps_buf];
-    YS_TRY(ys_unpack_nchw_launch(st, m->dtype, b.grad, b.ldc, 0, B, C, m->A, m->out_stage));
-    YS_CHECK_HIP(hipMemcpyAsync(host, m->out_stage, count * 4, hipMemcpyDeviceToHost, st));
-  } else if (k == "one2one_boxes" || k == "one2one_scores" || k == "one2one_dboxes" || k == "one2one_dscores") {
-    // End2End: the one2one towers alias cv2 / cv3 and read the same values (Head.cs:94-96, 152-167), so their outputs are the one2many
-    // buffers; their criterion pass (tal_topk 1) has gradient buffers of its own
-    YS_REQUIRE(m->e2e, "ys_model_get_output(%s): not an End2End model (ys_model_one2one_init)", key);
-    const bool g = k[8] == 'd', bx = k.find("boxes") != std::string::npos;
-    const int C = bx ? 4 * m->d.reg_max : m->d.nc;
-    YS_REQUIRE(!g || m->have_loss, "ys_model_get_output(%s): no loss has run", key);
-    YS_REQUIRE(count == (size_t)B * C * m->A, "ys_model_get_output(%s): expected %zu elements", key, (size_t)B * C * m->A);
-    const Buf& b = m->bufs[bx ? m->pd_buf : m->ps_buf];
-    const void* src = g ? (bx ? m->o2o_dpd : m->o2o_dps) : b.act;
-    YS_TRY(ys_unpack_nchw_launch(st, m->dtype, src, b.ldc, 0, B, C, m->A, m->out_stage));
-    YS_CHECK_HIP(hipMemcpyAsync(host, m->out_stage, count * 4, hipMemcpyDeviceToHost, st));
-  } else if (k == "det") {
-    // End2End eval forward: Detect.postprocess (Head.cs:117-127) -> [B, k, 6] = (x1, y1, x2, y2, score, class), k = min(max_det, A)
-    YS_REQUIRE(m->e2e, "ys_model_get_output(det): not an End2End model (ys_model_one2one_init)");
-    YS_REQUIRE(!m->fwd_training && !m->training, "ys_model_get_output(det): the last forward ran in training mode");
-    const size_t kk = (size_t)std::min(m->max_det, m->A);
-    const size_t rl = (size_t)(6 + (m->e2e_seg || m->e2e_obb ? m->nm : 0));      // End2End Segment: + the nm mask coefficients of the anchor (Head.cs:321-339); OBB: + the angle (Head.cs:439-452)
-    YS_REQUIRE(count == (size_t)B * kk * rl, "ys_model_get_output(det): expected %zu elements", (size_t)B * kk * rl);
-    YS_CHECK_HIP(hipMemcpyAsync(host, m->det_rows, count * 4, hipMemcpyDeviceToHost, st));
-  } else if (m->segment && (k == "one2one_mask_coefficient" || k == "one2one_dmask_coefficient")) {
-    // End2End Segment: cv4 is aliased like cv2 / cv3, so the one2one coefficients ARE the one2many ones; the second criterion pass has its own gradient
-    YS_REQUIRE(m->e2e_seg, "ys_model_get_output(%s): not an End2End Segment model (ys_model_e2e_init)", key);
-    const bool g = k[8] == 'd';
-    YS_REQUIRE(!g || m->have_seg_loss, "ys_model_get_output(%s): no segment loss has run", key);
-    YS_REQUIRE(count == (size_t)B * m->nm * m->A, "ys_model_get_output(%s): expected %zu elements", key, (size_t)B * m->nm * m->A);
-    const Buf& b = m->bufs[m->mc_buf];
-    YS_TRY(ys_unpack_nchw_launch(st, m->dtype, g ? m->o2o_dmc : b.act, b.ldc, 0, B, m->nm, m->A, m->out_stage));
-    YS_CHECK_HIP(hipMemcpyAsync(host, m->out_stage, count * 4, hipMemcpyDeviceToHost, st));
-  } else if (m->xkind == 2 && (k == "one2one_angle" || k == "one2one_dangle")) {
-    // End2End OBB: cv4 is aliased like cv2 / cv3 (Head.cs:454-469), so the one2one angle IS the one2many one; the second criterion pass has its own gradient
-    YS_REQUIRE(m->e2e_obb, "ys_model_get_output(%s): not an End2End OBB model (ys_model_e2e_obb_init)", key);
-    const bool g = k[8] == 'd';
-    YS_REQUIRE(!g || m->have_seg_loss, "ys_model_get_output(%s): the model's criterion has not run", key);
-    YS_REQUIRE(count == (size_t)B * m->nm * m->A, "ys_model_get_output(%s): expected %zu elements", key, (size_t)B * m->nm * m->A);
-    const Buf& b = m->bufs[m->mc_buf];
-    YS_TRY(ys_unpack_nchw_launch(st, m->dtype, g ? m->o2o_dmc : b.act, b.ldc, 0, B, m->nm, m->A, m->out_stage));
-    if (!g) YS_TRY(ys_obb_angle_launch(st, m->out_stage, (long)count));
-    YS_CHECK_HIP(hipMemcpyAsync(host, m->out_stage, count * 4, hipMemcpyDeviceToHost, st));
-  } else if (m->segment && (k == "mask_coefficient" || k == "dmask_coefficient")) {   // Head.cs:290-296: [B][nm][A]
-    const bool g = k[0] == 'd';
-    YS_REQUIRE(!g || m->have_seg_loss, "ys_model_get_output(%s): no segment loss has run", key);
-    YS_REQUIRE(count == (size_t)B * m->nm * m->A, "ys_model_get_output(%s): expected %zu elements", key, (size_t)B * m->nm * m->A);
-    const Buf& b = m->bufs[m->mc_buf];
-    YS_TRY(ys_unpack_nchw_launch(st, m->dtype, g ? b.grad : b.act, b.ldc, 0, B, m->nm, m->A, m->out_stage));
-    YS_CHECK_HIP(hipMemcpyAsync(host, m->out_stage, count * 4, hipMemcpyDeviceToHost, st));
-  } else if (m->segment && (k == "proto" || k == "dproto")) {                           // Head.cs:289: [B][nm][mh][mw]
-    const bool g = k[0] == 'd';
-    const long np = (long)m->mh * m->mw;
-    YS_REQUIRE(!g || m->have_seg_loss, "ys_model_get_output(%s): no segment loss has run", key);
-    YS_REQUIRE(count == (size_t)B * m->nm * np, "ys_model_get_output(%s): expected %zu elements", key, (size_t)B * m->nm * np);
-    const Buf& b = m->bufs[m->pr_buf];
-    YS_TRY(ys_unpack_nchw_launch(st, m->dtype, g ? b.grad : b.act, b.ldc, 0, B, m->nm, np, m->out_stage));
-    YS_CHECK_HIP(hipMemcpyAsync(host, m->out_stage, count * 4, hipMemcpyDeviceToHost, st));
-  } else if ((m->xkind == 3 && k == "dkpts") || (m->xkind == 2 && k == "dangle")) {   // d(sum(loss * B)) / d(raw kpts | angle LOGIT) [B][nk|1][A]
-    YS_REQUIRE(m->have_seg_loss, "ys_model_get_output(%s): the model's criterion has not run", key);
-    YS_REQUIRE(count == (size_t)B * m->nm * m->A, "ys_model_get_output(%s): expected %zu elements", key, (size_t)B * m->nm * m->A);
-    const Buf& b = m->bufs[m->mc_buf];
-    YS_TRY(ys_unpack_nchw_launch(st, m->dtype, b.grad, b.ldc, 0, B, m->nm, m->A, m->out_stage));
-    YS_CHECK_HIP(hipMemcpyAsync(host, m->out_stage, count * 4, hipMemcpyDeviceToHost, st));
-  } else if ((m->xkind == 2 && k == "angle") || (m->xkind == 3 && k == "kpts")) {
-    // Obb.forward_head: angle = (sigmoid(cat cv4) - 0.25) * pi [B][ne][A] (Head.cs:421-433); Pose.forward_head: raw kpts [B][nk][A] (:531-543)
-    YS_REQUIRE(count == (size_t)B * m->nm * m->A, "ys_model_get_output(%s): expected %zu elements", key, (size_t)B * m->nm * m->A);
-    const Buf& b = m->bufs[m->mc_buf];
-    YS_TRY(ys_unpack_nchw_launch(st, m->dtype, b.act, b.ldc, 0, B, m->nm, m->A, m->out_stage));
-    if (m->xkind == 2) YS_TRY(ys_obb_angle_launch(st, m->out_stage, (long)count));
-    YS_CHECK_HIP(hipMemcpyAsync(host, m->out_stage, count * 4, hipMemcpyDeviceToHost, st));
-  } else if (k == "pred") {
-    const size_t pc = (size_t)(4 + m->d.nc + m->nm);
-    YS_REQUIRE(!m->training, "ys_model_get_output(pred): model is in training mode (Detect returns preds only, Head.cs:103-106)");
-    YS_REQUIRE(count == (size_t)B * pc * m->A, "ys_model_get_output(pred): expected %zu elements", (size_t)B * pc * m->A);
-    YS_CHECK_HIP(hipMemcpyAsync(host, m->pred, count * 4, hipMemcpyDeviceToHost, st));
-  } else {
-    ys_set_error("ys_model_get_output: unknown key '%s'", key);
-    return YS_ERR_INVALID_ARG;
-  }
-  YS_CHECK_HIP(hipStreamSynchronize(st));
-  return YS_OK;
-}
-
-// The criterion's `preds` argument supplied by the caller (Loss.cs:411 `forward(preds, batch)`): head outputs in the reference layout
-// -- boxes [B, 4*reg_max, A], scores [B, nc, A] and, for Segment models, mask_coefficient [B, nm, A] and proto [B, nm, H/4, W/4] --
-// are packed into the engine's head buffers as if a forward had produced them.  ys_loss_detect / ys_loss_segment and the
-// "dboxes" / "dscores" / ... gradient outputs then work on them; ys_model_backward is refused (no graph state behind these preds).
-int ys_model_set_preds(ys_model* m, int batch, const float* boxes, const float* scores, const float* mask_coefficient, const float* proto) {
-  YS_REQUIRE(m && !m->is_block && boxes && scores, "ys_model_set_preds: null argument or block handle");
-  YS_REQUIRE(!m->cls, "ys_model_set_preds: a classify model has no detection outputs (its criterion is ys_loss_classify)");
-  YS_REQUIRE(batch > 0 && batch <= m->maxB, "ys_model_set_preds: batch %d outside (0, %d]", batch, m->maxB);
-  YS_REQUIRE(!m->segment || (mask_coefficient && proto), "ys_model_set_preds: a Segment model needs mask_coefficient and proto");
-  YS_REQUIRE(m->xkind < 2 || mask_coefficient, "ys_model_set_preds: a Pose / Obb model takes its raw kpts [B,nk,A] / angle LOGITS [B,1,A] in the mask_coefficient argument");
-  YS_CHECK_HIP(hipSetDevice(m->ctx->device));
-  hipStream_t st = m->ctx->stream;
-  struct Item { const float* src; int buf; int C; long rows; } items[4] = {
-    {boxes, m->pd_buf, 4 * m->d.reg_max, m->A}, {scores, m->ps_buf, m->d.nc, m->A},
-    {m->segment || m->xkind >= 2 ? mask_coefficient : nullptr, m->mc_buf, m->nm, m->A}, {m->segment ? proto : nullptr, m->pr_buf, m->nm, (long)m->mh * m->mw}};
-  for (const Item& it : items) {
-    if (!it.src) continue;
-    const Buf& b = m->bufs[it.buf];
-    const size_t cnt = (size_t)batch * it.C * it.rows;
-    YS_REQUIRE((long)cnt <= m->n_out_stage, "ys_model_set_preds: staging buffer too small");
-    YS_CHECK_HIP(hipMemcpyAsync(m->out_stage, it.src, cnt * 4, hipMemcpyHostToDevice, st));
-    YS_TRY(ys_pack_input_launch(st, m->dtype, m->out_stage, batch, it.C, 1, (int)it.rows, b.ldc, b.act));
-    YS_CHECK_HIP(hipStreamSynchronize(st));   // out_stage is reused by the next item
-  }
-  m->B = batch; m->have_fwd = true; m->fwd_training = false; m->have_loss = false; m->have_seg_loss = false;
-  return YS_OK;
-}
-
-int ys_model_pred_device(ys_model* m, float** dptr) {
-  YS_REQUIRE(m && dptr, "null argument");
-  *dptr = m->pred;
-  return YS_OK;
-}
-
-// YoloBaseTaskModel.One2one_Init -> Detect.one2one_init (Head.cs:152-167): the one2one towers are the SAME Sequential objects as cv2 / cv3
-// (CopyTo copies references), so the model gains no tensor -- only the second criterion pass's gradient / scalar buffers, the snapshot of
-// the towers' running statistics (their second momentum update) and the top-k output of the eval forward.
-static int e2e_init_impl(ys_model* m, int max_det, bool seg, bool obb = false) {
-  YS_CHECK_HIP(hipSetDevice(m->ctx->device));
-  const int B = m->maxB;
-  m->max_det = max_det > 0 ? max_det : 300;     // Detect.max_det (Head.cs:13)
-  const int k = std::min(m->max_det, m->A);
-  const Buf &pb = m->bufs[m->pd_buf], &sb = m->bufs[m->ps_buf];
-  YS_TRY(dev_alloc(m, &m->o2o_dpd, (size_t)B * pb.rows_per_b * pb.ldc * m->es));
-  YS_TRY(dev_alloc(m, &m->o2o_dps, (size_t)B * sb.rows_per_b * sb.ldc * m->es));
-  if (seg || obb) { const Buf& cb = m->bufs[m->mc_buf]; YS_TRY(dev_alloc(m, &m->o2o_dmc, (size_t)B * cb.rows_per_b * cb.ldc * m->es)); }
-  YS_TRY(dev_alloc(m, (void**)&m->scalars2, 64 * 4 + 64 * 8 * 8));
-  YS_TRY(dev_alloc(m, (void**)&m->det_rows, (size_t)B * k * (6 + (seg || obb ? m->nm : 0)) * 4));
-  YS_TRY(dev_alloc(m, (void**)&m->det_anchor, (size_t)B * k * 8));
-  YS_TRY(dev_alloc(m, &m->det_ws, ys_e2e_topk_ws_bytes(B, m->d.nc, m->A, m->max_det)));
-  // the towers' BatchNorm state as contiguous runs of `state`.  A Detect head's units are the last of `convs` and their state is the tail of `state`: one
-  // run.  In a Segment head Proto's units sit between cv3 and cv4; Proto runs once per forward (Head.cs:283-307), so its words are in no run.
-  std::vector<std::pair<long, long>> iv;        // [begin, end) words of every tower unit
-  for (size_t i = (size_t)m->head_conv0; i < m->convs.size(); i++) {
-    const ConvL& c = m->convs[i];
-    if (!c.bn || c.proto) continue;
-    iv.push_back({c.rm_off, c.rm_off + c.cout}); iv.push_back({c.rv_off, c.rv_off + c.cout}); iv.push_back({c.nbt_off, c.nbt_off + 1});
-  }
-  std::sort(iv.begin(), iv.end());
-  m->n_hstate_rng = 0; m->n_hstate = 0;
-  for (auto& v : iv) {
-    if (m->n_hstate_rng > 0 && m->hstate_rng[m->n_hstate_rng - 1].off + m->hstate_rng[m->n_hstate_rng - 1].count == v.first) { m->hstate_rng[m->n_hstate_rng - 1].count += v.second - v.first; }
-    else {
-      if (m->n_hstate_rng == 4) { ys_set_error("ys_model_e2e_init: internal: the towers' statistics lie in more than 4 runs of the state"); return YS_ERR_STATE; }
-      m->hstate_rng[m->n_hstate_rng++] = ys_model::Range{v.first, v.second - v.first};
-    }
-    m->n_hstate += v.second - v.first;
-  }
-  for (int i = 0; i < (int)m->convs.size(); i++) {          // no other unit's state inside a run
-    const ConvL& c = m->convs[i];
-    if (!c.bn || (i >= m->head_conv0 && !c.proto)) continue;
-    for (int r = 0; r < m->n_hstate_rng; r++)
-      if (c.rm_off < m->hstate_rng[r].off + m->hstate_rng[r].count && c.nbt_off >= m->hstate_rng[r].off) { ys_set_error("ys_model_e2e_init: internal: %s lies inside the towers' statistics", c.name.c_str()); return YS_ERR_STATE; }
-  }
-  if (m->n_hstate > 0) {
-    std::vector<unsigned char> isc((size_t)m->n_hstate, 0);
-    long so = 0;
-    for (int r = 0; r < m->n_hstate_rng; r++) {
-      for (size_t i = (size_t)m->head_conv0; i < m->convs.size(); i++) {
-        const ConvL& c = m->convs[i];
-        if (c.bn && !c.proto && c.nbt_off >= m->hstate_rng[r].off && c.nbt_off < m->hstate_rng[r].off + m->hstate_rng[r].count) isc[(size_t)(so + c.nbt_off - m->hstate_rng[r].off)] = 1;
-      }
-      so += m->hstate_rng[r].count;
-    }
-    YS_TRY(dev_alloc(m, (void**)&m->hstate_snap, (size_t)m->n_hstate * 4));
-    YS_TRY(dev_alloc(m, (void**)&m->hstate_count, (size_t)m->n_hstate));
-    YS_CHECK_HIP(hipMemcpyAsync(m->hstate_count, isc.data(), isc.size(), hipMemcpyHostToDevice, m->ctx->stream));
-    YS_CHECK_HIP(hipStreamSynchronize(m->ctx->stream));
-  }
-  m->e2e = true; m->e2e_seg = seg; m->e2e_obb = obb;
-  m->have_fwd = false; m->have_loss = false; m->have_seg_loss = false;      // "pred" changes its box format: a forward from before the switch is not an End2End one
-  return YS_OK;
-}
-
-int ys_model_one2one_init(ys_model* m, int max_det) {
-  YS_REQUIRE(m, "ys_model_one2one_init: null model");
-  YS_REQUIRE(max_det >= 0, "ys_model_one2one_init: max_det = %d", max_det);
-  if (m->is_block || m->is_head || m->cls || m->d.task != YS_DETECT || m->pd_buf < 0) {
-    ys_set_error("ys_model_one2one_init: End2End through this entry is built for full Detect models (Segment models: ys_model_e2e_init; OBB / Pose End2End and the standalone heads are follow-ups)");
-    return YS_ERR_UNSUPPORTED;
-  }
-  if (m->e2e) { ys_set_error("ys_model_one2one_init: already initialised"); return YS_ERR_STATE; }
-  return e2e_init_impl(m, max_det, false);
-}
-
-// One2one_Init for Detect AND Segment models (Models/Segmenter.cs:17-24; Segment.one2one_init, Head.cs:245-357: cv2, cv3 and cv4 aliased).  epochs:
-// the length of E2ESegmentLoss's gain schedule (Loss.cs:1192-1210); ignored by Detect models, whose criterion is unweighted.
-int ys_model_e2e_init(ys_model* m, int max_det, int epochs) {
-  YS_REQUIRE(m, "ys_model_e2e_init: null model");
-  YS_REQUIRE(max_det >= 0 && epochs >= 0, "ys_model_e2e_init: max_det = %d, epochs = %d", max_det, epochs);
-  const bool det = !m->is_block && !m->is_head && !m->cls && m->d.task == YS_DETECT && m->pd_buf >= 0;
-  const bool seg = !m->is_block && !m->is_head && !m->cls && m->d.task == YS_SEGMENT && m->segment && m->pd_buf >= 0 && m->mc_buf >= 0;
-  if (!det && !seg) {
-    ys_set_error("ys_model_e2e_init: End2End is built for full Detect and Segment models (OBB / Pose End2End and the standalone heads are follow-ups)");
-    return YS_ERR_UNSUPPORTED;
-  }
-  if (m->e2e) { ys_set_error("ys_model_e2e_init: already initialised"); return YS_ERR_STATE; }
-  YS_TRY(e2e_init_impl(m, max_det, seg));
-  if (seg) { m->e2e_epochs = epochs > 0 ? epochs : 100; m->e2e_updates = 0; m->o2m = 0.8f; m->o2o = 1.0f - 0.8f; }   // Loss.cs:1197-1207
-  return YS_OK;
-}
-
-// One2one_Init for OBB models (Models/Obber.cs:18-24; Obb.one2one_init, Head.cs:454-469: cv2, cv3 and cv4 aliased, no Proto; E2EOBBLoss, Loss.cs:1120-1177).
-// An entry of its own: ys_model_one2one_init and ys_model_e2e_init keep refusing OBB models.
-int ys_model_e2e_obb_init(ys_model* m, int max_det, int epochs) {
-  YS_REQUIRE(m, "ys_model_e2e_obb_init: null model");
-  YS_REQUIRE(max_det >= 0 && epochs >= 0, "ys_model_e2e_obb_init: max_det = %d, epochs = %d", max_det, epochs);
-  if (m->is_block || m->is_head || m->cls || m->d.task != YS_OBB || m->xkind != 2 || m->pd_buf < 0 || m->mc_buf < 0) {
-    ys_set_error("ys_model_e2e_obb_init: this entry is One2one_Init for full OBB models (Detect: ys_model_one2one_init; Segment: ys_model_e2e_init; Pose End2End is a follow-up)");
-    return YS_ERR_UNSUPPORTED;
-  }
-  if (m->e2e) { ys_set_error("ys_model_e2e_obb_init: already initialised"); return YS_ERR_STATE; }
-  YS_TRY(e2e_init_impl(m, max_det, false, true));
-  m->e2e_epochs = epochs > 0 ? epochs : 100; m->e2e_updates = 0; m->o2m = 0.8f; m->o2o = 1.0f - 0.8f;   // Loss.cs:1138-1148
-  return YS_OK;
-}
-
-// E2ESegmentLoss.update() (Loss.cs:1225-1235) and E2EOBBLoss.update() (Loss.cs:1166-1176), the same chain.  The reference's training loop calls update() for E2EOBBLoss only (YoloBaseTaskModel.cs:350-353), so a
-// Segment run of the reference keeps 0.8 / 0.2 for its whole life; callers that want the schedule call this once per epoch.
-int ys_model_e2e_update(ys_model* m) {
-  YS_REQUIRE(m, "ys_model_e2e_update: null model");
-  YS_REQUIRE(m->e2e, "ys_model_e2e_update: not an End2End model (ys_model_e2e_init)");
-  if (!m->e2e_seg && !m->e2e_obb) return YS_OK;  // E2EDetectLoss has no gains
-  m->e2e_updates += 1;
-  const int den = m->e2e_epochs - 1 > 1 ? m->e2e_epochs - 1 : 1;
-  const float r = 1.0f - (float)m->e2e_updates / (float)den;
-  m->o2m = (r > 0.f ? r : 0.f) * (0.8f - 0.1f) + 0.1f;
-  const float o = 1.0f - m->o2m;
-  m->o2o = o > 0.f ? o : 0.f;
-  return YS_OK;
-}
-
-int ys_model_e2e_gains(ys_model* m, float* o2m, float* o2o) {
-  YS_REQUIRE(m && o2m && o2o, "ys_model_e2e_gains: null argument");
-  YS_REQUIRE(m->e2e, "ys_model_e2e_gains: not an End2End model (ys_model_e2e_init)");
-  *o2m = m->o2m; *o2o = m->o2o;
-  return YS_OK;
-}
-
-int ys_model_det_device(ys_model* m, float** rows, int* k) {
-  YS_REQUIRE(m && rows && k, "ys_model_det_device: null argument");
-  YS_REQUIRE(m->e2e, "ys_model_det_device: not an End2End model (ys_model_one2one_init / ys_model_e2e_init)");
-  *rows = m->det_rows; *k = std::min(m->max_det, m->A);
-  return YS_OK;
-}
-
-int ys_model_reserve_labels(ys_model* m, int per_image) {
-  YS_REQUIRE(m && !m->is_block, "ys_model_reserve_labels: needs a full model");
-  YS_REQUIRE(per_image > 0, "ys_model_reserve_labels: per_image = %d", per_image);
-  if (per_image <= m->gcap) return YS_OK;
-  YS_CHECK_HIP(hipSetDevice(m->ctx->device));
-  m->have_loss = false; m->have_seg_loss = false;
-  return alloc_label_ws(m, (per_image + 15) / 16 * 16);
-}
-
-static int loss_detect_core(ys_model* m, const float* batch_idx, const float* cls, const float* bboxes, int n, int on_device, bool aux_follows);
-
-int ys_loss_detect(ys_model* m, const float* batch_idx, const float* cls, const float* bboxes, int n, int on_device) {
-  return loss_detect_core(m, batch_idx, cls, bboxes, n, on_device, false);
-}
-
-static int loss_detect_core(ys_model* m, const float* batch_idx, const float* cls, const float* bboxes, int n, int on_device, bool aux_follows) {
-  YS_REQUIRE(m, "null model");
-  // Training forward -> the criterion feeds backward (Amp.cs:338-348).  Eval forward -> validation loss on the eval-mode preds
-  // (Detector.cs:94-97): the head logits are produced in both modes; only backward needs the training-mode state.
-  YS_REQUIRE(!m->is_block && m->have_fwd, "ys_loss_detect: needs a forward of a full model first");
-  YS_REQUIRE(!m->cls, "ys_loss_detect: a classify model's criterion is ys_loss_classify (Loss.cs:1073-1091)");
-  YS_REQUIRE(m->xkind != 2 || aux_follows, "ys_loss_detect: an OBB model's criterion is ys_loss_obb (oriented labels, Loss.cs:486-684)");
-  YS_REQUIRE(m->xkind != 3 || aux_follows, "ys_loss_detect: a Pose model's criterion is ys_loss_pose (keypoint terms, Loss.cs:870-1071)");
-  YS_REQUIRE(!m->e2e_seg || aux_follows, "ys_loss_detect: an End2End Segment model's criterion is ys_loss_segment (E2ESegmentLoss: two detect passes and two mask terms, Loss.cs:1179-1236)");
-  const bool rot = m->xkind == 2;
-  const size_t lbytes = rot ? 20 : 16;
-  YS_REQUIRE(n >= 0, "ys_loss_detect: n_labels = %d", n);
-  YS_REQUIRE(n == 0 || (batch_idx && cls && bboxes), "ys_loss_detect: null label arrays");
-  YS_CHECK_HIP(hipSetDevice(m->ctx->device));
-  hipStream_t st = m->ctx->stream;
-  const float *bi = batch_idx, *cl = cls, *bb = bboxes;
-  int host_cmax = 0;                           // host labels: the largest per-image count (0 = unknown)
-  if (!on_device && n > 0) {
-    // host labels: size the padded GT workspace from the batch itself, like the reference's counts.max() (Loss.cs:376-380)
-    std::vector<int> cnt(m->B, 0);
-    int mx = 0;
-    for (int i = 0; i < n; i++) { const int b = (int)batch_idx[i]; if (b >= 0 && b < m->B) mx = std::max(mx, ++cnt[b]); }
-    // every label row is staged (rows whose batch_idx lies outside [0, B) are ignored by the kernels, like the reference's
-    // `batch_idx == j` matches): the staging arrays hold gcap * max_batch rows, so n itself bounds the capacity too
-    host_cmax = mx > 0 ? mx : 1;
-    const int per_rows = (n + m->maxB - 1) / m->maxB;
-    if (per_rows > mx) mx = per_rows;
-    if (mx > m->gcap) YS_TRY(alloc_label_ws(m, (mx + 15) / 16 * 16));
-    YS_REQUIRE(n <= m->max_labels, "ys_loss_detect: %d label rows exceed the staging capacity %d", n, m->max_labels);
-    YS_CHECK_HIP(hipMemcpyAsync(m->lab_bidx, batch_idx, (size_t)n * 4, hipMemcpyHostToDevice, st));
-    YS_CHECK_HIP(hipMemcpyAsync(m->lab_cls, cls, (size_t)n * 4, hipMemcpyHostToDevice, st));
-    YS_CHECK_HIP(hipMemcpyAsync(m->lab_box, bboxes, (size_t)n * lbytes, hipMemcpyHostToDevice, st));
-    bi = m->lab_bidx; cl = m->lab_cls; bb = m->lab_box;
-  }
-  YsTimer timer(m->ctx, "loss");
-  LossArgs a{};
-  a.pd = m->bufs[m->pd_buf].act; a.ps = m->bufs[m->ps_buf].act; a.dpd = m->bufs[m->pd_buf].grad; a.dps = m->bufs[m->ps_buf].grad;
-  a.ld_pd = m->ld_pd; a.ld_ps = m->ld_ps; a.B = m->B; a.A = m->A; a.nc = m->d.nc; a.reg_max = m->d.reg_max;
-  a.H = m->d.height; a.W = m->d.width; a.nl = m->nl;
-  for (int i = 0; i < 4; i++) { a.lvl_off[i] = m->lvl_off[i]; a.lvl_w[i] = m->lvl_w[i]; a.lvl_h[i] = m->lvl_h[i]; a.lvl_stride[i] = m->lvl_stride[i]; }
-  a.batch_idx = bi; a.cls = cl; a.bboxes = bb; a.n_labels = n; a.gcap = m->gcap;
-  a.gmax = (host_cmax > 0 && host_cmax < m->gcap) ? host_cmax : m->gcap;
-  a.gt_count = m->gt_count; a.gt_box = m->gt_box; a.gt_cls = m->gt_cls; a.pbox = m->pbox; a.ov = m->ov; a.align = m->align;
-  a.mpos = m->mpos; a.pos_align = m->pos_align; a.pos_ov = m->pos_ov; a.fg_gt = m->fg_gt; a.tnorm = m->tnorm;
-  a.partial = m->loss_partial; a.scalars = m->scalars;
-  a.hyp_box = 7.5f; a.hyp_cls = 0.5f; a.hyp_dfl = 1.5f; a.topk = 10;   // Loss.cs:344,357
-  // E2ESegmentLoss (Loss.cs:1222): loss = o2m * L_one2many + o2o * L_one2one.  Items and gradients are linear in the hyp_* factors, so the gain rides on
-  // them: no scale pass over any buffer
-  if (m->e2e_seg || m->e2e_obb) { a.hyp_box *= m->o2m; a.hyp_cls *= m->o2m; a.hyp_dfl *= m->o2m; }
-  if (rot) {                                                             // Loss.cs:489: hyp_angle = 1
-    const Buf& ab = m->bufs[m->mc_buf];
-    a.rot = 1; a.pa = ab.act; a.dpa = ab.grad; a.ld_pa = m->ld_mc; a.hyp_angle = m->e2e_obb ? m->o2m : 1.0f;
-  }
-  YS_TRY(ys_loss_detect_launch(st, m->dtype, a));
-  if (m->e2e_seg) m->seg_pass2 = a;        // ys_loss_segment runs the mask term on this assignment first, then the second pass
-  if (m->e2e_obb) {
-    // E2EOBBLoss (Loss.cs:1120-1177): o2m * v8OBBLoss(tal_topk 10)(one2many) + o2o * v8OBBLoss(tal_topk 7, tal_topk2 1)(one2one) on the same head outputs
-    // (aliased towers).  The second pass pads its own GT again (loss_prep_body: the thin-box widening of Tal.cs:283-287 lands in a fresh tensor, as in the
-    // reference where each criterion calls preprocess itself), reuses the assignment workspaces and writes gradients and scalars of its own.
-    a.topk = 7; a.topk2 = 1; a.dpd = m->o2o_dpd; a.dps = m->o2o_dps; a.dpa = m->o2o_dmc; a.scalars = m->scalars2;
-    a.hyp_box = 7.5f * m->o2o; a.hyp_cls = 0.5f * m->o2o; a.hyp_dfl = 1.5f * m->o2o; a.hyp_angle = m->o2o;
-    YS_TRY(ys_loss_detect_launch(st, m->dtype, a));
-  }
-  if (m->e2e && !m->e2e_seg && !m->e2e_obb) {
-    // E2EDetectLoss (Loss.cs:1094-1118): v8DetectionLoss(tal_topk 10) on one2many + v8DetectionLoss(tal_topk 1) on one2one, unweighted.
-    // The one2one head outputs ARE the one2many ones (aliased towers, same input values), so the second pass reads the same pd / ps and
-    // differs only in the assigner's topk.  It reuses the first pass's assignment workspaces: the stream is in order, and nothing after
-    // the first pass reads them again -- what outlives a pass are its gradients and its scalars, and those get buffers of their own.
-    a.topk = 1; a.dpd = m->o2o_dpd; a.dps = m->o2o_dps; a.scalars = m->scalars2;
-    YS_TRY(ys_loss_detect_launch(st, m->dtype, a));
-  }
-  YS_CHECK_HIP(hipGetLastError());
-  m->have_loss = true;
-  return YS_OK;
-}
-
-// End2End: the items / loss of the one2one criterion pass are added to the one2many ones (Loss.cs:1113-1117)
-static int add_o2o_items(ys_model* m, float h[16]) {
-  if (!m->e2e) return YS_OK;
-  float g[16];
-  YS_CHECK_HIP(hipMemcpyAsync(g, m->scalars2, sizeof(g), hipMemcpyDeviceToHost, m->ctx->stream));
-  YS_CHECK_HIP(hipStreamSynchronize(m->ctx->stream));
-  for (int i = 1; i <= 4; i++) h[i] += g[i];
-  if (m->e2e_seg) h[8] += g[8];            // the mask term (both already carry their gain)
-  if (m->e2e_obb) h[13] += g[13];          // the angle term
-  return YS_OK;
-}
-
-// v8SegmentationLoss (Loss.cs:711-780): detection part + assignment (loss.hip), then the mask term (segloss.hip).
-// masks: [B][mh][mw] fp32, overlap-encoded instance ids (0 = background, g+1 = the image's g-th label; YoloDataset.cs:265-267).
-int ys_loss_segment(ys_model* m, const float* batch_idx, const float* cls, const float* bboxes, int n, const float* masks, int on_device,
-                    int crop_mode) {
-  YS_REQUIRE(m && m->segment, "ys_loss_segment: model has no Segment head");
-  YS_REQUIRE(masks, "ys_loss_segment: null masks");
-  YS_TRY(loss_detect_core(m, batch_idx, cls, bboxes, n, on_device, true));
-  m->have_loss = false;
-  hipStream_t st = m->ctx->stream;
-  const float* mk = masks;
-  if (!on_device) {
-    YS_CHECK_HIP(hipMemcpyAsync(m->masks_dev, masks, (size_t)m->B * m->mh * m->mw * 4, hipMemcpyHostToDevice, st));
-    mk = m->masks_dev;
-  }
-  YsTimer timer(m->ctx, "loss_seg");
-  const Buf& mc = m->bufs[m->mc_buf];
-  const Buf& pr = m->bufs[m->pr_buf];
-  YS_TRY(ys_loss_segment_launch(st, m->dtype, mc.act, mc.grad, m->ld_mc, pr.act, pr.grad, m->ld_pr, mk, m->fg_gt, m->gt_box, m->seg_cnt,
-                                m->seg_off, m->seg_list, m->seg_ent, m->seg_part, m->scalars, m->B, m->A, m->nm, m->mh, m->mw, m->gcap,
-                                m->d.height, m->d.width, crop_mode, m->e2e_seg ? m->o2m : 1.0f));
-  if (m->e2e_seg) {
-    // E2ESegmentLoss (Loss.cs:1179-1236): the one2one criterion = v8SegmentationLoss(tal_topk 7, tal_topk2 1) on the same head outputs (aliased towers).
-    // The mask term above has read the first assignment (fg_gt, gt_box, seg_*); the second detect pass may now overwrite those workspaces.  Its gradients
-    // and scalars have buffers of their own; its mask term writes the one2one coefficient gradient and NO prototype gradient (proto.detach(), Head.cs:297).
-    LossArgs a = m->seg_pass2;
-    a.topk = 7; a.topk2 = 1; a.dpd = m->o2o_dpd; a.dps = m->o2o_dps; a.scalars = m->scalars2;
-    a.hyp_box = 7.5f * m->o2o; a.hyp_cls = 0.5f * m->o2o; a.hyp_dfl = 1.5f * m->o2o;
-    YS_TRY(ys_loss_detect_launch(st, m->dtype, a));
-    YS_TRY(ys_loss_segment_launch(st, m->dtype, mc.act, m->o2o_dmc, m->ld_mc, pr.act, nullptr, m->ld_pr, mk, m->fg_gt, m->gt_box, m->seg_cnt,
-                                  m->seg_off, m->seg_list, m->seg_ent, m->seg_part, m->scalars2, m->B, m->A, m->nm, m->mh, m->mw, m->gcap,
-                                  m->d.height, m->d.width, crop_mode, m->o2o));
-  }
-  YS_CHECK_HIP(hipGetLastError());
-  m->have_loss = true; m->have_seg_loss = true;
-  return YS_OK;
-}
-
-// v8OBBLoss (Loss.cs:486-684): the loss.hip pipeline in its rotated mode (probiou assigner and box term, rbox2dist DFL targets,
-// angle term).  bboxes: fp32 [n][5] = normalised cx, cy, w, h + angle in radians.
-int ys_loss_obb(ys_model* m, const float* batch_idx, const float* cls, const float* bboxes, int n, int on_device) {
-  YS_REQUIRE(m && m->xkind == 2, "ys_loss_obb: model has no Obb head");
-  YS_TRY(loss_detect_core(m, batch_idx, cls, bboxes, n, on_device, true));
-  m->have_seg_loss = true;
-  return YS_OK;
-}
-
-// v8PoseLoss (Loss.cs:870-1071): detection part + assignment (loss.hip), then the keypoint terms (poseloss.hip).
-// keypoints: fp32 [n][kpt_num][kpt_dim] normalised to the image like bboxes (x, y[, visibility]); row i belongs to label i.
-int ys_loss_pose(ys_model* m, const float* batch_idx, const float* cls, const float* bboxes, int n, const float* keypoints, int on_device) {
-  YS_REQUIRE(m && m->xkind == 3, "ys_loss_pose: model has no Pose head");
-  YS_REQUIRE(n == 0 || keypoints, "ys_loss_pose: null keypoints");
-  if (!on_device && batch_idx)                 // keypoint rows are addressed by a label's rank within its image: collate order only
-    for (int i = 1; i < n; i++)
-      YS_REQUIRE(batch_idx[i] >= batch_idx[i - 1], "ys_loss_pose: labels must be grouped by image in collate order (batch_idx[%d] = %g < batch_idx[%d] = %g)",
-                 i, (double)batch_idx[i], i - 1, (double)batch_idx[i - 1]);
-  YS_TRY(loss_detect_core(m, batch_idx, cls, bboxes, n, on_device, true));
-  m->have_loss = false;
-  hipStream_t st = m->ctx->stream;
-  const float* kp = keypoints;
-  if (!on_device && n > 0) {
-    YS_REQUIRE(n <= m->max_labels, "ys_loss_pose: %d labels exceed the staging capacity %d", n, m->max_labels);
-    YS_CHECK_HIP(hipMemcpyAsync(m->kp_dev, keypoints, (size_t)n * m->nm * 4, hipMemcpyHostToDevice, st));
-    kp = m->kp_dev;
-  }
-  YsTimer timer(m->ctx, "loss_pose");
-  const Buf& kb = m->bufs[m->mc_buf];
-  PoseArgs a{};
-  a.kp = kb.act; a.dkp = kb.grad; a.ld = m->ld_mc; a.fg_gt = m->fg_gt; a.gt_box = m->gt_box;
-  a.gt_src = m->gt_cls + 2L * m->B * m->gcap;
-  a.keypoints = kp; a.part = m->seg_part; a.scalars = m->scalars;
-  a.B = m->B; a.A = m->A; a.K = m->nm / m->kdim; a.D = m->kdim; a.gcap = m->gcap; a.H = m->d.height; a.W = m->d.width; a.nl = m->nl;
-  for (int i = 0; i < 4; i++) { a.lvl_off[i] = m->lvl_off[i]; a.lvl_w[i] = m->lvl_w[i]; a.lvl_stride[i] = m->lvl_stride[i]; }
-  a.hyp_pose = 12.0f; a.hyp_kobj = 1.0f;                                                  // Loss.cs:896
-  static const float oks[17] = {0.026f, 0.025f, 0.025f, 0.035f, 0.035f, 0.079f, 0.079f, 0.072f, 0.072f, 0.062f, 0.062f, 0.107f, 0.107f,
-                                0.087f, 0.087f, 0.089f, 0.089f};                          // OKS_SIGMA (Loss.cs:9-16)
-  const bool coco = a.K == 17 && a.D == 3;                                                // Loss.cs:903-905
-  for (int k = 0; k < a.K && k < YS_POSE_KMAX; k++) a.sigma[k] = coco ? oks[k] : 1.0f / (float)a.K;
-  YS_TRY(ys_loss_pose_launch(st, m->dtype, a, m->seg_cnt, m->seg_off, m->seg_list));
-  YS_CHECK_HIP(hipGetLastError());
-  m->have_loss = true; m->have_seg_loss = true;
-  return YS_OK;
-}
-
-// v8ClassificationLoss (Loss.cs:1073-1091): cross_entropy(preds["cls"], batch["cls"].view(-1)), mean reduction, and d(loss)/d(logits)
-// = (softmax - onehot) / B into the logits' gradient buffer.  cls: fp32 class ids [batch].  Works after a training forward (the step) and
-// after an eval forward (Classifier.Val's loss on the eval logits, Classifier.cs:90-93).
-int ys_loss_classify(ys_model* m, const float* cls, int batch, int on_device) {
-  YS_REQUIRE(m && cls, "ys_loss_classify: null argument");
-  YS_REQUIRE(m->cls, "ys_loss_classify: the model has no Classify head (task %d)", m->d.task);
-  YS_REQUIRE(m->have_fwd, "ys_loss_classify: needs a forward first");
-  YS_REQUIRE(batch == m->B, "ys_loss_classify: batch %d differs from the last forward's %d", batch, m->B);
-  if (!on_device)
-    for (int i = 0; i < batch; i++)
-      YS_REQUIRE(cls[i] >= 0.f && cls[i] < (float)m->d.nc && cls[i] == floorf(cls[i]), "ys_loss_classify: label %g of image %d is not a class id in [0, %d)",
-                 (double)cls[i], i, m->d.nc);
-  YS_CHECK_HIP(hipSetDevice(m->ctx->device));
-  hipStream_t st = m->ctx->stream;
-  const float* lab = cls;
-  if (!on_device) { YS_CHECK_HIP(hipMemcpyAsync(m->cls_lab, cls, (size_t)batch * 4, hipMemcpyHostToDevice, st)); lab = m->cls_lab; }
-  YsTimer timer(m->ctx, "loss");
-  const Buf& lb = m->bufs[m->logit_buf];
-  YS_TRY(ys_cls_xent_launch(st, m->dtype, lb.act, m->ld_cls, batch, m->d.nc, lab, lb.grad, nullptr, m->cls_rows, m->scalars));
-  YS_CHECK_HIP(hipGetLastError());
-  m->have_loss = true; m->have_seg_loss = true;
-  return YS_OK;
-}
-
-// device-resident labels cannot size the workspace without a host sync: the prep kernel records the batch's largest per-image
-// label count and the first synchronising read refuses a truncated assignment instead of returning it
-static int check_label_overflow(ys_model* m, float max_count) {
-  if ((int)max_count <= m->gcap) return YS_OK;
-  m->have_loss = false; m->have_seg_loss = false;
-  ys_set_error("loss: an image of this batch has %d labels but the workspace holds %d per image (the reference pads to the batch maximum, "
-               "Loss.cs:363-390): call ys_model_reserve_labels(model, %d) or pass max_labels at creation, then repeat the step",
-               (int)max_count, m->gcap, (int)max_count);
-  return YS_ERR_INVALID_ARG;
-}
-
-// loss items in the reference's order: detect [box, cls, dfl] (Loss.cs:414); segment [box, seg, cls, dfl, semseg] (Loss.cs:719)
-int ys_loss_read_items(ys_model* m, float* items, int n_items, float* loss_sum) {
-  YS_REQUIRE(m && m->have_loss, "ys_loss_read_items: no loss has run");
-  YS_REQUIRE(items && n_items == m->n_items, "ys_loss_read_items: this model's criterion has %d items", m->n_items);
-  float h[16];
-  YS_CHECK_HIP(hipMemcpyAsync(h, m->scalars, sizeof(h), hipMemcpyDeviceToHost, m->ctx->stream));
-  YS_CHECK_HIP(hipStreamSynchronize(m->ctx->stream));
-  if (m->cls) {                // v8ClassificationLoss: one item, the batch mean, which is also the scalar backward() runs on (Loss.cs:1086-1088)
-    if (h[14] != 0.f) {
-      m->have_loss = false;
-      ys_set_error("ys_loss_classify: %d label(s) of this batch are not class ids in [0, %d)", (int)h[14], m->d.nc);
-      return YS_ERR_INVALID_ARG;
-    }
-    items[0] = h[1];
-    if (loss_sum) *loss_sum = h[4];
-    return YS_OK;
-  }
-  YS_TRY(check_label_overflow(m, h[15]));
-  YS_TRY(add_o2o_items(m, h));
-  if (m->segment) {
-    YS_REQUIRE(m->have_seg_loss, "ys_loss_read_items: the Segment model needs ys_loss_segment");
-    items[0] = h[1]; items[1] = h[8]; items[2] = h[2]; items[3] = h[3]; items[4] = 0.f;
-  } else if (m->xkind == 2) {
-    items[0] = h[1]; items[1] = h[2]; items[2] = h[3]; items[3] = h[13];                     // box, cls, dfl, angle (Loss.cs:619)
-  } else if (m->xkind == 3) {
-    YS_REQUIRE(m->have_seg_loss, "ys_loss_read_items: the Pose model needs ys_loss_pose");
-    items[0] = h[1]; items[1] = h[10]; items[2] = h[11]; items[3] = h[2]; items[4] = h[3];   // box, pose, kobj, cls, dfl (Loss.cs:965)
-  } else {
-    items[0] = h[1]; items[1] = h[2]; items[2] = h[3];
-  }
-  if (loss_sum) *loss_sum = h[4];
-  return YS_OK;
-}
-
-int ys_loss_read(ys_model* m, float loss_items[3], float* loss_sum) {
-  YS_REQUIRE(m && m->have_loss, "ys_loss_read: no loss has run");
-  YS_REQUIRE(!m->cls, "ys_loss_read: a classify model has one loss item (ys_loss_read_items with n_items = 1)");
-  float h[16];
-  YS_CHECK_HIP(hipMemcpyAsync(h, m->scalars, sizeof(h), hipMemcpyDeviceToHost, m->ctx->stream));
-  YS_CHECK_HIP(hipStreamSynchronize(m->ctx->stream));
-  YS_TRY(check_label_overflow(m, h[15]));
-  YS_TRY(add_o2o_items(m, h));
-  if (loss_items) { loss_items[0] = h[1]; loss_items[1] = h[2]; loss_items[2] = h[3]; }
-  if (loss_sum) *loss_sum = h[4];
   return YS_OK;
 }
 
