@@ -293,16 +293,22 @@ int ys_stem_fwd_launch(hipStream_t st, const float* x, int B, int H, int W, cons
 //  * dy: the tile's rows [256 pixels][Cout] sit in LDS as they are in memory; a lane gathers its output channel's eight pixels.
 // A workgroup accumulates its tiles in registers and leaves ONE partial slab [Cout][9][8] (the generic kernel's split layout, so the
 // batched split reduction of the backward segment takes it as it is).
+// FUSE = 1: the unit's BatchNorm (+ SiLU) backward on the way.  model.0 has no dgrad, so its dy has this kernel as its only reader: `dy` is then the gradient dz of
+// the unit's OUTPUT, `y` its raw (pre-BN) output, and the bf16 dy unit is formed between the load and the LDS store with bn_bwd_apply_kernel's expression and
+// helpers (elementwise.hip) -- the same bf16 numbers into the same MFMA order, without the apply pass over the largest activation of the network.
 struct StemWgArgs {
   const float* x;
   const bf16_t* dy;          // [B][dy_bstride][dy_ldc] + dy_coff
+  const bf16_t* y;           // FUSE: [B * Hout * Wout][Cout]
+  const float *scale, *shift, *k2, *k3;   // FUSE: the unit's coefficient rows (bn_bwd_apply_kernel's)
+  int act;                   // FUSE: SiLU follows the BatchNorm
   float* partial;            // [gridDim.x][Cout][9][8]
   int B, H, W, Hout, Wout, Cout, dy_ldc, dy_coff;
   long dy_bstride;
   int tiles_x, tiles_y, ntiles;
 };
 
-template <int NR, int VEC>
+template <int NR, int VEC, int FUSE>
 __global__ void __launch_bounds__(STEM_THREADS)
 stem_wgrad_kernel(StemWgArgs a) {
   constexpr int PL = 40;                                // plane row pitch (entries): a multiple of 8 -> aligned 16-byte reads
@@ -312,6 +318,7 @@ stem_wgrad_kernel(StemWgArgs a) {
   constexpr int DY_BYTES = STEM_TH * STEM_TW * DP * 2, RED_BYTES = 4 * NR * 2 * 64 * 4 * 4;
   constexpr int R2_BYTES = DY_BYTES > RED_BYTES ? DY_BYTES : RED_BYTES;
   __shared__ uint4 sMem[(3 * PLANE * 2 + R2_BYTES + 15) / 16];
+  __shared__ float sCoef[FUSE ? 4 : 1][NR * 16];        // FUSE: scale, shift, k2, k3 of the unit's channels
   unsigned short* sE = (unsigned short*)sMem;           // even patch columns: entry i = patch column 2 i      (input column 2 (ox0 + i) - 1)
   unsigned short* sO = sE + PLANE;                      // odd patch columns:  entry i = patch column 2 i + 1
   unsigned short* sE1 = sO + PLANE;                     // even plane shifted: entry i = patch column 2 i + 2
@@ -339,6 +346,14 @@ stem_wgrad_kernel(StemWgArgs a) {
   float v[STEM_NLD];                          // (the form not taken is dead code: VEC is a template parameter)
   StemPatchV pv;
   uint4 dv[NDU];
+  uint4 yv[FUSE ? NDU : 1];
+  if (FUSE) {
+    for (int o = tid; o < 4 * NR * 16; o += STEM_THREADS) {         // read after the first barrier of the tile loop
+      const int r = o / (NR * 16), c = o - r * (NR * 16);
+      const float* p = r == 0 ? a.scale : (r == 1 ? a.shift : (r == 2 ? a.k2 : a.k3));
+      sCoef[r][c] = c < a.Cout ? p[c] : 0.f;
+    }
+  }
   auto fetch_tile = [&](int t) {              // everything tile t needs from memory, all loads back to back
     const int tx = t % a.tiles_x, trem = t / a.tiles_x;
     const int ty = trem % a.tiles_y, b = trem / a.tiles_y;
@@ -355,6 +370,11 @@ stem_wgrad_kernel(StemWgArgs a) {
       const long off = ok ? (((long)b * a.dy_bstride + (long)oy * a.Wout + ox) * a.dy_ldc + a.dy_coff + cu * 8) : 0;
       const uint4 t4 = *(const uint4*)(a.dy + off);
       dv[k] = ok ? t4 : ys_zero16();
+      if (FUSE) {
+        const long yoff = ok ? (((long)b * a.Hout + oy) * a.Wout + ox) * a.Cout + cu * 8 : 0;
+        const uint4 y4 = *(const uint4*)(a.y + yoff);
+        yv[k] = ok ? y4 : ys_zero16();
+      }
     }
   };
   // the NEXT tile's operands are requested as soon as the current ones sit in LDS (round 6, as in stem_fwd_kernel)
@@ -397,7 +417,34 @@ stem_wgrad_kernel(StemWgArgs a) {
       if (u < DU) {
         const int px = u / (NR * 2), cu = u - px * (NR * 2);
         unsigned* d = (unsigned*)(sDy + px * DP + cu * 8);     // DP is even: 4-byte aligned
-        d[0] = dv[k].x; d[1] = dv[k].y; d[2] = dv[k].z; d[3] = dv[k].w;
+        uint4 d4 = dv[k];
+        if (FUSE) {
+          // dz, y -> dy.  A unit outside the image or past Cout stays zero (not -k2): its coordinates are recomputed from the tile in hand
+          const int tx = tile % a.tiles_x, ty = (tile / a.tiles_x) % a.tiles_y;
+          const int oyl = px / STEM_TW, oxl = px - oyl * STEM_TW;
+          const bool ok = (bool)((int)(ty * STEM_TH + oyl < a.Hout) & (int)(tx * STEM_TW + oxl < a.Wout) & (int)(cu * 8 < a.Cout));
+          float g[8], f[8];
+          ys_unpack<bf16_t>(dv[k], g);
+          ys_unpack<bf16_t>(yv[k], f);
+          const float *sc = &sCoef[0][cu * 8], *sh = &sCoef[1][cu * 8], *a2 = &sCoef[2][cu * 8], *a3 = &sCoef[3][cu * 8];
+          if (a.act) {
+#pragma unroll
+            for (int e = 0; e < 8; e++) {
+              const float u_ = f[e] * sc[e] + sh[e];
+              const float du = g[e] * ys_silu_grad(u_);
+              f[e] = sc[e] * du - a2[e] - f[e] * a3[e];
+            }
+          } else {
+#pragma unroll
+            for (int e = 0; e < 8; e++) {
+              const float du = g[e];
+              f[e] = sc[e] * du - a2[e] - f[e] * a3[e];
+            }
+          }
+          const uint4 p4 = ys_pack<bf16_t>(f);
+          d4 = ok ? p4 : ys_zero16();
+        }
+        d[0] = d4.x; d[1] = d4.y; d[2] = d4.z; d[3] = d4.w;
       }
     }
     if (tile + (int)gridDim.x < a.ntiles) fetch_tile(tile + gridDim.x);
@@ -453,10 +500,12 @@ stem_wgrad_kernel(StemWgArgs a) {
 }
 
 // writes min(max_splits, 1024) partial slabs [Cout][9][8] into `partial`; *used = the number written
+// bnb != null: `dy` is dz of the unit's output and the BatchNorm (+ SiLU) backward runs inside the kernel (StemWgArgs)
 int ys_stem_wgrad_launch(hipStream_t st, const float* x, int B, int H, int W, const void* dy, int dy_ldc, int dy_coff, long dy_bstride,
-                         int Cout, float* partial, int max_splits, int* used) {
+                         int Cout, float* partial, int max_splits, int* used, const StemBnb* bnb) {
   StemWgArgs a{};
   a.x = x; a.dy = (const bf16_t*)dy; a.partial = partial;
+  if (bnb) { a.y = (const bf16_t*)bnb->y; a.scale = bnb->scale; a.shift = bnb->shift; a.k2 = bnb->k2; a.k3 = bnb->k3; a.act = bnb->act; }
   a.B = B; a.H = H; a.W = W; a.Hout = (H - 1) / 2 + 1; a.Wout = (W - 1) / 2 + 1; a.Cout = Cout;
   a.dy_ldc = dy_ldc; a.dy_coff = dy_coff; a.dy_bstride = dy_bstride;
   a.tiles_x = ys_cdiv(a.Wout, STEM_TW); a.tiles_y = ys_cdiv(a.Hout, STEM_TH); a.ntiles = B * a.tiles_x * a.tiles_y;
@@ -469,7 +518,15 @@ int ys_stem_wgrad_launch(hipStream_t st, const float* x, int B, int H, int W, co
   if (ys_kprof_enabled()) snprintf(lab, sizeof(lab), "wstem k3 s2 cin3 cout%d M%ld tile%dx%d grid%dx1", Cout, (long)B * a.Hout * a.Wout, STEM_TH, STEM_TW, grid);
   YsKprofScope prof(st, "conv_wgrad", lab);
   const bool vec = (W & 3) == 0 && ((size_t)x & 15) == 0;
-#define STEM_W(N_) if (nr == N_) { if (vec) YS_LAUNCH((stem_wgrad_kernel<N_, 1>), grid, STEM_THREADS, st, a); else YS_LAUNCH((stem_wgrad_kernel<N_, 0>), grid, STEM_THREADS, st, a); return YS_OK; }
+  if (bnb) {
+    // the fused form is built for the 16-channel stem (YOLOv8n / YOLOv11n), the width it was measured at: 134 VGPRs, three waves per SIMD.  The wider variants
+    // would run at one or two (232-256 VGPRs at 64 / 80 channels) and have not been timed against the separate pass
+    if (nr != 1) { ys_set_error("stem wgrad: the fused BatchNorm backward takes 16 output channels, not %d", Cout); return YS_ERR_UNSUPPORTED; }
+    YsKprofScope fused(st, "stem_bnb");          // a class of its own beside conv_wgrad: tests count the launches that took this form
+    if (vec) YS_LAUNCH((stem_wgrad_kernel<1, 1, 1>), grid, STEM_THREADS, st, a); else YS_LAUNCH((stem_wgrad_kernel<1, 0, 1>), grid, STEM_THREADS, st, a);
+    return YS_OK;
+  }
+#define STEM_W(N_) if (nr == N_) { if (vec) YS_LAUNCH((stem_wgrad_kernel<N_, 1, 0>), grid, STEM_THREADS, st, a); else YS_LAUNCH((stem_wgrad_kernel<N_, 0, 0>), grid, STEM_THREADS, st, a); return YS_OK; }
   STEM_W(1) STEM_W(2) STEM_W(3) STEM_W(4) STEM_W(5)
 #undef STEM_W
   ys_set_error("stem wgrad: %d output channels", Cout);

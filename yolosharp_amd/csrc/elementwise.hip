@@ -880,6 +880,261 @@ int ys_maxpool5_bwd_launch(hipStream_t st, int dtype, const void* dy, int dy_ldc
   return YS_OK;
 }
 
+// ------------------------------------------------------------------ SPPF: the three chained 5x5 pools of one concat buffer in one launch
+// A workgroup owns (image, four 16-byte units of channels: 32 bf16 or 16 f32, 64 contiguous bytes per pixel in memory): the map sits in LDS, the three pools run
+// from LDS and every stage writes its concat slice (+ its argmax plane in training).  Results are those of three maxpool5_fwd_kernel launches bit for bit:
+//  * the pool is separable -- a row pass keeps, per row of the window, the FIRST kw of the row maximum (strict '>'), the column pass the FIRST kh whose row maximum
+//    is strictly greater: together the first maximum in (kh, kw) scan order.  Both start from -inf with the code of the first tap of the clipped window, which is
+//    what "the first visited tap is always taken" gives for every non-NaN map; a NaN in the first tap is taken afterwards, as the scan does.
+//  * taps outside the map are clamped to the edge instead of skipped: on the low side the clamped taps read the first in-window element early and carry its real
+//    code (max(k, k0)); on the high side they repeat an element already seen, which strict '>' never takes.
+// Every loop runs SPPF_NIT rounds for every thread and the barriers sit between the loops: nothing here depends on the pixel or the channel.
+#define SPPF_THREADS 512
+#define SPPF_MAXHW 400                  // 20 x 20: LDS 25.6 KB map + 25.6 KB row maxima + 6.4 KB row codes (backward: 25.6 KB gradient + 12.8 KB codes)
+#define SPPF_CU 4                       // 16-byte units per pixel and workgroup
+#define SPPF_NIT ((SPPF_MAXHW * SPPF_CU + SPPF_THREADS - 1) / SPPF_THREADS)
+__device__ inline int sppf_min(int x, int y) { return x < y ? x : y; }
+__device__ inline int sppf_max(int x, int y) { return x > y ? x : y; }
+struct SppfArgs {
+  void* buf;                            // the concat buffer (forward: activations, backward: gradients), [B][H*W][ldc]
+  int ldc, coff[4];                     // slice i at channel offset coff[i]; pool i reads slice i and writes slice i + 1
+  int H, W, C, nchunk;
+  unsigned char* amax[3];               // argmax plane of pool i, [B*H*W][C] bytes (forward: null in eval mode)
+  int acc[3];                           // backward: slice i already holds a gradient contribution (grad_mode)
+};
+
+// EPL argmax codes of one unit <-> the bytes of the plane (bf16: 8 bytes, f32: 4)
+template <int EPL> __device__ inline uint2 sppf_ld_codes(const unsigned char* p) {
+  if constexpr (EPL == 8) return *(const uint2*)p;
+  else return make_uint2(*(const unsigned*)p, 0u);
+}
+template <int EPL> __device__ inline void sppf_st_codes(unsigned char* p, uint2 v) {
+  if constexpr (EPL == 8) *(uint2*)p = v;
+  else *(unsigned*)p = v.x;
+}
+
+template <class T>
+__global__ void __launch_bounds__(SPPF_THREADS)
+sppf_pool3_fwd_kernel(SppfArgs a) {
+  constexpr int EPL = Elem<T>::EPL;
+  T* const buf = (T*)a.buf;
+  __shared__ uint4 sV[SPPF_MAXHW * SPPF_CU];        // the stage's input map
+  __shared__ uint4 sR[SPPF_MAXHW * SPPF_CU];        // row maxima
+  __shared__ unsigned sRI[SPPF_MAXHW * SPPF_CU];    // their kw codes, 3 bits per channel
+  const int tid = threadIdx.x;
+  const int chunk = (int)blockIdx.x % a.nchunk, b = (int)blockIdx.x / a.nchunk;
+  const int HW = a.H * a.W, W = a.W, H = a.H;
+  const int nu = sppf_min(SPPF_CU, a.C / EPL - chunk * SPPF_CU);     // units of this chunk that exist (the last chunk may be short)
+  const int n = HW * SPPF_CU;
+  const long prow = (long)b * HW;
+#pragma unroll
+  for (int it = 0; it < SPPF_NIT; it++) {
+    const int idx = tid + it * SPPF_THREADS;
+    const int px = idx >> 2, u = idx & 3;
+    if (idx < n && u < nu) sV[idx] = ys_ld16(buf + (prow + px) * a.ldc + a.coff[0] + (chunk * SPPF_CU + u) * EPL);
+  }
+  __syncthreads();
+  for (int s = 0; s < 3; s++) {
+    // ---- row pass
+#pragma unroll
+    for (int it = 0; it < SPPF_NIT; it++) {
+      const int idx = tid + it * SPPF_THREADS;
+      const int px = idx >> 2, u = idx & 3;
+      if (idx < n && u < nu) {
+        const int h = px / W, w = px - h * W;
+        const int kw0 = sppf_max(0, 2 - w);
+        float best[EPL]; unsigned bi[EPL];
+#pragma unroll
+        for (int e = 0; e < EPL; e++) { best[e] = -INFINITY; bi[e] = (unsigned)kw0; }
+#pragma unroll
+        for (int kw = 0; kw < 5; kw++) {
+          const int iw = sppf_min(sppf_max(w + kw - 2, 0), W - 1);
+          const unsigned code = (unsigned)sppf_max(kw, kw0);
+          float f[EPL];
+          ys_unpack<T>(sV[(h * W + iw) * SPPF_CU + u], f);
+#pragma unroll
+          for (int e = 0; e < EPL; e++)
+            if (f[e] > best[e]) { best[e] = f[e]; bi[e] = code; }
+        }
+        unsigned ri = 0;
+#pragma unroll
+        for (int e = 0; e < EPL; e++) ri |= bi[e] << (3 * e);
+        sR[idx] = ys_pack<T>(best);            // exact: the maxima are storage values (or -inf)
+        sRI[idx] = ri;
+      }
+    }
+    __syncthreads();
+    // ---- column pass, first-tap NaN rule, stores
+    uint4 out[SPPF_NIT];
+#pragma unroll
+    for (int it = 0; it < SPPF_NIT; it++) {
+      const int idx = tid + it * SPPF_THREADS;
+      const int px = idx >> 2, u = idx & 3;
+      out[it] = ys_zero16();
+      if (idx < n && u < nu) {
+        const int h = px / W, w = px - h * W;
+        const int kh0 = sppf_max(0, 2 - h), kw0 = sppf_max(0, 2 - w);
+        float best[EPL]; unsigned bw[EPL];              // bw: the winning row's code word, its kh in bits 24..26
+#pragma unroll
+        for (int e = 0; e < EPL; e++) { best[e] = -INFINITY; bw[e] = ((unsigned)kh0 << 24) | ((unsigned)kw0 * 0x249249u); }   // kw0 in every 3-bit field
+#pragma unroll
+        for (int kh = 0; kh < 5; kh++) {
+          const int ih = sppf_min(sppf_max(h + kh - 2, 0), H - 1);
+          const int j = (ih * W + w) * SPPF_CU + u;
+          const unsigned word = sRI[j] | ((unsigned)sppf_max(kh, kh0) << 24);
+          float f[EPL];
+          ys_unpack<T>(sR[j], f);
+#pragma unroll
+          for (int e = 0; e < EPL; e++)
+            if (f[e] > best[e]) { best[e] = f[e]; bw[e] = word; }
+        }
+        float t0[EPL];                                // the first tap of the clipped window
+        ys_unpack<T>(sV[(sppf_max(h - 2, 0) * W + sppf_max(w - 2, 0)) * SPPF_CU + u], t0);
+        unsigned code[EPL];
+#pragma unroll
+        for (int e = 0; e < EPL; e++) {
+          code[e] = (bw[e] >> 24) * 5u + ((bw[e] >> (3 * e)) & 7u);
+          if (t0[e] != t0[e]) { best[e] = t0[e]; code[e] = (unsigned)(kh0 * 5 + kw0); }
+        }
+        out[it] = ys_pack<T>(best);
+        const long row = prow + px;
+        const int c = (chunk * SPPF_CU + u) * EPL;
+        ys_st16(buf + row * a.ldc + a.coff[s + 1] + c, out[it]);
+        if (a.amax[s]) {
+          uint2 pk = make_uint2(0u, 0u);
+#pragma unroll
+          for (int e = 0; e < EPL; e++) (e < 4 ? pk.x : pk.y) |= code[e] << (8 * (e & 3));
+          sppf_st_codes<EPL>(a.amax[s] + row * a.C + c, pk);
+        }
+      }
+    }
+    __syncthreads();                                // every first-tap read of sV is done
+#pragma unroll
+    for (int it = 0; it < SPPF_NIT; it++) {
+      const int idx = tid + it * SPPF_THREADS;
+      if (idx < n && (idx & 3) < nu) sV[idx] = out[it];
+    }
+    __syncthreads();
+  }
+}
+
+// G[slice 2] = round(scatter(G[slice 3]) + G[slice 2]), then slice 1 from that, then slice 0: the three maxpool5_bwd_kernel launches with their rounding points
+// (fp32 sum of the taps in (kh, kw) order, then the old value, then one rounding to the storage type per stage).  The upstream gradient map and the stage's argmax codes sit in LDS.
+template <class T>
+__global__ void __launch_bounds__(SPPF_THREADS)
+sppf_pool3_bwd_kernel(SppfArgs a) {
+  constexpr int EPL = Elem<T>::EPL;
+  T* const buf = (T*)a.buf;
+  __shared__ uint4 sG[SPPF_MAXHW * SPPF_CU];        // gradient of the stage's pool output
+  __shared__ uint2 sA[SPPF_MAXHW * SPPF_CU];        // its argmax codes
+  const int tid = threadIdx.x;
+  const int chunk = (int)blockIdx.x % a.nchunk, b = (int)blockIdx.x / a.nchunk;
+  const int HW = a.H * a.W, W = a.W, H = a.H;
+  const int nu = sppf_min(SPPF_CU, a.C / EPL - chunk * SPPF_CU);
+  const int n = HW * SPPF_CU;
+  const long prow = (long)b * HW;
+#pragma unroll
+  for (int it = 0; it < SPPF_NIT; it++) {
+    const int idx = tid + it * SPPF_THREADS;
+    const int px = idx >> 2, u = idx & 3;
+    if (idx < n && u < nu) {
+      const int c = (chunk * SPPF_CU + u) * EPL;
+      sG[idx] = ys_ld16(buf + (prow + px) * a.ldc + a.coff[3] + c);
+      sA[idx] = sppf_ld_codes<EPL>(a.amax[2] + (prow + px) * a.C + c);
+    }
+  }
+  __syncthreads();
+  for (int s = 2; s >= 0; s--) {
+    uint4 out[SPPF_NIT]; uint2 an[SPPF_NIT];
+#pragma unroll
+    for (int it = 0; it < SPPF_NIT; it++) {
+      const int idx = tid + it * SPPF_THREADS;
+      const int px = idx >> 2, u = idx & 3;
+      out[it] = ys_zero16(); an[it] = make_uint2(0u, 0u);
+      if (idx < n && u < nu) {
+        const int h = px / W, w = px - h * W;
+        const int c = (chunk * SPPF_CU + u) * EPL;
+        T* dp = buf + (prow + px) * a.ldc + a.coff[s] + c;
+        uint4 old = ys_zero16();
+        if (a.acc[s]) old = ys_ld16(dp);            // requested ahead of the taps
+        if (s > 0) an[it] = sppf_ld_codes<EPL>(a.amax[s - 1] + (prow + px) * a.C + c);
+        float acc[EPL];
+#pragma unroll
+        for (int e = 0; e < EPL; e++) acc[e] = 0.f;
+#pragma unroll 1                            // (five rows of taps unrolled at once spill registers in the f32 instantiation)
+        for (int kh = 0; kh < 5; kh++) {
+          const int oh = h - kh + 2;                // output whose window holds (h,w) at offset (kh,kw)
+          const bool okh = oh >= 0 && oh < H;
+          const int ohc = sppf_min(sppf_max(oh, 0), H - 1);
+#pragma unroll
+          for (int kw = 0; kw < 5; kw++) {
+            const int ow = w - kw + 2;
+            const bool ok = okh && ow >= 0 && ow < W;
+            const int j = (ohc * W + sppf_min(sppf_max(ow, 0), W - 1)) * SPPF_CU + u;
+            const unsigned code = ok ? (unsigned)(kh * 5 + kw) : 255u;      // no plane holds 255: a tap outside the map adds nothing
+            float g[EPL];
+            ys_unpack<T>(sG[j], g);
+            const uint2 am = sA[j];
+#pragma unroll
+            for (int e = 0; e < EPL; e++)
+              if ((((e < 4 ? am.x : am.y) >> (8 * (e & 3))) & 0xffu) == code) acc[e] += g[e];
+          }
+        }
+        if (a.acc[s]) {
+          float o[EPL];
+          ys_unpack<T>(old, o);
+#pragma unroll
+          for (int e = 0; e < EPL; e++) acc[e] += o[e];
+        }
+        out[it] = ys_pack<T>(acc);
+        ys_st16(dp, out[it]);
+      }
+    }
+    __syncthreads();                                // every read of this stage's map and codes is done
+#pragma unroll
+    for (int it = 0; it < SPPF_NIT; it++) {
+      const int idx = tid + it * SPPF_THREADS;
+      if (idx < n && (idx & 3) < nu) { sG[idx] = out[it]; sA[idx] = an[it]; }
+    }
+    __syncthreads();
+  }
+}
+
+// the fused form takes maps of at most SPPF_MAXHW pixels whose slices start on 16-byte units and whose argmax planes (null = none) are aligned for the unit's
+// code bytes; everything else runs the three launches
+int ys_sppf_pool3_ok(int dtype, int H, int W, int C, int ldc, const int* coff, unsigned char* const* argmax) {
+  const int epl = dtype == YS_BF16 ? 8 : 4;
+  if ((dtype != YS_BF16 && dtype != YS_F32) || H < 1 || W < 1 || H * W > SPPF_MAXHW || C < epl || (C % epl) || (ldc % epl)) return 0;
+  for (int i = 0; i < 4; i++) if (coff[i] % epl) return 0;
+  for (int i = 0; argmax && i < 3; i++) if ((size_t)argmax[i] % epl) return 0;
+  return 1;
+}
+static SppfArgs sppf_args(int dtype, void* buf, int ldc, const int* coff, int H, int W, int C) {
+  SppfArgs a{};
+  a.buf = buf; a.ldc = ldc; a.H = H; a.W = W; a.C = C; a.nchunk = ys_cdiv(C / (dtype == YS_BF16 ? 8 : 4), SPPF_CU);
+  for (int i = 0; i < 4; i++) a.coff[i] = coff[i];
+  return a;
+}
+int ys_sppf_pool3_fwd_launch(hipStream_t st, int dtype, void* act, int ldc, const int* coff, int B, int H, int W, int C, unsigned char* const* argmax) {
+  if (!ys_sppf_pool3_ok(dtype, H, W, C, ldc, coff, argmax)) { ys_set_error("sppf pools: unsupported view"); return YS_ERR_UNSUPPORTED; }
+  SppfArgs a = sppf_args(dtype, act, ldc, coff, H, W, C);
+  for (int i = 0; i < 3; i++) a.amax[i] = argmax ? argmax[i] : nullptr;
+  YsKprofScope prof(st, "sppf_pool3");
+  if (dtype == YS_BF16) YS_LAUNCH((sppf_pool3_fwd_kernel<bf16_t>), B * a.nchunk, SPPF_THREADS, st, a);
+  else YS_LAUNCH((sppf_pool3_fwd_kernel<float>), B * a.nchunk, SPPF_THREADS, st, a);
+  return YS_OK;
+}
+int ys_sppf_pool3_bwd_launch(hipStream_t st, int dtype, void* grad, int ldc, const int* coff, int B, int H, int W, int C, unsigned char* const* argmax,
+                             const int* accumulate) {
+  if (!argmax || !argmax[0] || !argmax[1] || !argmax[2] || !ys_sppf_pool3_ok(dtype, H, W, C, ldc, coff, argmax)) { ys_set_error("sppf pools: unsupported view"); return YS_ERR_UNSUPPORTED; }
+  SppfArgs a = sppf_args(dtype, grad, ldc, coff, H, W, C);
+  for (int i = 0; i < 3; i++) { a.amax[i] = argmax[i]; a.acc[i] = accumulate[i]; }
+  YsKprofScope prof(st, "sppf_pool3");
+  if (dtype == YS_BF16) YS_LAUNCH((sppf_pool3_bwd_kernel<bf16_t>), B * a.nchunk, SPPF_THREADS, st, a);
+  else YS_LAUNCH((sppf_pool3_bwd_kernel<float>), B * a.nchunk, SPPF_THREADS, st, a);
+  return YS_OK;
+}
+
 // ------------------------------------------------------------------ nearest 2x upsample
 template <class T>
 __global__ void __launch_bounds__(EW_THREADS)

@@ -928,6 +928,7 @@ int alloc_f8(ys_model* m, const std::vector<PrepDesc>& pd) {
   return YS_OK;
 }
 
+static bool stem_bnb_planned(const ys_model* m);
 int allocate(ys_model* m) {
   const int B = m->maxB;
   hipStream_t st = m->ctx->stream; (void)st;
@@ -1026,6 +1027,8 @@ int allocate(ys_model* m) {
   // bench.py switches the overlap off (ys_model_set_overlap) for its per-kernel profile steps.  YS_OVERLAP=0 disables it.
   m->overlap = (YS_OPT_INT("OVERLAP", 1) != 0);
   m->overlap_built = m->overlap;
+  m->stem_on = (YS_OPT_INT("STEM_DIRECT", 1) != 0);
+  m->stem_bnb_fuse = (YS_OPT_INT("STEM_BNB_FUSE", 1) != 0);   // YS_STEM_BNB_FUSE=0: model.0's BatchNorm backward is a pass of its own (the fused form's reference)
   if (m->overlap) {
     // lowest priority: the weight gradients are off the critical path (the optimizer is their only reader), and a priority class of
     // its own is a hardware queue of its own -- streams of one class share a handful of queues in creation order, and with the main
@@ -1042,6 +1045,7 @@ int allocate(ys_model* m) {
     // YOLOv8n at B = 64, ~10 GB for YOLOv8x at 1280 x 1280 x 16)
     for (auto& c : m->convs) {
       if (!c.bn || c.dw || c.ct || c.dy_own) continue;
+      if (c.idx == 0 && stem_bnb_planned(m)) continue;      // its dy is formed inside its weight-gradient kernel
       YS_TRY(dev_alloc(m, &c.dy_own, (size_t)B * c.Hout * c.Wout * c.cout_ld * m->es));
     }
     for (int k = 0; k <= ys_model::DY_RING; k++) YS_CHECK_HIP(hipEventCreateWithFlags(&m->ev_dy[k], hipEventDisableTiming));
@@ -1083,7 +1087,7 @@ int allocate(ys_model* m) {
   // wgrad partial workspace: a shared scratch (max over layers of splits * |W|: ConvTranspose phases, immediate reduction) followed by
   // one region per convolution, so that the split reduction of a whole backward segment can run as ONE launch after it
   m->defer_wgred = true;
-  m->stem_on = (YS_OPT_INT("STEM_DIRECT", 1) != 0);
+  m->sppf_fuse = (YS_OPT_INT("SPPF_FUSE", 1) != 0);       // YS_SPPF_FUSE=0: three pool launches per SPPF, forward and backward
   m->bnred_on = (YS_OPT_INT("BNRED", 1) != 0);           // YS_BNRED=0: every BN backward runs its own reduction pass
   long wgp = 0, wgp_regions = 0;
   std::vector<long> need(m->convs.size(), 0);
@@ -1220,6 +1224,16 @@ static const ConvL* stem_conv(const ys_model* m) {
   return &c;
 }
 static bool stem_direct(const ys_model* m) { return stem_conv(m) != nullptr; }
+// model.0's BatchNorm backward can run inside its weight-gradient kernel (conv_stem.hip, FUSE): the unit has no dgrad, so nothing else reads its dy.  Decided at
+// creation (no dy buffer is allocated for the unit then); a step whose forward did not read the fp32 image (ys_model_forward_u8) takes the separate pass.
+static bool stem_bnb_planned(const ys_model* m) {
+  if (!m->stem_bnb_fuse || !m->stem_on || m->is_block || m->is_head || m->dtype != YS_BF16 || m->convs.empty()) return false;
+  const ConvL& c = m->convs[0];
+  if (!c.first || !c.bn || c.dw || c.ct || c.has_res || c.pool_next || c.in.buf != m->in_buf || c.cout_ld != c.cout) return false;
+  if (!ys_stem_eligible(m->dtype, c.cin, c.cout, c.k, c.s) || c.cout != 16) return false;   // 16 channels: the width the fused kernel is built and measured for (conv_stem.hip)
+  const Buf& ob = m->bufs[c.out.buf];
+  return (ob.ldc & 7) == 0 && (c.out.coff & 7) == 0 && ob.rows_per_b == (long)c.Hout * c.Wout;
+}
 
 // geometry / operand part of the forward convolution arguments of layer c
 static ConvArgs fwd_args(ys_model* m, const ConvL& c, int B) {
@@ -1389,6 +1403,23 @@ int run_conv_fwd_group(ys_model* m, ConvL* const* cs, int n, int B) {
   return YS_OK;
 }
 
+// SPPF: ops [i0, i0 + 2] are three max-pools chained through the slices of one concat buffer, and the one-launch form takes the view (elementwise.hip)
+static bool sppf_chain(const ys_model* m, int i0, int* coff) {
+  if (!m->sppf_fuse || i0 < 0 || i0 + 2 >= (int)m->ops.size()) return false;
+  const Op& o0 = m->ops[i0];
+  for (int k = 0; k < 3; k++) {
+    const Op& o = m->ops[i0 + k];
+    if (o.type != OP_MAXPOOL || o.in.buf != o0.in.buf || o.out.buf != o0.in.buf || o.in.C != o0.in.C || o.out.C != o0.in.C || o.H != o0.H || o.W != o0.W ||
+        o.seg != o0.seg) return false;
+    if (k > 0 && o.in.coff != m->ops[i0 + k - 1].out.coff) return false;
+    coff[k] = o.in.coff; coff[k + 1] = o.out.coff;
+  }
+  for (int i = 0; i < 4; i++) for (int j = i + 1; j < 4; j++) if (abs(coff[i] - coff[j]) < o0.in.C) return false;   // four distinct slices
+  unsigned char* am[3];
+  for (int k = 0; k < 3; k++) am[k] = m->argmax + m->ops[i0 + k].aux_off;
+  return ys_sppf_pool3_ok(m->dtype, o0.H, o0.W, o0.in.C, m->bufs[o0.in.buf].ldc, coff, am) != 0;
+}
+
 static int join_wgrad_stream(ys_model* m);
 int forward_impl(ys_model* m, int B) {
   hipStream_t st = m->ctx->stream;
@@ -1435,6 +1466,11 @@ int forward_impl(ys_model* m, int B) {
             nc.Hin == cc.Hout && nc.Win == cc.Wout) next = &nc;
       }
       YS_TRY(run_conv_fwd(m, cc, B, next));
+    } else if (int pc[4]; op.type == OP_MAXPOOL && sppf_chain(m, (int)oi, pc)) {
+      unsigned char* am[3];
+      for (int k = 0; k < 3; k++) am[k] = m->training ? m->argmax + m->ops[oi + k].aux_off : nullptr;
+      YS_TRY(ys_sppf_pool3_fwd_launch(st, m->dtype, ib.act, ib.ldc, pc, B, op.H, op.W, op.in.C, am));
+      oi += 2;
     } else if (op.type == OP_MAXPOOL) {
       YS_TRY(ys_maxpool5_fwd_launch(st, m->dtype, ib.act, ib.ldc, op.in.coff, B, op.H, op.W, op.in.C, ob.act, ob.ldc,
                                     op.out.coff, m->training ? m->argmax + op.aux_off : nullptr));
@@ -1674,7 +1710,7 @@ int plan_bnred(ys_model* m, int B) {
 }
 
 // weight gradient of one convolution on stream `sw` (split partials into the layer's own region when the reduction is deferred)
-static int launch_wgrad(ys_model* m, ConvL& c, int B, const void* dy, int dy_ldc, int dy_coff, long dy_bstride, hipStream_t sw) {
+static int launch_wgrad(ys_model* m, ConvL& c, int B, const void* dy, int dy_ldc, int dy_coff, long dy_bstride, hipStream_t sw, bool bnb = false) {
   const Buf& ib = m->bufs[c.in.buf];
   const long M = (long)B * c.Hout * c.Wout;
   WgradArgs a{};
@@ -1687,12 +1723,16 @@ static int launch_wgrad(ys_model* m, ConvL& c, int B, const void* dy, int dy_ldc
   const bool defer = c.wgp_off >= 0;
   if (c.first && m->in_f32 && defer) {     // model.0: x is the fp32 image itself (conv_stem.hip); slabs in the generic split layout
     int used = 0;
-    YS_TRY(ys_stem_wgrad_launch(sw, m->in_f32, B, c.Hin, c.Win, dy, dy_ldc, dy_coff, dy_bstride, c.cout, m->wg_partial + c.wgp_off, c.wgp_splits, &used));
+    // bnb: dy is the gradient of the unit's output and the kernel runs the BatchNorm backward itself (run_conv_bwd: stem_fused)
+    const StemBnb sb{(char*)m->y_all + (size_t)c.y_off * m->es, chan_ptr(m, c, 0), chan_ptr(m, c, 1), chan_ptr(m, c, 4), chan_ptr(m, c, 5), c.act ? 1 : 0};
+    YS_TRY(ys_stem_wgrad_launch(sw, m->in_f32, B, c.Hin, c.Win, dy, dy_ldc, dy_coff, dy_bstride, c.cout, m->wg_partial + c.wgp_off, c.wgp_splits, &used,
+                                bnb ? &sb : nullptr));
     WgRedDesc& d = m->red_host[c.red_slot];
     d.partial = m->wg_partial + c.wgp_off; d.grad = m->grads + c.w_off; d.n = (long)c.cout * c.k * c.k * c.cin_pad; d.splits = used;
     d.cin_pad = c.cin_pad; d.cin_real = c.cin;
     return YS_OK;
   }
+  if (bnb) { ys_set_error("backward: %s was queued without its dy", c.name.c_str()); return YS_ERR_STATE; }
   if (defer) { a.partial = m->wg_partial + c.wgp_off; if (splits > c.wgp_splits) splits = c.wgp_splits; }   // own region (sized at max_batch)
   else if ((long)splits * c.cout * c.k * c.k * c.cin_pad > m->n_wgp) { ys_set_error("wgrad workspace too small"); return YS_ERR_STATE; }
   int used = 0;
@@ -1719,21 +1759,21 @@ static int flush_wgrads(ys_model* m, int B) {
     sw = m->st2;
     m->st2_dirty = true;
   }
-  for (const auto& p : m->pend_wg) YS_TRY(launch_wgrad(m, m->convs[p.conv], B, p.dy, p.ldc, p.coff, p.bstride, sw));
+  for (const auto& p : m->pend_wg) YS_TRY(launch_wgrad(m, m->convs[p.conv], B, p.dy, p.ldc, p.coff, p.bstride, sw, p.bnb));
   m->pend_wg.clear(); m->pend_mb = 0.0;
   return YS_OK;
 }
 // queue layer c's weight gradient; flush when the batch is full: 6 launches or 40 megabytes of (input + dy) tensors (
 // the P1 / P2 / P3 layers, whose kernels run 50-150 us, go over one or two at a time -- the bubble is small next to them and the second stream should not start
 // them late; the P4 / P5 layers, 15-30 us each, go over in fours to sixes)
-static int queue_wgrad(ys_model* m, ConvL& c, int B, const void* dy, int ldc, int coff, long bstride) {
-  if (!m->overlap) return launch_wgrad(m, c, B, dy, ldc, coff, bstride, m->ctx->stream);
+static int queue_wgrad(ys_model* m, ConvL& c, int B, const void* dy, int ldc, int coff, long bstride, bool bnb = false) {
+  if (!m->overlap) return launch_wgrad(m, c, B, dy, ldc, coff, bstride, m->ctx->stream, bnb);
   if (c.first && m->hold_stem) {               // everything queued so far goes now; the stem's own launch waits for the segment end
     YS_TRY(flush_wgrads(m, B));
-    m->pend_wg.push_back(ys_model::PendWg{c.idx, dy, ldc, coff, bstride});
+    m->pend_wg.push_back(ys_model::PendWg{c.idx, dy, ldc, coff, bstride, bnb});
     return YS_OK;
   }
-  m->pend_wg.push_back(ys_model::PendWg{c.idx, dy, ldc, coff, bstride});
+  m->pend_wg.push_back(ys_model::PendWg{c.idx, dy, ldc, coff, bstride, bnb});
   m->pend_mb += ((double)B * c.Hout * c.Wout * c.cout + (double)B * c.Hin * c.Win * c.cin_pad) * m->es * 1e-6;
   // (measured on config 2, same box, two rounds each: one per launch 8.71 / 8.71 ms, 4 / 24 MB 8.74 / 8.72, 6 / 40 MB 8.65 / 8.66, 12 / 80 MB 8.81 / 8.75, 8 / 200 MB 8.84 / 8.81,
   // everything in one batch per segment 8.93 / 8.87; round 5's ring + per-launch events 8.79 / 8.73)
@@ -1763,6 +1803,8 @@ int run_conv_bwd(ys_model* m, ConvL& c, int B) {
   const long M = (long)B * c.Hout * c.Wout;
   const void* dy = nullptr; int dy_ldc = 0, dy_coff = 0; long dy_bstride = (long)c.Hout * c.Wout;
   bool dy_q8 = false;                       // m->q8 already holds the e5m2 image of dy (written by the BN backward pass)
+  bool stem_scratch = false;                // model.0 planned for the fused form in a step that cannot take it: its dy sits in dy_scratch
+  bool stem_fused = false;                  // dy is not materialised: the stem's weight-gradient kernel forms it from dz and y
   if (c.bn) {
     const void* y = (char*)m->y_all + (size_t)c.y_off * m->es;
     void* rg = nullptr; int rgl = 0, rgc = 0;
@@ -1811,6 +1853,11 @@ int run_conv_bwd(ys_model* m, ConvL& c, int B) {
       YS_TRY(ys_bn_bwd_finalize_launch(st, m->stat_partial, nblk, c.cout, M, m->grads + c.g_off, m->grads + c.b_off,
                                        chan_ptr(m, c, 4), chan_ptr(m, c, 5), chan_ptr(m, c, 0), chan_ptr(m, c, 2), chan_ptr(m, c, 3)));
     }
+    // model.0 read from the fp32 image: no apply pass -- its weight-gradient kernel takes dz, y and the coefficient rows the finalize above just wrote
+    stem_fused = c.idx == 0 && m->in_f32 && c.wgp_off >= 0 && stem_bnb_planned(m);
+    // planned fused (no dy buffer of its own), but this step's forward packed its input (ys_model_forward_u8): dy goes to the shared scratch buffer.  model.0 is the
+    // last unit of the backward, nothing writes that buffer after it, and the next backward joins the second stream before it starts (ys_model_backward).
+    stem_scratch = !stem_fused && m->overlap && c.idx == 0 && !c.dy_own && !c.dw && stem_bnb_planned(m);
     void* dyb = m->dy_scratch;
     if (m->overlap && !c.dw && c.dy_own) dyb = c.dy_own;   // the unit's own buffer: its weight gradient reads it later, from the second stream (queue_wgrad)
     // fp8 mode: when this layer's dgrad will run the fp8 blocked-GEMM kernel, the same pass writes the e5m2 image of dy it consumes
@@ -1820,7 +1867,9 @@ int run_conv_bwd(ys_model* m, ConvL& c, int B) {
       q.f8 = 2; q.w8 = m->wd8_all + c.wd_off; q.qscale = m->f8_scales + 4L * c.idx + 2; q.deq = m->f8_scales + 4L * c.idx + 3;
       dy_q8 = ys_conv_wants_x8(q);
     }
-    if (dy_q8) {
+    if (stem_fused) {
+      if (rg_apply || dy_q8) { ys_set_error("backward: %s cannot take the fused BatchNorm backward", c.name.c_str()); return YS_ERR_STATE; }
+    } else if (dy_q8) {
       YS_TRY(ys_bn_bwd_apply_q8_launch(st, ob.grad, ob.ldc, c.out.coff, y, M, c.cout, chan_ptr(m, c, 0), chan_ptr(m, c, 1), chan_ptr(m, c, 4),
                                        chan_ptr(m, c, 5), c.act ? 1 : 0, dyb, m->q8, m->f8_scales + 4L * c.idx + 2,
                                        m->amax_dy + (size_t)c.idx * YS_AMAX_WAYS, rg_apply, rgl, rgc));
@@ -1829,6 +1878,7 @@ int run_conv_bwd(ys_model* m, ConvL& c, int B) {
                                     chan_ptr(m, c, 4), chan_ptr(m, c, 5), c.act ? 1 : 0, dyb, nullptr, rg_apply, rgl, rgc));
     }
     dy = dyb; dy_ldc = c.cout; dy_coff = 0;
+    if (stem_fused) { dy = ob.grad; dy_ldc = ob.ldc; dy_coff = c.out.coff; }
     }
   } else {
     // plain Conv2d with bias (head outputs): dy is the loss gradient itself
@@ -1847,8 +1897,8 @@ int run_conv_bwd(ys_model* m, ConvL& c, int B) {
     return YS_OK;
   }
   // ---- wgrad: queued for the second stream (issued at once without it)
-  if (c.bn && m->overlap && dy != c.dy_own) { ys_set_error("backward: %s has no dy buffer of its own", c.name.c_str()); return YS_ERR_STATE; }
-  YS_TRY(queue_wgrad(m, c, B, dy, dy_ldc, dy_coff, dy_bstride));
+  if (c.bn && m->overlap && dy != c.dy_own && !stem_fused && !stem_scratch) { ys_set_error("backward: %s has no dy buffer of its own", c.name.c_str()); return YS_ERR_STATE; }
+  YS_TRY(queue_wgrad(m, c, B, dy, dy_ldc, dy_coff, dy_bstride, stem_fused));
   // ---- dgrad (gather form with flipped/transposed weights)
   if (!c.first && !no_dx) {
     const int mode = grad_mode(m, c.in);
@@ -2026,6 +2076,17 @@ int backward_range(ys_model* m, int seg_lo, int seg_hi, bool async_end = false, 
     } else if (op.type == OP_POOL) {
       // nothing to launch: the Classify Conv unit's BN / SiLU backward (run_conv_bwd, pool_next) reads dpooled itself
       if (grad_mode(m, op.in) != 0) { ys_set_error("backward: the Classify map has a second gradient writer (op %d)", i); return YS_ERR_STATE; }
+    } else if (int pc[4]; op.type == OP_MAXPOOL && sppf_chain(m, i - 2, pc)) {
+      // the three pools' backward in one launch; the slice states move as the three launches would move them (pool 2's input first)
+      unsigned char* am[3]; int mode[3];
+      for (int k = 2; k >= 0; k--) {
+        am[k] = m->argmax + m->ops[i - 2 + k].aux_off;
+        mode[k] = grad_mode(m, m->ops[i - 2 + k].in);
+        if (mode[k] < 0) { ys_set_error("backward: inconsistent gradient slice state at op %d", i - 2 + k); return YS_ERR_STATE; }
+      }
+      const Buf& gb = m->bufs[op.in.buf];
+      YS_TRY(ys_sppf_pool3_bwd_launch(st, m->dtype, gb.grad, gb.ldc, pc, B, op.H, op.W, op.in.C, am, mode));
+      i -= 2;
     } else {
       const Buf& ib = m->bufs[op.in.buf];
       const Buf& ob = m->bufs[op.out.buf];
@@ -2060,7 +2121,8 @@ int backward_range(ys_model* m, int seg_lo, int seg_hi, bool async_end = false, 
   // The step's LAST dependency chain is dgrad(model.1) -> BN backward of model.0 -> stem weight gradient -> split reduction -> AdamW (round-6 trace: 200 us with the
   // main stream idle).  In the one-call backward the stem's weight gradient is therefore handed over on its own, AFTER the reduction of everything else in its
   // segment has been queued on the second stream: that reduction (48 us) then runs while the main stream is still in the BatchNorm backward of model.0, and only
-  // the stem's own slabs are reduced behind its weight gradient.
+  // the stem's own slabs are reduced behind its weight gradient.  (With the BatchNorm backward inside the stem's weight-gradient kernel -- PendWg::bnb -- that link is
+  // gone from the chain and the launch runs on the main stream: below.)
   bool stem_split = false;
   ys_model::PendWg stem_job{};
   if (async_end && !seg_events && m->overlap && seg_hi == ys_model::NSEG - 1 && !m->pend_wg.empty() && m->convs[m->pend_wg.back().conv].first &&
@@ -2072,7 +2134,14 @@ int backward_range(ys_model* m, int seg_lo, int seg_hi, bool async_end = false, 
   hipStream_t sr = on_st2 ? m->st2 : st;
   if (!on_st2) YS_TRY(join_wgrad_stream(m));
   if (m->f8 && seg_hi == ys_model::NSEG - 1) m->f8_bwd_done = true;     // every gradient maximum of the step is recorded (last segment = stem)
-  if (stem_split) {
+  if (stem_split && stem_job.bnb) {
+    // The stem's weight gradient with its BatchNorm backward inside needs nothing from the second stream and the main stream has nothing else left: it runs HERE,
+    // beside the reduction of the rest of the segment on the second stream, with no hand-over event -- and reads the unit's output and gradient map in stream order.
+    YS_TRY(reduce_range(rlo + 1, rhi, sr));
+    m->st2_dirty = true;
+    YS_TRY(launch_wgrad(m, m->convs[stem_job.conv], B, stem_job.dy, stem_job.ldc, stem_job.coff, stem_job.bstride, st, true));
+    YS_TRY(reduce_range(rlo, rlo + 1, st));
+  } else if (stem_split) {
     YS_TRY(reduce_range(rlo + 1, rhi, sr));
     m->pend_wg.push_back(stem_job);
     YS_TRY(flush_wgrads(m, B));
@@ -2356,7 +2425,7 @@ int ys_model_backward_segment(ys_model* m, int seg) {
   YS_REQUIRE(m->fwd_training, "ys_model_backward: the last forward ran in eval mode (no batch statistics / pre-BN outputs were kept)");
   YS_REQUIRE(seg >= 0 && seg < ys_model::NSEG, "ys_model_backward_segment: segment %d out of range", seg);
   YS_CHECK_HIP(hipSetDevice(m->ctx->device));
-  if (seg == 0) reset_grad_state(m);
+  if (seg == 0) { YS_TRY(join_wgrad_stream(m)); reset_grad_state(m); }   // (the join: see ys_model_backward)
   return backward_range(m, seg, seg);
 }
 
@@ -2365,7 +2434,7 @@ int ys_model_backward_segment_async(ys_model* m, int seg) {
   YS_REQUIRE(m->fwd_training, "ys_model_backward: the last forward ran in eval mode (no batch statistics / pre-BN outputs were kept)");
   YS_REQUIRE(seg >= 0 && seg < ys_model::NSEG, "ys_model_backward_segment_async: segment %d out of range", seg);
   YS_CHECK_HIP(hipSetDevice(m->ctx->device));
-  if (seg == 0) reset_grad_state(m);
+  if (seg == 0) { YS_TRY(join_wgrad_stream(m)); reset_grad_state(m); }
   return backward_range(m, seg, seg, true);
 }
 
@@ -2385,6 +2454,11 @@ int ys_model_backward(ys_model* m) {
   YS_REQUIRE(!m->segment || m->have_seg_loss, "ys_model_backward: the Segment model needs ys_loss_segment (mask gradients)");
   YS_CHECK_HIP(hipSetDevice(m->ctx->device));
   YsTimer timer(m->ctx, "backward");
+  // model.0's weight-gradient kernel reads that unit's raw output and the gradient map of its output (its BatchNorm backward runs inside it, run_conv_bwd: stem_fused).
+  // Where the launch went to the SECOND STREAM (the per-segment calls), it does so after the backward call has returned: every later writer of the two is ordered
+  // behind it by joining the stream -- the next forward does (forward_impl / ys_model_forward), and so does a backward that follows without one, whose dgrad of
+  // model.1 rewrites the gradient map.
+  YS_TRY(join_wgrad_stream(m));
   reset_grad_state(m);
   // Round 6: the one-call backward ends every segment asynchronously as well -- a segment's split reduction (wgrad_reduce_batched_kernel: 1.08 GB of partial slabs per
   // YOLOv8n step, 0.21 ms when it runs alone at the end) goes to the weight-gradient stream behind that segment's weight gradients and runs beside the next segment's

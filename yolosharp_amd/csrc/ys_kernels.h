@@ -105,8 +105,11 @@ bool ys_stem_eligible(int dtype, int cin, int cout, int k, int s);
 int ys_stem_fwd_rows(int B, int Hout, int Wout);
 int ys_stem_fwd_launch(hipStream_t st, const float* x, int B, int H, int W, const void* wf, int Cout, void* y, int out_ldc, int out_coff,
                        long out_bstride, float* stats, const float* scale, const float* shift, int act, int* rows, unsigned long long* stat_acc = nullptr);
+// bnb: the unit's BatchNorm (+ SiLU) backward inside the weight-gradient kernel -- `dy` is then dz of the unit's output, y its raw output [rows][Cout] and
+// scale / shift / k2 / k3 the coefficient rows ys_bn_bwd_apply_launch would take
+struct StemBnb { const void* y; const float *scale, *shift, *k2, *k3; int act; };
 int ys_stem_wgrad_launch(hipStream_t st, const float* x, int B, int H, int W, const void* dy, int dy_ldc, int dy_coff, long dy_bstride,
-                         int Cout, float* partial, int max_splits, int* used);
+                         int Cout, float* partial, int max_splits, int* used, const StemBnb* bnb = nullptr);
 int ys_conv_grid_m(const ConvArgs& a, int dtype);
 int ys_conv_is_p2(const ConvArgs& a);
 // partial rows a launch of `a` (a dgrad with a.nred segments) writes per segment when every kernel it dispatches to supports the fused
@@ -244,6 +247,12 @@ int ys_maxpool5_fwd_launch(hipStream_t st, int dtype, const void* x, int x_ldc, 
                            void* y, int y_ldc, int y_coff, unsigned char* argmax);
 int ys_maxpool5_bwd_launch(hipStream_t st, int dtype, const void* dy, int dy_ldc, int dy_coff, int B, int H, int W,
                            int C, const unsigned char* argmax, void* dx, int dx_ldc, int dx_coff, int accumulate);
+// SPPF: three chained pools of one concat buffer (pool i: slice coff[i] -> slice coff[i + 1]) in one launch, bit for bit the three launches above.
+// argmax / accumulate: one entry per pool (forward: argmax null in eval mode); ys_sppf_pool3_ok: whether the fused form takes the view
+int ys_sppf_pool3_ok(int dtype, int H, int W, int C, int ldc, const int* coff, unsigned char* const* argmax);
+int ys_sppf_pool3_fwd_launch(hipStream_t st, int dtype, void* act, int ldc, const int* coff, int B, int H, int W, int C, unsigned char* const* argmax);
+int ys_sppf_pool3_bwd_launch(hipStream_t st, int dtype, void* grad, int ldc, const int* coff, int B, int H, int W, int C, unsigned char* const* argmax,
+                             const int* accumulate);
 // nearest 2x upsample into a (concat) view, and its backward (2x2 sum)
 int ys_upsample2x_fwd_launch(hipStream_t st, int dtype, const void* x, int x_ldc, int x_coff, int B, int H, int W, int C,
                              void* y, int y_ldc, int y_coff);

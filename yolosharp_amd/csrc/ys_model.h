@@ -145,7 +145,7 @@ struct ys_model {
   // config 2 showed what the per-layer hand-off cost: every hipEventRecord between two kernels of the main stream is a ~6.6 us bubble (29 + 10 + 5 of them per step
   // between bn_bwd_apply and the dgrad that follows) and every ring-slot wait another ~6 us (21 per step): 0.6 ms of an 8.7 ms step with no kernel running on
   // the main stream, all of it in the backward pass (the forward has none).
-  struct PendWg { int conv; const void* dy; int ldc, coff; long bstride; };
+  struct PendWg { int conv; const void* dy; int ldc, coff; long bstride; bool bnb; };   // bnb: dy is dz, the BatchNorm backward runs inside the kernel (model.0)
   std::vector<PendWg> pend_wg; double pend_mb = 0.0; int ev_hand = 0;
   bool hold_stem = false;                      // one-call backward: model.0's weight gradient stays queued until the segment end (backward_range: stem_split)
   // head lanes (round 3): the towers of the three pyramid levels are independent chains (own buffers, own rows of the prediction buffers);
@@ -171,6 +171,8 @@ struct ys_model {
   unsigned char* argmax = nullptr; long n_argmax = 0;
   float* img_dev = nullptr;                      // staging for host images
   bool stem_on = true;                           // YS_STEM_DIRECT=0 at creation: model.0 reads the packed bf16 copy like every other layer
+  bool stem_bnb_fuse = true;                     // YS_STEM_BNB_FUSE=0 at creation: model.0's BatchNorm backward apply pass runs on its own
+  bool sppf_fuse = true;                         // YS_SPPF_FUSE=0 at creation: SPPF's three pools run as three launches (the fused form's reference)
   const float* in_f32 = nullptr;                 // the fp32 NCHW image of the current step when model.0 reads it directly (conv_stem.hip); null = the packed input buffer holds it
   float* pred = nullptr;                         // [B][4+nc][A] fp32 (eval)
   float* out_stage = nullptr; long n_out_stage = 0;
