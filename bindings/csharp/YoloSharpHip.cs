@@ -77,6 +77,11 @@ namespace YoloSharp.Native
         [DllImport(Lib)] internal static extern int ys_model_e2e_obb_init(IntPtr model, int maxDet, int epochs);
         // Obber.Val's per-image part (Obber.cs:102-114) for a batch: rows [B,maxDet,rowStride] (device or host), correct [B,maxDet,10]
         [DllImport(Lib)] internal static extern int ys_val_match_rotated_batched(IntPtr ctx, IntPtr rows, IntPtr count, int onDevice, int batch, int maxDet, int rowStride, int angleCol, IntPtr batchIdx, IntPtr cls, IntPtr bboxes, int nLabels, float imgW, float imgH, IntPtr correct);
+        // End2End Pose (PoseDetector.cs:21-36): One2one_Init for Pose models; ys_loss_pose is then E2EPoseLoss (gains 0.8 / 0.2; the reference's loop never steps them for Pose);
+        // outputs "one2one_kpts" / "one2one_dkpts"; "det" rows [B,k,6+nk] = (x1, y1, x2, y2, score, class, keypoints)
+        [DllImport(Lib)] internal static extern int ys_model_e2e_pose_init(IntPtr model, int maxDet, int epochs);
+        // PoseDetector.Val's per-image part (PoseDetector.cs:131-165) for a batch: rows [B,maxDet,rowStride] (device or host), correctBox / correctPose [B,maxDet,10]
+        [DllImport(Lib)] internal static extern int ys_val_match_pose_batched(IntPtr ctx, IntPtr rows, IntPtr count, int onDevice, int batch, int maxDet, int rowStride, int kptCol, int kptNum, int kptDim, IntPtr batchIdx, IntPtr cls, IntPtr bboxes, IntPtr keypoints, int labelKptDim, int nLabels, float imgW, float imgH, IntPtr correctBox, IntPtr correctPose);
         [DllImport(Lib)] internal static extern int ys_model_e2e_update(IntPtr model);
         [DllImport(Lib)] internal static extern int ys_model_e2e_gains(IntPtr model, out float o2m, out float o2o);
         [DllImport(Lib)] internal static extern int ys_e2e_topk_ex(IntPtr ctx, float[] pred, int onDevice, int batch, int nc, int extra, int anchors, int maxDet, [Out] float[] rows, [Out] long[] anchor);

@@ -148,7 +148,7 @@ YS_API int ys_model_reserve_labels(ys_model* m, int per_image);
  * modules as cv2 / cv3 (the reference copies references, SaveWeight drops the one2one keys), so the model gains NO tensor: ys_model_num_tensors /
  * tensor_info / num_params are unchanged and weight files move freely between End2End and plain models.  max_det: rows of the post-process
  * (0 = 300, Head.cs:13).  YS_DETECT models of both families and every dtype; Segment / OBB / Pose / Classify models and the standalone block /
- * head handles return YS_ERR_UNSUPPORTED (Segment models take ys_model_e2e_init, OBB models ys_model_e2e_obb_init below; Pose End2End is a follow-up).  Call it once, after ys_model_create.  From then on:
+ * head handles return YS_ERR_UNSUPPORTED (Segment models take ys_model_e2e_init, OBB models ys_model_e2e_obb_init, Pose models ys_model_e2e_pose_init below).  Call it once, after ys_model_create.  From then on:
  *   training forward (Head.cs:89-106): "one2one_boxes" / "one2one_scores" are outputs (the same values as "boxes" / "scores": same modules,
  *     same input values); the BatchNorm units of the towers update their running statistics twice, num_batches_tracked += 2.
  *   ys_loss_detect = E2EDetectLoss (Utils/Loss.cs:1094-1118): v8DetectionLoss(tal_topk 10) on one2many + v8DetectionLoss(tal_topk 1) on
@@ -202,6 +202,26 @@ YS_API int ys_model_e2e_gains(ys_model* m, float* o2m, float* o2o);
  *     (Obb.postprocess, Head.cs:439-452), k = min(max_det, A); ys_model_det_device returns its pointer and k.
  *   YS_FP8 models are accepted like fp8 Segment / Detect models by ys_model_e2e_init (the criterion and the one2one pass are dtype-agnostic). */
 YS_API int ys_model_e2e_obb_init(ys_model* m, int max_det, int epochs);
+/* ---- End2End for Pose models (Models/PoseDetector.cs:21-36; Pose.one2one_init, Modules/Head.cs:565-580; E2EPoseLoss, Utils/Loss.cs:1238-1295).
+ * One2one_Init for YS_POSE models of both families and every dtype.  max_det 0 = 300; epochs 0 = 100.  Every other task, a block handle or a head handle
+ * returns YS_ERR_UNSUPPORTED, a second call YS_ERR_STATE; the three entries above keep refusing Pose models.  cv2, cv3 and cv4 are aliased (no Proto),
+ * so NO tensor is added and `.bin` files move freely between plain and End2End Pose models.  From then on:
+ *   training forward: "one2one_boxes" / "one2one_scores" / "one2one_kpts" are the one2many values; the BatchNorm units of cv2 / cv3 / cv4 move their
+ *     running statistics twice per forward (num_batches_tracked += 2), the trunk once.
+ *   ys_loss_pose = E2EPoseLoss: v8PoseLoss(tal_topk 10) on one2many and v8PoseLoss(tal_topk 7, tal_topk2 1) on one2one (the assigner followed by
+ *     ys_tal_keep_best's stage; the one2many criterion is built with tal_topk2 = tal_topk and runs no second stage, Tal.cs:242), combined as
+ *     o2m * L_one2many + o2o * L_one2one; ys_loss_read_items returns the weighted 5 items (box, pose, kobj, cls, dfl), *loss_sum their sum * B.  It also
+ *     runs after an eval forward (the Val loss, PoseDetector.cs:123-124).  "dboxes" / "dscores" / "dkpts" are the one2many gradients (x o2m),
+ *     "one2one_dboxes" / "one2one_dscores" / "one2one_dkpts" the one2one ones (x o2o).  ys_loss_detect alone stays refused.
+ *   gains: 0.8 / 0.2 at creation; ys_model_e2e_update = E2EPoseLoss.update(), ys_model_e2e_gains reads them.  The reference's loop steps the schedule only
+ *     `if (loss is Loss.E2EOBBLoss)` (YoloBaseTaskModel.cs:350-353) and E2EPoseLoss is a class of its own, so a Pose run of the reference keeps 0.8 / 0.2:
+ *     leave ys_model_e2e_update out to reproduce it.
+ *   backward (all forms): towers receive o2m * g_one2many + o2o * g_one2one; the feature maps and everything below o2m * g_one2many.  The zero rows of
+ *     the padded keypoint towers keep zero gradients and parameters.
+ *   eval forward: "pred" [B, 4+nc+nk, A] carries xyxy boxes (Detect.decode_bboxes under end2end, Head.cs:201) and the decoded keypoints; "det"
+ *     [B, k, 6+nk] = (x1, y1, x2, y2, score, class, the nk keypoint values of the selected anchor) = ys_e2e_topk_ex(pred, extra = nk) (Pose.postprocess,
+ *     Head.cs:550-563), k = min(max_det, A); ys_model_det_device returns its pointer and k. */
+YS_API int ys_model_e2e_pose_init(ys_model* m, int max_det, int epochs);
 /* Detect.postprocess / get_topk_index with agnostic_nms = false (Head.cs:117-127, 175-196) over pred [B, 4+nc, A] fp32 (boxes in any
  * format, class scores): k = min(max_det, A); stage 1 = the k anchors with the largest max-over-classes score; stage 2 = the k largest of the
  * k * nc gathered scores, flattened [stage-1 rank][class]; out_rows [B, k, 6] = (box[0..3], score, class), out_anchor [B, k] = the anchor
@@ -374,6 +394,18 @@ YS_API int ys_val_match_batched(ys_ctx* ctx, const float* rows, const int32_t* c
 YS_API int ys_val_match_rotated_batched(ys_ctx* ctx, const float* rows, const int32_t* count, int on_device, int batch, int max_det,
                                         int row_stride, int angle_col, const float* batch_idx, const float* cls, const float* bboxes,
                                         int n_labels, float img_w, float img_h, uint8_t* correct);
+/* PoseDetector.Val (Models/PoseDetector.cs:131-165) for a whole batch: per image b, GT boxes = xyxy of bboxes[batch_idx == b] * (W, H, W, H), GT keypoints
+ * = keypoints[batch_idx == b] * (W, H, 1) (label_kpt_dim == 2: a "seen" column of ones is appended), area = w * h * 0.53; predictions = rows[b, 0:count[b]]:
+ * columns 0..3 the xyxy box, 5 the class, kpt_col.. the kpt_num * kpt_dim keypoint values.  correct_box[b] = match_predictions(rows[:, 5], cls,
+ * Metrics.box_iou(GT, pred)), correct_pose[b] = match_predictions(rows[:, 5], cls, Metrics.kpt_iou(GT kpts, pred kpts, OKS_SIGMA, area)) for
+ * linspace(0.5, 0.95, 10).  rows [B, max_det, row_stride], bboxes [n, 4], keypoints [n, kpt_num, label_kpt_dim], both outputs [B, max_det, 10].
+ * One launch, one workgroup per image; the same IoU / OKS functions as ys_box_iou / ys_kpt_iou, so both outputs equal those + ys_match_predictions
+ * per image bit for bit.  kpt_num <= 64, kpt_dim and label_kpt_dim 2 or 3, 6 <= kpt_col, kpt_col + kpt_num * kpt_dim <= row_stride.  Like
+ * ys_val_match_batched the label workspace holds n_labels entries per image, so no image can exceed it. */
+YS_API int ys_val_match_pose_batched(ys_ctx* ctx, const float* rows, const int32_t* count, int on_device, int batch, int max_det, int row_stride,
+                                     int kpt_col, int kpt_num, int kpt_dim, const float* batch_idx, const float* cls, const float* bboxes,
+                                     const float* keypoints, int label_kpt_dim, int n_labels, float img_w, float img_h, uint8_t* correct_box,
+                                     uint8_t* correct_pose);
 /* Metrics.box_iou (Utils/Metrics.cs:16-34): iou [n, m] of xyxy boxes, fp32, eps as given (reference default 1e-7). */
 YS_API int ys_box_iou(ys_ctx* ctx, const float* box1, int n, const float* box2, int m, float eps, int on_device, float* iou);
 

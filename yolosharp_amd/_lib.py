@@ -137,6 +137,9 @@ PROTOTYPES = {
     "ys_model_one2one_init": (C.c_int, [C.c_void_p, C.c_int]),
     "ys_model_e2e_init": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "ys_model_e2e_obb_init": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    "ys_model_e2e_pose_init": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    "ys_val_match_pose_batched": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p, C.c_void_p]),
     "ys_model_e2e_update": (C.c_int, [C.c_void_p]),
     "ys_val_match_rotated_batched": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                                C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_void_p]),

@@ -4,7 +4,7 @@
 //
 // Criteria (Utils/Loss.cs): v8DetectionLoss :330-484, v8OBBLoss :486-684, v8SegmentationLoss :711-780, v8PoseLoss :870-1071, v8ClassificationLoss
 // :1073-1091 and, over the aliased one2one towers of an End2End model (Modules/Head.cs:89-127, 152-167), E2EDetectLoss :1094-1118, E2EOBBLoss :1120-1177,
-// E2ESegmentLoss :1179-1236: two passes of the task's criterion over the SAME head outputs, the second with its own gradient and scalar buffers.
+// E2ESegmentLoss :1179-1236, E2EPoseLoss :1238-1295: two passes of the task's criterion over the SAME head outputs, the second with its own gradient and scalar buffers.
 #include "ys_model.h"
 #include <cmath>
 #include <cstring>
@@ -29,6 +29,7 @@ static const OutKey OUT_KEYS[] = {
   {"angle", 2, OUT_MC, false, false, true},                {"dangle", 2, OUT_MC, true, false, false},     // the gradients are w.r.t. the raw kpts | the angle LOGIT
   {"one2one_angle", 2, OUT_MC, false, true, true},         {"one2one_dangle", 2, OUT_MC, true, true, false},
   {"kpts", 3, OUT_MC, false, false, false},                {"dkpts", 3, OUT_MC, true, false, false},
+  {"one2one_kpts", 3, OUT_MC, false, true, false},         {"one2one_dkpts", 3, OUT_MC, true, true, false},
 };
 
 int ys_model_get_output(ys_model* m, const char* key, float* host, size_t count) {
@@ -58,7 +59,7 @@ int ys_model_get_output(ys_model* m, const char* key, float* host, size_t count)
     }
   } else if (k == "det") {
     // End2End eval forward: Detect.postprocess (Head.cs:117-127) -> [B, k, 6] = (x1, y1, x2, y2, score, class), k = min(max_det, A); End2End Segment: + the
-    // nm mask coefficients of the anchor (Head.cs:321-339); OBB: + the angle (Head.cs:439-452)
+    // nm mask coefficients of the anchor (Head.cs:321-339); OBB: + the angle (Head.cs:439-452); Pose: + the nk decoded keypoint values (Head.cs:550-563)
     YS_REQUIRE(m->e2e, "ys_model_get_output(det): not an End2End model (ys_model_one2one_init)");
     YS_REQUIRE(!m->fwd_training && !m->training, "ys_model_get_output(det): the last forward ran in training mode");
     const size_t n = (size_t)B * std::min(m->max_det, m->A) * (6 + m->nm);
@@ -80,7 +81,7 @@ int ys_model_get_output(ys_model* m, const char* key, float* host, size_t count)
     const long rows = e->buf == OUT_PR ? (long)m->mh * m->mw : m->A;
     const bool ran = e->buf == OUT_PD || e->buf == OUT_PS ? m->have_loss : m->have_seg_loss;   // cv4 / Proto gradients come from the task's own criterion
     YS_REQUIRE(!e->o2o || m->e2e, "ys_model_get_output(%s): not an End2End model (%s)", key,
-               head == 1 ? "ys_model_e2e_init" : head == 2 ? "ys_model_e2e_obb_init" : "ys_model_one2one_init");
+               head == 1 ? "ys_model_e2e_init" : head == 2 ? "ys_model_e2e_obb_init" : head == 3 ? "ys_model_e2e_pose_init" : "ys_model_one2one_init");
     YS_REQUIRE(!e->grad || ran, "ys_model_get_output(%s): the model's criterion has not run", key);
     YS_REQUIRE(count == (size_t)B * C * rows, "ys_model_get_output(%s): expected %zu elements", key, (size_t)B * C * rows);
     const Buf& b = m->bufs[bufs[e->buf]];
@@ -129,13 +130,13 @@ int ys_model_pred_device(ys_model* m, float** dptr) {
 // YoloBaseTaskModel.One2one_Init -> Detect.one2one_init (Head.cs:152-167): the one2one towers are the SAME Sequential objects as cv2 / cv3
 // (CopyTo copies references), so the model gains no tensor -- only the second criterion pass's gradient / scalar buffers, the snapshot of
 // the towers' running statistics (their second momentum update) and the top-k output of the eval forward.  Segment.one2one_init (Head.cs:245-357) and
-// Obb.one2one_init (Head.cs:454-469) alias cv4 as well; their criteria carry the gain schedule of `epochs` steps (Loss.cs:1138-1148, 1197-1207).
+// Obb.one2one_init (Head.cs:454-469) and Pose.one2one_init (Head.cs:565-580) alias cv4 as well; their criteria carry the gain schedule of `epochs` steps (Loss.cs:1138-1148, 1197-1207).
 // tasks: bit t = the entry accepts full models of ys_task t; the check order is unsupported handle, then second call.
 static int e2e_init(ys_model* m, int max_det, int epochs, unsigned tasks, const char* entry, const char* refusal) {
   const bool full = !m->is_block && !m->is_head && !m->cls && m->pd_buf >= 0 && (m->d.task == YS_DETECT || m->mc_buf >= 0);
   if (!full || !((tasks >> m->d.task) & 1u)) { ys_set_error("%s: %s", entry, refusal); return YS_ERR_UNSUPPORTED; }
   if (m->e2e) { ys_set_error("%s: already initialised", entry); return YS_ERR_STATE; }
-  const bool cv4 = m->segment || m->xkind == 2;
+  const bool cv4 = m->segment || m->xkind >= 2;
   YS_CHECK_HIP(hipSetDevice(m->ctx->device));
   const int B = m->maxB;
   m->max_det = max_det > 0 ? max_det : 300;     // Detect.max_det (Head.cs:13)
@@ -197,7 +198,7 @@ int ys_model_one2one_init(ys_model* m, int max_det) {
   YS_REQUIRE(m, "ys_model_one2one_init: null model");
   YS_REQUIRE(max_det >= 0, "ys_model_one2one_init: max_det = %d", max_det);
   return e2e_init(m, max_det, 0, 1u << YS_DETECT, "ys_model_one2one_init",
-                  "End2End through this entry is built for full Detect models (Segment models: ys_model_e2e_init; OBB / Pose End2End and the standalone heads are follow-ups)");
+                  "End2End through this entry is built for full Detect models (Segment models: ys_model_e2e_init; OBB models: ys_model_e2e_obb_init; Pose models: ys_model_e2e_pose_init; the standalone heads are not built)");
 }
 
 // One2one_Init for Detect AND Segment models (Models/Segmenter.cs:17-24).  epochs: ignored by Detect models, whose criterion is unweighted.
@@ -205,7 +206,7 @@ int ys_model_e2e_init(ys_model* m, int max_det, int epochs) {
   YS_REQUIRE(m, "ys_model_e2e_init: null model");
   YS_REQUIRE(max_det >= 0 && epochs >= 0, "ys_model_e2e_init: max_det = %d, epochs = %d", max_det, epochs);
   return e2e_init(m, max_det, epochs, 1u << YS_DETECT | 1u << YS_SEGMENT, "ys_model_e2e_init",
-                  "End2End is built for full Detect and Segment models (OBB / Pose End2End and the standalone heads are follow-ups)");
+                  "this entry is One2one_Init for full Detect and Segment models (OBB models: ys_model_e2e_obb_init; Pose models: ys_model_e2e_pose_init; the standalone heads are not built)");
 }
 
 // One2one_Init for OBB models (Models/Obber.cs:18-24).  An entry of its own: ys_model_one2one_init and ys_model_e2e_init keep refusing OBB models.
@@ -213,11 +214,19 @@ int ys_model_e2e_obb_init(ys_model* m, int max_det, int epochs) {
   YS_REQUIRE(m, "ys_model_e2e_obb_init: null model");
   YS_REQUIRE(max_det >= 0 && epochs >= 0, "ys_model_e2e_obb_init: max_det = %d, epochs = %d", max_det, epochs);
   return e2e_init(m, max_det, epochs, 1u << YS_OBB, "ys_model_e2e_obb_init",
-                  "this entry is One2one_Init for full OBB models (Detect: ys_model_one2one_init; Segment: ys_model_e2e_init; Pose End2End is a follow-up)");
+                  "this entry is One2one_Init for full OBB models (Detect: ys_model_one2one_init; Segment: ys_model_e2e_init; Pose: ys_model_e2e_pose_init)");
 }
 
-// E2ESegmentLoss.update() (Loss.cs:1225-1235) and E2EOBBLoss.update() (Loss.cs:1166-1176), the same chain.  The reference's training loop calls update() for E2EOBBLoss only (YoloBaseTaskModel.cs:350-353), so a
-// Segment run of the reference keeps 0.8 / 0.2 for its whole life; callers that want the schedule call this once per epoch.
+// One2one_Init for Pose models (Models/PoseDetector.cs:21-36).  An entry of its own: the three entries above keep refusing Pose models.
+int ys_model_e2e_pose_init(ys_model* m, int max_det, int epochs) {
+  YS_REQUIRE(m, "ys_model_e2e_pose_init: null model");
+  YS_REQUIRE(max_det >= 0 && epochs >= 0, "ys_model_e2e_pose_init: max_det = %d, epochs = %d", max_det, epochs);
+  return e2e_init(m, max_det, epochs, 1u << YS_POSE, "ys_model_e2e_pose_init",
+                  "this entry is One2one_Init for full Pose models (Detect: ys_model_one2one_init; Segment: ys_model_e2e_init; OBB: ys_model_e2e_obb_init)");
+}
+
+// E2ESegmentLoss.update() (Loss.cs:1225-1235), E2EOBBLoss.update() (Loss.cs:1166-1176) and E2EPoseLoss.update() (Loss.cs:1284-1294), the same chain.  The reference's training loop calls update() for
+// E2EOBBLoss only (YoloBaseTaskModel.cs:350-353; E2EPoseLoss is a class of its own), so a Segment or Pose run of the reference keeps 0.8 / 0.2 for its whole life; callers that want the schedule call this once per epoch.
 int ys_model_e2e_update(ys_model* m) {
   YS_REQUIRE(m, "ys_model_e2e_update: null model");
   YS_REQUIRE(m->e2e, "ys_model_e2e_update: not an End2End model (ys_model_e2e_init)");
@@ -240,7 +249,7 @@ int ys_model_e2e_gains(ys_model* m, float* o2m, float* o2o) {
 
 int ys_model_det_device(ys_model* m, float** rows, int* k) {
   YS_REQUIRE(m && rows && k, "ys_model_det_device: null argument");
-  YS_REQUIRE(m->e2e, "ys_model_det_device: not an End2End model (ys_model_one2one_init / ys_model_e2e_init)");
+  YS_REQUIRE(m->e2e, "ys_model_det_device: not an End2End model (ys_model_one2one_init / ys_model_e2e_init / _obb_init / _pose_init)");
   *rows = m->det_rows; *k = std::min(m->max_det, m->A);
   return YS_OK;
 }
@@ -255,7 +264,7 @@ int ys_model_reserve_labels(ys_model* m, int per_image) {
 }
 
 // The one2one criterion pass of an End2End model, from the arguments of its one2many pass.  E2EDetectLoss (Loss.cs:1094-1118): v8DetectionLoss(tal_topk 1),
-// unweighted.  E2ESegmentLoss (Loss.cs:1179-1236) / E2EOBBLoss (Loss.cs:1120-1177): the task's criterion with tal_topk 7, tal_topk2 1, weighted with o2o.
+// unweighted.  E2ESegmentLoss (Loss.cs:1179-1236) / E2EOBBLoss (Loss.cs:1120-1177) / E2EPoseLoss (Loss.cs:1238-1295): the task's criterion with tal_topk 7, tal_topk2 1, weighted with o2o.
 // The one2one head outputs ARE the one2many ones (aliased towers, same input values), so the pass reads the same pd / ps / pa.  It pads its own GT again
 // (loss_prep_body: the thin-box widening of Tal.cs:283-287 lands in a fresh tensor, as in the reference where each criterion calls preprocess itself) and
 // reuses the first pass's assignment workspaces: the stream is in order, and what outlives a pass are its gradients and its scalars -- those get buffers of
@@ -324,7 +333,7 @@ static int loss_detect_core(ys_model* m, const float* batch_idx, const float* cl
   }
   YS_TRY(ys_loss_detect_launch(st, m->dtype, a));
   if (first) *first = a;
-  if (m->e2e && !m->segment) YS_TRY(ys_loss_detect_launch(st, m->dtype, one2one_pass(m, a)));   // Segment: ys_loss_segment runs it, after its first mask term
+  if (m->e2e && !m->segment && m->xkind != 3) YS_TRY(ys_loss_detect_launch(st, m->dtype, one2one_pass(m, a)));   // Segment / Pose: ys_loss_segment / ys_loss_pose run it, after their first mask / keypoint term
   YS_CHECK_HIP(hipGetLastError());
   m->have_loss = true;
   return YS_OK;
@@ -378,7 +387,8 @@ int ys_loss_obb(ys_model* m, const float* batch_idx, const float* cls, const flo
   return YS_OK;
 }
 
-// v8PoseLoss (Loss.cs:870-1071): detection part + assignment (loss.hip), then the keypoint terms (poseloss.hip).
+// v8PoseLoss (Loss.cs:870-1071): detection part + assignment (loss.hip), then the keypoint terms (poseloss.hip).  On an End2End model (ys_model_e2e_pose_init)
+// E2EPoseLoss: detect(tal_topk 10) -> keypoint terms -> detect(tal_topk 7, keep-best) -> keypoint terms, each pair weighted with its gain.
 // keypoints: fp32 [n][kpt_num][kpt_dim] normalised to the image like bboxes (x, y[, visibility]); row i belongs to label i.
 int ys_loss_pose(ys_model* m, const float* batch_idx, const float* cls, const float* bboxes, int n, const float* keypoints, int on_device) {
   YS_REQUIRE(m && m->xkind == 3, "ys_loss_pose: model has no Pose head");
@@ -387,7 +397,8 @@ int ys_loss_pose(ys_model* m, const float* batch_idx, const float* cls, const fl
     for (int i = 1; i < n; i++)
       YS_REQUIRE(batch_idx[i] >= batch_idx[i - 1], "ys_loss_pose: labels must be grouped by image in collate order (batch_idx[%d] = %g < batch_idx[%d] = %g)",
                  i, (double)batch_idx[i], i - 1, (double)batch_idx[i - 1]);
-  YS_TRY(loss_detect_core(m, batch_idx, cls, bboxes, n, on_device, true));
+  LossArgs first{};
+  YS_TRY(loss_detect_core(m, batch_idx, cls, bboxes, n, on_device, true, &first));
   m->have_loss = false;
   hipStream_t st = m->ctx->stream;
   const float* kp = keypoints;
@@ -404,12 +415,21 @@ int ys_loss_pose(ys_model* m, const float* batch_idx, const float* cls, const fl
   a.keypoints = kp; a.part = m->seg_part; a.scalars = m->scalars;
   a.B = m->B; a.A = m->A; a.K = m->nm / m->kdim; a.D = m->kdim; a.gcap = m->gcap; a.H = m->d.height; a.W = m->d.width; a.nl = m->nl;
   for (int i = 0; i < 4; i++) { a.lvl_off[i] = m->lvl_off[i]; a.lvl_w[i] = m->lvl_w[i]; a.lvl_stride[i] = m->lvl_stride[i]; }
-  a.hyp_pose = 12.0f; a.hyp_kobj = 1.0f;                                                  // Loss.cs:896
+  a.hyp_pose = 12.0f * m->o2m; a.hyp_kobj = 1.0f * m->o2m;                                // Loss.cs:896; E2EPoseLoss: the gain rides on them (a plain model has o2m = 1)
   static const float oks[17] = {0.026f, 0.025f, 0.025f, 0.035f, 0.035f, 0.079f, 0.079f, 0.072f, 0.072f, 0.062f, 0.062f, 0.107f, 0.107f,
                                 0.087f, 0.087f, 0.089f, 0.089f};                          // OKS_SIGMA (Loss.cs:9-16)
   const bool coco = a.K == 17 && a.D == 3;                                                // Loss.cs:903-905
   for (int k = 0; k < a.K && k < YS_POSE_KMAX; k++) a.sigma[k] = coco ? oks[k] : 1.0f / (float)a.K;
   YS_TRY(ys_loss_pose_launch(st, m->dtype, a, m->seg_cnt, m->seg_off, m->seg_list));
+  if (m->e2e) {
+    // E2EPoseLoss (Loss.cs:1238-1295): the one2one criterion = v8PoseLoss(tal_topk 7, tal_topk2 1) on the same head outputs (aliased towers).  The keypoint
+    // term above has read the first assignment (fg_gt, gt_box, gt_src, seg_cnt / off / list); the second detect pass may now overwrite those workspaces.
+    // Its gradients and scalars have buffers of their own: the launch clears the whole one2one keypoint gradient (padding included) like the one2many one,
+    // and reuses seg_part, which the first launch's finalize has read by then (one stream).
+    YS_TRY(ys_loss_detect_launch(st, m->dtype, one2one_pass(m, first)));
+    a.dkp = m->o2o_dmc; a.scalars = m->scalars2; a.hyp_pose = 12.0f * m->o2o; a.hyp_kobj = 1.0f * m->o2o;
+    YS_TRY(ys_loss_pose_launch(st, m->dtype, a, m->seg_cnt, m->seg_off, m->seg_list));
+  }
   YS_CHECK_HIP(hipGetLastError());
   m->have_loss = true; m->have_seg_loss = true;
   return YS_OK;
@@ -452,6 +472,7 @@ static int read_scalars(ys_model* m, float h[16]) {
     for (int i = 1; i <= 4; i++) h[i] += g[i];
     if (m->segment) h[8] += g[8];            // the mask term
     if (m->xkind == 2) h[13] += g[13];       // the angle term
+    if (m->xkind == 3) { h[10] += g[10]; h[11] += g[11]; }   // the keypoint terms
   }
   if (m->cls || (int)h[15] <= m->gcap) return YS_OK;
   m->have_loss = false; m->have_seg_loss = false;

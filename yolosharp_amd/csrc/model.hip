@@ -1513,7 +1513,8 @@ int forward_impl(ys_model* m, int B) {
                                            (long)(4 + m->d.nc + m->nm) * m->A, (long)(4 + m->d.nc) * m->A));
     if (m->e2e)   // Detect.postprocess on the one2one branch (same values as the one2many branch): [B][k][6] (Head.cs:107-127).  Segment.postprocess (Head.cs:321-339):
                   // the same selection, the nm coefficients gathered by the same anchor index: [B][k][6 + nm]; Obb.postprocess (Head.cs:439-452): the angle channel
-                  // rides the same way, rows (cx, cy, w, h, score, class, angle).  A Detect model has nm = 0
+                  // rides the same way, rows (cx, cy, w, h, score, class, angle); Pose.postprocess (Head.cs:550-563): the nk decoded keypoint values, rows
+                  // (x1, y1, x2, y2, score, class, keypoints) -- the decode above wrote xyxy (Detect.decode_bboxes, Head.cs:201).  A Detect model has nm = 0
       YS_TRY(ys_e2e_topk_launch(st, m->pred, B, m->d.nc, m->A, m->max_det, m->det_ws, m->det_rows, m->det_anchor, m->nm));
   }
   YS_CHECK_HIP(hipGetLastError());
@@ -2031,7 +2032,7 @@ int backward_range(ys_model* m, int seg_lo, int seg_hi, bool async_end = false, 
     // joined in between: the second pass reuses every dy buffer and partial region.
     Buf &pb = m->bufs[m->pd_buf], &sb = m->bufs[m->ps_buf];
     std::swap(pb.grad, m->o2o_dpd); std::swap(sb.grad, m->o2o_dps);
-    if (m->o2o_dmc) std::swap(m->bufs[m->mc_buf].grad, m->o2o_dmc);     // cv4 is aliased too (Segment, Head.cs:245-357: Proto ran once and gets no one2one gradient; Obb, Head.cs:454-469: the angle logits)
+    if (m->o2o_dmc) std::swap(m->bufs[m->mc_buf].grad, m->o2o_dmc);     // cv4 is aliased too (Segment, Head.cs:245-357: Proto ran once and gets no one2one gradient; Obb, Head.cs:454-469: the angle logits; Pose, Head.cs:565-580: the raw keypoints, padded channels included)
     m->e2e_pass = true;
     const int rc = backward_range(m, 0, 0, false, false);
     m->e2e_pass = false;

@@ -42,15 +42,9 @@ box_iou_kernel(const float* __restrict__ b1, int n, const float* __restrict__ b2
 // Metrics.kpt_iou (Metrics.cs:186-212): OKS of ground-truth keypoints kpt1 [n][K][3] (x, y, visibility) against predictions
 // kpt2 [m][K][D]; area [n]; sigma = OKS sigmas when K == 17, else 1/K.  One thread per (gt, prediction) pair.
 struct KptSigma { float s[64]; };
-__global__ void __launch_bounds__(VM_THREADS)
-kpt_iou_kernel(const float* __restrict__ k1, int n, const float* __restrict__ k2, int m, const float* __restrict__ area, int K, int D,
-               KptSigma sg, float eps, float* __restrict__ out) {
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= (long)n * m) return;
-  const int r = (int)(i / m), c = (int)(i - (long)r * m);
-  const float* g = k1 + (long)r * K * 3;
-  const float* p = k2 + (long)c * K * D;
-  const float ar = area[r] + eps;
+// one (gt, prediction) pair: g [K][3], p [K][D], area of the gt.  Shared by kpt_iou_kernel and val_match_pose_kernel, so both evaluate the same operations.
+__device__ inline float vm_oks(const float* __restrict__ g, const float* __restrict__ p, float area, int K, int D, const KptSigma& sg, float eps) {
+  const float ar = area + eps;
   float acc = 0.f, cnt = 0.f;
   for (int k = 0; k < K; k++) {
     const float dx = g[3 * k] - p[D * k], dy = g[3 * k + 1] - p[D * k + 1];
@@ -60,7 +54,15 @@ kpt_iou_kernel(const float* __restrict__ k1, int n, const float* __restrict__ k2
     acc += expf(-e) * mk;
     cnt += mk;
   }
-  out[i] = acc / (cnt + eps);
+  return acc / (cnt + eps);
+}
+__global__ void __launch_bounds__(VM_THREADS)
+kpt_iou_kernel(const float* __restrict__ k1, int n, const float* __restrict__ k2, int m, const float* __restrict__ area, int K, int D,
+               KptSigma sg, float eps, float* __restrict__ out) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (long)n * m) return;
+  const int r = (int)(i / m), c = (int)(i - (long)r * m);
+  out[i] = vm_oks(k1 + (long)r * K * 3, k2 + (long)c * K * D, area[r], K, D, sg, eps);
 }
 
 // one workgroup per image
@@ -108,6 +110,80 @@ val_match_kernel(const float* __restrict__ rows, const int* __restrict__ count, 
     const float t = thr.t[ti];
     for (int d = 0; d < D; d++)
       if ((int)best[2 * d + 1] == k && best[2 * d] >= t) { cor[d * VM_NT + ti] = 1; break; }
+  }
+}
+
+// The per-image part of PoseDetector.Val (Models/PoseDetector.cs:131-165) for a whole batch: val_match_kernel with two metrics.  One workgroup per image
+// gathers the image's labels in collate order and computes, once per label, what :140-156 compute per image: the xyxy box of bboxes * (W, H, W, H), area =
+// (x2 - x1) * (y2 - y1) * 0.53f and the keypoints * (W, H, 1) with the "seen" column of ones for 2-column labels.  Those are pure functions of the label, so
+// they live in workspaces indexed by the LABEL (ws_gt [n_labels][5], ws_kp [n_labels][K][3]): a label belongs to one image, no two workgroups write one word.
+// Per detection: the best class-matching label by vm_iou and the best by vm_oks (lower label index among equals); per (label, threshold) and metric: the
+// first detection that chose the label.  Same operations as ys_box_iou / ys_kpt_iou + ys_match_predictions per image, so both outputs equal that path bit for bit.
+__global__ void __launch_bounds__(VM_THREADS)
+val_match_pose_kernel(const float* __restrict__ rows, const int* __restrict__ count, int max_det, int row_stride, int kpt_col, int K, int D,
+                      const float* __restrict__ batch_idx, const float* __restrict__ cls, const float* __restrict__ bboxes,
+                      const float* __restrict__ keypoints /*[n_labels][K][LD]*/, int LD, int n_labels, float img_w, float img_h, VmThr thr, KptSigma sg,
+                      int lcap, int* __restrict__ ws_lab /*[B][lcap]*/, float* __restrict__ ws_gt /*[n_labels][5]*/, float* __restrict__ ws_kp /*[n_labels][K][3]*/,
+                      float* __restrict__ ws_best /*[B][max_det][4]*/, unsigned char* __restrict__ correct_box /*[B][max_det][10]*/,
+                      unsigned char* __restrict__ correct_pose /*[B][max_det][10]*/, int* __restrict__ overflow) {
+  __shared__ int s_nl;
+  const int b = blockIdx.x, tid = threadIdx.x;
+  int* lab = ws_lab + (long)b * lcap;
+  float* best = ws_best + (long)b * max_det * 4;
+  unsigned char* cob = correct_box + (long)b * max_det * VM_NT;
+  unsigned char* cop = correct_pose + (long)b * max_det * VM_NT;
+  const int Dn = count[b] < max_det ? (count[b] > 0 ? count[b] : 0) : max_det;
+  for (int i = tid; i < max_det * VM_NT; i += VM_THREADS) { cob[i] = 0; cop[i] = 0; }
+  // labels of this image, in collate order (boolean-mask indexing keeps the order, PoseDetector.cs:138-141)
+  if (tid == 0) {
+    int k = 0;
+    for (int j = 0; j < n_labels; j++)
+      if ((int)batch_idx[j] == b) { if (k < lcap) lab[k] = j; k++; }
+    if (k > lcap) { atomicMax(overflow, k); k = lcap; }
+    s_nl = k;
+  }
+  __syncthreads();
+  const int L = s_nl;
+  for (int k = tid; k < L; k += VM_THREADS) {                    // PoseDetector.cs:140, 148, 156
+    const int j = lab[k];
+    const float cx = bboxes[4 * j] * img_w, cy = bboxes[4 * j + 1] * img_h, w = bboxes[4 * j + 2] * img_w, h = bboxes[4 * j + 3] * img_h;
+    const float x1 = cx - w / 2, y1 = cy - h / 2, x2 = cx + w / 2, y2 = cy + h / 2;
+    float* g = ws_gt + 5L * j;
+    g[0] = x1; g[1] = y1; g[2] = x2; g[3] = y2; g[4] = (x2 - x1) * (y2 - y1) * 0.53f;
+  }
+  for (int e = tid; e < L * K; e += VM_THREADS) {                // PoseDetector.cs:141-153
+    const int k = e / K, q = e - k * K;
+    const long j = lab[k];
+    const float* src = keypoints + (j * K + q) * LD;
+    float* dst = ws_kp + (j * K + q) * 3;
+    dst[0] = src[0] * img_w; dst[1] = src[1] * img_h; dst[2] = LD == 3 ? src[2] : 1.0f;      // (w, h, 1): the third factor is exact
+  }
+  __syncthreads();
+  // best class-matching label per detection, by box IoU and by OKS
+  for (int d = tid; d < Dn; d += VM_THREADS) {
+    const float* pr = rows + ((long)b * max_det + d) * row_stride;
+    const float px1 = pr[0], py1 = pr[1], px2 = pr[2], py2 = pr[3], pc = pr[5];
+    float bi = -1.f, bo = -1.f; int bl = -1, ol = -1;
+    for (int k = 0; k < L; k++) {
+      const long j = lab[k];
+      if (cls[j] != pc) continue;
+      const float* g = ws_gt + 5 * j;
+      const float iou = vm_iou(g[0], g[1], g[2], g[3], px1, py1, px2, py2, 1e-7f);
+      if (iou > bi) { bi = iou; bl = k; }
+      const float oks = vm_oks(ws_kp + j * K * 3, pr + kpt_col, g[4], K, D, sg, 1e-7f);
+      if (oks > bo) { bo = oks; ol = k; }
+    }
+    best[4 * d] = bi; best[4 * d + 1] = (float)bl; best[4 * d + 2] = bo; best[4 * d + 3] = (float)ol;
+  }
+  __syncthreads();
+  // every (metric, label, threshold): the first detection that chose this label and clears the threshold
+  for (int e = tid; e < 2 * L * VM_NT; e += VM_THREADS) {
+    const int mt = e / (L * VM_NT), r = e - mt * L * VM_NT;
+    const int k = r / VM_NT, ti = r - k * VM_NT;
+    const float t = thr.t[ti];
+    unsigned char* cor = mt ? cop : cob;
+    for (int d = 0; d < Dn; d++)
+      if ((int)best[4 * d + 2 * mt + 1] == k && best[4 * d + 2 * mt] >= t) { cor[d * VM_NT + ti] = 1; break; }
   }
 }
 
@@ -249,6 +325,15 @@ int ys_mask_iou(ys_ctx* ctx, const float* gt_ids, int nl, const uint8_t* pred_ma
   return YS_OK;
 }
 
+// OKS_SIGMA (PoseDetector.cs:12-19) when K == 17, else 1 / K (Metrics.cs:205)
+static KptSigma vm_sigmas(int kpt_num) {
+  static const float oks[17] = {0.026f, 0.025f, 0.025f, 0.035f, 0.035f, 0.079f, 0.079f, 0.072f, 0.072f, 0.062f, 0.062f, 0.107f, 0.107f,
+                                0.087f, 0.087f, 0.089f, 0.089f};
+  KptSigma ks{};
+  for (int k = 0; k < kpt_num; k++) ks.s[k] = kpt_num == 17 ? oks[k] : 1.0f / (float)kpt_num;
+  return ks;
+}
+
 int ys_kpt_iou(ys_ctx* ctx, const float* kpt1, int n, const float* kpt2, int m, const float* area, int kpt_num, int kpt_dim, float eps,
                int on_device, float* iou) {
   YS_REQUIRE(ctx && iou && n >= 0 && m >= 0, "ys_kpt_iou: bad argument");
@@ -263,10 +348,7 @@ int ys_kpt_iou(ys_ctx* ctx, const float* kpt1, int n, const float* kpt2, int m, 
   const float* da = (const float*)sg.in(area, (size_t)n * 4);
   float* d_iou = (float*)sg.out(iou, (size_t)n * m * 4);
   if (!sg.ok) { ys_set_error("ys_kpt_iou: out of device memory"); return YS_ERR_OOM; }
-  static const float oks[17] = {0.026f, 0.025f, 0.025f, 0.035f, 0.035f, 0.079f, 0.079f, 0.072f, 0.072f, 0.062f, 0.062f, 0.107f, 0.107f,
-                                0.087f, 0.087f, 0.089f, 0.089f};                       // PoseDetector.cs:12-19
-  KptSigma ks{};
-  for (int k = 0; k < kpt_num; k++) ks.s[k] = kpt_num == 17 ? oks[k] : 1.0f / (float)kpt_num;   // Metrics.cs:205
+  const KptSigma ks = vm_sigmas(kpt_num);
   YS_LAUNCH(kpt_iou_kernel, ys_cdiv((long)n * m, VM_THREADS), VM_THREADS, st, d1, n, d2, m, da, kpt_num, kpt_dim, ks, eps, d_iou);
   YS_CHECK_HIP(hipGetLastError());
   if (!on_device) {
@@ -374,6 +456,50 @@ int ys_val_match_rotated_batched(ys_ctx* ctx, const float* rows, const int32_t* 
   YS_TRY(ys_val_match_rot_launch(st, d_rows, d_cnt, batch, max_det, row_stride, angle_col, d_bi, d_cl, d_bb, n_labels, img_w, img_h, thr.t, lcap,
                                  d_lab, d_gt, d_best, d_cor, d_ovf));
   if (!on_device) YS_CHECK_HIP(hipMemcpyAsync(correct, d_cor, ncor, hipMemcpyDeviceToHost, st));
+  YS_CHECK_HIP(hipStreamSynchronize(st));      // the scratch buffers are released on return
+  return YS_OK;
+}
+
+// PoseDetector.Val's per-image part (Models/PoseDetector.cs:131-165) for a batch: val_match_pose_kernel above
+int ys_val_match_pose_batched(ys_ctx* ctx, const float* rows, const int32_t* count, int on_device, int batch, int max_det, int row_stride,
+                              int kpt_col, int kpt_num, int kpt_dim, const float* batch_idx, const float* cls, const float* bboxes,
+                              const float* keypoints, int label_kpt_dim, int n_labels, float img_w, float img_h, uint8_t* correct_box,
+                              uint8_t* correct_pose) {
+  YS_REQUIRE(ctx && rows && count && correct_box && correct_pose, "ys_val_match_pose_batched: null argument");
+  YS_REQUIRE(batch > 0 && max_det > 0 && n_labels >= 0, "ys_val_match_pose_batched: bad shape");
+  YS_REQUIRE(kpt_num > 0 && kpt_num <= 64 && (kpt_dim == 2 || kpt_dim == 3) && (label_kpt_dim == 2 || label_kpt_dim == 3),
+             "ys_val_match_pose_batched: %d keypoints of dim %d, labels of dim %d", kpt_num, kpt_dim, label_kpt_dim);
+  YS_REQUIRE(kpt_col >= 6 && kpt_col + kpt_num * kpt_dim <= row_stride, "ys_val_match_pose_batched: keypoint columns [%d, %d) outside a row of [6, %d)", kpt_col,
+             kpt_col + kpt_num * kpt_dim, row_stride);
+  YS_REQUIRE(n_labels == 0 || (batch_idx && cls && bboxes && keypoints), "ys_val_match_pose_batched: null label arrays");
+  YS_CHECK_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  const int lcap = n_labels > 0 ? n_labels : 1;          // an image can hold all labels of the batch
+  const size_t nrow = (size_t)batch * max_det * row_stride, ncor = (size_t)batch * max_det * VM_NT;
+  const size_t nkp = (size_t)n_labels * kpt_num;
+  VmStage sg(st, on_device);
+  int* d_lab = (int*)sg.alloc((size_t)batch * lcap * 4);
+  float* d_gt = (float*)sg.alloc((size_t)lcap * 20);
+  float* d_kp = (float*)sg.alloc((size_t)lcap * kpt_num * 12);
+  float* d_best = (float*)sg.alloc((size_t)batch * max_det * 16);
+  int* d_ovf = (int*)sg.alloc(4);
+  const float* d_rows = (const float*)sg.in(rows, nrow * 4);
+  const int* d_cnt = (const int*)sg.in(count, (size_t)batch * 4);
+  const float* d_bi = (const float*)sg.in(batch_idx, (size_t)n_labels * 4);
+  const float* d_cl = (const float*)sg.in(cls, (size_t)n_labels * 4);
+  const float* d_bb = (const float*)sg.in(bboxes, (size_t)n_labels * 16);
+  const float* d_kl = (const float*)sg.in(keypoints, nkp * label_kpt_dim * 4);
+  unsigned char* d_cb = (unsigned char*)sg.out(correct_box, ncor);
+  unsigned char* d_cp = (unsigned char*)sg.out(correct_pose, ncor);
+  if (!sg.ok) { ys_set_error("ys_val_match_pose_batched: out of device memory"); return YS_ERR_OOM; }
+  YS_CHECK_HIP(hipMemsetAsync(d_ovf, 0, 4, st));
+  YS_LAUNCH(val_match_pose_kernel, batch, VM_THREADS, st, d_rows, d_cnt, max_det, row_stride, kpt_col, kpt_num, kpt_dim, d_bi, d_cl, d_bb, d_kl,
+            label_kpt_dim, n_labels, img_w, img_h, vm_thresholds(), vm_sigmas(kpt_num), lcap, d_lab, d_gt, d_kp, d_best, d_cb, d_cp, d_ovf);
+  YS_CHECK_HIP(hipGetLastError());
+  if (!on_device) {
+    YS_CHECK_HIP(hipMemcpyAsync(correct_box, d_cb, ncor, hipMemcpyDeviceToHost, st));
+    YS_CHECK_HIP(hipMemcpyAsync(correct_pose, d_cp, ncor, hipMemcpyDeviceToHost, st));
+  }
   YS_CHECK_HIP(hipStreamSynchronize(st));      // the scratch buffers are released on return
   return YS_OK;
 }

@@ -183,13 +183,14 @@ struct ys_model {
   float *ov = nullptr, *align = nullptr; unsigned char* mpos = nullptr; unsigned *pos_align = nullptr, *pos_ov = nullptr;
   int* fg_gt = nullptr; float* tnorm = nullptr; float* loss_partial = nullptr; float* scalars = nullptr;
   // End2End (criterion.hip; Head.cs:89-127, 152-167): the one2one towers ALIAS cv2 / cv3 -- no tensors of their own.  Their criterion pass writes its
-  // gradients and scalars here; the eval forward adds the top-k rows "det" [B][k][6 + nm] (Detect: nm = 0; Segment: + the anchor's coefficients; OBB: + the angle)
+  // gradients and scalars here; the eval forward adds the top-k rows "det" [B][k][6 + nm] (Detect: nm = 0; Segment: + the anchor's coefficients; OBB: + the angle; Pose: + the decoded keypoints)
   bool e2e = false; int max_det = 300;
   void *o2o_dpd = nullptr, *o2o_dps = nullptr, *o2o_dmc = nullptr; float* scalars2 = nullptr;
   // Segment (Head.cs:245-357, Proto runs once) and OBB (Head.cs:454-469) alias cv4 as well.  E2ESegmentLoss / E2EOBBLoss weight their two criteria with the
   // gains o2m / o2o (0.8 / 0.2 until ys_model_e2e_update moves them); every other model keeps 1 / 1 (E2EDetectLoss is unweighted).  "pred" of an OBB model
-  // keeps its xywh + angle form (Obb.decode_bboxes ignores end2end, Head.cs:434-437)
-  bool e2e_cv4() const { return e2e && (segment || xkind == 2); }
+  // keeps its xywh + angle form (Obb.decode_bboxes ignores end2end, Head.cs:434-437).  Pose (Head.cs:485-610; E2EPoseLoss, Loss.cs:1238-1295) aliases cv4 the
+  // same way: o2o_dmc holds the one2one gradient of the raw keypoints, "pred" takes xyxy boxes (Detect.decode_bboxes, Head.cs:201) and det_rows is [B][k][6 + nk]
+  bool e2e_cv4() const { return e2e && (segment || xkind >= 2); }
   float o2m = 1.0f, o2o = 1.0f; int e2e_updates = 0, e2e_epochs = 100;
   float* det_rows = nullptr; long long* det_anchor = nullptr; void* det_ws = nullptr;
   int head_conv0 = 0, det_in[3] = {-1, -1, -1};       // first tower unit in `convs`; the three feature maps the head reads

@@ -325,13 +325,15 @@ class KeyPoint:
 class PoseDetector(Detector):
     """Models/PoseDetector.cs: ImagePredict (:39-98) = eval forward (pred carries the decoded keypoints) + NMS, result = the
     truncated box + KeyPoints (visibility 2.0 for 2-D keypoints); Val (:100-200) = eval forward + v8PoseLoss, NMS (conf 0.01, IoU
-    0.7), box_iou matching and Metrics.kpt_iou (area = w * h * 0.53) matching -> ap_per_class twice."""
+    0.7), box_iou matching and Metrics.kpt_iou (area = w * h * 0.53) matching -> ap_per_class twice.
+    On an End2End model (model.e2e_pose_init; PoseDetector.cs:21-36, 57, 129) the head's own top-k rows [B, k, 6+nk] are only thresholded (Ops.cs:258-267)
+    and Val keeps them on the device: ys_model_det_device -> ys_e2e_select_ex -> ys_val_match_pose_batched (one launch for the per-image part)."""
 
     def ImagePredict(self, image_chw_u8, predict_threshold=0.25, iou_threshold=0.5):
         x = pad_to_32(np.asarray(image_chw_u8, np.float32))[None]
         assert x.shape[2:] == (self.model.height, self.model.width), "create the model with the padded image size"
         inference, _ = self.amp.Evaluate(x)
-        output, _ = self.engine.non_max_suppression(inference["boxes"], predict_threshold, iou_threshold, nc=self.model.nc)
+        output, _ = self.engine.non_max_suppression(inference["boxes"], predict_threshold, iou_threshold, nc=self.model.nc, end2end=self.end2end)
         D = self.model.kpt_dim
         results = []
         for r in output[0]:
@@ -343,6 +345,8 @@ class PoseDetector(Detector):
 
     def Val(self, batches, conf_thres=0.01, iou_thres=0.7, max_det=300):
         from .model import v8PoseLoss
+        if self.end2end:
+            return self._val_end2end(batches, conf_thres, max_det)
         crit = v8PoseLoss(self.model)
         tps, tpps, confs, pcls, tcls = [], [], [], [], []
         loss_sum = None
@@ -372,6 +376,68 @@ class PoseDetector(Detector):
                 oks = self.engine.kpt_iou(gk, rows[:, 6:].reshape(-1, K, D), area)
                 tpps.append(self.engine.match_predictions(rows[:, 5], cl[sel], oks))
                 confs.append(rows[:, 4]); pcls.append(rows[:, 5]); tcls.append(cl[sel])
+        if not tps:
+            return np.zeros(5, np.float32), (0.0, 0.0, 0.0, 0.0), (0.0, 0.0, 0.0, 0.0)
+        conf, pc, tc = np.concatenate(confs), np.concatenate(pcls), np.concatenate(tcls)
+        box = M.val_summary(M.ap_per_class(np.concatenate(tps), conf, pc, tc))
+        pose = M.val_summary(M.ap_per_class(np.concatenate(tpps), conf, pc, tc))
+        return loss_sum, box, pose
+
+    def _val_end2end(self, batches, conf_thres, max_det):
+        """Val on an End2End model: the rows are the head's own [B, k, 6+nk] (ys_model_det_device); thresholding keeps a prefix of them and the per-image
+        box_iou / kpt_iou + two match_predictions run as one launch on the device pointers.  Only rows, counts and the two `correct` arrays come back per batch."""
+        from .model import v8PoseLoss
+        crit = v8PoseLoss(self.model)
+        eng, m = self.engine, self.model
+        K, D = m.kpt_num, m.kpt_dim
+        rl = 6 + K * D
+        tps, tpps, confs, pcls, tcls = [], [], [], [], []
+        loss_sum = None
+        d_det, k = m.det_device()
+        d_cnt = d_cob = d_cop = None
+        cap_b = 0
+        try:
+            for data in batches:
+                if np.asarray(data["batch_idx"]).size < 1:
+                    continue
+                images = np.ascontiguousarray(data["images"], np.float32)
+                B, _, H, W = images.shape
+                m.eval()
+                m.forward(images, fetch=False)
+                _, items = crit.forward(None, data)                 # PoseDetector.cs:123-124: E2EPoseLoss on the eval preds
+                loss_sum = items if loss_sum is None else loss_sum + items
+                if B > cap_b:
+                    for p_ in (d_cnt, d_cob, d_cop):
+                        if p_ is not None:
+                            eng.free(p_)
+                    d_cnt = d_cob = d_cop = None
+                    d_cnt, d_cob, d_cop = eng.malloc(B * 4), eng.malloc(B * k * 10), eng.malloc(B * k * 10)
+                    cap_b = B
+                _lib.check(eng.lib, eng.lib.ys_e2e_select_ex(eng.ctx, d_det, 1, B, k, rl, float(conf_thres), int(max_det), d_cnt))
+                bi = np.ascontiguousarray(np.asarray(data["batch_idx"], np.float32).reshape(-1))
+                cl = np.ascontiguousarray(np.asarray(data["cls"], np.float32).reshape(-1))
+                bb = np.ascontiguousarray(np.asarray(data["bboxes"], np.float32).reshape(-1, 4))
+                kp = np.ascontiguousarray(np.asarray(data["keypoints"], np.float32).reshape(len(bi), K, -1))
+                d_lab = []
+                try:
+                    for a in (bi, cl, bb, kp):
+                        d_lab.append(eng.to_device(a))
+                    _lib.check(eng.lib, eng.lib.ys_val_match_pose_batched(eng.ctx, d_det, d_cnt, 1, B, k, rl, 6, K, D, d_lab[0], d_lab[1], d_lab[2], d_lab[3],
+                                                                          kp.shape[2], bi.shape[0], float(W), float(H), d_cob, d_cop))
+                    rows = eng.from_device(d_det, (B, k, rl), np.float32)
+                    cnt = eng.from_device(d_cnt, (B,), np.int32)
+                    cob = eng.from_device(d_cob, (B, k, 10), np.uint8)
+                    cop = eng.from_device(d_cop, (B, k, 10), np.uint8)
+                finally:
+                    for p_ in d_lab:
+                        eng.free(p_)
+                for b in range(B):
+                    tps.append(cob[b, :cnt[b]].astype(bool)); tpps.append(cop[b, :cnt[b]].astype(bool))
+                    confs.append(rows[b, :cnt[b], 4]); pcls.append(rows[b, :cnt[b], 5]); tcls.append(cl[bi == b])
+        finally:
+            for p_ in (d_cnt, d_cob, d_cop):
+                if p_ is not None:
+                    eng.free(p_)
         if not tps:
             return np.zeros(5, np.float32), (0.0, 0.0, 0.0, 0.0), (0.0, 0.0, 0.0, 0.0)
         conf, pc, tc = np.concatenate(confs), np.concatenate(pcls), np.concatenate(tcls)

@@ -247,6 +247,39 @@ class Engine:
                                                                    _ptr(cl), _ptr(bb), bi.shape[0], float(img_w), float(img_h), _ptr(cor)))
         return [cor[b, :count[b]].astype(bool) for b in range(B)]
 
+    def val_match_pose(self, rows, count, batch, img_w, img_h, kpt_num, kpt_dim, kpt_col=6, on_device=False):
+        """PoseDetector.Val's per-image part (PoseDetector.cs:131-165) in one launch: rows [B,max_det,6+K*D] / count [B] = rows (x1,y1,x2,y2,conf,cls,
+        keypoints); batch = collate dict (batch_idx, cls, bboxes [N,4] normalised cxcywh, keypoints [N,K,2|3] normalised).  Returns two lists of bool
+        [count[b], 10]: match_predictions on Metrics.box_iou and on Metrics.kpt_iou (area = w * h * 0.53) per image, bit for bit what box_iou / kpt_iou +
+        match_predictions give (ys_val_match_pose_batched).  on_device: the same call on device copies of every argument."""
+        rows = np.ascontiguousarray(rows, np.float32)
+        count = np.ascontiguousarray(count, np.int32)
+        B, max_det, stride = rows.shape
+        bi = np.ascontiguousarray(np.asarray(batch["batch_idx"], np.float32).reshape(-1))
+        cl = np.ascontiguousarray(np.asarray(batch["cls"], np.float32).reshape(-1))
+        bb = np.ascontiguousarray(np.asarray(batch["bboxes"], np.float32).reshape(-1, 4))
+        kp = np.ascontiguousarray(np.asarray(batch["keypoints"], np.float32).reshape(bi.shape[0], int(kpt_num), -1))
+        ld = kp.shape[2]
+        cob, cop = np.zeros((B, max_det, 10), np.uint8), np.zeros((B, max_det, 10), np.uint8)
+        args = (B, max_det, stride, int(kpt_col), int(kpt_num), int(kpt_dim))
+        tail = (ld, bi.shape[0], float(img_w), float(img_h))
+        if not on_device:
+            _lib.check(self.lib, self.lib.ys_val_match_pose_batched(self.ctx, _ptr(rows), _ptr(count), 0, *args, _ptr(bi), _ptr(cl), _ptr(bb), _ptr(kp),
+                                                                    *tail, _ptr(cob), _ptr(cop)))
+        else:
+            dev = []
+            try:
+                for a in (rows, count, bi, cl, bb, kp):
+                    dev.append(self.to_device(a) if a.size else self.malloc(4))
+                for _ in range(2):
+                    dev.append(self.malloc(cob.size))
+                _lib.check(self.lib, self.lib.ys_val_match_pose_batched(self.ctx, dev[0], dev[1], 1, *args, dev[2], dev[3], dev[4], dev[5], *tail, dev[6], dev[7]))
+                cob, cop = self.from_device(dev[6], cob.shape, np.uint8), self.from_device(dev[7], cop.shape, np.uint8)
+            finally:
+                for p_ in dev:
+                    self.free(p_)
+        return [cob[b, :count[b]].astype(bool) for b in range(B)], [cop[b, :count[b]].astype(bool) for b in range(B)]
+
     def mask_iou(self, gt_ids, nl, pred_masks, eps=1e-7):
         """Metrics.mask_iou (Metrics.cs:120-125) on (gt_ids == k+1), k < nl, vs pred_masks bool/uint8 [n, h, w] -> [nl, n] fp32."""
         ids = np.ascontiguousarray(gt_ids, np.float32).reshape(-1)
@@ -313,7 +346,7 @@ class Engine:
         `agnostic` flag is accepted but ignored (Ops.cs:345), and invalid thresholds raise (YsError status 1).
         rotated=True (Ops.cs:286,349-353): oriented boxes, angle = last channel, boxes stay xywh, Ops.nms_rotated's
         "any earlier box overlaps" rule on Metrics.batch_probiou."""
-        if end2end:        # Ops.cs:258-267: prediction [B, k, 6 (+ nm | + angle)] rows ordered by score -> rows with score > conf_thres, at most max_det; no keep indices
+        if end2end:        # Ops.cs:258-267: prediction [B, k, 6 (+ nm | + angle | + nk)] rows ordered by score -> rows with score > conf_thres, at most max_det; no keep indices
             rows = np.ascontiguousarray(prediction, np.float32)
             cnt = self.e2e_select(rows, conf_thres, max_det)
             return [rows[b, :cnt[b]].copy() for b in range(rows.shape[0])], [np.zeros((0,), np.float32)]

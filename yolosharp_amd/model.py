@@ -41,7 +41,7 @@ class Yolov8:
         self._batch = 0
         self._info = None
         # Config.End2End (Config.cs:239) -> YoloBaseTaskModel.One2one_Init: the one2one towers alias cv2 / cv3 (Head.cs:152-167), no new tensors.
-        # Detect models only; the library refuses the other tasks (YsError status 4)
+        # Detect models through this argument; Segment / OBB / Pose models have entries of their own (e2e_init / e2e_obb_init / e2e_pose_init)
         self.end2end, self.max_det = False, int(max_det)
         if end2end:
             self.one2one_init(max_det)
@@ -73,7 +73,7 @@ class Yolov8:
         self.end2end, self.max_det = True, int(max_det) if max_det else 300
 
     def e2e_update(self):
-        """E2ESegmentLoss.update() (Loss.cs:1225-1230) / E2EOBBLoss.update() (Loss.cs:1166-1176); nothing on a Detect End2End model."""
+        """E2ESegmentLoss.update() (Loss.cs:1225-1230) / E2EOBBLoss.update() (Loss.cs:1166-1176) / E2EPoseLoss.update() (Loss.cs:1284-1294); nothing on a Detect End2End model."""
         _lib.check(self.lib, self.lib.ys_model_e2e_update(self.handle))
 
     def e2e_gains(self):
@@ -83,7 +83,7 @@ class Yolov8:
         return a.value, b.value
 
     def det_device(self):
-        """Device pointer of the End2End eval output "det" [B, k, 6] (Segment: [B, k, 6+nm]; OBB: [B, k, 7]) and k = min(max_det, A)."""
+        """Device pointer of the End2End eval output "det" [B, k, 6] (Segment: [B, k, 6+nm]; OBB: [B, k, 7]; Pose: [B, k, 6+nk]) and k = min(max_det, A)."""
         p, k = C.c_void_p(), C.c_int()
         _lib.check(self.lib, self.lib.ys_model_det_device(self.handle, C.byref(p), C.byref(k)))
         return p, k.value
@@ -193,11 +193,11 @@ class Yolov8:
         C_ = {"boxes": 4 * self.reg_max, "scores": self.nc, "pred": 4 + self.nc + self.NM, "dboxes": 4 * self.reg_max,
               "dscores": self.nc, "mask_coefficient": self.NM, "dmask_coefficient": self.NM, "angle": self.NM, "kpts": self.NM, "dkpts": self.NM, "dangle": self.NM}.get(key)
         if key.startswith("one2one_"):
-            C_ = 4 * self.reg_max if key.endswith("boxes") else (self.NM if key.endswith(("mask_coefficient", "angle")) else self.nc)
+            C_ = 4 * self.reg_max if key.endswith("boxes") else (self.NM if key.endswith(("mask_coefficient", "angle", "kpts")) else self.nc)
         if key in ("proto", "dproto"):
             a = np.empty((B, self.NM, self.height // 4, self.width // 4), np.float32)
         elif key == "det":
-            a = np.empty((B, min(self.max_det, self.A), 6 + (self.NM if self.TASK in (1, 2) else 0)), np.float32)
+            a = np.empty((B, min(self.max_det, self.A), 6 + (self.NM if self.TASK in (1, 2, 3) else 0)), np.float32)
         else:
             a = np.empty((B, C_, self.A), np.float32)
         _lib.check(self.lib, self.lib.ys_model_get_output(self.handle, key.encode(), _ptr(a), a.size))
@@ -356,14 +356,26 @@ class _ObbMixin:
 
 class _PoseMixin:
     """Head.Pose (Head.cs:484-606): preds gain the raw "kpts" [B,nk,A]; the eval inference tensor is [B, 4+nc+nk, A] with
-    kpts_decode applied (Head.cs:590-605).  Criterion: v8PoseLoss below."""
+    kpts_decode applied (Head.cs:590-605).  Criterion: v8PoseLoss below.
+    After e2e_pose_init (End2End, Head.cs:550-580): preds = {"one2many": {boxes, scores, kpts}, "one2one": {the same values}} and the eval inference dict
+    is {"boxes": det [B,k,6+nk] = (x1, y1, x2, y2, score, class, the anchor's decoded keypoints), "pred": [B,4+nc+nk,A] with xyxy boxes}."""
     TASK = 3
     NM = 51
+
+    def e2e_pose_init(self, max_det=300, epochs=100):
+        """One2one_Init for Pose models (ys_model_e2e_pose_init; PoseDetector.cs:21-36): cv2 / cv3 / cv4 aliased, the criterion becomes E2EPoseLoss with
+        the gains 0.8 / 0.2.  e2e_update / e2e_gains step and read the schedule of `epochs` steps; the reference's loop never steps it for Pose, nor does Trainer."""
+        _lib.check(self.lib, self.lib.ys_model_e2e_pose_init(self.handle, int(max_det), int(epochs)))
+        self.end2end, self.max_det = True, int(max_det) if max_det else 300
 
     def forward(self, x, fetch=True):
         inf, preds = Yolov8.forward(self, x, fetch)
         if fetch:
-            preds["kpts"] = self.get_output("kpts")
+            if self.end2end:
+                preds["one2many"]["kpts"] = self.get_output("kpts")
+                preds["one2one"]["kpts"] = self.get_output("one2one_kpts")
+            else:
+                preds["kpts"] = self.get_output("kpts")
         return inf, preds
 
     __call__ = forward
@@ -521,7 +533,9 @@ class v8PoseLoss(v8SegmentationLoss):
     """Loss.cs:870-1071.  batch additionally carries "keypoints" [N, kpt_num, kpt_dim] normalised (x, y[, visibility]).
     Labels must be grouped by image in collate order (batch_idx non-decreasing; the reference's _select_target_keypoints is only
     defined for that order) -- host labels are validated by the library.
-    Returns (loss*B [5], loss_detach [5]) in the order box, pose, kobj, cls, dfl."""
+    Returns (loss*B [5], loss_detach [5]) in the order box, pose, kobj, cls, dfl.
+    On an End2End Pose model (model.e2e_pose_init) the same call is E2EPoseLoss (Loss.cs:1238-1295): the returned items are
+    o2m * items(one2many, tal_topk 10) + o2o * items(one2one, tal_topk 7, tal_topk2 1) with the model's current gains (model.e2e_gains())."""
 
     def __init__(self, model):
         v8DetectionLoss.__init__(self, model)

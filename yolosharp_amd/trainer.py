@@ -82,7 +82,8 @@ class Trainer:
         self.crit = {0: v8DetectionLoss, 1: v8SegmentationLoss, 2: v8OBBLoss, 3: v8PoseLoss, 4: v8ClassificationLoss}[task](model)
         self.validator = {0: D.Detector, 1: D.Segmenter, 2: D.Obber, 3: D.PoseDetector, 4: D.Classifier}[task]
         # Config.End2End travels with the model (Yolov8(..., end2end=True) / model.e2e_init()): ys_loss_detect is then E2EDetectLoss, ys_loss_segment
-        # E2ESegmentLoss, ys_loss_obb E2EOBBLoss (model.e2e_obb_init()), and D.Detector / D.Segmenter / D.Obber validate without NMS
+        # E2ESegmentLoss, ys_loss_obb E2EOBBLoss (model.e2e_obb_init()), ys_loss_pose E2EPoseLoss (model.e2e_pose_init()), and D.Detector / D.Segmenter /
+        # D.Obber / D.PoseDetector validate without NMS
         self.end2end = bool(getattr(model, "end2end", False))
         self.sched = LrSchedule(model.nc, epochs, nb, **sched)
         self.best_fitness = -float("inf")
@@ -108,7 +109,8 @@ class Trainer:
             i += 1
         self.steps_run = i
         # TrainEpoch ends with `if (loss is Loss.E2EOBBLoss) loss.update()` (YoloBaseTaskModel.cs:350-353): after the loop, so also after an epoch in which
-        # no batch trained.  E2ESegmentLoss is another class and E2EDetectLoss has no gains: their models are not stepped.
+        # no batch trained.  E2ESegmentLoss and E2EPoseLoss are classes of their own (E2EPoseLoss only passes nameof(E2EOBBLoss) as its module name,
+        # Loss.cs:1251) and E2EDetectLoss has no gains: their models are not stepped.
         model = getattr(self, "model", None)
         if getattr(model, "end2end", False) and getattr(model, "TASK", 0) == 2:
             model.e2e_update()
@@ -122,7 +124,7 @@ class Trainer:
             tr = self.train_epoch(train_batches(), epoch)
             self.sched.end_epoch()
             # The reference steps the End2End gain schedule only `if (loss is Loss.E2EOBBLoss)` (YoloBaseTaskModel.cs:350-353): train_epoch does that for an
-            # End2End OBB model.  E2ESegmentLoss is another class, so a Segment run keeps o2m / o2o = 0.8 / 0.2 for its whole life, and E2EDetectLoss has no gains.
+            # End2End OBB model.  E2ESegmentLoss and E2EPoseLoss are other classes, so Segment and Pose runs keep o2m / o2o = 0.8 / 0.2 for their whole life, and E2EDetectLoss has no gains.
             rec = {"epoch": epoch, "train_loss": tr, "lr": list(self.sched.lrs)}
             if val_batches is not None:
                 vloss, metrics, *more = self.validator(self.model).Val(val_batches())   # Segmenter / PoseDetector add mask / pose metrics
