@@ -88,7 +88,7 @@ def _plain_conv_forward(self, x):
 
 
 def _attention_forward(self, x):
-    """C2PSA attention (Block.cs:719-810) with the engine's storage points (csrc/model.hip add_c2psa, csrc/attn_dw.hip): q / k / v are the
+    """C2PSA attention (Block.cs:719-810) with the engine's storage points (csrc/graph.hip add_c2psa, csrc/attn_dw.hip): q / k / v are the
     stored (bf16) qkv output; softmax probabilities are rounded to bf16 for the second product (the MFMA kernels' P operand) while dP = dO^T v
     stays fp32 on the way back (rounding it, as a straight-through rounding of P would, is amplified by the cancellation in dS = P (dP - t) and is
     not what the kernels do); dS is rounded to bf16 in front of the dq / dk products; the attention output is stored bf16; `attention + pe(v)` is one rounding inside pe's BatchNorm + SiLU pass.  Returns the INPUT of proj: proj carries

@@ -1,4 +1,4 @@
-"""Fused BN-backward reduction (round 3; csrc/conv_epi.h BnRedSeg, csrc/model.hip plan_bnred).
+"""Fused BN-backward reduction (round 3; csrc/conv_epi.h BnRedSeg, csrc/plan.hip plan_bnred).
 
 The dgrad launch that completes the gradient dz of a BN Conv unit's output also produces that unit's sums
 sum(du), sum(du * y) (du = dz * SiLU'(BN(y))) in its epilogue, replacing chan_reduce_kernel's pass over dz and y.  The two

@@ -138,7 +138,7 @@ def test_model_fp8_mode(backend, engine):
     x = np.random.default_rng(0).random((B, 3, H, W), dtype=np.float32)
     batch = {k: v.numpy() for k, v in O.synthetic_batch(B, H, W, nc, seed=1, kmax=5).items()}
     ms = {}
-    # the fp8 mode keeps one BN-backward reduction pass per unit (its kernels have no fused variant, csrc/model.hip plan_bnred):
+    # the fp8 mode keeps one BN-backward reduction pass per unit (its kernels have no fused variant, csrc/plan.hip plan_bnred):
     # the bf16 twin is built the same way, so that "first step = bf16 path" can be stated bit for bit
     # Same for the Detect towers: the fp8 mode runs cv2[i][0] / cv3[i][0] as separate launches (c3 = 80 is not a multiple of the fp8
     # K unit) and does not group the levels, so the twin is built with YS_HEAD_FUSE=0 / YS_GROUP=0.  (A fused 144-wide launch and two
@@ -204,7 +204,7 @@ def test_fp8_tracks_bf16_at_size():
         hist[dt] = rec
         m.close()
     # step 0: no recorded maxima yet -> bf16 kernels.  Bit-equal through round 4; since round 5 the bf16 model sums its BatchNorm statistics as fixed-point integer
-    # atomics (model.hip bn_atomic) while the fp8 model keeps the per-workgroup float rows (its quantising apply pass wants the finalized coefficients earlier): the same
+    # atomics (plan.hip allocate: bn_atomic) while the fp8 model keeps the per-workgroup float rows (its quantising apply pass wants the finalized coefficients earlier): the same
     # numbers added in a different order and precision, 1e-4 .. 6e-4 relative on the loss items
     assert np.allclose(hist["fp8"][0][0], hist["bf16"][0][0], rtol=2e-3), (hist["fp8"][0][0], hist["bf16"][0][0])
     for it in range(1, 5):

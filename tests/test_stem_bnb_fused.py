@@ -87,7 +87,7 @@ def test_fused_stem_bn_backward_gives_the_same_gradients(engine, backend, size, 
 def test_back_to_back_steps_without_optimizer_or_sync(engine, backend):
     """The ordering the fused form needs: wherever its weight-gradient launch runs on the second stream it reads model.0's raw output and the gradient
     map of its output after the backward call has returned, so the next forward (which rewrites the first) and the next backward's dgrad of model.1
-    (which rewrites the second) must be ordered behind it -- they join the stream (model.hip: forward_impl, ys_model_backward).  Two passes with no optimizer
+    (which rewrites the second) must be ordered behind it -- they join the stream (model.hip forward_impl, model_api.hip ys_model_backward).  Two passes with no optimizer
     step, no read and no synchronisation in between accumulate two identical gradient contributions; the result must equal the same sequence with
     the separate pass, and two fresh models must agree with each other.  (A pass does not prove the ordering -- the join in the code does; a
     missing one has a chance to show here.)"""

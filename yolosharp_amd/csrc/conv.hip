@@ -1220,7 +1220,7 @@ static P2Plan conv_p2_plan(const ConvArgs& a, int force_mr = 0, int force_npu = 
   }
   }
   if (!p.ok) return p;
-  if ((long)p.g.ntiles > 2L * ys_cdiv(a.M, 64)) { p.ok = 0; return p; }   // stats workspace bound (model.hip stat_max)
+  if ((long)p.g.ntiles > 2L * ys_cdiv(a.M, 64)) { p.ok = 0; return p; }   // stats workspace bound (plan.hip allocate: stat_max)
   // three workgroups per CU (TIGHT register variants) when three footprints fit the 160 KB
   const size_t lds3 = (size_t)50 * 1024;
   p.g.prb = p.g.PW * p.g.ppb;

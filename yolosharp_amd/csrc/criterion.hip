@@ -1,6 +1,6 @@
 // criterion.hip -- the criterion, End2End setup and output accessors of a model handle (ys_model.h): ys_model_get_output / _set_preds, the
 // ys_model_*e2e* / one2one entries, ys_model_reserve_labels and the ys_loss_* ABI.  Host code only: the kernels are loss.hip, segloss.hip, poseloss.hip,
-// classify.hip and e2e.hip, reached through their launchers (ys_kernels.h).  Of model.hip it uses the handle's fields, dev_alloc and alloc_label_ws.
+// classify.hip and e2e.hip, reached through their launchers (ys_kernels.h).  Of the other units of the handle it uses the fields, and plan.hip's dev_alloc and alloc_label_ws.
 //
 // Criteria (Utils/Loss.cs): v8DetectionLoss :330-484, v8OBBLoss :486-684, v8SegmentationLoss :711-780, v8PoseLoss :870-1071, v8ClassificationLoss
 // :1073-1091 and, over the aliased one2one towers of an End2End model (Modules/Head.cs:89-127, 152-167), E2EDetectLoss :1094-1118, E2EOBBLoss :1120-1177,
@@ -9,6 +9,9 @@
 #include <cmath>
 #include <cstring>
 #include <algorithm>
+
+using ysm::dev_alloc;
+using ysm::alloc_label_ws;
 
 extern "C" {
 

@@ -50,7 +50,7 @@ int rccl_load() {
 }  // namespace
 #endif
 
-// implemented in model.hip
+// implemented in model_api.hip
 int ys_model_segment_grad_range(ys_model* m, int seg, int64_t* offset, int64_t* count);
 int ys_model_grad_buffer(ys_model* m, float** dptr, int64_t* count);
 ys_ctx* ys_model_ctx(ys_model* m);

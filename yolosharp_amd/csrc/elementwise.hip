@@ -1265,7 +1265,7 @@ int ys_adamw_launch(hipStream_t st, float* p, const float* g, float* m, float* v
 }
 
 // All parameter groups in one launch: the flat parameter vector is a few contiguous [offset, count) ranges (segment x group,
-// model.hip layout_params), each with its own learning rate.
+// plan.hip layout_params), each with its own learning rate.
 __global__ void __launch_bounds__(EW_THREADS)
 adamw_ranges_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, long n,
                     AdamwRanges rg, float beta1, float beta2, float eps, float wd, float bc1, float bc2_sqrt, AdamwDup dup) {

@@ -1,5 +1,5 @@
-// ys_model.h -- the model handle behind the ys_model_* / ys_loss_* ABI: graph records, struct ys_model and the model.hip internals that
-// criterion.hip calls.  Shared by model.hip and criterion.hip only.
+// ys_model.h -- the model handle behind the ys_model_* / ys_optim_* / ys_block_* / ys_head_* / ys_loss_* ABI: graph records, struct ys_model and what the
+// handle's units call of each other (namespace ysm, at the end).  Shared by graph.hip, plan.hip, model.hip, model_api.hip and criterion.hip only.
 #pragma once
 #include "ys_internal.h"
 #include "ys_kernels.h"
@@ -138,15 +138,16 @@ struct ys_model {
   void* y_all = nullptr; long n_y = 0;
   void* dy_scratch = nullptr; long n_dy = 0;
   // weight gradients run on a second stream, concurrently with the BN-backward / dgrad chain of the following layers
-  // (both mostly latency-bound); dy lives in a ring of DY_RING buffers guarded by events
-  static constexpr int DY_RING = 4;
-  // round 6: weight gradients are handed to the second stream in BATCHES.  Every BatchNorm unit keeps its own dy buffer (ConvL::dy_own: no ring slot to wait for),
+  // (both mostly latency-bound).  A hand-over is one event recorded on the main stream that the second stream waits for: N_HAND + 1 events, taken in
+  // rotation by flush_wgrads (all of them, in index order); the ConvTranspose path always records the last one (run_convT_bwd)
+  static constexpr int N_HAND = 4;
+  // round 6: weight gradients are handed to the second stream in BATCHES.  Every BatchNorm unit keeps its own dy buffer (ConvL::dy_own: nothing shared to wait for),
   // a unit's weight-gradient launch is queued instead of issued, and ONE event record / wait pair hands a whole batch over (flush_wgrads).  A rocprofv3 trace of
   // config 2 showed what the per-layer hand-off cost: every hipEventRecord between two kernels of the main stream is a ~6.6 us bubble (29 + 10 + 5 of them per step
   // between bn_bwd_apply and the dgrad that follows) and every ring-slot wait another ~6 us (21 per step): 0.6 ms of an 8.7 ms step with no kernel running on
   // the main stream, all of it in the backward pass (the forward has none).
   struct PendWg { int conv; const void* dy; int ldc, coff; long bstride; bool bnb; };   // bnb: dy is dz, the BatchNorm backward runs inside the kernel (model.0)
-  std::vector<PendWg> pend_wg; double pend_mb = 0.0; int ev_hand = 0;
+  std::vector<PendWg> pend_wg; double pend_mb = 0.0; int hand_next = 0;
   bool hold_stem = false;                      // one-call backward: model.0's weight gradient stays queued until the segment end (backward_range: stem_split)
   // head lanes (round 3): the towers of the three pyramid levels are independent chains (own buffers, own rows of the prediction buffers);
   // the P4 / P5 chains are short, latency-bound launches (100-400 workgroups) that run beside the P3 chain on two side streams
@@ -154,8 +155,8 @@ struct ys_model {
   // ends; the segment's completion is two events (main stream, weight-gradient stream) a communication stream waits on (ys_model_segment_fence)
   hipEvent_t ev_seg_m[NSEG] = {nullptr, nullptr, nullptr, nullptr}, ev_seg_w[NSEG] = {nullptr, nullptr, nullptr, nullptr};
   bool seg_on_st2[NSEG] = {false, false, false, false};
-  bool overlap = false, overlap_built = false; hipStream_t st2 = nullptr;   // overlap_built: second stream / dy ring exist; overlap: in use (ys_model_set_overlap)
-  hipEvent_t ev_dy[DY_RING + 1] = {nullptr}, ev_join = nullptr;     // hand-over events (rotated; a wait binds to the record that preceded it)
+  bool overlap = false, overlap_built = false; hipStream_t st2 = nullptr;   // overlap_built: second stream / per-unit dy buffers / hand-over events exist; overlap: in use (ys_model_set_overlap)
+  hipEvent_t ev_hand[N_HAND + 1] = {nullptr}, ev_join = nullptr;    // hand-over events (a wait binds to the record that preceded it)
   bool st2_dirty = false;
   float* chan = nullptr; long n_chan = 0;       // per conv: scale, shift, mean, rstd, c1, c2 (6*cout)
   float* stat_partial = nullptr; long n_stat = 0;
@@ -204,6 +205,43 @@ struct ys_model {
   std::vector<void*> allocs;
 };
 
-// model.hip
+// What the units behind the handle call of each other.  Everything else in them is file-local.
+namespace ysm {
+
+constexpr float BN_EPS = 1e-3f, BN_MOMENTUM = 0.03f;   // every BatchNorm2d of the reference (Modules/Convs.cs:36-62)
+
+inline char* view_ptr(ys_model* m, void* base, const Buf& b, long row0) { return (char*)base + (size_t)row0 * b.ldc * m->es; }
+
+// graph.hip -- the op list: buffers, Conv units, blocks, heads and the whole-model graphs
+int new_buf(ys_model* m, int H, int W, int C);
+int add_detect(ys_model* m, const std::string& hp, const int* pv, const int* ch, const int* hh, const int* ww, bool legacy, int seg);
+int add_classify(ys_model* m, const std::string& hp, View in, int c1, int H, int W, int seg);
+int build_v8_detect(ys_model* m);
+int build_v8_classify(ys_model* m);
+int build_v11_detect(ys_model* m);
+int build_v11_classify(ys_model* m);
+int build_block(ys_model* m, const ys_block_desc& bd);
+
+// plan.hip -- parameter layout, weight shadows, every allocation, and the plans the step follows
 int dev_alloc(ys_model* m, void** p, size_t bytes, bool zero = true);   // hipMalloc tracked in ys_model::allocs (freed with the model), zero-filled on the stream
 int alloc_label_ws(ys_model* m, int gcap);                              // (re)allocates the criterion's ground-truth workspace for gcap labels per image
+int layout_params(ys_model* m);
+int allocate(ys_model* m);
+int prep_weights(ys_model* m);             // master weights -> forward / dgrad shadows, when they changed
+bool stem_direct(const ys_model* m);       // model.0 reads the fp32 image planes itself (conv_stem.hip)
+bool stem_bnb_planned(const ys_model* m);  // ... and its BatchNorm backward runs inside its weight-gradient kernel
+int plan_bnred(ys_model* m, int B);        // fused BN-backward reduction: which dgrad launches feed which producers
+// Weight-gradient geometry of layer c reading dy as a [M][dy_ldc] view -- THE place that fills it: workspace sizing (allocate) and launch see the same plan.
+// phase >= 0: that output phase of a ConvTranspose unit (1x1 GEMM over the input grid, dy rows strided over the 2x grid).  x / dy / partial are the caller's.
+WgradArgs wgrad_args(const ys_model* m, const ConvL& c, int B, int dy_ldc, int dy_coff, long dy_bstride, int phase = -1);
+
+// model.hip -- the step
+ConvArgs dgrad_args(ys_model* m, const ConvL& c, int B, const void* dy, int dy_ldc, int dy_coff, long dy_bstride);
+void f8_dgrad_operands(const ys_model* m, const ConvL& c, ConvArgs& a);   // fp8 dgrad: e4m3 dgrad weights and the unit's gradient scale pair (plan_bnred predicts with the same)
+int join_wgrad_stream(ys_model* m);        // order the main stream behind the weight-gradient stream
+int forward_impl(ys_model* m, int B);
+void reset_grad_state(ys_model* m);
+// async_end: leave the weight-gradient stream unjoined (its split reduction runs there too) and record the segment's completion events
+int backward_range(ys_model* m, int seg_lo, int seg_hi, bool async_end = false, bool seg_events = true);
+
+}  // namespace ysm
