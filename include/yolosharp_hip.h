@@ -502,6 +502,18 @@ YS_API int ys_conv_bn_act_fwd(ys_ctx* ctx, int dtype, const float* x_nchw, int B
                               const float* bn_gamma, const float* bn_beta, float* bn_mean, float* bn_var,
                               const float* bias, int act_silu, int training, float* y_nchw);
 
+/* The same unit with the statistics path chosen (training-mode BatchNorm only; otherwise stat_mode is ignored):
+ *   stat_mode 0  one statistics row per workgroup row of the convolution, a finalize launch, a BN + SiLU apply launch (= ys_conv_bn_act_fwd)
+ *   stat_mode 1  what a model with the default BN_ATOMIC = 1 runs: the convolution epilogues add their sums into zeroed 2^-20 fixed-point
+ *                accumulators and the apply pass finalizes from them (no finalize launch); YS_F32 / YS_BF16 only
+ * Optional outputs (may be NULL; training-mode BatchNorm only): y_raw [B,Cout,Ho,Wo] the convolution output the statistics are taken over,
+ * coef [4][Cout] = scale, shift, mean, rstd of this batch, *stat_rows the number of workgroup partial sums per channel the launch produced. */
+YS_API int ys_conv_bn_act_fwd_ex(ys_ctx* ctx, int dtype, const float* x_nchw, int B, int Cin, int H, int W,
+                                 const float* w_oihw, int Cout, int k, int stride,
+                                 const float* bn_gamma, const float* bn_beta, float* bn_mean, float* bn_var,
+                                 const float* bias, int act_silu, int training, int stat_mode, float* y_nchw,
+                                 float* y_raw, float* coef, int32_t* stat_rows);
+
 /* autograd of the same conv2d (Amp.cs:348,370): given dy [B,Cout,Ho,Wo] returns dx [B,Cin,H,W] (optional, may be
  * NULL) and dw [Cout,Cin,k,k]; all fp32 host arrays. */
 YS_API int ys_conv_bwd(ys_ctx* ctx, int dtype, const float* x_nchw, int B, int Cin, int H, int W,
@@ -534,6 +546,75 @@ YS_API int ys_dwconv3x3_fwd(ys_ctx* ctx, int dtype, const float* x, int B, int C
 YS_API int ys_dwconv3x3_bwd(ys_ctx* ctx, int dtype, const float* x, int B, int C, int H, int W, const float* w, const float* dy,
                             int x_ldc, int x_coff, int dx_ldc, int dx_coff, int accumulate, float* dx, float* dw,
                             int32_t* view_intact);
+
+/* ---- BatchNorm training kernels (csrc/elementwise.hip), one stateless call per launch sequence of a Conv unit (unit parity against float64).
+ * Host tensors are CHANNEL-MAJOR [C][rows] fp32 (NCHW with B = 1); C is a multiple of the 16-byte vector (4 fp32 / 8 bf16).  y and dy are dense on the
+ * device as in the model; z, res, dz and rg sit at channel `*_coff` of a [rows][*_coff + C + *_pad] buffer pre-filled with a sentinel, and every workspace
+ * carries a sentinel guard; view_intact = 1 when all of it survived.  eps = 1e-3, momentum = 0.03; the batch count is `rows`. */
+typedef struct ys_bn_fwd_case {
+  const float* y;                 /* [C][rows] pre-BN output (rounded to the storage type on the device) */
+  const float* gamma;             /* [C] */
+  const float* beta;              /* [C] */
+  float* run_mean;                /* [C] in / out */
+  float* run_var;                 /* [C] in / out */
+  float* nbt;                     /* num_batches_tracked as ONE float, in / out; may be NULL */
+  const float* res;               /* optional residual [C][rows], added after the activation */
+  const float* partial;           /* mode 1: [P][2][C] partial (sum, sum of squares) rows, pushed through the fixed-point accumulator */
+  float* z;                       /* out [C][rows] */
+  float* coef;                    /* out [4][C]: scale, shift, mean, rstd */
+  float* part_out;                /* modes 0 / 2, optional: the partial rows the statistics launch wrote, [nblk][2][C] (room for 768 rows) */
+  int64_t* acc_out;               /* mode 1, optional: the raw accumulators [8 shards][C][2] after the push (2^-20 fixed point; bit 62 of word 1 = poison) */
+  int32_t rows, C;
+  int32_t res_pad, res_coff;
+  int32_t z_pad, z_coff;
+  int32_t res_shares_z;           /* != 0: res and z are views of ONE buffer (pitch from the larger coff + C, plus z_pad) */
+  int32_t P;                      /* mode 1: partial rows */
+  int32_t nblk;                   /* out: partial rows of the statistics launch (modes 0 / 2) */
+  int32_t view_intact;            /* out */
+} ys_bn_fwd_case;
+/* mode 0: ys_chan_stats_launch -> ys_bn_finalize_launch -> ys_bn_act_apply_launch (the depthwise unit's path); n = 1
+ * mode 1: `partial` through ys_stat_acc_add (the device function of every convolution epilogue) -> ys_bn_fin_apply_launch; n = 1
+ * mode 2: ys_chan_stats_launch per problem, then ONE ys_bn_finalize_group_launch + ONE ys_bn_act_apply_group_launch over the n problems
+ * More than 256 vectors per row (modes 0 / 2) returns YS_ERR_UNSUPPORTED, more than 9 problems the grouped launcher's status; nothing is launched. */
+YS_API int ys_bn_train_fwd(ys_ctx* ctx, int dtype, int mode, int act_silu, int n, ys_bn_fwd_case* cases);
+
+typedef struct ys_bn_bwd_case {
+  const float* dz;                /* [C][rows] gradient of the unit's output, inside a padded view */
+  const float* y;                 /* [C][rows] pre-BN output of the forward pass */
+  const float* coef;              /* [4][C]: scale, shift, mean, rstd of the forward pass */
+  float* dgamma;                  /* [C] in / out (the kernels accumulate) */
+  float* dbeta;                   /* [C] in / out */
+  float* rg;                      /* optional [C][rows] in / out: the residual input's gradient view, receives rg + dz */
+  const float* src_part[3];       /* mode 3: partial rows [src_nblk[k]][2][C] of source k */
+  float* dy;                      /* out [C][rows] */
+  float* k23;                     /* out [2][C]: k2, k3 of dy = scale * du - k2 - y * k3 */
+  float* part_out;                /* optional: the partial rows of the reduction launch, [nblk][2][C] (room for 768 rows) */
+  int32_t rows, C;
+  int32_t dz_pad, dz_coff;
+  int32_t rg_pad, rg_coff;
+  int32_t nsrc;                   /* mode 3: sources in use; source k covers channels [src_c1[k - 1], src_c1[k]) */
+  int32_t src_nblk[3];
+  int32_t src_c1[3];
+  int32_t nblk;                   /* out */
+  int32_t view_intact;            /* out */
+} ys_bn_bwd_case;
+/* mode 0: ys_bn_bwd_reduce_launch (carries rg) -> ys_bn_bwd_finalize_launch -> ys_bn_bwd_apply_launch; n = 1
+ * mode 1: the same with rg carried by the apply pass (the schedule of a unit whose reduction is fused into a dgrad epilogue); n = 1
+ * mode 2: the reduction per problem, then ONE ys_bn_bwd_finalize_group_launch + ONE ys_bn_bwd_apply_group_launch (which carries rg) over n problems
+ * mode 3: ys_bn_bwd_finalize_src_launch alone on the caller's partial rows (dz, y, dy, rg unused); n = 1 */
+YS_API int ys_bn_train_bwd(ys_ctx* ctx, int dtype, int mode, int act_silu, int n, ys_bn_bwd_case* cases);
+
+/* grad[C] += column sums of x [B,C,rows_per_b] (the bias gradients): the view starts at channel coff of a [B * bstride][coff + Cp + ld_pad] buffer,
+ * Cp = C rounded up to the vector over ZEROED padding channels; images are bstride >= rows_per_b rows apart (the head outputs). */
+YS_API int ys_colsum(ys_ctx* ctx, int dtype, const float* x, int B, int C, int rows_per_b, int bstride, int ld_pad, int coff, float* grad,
+                     int32_t* view_intact);
+/* Nearest 2x up-sample src [B,C,H,W] -> dst [B,C,2H,2W] (backward = 0) or its gradient src [B,C,2H,2W] -> dst [B,C,H,W] (backward = 1; with
+ * accumulate != 0 dst holds the gradient already in the buffer and receives dst + sum, one rounding); row pitch *_ldc >= *_coff + C. */
+YS_API int ys_upsample2x(ys_ctx* ctx, int dtype, int backward, const float* src, int B, int H, int W, int C, int s_ldc, int s_coff, int d_ldc,
+                         int d_coff, int accumulate, float* dst, int32_t* view_intact);
+/* dst view (+)= src view; src, dst [C][rows]. */
+YS_API int ys_copy_view(ys_ctx* ctx, int dtype, const float* src, int rows, int C, int s_ldc, int s_coff, int d_ldc, int d_coff, int accumulate,
+                        float* dst, int32_t* view_intact);
 
 /* ---- per-block entry points: a TorchSharp-free body for the reference's block modules, one stateful handle per
  *      module instance (SURVEY 8b "ys_c2f_fwd/bwd, ys_c3k2_fwd/bwd, ys_sppf_fwd/bwd, ys_proto_fwd/bwd").  The handle IS a

@@ -62,7 +62,9 @@ def ref_forward(x, w, k, s, bn, bias, act, train, dtype):
 @pytest.mark.parametrize("backend", BACKENDS)
 @pytest.mark.parametrize("dtype", ["f32", "bf16"])
 @pytest.mark.parametrize("case", range(len(FWD_CASES)))
-def test_conv_bn_act_forward(backend, engine, dtype, case):
+def test_conv_bn_act_forward(backend, engine, dtype, case, stat_mode=None):
+    """stat_mode None: ys_conv_bn_act_fwd (statistics rows, a finalize launch); 1: ys_conv_bn_act_fwd_ex with the fixed-point accumulators a model runs
+    (ConvArgs::stat_acc in the convolution's epilogue, bn_fin_apply_kernel) -- the same reference and the same bounds."""
     B, Cin, H, W, Cout, k, s, has_bn, has_bias, act, train = FWD_CASES[case]
     g = torch.Generator().manual_seed(case)
     x = torch.randn(B, Cin, H, W, generator=g)
@@ -77,8 +79,11 @@ def test_conv_bn_act_forward(backend, engine, dtype, case):
     bn_ref = {kk: v.clone() for kk, v in bn.items()} if bn else None
     if bn and train:
         ref_forward(x, w, k, s, bn_ref, bias, act, train, dtype)     # updates running stats in place
+    extras = {} if stat_mode is not None else None
     y = engine.conv_bn_act(x.numpy(), w.numpy(), k, s, bn=bn_np, bias=None if bias is None else bias.numpy(), act=act,
-                           training=train, dtype=dtype)
+                           training=train, dtype=dtype, stat_mode=stat_mode, extras=extras)
+    if stat_mode is not None and bn and train:
+        assert extras["stat_rows"] >= 1 and np.isfinite(extras["coef"]).all() and extras["y_raw"].shape == y.shape
     ref = ref.numpy()
     scale = np.abs(ref).max()
     if dtype == "f32":    # north-star tolerance 1e-3 (measured ~1e-6)
@@ -95,6 +100,18 @@ def test_conv_bn_act_forward(backend, engine, dtype, case):
         rtol = 1e-4 if dtype == "f32" else 2e-2
         assert np.allclose(bn_np["running_mean"], bn_ref["running_mean"].numpy(), rtol=rtol, atol=rtol)
         assert np.allclose(bn_np["running_var"], bn_ref["running_var"].numpy(), rtol=rtol, atol=rtol)
+
+
+TRAIN_BN_CASES = [i for i, c in enumerate(FWD_CASES) if c[7] and c[10]]
+
+
+@pytest.mark.parametrize("backend", BACKENDS)
+@pytest.mark.parametrize("dtype", ["f32", "bf16"])
+@pytest.mark.parametrize("case", TRAIN_BN_CASES)
+def test_conv_bn_act_forward_accumulators(backend, engine, dtype, case):
+    """Every training case of test_conv_bn_act_forward on the production statistics path (stat_mode 1): the patch, streamed-weight, blocked-GEMM and halo
+    kernels each run their stat_acc epilogue branch, and bn_fin_apply_kernel finalizes -- held to the bounds of the row mode."""
+    test_conv_bn_act_forward(backend, engine, dtype, case, stat_mode=1)
 
 
 BWD_CASES = [(2, 16, 8, 8, 32, 3, 1), (2, 16, 8, 8, 16, 1, 1), (1, 32, 9, 7, 80, 3, 2), (2, 3, 8, 8, 16, 3, 2),
@@ -161,6 +178,7 @@ def test_halo_kernel_tile_stream(backend, engine, grid, monkeypatch):
     with engine.options(HALO_MAX_GRID=int(grid)):
         for case in (len(FWD_CASES) - 5, len(FWD_CASES) - 4, len(FWD_CASES) - 2):
             test_conv_bn_act_forward(backend, engine, "bf16", case)
+            test_conv_bn_act_forward(backend, engine, "bf16", case, stat_mode=1)
         test_conv_backward(backend, engine, "bf16", len(BWD_CASES) - 2)
 
 
@@ -173,6 +191,7 @@ def test_halo_kernel_16x8_tiles(backend, engine, grid):
     with engine.options(HALO_MR4=2, HALO_MAX_GRID=int(grid)):
         for case in range(len(FWD_CASES) - 5, len(FWD_CASES)):
             test_conv_bn_act_forward(backend, engine, "bf16", case)
+            test_conv_bn_act_forward(backend, engine, "bf16", case, stat_mode=1)
         for case in (len(BWD_CASES) - 2, len(BWD_CASES) - 1):
             test_conv_backward(backend, engine, "bf16", case)
 

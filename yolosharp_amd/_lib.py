@@ -46,6 +46,22 @@ class AugItem(C.Structure):
     _fields_ = [("src", C.c_int32 * 4), ("xc", C.c_int32), ("yc", C.c_int32), ("M", C.c_float * 9), ("flip_lr", C.c_int32), ("flip_ud", C.c_int32)]
 
 
+class BnFwdCase(C.Structure):
+    """ys_bn_fwd_case: one problem of ys_bn_train_fwd (host arrays channel-major [C][rows])."""
+    _fields_ = [("y", C.c_void_p), ("gamma", C.c_void_p), ("beta", C.c_void_p), ("run_mean", C.c_void_p), ("run_var", C.c_void_p), ("nbt", C.c_void_p),
+                ("res", C.c_void_p), ("partial", C.c_void_p), ("z", C.c_void_p), ("coef", C.c_void_p), ("part_out", C.c_void_p),
+                ("acc_out", C.c_void_p), ("rows", C.c_int32), ("C", C.c_int32), ("res_pad", C.c_int32), ("res_coff", C.c_int32), ("z_pad", C.c_int32), ("z_coff", C.c_int32),
+                ("res_shares_z", C.c_int32), ("P", C.c_int32), ("nblk", C.c_int32), ("view_intact", C.c_int32)]
+
+
+class BnBwdCase(C.Structure):
+    """ys_bn_bwd_case: one problem of ys_bn_train_bwd."""
+    _fields_ = [("dz", C.c_void_p), ("y", C.c_void_p), ("coef", C.c_void_p), ("dgamma", C.c_void_p), ("dbeta", C.c_void_p), ("rg", C.c_void_p),
+                ("src_part", C.c_void_p * 3), ("dy", C.c_void_p), ("k23", C.c_void_p), ("part_out", C.c_void_p),
+                ("rows", C.c_int32), ("C", C.c_int32), ("dz_pad", C.c_int32), ("dz_coff", C.c_int32), ("rg_pad", C.c_int32), ("rg_coff", C.c_int32),
+                ("nsrc", C.c_int32), ("src_nblk", C.c_int32 * 3), ("src_c1", C.c_int32 * 3), ("nblk", C.c_int32), ("view_intact", C.c_int32)]
+
+
 # name -> (restype, argtypes); must list every symbol of include/yolosharp_hip.h
 PROTOTYPES = {
     "ys_last_error": (C.c_char_p, []),
@@ -118,6 +134,15 @@ PROTOTYPES = {
     "ys_conv_bn_act_fwd": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                     C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "ys_conv_bn_act_fwd_ex": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                       C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, c_i32_p]),
+    "ys_bn_train_fwd": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(BnFwdCase)]),
+    "ys_bn_train_bwd": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(BnBwdCase)]),
+    "ys_colsum": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, c_i32_p]),
+    "ys_upsample2x": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                               C.c_int, C.c_void_p, c_i32_p]),
+    "ys_copy_view": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, c_i32_p]),
     "ys_conv_bwd": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
                              C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ys_attn_fwd": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,

@@ -12,13 +12,19 @@ struct DevBuf {
 };
 }  // namespace
 
-extern "C" int ys_conv_bn_act_fwd(ys_ctx* ctx, int dtype, const float* x_nchw, int B, int Cin, int H, int W,
-                                  const float* w_oihw, int Cout, int k, int stride, const float* bn_gamma,
-                                  const float* bn_beta, float* bn_mean, float* bn_var, const float* bias,
-                                  int act_silu, int training, float* y_nchw) {
+// stat_mode 0: the convolution writes one statistics row per workgroup row, ys_bn_finalize_launch + ys_bn_act_apply_launch.
+// stat_mode 1: what run_conv_fwd does for a model with BN_ATOMIC = 1 -- the epilogues add their sums into zeroed fixed-point accumulators
+// (ConvArgs::stat_acc, a.stats stays the take-statistics flag) and ys_bn_fin_apply_launch finalizes from them inside the apply pass.
+static int conv_bn_act_fwd_impl(ys_ctx* ctx, int dtype, const float* x_nchw, int B, int Cin, int H, int W,
+                                const float* w_oihw, int Cout, int k, int stride, const float* bn_gamma,
+                                const float* bn_beta, float* bn_mean, float* bn_var, const float* bias,
+                                int act_silu, int training, int stat_mode, float* y_nchw, float* y_raw, float* coef, int32_t* stat_rows) {
   YS_REQUIRE(ctx && x_nchw && w_oihw && y_nchw, "ys_conv_bn_act_fwd: null argument");
   YS_REQUIRE(dtype == YS_F32 || dtype == YS_BF16 || dtype == YS_FP8, "ys_conv_bn_act_fwd: bad dtype %d", dtype);
   YS_REQUIRE((k == 1 || k == 3) && (stride == 1 || stride == 2), "ys_conv_bn_act_fwd: k=%d stride=%d unsupported", k, stride);
+  YS_REQUIRE(stat_mode == 0 || stat_mode == 1, "ys_conv_bn_act_fwd: stat_mode %d", stat_mode);
+  YS_REQUIRE(!(stat_mode == 1 && dtype == YS_FP8), "ys_conv_bn_act_fwd: the fp8 mode keeps statistics rows (stat_mode 0)");
+  YS_REQUIRE(!(y_raw || coef || stat_rows) || (bn_gamma && training), "ys_conv_bn_act_fwd: y_raw / coef / stat_rows exist for training-mode BatchNorm only");
   // YS_FP8: bf16 storage; the convolution runs the fp8 MFMA kernel with CURRENT per-tensor scales of this call's own tensors
   // (s_w = 448 / amax|W|, s_x = 0.5 * 448 / amax|bf16(x)|, the recipe of f8.hip) when Cin % 32 == 0, else the bf16 kernel
   const bool want_f8 = dtype == YS_FP8;
@@ -42,7 +48,7 @@ extern "C" int ys_conv_bn_act_fwd(ys_ctx* ctx, int dtype, const float* x_nchw, i
     for (int ci = 0; ci < Cin; ci++)
       for (int t = 0; t < taps; t++) wint[((size_t)co * taps + t) * Cin + ci] = w_oihw[((size_t)co * Cin + ci) * taps + t];
 
-  DevBuf dx, dxn, dwm, dwf, dy, dz, dstat, dpar, dout;
+  DevBuf dx, dxn, dwm, dwf, dy, dz, dstat, dacc, dpar, dout;
   YS_TRY(dx.alloc((size_t)B * Cin * H * W * 4));
   YS_TRY(dxn.alloc((size_t)B * H * W * cpad * es));
   YS_TRY(dwm.alloc(wint.size() * 4));
@@ -100,14 +106,33 @@ extern "C" int ys_conv_bn_act_fwd(ys_ctx* ctx, int dtype, const float* x_nchw, i
   a.vec_ok = 1; a.M = (int)M;
   const void* result = nullptr;
   if (has_bn && training) {
+    YS_REQUIRE(Cout % epl == 0, "ys_conv_bn_act_fwd: training BN needs Cout %% %d == 0", epl);
     const int gm = ys_conv_grid_m(a, dtype);
     YS_TRY(dstat.alloc((size_t)gm * 2 * Cout * 4));
     a.y = dy.p; a.stats = (float*)dstat.p;
-    YS_TRY(ys_conv_launch(st, dtype, a));
-    YS_TRY(ys_bn_finalize_launch(st, (const float*)dstat.p, gm, Cout, M, g, bt, 1e-3f, 0.03f, rm, rv, nbt, sc, sh, mu, rs));
-    YS_REQUIRE(Cout % epl == 0, "ys_conv_bn_act_fwd: training BN needs Cout %% %d == 0", epl);
-    YS_TRY(ys_bn_act_apply_launch(st, dtype, dy.p, M, Cout, sc, sh, act_silu, nullptr, 0, 0, dz.p, cout_ld, 0));
+    if (stat_mode == 1) {
+      const size_t accb = (size_t)YS_STAT_SHARDS * Cout * 2 * sizeof(unsigned long long);
+      YS_TRY(dacc.alloc(accb));
+      YS_CHECK_HIP(hipMemsetAsync(dacc.p, 0, accb, st));      // one clear per forward, as ys_model_forward does for every unit
+      a.stat_acc = (unsigned long long*)dacc.p;
+      YS_TRY(ys_conv_launch(st, dtype, a));
+      BnAccFin f{};
+      f.acc = (const unsigned long long*)dacc.p; f.count = (double)M;
+      f.gamma = g; f.beta = bt; f.run_mean = rm; f.run_var = rv; f.nbt = nbt;
+      f.scale = sc; f.shift = sh; f.mean = mu; f.rstd = rs; f.eps = 1e-3f; f.momentum = 0.03f;
+      YS_TRY(ys_bn_fin_apply_launch(st, dtype, dy.p, M, Cout, f, act_silu, nullptr, 0, 0, dz.p, cout_ld, 0));
+    } else {
+      YS_TRY(ys_conv_launch(st, dtype, a));
+      YS_TRY(ys_bn_finalize_launch(st, (const float*)dstat.p, gm, Cout, M, g, bt, 1e-3f, 0.03f, rm, rv, nbt, sc, sh, mu, rs));
+      YS_TRY(ys_bn_act_apply_launch(st, dtype, dy.p, M, Cout, sc, sh, act_silu, nullptr, 0, 0, dz.p, cout_ld, 0));
+    }
     result = dz.p;
+    if (stat_rows) *stat_rows = gm;
+    if (coef) YS_CHECK_HIP(hipMemcpyAsync(coef, sc, (size_t)4 * Cout * 4, hipMemcpyDeviceToHost, st));      // scale, shift, mean, rstd are adjacent in the parameter block
+    if (y_raw) {
+      YS_TRY(ys_unpack_nchw_launch(st, dtype, dy.p, cout_ld, 0, B, Cout, (long)Ho * Wo, (float*)dout.p));
+      YS_CHECK_HIP(hipMemcpyAsync(y_raw, dout.p, (size_t)M * Cout * 4, hipMemcpyDeviceToHost, st));
+    }
     YS_CHECK_HIP(hipMemcpyAsync(bn_mean, rm, Cout * 4, hipMemcpyDeviceToHost, st));
     YS_CHECK_HIP(hipMemcpyAsync(bn_var, rv, Cout * 4, hipMemcpyDeviceToHost, st));
   } else {
@@ -128,6 +153,22 @@ extern "C" int ys_conv_bn_act_fwd(ys_ctx* ctx, int dtype, const float* x_nchw, i
   YS_CHECK_HIP(hipStreamSynchronize(st));
   YS_CHECK_HIP(hipGetLastError());
   return YS_OK;
+}
+
+extern "C" int ys_conv_bn_act_fwd(ys_ctx* ctx, int dtype, const float* x_nchw, int B, int Cin, int H, int W,
+                                  const float* w_oihw, int Cout, int k, int stride, const float* bn_gamma,
+                                  const float* bn_beta, float* bn_mean, float* bn_var, const float* bias,
+                                  int act_silu, int training, float* y_nchw) {
+  return conv_bn_act_fwd_impl(ctx, dtype, x_nchw, B, Cin, H, W, w_oihw, Cout, k, stride, bn_gamma, bn_beta, bn_mean, bn_var, bias, act_silu, training, 0,
+                              y_nchw, nullptr, nullptr, nullptr);
+}
+
+extern "C" int ys_conv_bn_act_fwd_ex(ys_ctx* ctx, int dtype, const float* x_nchw, int B, int Cin, int H, int W,
+                                     const float* w_oihw, int Cout, int k, int stride, const float* bn_gamma,
+                                     const float* bn_beta, float* bn_mean, float* bn_var, const float* bias,
+                                     int act_silu, int training, int stat_mode, float* y_nchw, float* y_raw, float* coef, int32_t* stat_rows) {
+  return conv_bn_act_fwd_impl(ctx, dtype, x_nchw, B, Cin, H, W, w_oihw, Cout, k, stride, bn_gamma, bn_beta, bn_mean, bn_var, bias, act_silu, training,
+                              training && bn_gamma ? stat_mode : 0, y_nchw, y_raw, coef, stat_rows);
 }
 
 // Gradients of y = conv2d(x, w, stride, padding=k/2) given dy (autograd of torch.nn.Conv2d, reached from
@@ -474,6 +515,372 @@ extern "C" int ys_dwconv3x3_bwd(ys_ctx* ctx, int dtype, const float* x, int B, i
   }
   YS_TRY(check_sentinel(st, bx.p, rows, x_ldc, x_coff, C, es, &ok));
   YS_CHECK_HIP(hipStreamSynchronize(st));
+  YS_CHECK_HIP(hipGetLastError());
+  if (view_intact) *view_intact = ok;
+  return YS_OK;
+}
+
+// ------------------------------------------------------------------ BatchNorm training kernels of elementwise.hip, one call per launch sequence
+// Host tensors are channel-major [C][rows] (NCHW with B = 1).  y / dy are dense [rows][C] on the device as in the model (a unit's own buffers); z, res, dz and
+// rg sit inside sentinel-padded views; partial-row workspaces and dy carry a sentinel guard behind them.
+namespace {
+constexpr int kEwMaxVec = 256;               // vectors per row the channel-reduction launchers take (EW_THREADS of elementwise.hip)
+
+// ys_stat_acc_add on test-supplied partial rows [P][2][C]: one thread per (row, which, channel) -- the device function every convolution epilogue calls
+__global__ void __launch_bounds__(256)
+stat_acc_push_kernel(const float* __restrict__ partial, int P, int C, unsigned long long* __restrict__ acc) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (long)P * 2 * C) return;
+  const long row = i / (2L * C);
+  const int which = (int)((i / C) & 1), c = (int)(i % C);
+  ys_stat_acc_add(acc, row, C, c, which, partial[i]);
+}
+
+// *ok &= every byte of the [rows][ld] buffer outside the nv channel ranges v[k] = {coff, C} is still the sentinel
+int check_sentinel_views(hipStream_t st, const void* wide, long rows, int ld, const int (*v)[2], int nv, size_t es, int* ok) {
+  std::vector<unsigned char> h((size_t)rows * ld * es);
+  YS_CHECK_HIP(hipMemcpyAsync(h.data(), wide, h.size(), hipMemcpyDeviceToHost, st));
+  YS_CHECK_HIP(hipStreamSynchronize(st));
+  const size_t pitch = (size_t)ld * es;
+  for (long r = 0; r < rows; r++)
+    for (int c = 0; c < ld; c++) {
+      bool in = false;
+      for (int k = 0; k < nv; k++) in |= c >= v[k][0] && c < v[k][0] + v[k][1];
+      if (in) continue;
+      for (size_t b = 0; b < es; b++)
+        if (h[(size_t)r * pitch + (size_t)c * es + b] != kSentinelByte) { *ok = 0; return YS_OK; }
+    }
+  return YS_OK;
+}
+
+int view_ok(const char* who, int dtype, int C, int pad, int coff) {
+  const int epl = ys_epl(dtype);
+  YS_REQUIRE(pad >= 0 && coff >= 0 && pad % epl == 0 && coff % epl == 0, "%s: view (pad %d, coff %d) must sit on the %d-element vector grid (C = %d)", who, pad, coff, epl, C);
+  return YS_OK;
+}
+int h2d(hipStream_t st, void* d, const void* h, size_t bytes) { YS_CHECK_HIP(hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, st)); return YS_OK; }
+int d2h(hipStream_t st, void* h, const void* d, size_t bytes) { YS_CHECK_HIP(hipMemcpyAsync(h, d, bytes, hipMemcpyDeviceToHost, st)); return YS_OK; }
+
+struct BnFwdBufs {
+  DevBuf y, z, res, par, part, acc;
+  int ldz = 0, ldr = 0, nblk = 0;
+  size_t npart = 0;
+  float *g, *bt, *rm, *rv, *sc, *sh, *mu, *rs, *nbt;
+  const void* resp = nullptr;
+};
+struct BnBwdBufs {
+  DevBuf dz, y, rg, dy, par, part, srcp[YS_BNRED_MAXSEG];
+  int ldd = 0, ldg = 0, nblk = 0;
+  size_t npart = 0;
+  float *sc, *sh, *mu, *rs, *dg, *db, *k2, *k3;
+};
+}  // namespace
+
+extern "C" int ys_bn_train_fwd(ys_ctx* ctx, int dtype, int mode, int act, int n, ys_bn_fwd_case* cases) {
+  YS_REQUIRE(ctx && cases, "ys_bn_train_fwd: null argument");
+  YS_REQUIRE(dtype == YS_F32 || dtype == YS_BF16, "ys_bn_train_fwd: bad dtype %d", dtype);
+  YS_REQUIRE(mode >= 0 && mode <= 2 && n >= 1 && (mode == 2 || n == 1), "ys_bn_train_fwd: mode %d with %d problems", mode, n);
+  YS_CHECK_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  const int epl = ys_epl(dtype);
+  const size_t es = ys_es(dtype);
+  if (n > YS_EW_GROUP_MAX) {                  // the grouped launcher's own refusal, before anything is staged
+    std::vector<BnFinProb> none((size_t)n);
+    return ys_bn_finalize_group_launch(st, none.data(), n, 1e-3f, 0.03f);
+  }
+  for (int i = 0; i < n; i++) {
+    const ys_bn_fwd_case& c = cases[i];
+    YS_REQUIRE(c.y && c.gamma && c.beta && c.run_mean && c.run_var && c.z && c.coef, "ys_bn_train_fwd: problem %d: null argument", i);
+    YS_REQUIRE(c.rows >= 1 && c.C >= epl && c.C % epl == 0, "ys_bn_train_fwd: problem %d: rows=%d C=%d (C must be a multiple of %d)", i, c.rows, c.C, epl);
+    YS_TRY(view_ok("ys_bn_train_fwd z", dtype, c.C, c.z_pad, c.z_coff));
+    if (c.res) YS_TRY(view_ok("ys_bn_train_fwd res", dtype, c.C, c.res_pad, c.res_coff));
+    YS_REQUIRE(!(c.res && c.res_shares_z) || c.res_coff + c.C <= c.z_coff || c.z_coff + c.C <= c.res_coff, "ys_bn_train_fwd: problem %d: res and z views overlap", i);
+    YS_REQUIRE(mode != 1 || (c.partial && c.P >= 1), "ys_bn_train_fwd: mode 1 needs partial rows");
+    // ys_chan_stats_launch's limit (one workgroup row holds every vector of a pixel), checked here so that nothing is staged or launched first
+    if (mode != 1 && c.C / epl > kEwMaxVec) { ys_set_error("chan_stats: unsupported channel count %d", c.C); return YS_ERR_UNSUPPORTED; }
+  }
+  BnFwdBufs bufs[YS_EW_GROUP_MAX];
+  for (int i = 0; i < n; i++) {
+    ys_bn_fwd_case& c = cases[i];
+    BnFwdBufs& b = bufs[i];
+    const int C = c.C; const long rows = c.rows;
+    const bool shared = c.res && c.res_shares_z;
+    b.ldz = c.z_coff + C + c.z_pad;
+    if (shared && c.res_coff + C + c.z_pad > b.ldz) b.ldz = c.res_coff + C + c.z_pad;
+    YS_TRY(alloc_filled(b.z, (size_t)rows * b.ldz * es, st));
+    if (c.res) {
+      b.ldr = shared ? b.ldz : c.res_coff + C + c.res_pad;
+      if (!shared) YS_TRY(alloc_filled(b.res, (size_t)rows * b.ldr * es, st));
+      b.resp = shared ? b.z.p : b.res.p;
+      YS_TRY(stage_view(st, dtype, c.res, 1, C, rows, (void*)b.resp, b.ldr, c.res_coff));
+    }
+    YS_TRY(b.y.alloc((size_t)rows * C * es));
+    YS_TRY(stage_view(st, dtype, c.y, 1, C, rows, b.y.p, C, 0));
+    YS_TRY(b.par.alloc((size_t)9 * C * 4));
+    float* par = (float*)b.par.p;
+    b.g = par; b.bt = par + C; b.rm = par + 2 * C; b.rv = par + 3 * C; b.sc = par + 4 * C; b.sh = par + 5 * C; b.mu = par + 6 * C; b.rs = par + 7 * C;
+    b.nbt = c.nbt ? par + 8 * C : nullptr;
+    YS_CHECK_HIP(hipMemsetAsync(par, 0, (size_t)9 * C * 4, st));
+    YS_TRY(h2d(st, b.g, c.gamma, (size_t)C * 4)); YS_TRY(h2d(st, b.bt, c.beta, (size_t)C * 4));
+    YS_TRY(h2d(st, b.rm, c.run_mean, (size_t)C * 4)); YS_TRY(h2d(st, b.rv, c.run_var, (size_t)C * 4));
+    if (c.nbt) YS_TRY(h2d(st, b.nbt, c.nbt, 4));
+    if (mode == 1) {
+      const size_t accb = (size_t)YS_STAT_SHARDS * C * 2 * sizeof(unsigned long long), np = (size_t)c.P * 2 * C;
+      YS_TRY(b.part.alloc(np * 4));
+      YS_TRY(h2d(st, b.part.p, c.partial, np * 4));
+      YS_TRY(alloc_filled(b.acc, accb + kGuardFloats * 4, st));
+      YS_CHECK_HIP(hipMemsetAsync(b.acc.p, 0, accb, st));
+      const float* rows_p = (const float*)b.part.p;        // plain values: the interpreter build's launch captures its arguments by copy
+      unsigned long long* acc_p = (unsigned long long*)b.acc.p;
+      const int P = c.P;
+      YS_LAUNCH(stat_acc_push_kernel, ys_cdiv((long)np, 256), 256, st, rows_p, P, C, acc_p);
+      BnAccFin f{};
+      f.acc = (const unsigned long long*)b.acc.p; f.count = (double)rows;
+      f.gamma = b.g; f.beta = b.bt; f.run_mean = b.rm; f.run_var = b.rv; f.nbt = b.nbt;
+      f.scale = b.sc; f.shift = b.sh; f.mean = b.mu; f.rstd = b.rs; f.eps = 1e-3f; f.momentum = 0.03f;
+      YS_TRY(ys_bn_fin_apply_launch(st, dtype, b.y.p, rows, C, f, act, b.resp, b.ldr, c.res_coff, b.z.p, b.ldz, c.z_coff));
+    } else {
+      b.npart = (size_t)ys_colsum_blocks(rows, C, dtype) * 2 * C;
+      YS_TRY(alloc_filled(b.part, (b.npart + kGuardFloats) * 4, st));
+      YS_TRY(ys_chan_stats_launch(st, dtype, b.y.p, rows, C, (float*)b.part.p, &b.nblk));
+      YS_REQUIRE((size_t)b.nblk * 2 * C == b.npart, "ys_bn_train_fwd: the launcher wrote %d partial rows, %zu were reserved", b.nblk, b.npart / (2 * (size_t)C));
+      if (mode == 0) {
+        YS_TRY(ys_bn_finalize_launch(st, (const float*)b.part.p, b.nblk, C, rows, b.g, b.bt, 1e-3f, 0.03f, b.rm, b.rv, b.nbt, b.sc, b.sh, b.mu, b.rs));
+        YS_TRY(ys_bn_act_apply_launch(st, dtype, b.y.p, rows, C, b.sc, b.sh, act, b.resp, b.ldr, c.res_coff, b.z.p, b.ldz, c.z_coff));
+      }
+    }
+  }
+  if (mode == 2) {
+    BnFinProb fp[YS_EW_GROUP_MAX]; BnApplyProb ap[YS_EW_GROUP_MAX];
+    for (int i = 0; i < n; i++) {
+      const BnFwdBufs& b = bufs[i];
+      fp[i] = BnFinProb{(const float*)b.part.p, b.nblk, cases[i].C, (double)cases[i].rows, b.g, b.bt, b.rm, b.rv, b.nbt, b.sc, b.sh, b.mu, b.rs};
+      ap[i] = BnApplyProb{b.y.p, (long)cases[i].rows, cases[i].C, b.sc, b.sh, b.resp, b.ldr, cases[i].res_coff, b.z.p, b.ldz, cases[i].z_coff};
+    }
+    YS_TRY(ys_bn_finalize_group_launch(st, fp, n, 1e-3f, 0.03f));
+    YS_TRY(ys_bn_act_apply_group_launch(st, dtype, ap, n, act));
+  }
+  for (int i = 0; i < n; i++) {
+    ys_bn_fwd_case& c = cases[i];
+    BnFwdBufs& b = bufs[i];
+    const int C = c.C; const long rows = c.rows;
+    YS_TRY(fetch_view(st, dtype, b.z.p, b.ldz, c.z_coff, 1, C, rows, c.z));
+    YS_TRY(d2h(st, c.coef, b.sc, (size_t)4 * C * 4));
+    YS_TRY(d2h(st, c.run_mean, b.rm, (size_t)C * 4)); YS_TRY(d2h(st, c.run_var, b.rv, (size_t)C * 4));
+    if (c.nbt) YS_TRY(d2h(st, c.nbt, b.nbt, 4));
+    c.nblk = b.nblk;
+    if (c.part_out && mode != 1) YS_TRY(d2h(st, c.part_out, b.part.p, b.npart * 4));
+    if (c.acc_out && mode == 1) YS_TRY(d2h(st, c.acc_out, b.acc.p, (size_t)YS_STAT_SHARDS * C * 2 * sizeof(unsigned long long)));
+    int ok = 1;
+    const int views[2][2] = {{c.z_coff, C}, {c.res_coff, C}};
+    YS_TRY(check_sentinel_views(st, b.z.p, rows, b.ldz, views, c.res && c.res_shares_z ? 2 : 1, es, &ok));
+    if (b.res.p) YS_TRY(check_sentinel(st, b.res.p, rows, b.ldr, c.res_coff, C, es, &ok));
+    if (mode == 1) YS_TRY(check_guard(st, b.acc.p, (size_t)YS_STAT_SHARDS * C * 4, &ok));
+    else YS_TRY(check_guard(st, b.part.p, b.npart, &ok));
+    YS_CHECK_HIP(hipStreamSynchronize(st));
+    c.view_intact = ok;
+  }
+  YS_CHECK_HIP(hipGetLastError());
+  return YS_OK;
+}
+
+extern "C" int ys_bn_train_bwd(ys_ctx* ctx, int dtype, int mode, int act, int n, ys_bn_bwd_case* cases) {
+  YS_REQUIRE(ctx && cases, "ys_bn_train_bwd: null argument");
+  YS_REQUIRE(dtype == YS_F32 || dtype == YS_BF16, "ys_bn_train_bwd: bad dtype %d", dtype);
+  YS_REQUIRE(mode >= 0 && mode <= 3 && n >= 1 && (mode == 2 || n == 1), "ys_bn_train_bwd: mode %d with %d problems", mode, n);
+  YS_CHECK_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  const int epl = ys_epl(dtype);
+  const size_t es = ys_es(dtype);
+  if (n > YS_EW_GROUP_MAX) {
+    std::vector<ChanFinProb> none((size_t)n);
+    return ys_bn_bwd_finalize_group_launch(st, none.data(), n);
+  }
+  for (int i = 0; i < n; i++) {
+    const ys_bn_bwd_case& c = cases[i];
+    YS_REQUIRE(c.coef && c.dgamma && c.dbeta && c.k23, "ys_bn_train_bwd: problem %d: null argument", i);
+    YS_REQUIRE(c.rows >= 1 && c.C >= epl && c.C % epl == 0, "ys_bn_train_bwd: problem %d: rows=%d C=%d (C must be a multiple of %d)", i, c.rows, c.C, epl);
+    if (mode == 3) {
+      YS_REQUIRE(c.nsrc >= 1 && c.nsrc <= YS_BNRED_MAXSEG, "ys_bn_train_bwd: %d partial-row sources", c.nsrc);
+      for (int k = 0; k < c.nsrc; k++) YS_REQUIRE(c.src_part[k] && c.src_nblk[k] >= 1, "ys_bn_train_bwd: source %d is empty", k);
+      continue;
+    }
+    YS_REQUIRE(c.dz && c.y && c.dy, "ys_bn_train_bwd: problem %d: null argument", i);
+    YS_TRY(view_ok("ys_bn_train_bwd dz", dtype, c.C, c.dz_pad, c.dz_coff));
+    if (c.rg) YS_TRY(view_ok("ys_bn_train_bwd rg", dtype, c.C, c.rg_pad, c.rg_coff));
+    if (c.C / epl > kEwMaxVec) { ys_set_error("bn_bwd: unsupported channel count %d", c.C); return YS_ERR_UNSUPPORTED; }   // ys_bn_bwd_reduce_launch's limit, before anything is staged
+  }
+  BnBwdBufs bufs[YS_EW_GROUP_MAX];
+  for (int i = 0; i < n; i++) {
+    ys_bn_bwd_case& c = cases[i];
+    BnBwdBufs& b = bufs[i];
+    const int C = c.C; const long rows = c.rows;
+    YS_TRY(b.par.alloc((size_t)8 * C * 4));
+    float* par = (float*)b.par.p;
+    b.sc = par; b.sh = par + C; b.mu = par + 2 * C; b.rs = par + 3 * C; b.dg = par + 4 * C; b.db = par + 5 * C; b.k2 = par + 6 * C; b.k3 = par + 7 * C;
+    YS_CHECK_HIP(hipMemsetAsync(par, kSentinelByte, (size_t)8 * C * 4, st));        // k2 / k3 start as the sentinel: an unwritten coefficient shows
+    YS_TRY(h2d(st, b.sc, c.coef, (size_t)4 * C * 4));
+    YS_TRY(h2d(st, b.dg, c.dgamma, (size_t)C * 4)); YS_TRY(h2d(st, b.db, c.dbeta, (size_t)C * 4));
+    if (mode == 3) {
+      FinSrc src{};
+      src.n = c.nsrc;
+      for (int k = 0; k < c.nsrc; k++) {
+        const size_t nb = (size_t)c.src_nblk[k] * 2 * C * 4;
+        YS_TRY(b.srcp[k].alloc(nb));
+        YS_TRY(h2d(st, b.srcp[k].p, c.src_part[k], nb));
+        src.p[k] = (const float*)b.srcp[k].p; src.nblk[k] = c.src_nblk[k]; src.c1[k] = c.src_c1[k];
+      }
+      YS_TRY(ys_bn_bwd_finalize_src_launch(st, src, C, rows, b.dg, b.db, b.k2, b.k3, b.sc, b.mu, b.rs));
+      continue;
+    }
+    b.ldd = c.dz_coff + C + c.dz_pad;
+    YS_TRY(alloc_filled(b.dz, (size_t)rows * b.ldd * es, st));
+    YS_TRY(stage_view(st, dtype, c.dz, 1, C, rows, b.dz.p, b.ldd, c.dz_coff));
+    YS_TRY(b.y.alloc((size_t)rows * C * es));
+    YS_TRY(stage_view(st, dtype, c.y, 1, C, rows, b.y.p, C, 0));
+    if (c.rg) {
+      b.ldg = c.rg_coff + C + c.rg_pad;
+      YS_TRY(alloc_filled(b.rg, (size_t)rows * b.ldg * es, st));
+      YS_TRY(stage_view(st, dtype, c.rg, 1, C, rows, b.rg.p, b.ldg, c.rg_coff));
+    }
+    YS_TRY(alloc_filled(b.dy, (size_t)rows * C * es + kGuardFloats * 4, st));
+    b.npart = (size_t)ys_colsum_blocks(rows, C, dtype) * 2 * C;
+    YS_TRY(alloc_filled(b.part, (b.npart + kGuardFloats) * 4, st));
+    YS_TRY(ys_bn_bwd_reduce_launch(st, dtype, b.dz.p, b.ldd, c.dz_coff, b.y.p, rows, C, b.sc, b.sh, b.mu, b.rs, act, mode == 0 ? b.rg.p : nullptr, b.ldg, c.rg_coff,
+                                   (float*)b.part.p, &b.nblk));
+    YS_REQUIRE((size_t)b.nblk * 2 * C == b.npart, "ys_bn_train_bwd: the launcher wrote %d partial rows, %zu were reserved", b.nblk, b.npart / (2 * (size_t)C));
+    if (mode == 2) continue;
+    YS_TRY(ys_bn_bwd_finalize_launch(st, (const float*)b.part.p, b.nblk, C, rows, b.dg, b.db, b.k2, b.k3, b.sc, b.mu, b.rs));
+    YS_TRY(ys_bn_bwd_apply_launch(st, dtype, b.dz.p, b.ldd, c.dz_coff, b.y.p, rows, C, b.sc, b.sh, b.k2, b.k3, act, b.dy.p, nullptr, mode == 1 ? b.rg.p : nullptr,
+                                  b.ldg, c.rg_coff));
+  }
+  if (mode == 2) {
+    ChanFinProb fp[YS_EW_GROUP_MAX]; BnBwdProb bp[YS_EW_GROUP_MAX];
+    for (int i = 0; i < n; i++) {
+      const BnBwdBufs& b = bufs[i];
+      FinSrc src{}; src.n = 1; src.p[0] = (const float*)b.part.p; src.nblk[0] = b.nblk; src.c1[0] = cases[i].C;
+      fp[i] = ChanFinProb{src, cases[i].C, (double)cases[i].rows, b.dg, b.db, b.k2, b.k3, b.sc, b.mu, b.rs};
+      bp[i] = BnBwdProb{b.dz.p, b.ldd, cases[i].dz_coff, b.y.p, (long)cases[i].rows, cases[i].C, b.sc, b.sh, b.k2, b.k3, b.dy.p, b.rg.p, b.ldg, cases[i].rg_coff};
+    }
+    YS_TRY(ys_bn_bwd_finalize_group_launch(st, fp, n));
+    YS_TRY(ys_bn_bwd_apply_group_launch(st, dtype, bp, n, act));
+  }
+  for (int i = 0; i < n; i++) {
+    ys_bn_bwd_case& c = cases[i];
+    BnBwdBufs& b = bufs[i];
+    const int C = c.C; const long rows = c.rows;
+    YS_TRY(d2h(st, c.dgamma, b.dg, (size_t)C * 4)); YS_TRY(d2h(st, c.dbeta, b.db, (size_t)C * 4));
+    YS_TRY(d2h(st, c.k23, b.k2, (size_t)2 * C * 4));
+    int ok = 1;
+    if (mode != 3) {
+      YS_TRY(fetch_view(st, dtype, b.dy.p, C, 0, 1, C, rows, c.dy));
+      if (c.rg) YS_TRY(fetch_view(st, dtype, b.rg.p, b.ldg, c.rg_coff, 1, C, rows, c.rg));
+      c.nblk = b.nblk;
+      if (c.part_out) YS_TRY(d2h(st, c.part_out, b.part.p, b.npart * 4));
+      YS_TRY(check_sentinel(st, b.dz.p, rows, b.ldd, c.dz_coff, C, es, &ok));
+      if (c.rg) YS_TRY(check_sentinel(st, b.rg.p, rows, b.ldg, c.rg_coff, C, es, &ok));
+      YS_TRY(check_guard(st, b.part.p, b.npart, &ok));
+      YS_TRY(check_guard(st, b.dy.p, (size_t)rows * C * es / 4, &ok));
+    }
+    YS_CHECK_HIP(hipStreamSynchronize(st));
+    c.view_intact = ok;
+  }
+  YS_CHECK_HIP(hipGetLastError());
+  return YS_OK;
+}
+
+// grad[C] += column sums of x [B][C][rows_per_b] (chan_reduce_kernel MODE 1 + chan_finalize_kernel MODE 1, the bias gradients): the view starts at channel coff
+// of a [B * bstride][coff + Cp + ld_pad] buffer, Cp = C rounded up to the vector width over ZEROED padding channels; images are bstride >= rows_per_b rows apart
+// and the rows between them hold the sentinel.
+extern "C" int ys_colsum(ys_ctx* ctx, int dtype, const float* x, int B, int C, int rows_per_b, int bstride, int ld_pad, int coff, float* grad,
+                         int32_t* view_intact) {
+  YS_REQUIRE(ctx && x && grad, "ys_colsum: null argument");
+  YS_REQUIRE(dtype == YS_F32 || dtype == YS_BF16, "ys_colsum: bad dtype %d", dtype);
+  YS_REQUIRE(B >= 1 && C >= 1 && rows_per_b >= 1 && bstride >= rows_per_b, "ys_colsum: B=%d C=%d rows_per_b=%d bstride=%d", B, C, rows_per_b, bstride);
+  YS_TRY(view_ok("ys_colsum", dtype, C, ld_pad, coff));
+  const int epl = ys_epl(dtype);
+  const size_t es = ys_es(dtype);
+  const int Cp = (C + epl - 1) / epl * epl, ld = coff + Cp + ld_pad;
+  if (Cp / epl > kEwMaxVec) { ys_set_error("colsum: unsupported channel count %d", C); return YS_ERR_UNSUPPORTED; }    // ys_colsum_launch's limit, before anything is staged
+  YS_CHECK_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  const long rows = (long)B * rows_per_b, brows = (long)B * bstride;
+  DevBuf dx, dpart, dgrad;
+  YS_TRY(alloc_filled(dx, (size_t)brows * ld * es, st));
+  std::vector<float> hp((size_t)Cp * rows_per_b, 0.f);
+  for (int b = 0; b < B; b++) {
+    memcpy(hp.data(), x + (size_t)b * C * rows_per_b, (size_t)C * rows_per_b * 4);
+    YS_TRY(stage_view(st, dtype, hp.data(), 1, Cp, rows_per_b, (char*)dx.p + (size_t)b * bstride * ld * es, ld, coff));
+  }
+  const size_t np = (size_t)ys_colsum_blocks(rows, Cp, dtype) * 2 * Cp;
+  YS_TRY(alloc_filled(dpart, (np + kGuardFloats) * 4, st));
+  YS_TRY(alloc_filled(dgrad, ((size_t)C + kGuardFloats) * 4, st));
+  YS_TRY(h2d(st, dgrad.p, grad, (size_t)C * 4));
+  YS_TRY(ys_colsum_launch(st, dtype, dx.p, ld, coff, rows, rows_per_b, bstride, C, (float*)dpart.p, (float*)dgrad.p));
+  YS_TRY(d2h(st, grad, dgrad.p, (size_t)C * 4));
+  int ok = 1;
+  YS_TRY(check_guard(st, dpart.p, np, &ok));
+  YS_TRY(check_guard(st, dgrad.p, (size_t)C, &ok));
+  YS_CHECK_HIP(hipStreamSynchronize(st));
+  YS_CHECK_HIP(hipGetLastError());
+  if (view_intact) *view_intact = ok;
+  return YS_OK;
+}
+
+// Nearest 2x up-sample of src [B][C][H*W] into dst [B][C][4*H*W] (backward = 0), or its gradient: src [B][C][4*H*W] summed 2 x 2 into dst [B][C][H*W]
+// (backward = 1; with accumulate != 0 dst holds the gradient already in the buffer and receives dst_in + sum, one rounding).  Both operands in padded views.
+extern "C" int ys_upsample2x(ys_ctx* ctx, int dtype, int backward, const float* src, int B, int H, int W, int C, int s_ldc, int s_coff, int d_ldc, int d_coff,
+                             int accumulate, float* dst, int32_t* view_intact) {
+  YS_REQUIRE(ctx && src && dst, "ys_upsample2x: null argument");
+  YS_REQUIRE(dtype == YS_F32 || dtype == YS_BF16, "ys_upsample2x: bad dtype %d", dtype);
+  const int epl = ys_epl(dtype);
+  const size_t es = ys_es(dtype);
+  YS_REQUIRE(B >= 1 && H >= 1 && W >= 1 && C >= epl && C % epl == 0, "ys_upsample2x: B=%d H=%d W=%d C=%d", B, H, W, C);
+  YS_REQUIRE(s_coff >= 0 && d_coff >= 0 && s_ldc >= s_coff + C && d_ldc >= d_coff + C && s_ldc % epl == 0 && s_coff % epl == 0 && d_ldc % epl == 0 && d_coff % epl == 0,
+             "ys_upsample2x: views (ldc %d coff %d), (ldc %d coff %d) must hold C=%d channels on the %d-element vector grid", s_ldc, s_coff, d_ldc, d_coff, C, epl);
+  YS_REQUIRE(!accumulate || backward, "ys_upsample2x: only the backward pass accumulates");
+  YS_CHECK_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  const long small = (long)H * W, big = 4 * small;
+  const long srpb = backward ? big : small, drpb = backward ? small : big;
+  DevBuf ds, dd;
+  YS_TRY(alloc_filled(ds, (size_t)B * srpb * s_ldc * es, st));
+  YS_TRY(alloc_filled(dd, (size_t)B * drpb * d_ldc * es, st));
+  YS_TRY(stage_view(st, dtype, src, B, C, srpb, ds.p, s_ldc, s_coff));
+  if (accumulate) YS_TRY(stage_view(st, dtype, dst, B, C, drpb, dd.p, d_ldc, d_coff));
+  if (backward) YS_TRY(ys_upsample2x_bwd_launch(st, dtype, ds.p, s_ldc, s_coff, B, H, W, C, dd.p, d_ldc, d_coff, accumulate ? 1 : 0));
+  else YS_TRY(ys_upsample2x_fwd_launch(st, dtype, ds.p, s_ldc, s_coff, B, H, W, C, dd.p, d_ldc, d_coff));
+  YS_TRY(fetch_view(st, dtype, dd.p, d_ldc, d_coff, B, C, drpb, dst));
+  int ok = 1;
+  YS_TRY(check_sentinel(st, dd.p, (long)B * drpb, d_ldc, d_coff, C, es, &ok));
+  YS_TRY(check_sentinel(st, ds.p, (long)B * srpb, s_ldc, s_coff, C, es, &ok));
+  YS_CHECK_HIP(hipGetLastError());
+  if (view_intact) *view_intact = ok;
+  return YS_OK;
+}
+
+// dst view (+)= src view (copy_view_kernel): src, dst [C][rows]; with accumulate != 0 dst holds the destination's content on entry
+extern "C" int ys_copy_view(ys_ctx* ctx, int dtype, const float* src, int rows, int C, int s_ldc, int s_coff, int d_ldc, int d_coff, int accumulate, float* dst,
+                            int32_t* view_intact) {
+  YS_REQUIRE(ctx && src && dst, "ys_copy_view: null argument");
+  YS_REQUIRE(dtype == YS_F32 || dtype == YS_BF16, "ys_copy_view: bad dtype %d", dtype);
+  const int epl = ys_epl(dtype);
+  const size_t es = ys_es(dtype);
+  YS_REQUIRE(rows >= 1 && C >= epl && C % epl == 0, "ys_copy_view: rows=%d C=%d", rows, C);
+  YS_REQUIRE(s_coff >= 0 && d_coff >= 0 && s_ldc >= s_coff + C && d_ldc >= d_coff + C && s_ldc % epl == 0 && s_coff % epl == 0 && d_ldc % epl == 0 && d_coff % epl == 0,
+             "ys_copy_view: views (ldc %d coff %d), (ldc %d coff %d) must hold C=%d channels on the %d-element vector grid", s_ldc, s_coff, d_ldc, d_coff, C, epl);
+  YS_CHECK_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  DevBuf ds, dd;
+  YS_TRY(alloc_filled(ds, (size_t)rows * s_ldc * es, st));
+  YS_TRY(alloc_filled(dd, (size_t)rows * d_ldc * es, st));
+  YS_TRY(stage_view(st, dtype, src, 1, C, rows, ds.p, s_ldc, s_coff));
+  if (accumulate) YS_TRY(stage_view(st, dtype, dst, 1, C, rows, dd.p, d_ldc, d_coff));
+  YS_TRY(ys_copy_view_launch(st, dtype, ds.p, s_ldc, s_coff, rows, C, dd.p, d_ldc, d_coff, accumulate ? 1 : 0));
+  YS_TRY(fetch_view(st, dtype, dd.p, d_ldc, d_coff, 1, C, rows, dst));
+  int ok = 1;
+  YS_TRY(check_sentinel(st, dd.p, rows, d_ldc, d_coff, C, es, &ok));
+  YS_TRY(check_sentinel(st, ds.p, rows, s_ldc, s_coff, C, es, &ok));
   YS_CHECK_HIP(hipGetLastError());
   if (view_intact) *view_intact = ok;
   return YS_OK;

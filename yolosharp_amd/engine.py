@@ -388,9 +388,11 @@ class Engine:
                                                      nc, max_nms, max_wh, rows_dev, keep_dev, cnt_dev))
 
     # ---- Convs.Conv.forward (Convs.cs:36-62) / plain Conv2d with bias (Head.cs:47-50)
-    def conv_bn_act(self, x, weight, k, s, bn=None, bias=None, act=True, training=True, dtype="f32"):
+    def conv_bn_act(self, x, weight, k, s, bn=None, bias=None, act=True, training=True, dtype="f32", stat_mode=None, extras=None):
         """x [B,Cin,H,W], weight [Cout,Cin,k,k] float32.  bn = dict(weight, bias, running_mean, running_var)
-        (running stats are updated in place when training).  Returns y [B,Cout,Ho,Wo] float32."""
+        (running stats are updated in place when training).  Returns y [B,Cout,Ho,Wo] float32.
+        stat_mode (ys_conv_bn_act_fwd_ex): 0 = statistics rows + finalize launch, 1 = fixed-point accumulators finalized inside the apply pass (what a model
+        runs); extras: a dict that receives y_raw, coef [4][Cout] and stat_rows of a training-mode BatchNorm call."""
         x = np.ascontiguousarray(x, np.float32)
         w = np.ascontiguousarray(weight, np.float32)
         B, Cin, H, W = x.shape
@@ -406,7 +408,103 @@ class Engine:
             rm, rv = bn["running_mean"], bn["running_var"]
             assert rm.dtype == np.float32 and rv.dtype == np.float32
         bs = np.ascontiguousarray(bias, np.float32) if bias is not None else None
-        _lib.check(self.lib, self.lib.ys_conv_bn_act_fwd(self.ctx, dt, _ptr(x), B, Cin, H, W, _ptr(w), Cout, k, s,
-                                                         _ptr(g), _ptr(b), _ptr(rm), _ptr(rv), _ptr(bs), int(act),
-                                                         int(training), _ptr(y)))
+        if stat_mode is None and extras is None:
+            _lib.check(self.lib, self.lib.ys_conv_bn_act_fwd(self.ctx, dt, _ptr(x), B, Cin, H, W, _ptr(w), Cout, k, s,
+                                                             _ptr(g), _ptr(b), _ptr(rm), _ptr(rv), _ptr(bs), int(act),
+                                                             int(training), _ptr(y)))
+            return y
+        y_raw = coef = None
+        rows = C.c_int32(0)
+        if extras is not None and bn is not None and training:
+            y_raw, coef = np.empty_like(y), np.empty((4, Cout), np.float32)
+        _lib.check(self.lib, self.lib.ys_conv_bn_act_fwd_ex(self.ctx, dt, _ptr(x), B, Cin, H, W, _ptr(w), Cout, k, s,
+                                                            _ptr(g), _ptr(b), _ptr(rm), _ptr(rv), _ptr(bs), int(act),
+                                                            int(training), int(stat_mode or 0), _ptr(y), _ptr(y_raw), _ptr(coef),
+                                                            C.byref(rows) if y_raw is not None else None))
+        if y_raw is not None:
+            extras.update(y_raw=y_raw, coef=coef, stat_rows=rows.value)
         return y
+
+    # ---- BatchNorm training kernels in isolation (ys_bn_train_fwd / ys_bn_train_bwd / ys_colsum / ys_upsample2x / ys_copy_view); arrays channel-major [C][rows]
+    def bn_train_fwd(self, problems, mode, act=True, dtype="f32"):
+        """problems: dicts with y [C][rows], gamma, beta, run_mean, run_var, optional nbt, res, partial [P][2][C] (mode 1), res_pad / res_coff / z_pad / z_coff /
+        res_shares_z.  Returns (status, [dict(z, coef, run_mean, run_var, nbt, part, view_intact)])."""
+        f32 = lambda a: None if a is None else np.array(a, np.float32, order="C")
+        cs, keep = (_lib.BnFwdCase * len(problems))(), []
+        for c, p in zip(cs, problems):
+            y = f32(p["y"])
+            Cn, rows = y.shape
+            k = dict(y=y, gamma=f32(p["gamma"]), beta=f32(p["beta"]), run_mean=f32(p["run_mean"]), run_var=f32(p["run_var"]),
+                     nbt=None if p.get("nbt") is None else np.array([p["nbt"]], np.float32), res=f32(p.get("res")), partial=f32(p.get("partial")),
+                     z=np.full((Cn, rows), np.nan, np.float32), coef=np.full((4, Cn), np.nan, np.float32), part_out=np.full((768, 2, Cn), np.nan, np.float32),
+                     acc_out=np.zeros((8, Cn, 2), np.uint64))
+            keep.append(k)
+            for name, a in k.items():
+                setattr(c, name, _ptr(a))
+            c.rows, c.C = rows, Cn
+            c.res_pad, c.res_coff, c.z_pad, c.z_coff = p.get("res_pad", 0), p.get("res_coff", 0), p.get("z_pad", 0), p.get("z_coff", 0)
+            c.res_shares_z = int(p.get("res_shares_z", 0))
+            c.P = 0 if k["partial"] is None else k["partial"].shape[0]
+            c.nblk, c.view_intact = 0, -1
+        status = self.lib.ys_bn_train_fwd(self.ctx, _dtype_code(dtype), mode, int(act), len(problems), cs)
+        out = [dict(z=k["z"], coef=k["coef"], run_mean=k["run_mean"], run_var=k["run_var"], nbt=None if k["nbt"] is None else float(k["nbt"][0]),
+                    part=k["part_out"][:c.nblk], acc=k["acc_out"], view_intact=c.view_intact) for c, k in zip(cs, keep)]
+        return status, out
+
+    def bn_train_bwd(self, problems, mode, act=True, dtype="f32"):
+        """problems: dicts with dz, y [C][rows], coef [4][C], dgamma, dbeta, optional rg, dz_pad / dz_coff / rg_pad / rg_coff; mode 3: rows, src = [(part [nblk][2][C],
+        c1), ...].  Returns (status, [dict(dy, k23, dgamma, dbeta, rg, part, view_intact)])."""
+        f32 = lambda a: None if a is None else np.array(a, np.float32, order="C")
+        cs, keep = (_lib.BnBwdCase * len(problems))(), []
+        for c, p in zip(cs, problems):
+            coef = f32(p["coef"])
+            Cn = coef.shape[1]
+            rows = p["rows"] if "rows" in p else np.shape(p["dz"])[1]
+            k = dict(dz=f32(p.get("dz")), y=f32(p.get("y")), coef=coef, dgamma=f32(p["dgamma"]), dbeta=f32(p["dbeta"]), rg=f32(p.get("rg")),
+                     dy=np.full((Cn, rows), np.nan, np.float32), k23=np.full((2, Cn), np.nan, np.float32), part_out=np.full((768, 2, Cn), np.nan, np.float32))
+            for name, a in k.items():
+                setattr(c, name, _ptr(a))
+            src = [(f32(s_), int(c1)) for s_, c1 in p.get("src", [])]
+            k["src"] = src
+            keep.append(k)
+            c.nsrc = len(src)
+            for i, (s_, c1) in enumerate(src):
+                c.src_part[i], c.src_nblk[i], c.src_c1[i] = s_.ctypes.data, s_.shape[0], c1
+            c.rows, c.C = rows, Cn
+            c.dz_pad, c.dz_coff, c.rg_pad, c.rg_coff = p.get("dz_pad", 0), p.get("dz_coff", 0), p.get("rg_pad", 0), p.get("rg_coff", 0)
+            c.nblk, c.view_intact = 0, -1
+        status = self.lib.ys_bn_train_bwd(self.ctx, _dtype_code(dtype), mode, int(act), len(problems), cs)
+        out = [dict(dy=k["dy"], k23=k["k23"], dgamma=k["dgamma"], dbeta=k["dbeta"], rg=k["rg"], part=k["part_out"][:c.nblk], view_intact=c.view_intact)
+               for c, k in zip(cs, keep)]
+        return status, out
+
+    def colsum(self, x, grad, bstride=None, ld_pad=0, coff=0, dtype="f32"):
+        """grad [C] + column sums of x [B][C][rows_per_b] -> (status, grad, view_intact)."""
+        x = np.ascontiguousarray(x, np.float32)
+        g = np.array(grad, np.float32)
+        B, Cn, rpb = x.shape
+        ok = C.c_int32(-1)
+        status = self.lib.ys_colsum(self.ctx, _dtype_code(dtype), _ptr(x), B, Cn, rpb, rpb if bstride is None else bstride, ld_pad, coff, _ptr(g), C.byref(ok))
+        return status, g, ok.value
+
+    def upsample2x(self, src, H, W, backward=False, views=(None, 0, None, 0), dst=None, dtype="f32"):
+        """src [B][C][H*W] -> [B][C][4*H*W], or backward src [B][C][4*H*W] -> [B][C][H*W] (dst given: accumulate into it) -> (status, dst, view_intact)."""
+        src = np.ascontiguousarray(src, np.float32)
+        B, Cn = src.shape[:2]
+        out = np.array(dst, np.float32) if dst is not None else np.full((B, Cn, H * W if backward else 4 * H * W), np.nan, np.float32)
+        sl, so, dl, do = views
+        ok = C.c_int32(-1)
+        status = self.lib.ys_upsample2x(self.ctx, _dtype_code(dtype), int(backward), _ptr(src), B, H, W, Cn, Cn + so if sl is None else sl, so,
+                                        Cn + do if dl is None else dl, do, int(dst is not None), _ptr(out), C.byref(ok))
+        return status, out, ok.value
+
+    def copy_view(self, src, views=(None, 0, None, 0), dst=None, dtype="f32"):
+        """dst view (+)= src view, src [C][rows] -> (status, dst, view_intact); dst given: accumulate into it."""
+        src = np.ascontiguousarray(src, np.float32)
+        Cn, rows = src.shape
+        out = np.array(dst, np.float32) if dst is not None else np.full((Cn, rows), np.nan, np.float32)
+        sl, so, dl, do = views
+        ok = C.c_int32(-1)
+        status = self.lib.ys_copy_view(self.ctx, _dtype_code(dtype), _ptr(src), rows, Cn, Cn + so if sl is None else sl, so, Cn + do if dl is None else dl, do,
+                                       int(dst is not None), _ptr(out), C.byref(ok))
+        return status, out, ok.value
