@@ -94,7 +94,7 @@ namespace YoloSharp.Native
                                                                  int outW, int outH, int color, [Out] byte[] dst, out int padL, out int padU);
         // Training input on the device (Data/YoloDataset.cs:57-151: Mosaic4 + RandomPerspective + FlipLR / FlipUD + Normalize + mul(1/255) + collate): the sources live in
         // one uint8 arena, an item carries what the reference draws per output image.  Device-resident callers pass IntPtr (on_device = 1) for every pointer.
-        // Quirk kept: a flipped box keeps x1 > x2 (negative w after cxcywh) unless flags has YS_AUG_SORT_FLIPPED (1).  Not built: RandomHSV, OBB corners, the no-mosaic branch.
+        // Quirk kept: a flipped box keeps x1 > x2 (negative w after cxcywh) unless flags has YS_AUG_SORT_FLIPPED (1).  Not built: RandomHSV, OBB corners, the `rand > p` case of Mosaic.
         [StructLayout(LayoutKind.Sequential)] internal struct YsAugSrc { public long imgOff, maskOff; public int h, w, mh, mw; }
         [StructLayout(LayoutKind.Sequential)] internal struct YsAugItem { public int src0, src1, src2, src3, xc, yc; public float m00, m01, m02, m10, m11, m12, m20, m21, m22; public int flipLr, flipUd; }
         [DllImport(Lib)] internal static extern int ys_augment_mosaic(IntPtr ctx, IntPtr arena, IntPtr srcs, int nSrc, IntPtr items, int batch, int onDevice, int imgsz,
@@ -102,6 +102,15 @@ namespace YoloSharp.Native
         [DllImport(Lib)] internal static extern int ys_augment_labels(IntPtr ctx, IntPtr srcs, IntPtr labOff, IntPtr cls, IntPtr boxes, IntPtr keypoints, int kptNum, int kptDim,
                                                                       IntPtr items, int batch, int onDevice, int imgsz, int perspective, int flags, int capacity,
                                                                       IntPtr outBatchIdx, IntPtr outCls, IntPtr outBboxes, IntPtr outKeypoints, IntPtr outCount);
+        // The LetterBox pipeline of CloseMosaic(true) / ImageProcessType.Letterbox (Data/YoloDataset.cs:378-429: LetterBox + FlipLR / FlipUD + Normalize + mul(1/255) + collate) on
+        // the same arena, tables and items: only src0, flipLr and flipUd of an item are read.  Quirk kept: a flipped cxcywh box's width becomes s - w (Augment.cs:888-892)
+        // unless flags has YS_AUG_FLIP_KEEP_SIZE (2).
+        internal const int YS_AUG_SORT_FLIPPED = 1, YS_AUG_FLIP_KEEP_SIZE = 2;
+        [DllImport(Lib)] internal static extern int ys_augment_letterbox(IntPtr ctx, IntPtr arena, IntPtr srcs, int nSrc, IntPtr items, int batch, int onDevice, int imgsz,
+                                                                         int maskRatio, IntPtr images, IntPtr masks);
+        [DllImport(Lib)] internal static extern int ys_augment_letterbox_labels(IntPtr ctx, IntPtr srcs, int nSrc, IntPtr labOff, IntPtr cls, IntPtr boxes, IntPtr keypoints,
+                                                                                int kptNum, int kptDim, IntPtr items, int batch, int onDevice, int imgsz, int flags, int capacity,
+                                                                                IntPtr outBatchIdx, IntPtr outCls, IntPtr outBboxes, IntPtr outKeypoints, IntPtr outCount);
         // Classify task (Head.Classify / v8ClassificationLoss / Classifier.Val, Models/Classifier.cs): outputs "cls" / "logits" / "dcls" [B,nc]
         // through ys_model_get_output; one loss item (the mean) through ys_loss_read_items
         [DllImport(Lib)] internal static extern int ys_loss_classify(IntPtr model, float[] cls, int batch, int onDevice);

@@ -481,8 +481,9 @@ YS_API int ys_letterbox(ys_ctx* ctx, const void* src, int is_float, int on_devic
  * host: an item that fails those checks yields an all-114 image (zero masks) and no labels; if more rows are kept than `capacity`, *out_count holds
  * the true total (> capacity) and the rows past capacity are not written.  Nothing is truncated silently.
  * Scope: kpt_dim must be 3 (apply_keypoints reads column 2; 2 -> YS_ERR_INVALID_ARG).  Not built: OBB corner labels (xyxyxyxy2xywhr is host code in
- * the reference), RandomHSV (TorchVision.NET ColorJitter, not part of the reference tree), the no-mosaic branch (rand > p: the reference then yields
- * images of unequal sizes its own collate cannot stack).  Deviations: a label-free sample is still warped (RandomPerspective.Apply returns the
+ * the reference), RandomHSV (TorchVision.NET ColorJitter, not part of the reference tree), the `rand > p` case of Augment.Mosaic (the reference then
+ * yields images of unequal sizes its own collate cannot stack).  The other no-mosaic case -- the LetterBox pipeline the reference trains on once the
+ * mosaic is closed -- is ys_augment_letterbox / ys_augment_letterbox_labels below.  Deviations: a label-free sample is still warped (RandomPerspective.Apply returns the
  * unwarped 2s x 2s canvas, :666-669); where the reference's mask slice would run past the source mask (it throws) the kernel reads 0. */
 typedef struct ys_aug_src { int64_t img_off, mask_off; int32_t h, w, mh, mw; } ys_aug_src;
 typedef struct ys_aug_item { int32_t src[4]; int32_t xc, yc; float M[9]; int32_t flip_lr, flip_ud; } ys_aug_item;
@@ -493,6 +494,40 @@ YS_API int ys_augment_labels(ys_ctx* ctx, const ys_aug_src* srcs, const int32_t*
                              const float* keypoints, int kpt_num, int kpt_dim, const ys_aug_item* items, int batch, int on_device,
                              int imgsz, int perspective, int flags, int capacity, float* out_batch_idx, float* out_cls, float* out_bboxes,
                              float* out_keypoints, int32_t* out_count);
+
+/* ---- the LetterBox (close-mosaic) training input: what YoloDataset.CloseMosaic(true) builds (Data/YoloDataset.cs:378-429; the training loop calls it
+ * with `epoch > Config.CloseMosaic`, Models/YoloBaseTaskModel.cs:180, so with the default 0 every epoch trains on it) and what ImageProcessType.Letterbox
+ * is (:70-74): LetterBox(imgsz, imgsz, mask_ratio) (Data/Augment.cs:698-778) + FlipLR + FlipUD (:860-966) + Normalize + mul(1/255) + collate.
+ * Same arena, ys_aug_src and label tables and the same ys_aug_item table as the Mosaic entries: both calls read only src[0], flip_lr and flip_ud of an
+ * item and ignore the rest, so one item table serves both branches.
+ *
+ * ys_augment_letterbox: images fp32 [batch, 3, imgsz, imgsz]; masks (may be NULL) fp32 [batch, imgsz / mask_ratio, imgsz / mask_ratio] whole ids.
+ * LetterboxImage (:756-777) in the reference's fp32 arithmetic: ratio = min(s / (float)w, s / (float)h), new_w = (int)(w * ratio), new_h likewise,
+ * pad_l = (s - new_w) / 2, pad_u = (s - new_h) / 2; the resize is ys_letterbox's nearest rule src = min(floor(dst * (float)in / out), in - 1); 114
+ * outside the window; the flips folded into the output coordinate; a byte b becomes (float)b * (1 / 255.0f).  The mask is letterboxed from ITS OWN
+ * size [mh, mw] onto (imgsz / mask_ratio)^2 with fill 0 (:725) -- its pads are not the image's pads / mask_ratio, so mask and image can sit a fraction
+ * of a cell apart (kept); a source without a mask gives a zero mask.  Nothing is blended: the output is bit-exact.
+ *
+ * ys_augment_letterbox_labels: EVERY label of src[0], in order (this branch has no thresholds), in the compacted layout of ys_augment_labels (tail
+ * rows batch_idx -1 and zeros, *out_count = the total).  The reference carries cxcywh through this branch (bbox_format = cxcywh, YoloDataset.cs:303);
+ * the tables hold pixel xyxy, converted here with cx = (x1 + x2) / 2, w = x2 - x1 (torchvision box_convert): a DEVIATION of a few fp32 roundings.
+ * Then, as written in the reference: boxes + (pad_l, pad_u, 0, 0) (:735-738), keypoints + (pad_l, pad_u) (:741-744), NEITHER scaled by ratio (kept;
+ * exact whenever ratio == 1, i.e. when the loader has resized the long side to imgsz), the flips, mul(1f / imgsz) (Struct.cs:106-115).
+ * QUIRK kept by default: FlipLR / FlipUD test bbox_format != xywh, which is true for cxcywh, and rewrite columns 0 AND 2 (1 AND 3) as s - value
+ * (:888-892, :943-947): a flipped box's width (height) becomes s - w.  flags & YS_AUG_FLIP_KEEP_SIZE leaves columns 2 / 3 alone.
+ * YS_AUG_SORT_FLIPPED is ignored here; ys_augment_labels takes YS_AUG_SORT_FLIPPED only.  Keypoints: x <- s - x / y <- s - y without a left / right
+ * index swap (the reference has none); visibility untouched.  kpt_dim must be 3.
+ *
+ * Host pointers (on_device = 0): YS_ERR_INVALID_ARG for a src[0] outside [0, n_src) or without an image, imgsz odd or < 2, and a capacity below the
+ * batch's label total.  Device pointers: an item that fails those checks yields an all-114 image, a zero mask and no rows; a total above `capacity` is
+ * reported in *out_count and the rows past capacity are not written. */
+#define YS_AUG_FLIP_KEEP_SIZE 2
+YS_API int ys_augment_letterbox(ys_ctx* ctx, const uint8_t* arena, const ys_aug_src* srcs, int n_src, const ys_aug_item* items, int batch,
+                                int on_device, int imgsz, int mask_ratio, float* images, float* masks);
+YS_API int ys_augment_letterbox_labels(ys_ctx* ctx, const ys_aug_src* srcs, int n_src, const int32_t* lab_off, const float* cls, const float* boxes,
+                                       const float* keypoints, int kpt_num, int kpt_dim, const ys_aug_item* items, int batch, int on_device,
+                                       int imgsz, int flags, int capacity, float* out_batch_idx, float* out_cls, float* out_bboxes,
+                                       float* out_keypoints, int32_t* out_count);
 
 /* ---- per-operator entry points (unit parity; a TorchSharp-free C# Conv wrapper) ---------------
  * Convs.Conv.forward (Convs.cs:36-62): y = act(BN(conv2d(x))) on fp32 NCHW / OIHW HOST arrays at the

@@ -11,6 +11,12 @@ Four measurements, each in a child process of its own under its own time limit (
   step_static      the YOLOv8n bf16 train step (forward, criterion, backward, AdamW, zero_grad) on one fixed device batch
   step_augmented   the same step fed by MosaicAugmenter.batch() -- host draws, item upload, both kernels -- every iteration
 Every figure is the median over --repeats timed blocks of --steps calls after --warmup calls, with a synchronise inside the window.
+
+--branch letterbox measures the close-mosaic branch (ys_augment_letterbox / ys_augment_letterbox_labels, MosaicAugmenter.close_mosaic(True)) on the same
+dataset instead; the default, mosaic, is the above unchanged.  Its legs: augment = the kernel pair (and the image call alone) -- the fp32 batch written
+plus the sources' bytes read once, over that time; torch_augment = a torch restatement of LetterBox + flips + stack + mul(1/255) (Data/Augment.cs:698-778,
+860-966) for the images; step_static / step_augmented as above with letterbox batches; and step_host = the same step through AMPWrapper.TrainStep on the
+batch's host copy (images and labels copied to the device every step): what a trainer without this branch does once the mosaic is closed.
 """
 import argparse
 import json
@@ -26,6 +32,7 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 LEGS = ("augment", "torch_augment", "step_static", "step_augmented")
+LETTERBOX_LEGS = LEGS + ("step_host",)
 HBM_TBPS = 6.3
 HYP = dict(degrees=10.0, translate=0.1, scale=0.5, shear=2.0, perspective=0.0)
 
@@ -98,6 +105,66 @@ def leg_augment(a):
             "bound": "HBM (streaming fp32 write + gather)", "labels_kept": kept, "B": B, "imgsz": S, "sources": a.sources}
 
 
+def leg_letterbox(a):
+    from yolosharp_amd import Engine, _lib
+    eng = Engine(0)
+    aug, imgs = _augmenter(eng, a)
+    aug.close_mosaic(True)
+    B, S = a.batch, a.imgsz
+    items = aug.draw(np.arange(B) % aug.count)
+    aug.run(items)                                                    # uploads the item table; the timed calls below reuse it on the device
+    lib = eng.lib
+
+    def images():
+        _lib.check(lib, lib.ys_augment_letterbox(eng.ctx, aug.d_arena, aug.d_srcs, aug.count, aug.d_items, B, 1, S, aug.r, aug.d_images, None))
+
+    def both():
+        images()
+        _lib.check(lib, lib.ys_augment_letterbox_labels(eng.ctx, aug.d_srcs, aug.count, aug.d_lab_off, aug.d_cls, aug.d_boxes, None, 0, 3, aug.d_items, B, 1, S, 0,
+                                                        aug.capacity, aug.d_bidx, aug.d_ocls, aug.d_obox, None, aug.d_cnt))
+
+    ms, runs = _timed(both, eng.synchronize, a)
+    ms_img, runs_img = _timed(images, eng.synchronize, a)
+    written = B * 3 * S * S * 4
+    read = sum(int(imgs[k].size) for k in items["src"][:, 0])
+    kept = int(eng.from_device(aug.d_cnt, (1,), np.int32)[0])
+    aug.close()
+    return {"ms_per_batch": round(ms, 4), "runs": runs, "images_only_ms": round(ms_img, 4), "images_only_runs": runs_img, "bytes_written": written,
+            "bytes_read_at_most": read, "hbm_share_of_%.1f_TBps" % HBM_TBPS: round((written + read) / (ms_img * 1e-3) / (HBM_TBPS * 1e12), 4),
+            "labels": kept, "B": B, "imgsz": S, "sources": a.sources}
+
+
+def leg_torch_letterbox(a):
+    import torch
+    import torch.nn.functional as F
+    from yolosharp_amd.augment import draw_letterbox_items
+    imgs, _ = _dataset(a)
+    B, S = a.batch, a.imgsz
+    items = draw_letterbox_items(np.random.default_rng(1), np.arange(B) % len(imgs), 0.5, 0.0)
+    dimgs = [torch.from_numpy(im).cuda() for im in imgs]
+
+    def one(it):
+        img = dimgs[int(it["src"][0])]
+        h, w = img.shape[1:]
+        ratio = min(np.float32(S) / np.float32(w), np.float32(S) / np.float32(h))
+        new_w, new_h = int(np.float32(w) * ratio), int(np.float32(h) * ratio)
+        if (new_h, new_w) != (h, w):                                  # torchvision's resize returns the image itself at its own size
+            img = F.interpolate(img[None].to(torch.float32), size=(new_h, new_w), mode="nearest")[0].to(torch.uint8)
+        pl, pu = (S - new_w) // 2, (S - new_h) // 2
+        out = F.pad(img, (pl, S - new_w - pl, pu, S - new_h - pu), value=114)
+        if it["flip_lr"]:
+            out = out.flip(-1)
+        if it["flip_ud"]:
+            out = out.flip(-2)
+        return out[None].mul(1 / 255.0)
+
+    def call():
+        return torch.cat([one(it) for it in items], 0)
+
+    ms, runs = _timed(call, torch.cuda.synchronize, a)
+    return {"ms_per_batch": round(ms, 4), "runs": runs, "what": "images only (resize + pad per image, flips, stack, mul 1/255)"}
+
+
 def leg_torch_augment(a):
     import torch
     import torch.nn.functional as F
@@ -141,12 +208,13 @@ def leg_torch_augment(a):
     return {"ms_per_batch": round(ms, 4), "runs": runs, "what": "images only (canvas paste + grid_sample per image, flips, stack, mul 1/255)"}
 
 
-def leg_step(a, augmented):
+def leg_step(a, augmented, host=False):
     from yolosharp_amd import Engine
     from yolosharp_amd.model import AMPWrapper, Yolov8, v8DetectionLoss
     eng = Engine(0)
     B, S = a.batch, a.imgsz
     aug, _ = _augmenter(eng, a)
+    aug.close_mosaic(a.branch == "letterbox")
     m = Yolov8(eng, nc=a.nc, size="n", height=S, width=S, max_batch=B, dtype="bf16")
     m.init_weights(1)
     m.reserve_labels(aug.max_per_image)
@@ -154,8 +222,13 @@ def leg_step(a, augmented):
     m.train()
     db = aug.batch(np.arange(B) % aug.count)
     state = {"i": 0}
+    hb = db.to_host() if host else None
 
     def step():
+        if host:                                                      # images and labels travel to the device every step (TrainStep without its loss read)
+            m.forward(hb["images"], fetch=False)
+            crit.forward(None, hb, read=False)
+            return amp.Step()
         d = db
         if augmented:
             state["i"] += 1
@@ -184,17 +257,21 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--leg-timeout", type=int, default=240, help="seconds per child process")
-    ap.add_argument("--leg", choices=LEGS, help="run one measurement in this process (what the driver starts)")
+    ap.add_argument("--branch", choices=("mosaic", "letterbox"), default="mosaic", help="the pipeline to measure (letterbox = the close-mosaic branch)")
+    ap.add_argument("--leg", choices=LETTERBOX_LEGS, help="run one measurement in this process (what the driver starts)")
     a = ap.parse_args()
+    lb = a.branch == "letterbox"
     if a.leg:
-        out = {"augment": lambda: leg_augment(a), "torch_augment": lambda: leg_torch_augment(a), "step_static": lambda: leg_step(a, False),
-               "step_augmented": lambda: leg_step(a, True)}[a.leg]()
+        out = {"augment": lambda: leg_letterbox(a) if lb else leg_augment(a), "torch_augment": lambda: leg_torch_letterbox(a) if lb else leg_torch_augment(a),
+               "step_static": lambda: leg_step(a, False), "step_augmented": lambda: leg_step(a, True), "step_host": lambda: leg_step(a, False, host=True)}[a.leg]()
         print(json.dumps(out))
         return 0
     res = {"metric": "augment_cost", "model": "yolov8n", "dtype": "bf16", "batch": a.batch, "imgsz": a.imgsz, "sources": a.sources}
+    if lb:
+        res["branch"] = "letterbox"
     fwd = [x for kv in (("--batch", a.batch), ("--imgsz", a.imgsz), ("--sources", a.sources), ("--nc", a.nc), ("--steps", a.steps), ("--warmup", a.warmup),
-                        ("--repeats", a.repeats)) for x in (kv[0], str(kv[1]))]
-    for leg in LEGS:
+                        ("--repeats", a.repeats), ("--branch", a.branch)) for x in (kv[0], str(kv[1]))]
+    for leg in (LETTERBOX_LEGS if lb else LEGS):
         try:
             r = subprocess.run([sys.executable, os.path.abspath(__file__), "--leg", leg] + fwd, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
                                text=True, timeout=a.leg_timeout, stdin=subprocess.DEVNULL)
@@ -210,6 +287,8 @@ def main():
     if "step_static" in res and "step_augmented" in res:
         res["augment_extra_ms_per_step"] = round(res["step_augmented"]["ms_per_step"] - res["step_static"]["ms_per_step"], 4)
         res["augment_extra_share_of_step"] = round(res["augment_extra_ms_per_step"] / res["step_static"]["ms_per_step"], 4)
+    if "step_static" in res and "step_host" in res:
+        res["host_batch_extra_ms_per_step"] = round(res["step_host"]["ms_per_step"] - res["step_static"]["ms_per_step"], 4)
     print(json.dumps(res))
     return 1 if "failed" in res else 0
 

@@ -3,7 +3,13 @@ device (csrc/augment.hip; include/yolosharp_hip.h ys_augment_mosaic / ys_augment
 image it draws what Augment.Mosaic (Data/Augment.cs:153-164), RandomPerspective.affine_transform (:323-356) and FlipLR / FlipUD (:869, :926)
 draw, and uploads one 68-byte item.  TorchSharp's torch.rand streams cannot be reproduced: the drawn PARAMETERS are the interface.
 
-Not built: RandomHSV (TorchVision.NET ColorJitter), OBB corner labels, the no-mosaic branch (rand > p).  kpt_dim = 3 only."""
+The close-mosaic branch -- what YoloDataset.CloseMosaic(true) builds (Data/YoloDataset.cs:378-429; the training loop calls it with
+`epoch > Config.CloseMosaic`, Models/YoloBaseTaskModel.cs:180) and what ImageProcessType.Letterbox is: LetterBox + FlipLR / FlipUD -- runs on the
+same uploaded arena, tables and buffers (ys_augment_letterbox / ys_augment_letterbox_labels; MosaicAugmenter.close_mosaic).  Its items carry the
+primary index and the two flip decisions only.
+
+Not built: RandomHSV (TorchVision.NET ColorJitter), OBB corner labels, the `rand > p` case of Augment.Mosaic (it yields images of unequal sizes).
+kpt_dim = 3 only."""
 import ctypes as C
 import math
 
@@ -14,7 +20,8 @@ from . import _lib
 SRC_DTYPE = np.dtype([("img_off", "<i8"), ("mask_off", "<i8"), ("h", "<i4"), ("w", "<i4"), ("mh", "<i4"), ("mw", "<i4")])
 ITEM_DTYPE = np.dtype([("src", "<i4", (4,)), ("xc", "<i4"), ("yc", "<i4"), ("M", "<f4", (9,)), ("flip_lr", "<i4"), ("flip_ud", "<i4")])
 assert SRC_DTYPE.itemsize == C.sizeof(_lib.AugSrc) == 32 and ITEM_DTYPE.itemsize == C.sizeof(_lib.AugItem) == 68
-YS_AUG_SORT_FLIPPED = 1
+YS_AUG_SORT_FLIPPED = 1              # ys_augment_labels: write a flipped box as (min, max)
+YS_AUG_FLIP_KEEP_SIZE = 2            # ys_augment_letterbox_labels: a flip leaves the cxcywh box's w / h alone (the reference writes s - w)
 
 
 def _ptr(a):
@@ -136,6 +143,50 @@ def augment_labels(engine, srcs, lab_off, cls, boxes, keypoints, items, imgsz, p
     return out
 
 
+def augment_letterbox(engine, arena, srcs, items, imgsz, mask_ratio=4, with_masks=False):
+    """ys_augment_letterbox on HOST arrays: -> (images fp32 [B, 3, s, s], masks fp32 [B, s/r, s/r] or None).  Reads src[0] and the flips of an item."""
+    arena = np.ascontiguousarray(arena, np.uint8)
+    srcs, items = np.ascontiguousarray(srcs, SRC_DTYPE), np.ascontiguousarray(items, ITEM_DTYPE)
+    B, s = items.shape[0], int(imgsz)
+    images = np.empty((B, 3, max(s, 0), max(s, 0)), np.float32)
+    masks = np.empty((B, s // mask_ratio, s // mask_ratio), np.float32) if with_masks else None
+    _lib.check(engine.lib, engine.lib.ys_augment_letterbox(engine.ctx, _ptr(arena), _ptr(srcs), srcs.shape[0], _ptr(items), B, 0, s, int(mask_ratio),
+                                                           _ptr(images), _ptr(masks)))
+    return images, masks
+
+
+def augment_letterbox_labels(engine, srcs, lab_off, cls, boxes, keypoints, items, imgsz, flags=0, capacity=None, kpt_dim=3):
+    """ys_augment_letterbox_labels on HOST arrays: -> dict(batch_idx, cls, bboxes, keypoints (or None), count), all `capacity` rows long."""
+    srcs, items = np.ascontiguousarray(srcs, SRC_DTYPE), np.ascontiguousarray(items, ITEM_DTYPE)
+    lab_off = np.ascontiguousarray(lab_off, np.int32)
+    assert lab_off.shape[0] == srcs.shape[0] + 1, (lab_off.shape, srcs.shape)
+    cls, boxes = np.ascontiguousarray(cls, np.float32), np.ascontiguousarray(boxes, np.float32)
+    kp = np.ascontiguousarray(keypoints, np.float32) if keypoints is not None else None
+    K = kp.shape[1] if kp is not None else 0
+    cap = int(capacity if capacity is not None else max(1, int(lab_off[-1])))
+    n = max(cap, 0)
+    out = dict(batch_idx=np.empty((n,), np.float32), cls=np.empty((n,), np.float32), bboxes=np.empty((n, 4), np.float32),
+               keypoints=np.empty((n, K, 3), np.float32) if kp is not None else None)
+    cnt = C.c_int32(-1)
+    _lib.check(engine.lib, engine.lib.ys_augment_letterbox_labels(engine.ctx, _ptr(srcs), srcs.shape[0], _ptr(lab_off), _ptr(cls), _ptr(boxes), _ptr(kp), K,
+                                                                  int(kpt_dim), _ptr(items), items.shape[0], 0, int(imgsz), int(flags), cap,
+                                                                  _ptr(out["batch_idx"]), _ptr(out["cls"]), _ptr(out["bboxes"]), _ptr(out["keypoints"]),
+                                                                  C.byref(cnt)))
+    out["count"] = cnt.value
+    return out
+
+
+def draw_letterbox_items(rng, indices, fliplr=0.5, flipud=0.0):
+    """The item table of one close-mosaic batch: per primary index only what FlipLR, then FlipUD draw (`rand > p -> skip`, each drawn only when its
+    p > 0: YoloDataset.cs:406-415); LetterBox draws nothing.  The other fields stay zero (src[1..3] = 0: valid, unread)."""
+    items = make_items(len(indices))
+    for b, idx in enumerate(indices):
+        flr = fliplr > 0 and not (rng.random() > fliplr)
+        fud = flipud > 0 and not (rng.random() > flipud)
+        items[b]["src"][0], items[b]["flip_lr"], items[b]["flip_ud"] = int(idx), int(flr), int(fud)
+    return items
+
+
 def draw_items(rng, indices, s, count, hyp, fliplr=0.5, flipud=0.0):
     """The item table of one batch: per primary index of `indices`, in the reference's per-image order, the three mixed indices as
     randint(0, count - 1) (:155), yc, then xc, in [s/2, 3s/2) (:163-164), the eight uniforms of the matrix, FlipLR then FlipUD as `rand > p -> skip`
@@ -157,10 +208,12 @@ def draw_items(rng, indices, s, count, hyp, fliplr=0.5, flipud=0.0):
 class DeviceBatch:
     """One collated training batch that lives in HBM: device pointers to images fp32 [B, 3, s, s], batch_idx / cls [capacity], bboxes [capacity, 4],
     masks [B, s/r, s/r] and keypoints [capacity, K, 3] (None when absent) and the device int `count`.  Rows [count, capacity) carry batch_idx -1,
-    which the criteria skip: n_labels = capacity, no host read.  n_input = the labels of the batch's tiles BEFORE the filters (a host number)."""
+    which the criteria skip: n_labels = capacity, no host read.  n_input = the labels of the batch's tiles BEFORE the filters (a host number; in the
+    LetterBox branch, which filters nothing, the batch's exact label count).  mode = the branch that produced it: "mosaic" or "letterbox"."""
 
     def __init__(self, engine, batch, imgsz, capacity, images, batch_idx, cls, bboxes, count, masks=None, keypoints=None, kpt_num=0, mask_ratio=4,
-                 n_input=0, max_per_image=64):
+                 n_input=0, max_per_image=64, mode="mosaic"):
+        self.mode = mode
         self.engine, self.batch, self.imgsz, self.capacity = engine, batch, imgsz, capacity
         self.images, self.batch_idx, self.cls, self.bboxes, self.count = images, batch_idx, cls, bboxes, count
         self.masks, self.keypoints, self.kpt_num, self.mask_ratio, self.n_input = masks, keypoints, kpt_num, mask_ratio, n_input
@@ -187,7 +240,11 @@ class MosaicAugmenter:
     id masks [mh, mw], per-image labels {cls, bboxes pixel xyxy, keypoints [n, K, 3]} -- is uploaded ONCE; a batch uploads its item table only.
     Draws per output image, in the reference's order, from one numpy Generator: the three mixed indices as randint(0, Count - 1) (:155: the upper bound is
     exclusive, so the LAST image is never mixed in -- kept); yc, then xc, in [s/2, 3s/2) (:163-164); the matrix (random_perspective_matrix); FlipLR then
-    FlipUD as `rand > p -> skip`, drawn only when p > 0 (YoloDataset.cs:76-85).  The output buffers are reused by the next batch."""
+    FlipUD as `rand > p -> skip`, drawn only when p > 0 (YoloDataset.cs:76-85).  The output buffers are reused by the next batch.
+    close_mosaic(True) switches to the reference's closed pipeline (YoloDataset.CloseMosaic): LetterBox + FlipLR / FlipUD of the primary image alone, on the
+    same buffers; per image it draws the two flip uniforms only.  `mode` names the branch the next batch comes from.  Of `flags`, the Mosaic branch takes
+    YS_AUG_SORT_FLIPPED and the LetterBox branch YS_AUG_FLIP_KEEP_SIZE; each ignores the other's (ys_augment_labels refuses flags it does not know, so
+    the LetterBox flag is not handed to it)."""
 
     def __init__(self, engine, images_u8, labels, imgsz, masks=None, mask_ratio=4, degrees=0.0, translate=0.1, scale=0.5, shear=0.0, perspective=0.0,
                  fliplr=0.5, flipud=0.0, seed=0, flags=0, max_batch=64):
@@ -196,6 +253,7 @@ class MosaicAugmenter:
         self.hyp = dict(degrees=degrees, translate=translate, scale=scale, shear=shear, perspective=perspective)
         self.fliplr, self.flipud = float(fliplr), float(flipud)
         self.rng = np.random.default_rng(seed)
+        self.mode = "mosaic"
         arena, self.srcs = pack_sources(images_u8, masks)
         self.lab_off, cls, boxes, kp = pack_labels(labels)
         self.count = len(images_u8)
@@ -224,22 +282,43 @@ class MosaicAugmenter:
         self._static = []
         self.d_kp = self.d_items = self.d_images = self.d_masks = self.d_bidx = self.d_ocls = self.d_obox = self.d_cnt = self.d_okp = None
 
+    def close_mosaic(self, closed):
+        """YoloDataset.CloseMosaic(closed): True = the LetterBox pipeline from the next batch on, False = back to Mosaic + RandomPerspective."""
+        self.mode = "letterbox" if closed else "mosaic"
+
     def draw(self, indices):
         """The item table for the primary dataset indices `indices` (what the data loader's shuffler hands to GetTensor)."""
+        if self.mode == "letterbox":
+            return draw_letterbox_items(self.rng, indices, self.fliplr, self.flipud)
         return draw_items(self.rng, indices, self.s, self.count, self.hyp, self.fliplr, self.flipud)
 
+    def _run_letterbox(self, items):
+        e, lib, B = self.engine, self.engine.lib, int(items.shape[0])
+        if items["src"][:, 0].min() < 0 or items["src"][:, 0].max() >= self.count:
+            raise ValueError("item source index outside [0, %d)" % self.count)
+        _lib.check(lib, lib.ys_memcpy_h2d(e.ctx, self.d_items, _ptr(items), items.nbytes))
+        _lib.check(lib, lib.ys_augment_letterbox(e.ctx, self.d_arena, self.d_srcs, self.count, self.d_items, B, 1, self.s, self.r, self.d_images, self.d_masks))
+        _lib.check(lib, lib.ys_augment_letterbox_labels(e.ctx, self.d_srcs, self.count, self.d_lab_off, self.d_cls, self.d_boxes, self.d_kp, self.K, 3, self.d_items,
+                                                        B, 1, self.s, self.flags, self.capacity, self.d_bidx, self.d_ocls, self.d_obox,
+                                                        self.d_okp, self.d_cnt))
+        n_input = int(sum(int(self.lab_off[k + 1] - self.lab_off[k]) for k in items["src"][:, 0]))      # nothing is filtered: the exact label count
+        return DeviceBatch(e, B, self.s, self.capacity, self.d_images, self.d_bidx, self.d_ocls, self.d_obox, self.d_cnt, masks=self.d_masks,
+                           keypoints=self.d_okp, kpt_num=self.K, mask_ratio=self.r, n_input=n_input, max_per_image=self.max_per_image, mode="letterbox")
+
     def run(self, items):
-        """Upload `items` and launch both kernels on the engine's stream (asynchronous) -> DeviceBatch."""
+        """Upload `items` and launch the kernels of the current branch (`mode`) on the engine's stream (asynchronous) -> DeviceBatch."""
         e, lib, B = self.engine, self.engine.lib, int(items.shape[0])
         assert 0 < B <= self.max_batch
         items = np.ascontiguousarray(items, ITEM_DTYPE)
+        if self.mode == "letterbox":
+            return self._run_letterbox(items)
         if items["src"].min() < 0 or items["src"].max() >= self.count:      # ys_augment_labels has no source count to check device items against
             raise ValueError("item source index outside [0, %d)" % self.count)
         persp = int(self.hyp["perspective"] > 0)
         _lib.check(lib, lib.ys_memcpy_h2d(e.ctx, self.d_items, _ptr(items), items.nbytes))
         _lib.check(lib, lib.ys_augment_mosaic(e.ctx, self.d_arena, self.d_srcs, self.count, self.d_items, B, 1, self.s, self.r, persp, self.d_images, self.d_masks))
         _lib.check(lib, lib.ys_augment_labels(e.ctx, self.d_srcs, self.d_lab_off, self.d_cls, self.d_boxes, self.d_kp, self.K, 3, self.d_items, B, 1, self.s, persp,
-                                              self.flags, self.capacity, self.d_bidx, self.d_ocls, self.d_obox, self.d_okp, self.d_cnt))
+                                              self.flags & ~YS_AUG_FLIP_KEEP_SIZE, self.capacity, self.d_bidx, self.d_ocls, self.d_obox, self.d_okp, self.d_cnt))
         n_input = int(sum(int(self.lab_off[k + 1] - self.lab_off[k]) for k in items["src"].reshape(-1)))
         return DeviceBatch(e, B, self.s, self.capacity, self.d_images, self.d_bidx, self.d_ocls, self.d_obox, self.d_cnt, masks=self.d_masks,
                            keypoints=self.d_okp, kpt_num=self.K, mask_ratio=self.r, n_input=n_input, max_per_image=self.max_per_image)

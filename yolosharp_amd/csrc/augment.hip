@@ -25,7 +25,8 @@
 // stream, about 5x above the HBM estimate of its bytes (DESIGN.md "Training input on the device").
 //
 // Scope (include/yolosharp_hip.h lists the same): kpt_dim = 3 only (apply_keypoints reads column 2); no OBB corner labels (xyxyxyxy2xywhr is host
-// code in the reference); no RandomHSV (TorchVision.NET ColorJitter, not in the reference tree); no no-mosaic branch.  Deviations: a label-free
+// code in the reference); no RandomHSV (TorchVision.NET ColorJitter, not in the reference tree); of the no-mosaic branches the close-mosaic one (LetterBox) is built below,
+// the `rand > p` one of Augment.Mosaic is not (it yields images of unequal sizes).  Deviations: a label-free
 // sample is still warped (RandomPerspective.Apply returns the unwarped canvas, :666-669); where the reference's mask slice would run past the
 // source mask (it throws) the kernel reads 0.
 #include "ys_internal.h"
@@ -430,6 +431,195 @@ aug_labels_kernel(const ys_aug_src* __restrict__ srcs, int n_src, const int* __r
   }
 }
 
+// ---------------------------------------------------------------------------------------------------------------- LetterBox branch
+// The close-mosaic training input (YoloDataset.CloseMosaic(true), Data/YoloDataset.cs:378-429; also ImageProcessType.Letterbox, :70-74):
+// LetterBox(s, s, mask_ratio) (Data/Augment.cs:698-778) + FlipLR / FlipUD (:860-966) + mul(1/255) + collate, on src[0] of an item alone.
+//
+//   aug_letterbox_kernel<3>       LetterboxImage (:756-777) of the image: nearest resize (the rule of letterbox_kernel, elementwise.hip) into the
+//                                 window [pad_u, pad_u + new_h) x [pad_l, pad_l + new_w), 114 elsewhere, flips folded into the output coordinate,
+//                                 byte * (1 / 255.0f): a pure gather, nothing is blended, so the output is bit-exact against a restatement.
+//                                 ratio == 1 -- the loader has resized the long side to s -- takes no division and reads a quad's four
+//                                 consecutive source bytes as aligned words, at any arena offset and row width.
+//   aug_letterbox_kernel<1>       the same on the [mh, mw] id mask with ITS OWN ratio and pads for an (s / r)^2 output (:725), fill 0, whole ids.
+//                                 The reference computes them from the mask's size, not as the image's pads / r: mask and image can sit a fraction
+//                                 of a cell apart (kept).
+//   aug_letterbox_count_kernel, aug_letterbox_labels_kernel
+//                                 every label of the source, in order (this branch has no thresholds); offsets = aug_count_scan_kernel over the
+//                                 sources' label counts.  The reference carries cxcywh here (bbox_format = cxcywh, YoloDataset.cs:303): the
+//                                 pixel xyxy table becomes cx = (x1 + x2) / 2, w = x2 - x1 (torchvision box_convert) -- a deviation of a few fp32
+//                                 roundings -- then + (pad_l, pad_u, 0, 0) (:735-738; keypoints + (pad_l, pad_u), :741-744), NEITHER scaled by
+//                                 ratio (kept: exact whenever ratio == 1), the flips, mul(1f / s) (Struct.cs:106-115).
+//                                 QUIRK kept by default: FlipLR / FlipUD test bbox_format != xywh, true for cxcywh, and rewrite columns 0 AND 2
+//                                 (1 AND 3) as s - value (:888-892, :943-947): a flipped box's width becomes s - w.  YS_AUG_FLIP_KEEP_SIZE leaves
+//                                 columns 2 / 3 alone.  Keypoints: x <- s - x / y <- s - y, no left / right index swap (the reference has none).
+struct AugLbGeom { int new_w, new_h, pad_l, pad_u; };
+
+// LetterboxImage's geometry (:761-770) of an h x w plane on an out x out canvas, in the reference's fp32 arithmetic
+__host__ __device__ inline AugLbGeom aug_letterbox_geom(int h, int w, int out) {
+  const float ratio_w = (float)out / (float)w, ratio_h = (float)out / (float)h;
+  const float ratio = ratio_w < ratio_h ? ratio_w : ratio_h;
+  AugLbGeom g;
+  g.new_w = (int)((float)w * ratio); g.new_h = (int)((float)h * ratio);
+  g.new_w = g.new_w < 0 ? 0 : (g.new_w > out ? out : g.new_w);      // fp32 cannot leave [0, out] for sizes below 2^24; the clamp keeps the window inside
+  g.new_h = g.new_h < 0 ? 0 : (g.new_h > out ? out : g.new_h);      // the output whatever the table holds
+  g.pad_l = (out - g.new_w) / 2; g.pad_u = (out - g.new_h) / 2;
+  return g;
+}
+
+// the source a LetterBox item names (src[0]; the other fields but the flips are ignored), or -1: outside the table, or a source without an image
+__host__ __device__ inline int aug_letterbox_src(const ys_aug_item& it, const ys_aug_src* srcs, int n_src) {
+  const int k = it.src[0];
+  if (k < 0 || k >= n_src) return -1;
+  const ys_aug_src& sr = srcs[k];
+  return (sr.h < 1 || sr.w < 1 || sr.img_off < 0) ? -1 : k;
+}
+
+// one thread: 4 consecutive x of one output row, C planes -> C 16-byte stores (vec: s % 4 == 0, base 16-byte aligned), else scalar stores.
+// C = 3: the image [B, 3, s, s]; C = 1: the id mask [B, s, s] with s = imgsz / mask_ratio.
+template <int C>
+__global__ void __launch_bounds__(AUG_T)
+aug_letterbox_kernel(const unsigned char* __restrict__ arena, const ys_aug_src* __restrict__ srcs, int n_src, const ys_aug_item* __restrict__ items,
+                     int s, int vec, float* __restrict__ out) {
+  const int qpr = (s + 3) >> 2;
+  const unsigned i = blockIdx.x * AUG_T + threadIdx.x;
+  if (i >= (unsigned)qpr * (unsigned)s) return;
+  const int y = (int)(i / (unsigned)qpr), x0 = (int)(i - (unsigned)y * (unsigned)qpr) * 4;
+  // wave-uniform: the item, its source and the window
+  const ys_aug_item& it = items[blockIdx.z];
+  const int k = aug_letterbox_src(it, srcs, n_src);
+  int h = 0, w = 0;
+  long long off = -1;
+  if (k >= 0) {
+    const ys_aug_src& sr = srcs[k];
+    if (C == 3) { h = sr.h; w = sr.w; off = sr.img_off; }
+    else if (sr.mask_off >= 0 && sr.mh >= 1 && sr.mw >= 1) { h = sr.mh; w = sr.mw; off = sr.mask_off; }
+  }
+  AugLbGeom g;
+  g.new_w = g.new_h = g.pad_l = g.pad_u = 0;               // a refused item, a source without a mask: the window is empty, nothing is read
+  // ratio == 1 (the loader has resized the long side to s): s / (float)s is exactly 1 and the other ratio is >= 1, so new = (h, w) -- no division, and
+  // the nearest rule is the identity.  A wave-uniform branch.
+  const bool ident = off >= 0 && ((w == s && h <= s) || (h == s && w <= s));
+  if (ident) { g.new_w = w; g.new_h = h; g.pad_l = (s - w) / 2; g.pad_u = (s - h) / 2; }
+  else if (off >= 0) g = aug_letterbox_geom(h, w, s);
+  const bool flr = it.flip_lr != 0, fud = it.flip_ud != 0;
+  const float q = C == 3 ? 1 / 255.0f : 1.0f;             // mul(1 / 255.0f), YoloDataset.cs:140: a multiply, bit-exact per byte; ids stay whole
+  const float fill = C == 3 ? 114.0f * q : 0.0f;
+  // the flips are folded into the output coordinate: out[y][x] = letterboxed[ly][lx]
+  const int ry = (fud ? s - 1 - y : y) - g.pad_u;
+  const bool row_in = (unsigned)ry < (unsigned)g.new_h;
+  float v[C][4];
+#pragma unroll
+  for (int j = 0; j < 4; j++)
+#pragma unroll
+    for (int c = 0; c < C; c++) v[c][j] = fill;
+  if (row_in) {
+    // ATen's nearest rule, fp32: src = min(floor(dst * (float)in / out), in - 1)
+    float sy = 1.0f, sx = 1.0f;
+    if (!ident) { sy = (float)h / (float)g.new_h; sx = (float)w / (float)g.new_w; }
+    int iy = (int)floorf((float)ry * sy);
+    iy = iy < h - 1 ? iy : h - 1;
+    const long long plane = (long long)h * w;
+    const unsigned char* __restrict__ row = arena + off + (long long)iy * w;
+    const int rx0 = (flr ? s - 1 - x0 : x0) - g.pad_l;     // source column of output x0; the quad's columns run down from it when flipped
+    const int lo = flr ? rx0 - 3 : rx0;
+    if (ident && x0 + 3 < s && lo >= 0 && lo + 3 < w) {
+      // the whole quad lies in the window and its four source bytes are consecutive, at any alignment: the one or two ALIGNED words that hold them
+      // (each holds at least one byte of the source, so neither can leave its page), shifted together
+#pragma unroll
+      for (int c = 0; c < C; c++) {
+        const unsigned char* __restrict__ p = row + c * plane + lo;
+        const unsigned sh = (unsigned)((unsigned long long)p & 3);
+        const unsigned* __restrict__ wp = (const unsigned*)(p - sh);
+        const unsigned w0 = wp[0], w1 = sh ? wp[1] : 0u;
+        unsigned px = (unsigned)((((unsigned long long)w1 << 32) | w0) >> (8 * sh));
+        if (flr) px = __builtin_bswap32(px);
+        v[c][0] = (float)(px & 255u) * q; v[c][1] = (float)((px >> 8) & 255u) * q;
+        v[c][2] = (float)((px >> 16) & 255u) * q; v[c][3] = (float)(px >> 24) * q;
+      }
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; j++) {
+        const int rx = flr ? rx0 - j : rx0 + j;
+        if (x0 + j < s && (unsigned)rx < (unsigned)g.new_w) {
+          int ix = (int)floorf((float)rx * sx);
+          ix = ix < w - 1 ? ix : w - 1;
+#pragma unroll
+          for (int c = 0; c < C; c++) v[c][j] = (float)row[c * plane + ix] * q;
+        }
+      }
+    }
+  }
+  const long long oplane = (long long)s * s;
+  float* dst = out + (long long)blockIdx.z * C * oplane + (long long)y * s + x0;
+  if (vec) {
+#pragma unroll
+    for (int c = 0; c < C; c++) ys_st16(dst + c * oplane, make_uint4(ys_f2u(v[c][0]), ys_f2u(v[c][1]), ys_f2u(v[c][2]), ys_f2u(v[c][3])));
+  } else {
+#pragma unroll
+    for (int j = 0; j < 4; j++)
+      if (x0 + j < s)
+#pragma unroll
+        for (int c = 0; c < C; c++) dst[c * oplane + j] = v[c][j];
+  }
+}
+
+// counts[b] = the label count of image b's source (0 for a refused item)
+__global__ void __launch_bounds__(AUG_T)
+aug_letterbox_count_kernel(const ys_aug_src* __restrict__ srcs, int n_src, const int* __restrict__ lab_off, const ys_aug_item* __restrict__ items, int B,
+                           int* __restrict__ counts) {
+  const int b = blockIdx.x * AUG_T + threadIdx.x;
+  if (b >= B) return;
+  const int k = aug_letterbox_src(items[b], srcs, n_src);
+  const int n = k >= 0 ? lab_off[k + 1] - lab_off[k] : 0;
+  counts[b] = n > 0 ? n : 0;
+}
+
+// one workgroup per image: rows [offs[b], offs[b + 1]) = the source's labels in order; the tail [total, capacity) = (batch_idx -1, zeros);
+// *o_count = total (a total above capacity is reported as it is; rows past capacity are not written)
+__global__ void __launch_bounds__(AUG_T)
+aug_letterbox_labels_kernel(const ys_aug_src* __restrict__ srcs, int n_src, const int* __restrict__ lab_off, const float* __restrict__ cls,
+                            const float* __restrict__ boxes, const float* __restrict__ kpts, int K, const ys_aug_item* __restrict__ items, int B, int s,
+                            int flags, int capacity, const int* __restrict__ offs, float* __restrict__ o_bidx, float* __restrict__ o_cls,
+                            float* __restrict__ o_box, float* __restrict__ o_kpt, int* __restrict__ o_count) {
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const ys_aug_item& it = items[b];
+  const int base = offs[b], n = offs[b + 1] - base, total = offs[B];
+  const int k = aug_letterbox_src(it, srcs, n_src);
+  if (k >= 0 && n > 0) {
+    const AugLbGeom g = aug_letterbox_geom(srcs[k].h, srcs[k].w, s);
+    const int first = lab_off[k];
+    const float S = (float)s, inv = 1.0f / S, pl = (float)g.pad_l, pu = (float)g.pad_u;
+    const bool flr = it.flip_lr != 0, fud = it.flip_ud != 0, keep_size = (flags & YS_AUG_FLIP_KEEP_SIZE) != 0;
+    for (int j = tid; j < n; j += AUG_T) {
+      const long long rowi = (long long)base + j;
+      if (rowi >= capacity) break;
+      const int l = first + j;
+      const float x1 = boxes[4 * l], y1 = boxes[4 * l + 1], x2 = boxes[4 * l + 2], y2 = boxes[4 * l + 3];
+      float cx = (x1 + x2) / 2.0f + pl, cy = (y1 + y2) / 2.0f + pu, bw = x2 - x1, bh = y2 - y1;
+      if (flr) { cx = S - cx; if (!keep_size) bw = S - bw; }
+      if (fud) { cy = S - cy; if (!keep_size) bh = S - bh; }
+      o_bidx[rowi] = (float)b; o_cls[rowi] = cls[l];
+      o_box[4 * rowi] = cx * inv; o_box[4 * rowi + 1] = cy * inv; o_box[4 * rowi + 2] = bw * inv; o_box[4 * rowi + 3] = bh * inv;
+      if (o_kpt) {
+        const float* __restrict__ kin = kpts + (long long)l * K * 3;
+        float* __restrict__ kout = o_kpt + rowi * K * 3;
+        for (int p = 0; p < K; p++) {
+          float px = kin[3 * p] + pl, py = kin[3 * p + 1] + pu;
+          if (flr) px = S - px;
+          if (fud) py = S - py;
+          kout[3 * p] = px * inv; kout[3 * p + 1] = py * inv; kout[3 * p + 2] = kin[3 * p + 2];
+        }
+      }
+    }
+  }
+  if (b == 0 && tid == 0) *o_count = total;
+  for (long long rowi = (long long)total + (long long)b * AUG_T + tid; rowi < capacity; rowi += (long long)B * AUG_T) {
+    o_bidx[rowi] = -1.0f; o_cls[rowi] = 0.0f;
+    o_box[4 * rowi] = 0.f; o_box[4 * rowi + 1] = 0.f; o_box[4 * rowi + 2] = 0.f; o_box[4 * rowi + 3] = 0.f;
+    if (o_kpt) for (int p = 0; p < K * 3; p++) o_kpt[rowi * K * 3 + p] = 0.f;
+  }
+}
+
 // ---------------------------------------------------------------------------------------------------------------- launchers
 size_t ys_aug_ws_bytes(int B) { return (size_t)B * sizeof(AugParams) + ((size_t)2 * B + 1) * sizeof(int) + 64; }   // params | counts [B] | offsets [B + 1]
 
@@ -460,5 +650,32 @@ int ys_aug_labels_launch(hipStream_t st, const ys_aug_src* srcs, int n_src, cons
     YS_LAUNCH(aug_labels_kernel, B, AUG_T, st, srcs, n_src, lab_off, cls, boxes, kpts, K, items, B, s, perspective, flags, capacity, pass, counts,
               o_bidx, o_cls, o_box, o_kpt, o_count);
   }
+  return YS_OK;
+}
+
+int ys_aug_letterbox_src_host(const ys_aug_item* it, const ys_aug_src* srcs, int n_src) { return aug_letterbox_src(*it, srcs, n_src); }
+
+int ys_aug_letterbox_launch(hipStream_t st, const unsigned char* arena, const ys_aug_src* srcs, int n_src, const ys_aug_item* items, int B, int s,
+                            int r, float* images, float* masks) {
+  const long quads = (long)((s + 3) / 4) * s;
+  YS_LAUNCH((aug_letterbox_kernel<3>), dim3(ys_cdiv(quads, AUG_T), 1, B), AUG_T, st, arena, srcs, n_src, items, s,
+            (s % 4 == 0 && ((size_t)images & 15) == 0) ? 1 : 0, images);
+  if (masks) {
+    const int ms = s / r;
+    const long mquads = (long)((ms + 3) / 4) * ms;
+    YS_LAUNCH((aug_letterbox_kernel<1>), dim3(ys_cdiv(mquads, AUG_T), 1, B), AUG_T, st, arena, srcs, n_src, items, ms,
+              (ms % 4 == 0 && ((size_t)masks & 15) == 0) ? 1 : 0, masks);
+  }
+  return YS_OK;
+}
+
+int ys_aug_letterbox_labels_launch(hipStream_t st, const ys_aug_src* srcs, int n_src, const int* lab_off, const float* cls, const float* boxes,
+                                   const float* kpts, int K, const ys_aug_item* items, int B, int s, int flags, int capacity, void* ws, float* o_bidx,
+                                   float* o_cls, float* o_box, float* o_kpt, int* o_count) {
+  int* counts = (int*)((char*)ws + (size_t)B * sizeof(AugParams));            // the workspace layout of ys_aug_ws_bytes: counts [B] | offsets [B + 1]
+  YS_LAUNCH(aug_letterbox_count_kernel, ys_cdiv(B, AUG_T), AUG_T, st, srcs, n_src, lab_off, items, B, counts);
+  YS_LAUNCH(aug_count_scan_kernel, 1, AUG_T, st, (const int*)counts, B, counts + B);
+  YS_LAUNCH(aug_letterbox_labels_kernel, B, AUG_T, st, srcs, n_src, lab_off, cls, boxes, kpts, K, items, B, s, flags, capacity, (const int*)(counts + B),
+            o_bidx, o_cls, o_box, o_kpt, o_count);
   return YS_OK;
 }

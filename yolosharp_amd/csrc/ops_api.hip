@@ -987,6 +987,16 @@ int aug_reserve_ws(ys_ctx* ctx, int batch) {
   ctx->aug_ws_bytes = need;
   return YS_OK;
 }
+// the part of the arena the sources name (what a host-pointer call uploads)
+size_t aug_arena_bytes(const ys_aug_src* srcs, int n_src) {
+  size_t bytes = 0;
+  for (int k = 0; k < n_src; k++) {
+    const ys_aug_src& sr = srcs[k];
+    if (sr.img_off >= 0 && sr.h > 0 && sr.w > 0) { const size_t e = (size_t)sr.img_off + (size_t)3 * sr.h * sr.w; bytes = e > bytes ? e : bytes; }
+    if (sr.mask_off >= 0 && sr.mh > 0 && sr.mw > 0) { const size_t e = (size_t)sr.mask_off + (size_t)sr.mh * sr.mw; bytes = e > bytes ? e : bytes; }
+  }
+  return bytes;
+}
 // the checks a host-resident item table allows (include/yolosharp_hip.h); n_src < 0: unknown, only src >= 0 is checked
 int aug_check_items(const char* fn, const ys_aug_item* items, int batch, const ys_aug_src* srcs, int n_src, int s, int perspective) {
   for (int b = 0; b < batch; b++) {
@@ -1018,13 +1028,7 @@ extern "C" int ys_augment_mosaic(ys_ctx* ctx, const uint8_t* arena, const ys_aug
   YsTimer timer(ctx, "augment");
   if (on_device) return ys_aug_mosaic_launch(st, arena, srcs, n_src, items, batch, imgsz, r, perspective != 0, ctx->aug_ws, images, masks);
   YS_TRY(aug_check_items("ys_augment_mosaic", items, batch, srcs, n_src, imgsz, perspective != 0));
-  // the part of the arena the sources name
-  size_t arena_bytes = 0;
-  for (int k = 0; k < n_src; k++) {
-    const ys_aug_src& sr = srcs[k];
-    if (sr.img_off >= 0 && sr.h > 0 && sr.w > 0) { const size_t e = (size_t)sr.img_off + (size_t)3 * sr.h * sr.w; arena_bytes = e > arena_bytes ? e : arena_bytes; }
-    if (sr.mask_off >= 0 && sr.mh > 0 && sr.mw > 0) { const size_t e = (size_t)sr.mask_off + (size_t)sr.mh * sr.mw; arena_bytes = e > arena_bytes ? e : arena_bytes; }
-  }
+  const size_t arena_bytes = aug_arena_bytes(srcs, n_src);
   const size_t n_img = (size_t)batch * 3 * imgsz * imgsz, n_msk = masks ? (size_t)batch * (imgsz / r) * (imgsz / r) : 0;
   DevBuf da, ds, di, dimg, dm;
   YS_TRY(da.alloc(arena_bytes)); YS_TRY(ds.alloc((size_t)n_src * sizeof(ys_aug_src))); YS_TRY(di.alloc((size_t)batch * sizeof(ys_aug_item)));
@@ -1091,6 +1095,99 @@ extern "C" int ys_augment_labels(ys_ctx* ctx, const ys_aug_src* srcs, const int3
   YS_TRY(ys_aug_labels_launch(st, (const ys_aug_src*)ds.p, n_src, (const int*)dl.p, (const float*)dc.p, (const float*)db.p, K ? (const float*)dk.p : nullptr, K,
                               (const ys_aug_item*)di.p, batch, imgsz, perspective != 0, flags, capacity, ctx->aug_ws, (float*)obi.p, (float*)ocl.p, (float*)obx.p,
                               K ? (float*)okp.p : nullptr, (int*)ocn.p));
+  YS_CHECK_HIP(hipMemcpyAsync(out_batch_idx, obi.p, cap * 4, hipMemcpyDeviceToHost, st));
+  YS_CHECK_HIP(hipMemcpyAsync(out_cls, ocl.p, cap * 4, hipMemcpyDeviceToHost, st));
+  YS_CHECK_HIP(hipMemcpyAsync(out_bboxes, obx.p, cap * 16, hipMemcpyDeviceToHost, st));
+  if (K) YS_CHECK_HIP(hipMemcpyAsync(out_keypoints, okp.p, cap * K * 12, hipMemcpyDeviceToHost, st));
+  YS_CHECK_HIP(hipMemcpyAsync(out_count, ocn.p, 4, hipMemcpyDeviceToHost, st));
+  YS_CHECK_HIP(hipStreamSynchronize(st));
+  return YS_OK;
+}
+
+// ---- the LetterBox (close-mosaic) branch of the training input (Data/YoloDataset.cs:378-429; Data/Augment.cs:698-778, 860-966)
+namespace {
+int aug_check_letterbox_items(const char* fn, const ys_aug_item* items, int batch, const ys_aug_src* srcs, int n_src) {
+  for (int b = 0; b < batch; b++) {
+    const int k = items[b].src[0];
+    YS_REQUIRE(k >= 0 && k < n_src, "%s: item %d: src[0] = %d is outside [0, %d)", fn, b, k, n_src);
+    YS_REQUIRE(ys_aug_letterbox_src_host(&items[b], srcs, n_src) == k, "%s: source %d has no image", fn, k);
+  }
+  return YS_OK;
+}
+}  // namespace
+
+extern "C" int ys_augment_letterbox(ys_ctx* ctx, const uint8_t* arena, const ys_aug_src* srcs, int n_src, const ys_aug_item* items, int batch,
+                                    int on_device, int imgsz, int mask_ratio, float* images, float* masks) {
+  YS_REQUIRE(ctx && arena && srcs && items && images, "ys_augment_letterbox: null argument");
+  YS_REQUIRE(batch > 0 && batch <= 65535 && n_src > 0, "ys_augment_letterbox: bad shape batch=%d (1..65535) n_src=%d", batch, n_src);
+  YS_REQUIRE(imgsz >= 2 && imgsz % 2 == 0 && imgsz <= 16384, "ys_augment_letterbox: imgsz %d must be even and in [2, 16384]", imgsz);
+  if (masks) YS_REQUIRE(mask_ratio >= 1 && imgsz % mask_ratio == 0, "ys_augment_letterbox: mask_ratio %d does not divide imgsz %d", mask_ratio, imgsz);
+  const int r = masks ? mask_ratio : 1;
+  YS_CHECK_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  YsTimer timer(ctx, "augment_letterbox");
+  if (on_device) return ys_aug_letterbox_launch(st, arena, srcs, n_src, items, batch, imgsz, r, images, masks);
+  YS_TRY(aug_check_letterbox_items("ys_augment_letterbox", items, batch, srcs, n_src));
+  const size_t arena_bytes = aug_arena_bytes(srcs, n_src);
+  const size_t n_img = (size_t)batch * 3 * imgsz * imgsz, n_msk = masks ? (size_t)batch * (imgsz / r) * (imgsz / r) : 0;
+  DevBuf da, ds, di, dimg, dm;
+  YS_TRY(da.alloc(arena_bytes)); YS_TRY(ds.alloc((size_t)n_src * sizeof(ys_aug_src))); YS_TRY(di.alloc((size_t)batch * sizeof(ys_aug_item)));
+  YS_TRY(dimg.alloc(n_img * 4)); YS_TRY(dm.alloc(n_msk * 4));
+  YS_CHECK_HIP(hipMemcpyAsync(da.p, arena, arena_bytes, hipMemcpyHostToDevice, st));
+  YS_CHECK_HIP(hipMemcpyAsync(ds.p, srcs, (size_t)n_src * sizeof(ys_aug_src), hipMemcpyHostToDevice, st));
+  YS_CHECK_HIP(hipMemcpyAsync(di.p, items, (size_t)batch * sizeof(ys_aug_item), hipMemcpyHostToDevice, st));
+  YS_TRY(ys_aug_letterbox_launch(st, (const unsigned char*)da.p, (const ys_aug_src*)ds.p, n_src, (const ys_aug_item*)di.p, batch, imgsz, r, (float*)dimg.p,
+                                 masks ? (float*)dm.p : nullptr));
+  YS_CHECK_HIP(hipMemcpyAsync(images, dimg.p, n_img * 4, hipMemcpyDeviceToHost, st));
+  if (masks) YS_CHECK_HIP(hipMemcpyAsync(masks, dm.p, n_msk * 4, hipMemcpyDeviceToHost, st));
+  YS_CHECK_HIP(hipStreamSynchronize(st));
+  return YS_OK;
+}
+
+extern "C" int ys_augment_letterbox_labels(ys_ctx* ctx, const ys_aug_src* srcs, int n_src, const int32_t* lab_off, const float* cls, const float* boxes,
+                                           const float* keypoints, int kpt_num, int kpt_dim, const ys_aug_item* items, int batch, int on_device,
+                                           int imgsz, int flags, int capacity, float* out_batch_idx, float* out_cls, float* out_bboxes,
+                                           float* out_keypoints, int32_t* out_count) {
+  YS_REQUIRE(ctx && srcs && lab_off && cls && boxes && items && out_batch_idx && out_cls && out_bboxes && out_count, "ys_augment_letterbox_labels: null argument");
+  YS_REQUIRE(batch > 0 && batch <= 65535 && capacity > 0 && n_src > 0, "ys_augment_letterbox_labels: bad shape batch=%d (1..65535) capacity=%d n_src=%d", batch,
+             capacity, n_src);
+  YS_REQUIRE(imgsz >= 2 && imgsz % 2 == 0 && imgsz <= 16384, "ys_augment_letterbox_labels: imgsz %d must be even and in [2, 16384]", imgsz);
+  YS_REQUIRE((keypoints != nullptr) == (out_keypoints != nullptr), "ys_augment_letterbox_labels: keypoints and out_keypoints go together");
+  if (keypoints) {
+    YS_REQUIRE(kpt_dim == 3, "ys_augment_letterbox_labels: kpt_dim %d: only (x, y, visibility) keypoints are supported", kpt_dim);
+    YS_REQUIRE(kpt_num > 0, "ys_augment_letterbox_labels: kpt_num %d", kpt_num);
+  }
+  YS_REQUIRE((flags & ~(YS_AUG_SORT_FLIPPED | YS_AUG_FLIP_KEEP_SIZE)) == 0, "ys_augment_letterbox_labels: unknown flags 0x%x", flags);
+  const int K = keypoints ? kpt_num : 0;
+  YS_CHECK_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  YS_TRY(aug_reserve_ws(ctx, batch));
+  YsTimer timer(ctx, "augment_letterbox_labels");
+  if (on_device)
+    return ys_aug_letterbox_labels_launch(st, srcs, n_src, lab_off, cls, boxes, keypoints, K, items, batch, imgsz, flags, capacity, ctx->aug_ws, out_batch_idx,
+                                          out_cls, out_bboxes, out_keypoints, out_count);
+  YS_TRY(aug_check_letterbox_items("ys_augment_letterbox_labels", items, batch, srcs, n_src));
+  for (int k = 0; k < n_src; k++)
+    YS_REQUIRE(lab_off[k] >= 0 && lab_off[k + 1] >= lab_off[k], "ys_augment_letterbox_labels: lab_off is not non-decreasing at source %d", k);
+  long total = 0;
+  for (int b = 0; b < batch; b++) total += lab_off[items[b].src[0] + 1] - lab_off[items[b].src[0]];
+  YS_REQUIRE(total <= capacity, "ys_augment_letterbox_labels: the batch carries %ld labels, capacity is %d", total, capacity);
+  const size_t cap = (size_t)capacity, n_lab = (size_t)lab_off[n_src];
+  DevBuf ds, dl, dc, db, dk, di, obi, ocl, obx, okp, ocn;
+  YS_TRY(ds.alloc((size_t)n_src * sizeof(ys_aug_src))); YS_TRY(dl.alloc((size_t)(n_src + 1) * 4)); YS_TRY(dc.alloc(n_lab * 4)); YS_TRY(db.alloc(n_lab * 16));
+  YS_TRY(dk.alloc(n_lab * K * 12)); YS_TRY(di.alloc((size_t)batch * sizeof(ys_aug_item)));
+  YS_TRY(obi.alloc(cap * 4)); YS_TRY(ocl.alloc(cap * 4)); YS_TRY(obx.alloc(cap * 16)); YS_TRY(okp.alloc(cap * K * 12)); YS_TRY(ocn.alloc(4));
+  YS_CHECK_HIP(hipMemcpyAsync(ds.p, srcs, (size_t)n_src * sizeof(ys_aug_src), hipMemcpyHostToDevice, st));
+  YS_CHECK_HIP(hipMemcpyAsync(dl.p, lab_off, (size_t)(n_src + 1) * 4, hipMemcpyHostToDevice, st));
+  if (n_lab) {
+    YS_CHECK_HIP(hipMemcpyAsync(dc.p, cls, n_lab * 4, hipMemcpyHostToDevice, st));
+    YS_CHECK_HIP(hipMemcpyAsync(db.p, boxes, n_lab * 16, hipMemcpyHostToDevice, st));
+    if (K) YS_CHECK_HIP(hipMemcpyAsync(dk.p, keypoints, n_lab * K * 12, hipMemcpyHostToDevice, st));
+  }
+  YS_CHECK_HIP(hipMemcpyAsync(di.p, items, (size_t)batch * sizeof(ys_aug_item), hipMemcpyHostToDevice, st));
+  YS_TRY(ys_aug_letterbox_labels_launch(st, (const ys_aug_src*)ds.p, n_src, (const int*)dl.p, (const float*)dc.p, (const float*)db.p,
+                                        K ? (const float*)dk.p : nullptr, K, (const ys_aug_item*)di.p, batch, imgsz, flags, capacity, ctx->aug_ws, (float*)obi.p,
+                                        (float*)ocl.p, (float*)obx.p, K ? (float*)okp.p : nullptr, (int*)ocn.p));
   YS_CHECK_HIP(hipMemcpyAsync(out_batch_idx, obi.p, cap * 4, hipMemcpyDeviceToHost, st));
   YS_CHECK_HIP(hipMemcpyAsync(out_cls, ocl.p, cap * 4, hipMemcpyDeviceToHost, st));
   YS_CHECK_HIP(hipMemcpyAsync(out_bboxes, obx.p, cap * 16, hipMemcpyDeviceToHost, st));

@@ -431,3 +431,11 @@ int ys_aug_mosaic_launch(hipStream_t st, const unsigned char* arena, const ys_au
 int ys_aug_labels_launch(hipStream_t st, const ys_aug_src* srcs, int n_src, const int* lab_off, const float* cls, const float* boxes,
                          const float* kpts, int K, const ys_aug_item* items, int B, int s, int perspective, int flags, int capacity, void* ws,
                          float* o_bidx, float* o_cls, float* o_box, float* o_kpt, int* o_count);
+// the LetterBox (close-mosaic) branch: LetterBox + flips + Normalize + collate of src[0] of an item (Data/Augment.cs:698-778, 860-966); the labels launch
+// uses the counts | offsets part of the same workspace
+int ys_aug_letterbox_src_host(const ys_aug_item* it, const ys_aug_src* srcs, int n_src);
+int ys_aug_letterbox_launch(hipStream_t st, const unsigned char* arena, const ys_aug_src* srcs, int n_src, const ys_aug_item* items, int B, int s,
+                            int r, float* images, float* masks);
+int ys_aug_letterbox_labels_launch(hipStream_t st, const ys_aug_src* srcs, int n_src, const int* lab_off, const float* cls, const float* boxes,
+                                   const float* kpts, int K, const ys_aug_item* items, int B, int s, int flags, int capacity, void* ws, float* o_bidx,
+                                   float* o_cls, float* o_box, float* o_kpt, int* o_count);

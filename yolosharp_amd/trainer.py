@@ -1,6 +1,7 @@
 """Host mirror of the reference's training driver around the engine:
 YoloBaseTaskModel.Train (:116-215), TrainEpoch (:291-356) with its warm-up, LambdaLR / OneCycle / LrLambda / Interp
-(:492-536) and the lr0 fit (:142).  Data loading / augmentation stay outside (out of scope); `fit` consumes ready batches."""
+(:492-536) and the lr0 fit (:142).  Data loading / augmentation stay outside (out of scope); `fit` consumes ready batches and, given the
+augmenter they come from, switches it to the LetterBox pipeline as the reference's loop does (:180)."""
 import math
 import os
 
@@ -117,10 +118,15 @@ class Trainer:
         n_items = getattr(self.crit, "N_ITEMS", 3)
         return items_sum if items_sum is not None else np.zeros(n_items, np.float32)
 
-    def fit(self, train_batches, val_batches=None):
-        """train_batches / val_batches: callables returning an iterable of batches for an epoch.  Returns the history."""
+    def fit(self, train_batches, val_batches=None, augmenter=None, close_mosaic=0):
+        """train_batches / val_batches: callables returning an iterable of batches for an epoch.  Returns the history.
+        augmenter: the augment.MosaicAugmenter train_batches draws from.  Before each epoch's train_batches() it is told
+        `augmenter.close_mosaic(epoch > close_mosaic)` -- trainDataSet.CloseMosaic(epoch > config.CloseMosaic), YoloBaseTaskModel.cs:180, with
+        Config.CloseMosaic's default of 0: the LetterBox pipeline from epoch 1 on.  Without an augmenter nothing changes."""
         hist = []
         for epoch in range(1, self.epochs + 1):
+            if augmenter is not None:
+                augmenter.close_mosaic(epoch > close_mosaic)
             tr = self.train_epoch(train_batches(), epoch)
             self.sched.end_epoch()
             # The reference steps the End2End gain schedule only `if (loss is Loss.E2EOBBLoss)` (YoloBaseTaskModel.cs:350-353): train_epoch does that for an
