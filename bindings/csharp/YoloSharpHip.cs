@@ -94,7 +94,7 @@ namespace YoloSharp.Native
                                                                  int outW, int outH, int color, [Out] byte[] dst, out int padL, out int padU);
         // Training input on the device (Data/YoloDataset.cs:57-151: Mosaic4 + RandomPerspective + FlipLR / FlipUD + Normalize + mul(1/255) + collate): the sources live in
         // one uint8 arena, an item carries what the reference draws per output image.  Device-resident callers pass IntPtr (on_device = 1) for every pointer.
-        // Quirk kept: a flipped box keeps x1 > x2 (negative w after cxcywh) unless flags has YS_AUG_SORT_FLIPPED (1).  Not built: RandomHSV, OBB corners, the `rand > p` case of Mosaic.
+        // Quirk kept: a flipped box keeps x1 > x2 (negative w after cxcywh) unless flags has YS_AUG_SORT_FLIPPED (1).  Not built: OBB corners, the `rand > p` case of Mosaic.
         [StructLayout(LayoutKind.Sequential)] internal struct YsAugSrc { public long imgOff, maskOff; public int h, w, mh, mw; }
         [StructLayout(LayoutKind.Sequential)] internal struct YsAugItem { public int src0, src1, src2, src3, xc, yc; public float m00, m01, m02, m10, m11, m12, m20, m21, m22; public int flipLr, flipUd; }
         [DllImport(Lib)] internal static extern int ys_augment_mosaic(IntPtr ctx, IntPtr arena, IntPtr srcs, int nSrc, IntPtr items, int batch, int onDevice, int imgsz,
@@ -111,6 +111,16 @@ namespace YoloSharp.Native
         [DllImport(Lib)] internal static extern int ys_augment_letterbox_labels(IntPtr ctx, IntPtr srcs, int nSrc, IntPtr labOff, IntPtr cls, IntPtr boxes, IntPtr keypoints,
                                                                                 int kptNum, int kptDim, IntPtr items, int batch, int onDevice, int imgsz, int flags, int capacity,
                                                                                 IntPtr outBatchIdx, IntPtr outCls, IntPtr outBboxes, IntPtr outKeypoints, IntPtr outCount);
+        // ColorJitter (RandomHSV, Data/Augment.cs:968-987; torchvision's uint8 algorithm, parity with TorchVision.NET unpinned): one row per output image holds what
+        // get_params draws -- the op id of each slot (0 brightness, 1 contrast, 2 saturation, 3 hue, -1 nothing) and the factor of each op id.  The *_jitter entries are
+        // the plain ones with the rows applied in the gather kernels' epilogue (jitter = IntPtr.Zero: the plain entry; a contrast row: YS_ERR_UNSUPPORTED);
+        // ys_color_jitter is the operator on its own (all four ops; dst uint8 or fp32 byte / 255), e.g. for ClassificationDataset's chain.
+        [StructLayout(LayoutKind.Sequential)] internal struct YsAugJitter { public int order0, order1, order2, order3; public float brightness, contrast, saturation, hue; }
+        [DllImport(Lib)] internal static extern int ys_augment_mosaic_jitter(IntPtr ctx, IntPtr arena, IntPtr srcs, int nSrc, IntPtr items, int batch, int onDevice, int imgsz,
+                                                                             int maskRatio, int perspective, IntPtr jitter, IntPtr images, IntPtr masks);
+        [DllImport(Lib)] internal static extern int ys_augment_letterbox_jitter(IntPtr ctx, IntPtr arena, IntPtr srcs, int nSrc, IntPtr items, int batch, int onDevice,
+                                                                                int imgsz, int maskRatio, IntPtr jitter, IntPtr images, IntPtr masks);
+        [DllImport(Lib)] internal static extern int ys_color_jitter(IntPtr ctx, IntPtr src, IntPtr jitter, int batch, int h, int w, int onDevice, IntPtr dst, int dstIsFloat);
         // Classify task (Head.Classify / v8ClassificationLoss / Classifier.Val, Models/Classifier.cs): outputs "cls" / "logits" / "dcls" [B,nc]
         // through ys_model_get_output; one loss item (the mean) through ys_loss_read_items
         [DllImport(Lib)] internal static extern int ys_loss_classify(IntPtr model, float[] cls, int batch, int onDevice);

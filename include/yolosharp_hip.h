@@ -481,8 +481,9 @@ YS_API int ys_letterbox(ys_ctx* ctx, const void* src, int is_float, int on_devic
  * host: an item that fails those checks yields an all-114 image (zero masks) and no labels; if more rows are kept than `capacity`, *out_count holds
  * the true total (> capacity) and the rows past capacity are not written.  Nothing is truncated silently.
  * Scope: kpt_dim must be 3 (apply_keypoints reads column 2; 2 -> YS_ERR_INVALID_ARG).  Not built: OBB corner labels (xyxyxyxy2xywhr is host code in
- * the reference), RandomHSV (TorchVision.NET ColorJitter, not part of the reference tree), the `rand > p` case of Augment.Mosaic (the reference then
- * yields images of unequal sizes its own collate cannot stack).  The other no-mosaic case -- the LetterBox pipeline the reference trains on once the
+ * the reference, and the corners need OpenCV's MinAreaRect) and the `rand > p` case of Augment.Mosaic (the reference then
+ * yields images of unequal sizes its own collate cannot stack).  RandomHSV, the last transform of both chains, is the ys_aug_jitter row of the
+ * *_jitter entries further down.  The other no-mosaic case -- the LetterBox pipeline the reference trains on once the
  * mosaic is closed -- is ys_augment_letterbox / ys_augment_letterbox_labels below.  Deviations: a label-free sample is still warped (RandomPerspective.Apply returns the
  * unwarped 2s x 2s canvas, :666-669); where the reference's mask slice would run past the source mask (it throws) the kernel reads 0. */
 typedef struct ys_aug_src { int64_t img_off, mask_off; int32_t h, w, mh, mw; } ys_aug_src;
@@ -528,6 +529,40 @@ YS_API int ys_augment_letterbox_labels(ys_ctx* ctx, const ys_aug_src* srcs, int 
                                        const float* keypoints, int kpt_num, int kpt_dim, const ys_aug_item* items, int batch, int on_device,
                                        int imgsz, int flags, int capacity, float* out_batch_idx, float* out_cls, float* out_bboxes,
                                        float* out_keypoints, int32_t* out_count);
+
+/* ---- ColorJitter (RandomHSV): the last transform of both training chains (Data/YoloDataset.cs:86, :416; Data/Augment.cs:968-987):
+ * torchvision.transforms.ColorJitter(brightness 0.4, contrast 0, saturation 0.7, hue 0.015) on the uint8 image -- after RandomPerspective the image is
+ * uint8 again (:452-454, :527-529).  ClassificationDataset ends its chain with the same operator and a non-zero contrast (Data/ClassificationDataset.cs:122).
+ * TorchVision.NET's source is not part of the reference tree: the contract is torchvision's public uint8 algorithm (transforms/_functional_tensor.py),
+ * restated here; parity with TorchVision.NET is UNPINNED.  Every op ends in a uint8 image (truncation between the ops, not once at the end); the factors
+ * are fp32 (torchvision draws them as fp32 and carries them as Python doubles; 1.0 - f formed in double and rounded is 1.0f - f); every step is one
+ * separately rounded fp32 operation with correctly rounded divisions, so the output is bit-exact against an fp32 restatement (tests/color_jitter_ref.py).
+ *   blend(a, b, f) = trunc(clamp(f * a + (1 - f) * b, 0, 255));  gray = trunc((0.2989f r + 0.587f g) + 0.114f b)
+ *   op 0 brightness: blend(c, 0, f)      op 1 contrast: blend(c, mean, f), mean = the fp32 mean of gray over the image in its state at that point
+ *   op 2 saturation: blend(c, gray, f)   op 3 hue: c / 255, _rgb2hsv, h = (h + f) mod 1 (Python-style), _hsv2rgb, trunc(v * 255.999f)
+ * A row holds what ColorJitter.get_params draws for one image: order[k] = the op id run in slot k (randperm(4)), or -1 for nothing (an op whose gain is 0
+ * keeps its slot and is skipped); factor[id] is indexed by op id.  A row is valid if its ids are in {-1, 0..3} with no id twice, factors 0..2 are finite
+ * and >= 0 and the hue factor is in [-0.5, 0.5].  The draws stay on the host like every other draw of this pipeline.
+ *
+ * ys_augment_mosaic_jitter / ys_augment_letterbox_jitter: the plain entries with `jitter` [batch] rows applied to the bytes in the gather kernels'
+ * epilogue, in front of the mul(1 / 255): no extra pass over the images.  The 114 of the border / padding is jittered like every other pixel.
+ * jitter == NULL IS the plain entry (the same kernel).  The rows follow the call's on_device.  A row that runs contrast is YS_ERR_UNSUPPORTED here (the
+ * mean would need the gather twice; the reference's box tasks pass contrast 0).  Host pointers: an invalid row is YS_ERR_INVALID_ARG.  Device pointers:
+ * an invalid or contrast row yields the all-114 image, not jittered, like a refused item; masks and labels do not read the rows.
+ *
+ * ys_color_jitter: the operator on its own, all four ops, src uint8 [batch, 3, h, w] -> dst uint8 (dst_is_float = 0) or fp32 byte * (1 / 255.0f).
+ * Contrast takes two launches: a reduction replays the ops in front of it and sums gray per image with integer atomics (any order, the same sum), the
+ * apply pass forms mean = (float)sum / (float)(h * w).  For h * w <= 65536 every partial sum is an exact fp32 integer and this equals torch.mean bit
+ * for bit; above that torch's own fp32 summation order decides the last bit of its mean -- the one DEVIATION.  Invalid rows: YS_ERR_INVALID_ARG with
+ * host pointers, the all-114 image with device pointers.  src and dst must not overlap. */
+typedef struct ys_aug_jitter { int32_t order[4]; float factor[4]; } ys_aug_jitter;
+YS_API int ys_augment_mosaic_jitter(ys_ctx* ctx, const uint8_t* arena, const ys_aug_src* srcs, int n_src, const ys_aug_item* items, int batch,
+                                    int on_device, int imgsz, int mask_ratio, int perspective, const ys_aug_jitter* jitter, float* images,
+                                    float* masks);
+YS_API int ys_augment_letterbox_jitter(ys_ctx* ctx, const uint8_t* arena, const ys_aug_src* srcs, int n_src, const ys_aug_item* items, int batch,
+                                       int on_device, int imgsz, int mask_ratio, const ys_aug_jitter* jitter, float* images, float* masks);
+YS_API int ys_color_jitter(ys_ctx* ctx, const uint8_t* src, const ys_aug_jitter* jitter, int batch, int h, int w, int on_device, void* dst,
+                           int dst_is_float);
 
 /* ---- per-operator entry points (unit parity; a TorchSharp-free C# Conv wrapper) ---------------
  * Convs.Conv.forward (Convs.cs:36-62): y = act(BN(conv2d(x))) on fp32 NCHW / OIHW HOST arrays at the

@@ -17,6 +17,11 @@ dataset instead; the default, mosaic, is the above unchanged.  Its legs: augment
 plus the sources' bytes read once, over that time; torch_augment = a torch restatement of LetterBox + flips + stack + mul(1/255) (Data/Augment.cs:698-778,
 860-966) for the images; step_static / step_augmented as above with letterbox batches; and step_host = the same step through AMPWrapper.TrainStep on the
 batch's host copy (images and labels copied to the device every step): what a trainer without this branch does once the mosaic is closed.
+
+--hsv measures the ColorJitter (RandomHSV) epilogue instead, for BOTH branches, in two child processes: hsv = the image call of each branch on the same
+device-resident tables through the plain entry, through the *_jitter entry with jitter = NULL (the same kernel: these two must agree) and with one drawn
+row per image (draw_jitter(0.015, 0.7, 0.4), the reference's default); torch_hsv = a torch restatement of torchvision's uint8 ColorJitter, per image, on
+a uint8 batch [B, 3, imgsz, imgsz] that already lives on the same GPU, with the same rows -- the extra pass a host without the epilogue would run.
 """
 import argparse
 import json
@@ -33,6 +38,7 @@ if ROOT not in sys.path:
 
 LEGS = ("augment", "torch_augment", "step_static", "step_augmented")
 LETTERBOX_LEGS = LEGS + ("step_host",)
+HSV_LEGS = ("hsv", "torch_hsv")
 HBM_TBPS = 6.3
 HYP = dict(degrees=10.0, translate=0.1, scale=0.5, shear=2.0, perspective=0.0)
 
@@ -208,6 +214,98 @@ def leg_torch_augment(a):
     return {"ms_per_batch": round(ms, 4), "runs": runs, "what": "images only (canvas paste + grid_sample per image, flips, stack, mul 1/255)"}
 
 
+HSV = (0.015, 0.7, 0.4)
+
+
+def leg_hsv(a):
+    """Per branch: the image call without rows (plain entry; *_jitter entry with NULL) and with one drawn row per image."""
+    from yolosharp_amd import Engine, _lib
+    from yolosharp_amd.augment import JITTER_DTYPE, draw_jitter
+    eng = Engine(0)
+    aug, _ = _augmenter(eng, a)
+    B, S = a.batch, a.imgsz
+    lib = eng.lib
+    rows = draw_jitter(np.random.default_rng(2), B, *HSV)
+    d_rows = eng.to_device(np.ascontiguousarray(rows, JITTER_DTYPE))
+    out = {"B": B, "imgsz": S, "hsv": list(HSV)}
+    for branch in ("mosaic", "letterbox"):
+        aug.close_mosaic(branch == "letterbox")
+        aug.run(aug.draw(np.arange(B) % aug.count))                   # uploads the item table; the timed calls below reuse it on the device
+        common = (eng.ctx, aug.d_arena, aug.d_srcs, aug.count, aug.d_items, B, 1, S, aug.r)
+        if branch == "mosaic":
+            calls = {"plain": lambda: lib.ys_augment_mosaic(*common, 0, aug.d_images, None),
+                     "null_rows": lambda: lib.ys_augment_mosaic_jitter(*common, 0, None, aug.d_images, None),
+                     "jitter": lambda: lib.ys_augment_mosaic_jitter(*common, 0, d_rows, aug.d_images, None)}
+        else:
+            calls = {"plain": lambda: lib.ys_augment_letterbox(*common, aug.d_images, None),
+                     "null_rows": lambda: lib.ys_augment_letterbox_jitter(*common, None, aug.d_images, None),
+                     "jitter": lambda: lib.ys_augment_letterbox_jitter(*common, d_rows, aug.d_images, None)}
+        res = {}
+        for name, fn in calls.items():
+            ms, runs = _timed(lambda: _lib.check(lib, fn()), eng.synchronize, a)
+            res[name + "_ms"], res[name + "_runs"] = round(ms, 4), runs
+        res["jitter_extra_ms"] = round(res["jitter_ms"] - res["plain_ms"], 4)
+        out[branch] = res
+    eng.free(d_rows)
+    aug.close()
+    return out
+
+
+def leg_torch_hsv(a):
+    """torchvision's uint8 ColorJitter restated in torch (transforms/_functional_tensor.py), per image, on a device-resident uint8 batch."""
+    import torch
+    from yolosharp_amd.augment import draw_jitter
+    B, S = a.batch, a.imgsz
+    rows = draw_jitter(np.random.default_rng(2), B, *HSV)
+    batch = torch.from_numpy(np.random.default_rng(3).integers(0, 256, (B, 3, S, S), dtype=np.uint8)).cuda()
+
+    def blend(img, other, f):
+        return (f * img + (1.0 - f) * other).clamp(0, 255).to(torch.uint8)
+
+    def gray(img):
+        r, g, b = img.unbind(0)
+        return (0.2989 * r + 0.587 * g + 0.114 * b).to(torch.uint8).unsqueeze(0)
+
+    def hue(img, f):
+        x = img.to(torch.float32) / 255.0
+        r, g, b = x.unbind(0)
+        maxc, minc = x.max(0).values, x.min(0).values
+        eqc = maxc == minc
+        cr = maxc - minc
+        ones = torch.ones_like(maxc)
+        s = cr / torch.where(eqc, ones, maxc)
+        d = torch.where(eqc, ones, cr)
+        rc, gc, bc = (maxc - r) / d, (maxc - g) / d, (maxc - b) / d
+        h = (maxc == r) * (bc - gc) + ((maxc == g) & (maxc != r)) * (2.0 + rc - bc) + ((maxc != g) & (maxc != r)) * (4.0 + gc - rc)
+        h = (torch.fmod(h / 6.0 + 1.0, 1.0) + f) % 1.0
+        i = torch.floor(h * 6.0)
+        ff = h * 6.0 - i
+        i = i.to(torch.int32) % 6
+        p, q, t = (maxc * (1.0 - s)).clamp(0, 1), (maxc * (1.0 - s * ff)).clamp(0, 1), (maxc * (1.0 - s * (1.0 - ff))).clamp(0, 1)
+        mask = (i.unsqueeze(0) == torch.arange(6, device=i.device).view(-1, 1, 1)).to(torch.float32)
+        a4 = torch.stack((torch.stack((maxc, q, p, p, t, maxc)), torch.stack((t, maxc, maxc, q, p, p)), torch.stack((p, p, t, maxc, maxc, q))))
+        return torch.einsum("ijk,xijk->xjk", mask, a4).mul(255.999).to(torch.uint8)
+
+    def one(img, row):
+        for op in row["order"]:
+            f = float(row["factor"][op]) if op >= 0 else 0.0
+            if op == 0:
+                img = blend(img, torch.zeros_like(img), f)
+            elif op == 1:
+                img = blend(img, gray(img).to(torch.float32).mean(), f)
+            elif op == 2:
+                img = blend(img, gray(img), f)
+            elif op == 3:
+                img = hue(img, f)
+        return img[None].mul(1 / 255.0)
+
+    def call():
+        return torch.cat([one(batch[b], rows[b]) for b in range(B)], 0)
+
+    ms, runs = _timed(call, torch.cuda.synchronize, a)
+    return {"ms_per_batch": round(ms, 4), "runs": runs, "what": "ColorJitter per image on a resident uint8 batch, stack, mul 1/255"}
+
+
 def leg_step(a, augmented, host=False):
     from yolosharp_amd import Engine
     from yolosharp_amd.model import AMPWrapper, Yolov8, v8DetectionLoss
@@ -258,20 +356,23 @@ def main():
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--leg-timeout", type=int, default=240, help="seconds per child process")
     ap.add_argument("--branch", choices=("mosaic", "letterbox"), default="mosaic", help="the pipeline to measure (letterbox = the close-mosaic branch)")
-    ap.add_argument("--leg", choices=LETTERBOX_LEGS, help="run one measurement in this process (what the driver starts)")
+    ap.add_argument("--hsv", action="store_true", help="measure the ColorJitter epilogue of both branches and its torch restatement instead")
+    ap.add_argument("--leg", choices=LETTERBOX_LEGS + HSV_LEGS, help="run one measurement in this process (what the driver starts)")
     a = ap.parse_args()
     lb = a.branch == "letterbox"
     if a.leg:
-        out = {"augment": lambda: leg_letterbox(a) if lb else leg_augment(a), "torch_augment": lambda: leg_torch_letterbox(a) if lb else leg_torch_augment(a),
+        out = {"hsv": lambda: leg_hsv(a), "torch_hsv": lambda: leg_torch_hsv(a), "augment": lambda: leg_letterbox(a) if lb else leg_augment(a), "torch_augment": lambda: leg_torch_letterbox(a) if lb else leg_torch_augment(a),
                "step_static": lambda: leg_step(a, False), "step_augmented": lambda: leg_step(a, True), "step_host": lambda: leg_step(a, False, host=True)}[a.leg]()
         print(json.dumps(out))
         return 0
     res = {"metric": "augment_cost", "model": "yolov8n", "dtype": "bf16", "batch": a.batch, "imgsz": a.imgsz, "sources": a.sources}
-    if lb:
+    if lb and not a.hsv:
         res["branch"] = "letterbox"
+    if a.hsv:
+        res["metric"] = "color_jitter_cost"
     fwd = [x for kv in (("--batch", a.batch), ("--imgsz", a.imgsz), ("--sources", a.sources), ("--nc", a.nc), ("--steps", a.steps), ("--warmup", a.warmup),
                         ("--repeats", a.repeats), ("--branch", a.branch)) for x in (kv[0], str(kv[1]))]
-    for leg in (LETTERBOX_LEGS if lb else LEGS):
+    for leg in (HSV_LEGS if a.hsv else LETTERBOX_LEGS if lb else LEGS):
         try:
             r = subprocess.run([sys.executable, os.path.abspath(__file__), "--leg", leg] + fwd, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
                                text=True, timeout=a.leg_timeout, stdin=subprocess.DEVNULL)
@@ -282,6 +383,9 @@ def main():
             res["failed"] = {"leg": leg, "rc": r.returncode, "stderr": r.stderr[-2000:]}
             break                                   # ... or that failed
         res[leg] = json.loads(r.stdout.strip().splitlines()[-1])
+    if "hsv" in res and "torch_hsv" in res:
+        for branch in ("mosaic", "letterbox"):
+            res["torch_over_epilogue_" + branch] = round(res["torch_hsv"]["ms_per_batch"] / max(res["hsv"][branch]["jitter_extra_ms"], 1e-4), 2)
     if "augment" in res and "torch_augment" in res:
         res["torch_over_augment_images"] = round(res["torch_augment"]["ms_per_batch"] / res["augment"]["images_only_ms"], 2)
     if "step_static" in res and "step_augmented" in res:

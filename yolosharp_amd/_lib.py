@@ -46,6 +46,11 @@ class AugItem(C.Structure):
     _fields_ = [("src", C.c_int32 * 4), ("xc", C.c_int32), ("yc", C.c_int32), ("M", C.c_float * 9), ("flip_lr", C.c_int32), ("flip_ud", C.c_int32)]
 
 
+class AugJitter(C.Structure):
+    """ys_aug_jitter: the ColorJitter draws of one output image (order[k] = op id of slot k or -1; factor[id] by op id: brightness, contrast, saturation, hue)."""
+    _fields_ = [("order", C.c_int32 * 4), ("factor", C.c_float * 4)]
+
+
 class BnFwdCase(C.Structure):
     """ys_bn_fwd_case: one problem of ys_bn_train_fwd (host arrays channel-major [C][rows])."""
     _fields_ = [("y", C.c_void_p), ("gamma", C.c_void_p), ("beta", C.c_void_p), ("run_mean", C.c_void_p), ("run_var", C.c_void_p), ("nbt", C.c_void_p),
@@ -183,6 +188,11 @@ PROTOTYPES = {
     "ys_augment_letterbox": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "ys_augment_letterbox_labels": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int,
                                              C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ys_augment_mosaic_jitter": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                          C.c_void_p]),
+    "ys_augment_letterbox_jitter": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                             C.c_void_p]),
+    "ys_color_jitter": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int]),
     "ys_block_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "ys_block_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "ys_device_malloc": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]),

@@ -8,7 +8,12 @@ The close-mosaic branch -- what YoloDataset.CloseMosaic(true) builds (Data/YoloD
 same uploaded arena, tables and buffers (ys_augment_letterbox / ys_augment_letterbox_labels; MosaicAugmenter.close_mosaic).  Its items carry the
 primary index and the two flip decisions only.
 
-Not built: RandomHSV (TorchVision.NET ColorJitter), OBB corner labels, the `rand > p` case of Augment.Mosaic (it yields images of unequal sizes).
+RandomHSV (Data/Augment.cs:968-987), the last transform of both chains (Data/YoloDataset.cs:86, :416), is torchvision ColorJitter(brightness 0.4, contrast 0,
+saturation 0.7, hue 0.015) on the uint8 image: MosaicAugmenter(hsv=(0.015, 0.7, 0.4)) draws one ys_aug_jitter row per image after the flips (draw_jitter follows
+ColorJitter.get_params) and the gather kernels apply it in their epilogue (ys_augment_mosaic_jitter / ys_augment_letterbox_jitter); color_jitter() is the operator
+on its own, contrast included (ys_color_jitter).  TorchVision.NET is not in the reference tree: torchvision's public uint8 algorithm is the contract.
+
+Not built: OBB corner labels, the `rand > p` case of Augment.Mosaic (it yields images of unequal sizes).
 kpt_dim = 3 only."""
 import ctypes as C
 import math
@@ -19,7 +24,10 @@ from . import _lib
 
 SRC_DTYPE = np.dtype([("img_off", "<i8"), ("mask_off", "<i8"), ("h", "<i4"), ("w", "<i4"), ("mh", "<i4"), ("mw", "<i4")])
 ITEM_DTYPE = np.dtype([("src", "<i4", (4,)), ("xc", "<i4"), ("yc", "<i4"), ("M", "<f4", (9,)), ("flip_lr", "<i4"), ("flip_ud", "<i4")])
+JITTER_DTYPE = np.dtype([("order", "<i4", (4,)), ("factor", "<f4", (4,))])
 assert SRC_DTYPE.itemsize == C.sizeof(_lib.AugSrc) == 32 and ITEM_DTYPE.itemsize == C.sizeof(_lib.AugItem) == 68
+assert JITTER_DTYPE.itemsize == C.sizeof(_lib.AugJitter) == 32
+JITTER_BRIGHTNESS, JITTER_CONTRAST, JITTER_SATURATION, JITTER_HUE = 0, 1, 2, 3      # the op ids of ColorJitter.forward
 YS_AUG_SORT_FLIPPED = 1              # ys_augment_labels: write a flipped box as (min, max)
 YS_AUG_FLIP_KEEP_SIZE = 2            # ys_augment_letterbox_labels: a flip leaves the cxcywh box's w / h alone (the reference writes s - w)
 
@@ -112,15 +120,70 @@ def pack_labels(labels):
     return lab_off, np.ascontiguousarray(cls), np.ascontiguousarray(boxes), kp
 
 
-def augment_mosaic(engine, arena, srcs, items, imgsz, mask_ratio=4, perspective=False, with_masks=False):
-    """ys_augment_mosaic on HOST arrays: -> (images fp32 [B, 3, s, s], masks fp32 [B, s/r, s/r] or None)."""
+def make_jitter(n):
+    """n ys_aug_jitter rows that do nothing: every slot -1, factors (1, 1, 1, 0)."""
+    rows = np.zeros((n,), JITTER_DTYPE)
+    rows["order"] = -1
+    rows["factor"] = (1.0, 1.0, 1.0, 0.0)
+    return rows
+
+
+def check_jitter(rows, allow_contrast=False):
+    """The library's row check (include/yolosharp_hip.h) on the host: ValueError for an invalid row, and for a contrast row where none is allowed."""
+    rows = np.ascontiguousarray(rows, JITTER_DTYPE)
+    for b, (order, factor) in enumerate(zip(rows["order"], rows["factor"])):
+        ids = [int(i) for i in order if i != -1]
+        if any(i < 0 or i > 3 for i in ids) or len(set(ids)) != len(ids):
+            raise ValueError("jitter row %d: order %s must hold ids in {-1, 0..3}, none twice" % (b, order.tolist()))
+        if not (np.all(np.isfinite(factor[:3])) and np.all(factor[:3] >= 0) and -0.5 <= factor[3] <= 0.5):
+            raise ValueError("jitter row %d: factors %s: brightness, contrast, saturation finite and >= 0, hue in [-0.5, 0.5]" % (b, factor.tolist()))
+        if JITTER_CONTRAST in ids and not allow_contrast:
+            raise ValueError("jitter row %d runs contrast: the fused entries have no image mean (color_jitter does)" % b)
+    return rows
+
+
+def draw_jitter(rng, n, hgain, sgain, vgain, cgain=0.0):
+    """n rows as torchvision ColorJitter.get_params draws them for ColorJitter(brightness=vgain, contrast=cgain, saturation=sgain, hue=hgain) -- RandomHSV's
+    argument order (Data/Augment.cs:968-987).  Per image: randperm(4) first (rng.permutation), then brightness U(max(0, 1 - v), 1 + v), contrast, saturation
+    likewise and hue U(-h, h), one rng.random() each, drawn ONLY for a non-zero gain.  An op with gain 0 keeps its slot of the permutation as -1."""
+    gains = (float(vgain), float(cgain), float(sgain), float(hgain))
+    assert all(g >= 0 for g in gains) and gains[3] <= 0.5, gains
+    rows = make_jitter(n)
+    for b in range(n):
+        perm = rng.permutation(4)
+        for op in range(4):
+            if gains[op] > 0:
+                lo, hi = (-gains[op], gains[op]) if op == JITTER_HUE else (max(0.0, 1.0 - gains[op]), 1.0 + gains[op])
+                rows[b]["factor"][op] = lo + (hi - lo) * rng.random()
+        rows[b]["order"] = [int(op) if gains[op] > 0 else -1 for op in perm]
+    return rows
+
+
+def color_jitter(engine, images_u8, rows, out_float=False):
+    """ys_color_jitter on HOST arrays: uint8 [B, 3, h, w] through the rows' ops (all four) -> uint8, or fp32 byte * (1 / 255.0f) with out_float."""
+    img = np.ascontiguousarray(images_u8, np.uint8)
+    rows = np.ascontiguousarray(rows, JITTER_DTYPE)
+    assert img.ndim == 4 and img.shape[1] == 3 and rows.shape == (img.shape[0],), (img.shape, rows.shape)
+    out = np.empty(img.shape, np.float32 if out_float else np.uint8)
+    _lib.check(engine.lib, engine.lib.ys_color_jitter(engine.ctx, _ptr(img), _ptr(rows), img.shape[0], img.shape[2], img.shape[3], 0, _ptr(out), int(bool(out_float))))
+    return out
+
+
+def augment_mosaic(engine, arena, srcs, items, imgsz, mask_ratio=4, perspective=False, with_masks=False, jitter=None):
+    """ys_augment_mosaic (jitter rows given: ys_augment_mosaic_jitter) on HOST arrays: -> (images fp32 [B, 3, s, s], masks fp32 [B, s/r, s/r] or None)."""
     arena = np.ascontiguousarray(arena, np.uint8)
     srcs, items = np.ascontiguousarray(srcs, SRC_DTYPE), np.ascontiguousarray(items, ITEM_DTYPE)
     B, s = items.shape[0], int(imgsz)
     images = np.empty((B, 3, max(s, 0), max(s, 0)), np.float32)
     masks = np.empty((B, s // mask_ratio, s // mask_ratio), np.float32) if with_masks else None
-    _lib.check(engine.lib, engine.lib.ys_augment_mosaic(engine.ctx, _ptr(arena), _ptr(srcs), srcs.shape[0], _ptr(items), B, 0, s, int(mask_ratio),
-                                                        int(bool(perspective)), _ptr(images), _ptr(masks)))
+    if jitter is None:
+        _lib.check(engine.lib, engine.lib.ys_augment_mosaic(engine.ctx, _ptr(arena), _ptr(srcs), srcs.shape[0], _ptr(items), B, 0, s, int(mask_ratio),
+                                                            int(bool(perspective)), _ptr(images), _ptr(masks)))
+    else:
+        jitter = np.ascontiguousarray(jitter, JITTER_DTYPE)
+        assert jitter.shape == (B,), jitter.shape
+        _lib.check(engine.lib, engine.lib.ys_augment_mosaic_jitter(engine.ctx, _ptr(arena), _ptr(srcs), srcs.shape[0], _ptr(items), B, 0, s, int(mask_ratio),
+                                                                   int(bool(perspective)), _ptr(jitter), _ptr(images), _ptr(masks)))
     return images, masks
 
 
@@ -143,15 +206,22 @@ def augment_labels(engine, srcs, lab_off, cls, boxes, keypoints, items, imgsz, p
     return out
 
 
-def augment_letterbox(engine, arena, srcs, items, imgsz, mask_ratio=4, with_masks=False):
-    """ys_augment_letterbox on HOST arrays: -> (images fp32 [B, 3, s, s], masks fp32 [B, s/r, s/r] or None).  Reads src[0] and the flips of an item."""
+def augment_letterbox(engine, arena, srcs, items, imgsz, mask_ratio=4, with_masks=False, jitter=None):
+    """ys_augment_letterbox (jitter rows given: ys_augment_letterbox_jitter) on HOST arrays: -> (images fp32 [B, 3, s, s], masks fp32 [B, s/r, s/r] or None).
+    Reads src[0] and the flips of an item."""
     arena = np.ascontiguousarray(arena, np.uint8)
     srcs, items = np.ascontiguousarray(srcs, SRC_DTYPE), np.ascontiguousarray(items, ITEM_DTYPE)
     B, s = items.shape[0], int(imgsz)
     images = np.empty((B, 3, max(s, 0), max(s, 0)), np.float32)
     masks = np.empty((B, s // mask_ratio, s // mask_ratio), np.float32) if with_masks else None
-    _lib.check(engine.lib, engine.lib.ys_augment_letterbox(engine.ctx, _ptr(arena), _ptr(srcs), srcs.shape[0], _ptr(items), B, 0, s, int(mask_ratio),
-                                                           _ptr(images), _ptr(masks)))
+    if jitter is None:
+        _lib.check(engine.lib, engine.lib.ys_augment_letterbox(engine.ctx, _ptr(arena), _ptr(srcs), srcs.shape[0], _ptr(items), B, 0, s, int(mask_ratio),
+                                                               _ptr(images), _ptr(masks)))
+    else:
+        jitter = np.ascontiguousarray(jitter, JITTER_DTYPE)
+        assert jitter.shape == (B,), jitter.shape
+        _lib.check(engine.lib, engine.lib.ys_augment_letterbox_jitter(engine.ctx, _ptr(arena), _ptr(srcs), srcs.shape[0], _ptr(items), B, 0, s, int(mask_ratio),
+                                                                      _ptr(jitter), _ptr(images), _ptr(masks)))
     return images, masks
 
 
@@ -176,22 +246,28 @@ def augment_letterbox_labels(engine, srcs, lab_off, cls, boxes, keypoints, items
     return out
 
 
-def draw_letterbox_items(rng, indices, fliplr=0.5, flipud=0.0):
+def draw_letterbox_items(rng, indices, fliplr=0.5, flipud=0.0, hsv=None):
     """The item table of one close-mosaic batch: per primary index only what FlipLR, then FlipUD draw (`rand > p -> skip`, each drawn only when its
-    p > 0: YoloDataset.cs:406-415); LetterBox draws nothing.  The other fields stay zero (src[1..3] = 0: valid, unread)."""
+    p > 0: YoloDataset.cs:406-415); LetterBox draws nothing.  The other fields stay zero (src[1..3] = 0: valid, unread).
+    hsv = (hgain, sgain, vgain): RandomHSV follows the flips (:416) -- per image one draw_jitter row after the two flip draws; -> (items, rows)."""
     items = make_items(len(indices))
+    rows = make_jitter(len(indices)) if hsv is not None else None
     for b, idx in enumerate(indices):
         flr = fliplr > 0 and not (rng.random() > fliplr)
         fud = flipud > 0 and not (rng.random() > flipud)
         items[b]["src"][0], items[b]["flip_lr"], items[b]["flip_ud"] = int(idx), int(flr), int(fud)
-    return items
+        if hsv is not None:
+            rows[b] = draw_jitter(rng, 1, *hsv)[0]
+    return items if hsv is None else (items, rows)
 
 
-def draw_items(rng, indices, s, count, hyp, fliplr=0.5, flipud=0.0):
+def draw_items(rng, indices, s, count, hyp, fliplr=0.5, flipud=0.0, hsv=None):
     """The item table of one batch: per primary index of `indices`, in the reference's per-image order, the three mixed indices as
     randint(0, count - 1) (:155), yc, then xc, in [s/2, 3s/2) (:163-164), the eight uniforms of the matrix, FlipLR then FlipUD as `rand > p -> skip`
-    (drawn only when p > 0).  hyp: degrees / translate / scale / shear / perspective.  The matrices are built for the whole batch at once."""
+    (drawn only when p > 0).  hyp: degrees / translate / scale / shear / perspective.  The matrices are built for the whole batch at once.
+    hsv = (hgain, sgain, vgain): RandomHSV follows the flips (YoloDataset.cs:86) -- per image one draw_jitter row after the two flip draws; -> (items, rows)."""
     items = make_items(len(indices))
+    rows = make_jitter(len(indices)) if hsv is not None else None
     u = np.empty((len(indices), 8), np.float64)
     for b, idx in enumerate(indices):
         mix = rng.integers(0, count - 1, size=3)
@@ -201,8 +277,10 @@ def draw_items(rng, indices, s, count, hyp, fliplr=0.5, flipud=0.0):
         flr = fliplr > 0 and not (rng.random() > fliplr)
         fud = flipud > 0 and not (rng.random() > flipud)
         items[b] = ((int(idx), int(mix[0]), int(mix[1]), int(mix[2])), xc, yc, 0.0, int(flr), int(fud))
+        if hsv is not None:
+            rows[b] = draw_jitter(rng, 1, *hsv)[0]
     items["M"] = perspective_matrices(u, s, **hyp).reshape(-1, 9)
-    return items
+    return items if hsv is None else (items, rows)
 
 
 class DeviceBatch:
@@ -244,11 +322,16 @@ class MosaicAugmenter:
     close_mosaic(True) switches to the reference's closed pipeline (YoloDataset.CloseMosaic): LetterBox + FlipLR / FlipUD of the primary image alone, on the
     same buffers; per image it draws the two flip uniforms only.  `mode` names the branch the next batch comes from.  Of `flags`, the Mosaic branch takes
     YS_AUG_SORT_FLIPPED and the LetterBox branch YS_AUG_FLIP_KEEP_SIZE; each ignores the other's (ys_augment_labels refuses flags it does not know, so
-    the LetterBox flag is not handed to it)."""
+    the LetterBox flag is not handed to it).
+    hsv = (hgain, sgain, vgain) -- the reference's default is (0.015, 0.7, 0.4) -- adds RandomHSV to both branches: draw() then returns (items, rows) with
+    one ColorJitter row per image, drawn after the image's two flip draws (draw_jitter), run(items, rows) uploads the rows beside the item table and calls the
+    *_jitter entries.  hsv = None (the default) draws nothing more and calls the plain entries."""
 
     def __init__(self, engine, images_u8, labels, imgsz, masks=None, mask_ratio=4, degrees=0.0, translate=0.1, scale=0.5, shear=0.0, perspective=0.0,
-                 fliplr=0.5, flipud=0.0, seed=0, flags=0, max_batch=64):
+                 fliplr=0.5, flipud=0.0, seed=0, flags=0, max_batch=64, hsv=None):
         assert len(images_u8) == len(labels) and len(images_u8) >= 2
+        self.hsv = tuple(float(g) for g in hsv) if hsv is not None else None
+        assert self.hsv is None or len(self.hsv) == 3
         self.engine, self.s, self.r, self.flags = engine, int(imgsz), int(mask_ratio), int(flags)
         self.hyp = dict(degrees=degrees, translate=translate, scale=scale, shear=shear, perspective=perspective)
         self.fliplr, self.flipud = float(fliplr), float(flipud)
@@ -269,6 +352,7 @@ class MosaicAugmenter:
         self.capacity = self.max_per_image * self.max_batch                                 # no batch can exceed it
         s, cap, B = self.s, self.capacity, self.max_batch
         self.d_items = e.malloc(B * ITEM_DTYPE.itemsize)
+        self.d_jitter = e.malloc(B * JITTER_DTYPE.itemsize) if self.hsv is not None else None
         self.d_images = e.malloc(B * 3 * s * s * 4)
         self.d_masks = e.malloc(B * (s // self.r) ** 2 * 4) if self.with_masks else None
         self.d_bidx, self.d_ocls, self.d_obox, self.d_cnt = e.malloc(cap * 4), e.malloc(cap * 4), e.malloc(cap * 16), e.malloc(4)
@@ -276,28 +360,43 @@ class MosaicAugmenter:
 
     def close(self):
         e = self.engine
-        for p in self._static + [self.d_kp, self.d_items, self.d_images, self.d_masks, self.d_bidx, self.d_ocls, self.d_obox, self.d_cnt, self.d_okp]:
+        for p in self._static + [self.d_kp, self.d_items, self.d_jitter, self.d_images, self.d_masks, self.d_bidx, self.d_ocls, self.d_obox, self.d_cnt, self.d_okp]:
             if p is not None:
                 e.free(p)
         self._static = []
-        self.d_kp = self.d_items = self.d_images = self.d_masks = self.d_bidx = self.d_ocls = self.d_obox = self.d_cnt = self.d_okp = None
+        self.d_kp = self.d_items = self.d_jitter = self.d_images = self.d_masks = self.d_bidx = self.d_ocls = self.d_obox = self.d_cnt = self.d_okp = None
 
     def close_mosaic(self, closed):
         """YoloDataset.CloseMosaic(closed): True = the LetterBox pipeline from the next batch on, False = back to Mosaic + RandomPerspective."""
         self.mode = "letterbox" if closed else "mosaic"
 
     def draw(self, indices):
-        """The item table for the primary dataset indices `indices` (what the data loader's shuffler hands to GetTensor)."""
+        """The item table for the primary dataset indices `indices` (what the data loader's shuffler hands to GetTensor); with hsv: (items, jitter rows)."""
         if self.mode == "letterbox":
-            return draw_letterbox_items(self.rng, indices, self.fliplr, self.flipud)
-        return draw_items(self.rng, indices, self.s, self.count, self.hyp, self.fliplr, self.flipud)
+            return draw_letterbox_items(self.rng, indices, self.fliplr, self.flipud, self.hsv)
+        return draw_items(self.rng, indices, self.s, self.count, self.hyp, self.fliplr, self.flipud, self.hsv)
 
-    def _run_letterbox(self, items):
+    def _upload_jitter(self, jitter, B):
+        """Validate the rows on the host (the device cannot refuse them aloud) and upload them beside the item table."""
+        e = self.engine
+        jitter = check_jitter(jitter)
+        if jitter.shape != (B,):
+            raise ValueError("%d jitter rows for %d items" % (jitter.shape[0], B))
+        if self.d_jitter is None:
+            self.d_jitter = e.malloc(self.max_batch * JITTER_DTYPE.itemsize)
+        _lib.check(e.lib, e.lib.ys_memcpy_h2d(e.ctx, self.d_jitter, _ptr(jitter), jitter.nbytes))
+        return self.d_jitter
+
+    def _run_letterbox(self, items, jitter=None):
         e, lib, B = self.engine, self.engine.lib, int(items.shape[0])
         if items["src"][:, 0].min() < 0 or items["src"][:, 0].max() >= self.count:
             raise ValueError("item source index outside [0, %d)" % self.count)
         _lib.check(lib, lib.ys_memcpy_h2d(e.ctx, self.d_items, _ptr(items), items.nbytes))
-        _lib.check(lib, lib.ys_augment_letterbox(e.ctx, self.d_arena, self.d_srcs, self.count, self.d_items, B, 1, self.s, self.r, self.d_images, self.d_masks))
+        if jitter is None:
+            _lib.check(lib, lib.ys_augment_letterbox(e.ctx, self.d_arena, self.d_srcs, self.count, self.d_items, B, 1, self.s, self.r, self.d_images, self.d_masks))
+        else:
+            _lib.check(lib, lib.ys_augment_letterbox_jitter(e.ctx, self.d_arena, self.d_srcs, self.count, self.d_items, B, 1, self.s, self.r,
+                                                            self._upload_jitter(jitter, B), self.d_images, self.d_masks))
         _lib.check(lib, lib.ys_augment_letterbox_labels(e.ctx, self.d_srcs, self.count, self.d_lab_off, self.d_cls, self.d_boxes, self.d_kp, self.K, 3, self.d_items,
                                                         B, 1, self.s, self.flags, self.capacity, self.d_bidx, self.d_ocls, self.d_obox,
                                                         self.d_okp, self.d_cnt))
@@ -305,18 +404,23 @@ class MosaicAugmenter:
         return DeviceBatch(e, B, self.s, self.capacity, self.d_images, self.d_bidx, self.d_ocls, self.d_obox, self.d_cnt, masks=self.d_masks,
                            keypoints=self.d_okp, kpt_num=self.K, mask_ratio=self.r, n_input=n_input, max_per_image=self.max_per_image, mode="letterbox")
 
-    def run(self, items):
-        """Upload `items` and launch the kernels of the current branch (`mode`) on the engine's stream (asynchronous) -> DeviceBatch."""
+    def run(self, items, jitter=None):
+        """Upload `items` (and the ColorJitter rows `jitter`, one per item; None = no jitter) and launch the kernels of the current branch (`mode`) on the
+        engine's stream (asynchronous) -> DeviceBatch."""
         e, lib, B = self.engine, self.engine.lib, int(items.shape[0])
         assert 0 < B <= self.max_batch
         items = np.ascontiguousarray(items, ITEM_DTYPE)
         if self.mode == "letterbox":
-            return self._run_letterbox(items)
+            return self._run_letterbox(items, jitter)
         if items["src"].min() < 0 or items["src"].max() >= self.count:      # ys_augment_labels has no source count to check device items against
             raise ValueError("item source index outside [0, %d)" % self.count)
         persp = int(self.hyp["perspective"] > 0)
         _lib.check(lib, lib.ys_memcpy_h2d(e.ctx, self.d_items, _ptr(items), items.nbytes))
-        _lib.check(lib, lib.ys_augment_mosaic(e.ctx, self.d_arena, self.d_srcs, self.count, self.d_items, B, 1, self.s, self.r, persp, self.d_images, self.d_masks))
+        if jitter is None:
+            _lib.check(lib, lib.ys_augment_mosaic(e.ctx, self.d_arena, self.d_srcs, self.count, self.d_items, B, 1, self.s, self.r, persp, self.d_images, self.d_masks))
+        else:
+            _lib.check(lib, lib.ys_augment_mosaic_jitter(e.ctx, self.d_arena, self.d_srcs, self.count, self.d_items, B, 1, self.s, self.r, persp,
+                                                         self._upload_jitter(jitter, B), self.d_images, self.d_masks))
         _lib.check(lib, lib.ys_augment_labels(e.ctx, self.d_srcs, self.d_lab_off, self.d_cls, self.d_boxes, self.d_kp, self.K, 3, self.d_items, B, 1, self.s, persp,
                                               self.flags & ~YS_AUG_FLIP_KEEP_SIZE, self.capacity, self.d_bidx, self.d_ocls, self.d_obox, self.d_okp, self.d_cnt))
         n_input = int(sum(int(self.lab_off[k + 1] - self.lab_off[k]) for k in items["src"].reshape(-1)))
@@ -324,7 +428,8 @@ class MosaicAugmenter:
                            keypoints=self.d_okp, kpt_num=self.K, mask_ratio=self.r, n_input=n_input, max_per_image=self.max_per_image)
 
     def batch(self, indices):
-        return self.run(self.draw(indices))
+        drawn = self.draw(indices)
+        return self.run(*drawn) if self.hsv is not None else self.run(drawn)
 
     def batches(self, batch_size, shuffle=True, drop_last=True):
         """One epoch: the primary indices in (shuffled) order, `batch_size` at a time."""

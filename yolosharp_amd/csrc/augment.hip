@@ -1,5 +1,5 @@
 // augment.hip -- the training input on the device: Mosaic4 + RandomPerspective + FlipLR / FlipUD + Normalize + collate
-// of the reference's default training pipeline (ImageProcessType.Mosiac, Data/YoloDataset.cs:57-151) as three kernels.
+// of the reference's default training pipeline (ImageProcessType.Mosiac, Data/YoloDataset.cs:57-151) as three kernels; RandomHSV (:86) as their epilogue.
 //
 //   aug_prep_kernel          one thread per output image: the four tile rectangles of Augment.Mosaic._mosaic4 (Data/Augment.cs:184-203,
 //                            mask rectangles :207-209) and the inverse of the forward matrix, in double (the reference inverts in fp32 with
@@ -25,7 +25,7 @@
 // stream, about 5x above the HBM estimate of its bytes (DESIGN.md "Training input on the device").
 //
 // Scope (include/yolosharp_hip.h lists the same): kpt_dim = 3 only (apply_keypoints reads column 2); no OBB corner labels (xyxyxyxy2xywhr is host
-// code in the reference); no RandomHSV (TorchVision.NET ColorJitter, not in the reference tree); of the no-mosaic branches the close-mosaic one (LetterBox) is built below,
+// code in the reference); RandomHSV (torchvision ColorJitter on the bytes) runs in the epilogue of the two image kernels, see "ColorJitter" below; of the no-mosaic branches the close-mosaic one (LetterBox) is built below,
 // the `rand > p` one of Augment.Mosaic is not (it yields images of unequal sizes).  Deviations: a label-free
 // sample is still warped (RandomPerspective.Apply returns the unwarped canvas, :666-669); where the reference's mask slice would run past the
 // source mask (it throws) the kernel reads 0.
@@ -185,8 +185,97 @@ __device__ __forceinline__ void aug_canvas_fetch(const unsigned char* __restrict
   }
 }
 
-// one output pixel (logical coordinates after the flips): three channels as fp32 in [0, 1]
-struct AugPx { float c0, c1, c2; };
+// ---------------------------------------------------------------------------------------------------------------- ColorJitter (RandomHSV)
+// RandomHSV (Data/Augment.cs:968-987) is torchvision ColorJitter(brightness 0.4, contrast 0, saturation 0.7, hue 0.015) on the uint8 image, the last
+// transform of both training chains (Data/YoloDataset.cs:86, :416).  TorchVision.NET is not part of the reference tree: what is restated here is
+// torchvision's public uint8 algorithm (transforms/_functional_tensor.py: _blend, rgb_to_grayscale, adjust_hue, _rgb2hsv, _hsv2rgb,
+// convert_image_dtype); parity with TorchVision.NET is UNPINNED.  Every op ends in a byte (truncation BETWEEN the ops), every step is one rounded fp32
+// operation (this file is compiled without contraction), hipcc's fp32 division is correctly rounded: the result is bit-exact against an fp32
+// restatement (tests/color_jitter_ref.py).
+//   blend(a, b, f) = trunc(clamp(f * a + (1 - f) * b, 0, 255)); 1.0 - f is formed in double there and then rounded: for an fp32 f that IS 1.0f - f
+//   gray = trunc((0.2989f r + 0.587f g) + 0.114f b)
+//   op 0 brightness blend(c, 0, f) | op 1 contrast blend(c, mean of gray over the image, f) | op 2 saturation blend(c, gray, f) | op 3 hue (below)
+// A row is per image, so the order and the factors are wave-uniform: scalar loads, one uniform branch per slot.  The slots are the OUTER loop and a
+// thread's four pixels the inner, unrolled one: each op's code exists once per pixel, and the four independent chains hide the latency of the
+// divisions (hue: 3 by 255, 4 in rgb2hsv, 1 by 6 per pixel, each ~10 VALU instructions with one quarter-rate v_rcp_f32).
+struct AugPx { float c0, c1, c2; };                       // one pixel: three bytes as fp32 (whole numbers), or the final [0, 1] values
+
+// 0 = invalid, 1 = valid, 2 = valid and runs contrast (ids in {-1, 0..3}, none twice; factors 0..2 finite and >= 0; hue in [-0.5, 0.5])
+__host__ __device__ inline int aug_jitter_state(const ys_aug_jitter& J) {
+  int seen = 0;
+  for (int k = 0; k < 4; k++) {
+    const int id = J.order[k];
+    if (id == -1) continue;
+    if (id < 0 || id > 3 || ((seen >> id) & 1)) return 0;
+    seen |= 1 << id;
+  }
+  for (int k = 0; k < 3; k++)
+    if (!(J.factor[k] >= 0.0f && J.factor[k] <= 3.402823466e38f)) return 0;
+  if (!(J.factor[3] >= -0.5f && J.factor[3] <= 0.5f)) return 0;
+  return (seen & 2) ? 2 : 1;
+}
+
+__device__ __forceinline__ float aug_jit_blend(float a, float b, float f, float g) {
+  const float v = f * a + g * b;
+  return truncf(fminf(fmaxf(v, 0.0f), 255.0f));
+}
+
+__device__ __forceinline__ float aug_jit_gray(const AugPx& p) { return truncf((0.2989f * p.c0 + 0.587f * p.c1) + 0.114f * p.c2); }
+
+// adjust_hue on a byte pixel: / 255, _rgb2hsv, (h + f) mod 1, _hsv2rgb, trunc(v * 255.999f).  Selects where torchvision multiplies by masks: the terms
+// it masks out are finite, so they add +-0 and the sum is the selected term.  fmod(x, 1) = x - trunc(x) (exact below 2^23).
+__device__ __forceinline__ void aug_jit_hue(float f, AugPx& px) {
+  const float r = px.c0 / 255.0f, g = px.c1 / 255.0f, b = px.c2 / 255.0f;
+  const float maxc = fmaxf(fmaxf(r, g), b), minc = fminf(fminf(r, g), b);
+  const bool eqc = maxc == minc;
+  const float cr = maxc - minc;
+  const float s = cr / (eqc ? 1.0f : maxc);
+  const float d = eqc ? 1.0f : cr;
+  const float rc = (maxc - r) / d, gc = (maxc - g) / d, bc = (maxc - b) / d;
+  float h = maxc == r ? bc - gc : (maxc == g ? (2.0f + rc) - bc : (4.0f + gc) - rc);
+  h = h / 6.0f + 1.0f;                                     // in [5/6, 11/6]
+  h = h - truncf(h);                                       // fmod(.., 1)
+  h = h + f;
+  h = h - truncf(h);                                       // the Python-style remainder: fmod, then + 1 where the result is negative
+  h = h < 0.0f ? h + 1.0f : h;                             // (can round to exactly 1: i = 6 below)
+  const float h6 = h * 6.0f, fi = floorf(h6), ff = h6 - fi;
+  int i = (int)fi;
+  i = i >= 6 ? i - 6 : i;
+  const float v = maxc;
+  const float p = fminf(fmaxf(v * (1.0f - s), 0.0f), 1.0f);
+  const float q = fminf(fmaxf(v * (1.0f - s * ff), 0.0f), 1.0f);
+  const float t = fminf(fmaxf(v * (1.0f - (s * (1.0f - ff))), 0.0f), 1.0f);
+  const float R = i == 0 ? v : (i == 1 ? q : (i == 2 ? p : (i == 3 ? p : (i == 4 ? t : v))));
+  const float G = i == 0 ? t : (i == 1 ? v : (i == 2 ? v : (i == 3 ? q : p)));
+  const float B = i == 0 ? p : (i == 1 ? p : (i == 2 ? t : (i == 3 ? v : (i == 4 ? v : q))));
+  px.c0 = truncf(R * 255.999f); px.c1 = truncf(G * 255.999f); px.c2 = truncf(B * 255.999f);   // convert_image_dtype: max + 1 - 1e-3, truncated
+}
+
+// the ops of one VALID row on a thread's four pixels, in the row's order; until_contrast: stop in front of op 1 (the reduction's replay)
+__device__ __forceinline__ void aug_jitter_quad(const ys_aug_jitter* __restrict__ J, float mean, bool until_contrast, AugPx& p0, AugPx& p1, AugPx& p2,
+                                                AugPx& p3) {
+#pragma unroll 1
+  for (int k = 0; k < 4; k++) {
+    const int id = J->order[k];                            // wave-uniform
+    if (id < 0) continue;
+    if (id == 1 && until_contrast) break;
+    const float f = J->factor[id];
+    if (id == 3) {
+      aug_jit_hue(f, p0); aug_jit_hue(f, p1); aug_jit_hue(f, p2); aug_jit_hue(f, p3);
+    } else {
+      const float g = 1.0f - f;
+      float o0 = 0.0f, o1 = 0.0f, o2 = 0.0f, o3 = 0.0f;
+      if (id == 2) { o0 = aug_jit_gray(p0); o1 = aug_jit_gray(p1); o2 = aug_jit_gray(p2); o3 = aug_jit_gray(p3); }
+      else if (id == 1) { o0 = mean; o1 = mean; o2 = mean; o3 = mean; }
+      p0.c0 = aug_jit_blend(p0.c0, o0, f, g); p0.c1 = aug_jit_blend(p0.c1, o0, f, g); p0.c2 = aug_jit_blend(p0.c2, o0, f, g);
+      p1.c0 = aug_jit_blend(p1.c0, o1, f, g); p1.c1 = aug_jit_blend(p1.c1, o1, f, g); p1.c2 = aug_jit_blend(p1.c2, o1, f, g);
+      p2.c0 = aug_jit_blend(p2.c0, o2, f, g); p2.c1 = aug_jit_blend(p2.c1, o2, f, g); p2.c2 = aug_jit_blend(p2.c2, o2, f, g);
+      p3.c0 = aug_jit_blend(p3.c0, o3, f, g); p3.c1 = aug_jit_blend(p3.c1, o3, f, g); p3.c2 = aug_jit_blend(p3.c2, o3, f, g);
+    }
+  }
+}
+
+// one output pixel (logical coordinates after the flips): three channels as bytes in fp32
 __device__ __forceinline__ AugPx aug_pixel(const unsigned char* __restrict__ arena, AUG_T4_PARAMS, const double* __restrict__ inv, int perspective, int in,
                                            bool live, int lx, int ly) {
   float b0 = 114.0f, b1 = 114.0f, b2 = 114.0f;
@@ -205,16 +294,20 @@ __device__ __forceinline__ AugPx aug_pixel(const unsigned char* __restrict__ are
     b1 = aug_blend_u8(nw[1], ne[1], sw[1], se[1], wx, wy);
     b2 = aug_blend_u8(nw[2], ne[2], sw[2], se[2], wx, wy);
   }
-  const float q = 1 / 255.0f;                             // mul(1 / 255.0f), YoloDataset.cs:140: a multiply, bit-exact per byte
-  AugPx r; r.c0 = b0 * q; r.c1 = b1 * q; r.c2 = b2 * q;
+  AugPx r; r.c0 = b0; r.c1 = b1; r.c2 = b2;
   return r;
 }
 
 // one thread: 4 consecutive x of one output row, three channels -> three 16-byte stores (vec: s % 4 == 0, rows 16-byte aligned)
 __global__ void __launch_bounds__(AUG_T)
-aug_mosaic_warp_kernel(const unsigned char* __restrict__ arena, const AugParams* __restrict__ params, int s, int perspective, int vec,
-                       float* __restrict__ images) {
+aug_mosaic_warp_kernel(const unsigned char* __restrict__ arena, const AugParams* __restrict__ params, const ys_aug_jitter* __restrict__ jitter, int s,
+                       int perspective, int vec, float* __restrict__ images) {
   const AugParams& P = params[blockIdx.z];
+  // the image's jitter row (wave-uniform; NULL = none).  A row that is invalid or asks for contrast (the mean needs the whole image first) refuses
+  // the image like a refused item: all 114, not jittered
+  const ys_aug_jitter* __restrict__ J = jitter ? jitter + blockIdx.z : nullptr;
+  const int jstate = J ? aug_jitter_state(*J) : 1;
+  const bool refused = jstate != 1;
   const int qpr = (s + 3) >> 2;
   const unsigned i = blockIdx.x * AUG_T + threadIdx.x;
   if (i >= (unsigned)qpr * (unsigned)s) return;
@@ -227,10 +320,13 @@ aug_mosaic_warp_kernel(const unsigned char* __restrict__ arena, const AugParams*
   // the flips are folded into the output coordinate: out[y][x] = warped[ly][lx]
   const int ly = P.flip_ud ? s - 1 - y : y;
   const int lx0 = P.flip_lr ? s - 1 - x0 : x0, dx = P.flip_lr ? -1 : 1;
-  const AugPx p0 = aug_pixel(arena, AUG_T4_ARGS, inv, perspective, in, x0 < s, lx0, ly);
-  const AugPx p1 = aug_pixel(arena, AUG_T4_ARGS, inv, perspective, in, x0 + 1 < s, lx0 + dx, ly);
-  const AugPx p2 = aug_pixel(arena, AUG_T4_ARGS, inv, perspective, in, x0 + 2 < s, lx0 + 2 * dx, ly);
-  const AugPx p3 = aug_pixel(arena, AUG_T4_ARGS, inv, perspective, in, x0 + 3 < s, lx0 + 3 * dx, ly);
+  AugPx p0 = aug_pixel(arena, AUG_T4_ARGS, inv, perspective, in, !refused && x0 < s, lx0, ly);
+  AugPx p1 = aug_pixel(arena, AUG_T4_ARGS, inv, perspective, in, !refused && x0 + 1 < s, lx0 + dx, ly);
+  AugPx p2 = aug_pixel(arena, AUG_T4_ARGS, inv, perspective, in, !refused && x0 + 2 < s, lx0 + 2 * dx, ly);
+  AugPx p3 = aug_pixel(arena, AUG_T4_ARGS, inv, perspective, in, !refused && x0 + 3 < s, lx0 + 3 * dx, ly);
+  if (J && !refused) aug_jitter_quad(J, 0.0f, false, p0, p1, p2, p3);
+  const float q = 1 / 255.0f;                             // mul(1 / 255.0f), YoloDataset.cs:140: a multiply, bit-exact per byte
+  p0.c0 *= q; p0.c1 *= q; p0.c2 *= q; p1.c0 *= q; p1.c1 *= q; p1.c2 *= q; p2.c0 *= q; p2.c1 *= q; p2.c2 *= q; p3.c0 *= q; p3.c1 *= q; p3.c2 *= q;
   const long long plane = (long long)s * s;
   float* dst = images + (long long)blockIdx.z * 3 * plane + (long long)y * s + x0;
   if (vec) {
@@ -479,14 +575,16 @@ __host__ __device__ inline int aug_letterbox_src(const ys_aug_item& it, const ys
 template <int C>
 __global__ void __launch_bounds__(AUG_T)
 aug_letterbox_kernel(const unsigned char* __restrict__ arena, const ys_aug_src* __restrict__ srcs, int n_src, const ys_aug_item* __restrict__ items,
-                     int s, int vec, float* __restrict__ out) {
+                     const ys_aug_jitter* __restrict__ jitter, int s, int vec, float* __restrict__ out) {
   const int qpr = (s + 3) >> 2;
   const unsigned i = blockIdx.x * AUG_T + threadIdx.x;
   if (i >= (unsigned)qpr * (unsigned)s) return;
   const int y = (int)(i / (unsigned)qpr), x0 = (int)(i - (unsigned)y * (unsigned)qpr) * 4;
   // wave-uniform: the item, its source and the window
   const ys_aug_item& it = items[blockIdx.z];
-  const int k = aug_letterbox_src(it, srcs, n_src);
+  // the image's jitter row (C == 3 only; NULL = none): an invalid row or one that asks for contrast refuses the image like a source outside the table
+  const ys_aug_jitter* __restrict__ J = (C == 3 && jitter) ? jitter + blockIdx.z : nullptr;
+  const int k = (J && aug_jitter_state(*J) != 1) ? -1 : aug_letterbox_src(it, srcs, n_src);
   int h = 0, w = 0;
   long long off = -1;
   if (k >= 0) {
@@ -502,8 +600,8 @@ aug_letterbox_kernel(const unsigned char* __restrict__ arena, const ys_aug_src* 
   if (ident) { g.new_w = w; g.new_h = h; g.pad_l = (s - w) / 2; g.pad_u = (s - h) / 2; }
   else if (off >= 0) g = aug_letterbox_geom(h, w, s);
   const bool flr = it.flip_lr != 0, fud = it.flip_ud != 0;
-  const float q = C == 3 ? 1 / 255.0f : 1.0f;             // mul(1 / 255.0f), YoloDataset.cs:140: a multiply, bit-exact per byte; ids stay whole
-  const float fill = C == 3 ? 114.0f * q : 0.0f;
+  const float q = 1 / 255.0f;                             // mul(1 / 255.0f), YoloDataset.cs:140: a multiply, bit-exact per byte; ids stay whole
+  const float fill = C == 3 ? 114.0f : 0.0f;
   // the flips are folded into the output coordinate: out[y][x] = letterboxed[ly][lx]
   const int ry = (fud ? s - 1 - y : y) - g.pad_u;
   const bool row_in = (unsigned)ry < (unsigned)g.new_h;
@@ -533,8 +631,8 @@ aug_letterbox_kernel(const unsigned char* __restrict__ arena, const ys_aug_src* 
         const unsigned w0 = wp[0], w1 = sh ? wp[1] : 0u;
         unsigned px = (unsigned)((((unsigned long long)w1 << 32) | w0) >> (8 * sh));
         if (flr) px = __builtin_bswap32(px);
-        v[c][0] = (float)(px & 255u) * q; v[c][1] = (float)((px >> 8) & 255u) * q;
-        v[c][2] = (float)((px >> 16) & 255u) * q; v[c][3] = (float)(px >> 24) * q;
+        v[c][0] = (float)(px & 255u); v[c][1] = (float)((px >> 8) & 255u);
+        v[c][2] = (float)((px >> 16) & 255u); v[c][3] = (float)(px >> 24);
       }
     } else {
 #pragma unroll
@@ -544,10 +642,22 @@ aug_letterbox_kernel(const unsigned char* __restrict__ arena, const ys_aug_src* 
           int ix = (int)floorf((float)rx * sx);
           ix = ix < w - 1 ? ix : w - 1;
 #pragma unroll
-          for (int c = 0; c < C; c++) v[c][j] = (float)row[c * plane + ix] * q;
+          for (int c = 0; c < C; c++) v[c][j] = (float)row[c * plane + ix];
         }
       }
     }
+  }
+  if constexpr (C == 3) {                                  // the bytes (the 114 of the padding included) through the row's ops, then mul(1 / 255.0f)
+    if (J && k >= 0) {
+      AugPx p0 = {v[0][0], v[1][0], v[2][0]}, p1 = {v[0][1], v[1][1], v[2][1]}, p2 = {v[0][2], v[1][2], v[2][2]}, p3 = {v[0][3], v[1][3], v[2][3]};
+      aug_jitter_quad(J, 0.0f, false, p0, p1, p2, p3);
+      v[0][0] = p0.c0; v[1][0] = p0.c1; v[2][0] = p0.c2; v[0][1] = p1.c0; v[1][1] = p1.c1; v[2][1] = p1.c2;
+      v[0][2] = p2.c0; v[1][2] = p2.c1; v[2][2] = p2.c2; v[0][3] = p3.c0; v[1][3] = p3.c1; v[2][3] = p3.c2;
+    }
+#pragma unroll
+    for (int j = 0; j < 4; j++)
+#pragma unroll
+      for (int c = 0; c < C; c++) v[c][j] *= q;
   }
   const long long oplane = (long long)s * s;
   float* dst = out + (long long)blockIdx.z * C * oplane + (long long)y * s + x0;
@@ -620,6 +730,97 @@ aug_letterbox_labels_kernel(const ys_aug_src* __restrict__ srcs, int n_src, cons
   }
 }
 
+// ---------------------------------------------------------------------------------------------------------------- ColorJitter on its own
+// ys_color_jitter: all four ops on uint8 planes [B, 3, n] (n = h * w; the ops are per pixel, so a thread takes four consecutive pixels of the
+// flattened plane).  vec: n % 4 == 0 and aligned bases -> one word per plane in, one word (uint8) or 16 bytes (fp32) per plane out.
+__device__ __forceinline__ void aug_cj_load(const unsigned char* __restrict__ src, long long n, long long i4, int vec, AugPx& p0, AugPx& p1, AugPx& p2,
+                                            AugPx& p3) {
+  float v[3][4];
+#pragma unroll
+  for (int c = 0; c < 3; c++) {
+    const unsigned char* __restrict__ p = src + c * n + i4;
+    if (vec) {
+      const unsigned px = *(const unsigned*)p;
+      v[c][0] = (float)(px & 255u); v[c][1] = (float)((px >> 8) & 255u); v[c][2] = (float)((px >> 16) & 255u); v[c][3] = (float)(px >> 24);
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; j++) v[c][j] = i4 + j < n ? (float)p[j] : 0.0f;
+    }
+  }
+  p0.c0 = v[0][0]; p0.c1 = v[1][0]; p0.c2 = v[2][0]; p1.c0 = v[0][1]; p1.c1 = v[1][1]; p1.c2 = v[2][1];
+  p2.c0 = v[0][2]; p2.c1 = v[1][2]; p2.c2 = v[2][2]; p3.c0 = v[0][3]; p3.c1 = v[1][3]; p3.c2 = v[2][3];
+}
+
+// contrast, launch 1 of 2: sums[b] += the gray bytes of image b in its state in front of the contrast op (the ops ahead of it are replayed).
+// Integer atomics: any order gives the same sum.  Images whose row does not run contrast leave at once.
+__global__ void __launch_bounds__(AUG_T)
+aug_cj_gray_sum_kernel(const unsigned char* __restrict__ src, const ys_aug_jitter* __restrict__ jitter, long long n, int vec,
+                       unsigned long long* __restrict__ sums) {
+  __shared__ unsigned s_red[AUG_T];
+  const ys_aug_jitter* __restrict__ J = jitter + blockIdx.z;
+  if (aug_jitter_state(*J) != 2) return;                   // wave-uniform, block-uniform
+  const long long i4 = ((long long)blockIdx.x * AUG_T + threadIdx.x) * 4;
+  unsigned sum = 0;
+  if (i4 < n) {
+    AugPx p0, p1, p2, p3;
+    aug_cj_load(src + (long long)blockIdx.z * 3 * n, n, i4, vec, p0, p1, p2, p3);
+    aug_jitter_quad(J, 0.0f, true, p0, p1, p2, p3);
+    sum = (unsigned)aug_jit_gray(p0);
+    if (i4 + 1 < n) sum += (unsigned)aug_jit_gray(p1);
+    if (i4 + 2 < n) sum += (unsigned)aug_jit_gray(p2);
+    if (i4 + 3 < n) sum += (unsigned)aug_jit_gray(p3);
+  }
+  s_red[threadIdx.x] = sum;
+  __syncthreads();
+  for (int d = AUG_T / 2; d > 0; d >>= 1) {
+    if ((int)threadIdx.x < d) s_red[threadIdx.x] += s_red[threadIdx.x + d];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) atomicAdd(&sums[blockIdx.z], (unsigned long long)s_red[0]);
+}
+
+// launch 2 of 2 (the only one for rows without contrast): every op in the row's order; mean = (float)sum / (float)n -- for n <= 65536 the sum is an
+// exact fp32 integer and this is torch.mean's value; above that torch's own fp32 summation order decides its last bit (the one deviation).
+// An invalid row gives the all-114 image, like a refused item of the fused entries.
+__global__ void __launch_bounds__(AUG_T)
+aug_cj_apply_kernel(const unsigned char* __restrict__ src, const ys_aug_jitter* __restrict__ jitter, long long n, int vec,
+                    const unsigned long long* __restrict__ sums, void* __restrict__ dst, int dst_is_float) {
+  const long long i4 = ((long long)blockIdx.x * AUG_T + threadIdx.x) * 4;
+  if (i4 >= n) return;
+  const ys_aug_jitter* __restrict__ J = jitter + blockIdx.z;
+  const int state = aug_jitter_state(*J);                  // wave-uniform
+  AugPx p0, p1, p2, p3;
+  if (state == 0) {
+    p0.c0 = p0.c1 = p0.c2 = 114.0f; p1 = p0; p2 = p0; p3 = p0;
+  } else {
+    aug_cj_load(src + (long long)blockIdx.z * 3 * n, n, i4, vec, p0, p1, p2, p3);
+    const float mean = state == 2 ? (float)sums[blockIdx.z] / (float)n : 0.0f;
+    aug_jitter_quad(J, mean, false, p0, p1, p2, p3);
+  }
+  const float v[3][4] = {{p0.c0, p1.c0, p2.c0, p3.c0}, {p0.c1, p1.c1, p2.c1, p3.c1}, {p0.c2, p1.c2, p2.c2, p3.c2}};
+  const long long base = (long long)blockIdx.z * 3 * n + i4;
+  if (dst_is_float) {
+    const float q = 1 / 255.0f;
+    float* __restrict__ o = (float*)dst + base;
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+      if (vec) ys_st16(o + c * n, make_uint4(ys_f2u(v[c][0] * q), ys_f2u(v[c][1] * q), ys_f2u(v[c][2] * q), ys_f2u(v[c][3] * q)));
+      else
+#pragma unroll
+        for (int j = 0; j < 4; j++) if (i4 + j < n) o[c * n + j] = v[c][j] * q;
+    }
+  } else {
+    unsigned char* __restrict__ o = (unsigned char*)dst + base;
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+      if (vec) *(unsigned*)(o + c * n) = (unsigned)v[c][0] | ((unsigned)v[c][1] << 8) | ((unsigned)v[c][2] << 16) | ((unsigned)v[c][3] << 24);
+      else
+#pragma unroll
+        for (int j = 0; j < 4; j++) if (i4 + j < n) o[c * n + j] = (unsigned char)v[c][j];
+    }
+  }
+}
+
 // ---------------------------------------------------------------------------------------------------------------- launchers
 size_t ys_aug_ws_bytes(int B) { return (size_t)B * sizeof(AugParams) + ((size_t)2 * B + 1) * sizeof(int) + 64; }   // params | counts [B] | offsets [B + 1]
 
@@ -628,11 +829,11 @@ int ys_aug_item_ok_host(const ys_aug_item* it, const ys_aug_src* srcs, int n_src
 }
 
 int ys_aug_mosaic_launch(hipStream_t st, const unsigned char* arena, const ys_aug_src* srcs, int n_src, const ys_aug_item* items, int B, int s,
-                         int r, int perspective, void* ws, float* images, float* masks) {
+                         int r, int perspective, const ys_aug_jitter* jitter, void* ws, float* images, float* masks) {
   AugParams* params = (AugParams*)ws;
   YS_LAUNCH(aug_prep_kernel, ys_cdiv(B, 64), 64, st, srcs, n_src, items, B, s, r, perspective, params);
   const long quads = (long)((s + 3) / 4) * s;
-  YS_LAUNCH(aug_mosaic_warp_kernel, dim3(ys_cdiv(quads, AUG_T), 1, B), AUG_T, st, arena, (const AugParams*)params, s, perspective,
+  YS_LAUNCH(aug_mosaic_warp_kernel, dim3(ys_cdiv(quads, AUG_T), 1, B), AUG_T, st, arena, (const AugParams*)params, jitter, s, perspective,
             (s % 4 == 0 && ((size_t)images & 15) == 0) ? 1 : 0, images);
   if (masks) {
     const long n = (long)(s / r) * (s / r);
@@ -656,14 +857,14 @@ int ys_aug_labels_launch(hipStream_t st, const ys_aug_src* srcs, int n_src, cons
 int ys_aug_letterbox_src_host(const ys_aug_item* it, const ys_aug_src* srcs, int n_src) { return aug_letterbox_src(*it, srcs, n_src); }
 
 int ys_aug_letterbox_launch(hipStream_t st, const unsigned char* arena, const ys_aug_src* srcs, int n_src, const ys_aug_item* items, int B, int s,
-                            int r, float* images, float* masks) {
+                            int r, const ys_aug_jitter* jitter, float* images, float* masks) {
   const long quads = (long)((s + 3) / 4) * s;
-  YS_LAUNCH((aug_letterbox_kernel<3>), dim3(ys_cdiv(quads, AUG_T), 1, B), AUG_T, st, arena, srcs, n_src, items, s,
+  YS_LAUNCH((aug_letterbox_kernel<3>), dim3(ys_cdiv(quads, AUG_T), 1, B), AUG_T, st, arena, srcs, n_src, items, jitter, s,
             (s % 4 == 0 && ((size_t)images & 15) == 0) ? 1 : 0, images);
   if (masks) {
     const int ms = s / r;
     const long mquads = (long)((ms + 3) / 4) * ms;
-    YS_LAUNCH((aug_letterbox_kernel<1>), dim3(ys_cdiv(mquads, AUG_T), 1, B), AUG_T, st, arena, srcs, n_src, items, ms,
+    YS_LAUNCH((aug_letterbox_kernel<1>), dim3(ys_cdiv(mquads, AUG_T), 1, B), AUG_T, st, arena, srcs, n_src, items, (const ys_aug_jitter*)nullptr, ms,
               (ms % 4 == 0 && ((size_t)masks & 15) == 0) ? 1 : 0, masks);
   }
   return YS_OK;
@@ -677,5 +878,17 @@ int ys_aug_letterbox_labels_launch(hipStream_t st, const ys_aug_src* srcs, int n
   YS_LAUNCH(aug_count_scan_kernel, 1, AUG_T, st, (const int*)counts, B, counts + B);
   YS_LAUNCH(aug_letterbox_labels_kernel, B, AUG_T, st, srcs, n_src, lab_off, cls, boxes, kpts, K, items, B, s, flags, capacity, (const int*)(counts + B),
             o_bidx, o_cls, o_box, o_kpt, o_count);
+  return YS_OK;
+}
+
+int ys_aug_jitter_state_host(const ys_aug_jitter* row) { return aug_jitter_state(*row); }
+
+// sums: B zeroed 64-bit counters (read and written only where a row runs contrast); with_contrast = 0 skips the reduction (the caller knows the rows)
+int ys_color_jitter_launch(hipStream_t st, const unsigned char* src, const ys_aug_jitter* jitter, int B, long long n, int with_contrast, void* sums,
+                           void* dst, int dst_is_float) {
+  const int vec = (n % 4 == 0 && ((size_t)src & 3) == 0 && ((size_t)dst & (dst_is_float ? 15 : 3)) == 0) ? 1 : 0;
+  const dim3 grid(ys_cdiv((n + 3) / 4, AUG_T), 1, B);
+  if (with_contrast) YS_LAUNCH(aug_cj_gray_sum_kernel, grid, AUG_T, st, src, jitter, n, vec, (unsigned long long*)sums);
+  YS_LAUNCH(aug_cj_apply_kernel, grid, AUG_T, st, src, jitter, n, vec, (const unsigned long long*)sums, dst, dst_is_float);
   return YS_OK;
 }

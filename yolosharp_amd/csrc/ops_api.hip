@@ -1015,33 +1015,72 @@ int aug_check_items(const char* fn, const ys_aug_item* items, int batch, const y
 }
 }  // namespace
 
-extern "C" int ys_augment_mosaic(ys_ctx* ctx, const uint8_t* arena, const ys_aug_src* srcs, int n_src, const ys_aug_item* items, int batch,
-                                 int on_device, int imgsz, int mask_ratio, int perspective, float* images, float* masks) {
-  YS_REQUIRE(ctx && arena && srcs && items && images, "ys_augment_mosaic: null argument");
-  YS_REQUIRE(batch > 0 && batch <= 65535 && n_src > 0, "ys_augment_mosaic: bad shape batch=%d (1..65535) n_src=%d", batch, n_src);
-  YS_REQUIRE(imgsz >= 2 && imgsz % 2 == 0 && imgsz <= 16384, "ys_augment_mosaic: imgsz %d must be even and in [2, 16384]", imgsz);
-  if (masks) YS_REQUIRE(mask_ratio >= 1 && imgsz % mask_ratio == 0 && 2 * imgsz / mask_ratio >= 2, "ys_augment_mosaic: mask_ratio %d does not divide imgsz %d", mask_ratio, imgsz);
+namespace {
+// the checks a host-resident jitter table allows: every row valid (YS_ERR_INVALID_ARG); allow_contrast = 0: no row runs contrast (YS_ERR_UNSUPPORTED).
+// *any_contrast (may be NULL) = some row runs it
+int aug_check_jitter(const char* fn, const ys_aug_jitter* rows, int batch, int allow_contrast, int* any_contrast) {
+  int any = 0;
+  for (int b = 0; b < batch; b++) {
+    const ys_aug_jitter& J = rows[b];
+    const int state = ys_aug_jitter_state_host(&J);
+    YS_REQUIRE(state != 0, "%s: jitter row %d is invalid: order (%d, %d, %d, %d) must hold ids in {-1, 0..3} with none twice, factors (%g, %g, %g) must be "
+               "finite and >= 0, hue %g in [-0.5, 0.5]", fn, b, J.order[0], J.order[1], J.order[2], J.order[3], (double)J.factor[0], (double)J.factor[1],
+               (double)J.factor[2], (double)J.factor[3]);
+    if (state == 2 && !allow_contrast) {
+      ys_set_error("%s: jitter row %d runs contrast: the fused entries have no image mean (ys_color_jitter does)", fn, b);
+      return YS_ERR_UNSUPPORTED;
+    }
+    any |= state == 2;
+  }
+  if (any_contrast) *any_contrast = any;
+  return YS_OK;
+}
+
+int aug_mosaic_impl(const char* fn, ys_ctx* ctx, const uint8_t* arena, const ys_aug_src* srcs, int n_src, const ys_aug_item* items, int batch, int on_device,
+                    int imgsz, int mask_ratio, int perspective, const ys_aug_jitter* jitter, float* images, float* masks) {
+  YS_REQUIRE(ctx && arena && srcs && items && images, "%s: null argument", fn);
+  YS_REQUIRE(batch > 0 && batch <= 65535 && n_src > 0, "%s: bad shape batch=%d (1..65535) n_src=%d", fn, batch, n_src);
+  YS_REQUIRE(imgsz >= 2 && imgsz % 2 == 0 && imgsz <= 16384, "%s: imgsz %d must be even and in [2, 16384]", fn, imgsz);
+  if (masks) YS_REQUIRE(mask_ratio >= 1 && imgsz % mask_ratio == 0 && 2 * imgsz / mask_ratio >= 2, "%s: mask_ratio %d does not divide imgsz %d", fn, mask_ratio, imgsz);
   const int r = masks ? mask_ratio : 1;
   YS_CHECK_HIP(hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
   YS_TRY(aug_reserve_ws(ctx, batch));
   YsTimer timer(ctx, "augment");
-  if (on_device) return ys_aug_mosaic_launch(st, arena, srcs, n_src, items, batch, imgsz, r, perspective != 0, ctx->aug_ws, images, masks);
-  YS_TRY(aug_check_items("ys_augment_mosaic", items, batch, srcs, n_src, imgsz, perspective != 0));
+  if (on_device) return ys_aug_mosaic_launch(st, arena, srcs, n_src, items, batch, imgsz, r, perspective != 0, jitter, ctx->aug_ws, images, masks);
+  YS_TRY(aug_check_items(fn, items, batch, srcs, n_src, imgsz, perspective != 0));
+  if (jitter) YS_TRY(aug_check_jitter(fn, jitter, batch, 0, nullptr));
   const size_t arena_bytes = aug_arena_bytes(srcs, n_src);
   const size_t n_img = (size_t)batch * 3 * imgsz * imgsz, n_msk = masks ? (size_t)batch * (imgsz / r) * (imgsz / r) : 0;
-  DevBuf da, ds, di, dimg, dm;
+  DevBuf da, ds, di, dj, dimg, dm;
   YS_TRY(da.alloc(arena_bytes)); YS_TRY(ds.alloc((size_t)n_src * sizeof(ys_aug_src))); YS_TRY(di.alloc((size_t)batch * sizeof(ys_aug_item)));
   YS_TRY(dimg.alloc(n_img * 4)); YS_TRY(dm.alloc(n_msk * 4));
   YS_CHECK_HIP(hipMemcpyAsync(da.p, arena, arena_bytes, hipMemcpyHostToDevice, st));
   YS_CHECK_HIP(hipMemcpyAsync(ds.p, srcs, (size_t)n_src * sizeof(ys_aug_src), hipMemcpyHostToDevice, st));
   YS_CHECK_HIP(hipMemcpyAsync(di.p, items, (size_t)batch * sizeof(ys_aug_item), hipMemcpyHostToDevice, st));
+  if (jitter) {
+    YS_TRY(dj.alloc((size_t)batch * sizeof(ys_aug_jitter)));
+    YS_CHECK_HIP(hipMemcpyAsync(dj.p, jitter, (size_t)batch * sizeof(ys_aug_jitter), hipMemcpyHostToDevice, st));
+  }
   YS_TRY(ys_aug_mosaic_launch(st, (const unsigned char*)da.p, (const ys_aug_src*)ds.p, n_src, (const ys_aug_item*)di.p, batch, imgsz, r, perspective != 0,
-                              ctx->aug_ws, (float*)dimg.p, masks ? (float*)dm.p : nullptr));
+                              jitter ? (const ys_aug_jitter*)dj.p : nullptr, ctx->aug_ws, (float*)dimg.p, masks ? (float*)dm.p : nullptr));
   YS_CHECK_HIP(hipMemcpyAsync(images, dimg.p, n_img * 4, hipMemcpyDeviceToHost, st));
   if (masks) YS_CHECK_HIP(hipMemcpyAsync(masks, dm.p, n_msk * 4, hipMemcpyDeviceToHost, st));
   YS_CHECK_HIP(hipStreamSynchronize(st));
   return YS_OK;
+}
+}  // namespace
+
+extern "C" int ys_augment_mosaic(ys_ctx* ctx, const uint8_t* arena, const ys_aug_src* srcs, int n_src, const ys_aug_item* items, int batch,
+                                 int on_device, int imgsz, int mask_ratio, int perspective, float* images, float* masks) {
+  return aug_mosaic_impl("ys_augment_mosaic", ctx, arena, srcs, n_src, items, batch, on_device, imgsz, mask_ratio, perspective, nullptr, images, masks);
+}
+
+// the same with the ColorJitter (RandomHSV, Data/Augment.cs:968-987) rows of the batch in the warp kernel's epilogue; jitter == NULL is the entry above
+extern "C" int ys_augment_mosaic_jitter(ys_ctx* ctx, const uint8_t* arena, const ys_aug_src* srcs, int n_src, const ys_aug_item* items, int batch,
+                                        int on_device, int imgsz, int mask_ratio, int perspective, const ys_aug_jitter* jitter, float* images,
+                                        float* masks) {
+  return aug_mosaic_impl("ys_augment_mosaic_jitter", ctx, arena, srcs, n_src, items, batch, on_device, imgsz, mask_ratio, perspective, jitter, images, masks);
 }
 
 extern "C" int ys_augment_labels(ys_ctx* ctx, const ys_aug_src* srcs, const int32_t* lab_off, const float* cls, const float* boxes,
@@ -1114,32 +1153,77 @@ int aug_check_letterbox_items(const char* fn, const ys_aug_item* items, int batc
   }
   return YS_OK;
 }
-}  // namespace
 
-extern "C" int ys_augment_letterbox(ys_ctx* ctx, const uint8_t* arena, const ys_aug_src* srcs, int n_src, const ys_aug_item* items, int batch,
-                                    int on_device, int imgsz, int mask_ratio, float* images, float* masks) {
-  YS_REQUIRE(ctx && arena && srcs && items && images, "ys_augment_letterbox: null argument");
-  YS_REQUIRE(batch > 0 && batch <= 65535 && n_src > 0, "ys_augment_letterbox: bad shape batch=%d (1..65535) n_src=%d", batch, n_src);
-  YS_REQUIRE(imgsz >= 2 && imgsz % 2 == 0 && imgsz <= 16384, "ys_augment_letterbox: imgsz %d must be even and in [2, 16384]", imgsz);
-  if (masks) YS_REQUIRE(mask_ratio >= 1 && imgsz % mask_ratio == 0, "ys_augment_letterbox: mask_ratio %d does not divide imgsz %d", mask_ratio, imgsz);
+int aug_letterbox_impl(const char* fn, ys_ctx* ctx, const uint8_t* arena, const ys_aug_src* srcs, int n_src, const ys_aug_item* items, int batch,
+                       int on_device, int imgsz, int mask_ratio, const ys_aug_jitter* jitter, float* images, float* masks) {
+  YS_REQUIRE(ctx && arena && srcs && items && images, "%s: null argument", fn);
+  YS_REQUIRE(batch > 0 && batch <= 65535 && n_src > 0, "%s: bad shape batch=%d (1..65535) n_src=%d", fn, batch, n_src);
+  YS_REQUIRE(imgsz >= 2 && imgsz % 2 == 0 && imgsz <= 16384, "%s: imgsz %d must be even and in [2, 16384]", fn, imgsz);
+  if (masks) YS_REQUIRE(mask_ratio >= 1 && imgsz % mask_ratio == 0, "%s: mask_ratio %d does not divide imgsz %d", fn, mask_ratio, imgsz);
   const int r = masks ? mask_ratio : 1;
   YS_CHECK_HIP(hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
   YsTimer timer(ctx, "augment_letterbox");
-  if (on_device) return ys_aug_letterbox_launch(st, arena, srcs, n_src, items, batch, imgsz, r, images, masks);
-  YS_TRY(aug_check_letterbox_items("ys_augment_letterbox", items, batch, srcs, n_src));
+  if (on_device) return ys_aug_letterbox_launch(st, arena, srcs, n_src, items, batch, imgsz, r, jitter, images, masks);
+  YS_TRY(aug_check_letterbox_items(fn, items, batch, srcs, n_src));
+  if (jitter) YS_TRY(aug_check_jitter(fn, jitter, batch, 0, nullptr));
   const size_t arena_bytes = aug_arena_bytes(srcs, n_src);
   const size_t n_img = (size_t)batch * 3 * imgsz * imgsz, n_msk = masks ? (size_t)batch * (imgsz / r) * (imgsz / r) : 0;
-  DevBuf da, ds, di, dimg, dm;
+  DevBuf da, ds, di, dj, dimg, dm;
   YS_TRY(da.alloc(arena_bytes)); YS_TRY(ds.alloc((size_t)n_src * sizeof(ys_aug_src))); YS_TRY(di.alloc((size_t)batch * sizeof(ys_aug_item)));
   YS_TRY(dimg.alloc(n_img * 4)); YS_TRY(dm.alloc(n_msk * 4));
   YS_CHECK_HIP(hipMemcpyAsync(da.p, arena, arena_bytes, hipMemcpyHostToDevice, st));
   YS_CHECK_HIP(hipMemcpyAsync(ds.p, srcs, (size_t)n_src * sizeof(ys_aug_src), hipMemcpyHostToDevice, st));
   YS_CHECK_HIP(hipMemcpyAsync(di.p, items, (size_t)batch * sizeof(ys_aug_item), hipMemcpyHostToDevice, st));
-  YS_TRY(ys_aug_letterbox_launch(st, (const unsigned char*)da.p, (const ys_aug_src*)ds.p, n_src, (const ys_aug_item*)di.p, batch, imgsz, r, (float*)dimg.p,
-                                 masks ? (float*)dm.p : nullptr));
+  if (jitter) {
+    YS_TRY(dj.alloc((size_t)batch * sizeof(ys_aug_jitter)));
+    YS_CHECK_HIP(hipMemcpyAsync(dj.p, jitter, (size_t)batch * sizeof(ys_aug_jitter), hipMemcpyHostToDevice, st));
+  }
+  YS_TRY(ys_aug_letterbox_launch(st, (const unsigned char*)da.p, (const ys_aug_src*)ds.p, n_src, (const ys_aug_item*)di.p, batch, imgsz, r,
+                                 jitter ? (const ys_aug_jitter*)dj.p : nullptr, (float*)dimg.p, masks ? (float*)dm.p : nullptr));
   YS_CHECK_HIP(hipMemcpyAsync(images, dimg.p, n_img * 4, hipMemcpyDeviceToHost, st));
   if (masks) YS_CHECK_HIP(hipMemcpyAsync(masks, dm.p, n_msk * 4, hipMemcpyDeviceToHost, st));
+  YS_CHECK_HIP(hipStreamSynchronize(st));
+  return YS_OK;
+}
+}  // namespace
+
+extern "C" int ys_augment_letterbox(ys_ctx* ctx, const uint8_t* arena, const ys_aug_src* srcs, int n_src, const ys_aug_item* items, int batch,
+                                    int on_device, int imgsz, int mask_ratio, float* images, float* masks) {
+  return aug_letterbox_impl("ys_augment_letterbox", ctx, arena, srcs, n_src, items, batch, on_device, imgsz, mask_ratio, nullptr, images, masks);
+}
+
+// the same with the batch's ColorJitter rows in the image kernel's epilogue; jitter == NULL is the entry above
+extern "C" int ys_augment_letterbox_jitter(ys_ctx* ctx, const uint8_t* arena, const ys_aug_src* srcs, int n_src, const ys_aug_item* items, int batch,
+                                           int on_device, int imgsz, int mask_ratio, const ys_aug_jitter* jitter, float* images, float* masks) {
+  return aug_letterbox_impl("ys_augment_letterbox_jitter", ctx, arena, srcs, n_src, items, batch, on_device, imgsz, mask_ratio, jitter, images, masks);
+}
+
+// ---- ColorJitter on its own (augment.hip; Data/Augment.cs:968-987, Data/ClassificationDataset.cs:122): all four ops, uint8 or fp32 * (1 / 255.0f) out
+extern "C" int ys_color_jitter(ys_ctx* ctx, const uint8_t* src, const ys_aug_jitter* jitter, int batch, int h, int w, int on_device, void* dst,
+                               int dst_is_float) {
+  YS_REQUIRE(ctx && src && jitter && dst, "ys_color_jitter: null argument");
+  YS_REQUIRE(batch > 0 && batch <= 65535 && h > 0 && w > 0 && h <= 16384 && w <= 16384, "ys_color_jitter: bad shape batch=%d (1..65535) h=%d w=%d (1..16384)",
+             batch, h, w);
+  YS_CHECK_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  YS_TRY(aug_reserve_ws(ctx, batch));                      // the per-image gray sums live in the augmenter's workspace (8 bytes per image)
+  YsTimer timer(ctx, "color_jitter");
+  const long long n = (long long)h * w;
+  if (on_device) {                                         // the host cannot read the rows: the reduction runs and leaves at once where a row has no contrast
+    YS_CHECK_HIP(hipMemsetAsync(ctx->aug_ws, 0, (size_t)batch * 8, st));
+    return ys_color_jitter_launch(st, src, jitter, batch, n, 1, ctx->aug_ws, dst, dst_is_float != 0);
+  }
+  int contrast = 0;
+  YS_TRY(aug_check_jitter("ys_color_jitter", jitter, batch, 1, &contrast));
+  const size_t n_px = (size_t)batch * 3 * (size_t)n, out_bytes = n_px * (dst_is_float ? 4 : 1);
+  DevBuf dsrc, dj, dout;
+  YS_TRY(dsrc.alloc(n_px)); YS_TRY(dj.alloc((size_t)batch * sizeof(ys_aug_jitter))); YS_TRY(dout.alloc(out_bytes));
+  YS_CHECK_HIP(hipMemcpyAsync(dsrc.p, src, n_px, hipMemcpyHostToDevice, st));
+  YS_CHECK_HIP(hipMemcpyAsync(dj.p, jitter, (size_t)batch * sizeof(ys_aug_jitter), hipMemcpyHostToDevice, st));
+  if (contrast) YS_CHECK_HIP(hipMemsetAsync(ctx->aug_ws, 0, (size_t)batch * 8, st));
+  YS_TRY(ys_color_jitter_launch(st, (const unsigned char*)dsrc.p, (const ys_aug_jitter*)dj.p, batch, n, contrast, ctx->aug_ws, dout.p, dst_is_float != 0));
+  YS_CHECK_HIP(hipMemcpyAsync(dst, dout.p, out_bytes, hipMemcpyDeviceToHost, st));
   YS_CHECK_HIP(hipStreamSynchronize(st));
   return YS_OK;
 }

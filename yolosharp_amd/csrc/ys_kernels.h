@@ -412,6 +412,7 @@ int ys_process_mask_launch(hipStream_t st, const float* protos, const float* mas
 // ---- augment.hip: Mosaic4 + RandomPerspective + flips + Normalize + collate on the device (Data/Augment.cs:158-274, 315-695, 860-966)
 struct ys_aug_src;
 struct ys_aug_item;
+struct ys_aug_jitter;
 // per output image, written by aug_prep_kernel: the inverse matrices (image, mask) in double and the four tiles' geometry
 struct AugTile {
   long long img_off, mask_off;          // byte offsets into the arena (mask_off < 0: no mask)
@@ -427,7 +428,7 @@ struct AugParams {
 size_t ys_aug_ws_bytes(int B);
 int ys_aug_item_ok_host(const ys_aug_item* it, const ys_aug_src* srcs, int n_src, int s, int perspective);
 int ys_aug_mosaic_launch(hipStream_t st, const unsigned char* arena, const ys_aug_src* srcs, int n_src, const ys_aug_item* items, int B, int s,
-                         int r, int perspective, void* ws, float* images, float* masks);
+                         int r, int perspective, const ys_aug_jitter* jitter, void* ws, float* images, float* masks);
 int ys_aug_labels_launch(hipStream_t st, const ys_aug_src* srcs, int n_src, const int* lab_off, const float* cls, const float* boxes,
                          const float* kpts, int K, const ys_aug_item* items, int B, int s, int perspective, int flags, int capacity, void* ws,
                          float* o_bidx, float* o_cls, float* o_box, float* o_kpt, int* o_count);
@@ -435,7 +436,12 @@ int ys_aug_labels_launch(hipStream_t st, const ys_aug_src* srcs, int n_src, cons
 // uses the counts | offsets part of the same workspace
 int ys_aug_letterbox_src_host(const ys_aug_item* it, const ys_aug_src* srcs, int n_src);
 int ys_aug_letterbox_launch(hipStream_t st, const unsigned char* arena, const ys_aug_src* srcs, int n_src, const ys_aug_item* items, int B, int s,
-                            int r, float* images, float* masks);
+                            int r, const ys_aug_jitter* jitter, float* images, float* masks);
+// ColorJitter (RandomHSV, Data/Augment.cs:968-987): a row's state (0 invalid, 1 valid, 2 valid and runs contrast); the stand-alone operator on uint8
+// planes [B, 3, n] (jitter = NULL in the two launches above: no epilogue)
+int ys_aug_jitter_state_host(const ys_aug_jitter* row);
+int ys_color_jitter_launch(hipStream_t st, const unsigned char* src, const ys_aug_jitter* jitter, int B, long long n, int with_contrast, void* sums,
+                           void* dst, int dst_is_float);
 int ys_aug_letterbox_labels_launch(hipStream_t st, const ys_aug_src* srcs, int n_src, const int* lab_off, const float* cls, const float* boxes,
                                    const float* kpts, int K, const ys_aug_item* items, int B, int s, int flags, int capacity, void* ws, float* o_bidx,
                                    float* o_cls, float* o_box, float* o_kpt, int* o_count);
