@@ -617,7 +617,7 @@ YS_API int ys_dwconv3x3_bwd(ys_ctx* ctx, int dtype, const float* x, int B, int C
                             int x_ldc, int x_coff, int dx_ldc, int dx_coff, int accumulate, float* dx, float* dw,
                             int32_t* view_intact);
 
-/* ---- BatchNorm training kernels (csrc/elementwise.hip), one stateless call per launch sequence of a Conv unit (unit parity against float64).
+/* ---- BatchNorm training kernels (csrc/batchnorm.hip), one stateless call per launch sequence of a Conv unit (unit parity against float64).
  * Host tensors are CHANNEL-MAJOR [C][rows] fp32 (NCHW with B = 1); C is a multiple of the 16-byte vector (4 fp32 / 8 bf16).  y and dy are dense on the
  * device as in the model; z, res, dz and rg sit at channel `*_coff` of a [rows][*_coff + C + *_pad] buffer pre-filled with a sentinel, and every workspace
  * carries a sentinel guard; view_intact = 1 when all of it survived.  eps = 1e-3, momentum = 0.03; the batch count is `rows`. */

@@ -2,11 +2,11 @@
 at every point where the engine's bf16 path stores a tensor -- so that a bf16 parity test compares like with like instead of granting
 the engine "2-5 % of the global maximum" against an fp32 reference.
 
-Where the engine rounds (csrc/conv.hip, conv_epi.h, elementwise.hip):
+Where the engine rounds (csrc/conv.hip, conv_epi.h, batchnorm.hip):
   * convolution operands: the input tensor and the weight shadow are bf16, products accumulate in fp32 (MFMA);
   * the raw convolution output y is stored bf16 BEFORE the batch statistics are taken (conv_epi.h: statistics of the rounded values);
   * BatchNorm + SiLU run in fp32 on y and the result z is stored bf16; a Bottleneck shortcut is added in the same pass (one rounding of
-    x + z, elementwise.hip bn_act_apply);
+    x + z, batchnorm.hip bn_act_apply);
   * the Detect towers' last 1x1 convolutions add their bias to the fp32 accumulators and store bf16 (`pd`, `ps`);
   * backward: every gradient tensor that mirrors one of those buffers is bf16 (dz, dy); weight / BatchNorm parameter gradients are fp32.
 Torch's autograd computes the same chain when each stored tensor passes through `_RoundSTE` (forward: round to bf16; backward: round

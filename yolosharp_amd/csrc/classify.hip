@@ -12,7 +12,7 @@
 //                  (score descending, index ascending): the reference's argsort(descending) with ties to the lower index.
 // Every lane of a wave runs the same trip counts around the wave reductions (the interpreter build needs full waves there).
 #include "ys_internal.h"
-#include "ys_kernels.h"
+#include "bn_math.h"
 
 #define CLS_THREADS 256
 #define CLS_TOPK_MAX 16
@@ -35,9 +35,7 @@ cls_pool_fwd_kernel(const T* __restrict__ x, int ldc, int coff, long bstride, in
     float f[EPL];
     ys_unpack<T>(*(const uint4*)(p + (long)i * ldc), f);
     for (int j = 0; j < EPL; j++) {
-      float v = f[j];
-      if (APPLY) { v = v * sc[j] + sh[j]; if (act) v = ys_silu(v); }
-      acc[j] += v;
+      acc[j] += APPLY ? bn_act1(f[j], sc[j], sh[j], act != 0) : f[j];
     }
   }
   const float inv = 1.0f / (float)HW;
@@ -66,8 +64,8 @@ int ys_cls_pool_fwd_launch(hipStream_t st, int dtype, const void* x, int ldc, in
 
 // ---- pool backward fused into the Conv unit's BN / SiLU backward.  dz[b][p][c] = dpooled[b][c] / HW is the same at every pixel of an
 // image, so it is never written: the reduction pass takes it from dpooled (one thread per (image, EPL channels), pixels in order -> the
-// partial rows [B][2][C] bn_bwd_finalize reads, nblk = B), and the apply pass writes the convolution's dy from it.  Same arithmetic as
-// chan_reduce_kernel / bn_bwd_apply_kernel (elementwise.hip) with dz = dpooled / HW kept in fp32.
+// partial rows [B][2][C] bn_bwd_finalize reads, nblk = B), and the apply pass writes the convolution's dy from it.  The arithmetic of
+// chan_reduce_kernel / bn_bwd_apply_kernel (batchnorm.hip; bn_math.h) with dz = dpooled / HW kept in fp32.
 template <class T, bool ACT>
 __global__ void __launch_bounds__(CLS_THREADS)
 cls_bn_bwd_reduce_kernel(const T* __restrict__ dp, int ldp, const T* __restrict__ y, int B, int HW, int C, const float* __restrict__ scale,
@@ -87,8 +85,7 @@ cls_bn_bwd_reduce_kernel(const T* __restrict__ dp, int ldp, const T* __restrict_
     float f[EPL];
     ys_unpack<T>(*(const uint4*)(yp + (long)i * C), f);
     for (int e = 0; e < EPL; e++) {
-      const float u = f[e] * sc[e] + sh[e];
-      const float du = ACT ? g[e] * ys_silu_grad(u) : g[e];
+      const float du = bn_du1(g[e], f[e], sc[e], sh[e], ACT);
       a1[e] += du;
       a2[e] += du * f[e];
     }
@@ -113,10 +110,7 @@ cls_bn_bwd_apply_kernel(const T* __restrict__ dp, int ldp, const T* __restrict__
   const float inv = 1.0f / (float)HW;
   for (int e = 0; e < EPL; e++) {
     const float sc = scale[c + e];
-    const float u = f[e] * sc + shift[c + e];
-    const float gz = g[e] * inv;
-    const float du = ACT ? gz * ys_silu_grad(u) : gz;
-    f[e] = sc * du - k2[c + e] - f[e] * k3[c + e];
+    f[e] = bn_dy1(bn_du1(g[e] * inv, f[e], sc, shift[c + e], ACT), f[e], sc, k2[c + e], k3[c + e]);
   }
   *(uint4*)(dy + row * C + c) = ys_pack<T>(f);
 }
@@ -128,10 +122,7 @@ int ys_cls_bn_bwd_reduce_launch(hipStream_t st, int dtype, const void* dpooled, 
   YsKprofScope prof(st, "cls_pool_bwd");
   const long n = (long)B * (C / epl);
   const int grid = (int)((n + CLS_THREADS - 1) / CLS_THREADS);
-#define CLS_RED(TT, AF) YS_LAUNCH((cls_bn_bwd_reduce_kernel<TT, AF>), grid, CLS_THREADS, st, (const TT*)dpooled, ldp, (const TT*)y, B, HW, C, scale, shift, partial)
-  if (dtype == YS_BF16) { if (act) CLS_RED(bf16_t, true); else CLS_RED(bf16_t, false); }
-  else { if (act) CLS_RED(float, true); else CLS_RED(float, false); }
-#undef CLS_RED
+  YS_DISPATCH_T_ACT(dtype, act, YS_LAUNCH((cls_bn_bwd_reduce_kernel<TT, AF>), grid, CLS_THREADS, st, (const TT*)dpooled, ldp, (const TT*)y, B, HW, C, scale, shift, partial));
   return YS_OK;
 }
 
@@ -143,10 +134,7 @@ int ys_cls_bn_bwd_apply_launch(hipStream_t st, int dtype, const void* dpooled, i
   const long rows = (long)B * HW;
   const long n = rows * (C / epl);
   const int grid = (int)((n + CLS_THREADS - 1) / CLS_THREADS);
-#define CLS_APP(TT, AF) YS_LAUNCH((cls_bn_bwd_apply_kernel<TT, AF>), grid, CLS_THREADS, st, (const TT*)dpooled, ldp, (const TT*)y, rows, HW, C, scale, shift, k2, k3, (TT*)dy)
-  if (dtype == YS_BF16) { if (act) CLS_APP(bf16_t, true); else CLS_APP(bf16_t, false); }
-  else { if (act) CLS_APP(float, true); else CLS_APP(float, false); }
-#undef CLS_APP
+  YS_DISPATCH_T_ACT(dtype, act, YS_LAUNCH((cls_bn_bwd_apply_kernel<TT, AF>), grid, CLS_THREADS, st, (const TT*)dpooled, ldp, (const TT*)y, rows, HW, C, scale, shift, k2, k3, (TT*)dy));
   return YS_OK;
 }
 

@@ -1,9 +1,10 @@
 // elementwise.hip -- HBM-bound NHWC kernels around the convolutions (gfx950).
-//   BatchNorm2d(eps 1e-3, momentum 0.03) + SiLU forward/backward  (Modules/Convs.cs:36-62)
-//   MaxPool2d(5,1,2) chain of SPPF                                  (Modules/Block.cs:236-285)
+//   input pack / unpack, LetterBox resize                           (Detector.cs:33-41, Data/Augment.cs:698-857)
+//   MaxPool2d(5,1,2) chain of SPPF                                   (Modules/Block.cs:236-285)
 //   Upsample(x2, nearest) + Concat as channel-slice writes           (Models/Yolo.cs:70-75, Convs.cs:435-448)
 //   Detect._inference decode                                         (Modules/Head.cs:204-223, Block.cs:40-45)
 //   AdamW step                                                       (YoloBaseTaskModel.cs:144-153, Amp.cs:355-372)
+// (The BatchNorm + SiLU training passes are batchnorm.hip.)
 // All tensors are [rows][ldc] views with a channel offset; one thread moves 16 bytes (8 bf16 / 4 f32).
 #include "ys_internal.h"
 #include "ys_kernels.h"
@@ -163,616 +164,6 @@ int ys_unpack_nchw_strided_launch(hipStream_t st, int dtype, const void* x, int 
   const long n = (long)B * C * rpb;
   if (dtype == YS_BF16) YS_LAUNCH((unpack_nchw_strided_kernel<bf16_t>), ys_cdiv(n, EW_THREADS), EW_THREADS, st, (const bf16_t*)x, ldc, coff, B, C, rpb, y, y_bstride, y_off);
   else YS_LAUNCH((unpack_nchw_strided_kernel<float>), ys_cdiv(n, EW_THREADS), EW_THREADS, st, (const float*)x, ldc, coff, B, C, rpb, y, y_bstride, y_off);
-  return YS_OK;
-}
-
-// ------------------------------------------------------------------ block reduction helper (double)
-// two sums at once: wave shuffles, then one LDS exchange of the EW_THREADS/64 wave totals combined in a fixed order (the LDS
-// tree above costs 9 barriers per value -- most of a ~5 us finalize kernel)
-__device__ inline void block_sum2_d(double& a, double& b, double* sbuf) {
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) { a += __shfl_down(a, off); b += __shfl_down(b, off); }
-  if (lane == 0) { sbuf[2 * wave] = a; sbuf[2 * wave + 1] = b; }
-  __syncthreads();
-  double ta = 0.0, tb = 0.0;
-#pragma unroll
-  for (int w = 0; w < EW_THREADS / 64; w++) { ta += sbuf[2 * w]; tb += sbuf[2 * w + 1]; }
-  a = ta; b = tb;
-}
-
-// ------------------------------------------------------------------ BN forward finalize
-// one workgroup per channel: deterministic sum of the conv epilogue's partials in double
-__global__ void __launch_bounds__(EW_THREADS)
-bn_finalize_kernel(const float* __restrict__ partial, int nblk, int C, double count, const float* __restrict__ gamma,
-                   const float* __restrict__ beta, float eps, float momentum, float* __restrict__ run_mean,
-                   float* __restrict__ run_var, float* __restrict__ nbt, float* __restrict__ scale,
-                   float* __restrict__ shift, float* __restrict__ mean_o, float* __restrict__ rstd_o) {
-  __shared__ double sbuf[EW_THREADS];
-  const int c = blockIdx.x;
-  // per-channel operands of the tail are fetched first: their latency overlaps the partial loads instead of forming a second
-  // dependent round trip after the reduction
-  float g = 0.f, bt = 0.f, rm0 = 0.f, rv0 = 0.f, nbt0 = 0.f;
-  if (threadIdx.x == 0) { g = gamma[c]; bt = beta[c]; rm0 = run_mean[c]; rv0 = run_var[c]; if (c == 0 && nbt) nbt0 = nbt[0]; }
-  double s1 = 0.0, s2 = 0.0;
-  for (int k = threadIdx.x; k < nblk; k += EW_THREADS) {
-    s1 += (double)partial[((long)k * 2 + 0) * C + c];
-    s2 += (double)partial[((long)k * 2 + 1) * C + c];
-  }
-  block_sum2_d(s1, s2, sbuf);
-  if (threadIdx.x == 0) {
-    const double mean = s1 / count;
-    double var = s2 / count - mean * mean;  // biased (torch BatchNorm2d training normalisation)
-    if (var < 0.0) var = 0.0;
-    const float rstd = (float)(1.0 / sqrt(var + (double)eps));
-    scale[c] = g * rstd;
-    shift[c] = bt - (float)mean * g * rstd;
-    mean_o[c] = (float)mean;
-    rstd_o[c] = rstd;
-    // running stats: momentum 0.03, unbiased variance (Convs.cs:41-42,48)
-    const double unb = count > 1.0 ? var * count / (count - 1.0) : var;
-    run_mean[c] = (1.0f - momentum) * rm0 + momentum * (float)mean;
-    run_var[c] = (1.0f - momentum) * rv0 + momentum * (float)unb;
-    if (c == 0 && nbt) nbt[0] = nbt0 + 1.0f;
-  }
-}
-int ys_bn_finalize_launch(hipStream_t st, const float* partial, int nblk, int C, long count, const float* gamma,
-                          const float* beta, float eps, float momentum, float* run_mean, float* run_var, float* nbt,
-                          float* scale, float* shift, float* mean, float* rstd) {
-  YS_LAUNCH(bn_finalize_kernel, C, EW_THREADS, st, partial, nblk, C, (double)count, gamma, beta, eps, momentum,
-            run_mean, run_var, nbt, scale, shift, mean, rstd);
-  return YS_OK;
-}
-
-__global__ void __launch_bounds__(EW_THREADS)
-bn_eval_coeffs_kernel(int C, const float* __restrict__ gamma, const float* __restrict__ beta,
-                      const float* __restrict__ rm, const float* __restrict__ rv, float eps,
-                      float* __restrict__ scale, float* __restrict__ shift) {
-  const int c = blockIdx.x * blockDim.x + threadIdx.x;
-  if (c >= C) return;
-  const float rstd = 1.0f / sqrtf(rv[c] + eps);
-  scale[c] = gamma[c] * rstd;
-  shift[c] = beta[c] - rm[c] * gamma[c] * rstd;
-}
-int ys_bn_eval_coeffs_launch(hipStream_t st, int C, const float* gamma, const float* beta, const float* rm,
-                             const float* rv, float eps, float* scale, float* shift) {
-  YS_LAUNCH(bn_eval_coeffs_kernel, ys_cdiv(C, EW_THREADS), EW_THREADS, st, C, gamma, beta, rm, rv, eps, scale, shift);
-  return YS_OK;
-}
-
-// ------------------------------------------------------------------ BN + act apply (training forward, pass 2)
-// ACT is a template parameter: a run-time flag inside the unrolled element loop splits it into basic blocks (see chan_reduce);
-// rows * CG < 2^31 (every graph here) takes 32-bit index arithmetic instead of a ~80-instruction 64-bit division.
-template <class T, bool ACT>
-__global__ void __launch_bounds__(EW_THREADS)
-bn_act_apply_kernel(const T* __restrict__ y, long rows, int C, const float* __restrict__ scale,
-                    const float* __restrict__ shift, const T* __restrict__ res, int res_ldc, int res_coff,
-                    T* __restrict__ z, int z_ldc, int z_coff, int small, unsigned* __restrict__ amax) {
-  constexpr int EPL = Elem<T>::EPL;
-  const int CG = C / EPL;
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  float mx = 0.f;
-  if (i < rows * CG) {
-    long row; int c;
-    if (small) { const unsigned iu = (unsigned)i, r = iu / (unsigned)CG; row = r; c = (int)(iu - r * (unsigned)CG) * EPL; }
-    else { row = i / CG; c = (int)(i - row * CG) * EPL; }
-    float f[EPL], r[EPL], sc[EPL], sh[EPL];
-    ys_unpack<T>(ys_ld16(y + row * C + c), f);
-    if (res) ys_unpack<T>(ys_ld16(res + row * res_ldc + res_coff + c), r);
-    ys_ldcoef<EPL>(scale + c, sc);
-    ys_ldcoef<EPL>(shift + c, sh);
-#pragma unroll
-    for (int e = 0; e < EPL; e++) {
-      float u = f[e] * sc[e] + sh[e];
-      if (ACT) u = ys_silu(u);
-      if (res) u += r[e];
-      f[e] = u;
-      mx = fmaxf(mx, fabsf(u));
-    }
-    ys_st16(z + row * z_ldc + z_coff + c, ys_pack<T>(f));
-  }
-  // fp8 mode: amax(|z|) of the tensor this pass writes feeds the NEXT step's activation scale (delayed scaling, f8.hip); the
-  // maximum of non-negative floats is order-independent, so the atomic keeps the step deterministic
-  if (amax) ys_amax_update(amax, mx);
-}
-// amax bookkeeping of a grid-stride pass: workgroup maximum through LDS, then ONE slot update per workgroup
-__device__ inline void ys_amax_update_wg(unsigned* slots, float mx) {
-  __shared__ float s_wmax[EW_THREADS / 64];
-  mx = ys_wave_max(mx);
-  if ((threadIdx.x & 63) == 0) s_wmax[threadIdx.x >> 6] = mx;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float v = s_wmax[0];
-    for (int w = 1; w < EW_THREADS / 64; w++) v = fmaxf(v, s_wmax[w]);
-    if (v > 0.f) {
-      unsigned* slot = slots + (blockIdx.x & (YS_AMAX_WAYS - 1));
-      const unsigned cur = *(volatile unsigned*)slot;
-      if (ys_f2u(v) > cur) atomicMax(slot, ys_f2u(v));
-    }
-  }
-}
-
-// fp8 mode, bf16 storage: the same pass also writes the e4m3 image (dense [rows][C], the consumer's delayed activation scale) of the
-// tensor it produces and records amax(|z|) -- used when the next convolution of the schedule reads exactly this
-// view and will run the fp8 blocked-GEMM kernel (Bottleneck cv1 -> cv2), instead of a quantisation pass over z.  Grid-stride with a
-// bounded grid: one amax atomic per workgroup.
-template <bool ACT>
-__global__ void __launch_bounds__(EW_THREADS)
-bn_act_apply_q8_kernel(const bf16_t* __restrict__ y, long rows, int C, const float* __restrict__ scale, const float* __restrict__ shift,
-                       const bf16_t* __restrict__ res, int res_ldc, int res_coff, bf16_t* __restrict__ z, int z_ldc, int z_coff,
-                       unsigned char* __restrict__ q8, const float* __restrict__ qscale, unsigned* __restrict__ amax) {
-  const int CG = C / 8;
-  const long n = rows * CG;
-  const float qs = qscale[0];
-  float mx = 0.f;
-  for (long i = (long)blockIdx.x * EW_THREADS + threadIdx.x; i < n; i += (long)gridDim.x * EW_THREADS) {
-    const long row = i / CG; const int c = (int)(i - row * CG) * 8;
-    float f[8], r[8], sc[8], sh[8];
-    ys_unpack<bf16_t>(ys_ld16(y + row * C + c), f);
-    if (res) ys_unpack<bf16_t>(ys_ld16(res + row * res_ldc + res_coff + c), r);
-    ys_ldcoef<8>(scale + c, sc);
-    ys_ldcoef<8>(shift + c, sh);
-#pragma unroll
-    for (int e = 0; e < 8; e++) {
-      float u = f[e] * sc[e] + sh[e];
-      if (ACT) u = ys_silu(u);
-      if (res) u += r[e];
-      f[e] = u;
-    }
-    const uint4 pk = ys_pack<bf16_t>(f);
-    ys_st16(z + row * z_ldc + z_coff + c, pk);
-    ys_unpack<bf16_t>(pk, f);                   // quantise the stored (bf16-rounded) value: what every other reader of z sees
-#pragma unroll
-    for (int e = 0; e < 8; e++) { mx = fmaxf(mx, fabsf(f[e])); f[e] *= qs; }
-    *(uint2*)(q8 + row * C + c) = ys_pack_f8x8<0>(f);
-  }
-  if (amax) ys_amax_update_wg(amax, mx);
-}
-int ys_bn_act_apply_q8_launch(hipStream_t st, const void* y, long rows, int C, const float* scale, const float* shift, int act,
-                              const void* res, int res_ldc, int res_coff, void* z, int z_ldc, int z_coff, void* q8,
-                              const float* qscale, unsigned* amax) {
-  const long n = rows * (C / 8);
-  const long gcap = 2048;
-  long g = ys_cdiv(n, EW_THREADS * 4L); if (g > gcap) g = gcap; if (g < 1) g = 1;
-#define BAQ_LAUNCH(AF) YS_LAUNCH((bn_act_apply_q8_kernel<AF>), (int)g, EW_THREADS, st, (const bf16_t*)y, rows, C, scale, shift, (const bf16_t*)res, res_ldc, res_coff, (bf16_t*)z, z_ldc, z_coff, (unsigned char*)q8, qscale, amax)
-  if (act) BAQ_LAUNCH(true); else BAQ_LAUNCH(false);
-#undef BAQ_LAUNCH
-  return YS_OK;
-}
-
-int ys_bn_act_apply_launch(hipStream_t st, int dtype, const void* y, long rows, int C, const float* scale,
-                           const float* shift, int act, const void* res, int res_ldc, int res_coff, void* z,
-                           int z_ldc, int z_coff, unsigned* amax) {
-  const int epl = dtype == YS_BF16 ? 8 : 4;
-  const long n = rows * (C / epl);
-  const int small = n < (1L << 31) ? 1 : 0;
-#define BA_LAUNCH(TT, AF) YS_LAUNCH((bn_act_apply_kernel<TT, AF>), ys_cdiv(n, EW_THREADS), EW_THREADS, st, (const TT*)y, rows, C, scale, shift, (const TT*)res, res_ldc, res_coff, (TT*)z, z_ldc, z_coff, small, amax)
-  if (dtype == YS_BF16) { if (act) BA_LAUNCH(bf16_t, true); else BA_LAUNCH(bf16_t, false); }
-  else { if (act) BA_LAUNCH(float, true); else BA_LAUNCH(float, false); }
-#undef BA_LAUNCH
-  return YS_OK;
-}
-
-// ------------------------------------------------------------------ BN finalize + apply in one pass (round 5)
-// The convolution left the unit's batch statistics as fixed-point integer sums (ys_stat_acc_add: 64-bit atomics, YS_STAT_SHARDS copies).  Every workgroup adds the
-// copies and does bn_finalize_kernel's arithmetic for all C channels itself (same integers in, same double arithmetic: the same coefficients in every workgroup, no
-// hand-off between workgroups) into LDS; workgroup 0 also stores scale / shift / mean / rstd for the backward pass and updates the running statistics.  Grid-stride
-// with a bounded grid so that the C-channel prologue is paid ~2 thousand times per launch, not once per 256 vectors.  The separate bn_finalize launch (4.9 us + a
-// kernel boundary, 45 per YOLOv8n step) goes.
-template <class T, bool ACT>
-__global__ void __launch_bounds__(EW_THREADS)
-bn_fin_apply_kernel(const T* __restrict__ y, long rows, int C, BnAccFin f, const T* __restrict__ res, int res_ldc, int res_coff,
-                    T* __restrict__ z, int z_ldc, int z_coff) {
-  constexpr int EPL = Elem<T>::EPL;
-  YS_DYN_LDS(lds);
-  float* s_sc = (float*)lds;                   // [C] scale, [C] shift
-  float* s_sh = s_sc + C;
-  for (int c = threadIdx.x; c < C; c += EW_THREADS) {
-    long long a1 = 0, a2 = 0;
-    bool poisoned = false;
-#pragma unroll
-    for (int s = 0; s < YS_STAT_SHARDS; s++) {
-      const unsigned long long w2 = f.acc[((long)s * C + c) * 2 + 1];
-      poisoned |= (w2 >> 62) != 0;               // a producer workgroup saw a non-finite / out-of-range partial (ys_stat_acc_add)
-      a1 += (long long)f.acc[((long)s * C + c) * 2 + 0];
-      a2 += (long long)w2;
-    }
-    const double s1 = (double)a1 * (1.0 / (double)YS_STAT_FIX), s2 = (double)a2 * (1.0 / (double)YS_STAT_FIX);
-    double mean = s1 / f.count;
-    double var = s2 / f.count - mean * mean;   // biased (torch BatchNorm2d training normalisation)
-    if (var < 0.0) var = 0.0;
-    if (poisoned) { mean = __builtin_nan(""); var = mean; }
-    const float g = f.gamma[c], bt = f.beta[c];
-    const float rstd = (float)(1.0 / sqrt(var + (double)f.eps));
-    const float sc = g * rstd, sh = bt - (float)mean * g * rstd;
-    s_sc[c] = sc; s_sh[c] = sh;
-    if (blockIdx.x == 0) {
-      f.scale[c] = sc; f.shift[c] = sh; f.mean[c] = (float)mean; f.rstd[c] = rstd;
-      // running stats: momentum 0.03, unbiased variance (Convs.cs:41-42,48)
-      const double unb = f.count > 1.0 ? var * f.count / (f.count - 1.0) : var;
-      f.run_mean[c] = (1.0f - f.momentum) * f.run_mean[c] + f.momentum * (float)mean;
-      f.run_var[c] = (1.0f - f.momentum) * f.run_var[c] + f.momentum * (float)unb;
-      if (c == 0 && f.nbt) f.nbt[0] = f.nbt[0] + 1.0f;
-    }
-  }
-  __syncthreads();
-  const int CG = C / EPL;
-  const long n = rows * CG;
-  for (long i = (long)blockIdx.x * EW_THREADS + threadIdx.x; i < n; i += (long)gridDim.x * EW_THREADS) {
-    const long row = i / CG; const int c = (int)(i - row * CG) * EPL;
-    float v[EPL], r[EPL];
-    ys_unpack<T>(ys_ld16(y + row * C + c), v);
-    if (res) ys_unpack<T>(ys_ld16(res + row * res_ldc + res_coff + c), r);
-#pragma unroll
-    for (int e = 0; e < EPL; e++) {
-      float u = v[e] * s_sc[c + e] + s_sh[c + e];
-      if (ACT) u = ys_silu(u);
-      if (res) u += r[e];
-      v[e] = u;
-    }
-    ys_st16(z + row * z_ldc + z_coff + c, ys_pack<T>(v));
-  }
-}
-int ys_bn_fin_apply_launch(hipStream_t st, int dtype, const void* y, long rows, int C, const BnAccFin& f, int act, const void* res, int res_ldc, int res_coff,
-                           void* z, int z_ldc, int z_coff) {
-  const int epl = dtype == YS_BF16 ? 8 : 4;
-  const long n = rows * (C / epl);
-  const long gcap = 2048;
-  long g = ys_cdiv(n, EW_THREADS * 2L); if (g > gcap) g = gcap; if (g < 1) g = 1;
-  const size_t lds = (size_t)2 * C * sizeof(float);
-#define BFA_LAUNCH(TT, AF) YS_LAUNCH_LDS((bn_fin_apply_kernel<TT, AF>), (int)g, EW_THREADS, lds, st, (const TT*)y, rows, C, f, (const TT*)res, res_ldc, res_coff, (TT*)z, z_ldc, z_coff)
-  if (dtype == YS_BF16) { if (act) BFA_LAUNCH(bf16_t, true); else BFA_LAUNCH(bf16_t, false); }
-  else { if (act) BFA_LAUNCH(float, true); else BFA_LAUNCH(float, false); }
-#undef BFA_LAUNCH
-  return YS_OK;
-}
-
-// ------------------------------------------------------------------ per-channel reductions over rows
-// thread t owns channel vector cv = t % CG and row lane t / CG; workgroup blk owns a contiguous row range.
-// MODE 0: BN backward (sum du, sum du*xhat), optional res_grad += dz.   MODE 1: plain column sum.
-constexpr int CR_U = 2;   // rows per software-pipelined trip of chan_reduce_kernel
-template <class T, int MODE, bool RG = false, bool ACT = false>
-__global__ void __launch_bounds__(EW_THREADS)
-chan_reduce_kernel(const T* __restrict__ dz, int dz_ldc, int dz_coff, const T* __restrict__ y, long rows, int C,
-                   const float* __restrict__ scale, const float* __restrict__ shift, const float* __restrict__ mean,
-                   const float* __restrict__ rstd, int act, T* __restrict__ rg, int rg_ldc, int rg_coff,
-                   float* __restrict__ partial, long rpb, long bstride) {
-  constexpr int EPL = Elem<T>::EPL;
-  constexpr int NV = MODE == 1 ? EPL : 2 * EPL;          // running sums per thread
-  __shared__ float sAcc[NV][EW_THREADS];                 // [value][thread]: conflict-free for consecutive threads
-  const int CG = C / EPL;
-  const int RP = EW_THREADS / CG;  // rows per pass
-  const int tid = threadIdx.x;
-  const int cv = tid % CG, rl = tid / CG;
-  const int c = cv * EPL;
-  const long rows_per_blk = (rows + gridDim.x - 1) / gridDim.x;
-  const long r0 = (long)blockIdx.x * rows_per_blk;
-  long r1 = r0 + rows_per_blk;
-  if (r1 > rows) r1 = rows;
-  float a1[EPL], a2[EPL];
-#pragma unroll
-  for (int e = 0; e < EPL; e++) { a1[e] = 0.f; a2[e] = 0.f; }
-  if (rl < RP) {
-    // the second BN-backward sum is accumulated against the raw conv output (sum du*y); chan_finalize turns it into
-    // sum du*xhat = rstd * (sum du*y - mean * sum du) in double.  Keeping mean / rstd out of the loop saves 16 VGPRs per
-    // thread (occupancy 3 -> 5 waves per SIMD), which is what this latency-bound pass needs.
-    float sc[EPL], sh[EPL];
-    if (MODE == 0) { ys_ldcoef<EPL>(scale + c, sc); ys_ldcoef<EPL>(shift + c, sh); }
-    // Software-pipelined over trips of U rows: the loads of trip t+1 are issued before the arithmetic of trip t.  The SiLU
-    // derivative is ~18 VALU issue slots per element, i.e. about as long as the HBM latency of a trip; without the
-    // prefetch every wave of a SIMD alternates in step between "all waiting" and "all computing" and the two never overlap.
-    constexpr int U = CR_U;
-    const bool dense = MODE != 1 || rpb == rows;         // no per-image row stride (always for the BN passes): skip the 64-bit division
-    const long step = (long)RP * U;
-    auto issue = [&](long rowb, uint4 (&gv)[U], uint4 (&fv)[U], uint4 (&ov)[U]) {
-#pragma unroll
-      for (int k = 0; k < U; k++) {
-        // rows past the end are clamped to the last row and ignored by consume(): loads inside exec-masked branches make the
-        // compiler fall back to s_waitcnt vmcnt(0) at the join, which would wait for the prefetch as well
-        long row = rowb + (long)k * RP;
-        row = row < r1 ? row : r1 - 1;
-        long zrow = row;
-        if (!dense) { const long zb = row / rpb; zrow = zb * bstride + (row - zb * rpb); }   // dz rows strided per image (head outputs)
-        gv[k] = ys_ld16(dz + zrow * dz_ldc + dz_coff + c);
-        if (MODE == 0) {
-          fv[k] = ys_ld16(y + row * C + c);
-          if (RG) ov[k] = ys_ld16(rg + row * rg_ldc + rg_coff + c);
-        } else { fv[k] = ys_zero16(); }
-        if (!RG) ov[k] = ys_zero16();
-      }
-    };
-    auto consume = [&](long rowb, const uint4 (&gv)[U], const uint4 (&fv)[U], const uint4 (&ov)[U]) {
-#pragma unroll
-      for (int k = 0; k < U; k++) {
-        const long row = rowb + (long)k * RP;
-        if (row >= r1) continue;
-        float g[EPL];
-        ys_unpack<T>(gv[k], g);
-        if (MODE == 0) {
-          float f[EPL];
-          ys_unpack<T>(fv[k], f);
-          if (RG) {
-            float o[EPL];
-            ys_unpack<T>(ov[k], o);
-#pragma unroll
-            for (int e = 0; e < EPL; e++) o[e] += g[e];
-            ys_st16(rg + row * rg_ldc + rg_coff + c, ys_pack<T>(o));
-          }
-#pragma unroll
-          for (int e = 0; e < EPL; e++) {
-            const float u = f[e] * sc[e] + sh[e];
-            const float du = ACT ? g[e] * ys_silu_grad(u) : g[e];   // compile-time: a run-time flag here splits the unrolled
-            a1[e] += du;                                            // elements into basic blocks and serialises the exp/rcp chains
-            a2[e] += du * f[e];
-          }
-        } else if (MODE == 2) {
-#pragma unroll
-          for (int e = 0; e < EPL; e++) { a1[e] += g[e]; a2[e] += g[e] * g[e]; }
-        } else {
-#pragma unroll
-          for (int e = 0; e < EPL; e++) a1[e] += g[e];
-        }
-      }
-    };
-    uint4 gA[U], fA[U], oA[U], gB[U], fB[U], oB[U];
-    long rowb = r0 + rl;
-    if (rowb < r1) {
-      issue(rowb, gA, fA, oA);
-      while (true) {                                     // two trips per iteration: the buffers alternate without dynamic indexing
-        issue(rowb + step, gB, fB, oB);                  // (unconditional: past the end it re-reads the last row)
-        consume(rowb, gA, fA, oA);
-        rowb += step;
-        if (rowb >= r1) break;
-        issue(rowb + step, gA, fA, oA);
-        consume(rowb, gB, fB, oB);
-        rowb += step;
-        if (rowb >= r1) break;
-      }
-    }
-  }
-  // workgroup reduction over the RP row lanes: pairwise halving with every thread taking part (the previous form -- CG threads
-  // each walking RP rows -- was a serial chain of up to 2048 LDS reads per workgroup for the 16-channel layers)
-#pragma unroll
-  for (int e = 0; e < EPL; e++) { sAcc[e][tid] = a1[e]; if (MODE != 1) sAcc[EPL + e][tid] = a2[e]; }
-  __syncthreads();
-  for (int n = RP; n > 1;) {
-    const int half = (n + 1) >> 1;
-    if (rl + half < n) {
-#pragma unroll
-      for (int v = 0; v < NV; v++) sAcc[v][tid] += sAcc[v][tid + half * CG];
-    }
-    __syncthreads();
-    n = half;
-  }
-  if (tid < CG) {
-#pragma unroll
-    for (int e = 0; e < EPL; e++) {
-      partial[((long)blockIdx.x * 2 + 0) * C + c + e] = sAcc[e][tid];
-      partial[((long)blockIdx.x * 2 + 1) * C + c + e] = MODE != 1 ? sAcc[(MODE != 1 ? EPL : 0) + e][tid] : 0.f;
-    }
-  }
-}
-
-static int reduce_blocks(long rows, int C, int epl) {
-  const int cg = C / epl;
-  const int rp = EW_THREADS / cg;
-  // prefer 16 row passes per workgroup, but keep >= 512 workgroups (2 per CU) while a workgroup still has a few trips of
-  // work; at most 768 (3 per CU, one resident round at 4-5 waves per SIMD): more partial rows only lengthen the finalize
-  // kernel and add a ragged second round (measured: 2048 -> 12.86, 1024 -> 12.77, 768/512 -> 12.75 ms/step)
-  const long maxnb = 768, minnb = 512;
-  long passes = 16;
-  while (passes > 4 && (rows + (long)rp * passes - 1) / ((long)rp * passes) < minnb) passes >>= 1;
-  long nb = (rows + (long)rp * passes - 1) / ((long)rp * passes);
-  if (nb > maxnb) nb = maxnb;
-  if (nb < 1) nb = 1;
-  return (int)nb;
-}
-int ys_colsum_blocks(long rows, int C, int dtype) { return reduce_blocks(rows, C, dtype == YS_BF16 ? 8 : 4); }
-
-int ys_bn_bwd_reduce_launch(hipStream_t st, int dtype, const void* dz, int dz_ldc, int dz_coff, const void* y, long rows,
-                            int C, const float* scale, const float* shift, const float* mean, const float* rstd,
-                            int act, void* res_grad, int rg_ldc, int rg_coff, float* partial, int* nblk_out) {
-  const int epl = dtype == YS_BF16 ? 8 : 4;
-  if (C % epl || C / epl > EW_THREADS) { ys_set_error("bn_bwd: unsupported channel count %d", C); return YS_ERR_UNSUPPORTED; }
-  const int nb = reduce_blocks(rows, C, epl);
-  *nblk_out = nb;
-#define CR_LAUNCH(TT, RGF, ACTF) \
-  YS_LAUNCH((chan_reduce_kernel<TT, 0, RGF, ACTF>), nb, EW_THREADS, st, (const TT*)dz, dz_ldc, dz_coff, (const TT*)y, rows, C, scale, shift, mean, rstd, act, (TT*)res_grad, rg_ldc, rg_coff, partial, rows, rows)
-  const int variant = (dtype == YS_BF16 ? 4 : 0) | (res_grad ? 2 : 0) | (act ? 1 : 0);
-  switch (variant) {
-    case 0: CR_LAUNCH(float, false, false); break;
-    case 1: CR_LAUNCH(float, false, true); break;
-    case 2: CR_LAUNCH(float, true, false); break;
-    case 3: CR_LAUNCH(float, true, true); break;
-    case 4: CR_LAUNCH(bf16_t, false, false); break;
-    case 5: CR_LAUNCH(bf16_t, false, true); break;
-    case 6: CR_LAUNCH(bf16_t, true, false); break;
-    default: CR_LAUNCH(bf16_t, true, true); break;
-  }
-#undef CR_LAUNCH
-  return YS_OK;
-}
-
-// per-channel (sum, sum of squares) partials of a dense [rows][C] tensor (BN statistics of depthwise conv outputs)
-int ys_chan_stats_launch(hipStream_t st, int dtype, const void* y, long rows, int C, float* partial, int* nblk_out) {
-  const int epl = dtype == YS_BF16 ? 8 : 4;
-  if (C % epl || C / epl > EW_THREADS) { ys_set_error("chan_stats: unsupported channel count %d", C); return YS_ERR_UNSUPPORTED; }
-  const int nb = reduce_blocks(rows, C, epl);
-  *nblk_out = nb;
-  if (dtype == YS_BF16)
-    YS_LAUNCH((chan_reduce_kernel<bf16_t, 2>), nb, EW_THREADS, st, (const bf16_t*)y, C, 0, (const bf16_t*)nullptr, rows, C, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, 0, (bf16_t*)nullptr, 0, 0, partial, rows, rows);
-  else
-    YS_LAUNCH((chan_reduce_kernel<float, 2>), nb, EW_THREADS, st, (const float*)y, C, 0, (const float*)nullptr, rows, C, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, 0, (float*)nullptr, 0, 0, partial, rows, rows);
-  return YS_OK;
-}
-
-// one workgroup per channel: sums partials; MODE 0 -> BN grads + coefficients, MODE 1 -> bias grad.
-// The partial rows of a channel come from the source that covers it (FinSrc): one source = the channel-reduction pass; several =
-// the dgrad launches whose epilogues produced the sums (fused BN-backward reduction, BnRedSeg), each with its own row count.
-template <int MODE>
-__global__ void __launch_bounds__(EW_THREADS)
-chan_finalize_kernel(FinSrc src, int C, double count, float* __restrict__ g0,
-                     float* __restrict__ g1, float* __restrict__ c1, float* __restrict__ c2,
-                     const float* __restrict__ scale, const float* __restrict__ mean, const float* __restrict__ rstd) {
-  __shared__ double sbuf[EW_THREADS];
-  const int c = blockIdx.x;
-  const float* __restrict__ partial = src.p[0]; int nblk = src.nblk[0];
-#pragma unroll
-  for (int k = 1; k < YS_BNRED_MAXSEG; k++) if (k < src.n && c >= src.c1[k - 1]) { partial = src.p[k]; nblk = src.nblk[k]; }
-  float sc = 0.f, mu = 0.f, rs = 0.f, g0p = 0.f, g1p = 0.f;   // tail operands first (see bn_finalize_kernel)
-  if (threadIdx.x == 0) {
-    g0p = g0[c];
-    if (MODE == 0) { sc = scale[c]; mu = mean[c]; rs = rstd[c]; g1p = g1[c]; }
-  }
-  double s1 = 0.0, s2 = 0.0;
-  for (int k = threadIdx.x; k < nblk; k += EW_THREADS) {
-    s1 += (double)partial[((long)k * 2 + 0) * C + c];
-    if (MODE == 0) s2 += (double)partial[((long)k * 2 + 1) * C + c];
-  }
-  block_sum2_d(s1, s2, sbuf);
-  if (threadIdx.x == 0) {
-    if (MODE == 0) {
-      s2 = (double)rs * (s2 - (double)mu * s1);   // sum(du * xhat) from sum(du * y) (chan_reduce_kernel)
-      g0[c] = g0p + (float)s2;  // dgamma += sum(du * xhat)
-      g1[c] = g1p + (float)s1;  // dbeta  += sum(du)
-      // dy = gamma*rstd*(du - m1 - xhat*m2) = scale*du - k2 - y*k3  (m1 = mean(du), m2 = mean(du*xhat))
-      const float m1 = (float)(s1 / count), m2 = (float)(s2 / count);
-      c1[c] = sc * (m1 - mu * rs * m2);   // k2
-      c2[c] = sc * rs * m2;               // k3
-    } else {
-      g0[c] = g0p + (float)s1;
-    }
-  }
-}
-int ys_bn_bwd_finalize_src_launch(hipStream_t st, const FinSrc& src, int C, long count, float* dgamma, float* dbeta, float* c1,
-                                  float* c2, const float* scale, const float* mean, const float* rstd) {
-  YS_LAUNCH((chan_finalize_kernel<0>), C, EW_THREADS, st, src, C, (double)count, dgamma, dbeta, c1, c2, scale, mean, rstd);
-  return YS_OK;
-}
-int ys_bn_bwd_finalize_launch(hipStream_t st, const float* partial, int nblk, int C, long count, float* dgamma,
-                              float* dbeta, float* c1, float* c2, const float* scale, const float* mean, const float* rstd) {
-  FinSrc src{}; src.n = 1; src.p[0] = partial; src.nblk[0] = nblk; src.c1[0] = C;
-  return ys_bn_bwd_finalize_src_launch(st, src, C, count, dgamma, dbeta, c1, c2, scale, mean, rstd);
-}
-
-int ys_colsum_launch(hipStream_t st, int dtype, const void* x, int ldc, int coff, long rows, long rows_per_b,
-                     long bstride, int C, float* partial, float* grad) {
-  const int epl = dtype == YS_BF16 ? 8 : 4;
-  const int Cp = (C + epl - 1) / epl * epl;  // padded channels of the view are zero
-  if (Cp / epl > EW_THREADS) { ys_set_error("colsum: unsupported channel count %d", C); return YS_ERR_UNSUPPORTED; }
-  const int nb = reduce_blocks(rows, Cp, epl);
-  if (dtype == YS_BF16)
-    YS_LAUNCH((chan_reduce_kernel<bf16_t, 1>), nb, EW_THREADS, st, (const bf16_t*)x, ldc, coff, (const bf16_t*)nullptr, rows, Cp, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, 0, (bf16_t*)nullptr, 0, 0, partial, rows_per_b, bstride);
-  else
-    YS_LAUNCH((chan_reduce_kernel<float, 1>), nb, EW_THREADS, st, (const float*)x, ldc, coff, (const float*)nullptr, rows, Cp, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, 0, (float*)nullptr, 0, 0, partial, rows_per_b, bstride);
-  // partial rows are Cp wide; finalize only the C real channels
-  FinSrc src{}; src.n = 1; src.p[0] = partial; src.nblk[0] = nb; src.c1[0] = Cp;
-  YS_LAUNCH((chan_finalize_kernel<1>), C, EW_THREADS, st, src, Cp, 1.0, grad, (float*)nullptr, (float*)nullptr, (float*)nullptr, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr);
-  return YS_OK;
-}
-
-template <class T, bool ACT>
-__global__ void __launch_bounds__(EW_THREADS)
-bn_bwd_apply_kernel(const T* __restrict__ dz, int dz_ldc, int dz_coff, const T* __restrict__ y, long rows, int C,
-                    const float* __restrict__ scale, const float* __restrict__ shift, const float* __restrict__ k2,
-                    const float* __restrict__ k3, T* __restrict__ dy, int small, unsigned* __restrict__ amax,
-                    T* __restrict__ rg, int rg_ldc, int rg_coff) {
-  constexpr int EPL = Elem<T>::EPL;
-  const int CG = C / EPL;
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  float mx = 0.f;
-  if (i < rows * CG) {
-    long row; int c;
-    if (small) { const unsigned iu = (unsigned)i, r = iu / (unsigned)CG; row = r; c = (int)(iu - r * (unsigned)CG) * EPL; }
-    else { row = i / CG; c = (int)(i - row * CG) * EPL; }
-    float g[EPL], f[EPL], sc[EPL], sh[EPL], a2[EPL], a3[EPL];
-    ys_unpack<T>(ys_ld16(dz + row * dz_ldc + dz_coff + c), g);
-    ys_unpack<T>(ys_ld16(y + row * C + c), f);
-    if (rg) {     // d(residual input) += dz: the Bottleneck shortcut's share, done here when the reduction pass that used to carry it is fused away
-      float o[EPL];
-      T* rp = rg + row * rg_ldc + rg_coff + c;
-      ys_unpack<T>(ys_ld16(rp), o);
-#pragma unroll
-      for (int e = 0; e < EPL; e++) o[e] += g[e];
-      ys_st16(rp, ys_pack<T>(o));
-    }
-    ys_ldcoef<EPL>(scale + c, sc); ys_ldcoef<EPL>(shift + c, sh); ys_ldcoef<EPL>(k2 + c, a2); ys_ldcoef<EPL>(k3 + c, a3);
-#pragma unroll
-    for (int e = 0; e < EPL; e++) {
-      const float u = f[e] * sc[e] + sh[e];
-      const float du = ACT ? g[e] * ys_silu_grad(u) : g[e];
-      f[e] = sc[e] * du - a2[e] - f[e] * a3[e];
-      mx = fmaxf(mx, fabsf(f[e]));
-    }
-    ys_st16(dy + row * C + c, ys_pack<T>(f));
-  }
-  if (amax) ys_amax_update(amax, mx);          // fp8 mode: amax(|dy|) for the next step's gradient scale (f8.hip)
-}
-// fp8 mode, bf16 storage: the same pass also writes the e5m2 image of dy (dense [rows][C], scaled by the layer's delayed gradient
-// scale) that the fp8 dgrad kernel consumes, and records amax(|dy|) for the next step's scale -- instead of a separate quantisation
-// pass over dy (f8_quant_view_kernel: 2 B read + 1 B written per element and layer).  Grid-stride with a bounded grid so that the
-// amax bookkeeping is one atomic per workgroup (one-shot waves each paying a dependent global round trip were measured 5x slower).
-template <bool ACT>
-__global__ void __launch_bounds__(EW_THREADS)
-bn_bwd_apply_q8_kernel(const bf16_t* __restrict__ dz, int dz_ldc, int dz_coff, const bf16_t* __restrict__ y, long rows, int C,
-                       const float* __restrict__ scale, const float* __restrict__ shift, const float* __restrict__ k2,
-                       const float* __restrict__ k3, bf16_t* __restrict__ dy, unsigned char* __restrict__ q8,
-                       const float* __restrict__ qscale, unsigned* __restrict__ amax, bf16_t* __restrict__ rg, int rg_ldc, int rg_coff) {
-  const int CG = C / 8;
-  const long n = rows * CG;
-  const float qs = qscale[0];
-  float mx = 0.f;
-  for (long i = (long)blockIdx.x * EW_THREADS + threadIdx.x; i < n; i += (long)gridDim.x * EW_THREADS) {
-    const long row = i / CG; const int c = (int)(i - row * CG) * 8;
-    float g[8], f[8], sc[8], sh[8], a2[8], a3[8];
-    ys_unpack<bf16_t>(ys_ld16(dz + row * dz_ldc + dz_coff + c), g);
-    ys_unpack<bf16_t>(ys_ld16(y + row * C + c), f);
-    if (rg) {
-      float o[8];
-      bf16_t* rp = rg + row * rg_ldc + rg_coff + c;
-      ys_unpack<bf16_t>(ys_ld16(rp), o);
-#pragma unroll
-      for (int e = 0; e < 8; e++) o[e] += g[e];
-      ys_st16(rp, ys_pack<bf16_t>(o));
-    }
-    ys_ldcoef<8>(scale + c, sc); ys_ldcoef<8>(shift + c, sh); ys_ldcoef<8>(k2 + c, a2); ys_ldcoef<8>(k3 + c, a3);
-#pragma unroll
-    for (int e = 0; e < 8; e++) {
-      const float u = f[e] * sc[e] + sh[e];
-      const float du = ACT ? g[e] * ys_silu_grad(u) : g[e];
-      f[e] = sc[e] * du - a2[e] - f[e] * a3[e];
-    }
-    const uint4 pk = ys_pack<bf16_t>(f);
-    ys_st16(dy + row * C + c, pk);
-    ys_unpack<bf16_t>(pk, f);                   // quantise what the bf16 consumers (wgrad) see: the rounded value
-#pragma unroll
-    for (int e = 0; e < 8; e++) { mx = fmaxf(mx, fabsf(f[e])); f[e] *= qs; }
-    *(uint2*)(q8 + row * C + c) = ys_pack_f8x8<1>(f);
-  }
-  if (amax) ys_amax_update_wg(amax, mx);
-}
-int ys_bn_bwd_apply_q8_launch(hipStream_t st, const void* dz, int dz_ldc, int dz_coff, const void* y, long rows, int C,
-                              const float* scale, const float* shift, const float* k2, const float* k3, int act, void* dy,
-                              void* q8, const float* qscale, unsigned* amax, void* rg, int rg_ldc, int rg_coff) {
-  const long n = rows * (C / 8);
-  const long gcap = 2048;
-  long g = ys_cdiv(n, EW_THREADS * 4L); if (g > gcap) g = gcap; if (g < 1) g = 1;
-#define BQ_LAUNCH(AF) YS_LAUNCH((bn_bwd_apply_q8_kernel<AF>), (int)g, EW_THREADS, st, (const bf16_t*)dz, dz_ldc, dz_coff, (const bf16_t*)y, rows, C, scale, shift, k2, k3, (bf16_t*)dy, (unsigned char*)q8, qscale, amax, (bf16_t*)rg, rg_ldc, rg_coff)
-  if (act) BQ_LAUNCH(true); else BQ_LAUNCH(false);
-#undef BQ_LAUNCH
-  return YS_OK;
-}
-
-int ys_bn_bwd_apply_launch(hipStream_t st, int dtype, const void* dz, int dz_ldc, int dz_coff, const void* y, long rows,
-                           int C, const float* scale, const float* shift, const float* k2, const float* k3, int act, void* dy,
-                           unsigned* amax, void* rg, int rg_ldc, int rg_coff) {
-  const int epl = dtype == YS_BF16 ? 8 : 4;
-  const long n = rows * (C / epl);
-  const int small = n < (1L << 31) ? 1 : 0;
-#define BB_LAUNCH(TT, AF) YS_LAUNCH((bn_bwd_apply_kernel<TT, AF>), ys_cdiv(n, EW_THREADS), EW_THREADS, st, (const TT*)dz, dz_ldc, dz_coff, (const TT*)y, rows, C, scale, shift, k2, k3, (TT*)dy, small, amax, (TT*)rg, rg_ldc, rg_coff)
-  if (dtype == YS_BF16) { if (act) BB_LAUNCH(bf16_t, true); else BB_LAUNCH(bf16_t, false); }
-  else { if (act) BB_LAUNCH(float, true); else BB_LAUNCH(float, false); }
-#undef BB_LAUNCH
   return YS_OK;
 }
 
@@ -1475,197 +866,5 @@ int ys_detect_decode_launch(hipStream_t st, int dtype, const void* pd, int ld_pd
     YS_LAUNCH_LDS((detect_decode_kernel<bf16_t>), ys_cdiv(n, DEC_ANCH), EW_THREADS, lds_bytes, st, (const bf16_t*)pd, ld_pd, (const bf16_t*)ps, ld_ps, B, A, nc, reg_max, nl, lo[0], o1, o2, lw[0], w1, w2, ls[0], s1, s2, pred, pred_C, (const bf16_t*)px, ld_px, xkind, nx, kdim, xyxy);
   else
     YS_LAUNCH_LDS((detect_decode_kernel<float>), ys_cdiv(n, DEC_ANCH), EW_THREADS, lds_bytes, st, (const float*)pd, ld_pd, (const float*)ps, ld_ps, B, A, nc, reg_max, nl, lo[0], o1, o2, lw[0], w1, w2, ls[0], s1, s2, pred, pred_C, (const float*)px, ld_px, xkind, nx, kdim, xyxy);
-  return YS_OK;
-}
-
-// ------------------------------------------------------------------ grouped (multi-problem) BatchNorm passes
-// The BN passes of INDEPENDENT Conv units that the planner runs side by side (the tower layers of the three pyramid levels of a
-// head, model.hip run_conv_fwd_group / run_conv_bwd_group) as one launch each: workgroups [end[i-1], end[i]) serve problem i.  The
-// P4 / P5 instances are 5-14 us launch-latency-bound kernels on their own; same arithmetic, same order of operations per element
-// and per channel as the single-problem kernels above (bit-identical results).
-template <class G> __device__ inline int ys_ew_group_pick(const G& g, int bx, int& start) {
-  int pi = 0;
-#pragma unroll
-  for (int k = 0; k + 1 < YS_EW_GROUP_MAX; k++) pi += (int)(k + 1 < g.n && bx >= g.end[k]);
-  start = pi ? g.end[pi - 1] : 0;
-  return pi;
-}
-
-__global__ void __launch_bounds__(EW_THREADS)
-bn_finalize_group_kernel(BnFinGroup grp, float eps, float momentum) {
-  __shared__ double sbuf[EW_THREADS];
-  int start;
-  const BnFinProb& p = grp.p[ys_ew_group_pick(grp, (int)blockIdx.x, start)];
-  const int c = (int)blockIdx.x - start, C = p.C;
-  const float* __restrict__ partial = p.partial;
-  float g = 0.f, bt = 0.f, rm0 = 0.f, rv0 = 0.f, nbt0 = 0.f;
-  if (threadIdx.x == 0) { g = p.gamma[c]; bt = p.beta[c]; rm0 = p.run_mean[c]; rv0 = p.run_var[c]; if (c == 0 && p.nbt) nbt0 = p.nbt[0]; }
-  double s1 = 0.0, s2 = 0.0;
-  for (int k = threadIdx.x; k < p.nblk; k += EW_THREADS) {
-    s1 += (double)partial[((long)k * 2 + 0) * C + c];
-    s2 += (double)partial[((long)k * 2 + 1) * C + c];
-  }
-  block_sum2_d(s1, s2, sbuf);
-  if (threadIdx.x == 0) {
-    const double count = p.count;
-    const double mean = s1 / count;
-    double var = s2 / count - mean * mean;
-    if (var < 0.0) var = 0.0;
-    const float rstd = (float)(1.0 / sqrt(var + (double)eps));
-    p.scale[c] = g * rstd;
-    p.shift[c] = bt - (float)mean * g * rstd;
-    p.mean[c] = (float)mean;
-    p.rstd[c] = rstd;
-    const double unb = count > 1.0 ? var * count / (count - 1.0) : var;
-    p.run_mean[c] = (1.0f - momentum) * rm0 + momentum * (float)mean;
-    p.run_var[c] = (1.0f - momentum) * rv0 + momentum * (float)unb;
-    if (c == 0 && p.nbt) p.nbt[0] = nbt0 + 1.0f;
-  }
-}
-int ys_bn_finalize_group_launch(hipStream_t st, const BnFinProb* probs, int n, float eps, float momentum) {
-  if (n < 1 || n > YS_EW_GROUP_MAX) { ys_set_error("bn finalize group: %d problems", n); return YS_ERR_INVALID_ARG; }
-  BnFinGroup grp{};
-  grp.n = n;
-  int total = 0;
-  for (int i = 0; i < n; i++) { grp.p[i] = probs[i]; total += probs[i].C; grp.end[i] = total; }
-  for (int i = n; i < YS_EW_GROUP_MAX; i++) grp.end[i] = total;
-  YS_LAUNCH(bn_finalize_group_kernel, total, EW_THREADS, st, grp, eps, momentum);
-  return YS_OK;
-}
-
-template <class T, bool ACT>
-__global__ void __launch_bounds__(EW_THREADS)
-bn_act_apply_group_kernel(BnApplyGroup grp) {
-  constexpr int EPL = Elem<T>::EPL;
-  int start;
-  const BnApplyProb& p = grp.p[ys_ew_group_pick(grp, (int)blockIdx.x, start)];
-  const int C = p.C, CG = C / EPL;
-  const unsigned iu = (unsigned)((int)blockIdx.x - start) * (unsigned)EW_THREADS + threadIdx.x;     // rows * CG < 2^31 (checked by the launcher)
-  if ((long)iu < p.rows * CG) {
-    const unsigned r = iu / (unsigned)CG;
-    const long row = r; const int c = (int)(iu - r * (unsigned)CG) * EPL;
-    const T* __restrict__ y = (const T*)p.y; const T* __restrict__ res = (const T*)p.res; T* __restrict__ z = (T*)p.z;
-    float f[EPL], rr[EPL], sc[EPL], sh[EPL];
-    ys_unpack<T>(ys_ld16(y + row * C + c), f);
-    if (res) ys_unpack<T>(ys_ld16(res + row * p.res_ldc + p.res_coff + c), rr);
-    ys_ldcoef<EPL>(p.scale + c, sc);
-    ys_ldcoef<EPL>(p.shift + c, sh);
-#pragma unroll
-    for (int e = 0; e < EPL; e++) {
-      float u = f[e] * sc[e] + sh[e];
-      if (ACT) u = ys_silu(u);
-      if (res) u += rr[e];
-      f[e] = u;
-    }
-    ys_st16(z + row * p.z_ldc + p.z_coff + c, ys_pack<T>(f));
-  }
-}
-int ys_bn_act_apply_group_launch(hipStream_t st, int dtype, const BnApplyProb* probs, int n, int act) {
-  if (n < 1 || n > YS_EW_GROUP_MAX) { ys_set_error("bn apply group: %d problems", n); return YS_ERR_INVALID_ARG; }
-  const int epl = dtype == YS_BF16 ? 8 : 4;
-  BnApplyGroup grp{};
-  grp.n = n;
-  long total = 0;
-  for (int i = 0; i < n; i++) {
-    const long nn = probs[i].rows * (probs[i].C / epl);
-    if (nn >= (1L << 31)) { ys_set_error("bn apply group: problem too large"); return YS_ERR_UNSUPPORTED; }
-    grp.p[i] = probs[i]; total += ys_cdiv(nn, EW_THREADS); grp.end[i] = (int)total;
-  }
-  for (int i = n; i < YS_EW_GROUP_MAX; i++) grp.end[i] = (int)total;
-#define BAG_LAUNCH(TT, AF) YS_LAUNCH((bn_act_apply_group_kernel<TT, AF>), (int)total, EW_THREADS, st, grp)
-  if (dtype == YS_BF16) { if (act) BAG_LAUNCH(bf16_t, true); else BAG_LAUNCH(bf16_t, false); }
-  else { if (act) BAG_LAUNCH(float, true); else BAG_LAUNCH(float, false); }
-#undef BAG_LAUNCH
-  return YS_OK;
-}
-
-// MODE 0 (BN backward) of chan_finalize_kernel for several units at once
-__global__ void __launch_bounds__(EW_THREADS)
-chan_finalize_group_kernel(ChanFinGroup grp) {
-  __shared__ double sbuf[EW_THREADS];
-  int start;
-  const ChanFinProb& p = grp.p[ys_ew_group_pick(grp, (int)blockIdx.x, start)];
-  const int c = (int)blockIdx.x - start, C = p.C;
-  const float* __restrict__ partial = p.src.p[0]; int nblk = p.src.nblk[0];
-#pragma unroll
-  for (int k = 1; k < YS_BNRED_MAXSEG; k++) if (k < p.src.n && c >= p.src.c1[k - 1]) { partial = p.src.p[k]; nblk = p.src.nblk[k]; }
-  float sc = 0.f, mu = 0.f, rs = 0.f, g0p = 0.f, g1p = 0.f;
-  if (threadIdx.x == 0) { g0p = p.g0[c]; sc = p.scale[c]; mu = p.mean[c]; rs = p.rstd[c]; g1p = p.g1[c]; }
-  double s1 = 0.0, s2 = 0.0;
-  for (int k = threadIdx.x; k < nblk; k += EW_THREADS) {
-    s1 += (double)partial[((long)k * 2 + 0) * C + c];
-    s2 += (double)partial[((long)k * 2 + 1) * C + c];
-  }
-  block_sum2_d(s1, s2, sbuf);
-  if (threadIdx.x == 0) {
-    const double count = p.count;
-    s2 = (double)rs * (s2 - (double)mu * s1);
-    p.g0[c] = g0p + (float)s2;
-    p.g1[c] = g1p + (float)s1;
-    const float m1 = (float)(s1 / count), m2 = (float)(s2 / count);
-    p.c1[c] = sc * (m1 - mu * rs * m2);
-    p.c2[c] = sc * rs * m2;
-  }
-}
-int ys_bn_bwd_finalize_group_launch(hipStream_t st, const ChanFinProb* probs, int n) {
-  if (n < 1 || n > YS_EW_GROUP_MAX) { ys_set_error("bn backward finalize group: %d problems", n); return YS_ERR_INVALID_ARG; }
-  ChanFinGroup grp{};
-  grp.n = n;
-  int total = 0;
-  for (int i = 0; i < n; i++) { grp.p[i] = probs[i]; total += probs[i].C; grp.end[i] = total; }
-  for (int i = n; i < YS_EW_GROUP_MAX; i++) grp.end[i] = total;
-  YS_LAUNCH(chan_finalize_group_kernel, total, EW_THREADS, st, grp);
-  return YS_OK;
-}
-
-template <class T, bool ACT>
-__global__ void __launch_bounds__(EW_THREADS)
-bn_bwd_apply_group_kernel(BnBwdGroup grp) {
-  constexpr int EPL = Elem<T>::EPL;
-  int start;
-  const BnBwdProb& p = grp.p[ys_ew_group_pick(grp, (int)blockIdx.x, start)];
-  const int C = p.C, CG = C / EPL;
-  const unsigned iu = (unsigned)((int)blockIdx.x - start) * (unsigned)EW_THREADS + threadIdx.x;
-  if ((long)iu < p.rows * CG) {
-    const unsigned r = iu / (unsigned)CG;
-    const long row = r; const int c = (int)(iu - r * (unsigned)CG) * EPL;
-    const T* __restrict__ dz = (const T*)p.dz; const T* __restrict__ y = (const T*)p.y; T* __restrict__ dy = (T*)p.dy; T* __restrict__ rg = (T*)p.rg;
-    float g[EPL], f[EPL], sc[EPL], sh[EPL], a2[EPL], a3[EPL];
-    ys_unpack<T>(ys_ld16(dz + row * p.dz_ldc + p.dz_coff + c), g);
-    ys_unpack<T>(ys_ld16(y + row * C + c), f);
-    if (rg) {
-      float o[EPL];
-      T* rp = rg + row * p.rg_ldc + p.rg_coff + c;
-      ys_unpack<T>(ys_ld16(rp), o);
-#pragma unroll
-      for (int e = 0; e < EPL; e++) o[e] += g[e];
-      ys_st16(rp, ys_pack<T>(o));
-    }
-    ys_ldcoef<EPL>(p.scale + c, sc); ys_ldcoef<EPL>(p.shift + c, sh); ys_ldcoef<EPL>(p.k2 + c, a2); ys_ldcoef<EPL>(p.k3 + c, a3);
-#pragma unroll
-    for (int e = 0; e < EPL; e++) {
-      const float u = f[e] * sc[e] + sh[e];
-      const float du = ACT ? g[e] * ys_silu_grad(u) : g[e];
-      f[e] = sc[e] * du - a2[e] - f[e] * a3[e];
-    }
-    ys_st16(dy + row * C + c, ys_pack<T>(f));
-  }
-}
-int ys_bn_bwd_apply_group_launch(hipStream_t st, int dtype, const BnBwdProb* probs, int n, int act) {
-  if (n < 1 || n > YS_EW_GROUP_MAX) { ys_set_error("bn backward apply group: %d problems", n); return YS_ERR_INVALID_ARG; }
-  const int epl = dtype == YS_BF16 ? 8 : 4;
-  BnBwdGroup grp{};
-  grp.n = n;
-  long total = 0;
-  for (int i = 0; i < n; i++) {
-    const long nn = probs[i].rows * (probs[i].C / epl);
-    if (nn >= (1L << 31)) { ys_set_error("bn backward apply group: problem too large"); return YS_ERR_UNSUPPORTED; }
-    grp.p[i] = probs[i]; total += ys_cdiv(nn, EW_THREADS); grp.end[i] = (int)total;
-  }
-  for (int i = n; i < YS_EW_GROUP_MAX; i++) grp.end[i] = (int)total;
-#define BBG_LAUNCH(TT, AF) YS_LAUNCH((bn_bwd_apply_group_kernel<TT, AF>), (int)total, EW_THREADS, st, grp)
-  if (dtype == YS_BF16) { if (act) BBG_LAUNCH(bf16_t, true); else BBG_LAUNCH(bf16_t, false); }
-  else { if (act) BBG_LAUNCH(float, true); else BBG_LAUNCH(float, false); }
-#undef BBG_LAUNCH
   return YS_OK;
 }

@@ -520,11 +520,11 @@ extern "C" int ys_dwconv3x3_bwd(ys_ctx* ctx, int dtype, const float* x, int B, i
   return YS_OK;
 }
 
-// ------------------------------------------------------------------ BatchNorm training kernels of elementwise.hip, one call per launch sequence
+// ------------------------------------------------------------------ BatchNorm training kernels of batchnorm.hip, one call per launch sequence
 // Host tensors are channel-major [C][rows] (NCHW with B = 1).  y / dy are dense [rows][C] on the device as in the model (a unit's own buffers); z, res, dz and
 // rg sit inside sentinel-padded views; partial-row workspaces and dy carry a sentinel guard behind them.
 namespace {
-constexpr int kEwMaxVec = 256;               // vectors per row the channel-reduction launchers take (EW_THREADS of elementwise.hip)
+constexpr int kEwMaxVec = 256;               // vectors per row the channel-reduction launchers take (EW_THREADS of batchnorm.hip)
 
 // ys_stat_acc_add on test-supplied partial rows [P][2][C]: one thread per (row, which, channel) -- the device function every convolution epilogue calls
 __global__ void __launch_bounds__(256)

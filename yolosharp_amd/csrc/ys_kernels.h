@@ -10,6 +10,13 @@
 #define YS_BNRED_MAXSEG 3
 #define YS_GROUP_MAX 4        // problems of one grouped convolution launch (the three pyramid levels of a head; the four phases of a stride-2 dgrad)
 #define YS_EW_GROUP_MAX 9     // problems of one grouped elementwise launch (BN passes of up to three towers x three levels)
+// dtype x act -> the <T, ACT> instance of a kernel: the statement is expanded once per combination with the storage type as TT and the
+// activation flag as the constant AF, e.g.  YS_DISPATCH_T_ACT(dtype, act, YS_LAUNCH((k<TT, AF>), grid, block, st, (const TT*)x));
+#define YS_DISPATCH_ACT(act, ...) \
+  do { if (act) { constexpr bool AF = true; __VA_ARGS__; } else { constexpr bool AF = false; __VA_ARGS__; } } while (0)
+#define YS_DISPATCH_T_ACT(dtype, act, ...) \
+  do { if ((dtype) == YS_BF16) { using TT = bf16_t; YS_DISPATCH_ACT(act, __VA_ARGS__); } \
+       else { using TT = float; YS_DISPATCH_ACT(act, __VA_ARGS__); } } while (0)
 struct BnRedSeg {
   const void* y;        // producer's raw conv output, dense [M][C]
   const float* scale;   // producer's BN scale / shift (forward, training statistics), [C]
@@ -222,7 +229,7 @@ struct FinSrc { const float* p[YS_BNRED_MAXSEG]; int nblk[YS_BNRED_MAXSEG]; int 
 int ys_bn_bwd_finalize_src_launch(hipStream_t st, const FinSrc& src, int C, long count, float* dgamma, float* dbeta, float* k2,
                                   float* k3, const float* scale, const float* mean, const float* rstd);
 // column sums of a [rows][ldc] view into grad[C] (+=)   (bias gradients)
-// ---- grouped (multi-problem) launches: independent Conv units of the same kind side by side in one grid (elementwise.hip, conv.hip)
+// ---- grouped (multi-problem) launches: independent Conv units of the same kind side by side in one grid (batchnorm.hip, conv.hip)
 struct BnFinProb { const float* partial; int nblk, C; double count; const float *gamma, *beta; float *run_mean, *run_var, *nbt, *scale, *shift, *mean, *rstd; };
 struct BnFinGroup { int n; int end[YS_EW_GROUP_MAX]; BnFinProb p[YS_EW_GROUP_MAX]; };
 struct BnApplyProb { const void* y; long rows; int C; const float *scale, *shift; const void* res; int res_ldc, res_coff; void* z; int z_ldc, z_coff; };
