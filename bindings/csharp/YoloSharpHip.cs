@@ -94,7 +94,7 @@ namespace YoloSharp.Native
                                                                  int outW, int outH, int color, [Out] byte[] dst, out int padL, out int padU);
         // Training input on the device (Data/YoloDataset.cs:57-151: Mosaic4 + RandomPerspective + FlipLR / FlipUD + Normalize + mul(1/255) + collate): the sources live in
         // one uint8 arena, an item carries what the reference draws per output image.  Device-resident callers pass IntPtr (on_device = 1) for every pointer.
-        // Quirk kept: a flipped box keeps x1 > x2 (negative w after cxcywh) unless flags has YS_AUG_SORT_FLIPPED (1).  Not built: OBB corners, the `rand > p` case of Mosaic.
+        // Quirk kept: a flipped box keeps x1 > x2 (negative w after cxcywh) unless flags has YS_AUG_SORT_FLIPPED (1).  OBB corner labels: the *_obb entries below.  Not built: the `rand > p` case of Mosaic.
         [StructLayout(LayoutKind.Sequential)] internal struct YsAugSrc { public long imgOff, maskOff; public int h, w, mh, mw; }
         [StructLayout(LayoutKind.Sequential)] internal struct YsAugItem { public int src0, src1, src2, src3, xc, yc; public float m00, m01, m02, m10, m11, m12, m20, m21, m22; public int flipLr, flipUd; }
         [DllImport(Lib)] internal static extern int ys_augment_mosaic(IntPtr ctx, IntPtr arena, IntPtr srcs, int nSrc, IntPtr items, int batch, int onDevice, int imgsz,
@@ -121,6 +121,16 @@ namespace YoloSharp.Native
         [DllImport(Lib)] internal static extern int ys_augment_letterbox_jitter(IntPtr ctx, IntPtr arena, IntPtr srcs, int nSrc, IntPtr items, int batch, int onDevice,
                                                                                 int imgsz, int maskRatio, IntPtr jitter, IntPtr images, IntPtr masks);
         [DllImport(Lib)] internal static extern int ys_color_jitter(IntPtr ctx, IntPtr src, IntPtr jitter, int batch, int h, int w, int onDevice, IntPtr dst, int dstIsFloat);
+        // OBB corner labels (Data/YoloDataset.cs:110-129; Utils/Ops.cs:44-54): corners [n, 4, 2] pixels in place of the keypoints, outBboxes [capacity, 5] = (cx, cy, w, h) / imgsz
+        // and the angle of the minimum-area rectangle, angle in (0, pi/2], w along the angle (OpenCV >= 4.5.1's form; the choice among equal-area rectangles is unpinned
+        // against OpenCV).  boxes [n, 4] alone decides what is kept; flags must be 0.  ys_xyxyxyxy2xywhr is the rectangle on its own: [n, 4, 2] -> [n, 5], pixels and radians.
+        [DllImport(Lib)] internal static extern int ys_xyxyxyxy2xywhr(IntPtr ctx, IntPtr corners, int n, int onDevice, IntPtr outRows);
+        [DllImport(Lib)] internal static extern int ys_augment_labels_obb(IntPtr ctx, IntPtr srcs, IntPtr labOff, IntPtr cls, IntPtr boxes, IntPtr corners, IntPtr items, int batch,
+                                                                          int onDevice, int imgsz, int perspective, int flags, int capacity, IntPtr outBatchIdx, IntPtr outCls,
+                                                                          IntPtr outBboxes, IntPtr outCount);
+        [DllImport(Lib)] internal static extern int ys_augment_letterbox_labels_obb(IntPtr ctx, IntPtr srcs, int nSrc, IntPtr labOff, IntPtr cls, IntPtr boxes, IntPtr corners,
+                                                                                    IntPtr items, int batch, int onDevice, int imgsz, int flags, int capacity,
+                                                                                    IntPtr outBatchIdx, IntPtr outCls, IntPtr outBboxes, IntPtr outCount);
         // Classify task (Head.Classify / v8ClassificationLoss / Classifier.Val, Models/Classifier.cs): outputs "cls" / "logits" / "dcls" [B,nc]
         // through ys_model_get_output; one loss item (the mean) through ys_loss_read_items
         [DllImport(Lib)] internal static extern int ys_loss_classify(IntPtr model, float[] cls, int batch, int onDevice);

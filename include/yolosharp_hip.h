@@ -480,8 +480,8 @@ YS_API int ys_letterbox(ys_ctx* ctx, const void* src, int is_float, int on_devic
  * [0, 2 * imgsz], a singular M, and a capacity below the sum of the four tiles' label counts of some image.  Device items cannot be read by the
  * host: an item that fails those checks yields an all-114 image (zero masks) and no labels; if more rows are kept than `capacity`, *out_count holds
  * the true total (> capacity) and the rows past capacity are not written.  Nothing is truncated silently.
- * Scope: kpt_dim must be 3 (apply_keypoints reads column 2; 2 -> YS_ERR_INVALID_ARG).  Not built: OBB corner labels (xyxyxyxy2xywhr is host code in
- * the reference, and the corners need OpenCV's MinAreaRect) and the `rand > p` case of Augment.Mosaic (the reference then
+ * Scope: kpt_dim must be 3 (apply_keypoints reads column 2; 2 -> YS_ERR_INVALID_ARG).  OBB corner labels are the *_obb entries further down.  Not built:
+ * the `rand > p` case of Augment.Mosaic (the reference then
  * yields images of unequal sizes its own collate cannot stack).  RandomHSV, the last transform of both chains, is the ys_aug_jitter row of the
  * *_jitter entries further down.  The other no-mosaic case -- the LetterBox pipeline the reference trains on once the
  * mosaic is closed -- is ys_augment_letterbox / ys_augment_letterbox_labels below.  Deviations: a label-free sample is still warped (RandomPerspective.Apply returns the
@@ -563,6 +563,46 @@ YS_API int ys_augment_letterbox_jitter(ys_ctx* ctx, const uint8_t* arena, const 
                                        int on_device, int imgsz, int mask_ratio, const ys_aug_jitter* jitter, float* images, float* masks);
 YS_API int ys_color_jitter(ys_ctx* ctx, const uint8_t* src, const ys_aug_jitter* jitter, int batch, int h, int w, int on_device, void* dst,
                            int dst_is_float);
+
+/* ---- OBB corner labels for the training input (Data/YoloDataset.cs:110-129, 216-244; Utils/Ops.cs:44-54): an OBB label carries four corners
+ * [n, 4, 2] (pixels, the source's frame) beside its axis-aligned box; the criterion's row is xyxyxyxy2xywhr of the transformed corners -- OpenCV
+ * MinAreaRect, host code in the reference -- with columns 0-3 divided by imgsz, and it REPLACES the box: ys_loss_obb never sees the axis-aligned one.
+ *
+ * ys_xyxyxyxy2xywhr: the operator on its own.  corners [n, 4, 2] -> out [n, 5] = (cx, cy, w, h) in the corners' units and the angle in radians; no
+ * division by imgsz; n = 0 is a no-op.  CONTRACT: the enclosing rectangle of minimum area, in OpenCV >= 4.5.1's documented canonical form (the
+ * reference pins OpenCvSharp 4.11): angle in (0, pi/2], w = the side whose direction makes `angle` with the +x axis, h = the other side.  An
+ * axis-aligned rectangle is therefore angle = pi/2 with (w, h) = (y extent, x extent), never angle = 0; a rectangle has exactly one such row.
+ * How: the minimum-area rectangle has a side along a hull edge and every hull edge is one of the 6 point pairs, so the minimum of the bounding
+ * rectangles along the 6 pair directions -- order (0,1) (1,2) (2,3) (3,0) (0,2) (1,3), zero-length pairs skipped, the FIRST strict minimum wins -- is
+ * the answer, and a pure function of the input.  fp32 in and out; the differences, projections, areas and atan2 in between are double.
+ * Degenerate inputs give finite rows: four identical points (x, y, 0, 0, 0); exactly collinear points w = the span, h = 0 and the line's OWN
+ * direction folded by half turns into (0, pi] -- the one kind of row whose angle can exceed pi/2 (a line in the second quadrant; a horizontal one is
+ * pi): with w as the span a quarter-turn fold would describe the segment turned by 90 degrees.  DEVIATION: OpenCV leaves the raw atan2 of the line,
+ * in (-pi, pi], there.  These rows are reachable: the Mosaic keep decision is made on the box of
+ * the transformed axis-aligned box, which can overlap the image while all four clipped corners lie on one border.
+ * UNPINNED: OpenCV is not available to this project's tests, so the choice among geometrically DIFFERENT rectangles of equal area -- an acute
+ * triangle (one corner repeated): all three edges tie exactly; many quads clipped to the image -- is the pair order above, not pinned against the
+ * reference binary.  It matters: of 20 000 random boxes of 2-16 px on a 64 px image about 2 % of the kept labels had a geometrically different
+ * rectangle within 1e-4 of the minimum area, with large, heavily clipped boxes about 16 % (float64 brute force on the CPU).
+ *
+ * ys_augment_labels_obb = ys_augment_labels with corners [n, 4, 2] in place of the keypoint arguments and out_bboxes [capacity, 5] in place of the box
+ * and keypoint outputs: same two-pass count / scan / write, compaction order, tail rows (batch_idx -1, zeros), *out_count, capacity rule and
+ * host-pointer validation.  `boxes` [n, 4] stays an input: it ALONE decides which rows are kept, exactly as in ys_augment_labels (quirk kept: the
+ * reference filters on the axis-aligned box, :245 and :683-684).  A kept row, fp32 in the reference's order: corners + (padw, padh), NOT clipped to
+ * the canvas (:253-256); (x, y, 1) . M^T, divided by the third component only when perspective != 0 (apply_obb_corners, :604-635; apply_keypoints
+ * always divides); clamp to [0, imgsz] (clip_obb_corners, Utils/Ops.cs:191-199); FlipLR x <- s - x, FlipUD y <- s - y; the rectangle; columns 0-3
+ * / (float)imgsz (a division, YoloDataset.cs:121).  flags must be 0 (YS_ERR_INVALID_ARG otherwise): the box-flip switches have nothing to act on.
+ *
+ * ys_augment_letterbox_labels_obb, the same relative to ys_augment_letterbox_labels: every label kept, corners + (pad_l, pad_u) NOT scaled by ratio
+ * (the quirk that branch keeps for boxes, :746-749), NOTHING clipped (a corner outside [0, imgsz] stays there), the flips (:825-828), the rectangle,
+ * the division. */
+YS_API int ys_xyxyxyxy2xywhr(ys_ctx* ctx, const float* corners, int n, int on_device, float* out);
+YS_API int ys_augment_labels_obb(ys_ctx* ctx, const ys_aug_src* srcs, const int32_t* lab_off, const float* cls, const float* boxes,
+                                 const float* corners, const ys_aug_item* items, int batch, int on_device, int imgsz, int perspective, int flags,
+                                 int capacity, float* out_batch_idx, float* out_cls, float* out_bboxes, int32_t* out_count);
+YS_API int ys_augment_letterbox_labels_obb(ys_ctx* ctx, const ys_aug_src* srcs, int n_src, const int32_t* lab_off, const float* cls, const float* boxes,
+                                           const float* corners, const ys_aug_item* items, int batch, int on_device, int imgsz, int flags, int capacity,
+                                           float* out_batch_idx, float* out_cls, float* out_bboxes, int32_t* out_count);
 
 /* ---- per-operator entry points (unit parity; a TorchSharp-free C# Conv wrapper) ---------------
  * Convs.Conv.forward (Convs.cs:36-62): y = act(BN(conv2d(x))) on fp32 NCHW / OIHW HOST arrays at the

@@ -22,6 +22,13 @@ batch's host copy (images and labels copied to the device every step): what a tr
 device-resident tables through the plain entry, through the *_jitter entry with jitter = NULL (the same kernel: these two must agree) and with one drawn
 row per image (draw_jitter(0.015, 0.7, 0.4), the reference's default); torch_hsv = a torch restatement of torchvision's uint8 ColorJitter, per image, on
 a uint8 batch [B, 3, imgsz, imgsz] that already lives on the same GPU, with the same rows -- the extra pass a host without the epilogue would run.
+
+--task obb measures the OBB corner labels (ys_augment_labels_obb / ys_augment_letterbox_labels_obb) on the same dataset with four rotated-rectangle
+corners per label, in four child processes: obb_labels = ms per label call of each branch on device-resident tables (and of the box entries beside them);
+numpy_obb_labels = a numpy restatement of the same rows on the host (keep rule, corner chain, the six-direction rectangle, vectorised over the batch's
+labels; written here, not imported from tests/); step_augmented = the YOLOv8n-OBB bf16 train step fed by MosaicAugmenter.batch() every iteration, in the
+branch --branch names; step_host = the same step through the host entry (AMPWrapper.TrainStep's calls) on a batch's host copy, images and labels copied
+to the device every step -- the only way to train OBB without these entries.
 """
 import argparse
 import json
@@ -38,6 +45,7 @@ if ROOT not in sys.path:
 
 LEGS = ("augment", "torch_augment", "step_static", "step_augmented")
 LETTERBOX_LEGS = LEGS + ("step_host",)
+OBB_LEGS = ("obb_labels", "numpy_obb_labels", "step_augmented", "step_host")
 HSV_LEGS = ("hsv", "torch_hsv")
 HBM_TBPS = 6.3
 HYP = dict(degrees=10.0, translate=0.1, scale=0.5, shear=2.0, perspective=0.0)
@@ -56,6 +64,11 @@ def _dataset(a):
         x1, y1 = g.random(n) * w * 0.7, g.random(n) * h * 0.7
         labels.append(dict(cls=g.integers(0, a.nc, n).astype(np.float32),
                            bboxes=np.stack([x1, y1, x1 + (0.05 + 0.25 * g.random(n)) * w, y1 + (0.05 + 0.25 * g.random(n)) * h], 1).astype(np.float32)))
+        if a.task == "obb":                                           # the same rectangles, turned about their centres: "obb" corners, the box derived from them
+            b, th = labels[-1].pop("bboxes").astype(np.float64), g.random(n) * np.pi
+            c, hw, hh = (b[:, :2] + b[:, 2:]) / 2, (b[:, 2] - b[:, 0]) / 2, (b[:, 3] - b[:, 1]) / 2
+            u, v = np.stack([np.cos(th), np.sin(th)], 1), np.stack([-np.sin(th), np.cos(th)], 1)
+            labels[-1]["obb"] = np.stack([c + s1 * hw[:, None] * u + s2 * hh[:, None] * v for s1, s2 in ((-1, -1), (1, -1), (1, 1), (-1, 1))], 1).astype(np.float32)
     return imgs, labels
 
 
@@ -214,6 +227,123 @@ def leg_torch_augment(a):
     return {"ms_per_batch": round(ms, 4), "runs": runs, "what": "images only (canvas paste + grid_sample per image, flips, stack, mul 1/255)"}
 
 
+def leg_obb_labels(a):
+    """Per branch: the OBB label call and, beside it, the box label call on the same tables and items."""
+    from yolosharp_amd import Engine, _lib
+    eng = Engine(0)
+    aug, _ = _augmenter(eng, a)
+    B, S, lib = a.batch, a.imgsz, eng.lib
+    out = {"B": B, "imgsz": S, "labels_in_tables": int(aug.lab_off[-1])}
+    for branch in ("mosaic", "letterbox"):
+        aug.close_mosaic(branch == "letterbox")
+        aug.run(aug.draw(np.arange(B) % aug.count))                   # uploads the item table; the timed calls below reuse it on the device
+        tail = (aug.d_items, B, 1, S)
+        outs = (aug.capacity, aug.d_bidx, aug.d_ocls, aug.d_obox)
+        if branch == "mosaic":
+            calls = {"obb": lambda: lib.ys_augment_labels_obb(eng.ctx, aug.d_srcs, aug.d_lab_off, aug.d_cls, aug.d_boxes, aug.d_obb, *tail, 0, 0, *outs, aug.d_cnt),
+                     "box": lambda: lib.ys_augment_labels(eng.ctx, aug.d_srcs, aug.d_lab_off, aug.d_cls, aug.d_boxes, None, 0, 3, *tail, 0, 0, *outs, None, aug.d_cnt)}
+        else:
+            calls = {"obb": lambda: lib.ys_augment_letterbox_labels_obb(eng.ctx, aug.d_srcs, aug.count, aug.d_lab_off, aug.d_cls, aug.d_boxes, aug.d_obb, *tail, 0,
+                                                                        *outs, aug.d_cnt),
+                     "box": lambda: lib.ys_augment_letterbox_labels(eng.ctx, aug.d_srcs, aug.count, aug.d_lab_off, aug.d_cls, aug.d_boxes, None, 0, 3, *tail, 0,
+                                                                    *outs, None, aug.d_cnt)}
+        res = {}
+        for name in ("box", "obb"):                                   # obb last: the count read below is its
+            ms, runs = _timed(lambda: _lib.check(lib, calls[name]()), eng.synchronize, a)
+            res[name + "_ms"], res[name + "_runs"] = round(ms, 4), runs
+        res["rows_kept"] = int(eng.from_device(aug.d_cnt, (1,), np.int32)[0])
+        out[branch] = res
+    aug.close()
+    return out
+
+
+def _np_min_area_rect(c):
+    """corners [n, 4, 2] float64 -> [n, 5]: the six-direction rectangle of csrc/augment.hip, vectorised over the rows."""
+    n = c.shape[0]
+    best = np.full(n, np.inf)
+    out = np.zeros((n, 5))
+    out[:, :2] = c[:, 0]
+    for i, j in ((0, 1), (1, 2), (2, 3), (3, 0), (0, 2), (1, 3)):
+        d = c[:, j] - c[:, i]
+        ln = np.hypot(d[:, 0], d[:, 1])
+        ok = ln > 0
+        u = d / np.where(ok, ln, 1.0)[:, None]
+        neg = (u[:, 1] < 0) | ((u[:, 1] == 0) & (u[:, 0] < 0))
+        u = np.where(neg[:, None], -u, u)
+        flat, left = u[:, 1] == 0, u[:, 0] < 0
+        u = np.where(flat[:, None], np.stack([np.zeros(n), u[:, 0]], 1), np.where(left[:, None], np.stack([u[:, 1], -u[:, 0]], 1), u))
+        nv = np.stack([-u[:, 1], u[:, 0]], 1)
+        t, m = np.einsum("nkc,nc->nk", c, u), np.einsum("nkc,nc->nk", c, nv)
+        w, h = t.max(1) - t.min(1), m.max(1) - m.min(1)
+        better = ok & (w * h < best)
+        ctr = ((t.max(1) + t.min(1)) / 2)[:, None] * u + ((m.max(1) + m.min(1)) / 2)[:, None] * nv
+        row = np.concatenate([ctr, w[:, None], h[:, None], np.arctan2(u[:, 1], u[:, 0])[:, None]], 1)
+        out, best = np.where(better[:, None], row, out), np.where(better, w * h, best)
+    return out
+
+
+def leg_numpy_obb_labels(a):
+    """The rows of one batch on the host, per branch, from the same tables and items (numpy, vectorised over the batch's labels)."""
+    from yolosharp_amd.augment import draw_items, draw_letterbox_items, mosaic4_rects, pack_labels, pack_obb
+    imgs, labels = _dataset(a)
+    B, S = a.batch, a.imgsz
+    lab_off, cls, boxes, _ = pack_labels(labels)
+    corners = pack_obb(labels)
+    f = np.float32
+
+    def mosaic(items):
+        rows = []
+        for b, it in enumerate(items):
+            shapes = [imgs[k].shape[1:] for k in it["src"]]
+            idx, pad = [], []
+            for k, (ra, rb) in zip(it["src"], mosaic4_rects(int(it["xc"]), int(it["yc"]), shapes, S)):
+                idx.append(np.arange(lab_off[k], lab_off[k + 1])); pad.append(np.tile(f([ra[0] - rb[0], ra[1] - rb[1]]), (len(idx[-1]), 1)))
+            idx, pad, M = np.concatenate(idx), np.concatenate(pad), it["M"].reshape(3, 3)
+            bx = boxes[idx] + np.tile(pad, 2)
+            org = (bx[:, 2] - bx[:, 0]) * (bx[:, 3] - bx[:, 1])
+            bx = np.clip(bx, 0, 2 * S)
+            area = (bx[:, 2] - bx[:, 0]) * (bx[:, 3] - bx[:, 1])
+            xy = np.concatenate([bx[:, [0, 1, 2, 3, 0, 3, 2, 1]].reshape(-1, 2), np.ones((4 * len(idx), 1), f)], 1) @ M.T
+            xy = xy[:, :2].reshape(-1, 4, 2)
+            nb = np.clip(np.concatenate([xy.min(1), xy.max(1)], 1), 0, S)
+            keep = (area > 0) & (area > f(0.7) * org) & ((nb[:, 2] - nb[:, 0]) * (nb[:, 3] - nb[:, 1]) > 0)
+            c = corners[idx][keep] + pad[keep][:, None]
+            c = np.clip((np.concatenate([c, np.ones(c.shape[:2] + (1,), f)], 2) @ M.T)[..., :2], 0, S)
+            if it["flip_lr"]:
+                c[..., 0] = S - c[..., 0]
+            if it["flip_ud"]:
+                c[..., 1] = S - c[..., 1]
+            r = _np_min_area_rect(c.astype(np.float64)).astype(f)
+            r[:, :4] /= f(S)
+            rows.append(np.concatenate([np.full((len(r), 1), b, f), cls[idx][keep][:, None], r], 1))
+        return np.concatenate(rows)
+
+    def letterbox(items):
+        rows = []
+        for b, it in enumerate(items):
+            k = int(it["src"][0])
+            h, w = imgs[k].shape[1:]
+            ratio = min(f(S) / f(w), f(S) / f(h))
+            pad = f([(S - int(f(w) * ratio)) // 2, (S - int(f(h) * ratio)) // 2])
+            c = corners[lab_off[k]:lab_off[k + 1]] + pad
+            if it["flip_lr"]:
+                c[..., 0] = S - c[..., 0]
+            if it["flip_ud"]:
+                c[..., 1] = S - c[..., 1]
+            r = _np_min_area_rect(c.astype(np.float64)).astype(f)
+            r[:, :4] /= f(S)
+            rows.append(np.concatenate([np.full((len(r), 1), b, f), cls[lab_off[k]:lab_off[k + 1]][:, None], r], 1))
+        return np.concatenate(rows)
+
+    out = {"what": "keep rule, corner chain, six-direction rectangle and collate in numpy on the host, one batch"}
+    its = {"mosaic": draw_items(np.random.default_rng(1), np.arange(B) % len(imgs), S, len(imgs), HYP, 0.5, 0.0),
+           "letterbox": draw_letterbox_items(np.random.default_rng(1), np.arange(B) % len(imgs), 0.5, 0.0)}
+    for branch, fn in (("mosaic", mosaic), ("letterbox", letterbox)):
+        ms, runs = _timed(lambda: fn(its[branch]), lambda: None, a)
+        out[branch] = {"ms_per_batch": round(ms, 4), "runs": runs, "rows": int(fn(its[branch]).shape[0])}
+    return out
+
+
 HSV = (0.015, 0.7, 0.4)
 
 
@@ -308,7 +438,9 @@ def leg_torch_hsv(a):
 
 def leg_step(a, augmented, host=False):
     from yolosharp_amd import Engine
-    from yolosharp_amd.model import AMPWrapper, Yolov8, v8DetectionLoss
+    from yolosharp_amd.model import AMPWrapper, Yolov8, Yolov8Obb, v8DetectionLoss, v8OBBLoss
+    if a.task == "obb":
+        Yolov8, v8DetectionLoss = Yolov8Obb, v8OBBLoss
     eng = Engine(0)
     B, S = a.batch, a.imgsz
     aug, _ = _augmenter(eng, a)
@@ -357,11 +489,12 @@ def main():
     ap.add_argument("--leg-timeout", type=int, default=240, help="seconds per child process")
     ap.add_argument("--branch", choices=("mosaic", "letterbox"), default="mosaic", help="the pipeline to measure (letterbox = the close-mosaic branch)")
     ap.add_argument("--hsv", action="store_true", help="measure the ColorJitter epilogue of both branches and its torch restatement instead")
-    ap.add_argument("--leg", choices=LETTERBOX_LEGS + HSV_LEGS, help="run one measurement in this process (what the driver starts)")
+    ap.add_argument("--task", choices=("detect", "obb"), default="detect", help="obb: the OBB corner-label entries and the YOLOv8n-OBB step")
+    ap.add_argument("--leg", choices=LETTERBOX_LEGS + HSV_LEGS + OBB_LEGS[:2], help="run one measurement in this process (what the driver starts)")
     a = ap.parse_args()
     lb = a.branch == "letterbox"
     if a.leg:
-        out = {"hsv": lambda: leg_hsv(a), "torch_hsv": lambda: leg_torch_hsv(a), "augment": lambda: leg_letterbox(a) if lb else leg_augment(a), "torch_augment": lambda: leg_torch_letterbox(a) if lb else leg_torch_augment(a),
+        out = {"obb_labels": lambda: leg_obb_labels(a), "numpy_obb_labels": lambda: leg_numpy_obb_labels(a), "hsv": lambda: leg_hsv(a), "torch_hsv": lambda: leg_torch_hsv(a), "augment": lambda: leg_letterbox(a) if lb else leg_augment(a), "torch_augment": lambda: leg_torch_letterbox(a) if lb else leg_torch_augment(a),
                "step_static": lambda: leg_step(a, False), "step_augmented": lambda: leg_step(a, True), "step_host": lambda: leg_step(a, False, host=True)}[a.leg]()
         print(json.dumps(out))
         return 0
@@ -370,9 +503,11 @@ def main():
         res["branch"] = "letterbox"
     if a.hsv:
         res["metric"] = "color_jitter_cost"
+    if a.task == "obb":
+        res.update(metric="obb_label_cost", model="yolov8n-obb", branch=a.branch)
     fwd = [x for kv in (("--batch", a.batch), ("--imgsz", a.imgsz), ("--sources", a.sources), ("--nc", a.nc), ("--steps", a.steps), ("--warmup", a.warmup),
-                        ("--repeats", a.repeats), ("--branch", a.branch)) for x in (kv[0], str(kv[1]))]
-    for leg in (HSV_LEGS if a.hsv else LETTERBOX_LEGS if lb else LEGS):
+                        ("--repeats", a.repeats), ("--branch", a.branch), ("--task", a.task)) for x in (kv[0], str(kv[1]))]
+    for leg in (OBB_LEGS if a.task == "obb" else HSV_LEGS if a.hsv else LETTERBOX_LEGS if lb else LEGS):
         try:
             r = subprocess.run([sys.executable, os.path.abspath(__file__), "--leg", leg] + fwd, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
                                text=True, timeout=a.leg_timeout, stdin=subprocess.DEVNULL)
@@ -391,6 +526,11 @@ def main():
     if "step_static" in res and "step_augmented" in res:
         res["augment_extra_ms_per_step"] = round(res["step_augmented"]["ms_per_step"] - res["step_static"]["ms_per_step"], 4)
         res["augment_extra_share_of_step"] = round(res["augment_extra_ms_per_step"] / res["step_static"]["ms_per_step"], 4)
+    if "obb_labels" in res and "numpy_obb_labels" in res:
+        for branch in ("mosaic", "letterbox"):
+            res["numpy_over_kernel_" + branch] = round(res["numpy_obb_labels"][branch]["ms_per_batch"] / max(res["obb_labels"][branch]["obb_ms"], 1e-4), 1)
+    if a.task == "obb" and "step_augmented" in res and "step_host" in res:
+        res["host_batch_extra_ms_per_step"] = round(res["step_host"]["ms_per_step"] - res["step_augmented"]["ms_per_step"], 4)
     if "step_static" in res and "step_host" in res:
         res["host_batch_extra_ms_per_step"] = round(res["step_host"]["ms_per_step"] - res["step_static"]["ms_per_step"], 4)
     print(json.dumps(res))

@@ -13,7 +13,13 @@ saturation 0.7, hue 0.015) on the uint8 image: MosaicAugmenter(hsv=(0.015, 0.7, 
 ColorJitter.get_params) and the gather kernels apply it in their epilogue (ys_augment_mosaic_jitter / ys_augment_letterbox_jitter); color_jitter() is the operator
 on its own, contrast included (ys_color_jitter).  TorchVision.NET is not in the reference tree: torchvision's public uint8 algorithm is the contract.
 
-Not built: OBB corner labels, the `rand > p` case of Augment.Mosaic (it yields images of unequal sizes).
+OBB corner labels (Data/YoloDataset.cs:110-129, 216-244): labels that carry "obb" [n, 4, 2] pixel corners go through ys_augment_labels_obb /
+ys_augment_letterbox_labels_obb -- the corners through the branch's chain, then xyxyxyxy2xywhr (the minimum-area rectangle, OpenCV >= 4.5.1's canonical form:
+angle in (0, pi/2], w along the angle) and columns 0-3 / imgsz: the batch's boxes are [capacity, 5].  Quirks kept: the keep decision is made on the axis-aligned
+box alone, the LetterBox pads are not scaled by ratio and that branch clips nothing.  The choice among equal-area rectangles is UNPINNED against OpenCV
+(include/yolosharp_hip.h).  xyxyxyxy2xywhr() is the operator on its own.
+
+Not built: the `rand > p` case of Augment.Mosaic (it yields images of unequal sizes).
 kpt_dim = 3 only."""
 import ctypes as C
 import math
@@ -108,16 +114,37 @@ def pack_sources(images_u8, masks=None):
 
 def pack_labels(labels):
     """Per-source label dicts {cls [n], bboxes [n, 4] pixel xyxy in the source's frame, keypoints [n, K, 3] (optional)} -> (lab_off [n_src + 1],
-    cls, boxes, keypoints or None)."""
+    cls, boxes, keypoints or None).  OBB labels carry "obb" [n, 4, 2] pixel corners: see pack_obb; where "bboxes" is absent the box is the corners'
+    axis-aligned one (min / max per axis, YoloDataset.cs:235-243)."""
     cnt = [int(np.asarray(l["cls"]).reshape(-1).shape[0]) for l in labels]
     lab_off = np.concatenate([[0], np.cumsum(cnt)]).astype(np.int32)
     cls = np.concatenate([np.asarray(l["cls"], np.float32).reshape(-1) for l in labels]) if labels else np.zeros((0,), np.float32)
-    boxes = np.concatenate([np.asarray(l["bboxes"], np.float32).reshape(-1, 4) for l in labels])
+    boxes = np.concatenate([np.asarray(l["bboxes"], np.float32).reshape(-1, 4) if l.get("bboxes") is not None else _obb_boxes(l["obb"]) for l in labels])
     kp = None
     if labels and labels[0].get("keypoints") is not None:
         K = np.asarray(labels[0]["keypoints"]).shape[1]
         kp = np.ascontiguousarray(np.concatenate([np.asarray(l["keypoints"], np.float32).reshape(-1, K, 3) for l in labels]))
     return lab_off, np.ascontiguousarray(cls), np.ascontiguousarray(boxes), kp
+
+
+def _obb_boxes(corners):
+    c = np.asarray(corners, np.float32).reshape(-1, 4, 2)
+    return np.concatenate([c.min(1), c.max(1)], 1).astype(np.float32).reshape(-1, 4)
+
+
+def pack_obb(labels):
+    """The "obb" corners [n, 4, 2] (pixels, the source's frame) of per-source label dicts as one table, or None when the labels carry none."""
+    if not labels or labels[0].get("obb") is None:
+        return None
+    return np.ascontiguousarray(np.concatenate([np.asarray(l["obb"], np.float32).reshape(-1, 4, 2) for l in labels]))
+
+
+def xyxyxyxy2xywhr(engine, corners):
+    """ys_xyxyxyxy2xywhr on a HOST array: corners [n, 4, 2] -> [n, 5] = (cx, cy, w, h) in the corners' units, angle in radians in (0, pi/2]."""
+    c = np.ascontiguousarray(corners, np.float32).reshape(-1, 4, 2)
+    out = np.empty((c.shape[0], 5), np.float32)
+    _lib.check(engine.lib, engine.lib.ys_xyxyxyxy2xywhr(engine.ctx, _ptr(c), c.shape[0], 0, _ptr(out)))
+    return out
 
 
 def make_jitter(n):
@@ -206,6 +233,39 @@ def augment_labels(engine, srcs, lab_off, cls, boxes, keypoints, items, imgsz, p
     return out
 
 
+def augment_labels_obb(engine, srcs, lab_off, cls, boxes, corners, items, imgsz, perspective=False, flags=0, capacity=None):
+    """ys_augment_labels_obb on HOST arrays: -> dict(batch_idx, cls, bboxes [capacity, 5], count)."""
+    srcs, items = np.ascontiguousarray(srcs, SRC_DTYPE), np.ascontiguousarray(items, ITEM_DTYPE)
+    lab_off = np.ascontiguousarray(lab_off, np.int32)
+    cls, boxes, corners = (np.ascontiguousarray(a, np.float32) for a in (cls, boxes, corners))
+    cap = int(capacity if capacity is not None else max(1, int(lab_off[-1])))
+    n = max(cap, 0)
+    out = dict(batch_idx=np.empty((n,), np.float32), cls=np.empty((n,), np.float32), bboxes=np.empty((n, 5), np.float32))
+    cnt = C.c_int32(-1)
+    _lib.check(engine.lib, engine.lib.ys_augment_labels_obb(engine.ctx, _ptr(srcs), _ptr(lab_off), _ptr(cls), _ptr(boxes), _ptr(corners), _ptr(items), items.shape[0], 0,
+                                                            int(imgsz), int(bool(perspective)), int(flags), cap, _ptr(out["batch_idx"]), _ptr(out["cls"]),
+                                                            _ptr(out["bboxes"]), C.byref(cnt)))
+    out["count"] = cnt.value
+    return out
+
+
+def augment_letterbox_labels_obb(engine, srcs, lab_off, cls, boxes, corners, items, imgsz, flags=0, capacity=None):
+    """ys_augment_letterbox_labels_obb on HOST arrays: -> dict(batch_idx, cls, bboxes [capacity, 5], count)."""
+    srcs, items = np.ascontiguousarray(srcs, SRC_DTYPE), np.ascontiguousarray(items, ITEM_DTYPE)
+    lab_off = np.ascontiguousarray(lab_off, np.int32)
+    assert lab_off.shape[0] == srcs.shape[0] + 1, (lab_off.shape, srcs.shape)
+    cls, boxes, corners = (np.ascontiguousarray(a, np.float32) for a in (cls, boxes, corners))
+    cap = int(capacity if capacity is not None else max(1, int(lab_off[-1])))
+    n = max(cap, 0)
+    out = dict(batch_idx=np.empty((n,), np.float32), cls=np.empty((n,), np.float32), bboxes=np.empty((n, 5), np.float32))
+    cnt = C.c_int32(-1)
+    _lib.check(engine.lib, engine.lib.ys_augment_letterbox_labels_obb(engine.ctx, _ptr(srcs), srcs.shape[0], _ptr(lab_off), _ptr(cls), _ptr(boxes), _ptr(corners),
+                                                                      _ptr(items), items.shape[0], 0, int(imgsz), int(flags), cap, _ptr(out["batch_idx"]),
+                                                                      _ptr(out["cls"]), _ptr(out["bboxes"]), C.byref(cnt)))
+    out["count"] = cnt.value
+    return out
+
+
 def augment_letterbox(engine, arena, srcs, items, imgsz, mask_ratio=4, with_masks=False, jitter=None):
     """ys_augment_letterbox (jitter rows given: ys_augment_letterbox_jitter) on HOST arrays: -> (images fp32 [B, 3, s, s], masks fp32 [B, s/r, s/r] or None).
     Reads src[0] and the flips of an item."""
@@ -284,14 +344,14 @@ def draw_items(rng, indices, s, count, hyp, fliplr=0.5, flipud=0.0, hsv=None):
 
 
 class DeviceBatch:
-    """One collated training batch that lives in HBM: device pointers to images fp32 [B, 3, s, s], batch_idx / cls [capacity], bboxes [capacity, 4],
-    masks [B, s/r, s/r] and keypoints [capacity, K, 3] (None when absent) and the device int `count`.  Rows [count, capacity) carry batch_idx -1,
+    """One collated training batch that lives in HBM: device pointers to images fp32 [B, 3, s, s], batch_idx / cls [capacity], bboxes [capacity, box_dim]
+    (box_dim 4: cxcywh; 5: an OBB batch's cx, cy, w, h, angle), masks [B, s/r, s/r] and keypoints [capacity, K, 3] (None when absent) and the device int `count`.  Rows [count, capacity) carry batch_idx -1,
     which the criteria skip: n_labels = capacity, no host read.  n_input = the labels of the batch's tiles BEFORE the filters (a host number; in the
     LetterBox branch, which filters nothing, the batch's exact label count).  mode = the branch that produced it: "mosaic" or "letterbox"."""
 
     def __init__(self, engine, batch, imgsz, capacity, images, batch_idx, cls, bboxes, count, masks=None, keypoints=None, kpt_num=0, mask_ratio=4,
-                 n_input=0, max_per_image=64, mode="mosaic"):
-        self.mode = mode
+                 n_input=0, max_per_image=64, mode="mosaic", box_dim=4):
+        self.mode, self.box_dim = mode, int(box_dim)
         self.engine, self.batch, self.imgsz, self.capacity = engine, batch, imgsz, capacity
         self.images, self.batch_idx, self.cls, self.bboxes, self.count = images, batch_idx, cls, bboxes, count
         self.masks, self.keypoints, self.kpt_num, self.mask_ratio, self.n_input = masks, keypoints, kpt_num, mask_ratio, n_input
@@ -305,7 +365,7 @@ class DeviceBatch:
             raise _lib.YsError(1, "augmenter kept %d labels, capacity is %d" % (n, cap))
         out = dict(images=e.from_device(self.images, (self.batch, 3, s, s), np.float32),
                    batch_idx=e.from_device(self.batch_idx, (cap,), np.float32)[:n], cls=e.from_device(self.cls, (cap,), np.float32)[:n],
-                   bboxes=e.from_device(self.bboxes, (cap, 4), np.float32)[:n])
+                   bboxes=e.from_device(self.bboxes, (cap, self.box_dim), np.float32)[:n])
         if self.masks is not None:
             out["masks"] = e.from_device(self.masks, (self.batch, s // self.mask_ratio, s // self.mask_ratio), np.float32)
         if self.keypoints is not None:
@@ -325,7 +385,9 @@ class MosaicAugmenter:
     the LetterBox flag is not handed to it).
     hsv = (hgain, sgain, vgain) -- the reference's default is (0.015, 0.7, 0.4) -- adds RandomHSV to both branches: draw() then returns (items, rows) with
     one ColorJitter row per image, drawn after the image's two flip draws (draw_jitter), run(items, rows) uploads the rows beside the item table and calls the
-    *_jitter entries.  hsv = None (the default) draws nothing more and calls the plain entries."""
+    *_jitter entries.  hsv = None (the default) draws nothing more and calls the plain entries.
+    OBB: labels that carry "obb" [n, 4, 2] pixel corners ("bboxes" may be left out: pack_labels) are uploaded once beside the boxes, the batch's boxes are
+    [capacity, 5] and both branches call the *_obb label entries.  Those take no flags, and an OBB label has neither masks nor keypoints: each is refused."""
 
     def __init__(self, engine, images_u8, labels, imgsz, masks=None, mask_ratio=4, degrees=0.0, translate=0.1, scale=0.5, shear=0.0, perspective=0.0,
                  fliplr=0.5, flipud=0.0, seed=0, flags=0, max_batch=64, hsv=None):
@@ -339,6 +401,12 @@ class MosaicAugmenter:
         self.mode = "mosaic"
         arena, self.srcs = pack_sources(images_u8, masks)
         self.lab_off, cls, boxes, kp = pack_labels(labels)
+        obb = pack_obb(labels)
+        if obb is not None and (self.flags != 0 or masks is not None or kp is not None):
+            raise ValueError("OBB labels take flags = 0 (the box-flip switches have nothing to act on) and neither masks nor keypoints")
+        if obb is not None and obb.shape[0] != boxes.shape[0]:
+            raise ValueError("every source's labels must carry \"obb\" corners, or none")
+        self.obb, self.box_dim = obb is not None, (5 if obb is not None else 4)
         self.count = len(images_u8)
         self.with_masks, self.K = masks is not None, (kp.shape[1] if kp is not None else 0)
         e = engine
@@ -346,6 +414,7 @@ class MosaicAugmenter:
                         e.to_device(boxes if boxes.size else np.zeros(4, np.float32))]
         self.d_arena, self.d_srcs, self.d_lab_off, self.d_cls, self.d_boxes = self._static
         self.d_kp = e.to_device(kp if kp.size else np.zeros(3, np.float32)) if kp is not None else None
+        self.d_obb = e.to_device(obb if obb.size else np.zeros(8, np.float32)) if self.obb else None
         per_src = np.diff(self.lab_off)
         self.max_batch = int(max_batch)
         self.max_per_image = max(1, int(np.sort(per_src)[::-1][:4].sum()))                  # four tiles per image
@@ -355,16 +424,16 @@ class MosaicAugmenter:
         self.d_jitter = e.malloc(B * JITTER_DTYPE.itemsize) if self.hsv is not None else None
         self.d_images = e.malloc(B * 3 * s * s * 4)
         self.d_masks = e.malloc(B * (s // self.r) ** 2 * 4) if self.with_masks else None
-        self.d_bidx, self.d_ocls, self.d_obox, self.d_cnt = e.malloc(cap * 4), e.malloc(cap * 4), e.malloc(cap * 16), e.malloc(4)
+        self.d_bidx, self.d_ocls, self.d_obox, self.d_cnt = e.malloc(cap * 4), e.malloc(cap * 4), e.malloc(cap * 4 * self.box_dim), e.malloc(4)
         self.d_okp = e.malloc(cap * self.K * 12) if self.K else None
 
     def close(self):
         e = self.engine
-        for p in self._static + [self.d_kp, self.d_items, self.d_jitter, self.d_images, self.d_masks, self.d_bidx, self.d_ocls, self.d_obox, self.d_cnt, self.d_okp]:
+        for p in self._static + [self.d_kp, self.d_obb, self.d_items, self.d_jitter, self.d_images, self.d_masks, self.d_bidx, self.d_ocls, self.d_obox, self.d_cnt, self.d_okp]:
             if p is not None:
                 e.free(p)
         self._static = []
-        self.d_kp = self.d_items = self.d_jitter = self.d_images = self.d_masks = self.d_bidx = self.d_ocls = self.d_obox = self.d_cnt = self.d_okp = None
+        self.d_kp = self.d_obb = self.d_items = self.d_jitter = self.d_images = self.d_masks = self.d_bidx = self.d_ocls = self.d_obox = self.d_cnt = self.d_okp = None
 
     def close_mosaic(self, closed):
         """YoloDataset.CloseMosaic(closed): True = the LetterBox pipeline from the next batch on, False = back to Mosaic + RandomPerspective."""
@@ -397,12 +466,16 @@ class MosaicAugmenter:
         else:
             _lib.check(lib, lib.ys_augment_letterbox_jitter(e.ctx, self.d_arena, self.d_srcs, self.count, self.d_items, B, 1, self.s, self.r,
                                                             self._upload_jitter(jitter, B), self.d_images, self.d_masks))
-        _lib.check(lib, lib.ys_augment_letterbox_labels(e.ctx, self.d_srcs, self.count, self.d_lab_off, self.d_cls, self.d_boxes, self.d_kp, self.K, 3, self.d_items,
-                                                        B, 1, self.s, self.flags, self.capacity, self.d_bidx, self.d_ocls, self.d_obox,
-                                                        self.d_okp, self.d_cnt))
+        if self.obb:
+            _lib.check(lib, lib.ys_augment_letterbox_labels_obb(e.ctx, self.d_srcs, self.count, self.d_lab_off, self.d_cls, self.d_boxes, self.d_obb, self.d_items, B, 1,
+                                                                self.s, 0, self.capacity, self.d_bidx, self.d_ocls, self.d_obox, self.d_cnt))
+        else:
+            _lib.check(lib, lib.ys_augment_letterbox_labels(e.ctx, self.d_srcs, self.count, self.d_lab_off, self.d_cls, self.d_boxes, self.d_kp, self.K, 3, self.d_items,
+                                                            B, 1, self.s, self.flags, self.capacity, self.d_bidx, self.d_ocls, self.d_obox,
+                                                            self.d_okp, self.d_cnt))
         n_input = int(sum(int(self.lab_off[k + 1] - self.lab_off[k]) for k in items["src"][:, 0]))      # nothing is filtered: the exact label count
         return DeviceBatch(e, B, self.s, self.capacity, self.d_images, self.d_bidx, self.d_ocls, self.d_obox, self.d_cnt, masks=self.d_masks,
-                           keypoints=self.d_okp, kpt_num=self.K, mask_ratio=self.r, n_input=n_input, max_per_image=self.max_per_image, mode="letterbox")
+                           keypoints=self.d_okp, kpt_num=self.K, mask_ratio=self.r, n_input=n_input, max_per_image=self.max_per_image, mode="letterbox", box_dim=self.box_dim)
 
     def run(self, items, jitter=None):
         """Upload `items` (and the ColorJitter rows `jitter`, one per item; None = no jitter) and launch the kernels of the current branch (`mode`) on the
@@ -421,11 +494,15 @@ class MosaicAugmenter:
         else:
             _lib.check(lib, lib.ys_augment_mosaic_jitter(e.ctx, self.d_arena, self.d_srcs, self.count, self.d_items, B, 1, self.s, self.r, persp,
                                                          self._upload_jitter(jitter, B), self.d_images, self.d_masks))
-        _lib.check(lib, lib.ys_augment_labels(e.ctx, self.d_srcs, self.d_lab_off, self.d_cls, self.d_boxes, self.d_kp, self.K, 3, self.d_items, B, 1, self.s, persp,
-                                              self.flags & ~YS_AUG_FLIP_KEEP_SIZE, self.capacity, self.d_bidx, self.d_ocls, self.d_obox, self.d_okp, self.d_cnt))
+        if self.obb:
+            _lib.check(lib, lib.ys_augment_labels_obb(e.ctx, self.d_srcs, self.d_lab_off, self.d_cls, self.d_boxes, self.d_obb, self.d_items, B, 1, self.s, persp, 0,
+                                                      self.capacity, self.d_bidx, self.d_ocls, self.d_obox, self.d_cnt))
+        else:
+            _lib.check(lib, lib.ys_augment_labels(e.ctx, self.d_srcs, self.d_lab_off, self.d_cls, self.d_boxes, self.d_kp, self.K, 3, self.d_items, B, 1, self.s, persp,
+                                                  self.flags & ~YS_AUG_FLIP_KEEP_SIZE, self.capacity, self.d_bidx, self.d_ocls, self.d_obox, self.d_okp, self.d_cnt))
         n_input = int(sum(int(self.lab_off[k + 1] - self.lab_off[k]) for k in items["src"].reshape(-1)))
         return DeviceBatch(e, B, self.s, self.capacity, self.d_images, self.d_bidx, self.d_ocls, self.d_obox, self.d_cnt, masks=self.d_masks,
-                           keypoints=self.d_okp, kpt_num=self.K, mask_ratio=self.r, n_input=n_input, max_per_image=self.max_per_image)
+                           keypoints=self.d_okp, kpt_num=self.K, mask_ratio=self.r, n_input=n_input, max_per_image=self.max_per_image, box_dim=self.box_dim)
 
     def batch(self, indices):
         drawn = self.draw(indices)

@@ -24,8 +24,8 @@
 // fp32 is (see aug_blend_u8), and it has a price: measured at B = 64 / 640 px the kernel reaches 17 % of the HBM rate -- it is bound by its instruction
 // stream, about 5x above the HBM estimate of its bytes (DESIGN.md "Training input on the device").
 //
-// Scope (include/yolosharp_hip.h lists the same): kpt_dim = 3 only (apply_keypoints reads column 2); no OBB corner labels (xyxyxyxy2xywhr is host
-// code in the reference); RandomHSV (torchvision ColorJitter on the bytes) runs in the epilogue of the two image kernels, see "ColorJitter" below; of the no-mosaic branches the close-mosaic one (LetterBox) is built below,
+// Scope (include/yolosharp_hip.h lists the same): kpt_dim = 3 only (apply_keypoints reads column 2); OBB corner labels
+// (xyxyxyxy2xywhr, host code in the reference) are the <true> instances of the two label kernels, see "OBB corner labels" below; RandomHSV (torchvision ColorJitter on the bytes) runs in the epilogue of the two image kernels, see "ColorJitter" below; of the no-mosaic branches the close-mosaic one (LetterBox) is built below,
 // the `rand > p` one of Augment.Mosaic is not (it yields images of unequal sizes).  Deviations: a label-free
 // sample is still warped (RandomPerspective.Apply returns the unwarped canvas, :666-669); where the reference's mask slice would run past the
 // source mask (it throws) the kernel reads 0.
@@ -427,6 +427,106 @@ __device__ inline void aug_label_kpts(const float* __restrict__ kin, int K, floa
   }
 }
 
+// ---------------------------------------------------------------------------------------------------------------- OBB corner labels
+// xyxyxyxy2xywhr (Utils/Ops.cs:44-54) is OpenCV MinAreaRect of a label's four corners, host code in the reference (YoloDataset.GetTensor, :110-129).
+// Here: the enclosing rectangle of minimum area of four points, without a hull and without indexed private arrays.  The minimum-area rectangle has a
+// side collinear with a hull edge; every hull edge is one of the 6 point pairs; the bounding rectangle along any OTHER pair's direction still encloses
+// the points -- so the minimum over the 6 pair directions is the answer.  Zero-length pairs are skipped.  6 directions x 3 projections (the points are
+// taken relative to point 0), unrolled, everything in registers.
+//   pair order: (0,1) (1,2) (2,3) (3,0) (0,2) (1,3); the FIRST strict minimum of the area wins: the row is a pure function of the input.
+//   canonical form (OpenCV >= 4.5.1's documented one; the reference pins OpenCvSharp 4.11): a pair's direction is folded by quarter turns -- exact: swaps
+//   and sign changes -- into u = (ux >= 0, uy > 0); angle = atan2(uy, ux) in (0, pi/2], w = the extent along u, h = the extent along its normal.  An
+//   axis-aligned rectangle is angle = pi/2 with (w, h) = (y extent, x extent), never angle = 0.  A rectangle has one such representative.
+//   precision: the inputs are fp32, everything from the differences to atan2 is double, the five results are rounded to fp32 once.  Products of two
+//   fp32 values are exact in double, so exactly collinear points on a border (the clipped case) give an extent of exactly 0, whole-number inputs give
+//   exact areas (ties between the parallel edges of a rectangle are exact ties, whatever corner the list starts at), and the rounding of the
+//   direction never decides between two candidates that differ by more than 1e-15 relative.  One thread per label: the cost is nothing.
+//   degenerate inputs, finite rows: four identical points give (x, y, 0, 0, 0).  Exactly collinear points (two distinct points included) give
+//   w = the span, h = 0 and the line's OWN direction folded by half turns into (0, pi]: the one kind of row whose angle can exceed pi/2 (a line in
+//   the second quadrant; a horizontal one is pi).  A quarter-turn fold cannot name such a segment with w as its span -- (span, 0, angle - pi/2) is
+//   the segment turned by 90 degrees -- and the row must describe the points it encloses.  DEVIATION: OpenCV leaves the raw atan2 of the line, in
+//   (-pi, pi], there.
+// UNPINNED: OpenCV is not available to the tests; the choice among geometrically different rectangles of EQUAL area (an acute triangle: all three
+// edges tie exactly; many quads clipped to the image) is this file's pair order, not pinned against the reference binary.
+struct AugRect { double area, w, h, cx, cy, ang; };
+
+// the candidate along the pair a -> b (coordinates relative to point 0, which is the origin; 1..3 the other points)
+__device__ __forceinline__ void aug_rect_pair(double ax, double ay, double bx, double by, double x1, double y1, double x2, double y2, double x3, double y3,
+                                              bool& any, AugRect& best) {
+  double ux = bx - ax, uy = by - ay;
+  if (ux == 0.0 && uy == 0.0) return;
+  if (uy < 0.0 || (uy == 0.0 && ux < 0.0)) { ux = -ux; uy = -uy; }                   // the upper half plane, +x axis included
+  if (uy == 0.0) { uy = ux; ux = 0.0; }                                              // +x axis: a quarter turn forward -> pi/2
+  else if (ux < 0.0) { const double t = ux; ux = uy; uy = -t; }                      // second quadrant: a quarter turn back
+  // projections on u and on n = (-uy, ux), unnormalised; point 0 projects to (0, 0)
+  const double t1 = x1 * ux + y1 * uy, t2 = x2 * ux + y2 * uy, t3 = x3 * ux + y3 * uy;
+  const double m1 = y1 * ux - x1 * uy, m2 = y2 * ux - x2 * uy, m3 = y3 * ux - x3 * uy;
+  const double tlo = fmin(fmin(0.0, t1), fmin(t2, t3)), thi = fmax(fmax(0.0, t1), fmax(t2, t3));
+  const double mlo = fmin(fmin(0.0, m1), fmin(m2, m3)), mhi = fmax(fmax(0.0, m1), fmax(m2, m3));
+  const double len2 = ux * ux + uy * uy;
+  const double area = ((thi - tlo) * (mhi - mlo)) / len2;
+  if (any && !(area < best.area)) return;
+  const double len = sqrt(len2), tc = (tlo + thi) / 2.0, mc = (mlo + mhi) / 2.0;
+  any = true;
+  best.area = area; best.w = (thi - tlo) / len; best.h = (mhi - mlo) / len;
+  best.cx = (tc * ux - mc * uy) / len2; best.cy = (tc * uy + mc * ux) / len2;
+  best.ang = atan2(uy, ux);
+}
+
+// c = x0 y0 x1 y1 x2 y2 x3 y3 (constant indices only) -> out = cx, cy, w, h (the units of c), angle (radians)
+__device__ inline void aug_min_area_rect(const float* c, float* out) {
+  const double ox = (double)c[0], oy = (double)c[1];
+  const double x1 = (double)c[2] - ox, y1 = (double)c[3] - oy, x2 = (double)c[4] - ox, y2 = (double)c[5] - oy, x3 = (double)c[6] - ox, y3 = (double)c[7] - oy;
+  bool any = false;
+  AugRect r;
+  r.area = 0.0; r.w = 0.0; r.h = 0.0; r.cx = 0.0; r.cy = 0.0; r.ang = 0.0;           // four identical points
+  aug_rect_pair(0.0, 0.0, x1, y1, x1, y1, x2, y2, x3, y3, any, r);
+  aug_rect_pair(x1, y1, x2, y2, x1, y1, x2, y2, x3, y3, any, r);
+  aug_rect_pair(x2, y2, x3, y3, x1, y1, x2, y2, x3, y3, any, r);
+  aug_rect_pair(x3, y3, 0.0, 0.0, x1, y1, x2, y2, x3, y3, any, r);
+  aug_rect_pair(0.0, 0.0, x2, y2, x1, y1, x2, y2, x3, y3, any, r);
+  aug_rect_pair(x1, y1, x3, y3, x1, y1, x2, y2, x3, y3, any, r);
+  if (r.w == 0.0 && r.h != 0.0) { r.w = r.h; r.h = 0.0; r.ang += 1.5707963267948966; }   // exactly collinear along the normal: w = the span, the line's direction
+  out[0] = (float)(ox + r.cx); out[1] = (float)(oy + r.cy); out[2] = (float)r.w; out[3] = (float)r.h; out[4] = (float)r.ang;
+}
+
+// corners [4][2] of one label -> the criterion's row (cx / s, cy / s, w / s, h / s, angle), fp32 in the reference's order: + pad; warp (the Mosaic
+// branch): apply_obb_corners (Augment.cs:604-635: (x, y, 1) . M^T, divided by the third component only when perspective > 0 -- apply_keypoints always
+// divides) and clip_obb_corners (Utils/Ops.cs:191-199: clamp to [0, s]); FlipLR x <- s - x, FlipUD y <- s - y (:908-911, :958-961); the rectangle;
+// columns 0-3 DIVIDED by s (YoloDataset.cs:121: a division, not mul(1 / s)).  _mosaic4 does not clip the corners to the canvas (:253-256).
+__device__ inline void aug_label_obb(const float* __restrict__ cin, float padw, float padh, bool warp, const float* M, int s, int perspective, int flip_lr,
+                                     int flip_ud, float* out) {
+  const float S = (float)s;
+  float c[8];
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    float x = cin[2 * k] + padw, y = cin[2 * k + 1] + padh;
+    if (warp) {
+      float px = (x * M[0] + y * M[1]) + M[2], py = (x * M[3] + y * M[4]) + M[5];
+      if (perspective) { const float pw = (x * M[6] + y * M[7]) + M[8]; px /= pw; py /= pw; }
+      x = fminf(fmaxf(px, 0.0f), S); y = fminf(fmaxf(py, 0.0f), S);
+    }
+    if (flip_lr) x = S - x;
+    if (flip_ud) y = S - y;
+    c[2 * k] = x; c[2 * k + 1] = y;
+  }
+  aug_min_area_rect(c, out);
+  out[0] = out[0] / S; out[1] = out[1] / S; out[2] = out[2] / S; out[3] = out[3] / S;
+}
+
+// ys_xyxyxyxy2xywhr: the operator on its own, one thread per row, pixels in, pixels and radians out
+__global__ void __launch_bounds__(AUG_T)
+aug_xyxyxyxy2xywhr_kernel(const float* __restrict__ corners, int n, float* __restrict__ out) {
+  const int i = blockIdx.x * AUG_T + threadIdx.x;
+  if (i >= n) return;
+  float c[8], r[5];
+#pragma unroll
+  for (int k = 0; k < 8; k++) c[k] = corners[8 * (long long)i + k];
+  aug_min_area_rect(c, r);
+#pragma unroll
+  for (int k = 0; k < 5; k++) out[5 * (long long)i + k] = r[k];
+}
+
 // offs[b] = counts[0] + ... + counts[b - 1], offs[B] = the total: one workgroup, chunks of AUG_T with a carry (Hillis-Steele in LDS, fixed order)
 __global__ void __launch_bounds__(AUG_T)
 aug_count_scan_kernel(const int* __restrict__ counts, int B, int* __restrict__ offs) {
@@ -453,6 +553,8 @@ aug_count_scan_kernel(const int* __restrict__ counts, int B, int* __restrict__ o
 
 // pass 0: counts[b] = kept labels of image b.  pass 1: rows [base(b), base(b) + counts[b]) with base = the exclusive scan of counts (counts[B + b], written by aug_count_scan_kernel between the passes), the tail
 // [total, capacity) = (batch_idx -1, zeros), *out_count = total (a total above capacity is reported as it is; rows past capacity are not written).
+// OBB: kpts holds the labels' corners [n][4][2] instead, o_box has 5 columns (aug_label_obb) and o_kpt is NULL; `boxes` alone decides what is kept.
+template <bool OBB>
 __global__ void __launch_bounds__(AUG_T)
 aug_labels_kernel(const ys_aug_src* __restrict__ srcs, int n_src, const int* __restrict__ lab_off, const float* __restrict__ cls,
                   const float* __restrict__ boxes, const float* __restrict__ kpts, int K, const ys_aug_item* __restrict__ items, int B, int s,
@@ -507,9 +609,16 @@ aug_labels_kernel(const ys_aug_src* __restrict__ srcs, int n_src, const int* __r
       const long long rowi = (long long)s_base + rank;
       if (rowi < capacity) {
         o_bidx[rowi] = (float)b; o_cls[rowi] = cls[l];
-        o_box[4 * rowi] = row[0]; o_box[4 * rowi + 1] = row[1]; o_box[4 * rowi + 2] = row[2]; o_box[4 * rowi + 3] = row[3];
-        if (o_kpt) aug_label_kpts(kpts + (long long)l * K * 3, K, (float)s_padw[t], (float)s_padh[t], M, s, it.flip_lr != 0, it.flip_ud != 0,
-                                  o_kpt + rowi * K * 3);
+        if constexpr (OBB) {
+          float r5[5];
+          aug_label_obb(kpts + 8 * (long long)l, (float)s_padw[t], (float)s_padh[t], true, M, s, perspective, it.flip_lr != 0, it.flip_ud != 0, r5);
+#pragma unroll
+          for (int k = 0; k < 5; k++) o_box[5 * rowi + k] = r5[k];
+        } else {
+          o_box[4 * rowi] = row[0]; o_box[4 * rowi + 1] = row[1]; o_box[4 * rowi + 2] = row[2]; o_box[4 * rowi + 3] = row[3];
+          if (o_kpt) aug_label_kpts(kpts + (long long)l * K * 3, K, (float)s_padw[t], (float)s_padh[t], M, s, it.flip_lr != 0, it.flip_ud != 0,
+                                    o_kpt + rowi * K * 3);
+        }
       }
     }
     done += chunk;
@@ -522,8 +631,13 @@ aug_labels_kernel(const ys_aug_src* __restrict__ srcs, int n_src, const int* __r
   if (b == 0 && tid == 0) *o_count = s_total;
   for (long long rowi = (long long)s_total + (long long)b * AUG_T + tid; rowi < capacity; rowi += (long long)B * AUG_T) {
     o_bidx[rowi] = -1.0f; o_cls[rowi] = 0.0f;
-    o_box[4 * rowi] = 0.f; o_box[4 * rowi + 1] = 0.f; o_box[4 * rowi + 2] = 0.f; o_box[4 * rowi + 3] = 0.f;
-    if (o_kpt) for (int k = 0; k < K * 3; k++) o_kpt[rowi * K * 3 + k] = 0.f;
+    if constexpr (OBB) {
+#pragma unroll
+      for (int k = 0; k < 5; k++) o_box[5 * rowi + k] = 0.f;
+    } else {
+      o_box[4 * rowi] = 0.f; o_box[4 * rowi + 1] = 0.f; o_box[4 * rowi + 2] = 0.f; o_box[4 * rowi + 3] = 0.f;
+      if (o_kpt) for (int k = 0; k < K * 3; k++) o_kpt[rowi * K * 3 + k] = 0.f;
+    }
   }
 }
 
@@ -685,7 +799,10 @@ aug_letterbox_count_kernel(const ys_aug_src* __restrict__ srcs, int n_src, const
 }
 
 // one workgroup per image: rows [offs[b], offs[b + 1]) = the source's labels in order; the tail [total, capacity) = (batch_idx -1, zeros);
-// *o_count = total (a total above capacity is reported as it is; rows past capacity are not written)
+// *o_count = total (a total above capacity is reported as it is; rows past capacity are not written).
+// OBB: kpts holds the corners [n][4][2], o_box has 5 columns, o_kpt is NULL: corners + (pad_l, pad_u), not scaled by ratio like the boxes (:746-749),
+// nothing clipped (a corner may lie outside [0, s]), the flips (:825-828), aug_label_obb's rectangle and division.
+template <bool OBB>
 __global__ void __launch_bounds__(AUG_T)
 aug_letterbox_labels_kernel(const ys_aug_src* __restrict__ srcs, int n_src, const int* __restrict__ lab_off, const float* __restrict__ cls,
                             const float* __restrict__ boxes, const float* __restrict__ kpts, int K, const ys_aug_item* __restrict__ items, int B, int s,
@@ -704,6 +821,14 @@ aug_letterbox_labels_kernel(const ys_aug_src* __restrict__ srcs, int n_src, cons
       const long long rowi = (long long)base + j;
       if (rowi >= capacity) break;
       const int l = first + j;
+      if constexpr (OBB) {
+        float r5[5];
+        aug_label_obb(kpts + 8 * (long long)l, pl, pu, false, nullptr, s, 0, flr, fud, r5);
+        o_bidx[rowi] = (float)b; o_cls[rowi] = cls[l];
+#pragma unroll
+        for (int p = 0; p < 5; p++) o_box[5 * rowi + p] = r5[p];
+        continue;
+      }
       const float x1 = boxes[4 * l], y1 = boxes[4 * l + 1], x2 = boxes[4 * l + 2], y2 = boxes[4 * l + 3];
       float cx = (x1 + x2) / 2.0f + pl, cy = (y1 + y2) / 2.0f + pu, bw = x2 - x1, bh = y2 - y1;
       if (flr) { cx = S - cx; if (!keep_size) bw = S - bw; }
@@ -725,6 +850,11 @@ aug_letterbox_labels_kernel(const ys_aug_src* __restrict__ srcs, int n_src, cons
   if (b == 0 && tid == 0) *o_count = total;
   for (long long rowi = (long long)total + (long long)b * AUG_T + tid; rowi < capacity; rowi += (long long)B * AUG_T) {
     o_bidx[rowi] = -1.0f; o_cls[rowi] = 0.0f;
+    if constexpr (OBB) {
+#pragma unroll
+      for (int p = 0; p < 5; p++) o_box[5 * rowi + p] = 0.f;
+      continue;
+    }
     o_box[4 * rowi] = 0.f; o_box[4 * rowi + 1] = 0.f; o_box[4 * rowi + 2] = 0.f; o_box[4 * rowi + 3] = 0.f;
     if (o_kpt) for (int p = 0; p < K * 3; p++) o_kpt[rowi * K * 3 + p] = 0.f;
   }
@@ -844,13 +974,20 @@ int ys_aug_mosaic_launch(hipStream_t st, const unsigned char* arena, const ys_au
 
 int ys_aug_labels_launch(hipStream_t st, const ys_aug_src* srcs, int n_src, const int* lab_off, const float* cls, const float* boxes,
                          const float* kpts, int K, const ys_aug_item* items, int B, int s, int perspective, int flags, int capacity, void* ws,
-                         float* o_bidx, float* o_cls, float* o_box, float* o_kpt, int* o_count) {
+                         float* o_bidx, float* o_cls, float* o_box, float* o_kpt, int* o_count, int obb) {
   int* counts = (int*)((char*)ws + (size_t)B * sizeof(AugParams));
   for (int pass = 0; pass < 2; pass++) {
     if (pass == 1) YS_LAUNCH(aug_count_scan_kernel, 1, AUG_T, st, (const int*)counts, B, counts + B);
-    YS_LAUNCH(aug_labels_kernel, B, AUG_T, st, srcs, n_src, lab_off, cls, boxes, kpts, K, items, B, s, perspective, flags, capacity, pass, counts,
-              o_bidx, o_cls, o_box, o_kpt, o_count);
+    if (obb) YS_LAUNCH((aug_labels_kernel<true>), B, AUG_T, st, srcs, n_src, lab_off, cls, boxes, kpts, 0, items, B, s, perspective, flags, capacity, pass, counts,
+                       o_bidx, o_cls, o_box, (float*)nullptr, o_count);
+    else YS_LAUNCH((aug_labels_kernel<false>), B, AUG_T, st, srcs, n_src, lab_off, cls, boxes, kpts, K, items, B, s, perspective, flags, capacity, pass, counts,
+                   o_bidx, o_cls, o_box, o_kpt, o_count);
   }
+  return YS_OK;
+}
+
+int ys_xyxyxyxy2xywhr_launch(hipStream_t st, const float* corners, int n, float* out) {
+  YS_LAUNCH(aug_xyxyxyxy2xywhr_kernel, ys_cdiv(n, AUG_T), AUG_T, st, corners, n, out);
   return YS_OK;
 }
 
@@ -872,12 +1009,14 @@ int ys_aug_letterbox_launch(hipStream_t st, const unsigned char* arena, const ys
 
 int ys_aug_letterbox_labels_launch(hipStream_t st, const ys_aug_src* srcs, int n_src, const int* lab_off, const float* cls, const float* boxes,
                                    const float* kpts, int K, const ys_aug_item* items, int B, int s, int flags, int capacity, void* ws, float* o_bidx,
-                                   float* o_cls, float* o_box, float* o_kpt, int* o_count) {
+                                   float* o_cls, float* o_box, float* o_kpt, int* o_count, int obb) {
   int* counts = (int*)((char*)ws + (size_t)B * sizeof(AugParams));            // the workspace layout of ys_aug_ws_bytes: counts [B] | offsets [B + 1]
   YS_LAUNCH(aug_letterbox_count_kernel, ys_cdiv(B, AUG_T), AUG_T, st, srcs, n_src, lab_off, items, B, counts);
   YS_LAUNCH(aug_count_scan_kernel, 1, AUG_T, st, (const int*)counts, B, counts + B);
-  YS_LAUNCH(aug_letterbox_labels_kernel, B, AUG_T, st, srcs, n_src, lab_off, cls, boxes, kpts, K, items, B, s, flags, capacity, (const int*)(counts + B),
-            o_bidx, o_cls, o_box, o_kpt, o_count);
+  if (obb) YS_LAUNCH((aug_letterbox_labels_kernel<true>), B, AUG_T, st, srcs, n_src, lab_off, cls, boxes, kpts, 0, items, B, s, flags, capacity,
+                     (const int*)(counts + B), o_bidx, o_cls, o_box, (float*)nullptr, o_count);
+  else YS_LAUNCH((aug_letterbox_labels_kernel<false>), B, AUG_T, st, srcs, n_src, lab_off, cls, boxes, kpts, K, items, B, s, flags, capacity,
+                 (const int*)(counts + B), o_bidx, o_cls, o_box, o_kpt, o_count);
   return YS_OK;
 }
 

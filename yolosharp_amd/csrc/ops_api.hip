@@ -1083,28 +1083,33 @@ extern "C" int ys_augment_mosaic_jitter(ys_ctx* ctx, const uint8_t* arena, const
   return aug_mosaic_impl("ys_augment_mosaic_jitter", ctx, arena, srcs, n_src, items, batch, on_device, imgsz, mask_ratio, perspective, jitter, images, masks);
 }
 
-extern "C" int ys_augment_labels(ys_ctx* ctx, const ys_aug_src* srcs, const int32_t* lab_off, const float* cls, const float* boxes,
-                                 const float* keypoints, int kpt_num, int kpt_dim, const ys_aug_item* items, int batch, int on_device,
-                                 int imgsz, int perspective, int flags, int capacity, float* out_batch_idx, float* out_cls, float* out_bboxes,
-                                 float* out_keypoints, int32_t* out_count) {
-  YS_REQUIRE(ctx && srcs && lab_off && cls && boxes && items && out_batch_idx && out_cls && out_bboxes && out_count, "ys_augment_labels: null argument");
-  YS_REQUIRE(batch > 0 && batch <= 65535 && capacity > 0, "ys_augment_labels: bad shape batch=%d (1..65535) capacity=%d", batch, capacity);
-  YS_REQUIRE(imgsz >= 2 && imgsz % 2 == 0 && imgsz <= 16384, "ys_augment_labels: imgsz %d must be even and in [2, 16384]", imgsz);
-  YS_REQUIRE((keypoints != nullptr) == (out_keypoints != nullptr), "ys_augment_labels: keypoints and out_keypoints go together");
+namespace {
+// ys_augment_labels (corners == NULL) and ys_augment_labels_obb (corners [n, 4, 2] in place of the keypoints, out_bboxes [capacity, 5], flags 0)
+int aug_labels_impl(const char* fn, ys_ctx* ctx, const ys_aug_src* srcs, const int32_t* lab_off, const float* cls, const float* boxes, const float* keypoints,
+                    int kpt_num, int kpt_dim, const float* corners, int obb, const ys_aug_item* items, int batch, int on_device, int imgsz, int perspective,
+                    int flags, int capacity, float* out_batch_idx, float* out_cls, float* out_bboxes, float* out_keypoints, int32_t* out_count) {
+  YS_REQUIRE(ctx && srcs && lab_off && cls && boxes && items && out_batch_idx && out_cls && out_bboxes && out_count && (!obb || corners), "%s: null argument", fn);
+  YS_REQUIRE(batch > 0 && batch <= 65535 && capacity > 0, "%s: bad shape batch=%d (1..65535) capacity=%d", fn, batch, capacity);
+  YS_REQUIRE(imgsz >= 2 && imgsz % 2 == 0 && imgsz <= 16384, "%s: imgsz %d must be even and in [2, 16384]", fn, imgsz);
+  YS_REQUIRE((keypoints != nullptr) == (out_keypoints != nullptr), "%s: keypoints and out_keypoints go together", fn);
   if (keypoints) {
-    YS_REQUIRE(kpt_dim == 3, "ys_augment_labels: kpt_dim %d: only (x, y, visibility) keypoints are supported (apply_keypoints reads column 2)", kpt_dim);
-    YS_REQUIRE(kpt_num > 0, "ys_augment_labels: kpt_num %d", kpt_num);
+    YS_REQUIRE(kpt_dim == 3, "%s: kpt_dim %d: only (x, y, visibility) keypoints are supported (apply_keypoints reads column 2)", fn, kpt_dim);
+    YS_REQUIRE(kpt_num > 0, "%s: kpt_num %d", fn, kpt_num);
   }
-  YS_REQUIRE((flags & ~YS_AUG_SORT_FLIPPED) == 0, "ys_augment_labels: unknown flags 0x%x", flags);
+  if (obb) YS_REQUIRE(flags == 0, "%s: flags 0x%x: the box-flip switches have nothing to act on, flags must be 0", fn, flags);
+  else YS_REQUIRE((flags & ~YS_AUG_SORT_FLIPPED) == 0, "%s: unknown flags 0x%x", fn, flags);
+  // the per-label table beside the boxes: K keypoints of 3 floats, or 4 corners of 2; the width of an output box row
   const int K = keypoints ? kpt_num : 0;
+  const size_t xf = obb ? 8 : (size_t)K * 3, bw = obb ? 5 : 4;
+  const float* extra = obb ? corners : keypoints;
   YS_CHECK_HIP(hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
   YS_TRY(aug_reserve_ws(ctx, batch));
   YsTimer timer(ctx, "augment_labels");
   if (on_device)    // the source count is not part of the signature: lab_off has one entry per source and one more, device items are the caller's responsibility
-    return ys_aug_labels_launch(st, srcs, 0x7fffffff, lab_off, cls, boxes, keypoints, K, items, batch, imgsz, perspective != 0, flags, capacity, ctx->aug_ws,
-                                out_batch_idx, out_cls, out_bboxes, out_keypoints, out_count);
-  YS_TRY(aug_check_items("ys_augment_labels", items, batch, srcs, -1, imgsz, perspective != 0));
+    return ys_aug_labels_launch(st, srcs, 0x7fffffff, lab_off, cls, boxes, extra, K, items, batch, imgsz, perspective != 0, flags, capacity, ctx->aug_ws,
+                                out_batch_idx, out_cls, out_bboxes, out_keypoints, out_count, obb);
+  YS_TRY(aug_check_items(fn, items, batch, srcs, -1, imgsz, perspective != 0));
   int n_src = 0;
   for (int b = 0; b < batch; b++) for (int i = 0; i < 4; i++) n_src = items[b].src[i] + 1 > n_src ? items[b].src[i] + 1 : n_src;
   size_t n_lab = 0;
@@ -1112,33 +1117,67 @@ extern "C" int ys_augment_labels(ys_ctx* ctx, const ys_aug_src* srcs, const int3
     long sum = 0;
     for (int i = 0; i < 4; i++) {
       const int k = items[b].src[i];
-      YS_REQUIRE(lab_off[k] >= 0 && lab_off[k + 1] >= lab_off[k], "ys_augment_labels: lab_off is not non-decreasing at source %d", k);
+      YS_REQUIRE(lab_off[k] >= 0 && lab_off[k + 1] >= lab_off[k], "%s: lab_off is not non-decreasing at source %d", fn, k);
       sum += lab_off[k + 1] - lab_off[k];
       n_lab = (size_t)lab_off[k + 1] > n_lab ? (size_t)lab_off[k + 1] : n_lab;
     }
-    YS_REQUIRE(sum <= capacity, "ys_augment_labels: item %d carries %ld labels over its four tiles, capacity is %d", b, sum, capacity);
+    YS_REQUIRE(sum <= capacity, "%s: item %d carries %ld labels over its four tiles, capacity is %d", fn, b, sum, capacity);
   }
   const size_t cap = (size_t)capacity;
   DevBuf ds, dl, dc, db, dk, di, obi, ocl, obx, okp, ocn;
   YS_TRY(ds.alloc((size_t)n_src * sizeof(ys_aug_src))); YS_TRY(dl.alloc((size_t)(n_src + 1) * 4)); YS_TRY(dc.alloc(n_lab * 4)); YS_TRY(db.alloc(n_lab * 16));
-  YS_TRY(dk.alloc(n_lab * K * 12)); YS_TRY(di.alloc((size_t)batch * sizeof(ys_aug_item)));
-  YS_TRY(obi.alloc(cap * 4)); YS_TRY(ocl.alloc(cap * 4)); YS_TRY(obx.alloc(cap * 16)); YS_TRY(okp.alloc(cap * K * 12)); YS_TRY(ocn.alloc(4));
+  YS_TRY(dk.alloc(n_lab * xf * 4)); YS_TRY(di.alloc((size_t)batch * sizeof(ys_aug_item)));
+  YS_TRY(obi.alloc(cap * 4)); YS_TRY(ocl.alloc(cap * 4)); YS_TRY(obx.alloc(cap * bw * 4)); YS_TRY(okp.alloc(cap * K * 12)); YS_TRY(ocn.alloc(4));
   YS_CHECK_HIP(hipMemcpyAsync(ds.p, srcs, (size_t)n_src * sizeof(ys_aug_src), hipMemcpyHostToDevice, st));
   YS_CHECK_HIP(hipMemcpyAsync(dl.p, lab_off, (size_t)(n_src + 1) * 4, hipMemcpyHostToDevice, st));
   if (n_lab) {
     YS_CHECK_HIP(hipMemcpyAsync(dc.p, cls, n_lab * 4, hipMemcpyHostToDevice, st));
     YS_CHECK_HIP(hipMemcpyAsync(db.p, boxes, n_lab * 16, hipMemcpyHostToDevice, st));
-    if (K) YS_CHECK_HIP(hipMemcpyAsync(dk.p, keypoints, n_lab * K * 12, hipMemcpyHostToDevice, st));
+    if (xf) YS_CHECK_HIP(hipMemcpyAsync(dk.p, extra, n_lab * xf * 4, hipMemcpyHostToDevice, st));
   }
   YS_CHECK_HIP(hipMemcpyAsync(di.p, items, (size_t)batch * sizeof(ys_aug_item), hipMemcpyHostToDevice, st));
-  YS_TRY(ys_aug_labels_launch(st, (const ys_aug_src*)ds.p, n_src, (const int*)dl.p, (const float*)dc.p, (const float*)db.p, K ? (const float*)dk.p : nullptr, K,
+  YS_TRY(ys_aug_labels_launch(st, (const ys_aug_src*)ds.p, n_src, (const int*)dl.p, (const float*)dc.p, (const float*)db.p, xf ? (const float*)dk.p : nullptr, K,
                               (const ys_aug_item*)di.p, batch, imgsz, perspective != 0, flags, capacity, ctx->aug_ws, (float*)obi.p, (float*)ocl.p, (float*)obx.p,
-                              K ? (float*)okp.p : nullptr, (int*)ocn.p));
+                              K ? (float*)okp.p : nullptr, (int*)ocn.p, obb));
   YS_CHECK_HIP(hipMemcpyAsync(out_batch_idx, obi.p, cap * 4, hipMemcpyDeviceToHost, st));
   YS_CHECK_HIP(hipMemcpyAsync(out_cls, ocl.p, cap * 4, hipMemcpyDeviceToHost, st));
-  YS_CHECK_HIP(hipMemcpyAsync(out_bboxes, obx.p, cap * 16, hipMemcpyDeviceToHost, st));
+  YS_CHECK_HIP(hipMemcpyAsync(out_bboxes, obx.p, cap * bw * 4, hipMemcpyDeviceToHost, st));
   if (K) YS_CHECK_HIP(hipMemcpyAsync(out_keypoints, okp.p, cap * K * 12, hipMemcpyDeviceToHost, st));
   YS_CHECK_HIP(hipMemcpyAsync(out_count, ocn.p, 4, hipMemcpyDeviceToHost, st));
+  YS_CHECK_HIP(hipStreamSynchronize(st));
+  return YS_OK;
+}
+}  // namespace
+
+extern "C" int ys_augment_labels(ys_ctx* ctx, const ys_aug_src* srcs, const int32_t* lab_off, const float* cls, const float* boxes,
+                                 const float* keypoints, int kpt_num, int kpt_dim, const ys_aug_item* items, int batch, int on_device,
+                                 int imgsz, int perspective, int flags, int capacity, float* out_batch_idx, float* out_cls, float* out_bboxes,
+                                 float* out_keypoints, int32_t* out_count) {
+  return aug_labels_impl("ys_augment_labels", ctx, srcs, lab_off, cls, boxes, keypoints, kpt_num, kpt_dim, nullptr, 0, items, batch, on_device, imgsz, perspective,
+                         flags, capacity, out_batch_idx, out_cls, out_bboxes, out_keypoints, out_count);
+}
+
+// OBB corner labels (Data/YoloDataset.cs:110-129, 216-244): the corners through the chain, the minimum-area rectangle, rows of 5
+extern "C" int ys_augment_labels_obb(ys_ctx* ctx, const ys_aug_src* srcs, const int32_t* lab_off, const float* cls, const float* boxes,
+                                     const float* corners, const ys_aug_item* items, int batch, int on_device, int imgsz, int perspective, int flags,
+                                     int capacity, float* out_batch_idx, float* out_cls, float* out_bboxes, int32_t* out_count) {
+  return aug_labels_impl("ys_augment_labels_obb", ctx, srcs, lab_off, cls, boxes, nullptr, 0, 3, corners, 1, items, batch, on_device, imgsz, perspective, flags,
+                         capacity, out_batch_idx, out_cls, out_bboxes, nullptr, out_count);
+}
+
+// the rectangle on its own: corners [n, 4, 2] -> out [n, 5] = cx, cy, w, h in the corners' units, angle in radians; n == 0 does nothing
+extern "C" int ys_xyxyxyxy2xywhr(ys_ctx* ctx, const float* corners, int n, int on_device, float* out) {
+  YS_REQUIRE(ctx && n >= 0 && (n == 0 || (corners && out)), "ys_xyxyxyxy2xywhr: null argument or n = %d < 0", n);
+  if (n == 0) return YS_OK;
+  YS_CHECK_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  YsTimer timer(ctx, "xyxyxyxy2xywhr");
+  if (on_device) return ys_xyxyxyxy2xywhr_launch(st, corners, n, out);
+  DevBuf dc, dout;
+  YS_TRY(dc.alloc((size_t)n * 32)); YS_TRY(dout.alloc((size_t)n * 20));
+  YS_CHECK_HIP(hipMemcpyAsync(dc.p, corners, (size_t)n * 32, hipMemcpyHostToDevice, st));
+  YS_TRY(ys_xyxyxyxy2xywhr_launch(st, (const float*)dc.p, n, (float*)dout.p));
+  YS_CHECK_HIP(hipMemcpyAsync(out, dout.p, (size_t)n * 20, hipMemcpyDeviceToHost, st));
   YS_CHECK_HIP(hipStreamSynchronize(st));
   return YS_OK;
 }
@@ -1228,55 +1267,75 @@ extern "C" int ys_color_jitter(ys_ctx* ctx, const uint8_t* src, const ys_aug_jit
   return YS_OK;
 }
 
-extern "C" int ys_augment_letterbox_labels(ys_ctx* ctx, const ys_aug_src* srcs, int n_src, const int32_t* lab_off, const float* cls, const float* boxes,
-                                           const float* keypoints, int kpt_num, int kpt_dim, const ys_aug_item* items, int batch, int on_device,
-                                           int imgsz, int flags, int capacity, float* out_batch_idx, float* out_cls, float* out_bboxes,
-                                           float* out_keypoints, int32_t* out_count) {
-  YS_REQUIRE(ctx && srcs && lab_off && cls && boxes && items && out_batch_idx && out_cls && out_bboxes && out_count, "ys_augment_letterbox_labels: null argument");
-  YS_REQUIRE(batch > 0 && batch <= 65535 && capacity > 0 && n_src > 0, "ys_augment_letterbox_labels: bad shape batch=%d (1..65535) capacity=%d n_src=%d", batch,
-             capacity, n_src);
-  YS_REQUIRE(imgsz >= 2 && imgsz % 2 == 0 && imgsz <= 16384, "ys_augment_letterbox_labels: imgsz %d must be even and in [2, 16384]", imgsz);
-  YS_REQUIRE((keypoints != nullptr) == (out_keypoints != nullptr), "ys_augment_letterbox_labels: keypoints and out_keypoints go together");
+namespace {
+// ys_augment_letterbox_labels (corners == NULL) and ys_augment_letterbox_labels_obb, like aug_labels_impl
+int aug_letterbox_labels_impl(const char* fn, ys_ctx* ctx, const ys_aug_src* srcs, int n_src, const int32_t* lab_off, const float* cls, const float* boxes,
+                              const float* keypoints, int kpt_num, int kpt_dim, const float* corners, int obb, const ys_aug_item* items, int batch,
+                              int on_device, int imgsz, int flags, int capacity, float* out_batch_idx, float* out_cls, float* out_bboxes, float* out_keypoints,
+                              int32_t* out_count) {
+  YS_REQUIRE(ctx && srcs && lab_off && cls && boxes && items && out_batch_idx && out_cls && out_bboxes && out_count && (!obb || corners), "%s: null argument", fn);
+  YS_REQUIRE(batch > 0 && batch <= 65535 && capacity > 0 && n_src > 0, "%s: bad shape batch=%d (1..65535) capacity=%d n_src=%d", fn, batch, capacity, n_src);
+  YS_REQUIRE(imgsz >= 2 && imgsz % 2 == 0 && imgsz <= 16384, "%s: imgsz %d must be even and in [2, 16384]", fn, imgsz);
+  YS_REQUIRE((keypoints != nullptr) == (out_keypoints != nullptr), "%s: keypoints and out_keypoints go together", fn);
   if (keypoints) {
-    YS_REQUIRE(kpt_dim == 3, "ys_augment_letterbox_labels: kpt_dim %d: only (x, y, visibility) keypoints are supported", kpt_dim);
-    YS_REQUIRE(kpt_num > 0, "ys_augment_letterbox_labels: kpt_num %d", kpt_num);
+    YS_REQUIRE(kpt_dim == 3, "%s: kpt_dim %d: only (x, y, visibility) keypoints are supported", fn, kpt_dim);
+    YS_REQUIRE(kpt_num > 0, "%s: kpt_num %d", fn, kpt_num);
   }
-  YS_REQUIRE((flags & ~(YS_AUG_SORT_FLIPPED | YS_AUG_FLIP_KEEP_SIZE)) == 0, "ys_augment_letterbox_labels: unknown flags 0x%x", flags);
+  if (obb) YS_REQUIRE(flags == 0, "%s: flags 0x%x: the box-flip switches have nothing to act on, flags must be 0", fn, flags);
+  else YS_REQUIRE((flags & ~(YS_AUG_SORT_FLIPPED | YS_AUG_FLIP_KEEP_SIZE)) == 0, "%s: unknown flags 0x%x", fn, flags);
   const int K = keypoints ? kpt_num : 0;
+  const size_t xf = obb ? 8 : (size_t)K * 3, bw = obb ? 5 : 4;
+  const float* extra = obb ? corners : keypoints;
   YS_CHECK_HIP(hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
   YS_TRY(aug_reserve_ws(ctx, batch));
   YsTimer timer(ctx, "augment_letterbox_labels");
   if (on_device)
-    return ys_aug_letterbox_labels_launch(st, srcs, n_src, lab_off, cls, boxes, keypoints, K, items, batch, imgsz, flags, capacity, ctx->aug_ws, out_batch_idx,
-                                          out_cls, out_bboxes, out_keypoints, out_count);
-  YS_TRY(aug_check_letterbox_items("ys_augment_letterbox_labels", items, batch, srcs, n_src));
+    return ys_aug_letterbox_labels_launch(st, srcs, n_src, lab_off, cls, boxes, extra, K, items, batch, imgsz, flags, capacity, ctx->aug_ws, out_batch_idx,
+                                          out_cls, out_bboxes, out_keypoints, out_count, obb);
+  YS_TRY(aug_check_letterbox_items(fn, items, batch, srcs, n_src));
   for (int k = 0; k < n_src; k++)
-    YS_REQUIRE(lab_off[k] >= 0 && lab_off[k + 1] >= lab_off[k], "ys_augment_letterbox_labels: lab_off is not non-decreasing at source %d", k);
+    YS_REQUIRE(lab_off[k] >= 0 && lab_off[k + 1] >= lab_off[k], "%s: lab_off is not non-decreasing at source %d", fn, k);
   long total = 0;
   for (int b = 0; b < batch; b++) total += lab_off[items[b].src[0] + 1] - lab_off[items[b].src[0]];
-  YS_REQUIRE(total <= capacity, "ys_augment_letterbox_labels: the batch carries %ld labels, capacity is %d", total, capacity);
+  YS_REQUIRE(total <= capacity, "%s: the batch carries %ld labels, capacity is %d", fn, total, capacity);
   const size_t cap = (size_t)capacity, n_lab = (size_t)lab_off[n_src];
   DevBuf ds, dl, dc, db, dk, di, obi, ocl, obx, okp, ocn;
   YS_TRY(ds.alloc((size_t)n_src * sizeof(ys_aug_src))); YS_TRY(dl.alloc((size_t)(n_src + 1) * 4)); YS_TRY(dc.alloc(n_lab * 4)); YS_TRY(db.alloc(n_lab * 16));
-  YS_TRY(dk.alloc(n_lab * K * 12)); YS_TRY(di.alloc((size_t)batch * sizeof(ys_aug_item)));
-  YS_TRY(obi.alloc(cap * 4)); YS_TRY(ocl.alloc(cap * 4)); YS_TRY(obx.alloc(cap * 16)); YS_TRY(okp.alloc(cap * K * 12)); YS_TRY(ocn.alloc(4));
+  YS_TRY(dk.alloc(n_lab * xf * 4)); YS_TRY(di.alloc((size_t)batch * sizeof(ys_aug_item)));
+  YS_TRY(obi.alloc(cap * 4)); YS_TRY(ocl.alloc(cap * 4)); YS_TRY(obx.alloc(cap * bw * 4)); YS_TRY(okp.alloc(cap * K * 12)); YS_TRY(ocn.alloc(4));
   YS_CHECK_HIP(hipMemcpyAsync(ds.p, srcs, (size_t)n_src * sizeof(ys_aug_src), hipMemcpyHostToDevice, st));
   YS_CHECK_HIP(hipMemcpyAsync(dl.p, lab_off, (size_t)(n_src + 1) * 4, hipMemcpyHostToDevice, st));
   if (n_lab) {
     YS_CHECK_HIP(hipMemcpyAsync(dc.p, cls, n_lab * 4, hipMemcpyHostToDevice, st));
     YS_CHECK_HIP(hipMemcpyAsync(db.p, boxes, n_lab * 16, hipMemcpyHostToDevice, st));
-    if (K) YS_CHECK_HIP(hipMemcpyAsync(dk.p, keypoints, n_lab * K * 12, hipMemcpyHostToDevice, st));
+    if (xf) YS_CHECK_HIP(hipMemcpyAsync(dk.p, extra, n_lab * xf * 4, hipMemcpyHostToDevice, st));
   }
   YS_CHECK_HIP(hipMemcpyAsync(di.p, items, (size_t)batch * sizeof(ys_aug_item), hipMemcpyHostToDevice, st));
   YS_TRY(ys_aug_letterbox_labels_launch(st, (const ys_aug_src*)ds.p, n_src, (const int*)dl.p, (const float*)dc.p, (const float*)db.p,
-                                        K ? (const float*)dk.p : nullptr, K, (const ys_aug_item*)di.p, batch, imgsz, flags, capacity, ctx->aug_ws, (float*)obi.p,
-                                        (float*)ocl.p, (float*)obx.p, K ? (float*)okp.p : nullptr, (int*)ocn.p));
+                                        xf ? (const float*)dk.p : nullptr, K, (const ys_aug_item*)di.p, batch, imgsz, flags, capacity, ctx->aug_ws, (float*)obi.p,
+                                        (float*)ocl.p, (float*)obx.p, K ? (float*)okp.p : nullptr, (int*)ocn.p, obb));
   YS_CHECK_HIP(hipMemcpyAsync(out_batch_idx, obi.p, cap * 4, hipMemcpyDeviceToHost, st));
   YS_CHECK_HIP(hipMemcpyAsync(out_cls, ocl.p, cap * 4, hipMemcpyDeviceToHost, st));
-  YS_CHECK_HIP(hipMemcpyAsync(out_bboxes, obx.p, cap * 16, hipMemcpyDeviceToHost, st));
+  YS_CHECK_HIP(hipMemcpyAsync(out_bboxes, obx.p, cap * bw * 4, hipMemcpyDeviceToHost, st));
   if (K) YS_CHECK_HIP(hipMemcpyAsync(out_keypoints, okp.p, cap * K * 12, hipMemcpyDeviceToHost, st));
   YS_CHECK_HIP(hipMemcpyAsync(out_count, ocn.p, 4, hipMemcpyDeviceToHost, st));
   YS_CHECK_HIP(hipStreamSynchronize(st));
   return YS_OK;
+}
+}  // namespace
+
+extern "C" int ys_augment_letterbox_labels(ys_ctx* ctx, const ys_aug_src* srcs, int n_src, const int32_t* lab_off, const float* cls, const float* boxes,
+                                           const float* keypoints, int kpt_num, int kpt_dim, const ys_aug_item* items, int batch, int on_device,
+                                           int imgsz, int flags, int capacity, float* out_batch_idx, float* out_cls, float* out_bboxes,
+                                           float* out_keypoints, int32_t* out_count) {
+  return aug_letterbox_labels_impl("ys_augment_letterbox_labels", ctx, srcs, n_src, lab_off, cls, boxes, keypoints, kpt_num, kpt_dim, nullptr, 0, items, batch,
+                                   on_device, imgsz, flags, capacity, out_batch_idx, out_cls, out_bboxes, out_keypoints, out_count);
+}
+
+extern "C" int ys_augment_letterbox_labels_obb(ys_ctx* ctx, const ys_aug_src* srcs, int n_src, const int32_t* lab_off, const float* cls, const float* boxes,
+                                               const float* corners, const ys_aug_item* items, int batch, int on_device, int imgsz, int flags, int capacity,
+                                               float* out_batch_idx, float* out_cls, float* out_bboxes, int32_t* out_count) {
+  return aug_letterbox_labels_impl("ys_augment_letterbox_labels_obb", ctx, srcs, n_src, lab_off, cls, boxes, nullptr, 0, 3, corners, 1, items, batch, on_device,
+                                   imgsz, flags, capacity, out_batch_idx, out_cls, out_bboxes, nullptr, out_count);
 }

@@ -438,7 +438,10 @@ int ys_aug_mosaic_launch(hipStream_t st, const unsigned char* arena, const ys_au
                          int r, int perspective, const ys_aug_jitter* jitter, void* ws, float* images, float* masks);
 int ys_aug_labels_launch(hipStream_t st, const ys_aug_src* srcs, int n_src, const int* lab_off, const float* cls, const float* boxes,
                          const float* kpts, int K, const ys_aug_item* items, int B, int s, int perspective, int flags, int capacity, void* ws,
-                         float* o_bidx, float* o_cls, float* o_box, float* o_kpt, int* o_count);
+                         float* o_bidx, float* o_cls, float* o_box, float* o_kpt, int* o_count, int obb = 0);
+// OBB corner labels: obb != 0 in the two label launches = kpts holds corners [n][4][2], o_box has 5 columns (cx, cy, w, h normalised, angle), o_kpt NULL;
+// the rectangle on its own: corners [n][4][2] -> out [n][5] in the corners' units and radians
+int ys_xyxyxyxy2xywhr_launch(hipStream_t st, const float* corners, int n, float* out);
 // the LetterBox (close-mosaic) branch: LetterBox + flips + Normalize + collate of src[0] of an item (Data/Augment.cs:698-778, 860-966); the labels launch
 // uses the counts | offsets part of the same workspace
 int ys_aug_letterbox_src_host(const ys_aug_item* it, const ys_aug_src* srcs, int n_src);
@@ -451,4 +454,4 @@ int ys_color_jitter_launch(hipStream_t st, const unsigned char* src, const ys_au
                            void* dst, int dst_is_float);
 int ys_aug_letterbox_labels_launch(hipStream_t st, const ys_aug_src* srcs, int n_src, const int* lab_off, const float* cls, const float* boxes,
                                    const float* kpts, int K, const ys_aug_item* items, int B, int s, int flags, int capacity, void* ws, float* o_bidx,
-                                   float* o_cls, float* o_box, float* o_kpt, int* o_count);
+                                   float* o_cls, float* o_box, float* o_kpt, int* o_count, int obb = 0);

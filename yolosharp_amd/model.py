@@ -608,6 +608,11 @@ class AMPWrapper:
         `capacity` rows (those behind the batch's count carry batch_idx -1 and are skipped)."""
         m = self.model
         assert batch.imgsz == m.height == m.width, (batch.imgsz, m.height, m.width)
+        if m.TASK not in (0, 1, 2, 3):
+            raise ValueError("TrainStepDevice: the device augmenter produces Detect, Segment, OBB and Pose batches")
+        box_dim = getattr(batch, "box_dim", 4)
+        if box_dim != (5 if m.TASK == 2 else 4):        # an OBB criterion reads rows of 5 (cx, cy, w, h, angle), every other one rows of 4
+            raise ValueError("TrainStepDevice: a batch with %d-column boxes for a model of task %d" % (box_dim, m.TASK))
         m.train()
         m.reserve_labels(batch.max_per_image)
         m.forward_device(batch.images, batch.batch)
@@ -616,8 +621,6 @@ class AMPWrapper:
             args.append(batch.masks)
         elif m.TASK == 3:
             args.append(batch.keypoints)
-        elif m.TASK != 0:
-            raise ValueError("TrainStepDevice: the device augmenter produces Detect, Segment and Pose batches")
         loss_func.forward_device(*args)
         loss, items = loss_func.read()
         self.Step()
