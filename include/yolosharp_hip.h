@@ -726,6 +726,43 @@ YS_API int ys_upsample2x(ys_ctx* ctx, int dtype, int backward, const float* src,
 YS_API int ys_copy_view(ys_ctx* ctx, int dtype, const float* src, int rows, int C, int s_ldc, int s_coff, int d_ldc, int d_coff, int accumulate,
                         float* dst, int32_t* view_intact);
 
+/* ---- fp8 convolution path (csrc/f8.hip and the quantising passes of csrc/batchnorm.hip), one stateless call per kernel (unit parity against exact
+ * references: OCP e4m3fn / e5m2, round to nearest even, saturating).  Sentinels and guards as above.
+ *
+ * One quantiser launch on x [rows][C] fp32 (ROW-major), stored as bf16 at channel coff of a [rows][coff + C + pad] buffer:
+ *   kind 0 / 1  f8_quant_view_kernel<e4m3 / e5m2>: q8 [rows][C] = fp8(bf16(x) * qscale), records amax(|bf16(x)|)           (C % 16 == 0)
+ *   kind 2      f8_view_amax_kernel alone: records amax, q8 unused (may be NULL)                                              (C % 8 == 0)
+ *   kind 3      f8_quant_weights_kernel on the flat rows * C elements (any count; coff = pad = 0): qscale is amax_w, the multiplier 448 / amax_w (1 when
+ *               amax_w is 0); records nothing
+ * *amax = the maximum over the ys_f8_amax_ways() slots of the tensor; slots (may be NULL) receives the slots themselves -- one per workgroup index modulo the way
+ * count, a slot no workgroup wrote stays 0. */
+YS_API int ys_f8_quant(ys_ctx* ctx, int kind, const float* x, int rows, int C, int coff, int pad, float qscale, uint8_t* q8, float* amax, float* slots,
+                       int32_t* view_intact);
+YS_API int ys_f8_amax_ways(void);
+/* The scale bookkeeping of a step: ys_f8_weight_amax_launch over the layers (offset, count) of the flat fp32 parameter array, then ys_f8_scales_launch over the
+ * convolutions (conv_layer[c] = index of its layer).  amax_x / amax_dy [n_convs][ways] in / out (float values; cleared by the call), scales [n_convs][4] =
+ * s_x, 1 / (s_x s_w), s_g, 1 / (s_g s_w) in / out (a convolution without a recorded maximum keeps s_x / s_g), amax_w [n_layers] out. */
+YS_API int ys_f8_scales(ys_ctx* ctx, const float* params, int64_t n_params, const int64_t* layer_off, const int64_t* layer_count, int n_layers,
+                        const int32_t* conv_layer, int n_convs, float* amax_x, float* amax_dy, float* scales, float* amax_w);
+/* ys_bn_act_apply_q8_launch alone (bf16 storage) with the caller's coefficients: z = act(y scale + shift) (+ res) into its padded view, q8 [rows][C] =
+ * e4m3(z qscale) of the STORED z, *amax = max |z|.  y, res, z channel-major [C][rows] as in ys_bn_train_fwd; q8 row-major as on the device. */
+YS_API int ys_bn_apply_q8_fwd(ys_ctx* ctx, int act_silu, const float* y, int rows, int C, const float* scale, const float* shift, const float* res, int res_pad,
+                              int res_coff, int z_pad, int z_coff, int res_shares_z, float qscale, float* z, uint8_t* q8, float* amax, int32_t* view_intact);
+/* ys_bn_bwd_apply_q8_launch alone: coef [4][C] = scale, shift, k2, k3; dy = scale du - k2 - y k3 (dense), q8 = e5m2(dy qscale) of the stored dy, *amax = max |dy|;
+ * rg (optional, in / out, padded view) receives rg + dz. */
+YS_API int ys_bn_apply_q8_bwd(ys_ctx* ctx, int act_silu, const float* dz, const float* y, int rows, int C, const float* coef, int dz_pad, int dz_coff, float* rg,
+                              int rg_pad, int rg_coff, float qscale, float* dy, uint8_t* q8, float* amax, int32_t* view_intact);
+/* The fp8 branch of ys_conv_bn_act_fwd_ex (dtype YS_FP8, stat_mode 0; Cin % 32 == 0) with a DELAYED activation scale: prev_amax > 0 replaces the input's own
+ * amax in s_x = 0.5 * 448 / amax (0 = current scaling, as ys_conv_bn_act_fwd).  The launch records amax(|bf16(x)|) through ConvArgs::amax as a model's step
+ * does: *amax = the maximum over the ways; scales [4] = s_x, 1 / (s_x s_w), s_g, 1 / (s_g s_w) as used. */
+YS_API int ys_conv_f8_fwd(ys_ctx* ctx, const float* x_nchw, int B, int Cin, int H, int W, const float* w_oihw, int Cout, int k, int stride,
+                          const float* bn_gamma, const float* bn_beta, float* bn_mean, float* bn_var, const float* bias, int act_silu, int training,
+                          float prev_amax, float* y_nchw, float* y_raw, float* coef, int32_t* stat_rows, float* scales, float* amax);
+/* The fp8 input gradient of ys_conv_bwd (dy -> e5m2, weights -> e4m3; Cout % 32 == 0) with a delayed gradient scale s_g = 8192 / prev_amax (0 = current);
+ * *amax = the recorded amax(|bf16(dy)|). */
+YS_API int ys_conv_f8_dgrad(ys_ctx* ctx, int B, int Cin, int H, int W, const float* w_oihw, int Cout, int k, int stride, const float* dy_nchw,
+                            float prev_amax, float* dx_nchw, float* scales, float* amax);
+
 /* ---- per-block entry points: a TorchSharp-free body for the reference's block modules, one stateful handle per
  *      module instance (SURVEY 8b "ys_c2f_fwd/bwd, ys_c3k2_fwd/bwd, ys_sppf_fwd/bwd, ys_proto_fwd/bwd").  The handle IS a
  *      ys_model: ys_model_num_tensors / tensor_info / set_tensor / get_tensor / get_grad / init_weights / set_training /

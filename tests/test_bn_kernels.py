@@ -49,6 +49,7 @@ The same on the MI355X (gfx950 build):
   backward  reduction rows 0.125 / 0.142    finalize 0.125 / 0.205   FinSrc finalize 0.125        apply fp32 0.111 / 0.125   apply bf16 0.995   end to end 0.995
   column sums 0.125   upsample2x backward 0.996   copy_view accumulate 0.996   convolution: accumulators 0.154, statistics rows 0.131, apply 0.993
 (bf16 ratios near 1 are the store rounding itself: half an ulp at the bottom of a binade is 2^-8 |ref|; 0.125 is a result equal to the float32 evaluation.)
+The statistics epilogue of the fp8 convolution kernels (test_conv_epilogue_statistics_fp8, statistics rows only): rows 0.125, apply 0.985 on both builds.
 """
 import numpy as np
 import pytest
@@ -753,6 +754,24 @@ def test_conv_epilogue_statistics(backend, engine, dtype, case):
     """ys_conv_bn_act_fwd_ex on the patch, 1x1, streamed-weight, blocked-GEMM and halo kernels: the coefficients of both statistics paths against the float64
     statistics of the convolution output the entry returns (the accumulator path with its P 2^-21 terms, P = the returned row count), z against the returned
     coefficients, and two consecutive calls bit-identical (accumulators that are not cleared between calls add up)."""
+    conv_epilogue_statistics(engine, dtype, case, (1, 0))
+
+
+# the fp8 kernels' statistics epilogue sums y = acc / (s_x s_w) AFTER that rescale (statistics of the raw accumulator would be off by the factor BatchNorm mostly
+# hides): one conv_p2_kernel<F8> and one conv_gemm_kernel<F8 = 1> shape of tests/test_fp8_kernels.py, statistics rows only (the mode the fp8 path keeps)
+F8_CONV_CASES = [((2, 96, 12, 12, 72, 3, 1), "p2f8"), ((1, 160, 9, 11, 80, 3, 2), "gemmf8")]
+
+
+@pytest.mark.parametrize("backend", BACKENDS)
+@pytest.mark.parametrize("case", F8_CONV_CASES, ids=lambda c: c[1])
+def test_conv_epilogue_statistics_fp8(backend, engine, case):
+    """test_conv_epilogue_statistics with dtype "fp8", at its bf16 bounds; the kernel asserted from the per-launch profile."""
+    (B, Cin, H, W, Cout, k, s), kern = case
+    _, labels = engine.conv_labels(lambda: conv_epilogue_statistics(engine, "fp8", case[0], (0,)))
+    assert len(labels) == 2 and all(l.startswith("%s k%d s%d div1 cin%d cout%d " % (kern, k * 11, s, Cin, Cout)) for l in labels), labels
+
+
+def conv_epilogue_statistics(engine, dtype, case, modes):
     B, Cin, H, W, Cout, k, s = case
     rng = np.random.default_rng(Cin + Cout)
     x = rng.standard_normal((B, Cin, H, W)).astype(f32)
@@ -760,7 +779,7 @@ def test_conv_epilogue_statistics(backend, engine, dtype, case):
     g, bt = rng.uniform(0.5, 1.5, Cout).astype(f32), (0.1 * rng.standard_normal(Cout)).astype(f32)
     rm0, rv0 = (0.1 * rng.standard_normal(Cout)).astype(f32), rng.uniform(0.5, 1.5, Cout).astype(f32)
     names = ("scale", "shift", "mean", "rstd")
-    for mode in (1, 0):
+    for mode in modes:
         runs = []
         for _ in range(2):
             bn = dict(weight=g, bias=bt, running_mean=rm0.copy(), running_var=rv0.copy())
@@ -769,6 +788,7 @@ def test_conv_epilogue_statistics(backend, engine, dtype, case):
             runs.append((z, ex["y_raw"], ex["coef"], bn["running_mean"], bn["running_var"]))
         assert all(np.array_equal(a, b) for a, b in zip(*runs)), "stat_mode %d: two consecutive calls differ" % mode
         z, y_raw, coef, rm, rv = runs[0]
+        store_dt = "bf16" if dtype == "fp8" else dtype       # the storage type: the fp8 path is held to the bf16 bounds
         y = np.ascontiguousarray(y_raw.transpose(1, 0, 2, 3).reshape(Cout, -1))
         n = y.shape[1]
         y64 = y.astype(f64)
@@ -779,12 +799,12 @@ def test_conv_epilogue_statistics(backend, engine, dtype, case):
         for o in range(2):
             q = coef_form(seq32(y)[o], seq32(y * y)[o], n, g, bt, rm0, rv0, f32)
             d = {kk: max(d[kk], d32_of(q[kk], r64[kk])) for kk in r64}
-        bad, path = [], "convolution accumulators" if mode == 1 else "convolution statistics rows"
+        bad, path = [], ("fp8 " if dtype == "fp8" else "") + ("convolution accumulators" if mode == 1 else "convolution statistics rows")
         for kk, got in zip(names + ("run_mean", "run_var"), list(coef) + [rm, rv]):
             violation(got, r64[kk], 8 * d[kk] + extra[kk], kk, path, bad)
         zt = np.ascontiguousarray(z.transpose(1, 0, 2, 3).reshape(Cout, -1))
         z64 = apply_form(y, coef[0], coef[1], None, 1, f64)
-        violation(zt, z64, tol(z64, d32_max([apply_form(y, coef[0], coef[1], None, 1, f32, fma) for fma in (False, True)], z64), dtype), "z", path + " apply", bad)
+        violation(zt, z64, tol(z64, d32_max([apply_form(y, coef[0], coef[1], None, 1, f32, fma) for fma in (False, True)], z64), store_dt), "z", path + " apply", bad)
         assert not bad, "stat_mode %d: %s" % (mode, "; ".join(bad))
 
 

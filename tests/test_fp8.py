@@ -50,13 +50,16 @@ def test_quantiser_known_values():
 
 CASES = [
     # B, Cin, H, W, Cout, k, s
-    (2, 64, 12, 12, 64, 3, 1),       # resident weights, two K-steps of 128 + tail (K = 576)
-    (1, 32, 20, 40, 48, 3, 1),       # multi-tile image, K = 288 (tail pieces), Cout not a multiple of 32
-    (2, 128, 9, 11, 128, 3, 2),      # stride 2, odd sizes
-    (1, 256, 6, 6, 80, 1, 1),        # 1x1, K = 256
-    (1, 320, 8, 8, 96, 3, 1),        # streamed weights (K = 2880 per row)
+    (2, 64, 12, 12, 64, 3, 1),       # conv_p2_kernel<F8>, resident weights, four K-steps of 128 + a half (K = 576); dgrad the same kernel
+    (1, 32, 20, 40, 48, 3, 1),       # the same kernel, multi-tile image, K = 288 (tail pieces), Cout not a multiple of 32
+    (2, 128, 9, 11, 128, 3, 2),      # the same kernel at stride 2, odd sizes; dgrad: four phase launches of it
+    (1, 256, 6, 6, 80, 1, 1),        # 1x1, K = 256: conv_gemm_kernel<F8 = 1>, 256x80 tile; dgrad (80 gradient channels, no multiple of 32): the bf16 patch kernel
+    (1, 320, 8, 8, 96, 3, 1),        # conv_gemm_kernel<F8 = 1> (Cin >= GEMM_MIN_CIN, Cout >= 64), K = 2880; dgrad: conv_p2_kernel<F8>, e5m2 input
     (1, 160, 10, 12, 256, 3, 1),     # blocked-GEMM fp8 kernel both ways (conv_gemm.hip): forward K = 1440, dgrad K = 2304 (e5m2 operand)
 ]
+# the kernel each case runs on, asserted from the per-launch profile (forward; dgrad per phase geometry)
+FWD_KERNEL = ["p2f8", "p2f8", "p2f8", "gemmf8", "gemmf8", "gemmf8"]
+DGRAD_KERNEL = [{"k33": "p2f8"}, None, {"k11": "p2f8", "k12": "p2f8", "k21": "p2f8", "k22": "p2f8"}, {"k11": "p2"}, {"k33": "p2f8"}, {"k33": "gemmf8"}]
 
 
 @pytest.mark.parametrize("backend", BACKENDS)
@@ -66,7 +69,9 @@ def test_conv_forward_fp8_matches_quantised_fp32(backend, engine, case):
     g = torch.Generator().manual_seed(100 + case)
     x = torch.randn(B, Cin, H, W, generator=g).numpy() * 1.7
     w = (torch.randn(Cout, Cin, k, k, generator=g) / (Cin * k * k) ** 0.5).numpy()
-    y = engine.conv_bn_act(x, w, k, s, bn=None, bias=np.zeros(Cout, np.float32), act=False, training=True, dtype="fp8")
+    from test_fp8_kernels import fwd_reference, geom, held, one_label
+    y, labels = engine.conv_labels(lambda: engine.conv_bn_act(x, w, k, s, bn=None, bias=np.zeros(Cout, np.float32), act=False, training=True, dtype="fp8"))
+    one_label(labels, FWD_KERNEL[case] + " " + geom(k, s, Cin, Cout))
     xb, wb = bf16(x), bf16(w)
     sx = np.float32(0.5) * np.float32(448.0) / np.abs(xb).max()
     sw = np.float32(448.0) / np.abs(w).max()
@@ -75,6 +80,9 @@ def test_conv_forward_fp8_matches_quantised_fp32(backend, engine, case):
     ref = (F.conv2d(torch.from_numpy(xq).double(), torch.from_numpy(wq).double(), None, stride=s, padding=k // 2) * float(deq)).float().numpy()
     scale = np.abs(ref).max()
     assert np.abs(y - ref).max() <= 6e-3 * scale, (np.abs(y - ref).max(), scale)        # bf16 rounding of the stored result (2^-9)
+    # ... and per element (tests/test_fp8_kernels.py): |y - ref| <= 2^-8 |ref| + (K + 2) ACC_ULP A
+    ref64, A, _, _, _ = fwd_reference(x, w, k, s)
+    held(y, ref64, A, k * k * Cin, "forward case %d" % case, "fp8 conv forward " + FWD_KERNEL[case])
     # and the quantisation itself is what separates it from the bf16 kernel: a few percent, not more
     plain = F.conv2d(torch.from_numpy(xb), torch.from_numpy(wb), None, stride=s, padding=k // 2).numpy()
     rel = np.linalg.norm(y - plain) / np.linalg.norm(plain)
@@ -87,6 +95,7 @@ def test_conv_dgrad_fp8_matches_quantised_fp32(backend, engine, case):
     """Input gradient on the fp8 kernel (dy -> e5m2, flipped / transposed weights -> e4m3; stride 2 as four phase convolutions);
     the weight gradient keeps the bf16 operands."""
     from yolosharp_amd import _lib
+    from test_fp8_kernels import dgrad_reference, dgrad_routes_ok, held
     B, Cin, H, W, Cout, k, s = CASES[case]
     g = torch.Generator().manual_seed(200 + case)
     x = bf16(torch.randn(B, Cin, H, W, generator=g).numpy())
@@ -95,15 +104,26 @@ def test_conv_dgrad_fp8_matches_quantised_fp32(backend, engine, case):
     dy = bf16(torch.randn(B, Cout, Ho, Wo, generator=g).numpy() * 1e-3)
     dx = np.zeros_like(x); dw = np.zeros_like(w)
     vp = lambda a: a.ctypes.data_as(C.c_void_p)
-    _lib.check(engine.lib, engine.lib.ys_conv_bwd(engine.ctx, 2, vp(x), B, Cin, H, W, vp(np.ascontiguousarray(w)), Cout, k, s, vp(dy), vp(dx), vp(dw)))
+    wc = np.ascontiguousarray(w)
+    _, labels = engine.conv_labels(lambda: _lib.check(engine.lib, engine.lib.ys_conv_bwd(engine.ctx, 2, vp(x), B, Cin, H, W, vp(wc), Cout, k, s, vp(dy), vp(dx), vp(dw))))
+    dgrad_routes_ok(labels, CASES[case], DGRAD_KERNEL[case])
     sg = np.float32(8192.0) / np.abs(dy).max()
     sw = np.float32(448.0) / np.abs(w).max()
     dyq, wq = q_e5m2(dy * sg), q_e4m3(bf16(w) * sw)
     xt = torch.zeros(B, Cin, H, W, dtype=torch.float64, requires_grad=True)
     F.conv2d(xt, torch.from_numpy(wq).double(), None, stride=s, padding=k // 2).backward(torch.from_numpy(dyq).double())
     ref = (xt.grad / float(sg * sw)).float().numpy()
-    if Cout % 32 == 0:
+    if DGRAD_KERNEL[case] == {"k11": "p2"}:
+        # Cout = 80 is no multiple of the fp8 kernels' 32-channel unit: the labels show the bf16 patch kernel, and dx is held to the bf16 bound against the
+        # bf16 reference, as tests/test_conv.py::test_conv_backward holds it
+        from bf16_ref import check_elem
+        xb = torch.zeros(B, Cin, H, W, requires_grad=True)
+        F.conv2d(xb, torch.from_numpy(bf16(w)), None, stride=s, padding=k // 2).backward(torch.from_numpy(dy))
+        check_elem(dx, xb.grad.numpy(), "bf16 dgrad of fp8 case %d" % case)
+    else:
         assert np.abs(dx - ref).max() <= 6e-3 * np.abs(ref).max(), (np.abs(dx - ref).max(), np.abs(ref).max())
+        ref64, A, _, _, _ = dgrad_reference((B, Cin, H, W), w, k, s, dy)
+        held(dx, ref64, A, (-(-k // s)) ** 2 * Cout, "dgrad case %d" % case, "fp8 conv dgrad " + "+".join(sorted(set(DGRAD_KERNEL[case].values()))))
     # weight gradient: bf16 operands, fp32 accumulation (unchanged by the mode)
     xt2 = torch.from_numpy(x).requires_grad_(False)
     wt = torch.from_numpy(bf16(w)).requires_grad_(True)

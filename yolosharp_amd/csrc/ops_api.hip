@@ -18,7 +18,8 @@ struct DevBuf {
 static int conv_bn_act_fwd_impl(ys_ctx* ctx, int dtype, const float* x_nchw, int B, int Cin, int H, int W,
                                 const float* w_oihw, int Cout, int k, int stride, const float* bn_gamma,
                                 const float* bn_beta, float* bn_mean, float* bn_var, const float* bias,
-                                int act_silu, int training, int stat_mode, float* y_nchw, float* y_raw, float* coef, int32_t* stat_rows) {
+                                int act_silu, int training, int stat_mode, float* y_nchw, float* y_raw, float* coef, int32_t* stat_rows,
+                                float prev_amax = 0.f, float* f8_scales = nullptr, float* f8_amax = nullptr) {
   YS_REQUIRE(ctx && x_nchw && w_oihw && y_nchw, "ys_conv_bn_act_fwd: null argument");
   YS_REQUIRE(dtype == YS_F32 || dtype == YS_BF16 || dtype == YS_FP8, "ys_conv_bn_act_fwd: bad dtype %d", dtype);
   YS_REQUIRE((k == 1 || k == 3) && (stride == 1 || stride == 2), "ys_conv_bn_act_fwd: k=%d stride=%d unsupported", k, stride);
@@ -93,11 +94,14 @@ static int conv_bn_act_fwd_impl(ys_ctx* ctx, int dtype, const float* x_nchw, int
     YS_CHECK_HIP(hipMemcpyAsync(dl.p, &hl, sizeof hl, hipMemcpyHostToDevice, st));
     YS_CHECK_HIP(hipMemcpyAsync(dc.p, &hc, sizeof hc, hipMemcpyHostToDevice, st));
     YS_TRY(ys_f8_weight_amax_launch(st, (const float*)dwm.p, (const F8Layer*)dl.p, 1, qf));
-    YS_TRY(ys_f8_view_amax_launch(st, dxn.p, (long)B * H * W, cpad, cpad, 0, (unsigned*)(qf + 16)));
+    // delayed scaling (ys_conv_f8_fwd): the caller's amax of an EARLIER step stands in the slot instead of this input's own
+    if (prev_amax > 0.f) YS_CHECK_HIP(hipMemcpyAsync(qf + 16, &prev_amax, 4, hipMemcpyHostToDevice, st));
+    else YS_TRY(ys_f8_view_amax_launch(st, dxn.p, (long)B * H * W, cpad, cpad, 0, (unsigned*)(qf + 16)));
     YS_TRY(ys_f8_scales_launch(st, (const F8Conv*)dc.p, 1, qf, (unsigned*)(qf + 16), (unsigned*)(qf + 96), qf + 200));
     YS_TRY(ys_f8_quant_weights_launch(st, dwf.p, (long)Cout * taps * cpad, qf, dw8.p));
     YS_CHECK_HIP(hipStreamSynchronize(st));     // hl / hc / dl / dc are temporaries of this scope
     a.f8 = 1; a.w8 = dw8.p; a.qscale = qf + 200; a.deq = qf + 201; a.q8 = dq8.p;
+    if (f8_amax) a.amax = (unsigned*)(qf + 16);   // the slots the scales launch just cleared: the launch records amax(|input|) as a model's step does
   }
   a.B = B; a.Hin = H; a.Win = W; a.Cin = cpad; a.Hout = Ho; a.Wout = Wo; a.Cout = Cout; a.KH = k; a.KW = k;
   a.SA = stride; a.DIVS = 0; a.DIVM = 0; a.PAD = pad;
@@ -150,9 +154,23 @@ static int conv_bn_act_fwd_impl(ys_ctx* ctx, int dtype, const float* x_nchw, int
   }
   YS_TRY(ys_unpack_nchw_launch(st, dtype, result, cout_ld, 0, B, Cout, (long)Ho * Wo, (float*)dout.p));
   YS_CHECK_HIP(hipMemcpyAsync(y_nchw, dout.p, (size_t)M * Cout * 4, hipMemcpyDeviceToHost, st));
+  if (a.f8 && f8_scales) YS_CHECK_HIP(hipMemcpyAsync(f8_scales, (const float*)dq.p + 200, 16, hipMemcpyDeviceToHost, st));
+  float ways[YS_AMAX_WAYS] = {};
+  if (a.f8 && f8_amax) YS_CHECK_HIP(hipMemcpyAsync(ways, (const float*)dq.p + 16, sizeof ways, hipMemcpyDeviceToHost, st));
   YS_CHECK_HIP(hipStreamSynchronize(st));
   YS_CHECK_HIP(hipGetLastError());
+  if (f8_amax) { float m = 0.f; for (float v : ways) m = v > m ? v : m; *f8_amax = m; }
   return YS_OK;
+}
+
+extern "C" int ys_conv_f8_fwd(ys_ctx* ctx, const float* x_nchw, int B, int Cin, int H, int W, const float* w_oihw, int Cout, int k, int stride,
+                              const float* bn_gamma, const float* bn_beta, float* bn_mean, float* bn_var, const float* bias, int act_silu, int training,
+                              float prev_amax, float* y_nchw, float* y_raw, float* coef, int32_t* stat_rows, float* scales, float* amax) {
+  YS_REQUIRE(scales && amax, "ys_conv_f8_fwd: null argument");
+  YS_REQUIRE(Cin >= 32 && Cin % 32 == 0, "ys_conv_f8_fwd: Cin=%d (the fp8 kernels take multiples of 32 input channels)", Cin);
+  YS_REQUIRE(prev_amax >= 0.f && prev_amax < __builtin_inff(), "ys_conv_f8_fwd: prev_amax must be finite and >= 0");
+  return conv_bn_act_fwd_impl(ctx, YS_FP8, x_nchw, B, Cin, H, W, w_oihw, Cout, k, stride, bn_gamma, bn_beta, bn_mean, bn_var, bias, act_silu, training, 0,
+                              y_nchw, y_raw, coef, stat_rows, prev_amax, scales, amax);
 }
 
 extern "C" int ys_conv_bn_act_fwd(ys_ctx* ctx, int dtype, const float* x_nchw, int B, int Cin, int H, int W,
@@ -173,10 +191,11 @@ extern "C" int ys_conv_bn_act_fwd_ex(ys_ctx* ctx, int dtype, const float* x_nchw
 
 // Gradients of y = conv2d(x, w, stride, padding=k/2) given dy (autograd of torch.nn.Conv2d, reached from
 // Amp.cs:348,370): dx [B,Cin,H,W] (may be null) and dw [Cout,Cin,k,k], all fp32 NCHW/OIHW host arrays.
-extern "C" int ys_conv_bwd(ys_ctx* ctx, int dtype, const float* x_nchw, int B, int Cin, int H, int W,
-                           const float* w_oihw, int Cout, int k, int stride, const float* dy_nchw,
-                           float* dx_nchw, float* dw_oihw) {
-  YS_REQUIRE(ctx && x_nchw && w_oihw && dy_nchw && dw_oihw, "ys_conv_bwd: null argument");
+// dw_oihw == nullptr (ys_conv_f8_dgrad): the input gradient alone, x_nchw unused
+static int conv_bwd_impl(ys_ctx* ctx, int dtype, const float* x_nchw, int B, int Cin, int H, int W,
+                         const float* w_oihw, int Cout, int k, int stride, const float* dy_nchw,
+                         float* dx_nchw, float* dw_oihw, float prev_amax, float* f8_scales, float* f8_amax) {
+  YS_REQUIRE(ctx && w_oihw && dy_nchw && (dw_oihw ? x_nchw != nullptr : dx_nchw != nullptr), "ys_conv_bwd: null argument");
   YS_REQUIRE(dtype == YS_F32 || dtype == YS_BF16 || dtype == YS_FP8, "ys_conv_bwd: bad dtype %d", dtype);
   const bool want_f8 = dtype == YS_FP8;           // dgrad on the fp8 kernel (dy -> e5m2, weights -> e4m3, current scales); wgrad stays bf16
   if (want_f8) dtype = YS_BF16;
@@ -206,23 +225,26 @@ extern "C" int ys_conv_bwd(ys_ctx* ctx, int dtype, const float* x_nchw, int B, i
   YS_TRY(dgw.alloc(wint.size() * 4));
   YS_CHECK_HIP(hipMemsetAsync(dgx.p, 0, (size_t)B * H * W * cpad * es, st));
   YS_CHECK_HIP(hipMemsetAsync(dgw.p, 0, wint.size() * 4, st));
-  YS_CHECK_HIP(hipMemcpyAsync(dx.p, x_nchw, (size_t)B * Cin * H * W * 4, hipMemcpyHostToDevice, st));
+  if (dw_oihw) YS_CHECK_HIP(hipMemcpyAsync(dx.p, x_nchw, (size_t)B * Cin * H * W * 4, hipMemcpyHostToDevice, st));
   YS_CHECK_HIP(hipMemcpyAsync(ddy.p, dy_nchw, (size_t)M * Cout * 4, hipMemcpyHostToDevice, st));
   YS_CHECK_HIP(hipMemcpyAsync(dwm.p, wint.data(), wint.size() * 4, hipMemcpyHostToDevice, st));
-  YS_TRY(ys_pack_input_launch(st, dtype, (const float*)dx.p, B, Cin, H, W, cpad, dxn.p));
+  if (dw_oihw) YS_TRY(ys_pack_input_launch(st, dtype, (const float*)dx.p, B, Cin, H, W, cpad, dxn.p));
   YS_TRY(ys_pack_input_launch(st, dtype, (const float*)ddy.p, B, Cout, Ho, Wo, copad, ddyn.p));
   YS_TRY(ys_weight_prep_launch(st, dtype, (const float*)dwm.p, Cout, taps, Cin, cpad, copad, dwf.p, dwd.p, ys_conv_dgrad_uses_phases(dtype, k, stride) ? 1 : 0));
-  WgradArgs wa{};
-  wa.x = dxn.p; wa.dy = ddyn.p;
-  wa.B = B; wa.Hin = H; wa.Win = W; wa.Cin = cpad; wa.Hout = Ho; wa.Wout = Wo; wa.Cout = Cout; wa.KH = wa.KW = k;
-  wa.stride = stride; wa.pad = pad; wa.in_ldc = cpad; wa.in_coff = 0; wa.in_bstride = (long)H * W;
-  wa.dy_ldc = copad; wa.dy_coff = 0; wa.dy_bstride = (long)Ho * Wo; wa.M = (int)M;
-  const int splits = ys_wgrad_splits(wa, dtype);
-  YS_TRY(dpart.alloc((size_t)splits * Cout * taps * cpad * 4));
-  wa.partial = (float*)dpart.p;
-  YS_TRY(ys_wgrad_launch(st, dtype, wa, splits, Cin, (float*)dgw.p));
-  std::vector<float> gw(wint.size());
-  YS_CHECK_HIP(hipMemcpyAsync(gw.data(), dgw.p, gw.size() * 4, hipMemcpyDeviceToHost, st));
+  std::vector<float> gw(dw_oihw ? wint.size() : 0);
+  if (dw_oihw) {
+    WgradArgs wa{};
+    wa.x = dxn.p; wa.dy = ddyn.p;
+    wa.B = B; wa.Hin = H; wa.Win = W; wa.Cin = cpad; wa.Hout = Ho; wa.Wout = Wo; wa.Cout = Cout; wa.KH = wa.KW = k;
+    wa.stride = stride; wa.pad = pad; wa.in_ldc = cpad; wa.in_coff = 0; wa.in_bstride = (long)H * W;
+    wa.dy_ldc = copad; wa.dy_coff = 0; wa.dy_bstride = (long)Ho * Wo; wa.M = (int)M;
+    const int splits = ys_wgrad_splits(wa, dtype);
+    YS_TRY(dpart.alloc((size_t)splits * Cout * taps * cpad * 4));
+    wa.partial = (float*)dpart.p;
+    YS_TRY(ys_wgrad_launch(st, dtype, wa, splits, Cin, (float*)dgw.p));
+    YS_CHECK_HIP(hipMemcpyAsync(gw.data(), dgw.p, gw.size() * 4, hipMemcpyDeviceToHost, st));
+  }
+  float ways[YS_AMAX_WAYS] = {};
   if (dx_nchw) {
     ConvArgs a{};
     a.x = ddyn.p; a.w = dwd.p; a.y = dgx.p;
@@ -240,11 +262,13 @@ extern "C" int ys_conv_bwd(ys_ctx* ctx, int dtype, const float* x_nchw, int B, i
       YS_CHECK_HIP(hipMemcpyAsync(dl.p, &hl, sizeof hl, hipMemcpyHostToDevice, st));
       YS_CHECK_HIP(hipMemcpyAsync(dc.p, &hc, sizeof hc, hipMemcpyHostToDevice, st));
       YS_TRY(ys_f8_weight_amax_launch(st, (const float*)dwm.p, (const F8Layer*)dl.p, 1, qf));
-      YS_TRY(ys_f8_view_amax_launch(st, ddyn.p, M, copad, copad, 0, (unsigned*)(qf + 96)));
+      if (prev_amax > 0.f) YS_CHECK_HIP(hipMemcpyAsync(qf + 96, &prev_amax, 4, hipMemcpyHostToDevice, st));     // delayed scaling: see conv_bn_act_fwd_impl
+      else YS_TRY(ys_f8_view_amax_launch(st, ddyn.p, M, copad, copad, 0, (unsigned*)(qf + 96)));
       YS_TRY(ys_f8_scales_launch(st, (const F8Conv*)dc.p, 1, qf, (unsigned*)(qf + 16), (unsigned*)(qf + 96), qf + 200));
       YS_TRY(ys_f8_quant_weights_launch(st, dwd.p, (long)Cin * taps * copad, qf, dw8.p));
       YS_CHECK_HIP(hipStreamSynchronize(st));
       a.f8 = 2; a.w8 = dw8.p; a.qscale = qf + 202; a.deq = qf + 203; a.q8 = dq8.p;
+      if (f8_amax) a.amax = (unsigned*)(qf + 96);
     }
     a.B = B; a.Hin = Ho; a.Win = Wo; a.Cin = copad; a.Hout = H; a.Wout = W; a.Cout = Cin; a.KH = a.KW = k;
     a.SA = 1; a.DIVS = stride == 2 ? 1 : 0; a.DIVM = stride - 1; a.PAD = k - 1 - pad;
@@ -253,13 +277,33 @@ extern "C" int ys_conv_bwd(ys_ctx* ctx, int dtype, const float* x_nchw, int B, i
     YS_TRY(ys_conv_launch(st, dtype, a));
     YS_TRY(ys_unpack_nchw_launch(st, dtype, dgx.p, cpad, 0, B, Cin, (long)H * W, (float*)dgxo.p));
     YS_CHECK_HIP(hipMemcpyAsync(dx_nchw, dgxo.p, (size_t)B * Cin * H * W * 4, hipMemcpyDeviceToHost, st));
+    if (a.f8 && f8_scales) YS_CHECK_HIP(hipMemcpyAsync(f8_scales, (const float*)dq.p + 200, 16, hipMemcpyDeviceToHost, st));
+    if (a.f8 && f8_amax) YS_CHECK_HIP(hipMemcpyAsync(ways, (const float*)dq.p + 96, sizeof ways, hipMemcpyDeviceToHost, st));
+    YS_CHECK_HIP(hipStreamSynchronize(st));     // dw8 / dq / dq8 are temporaries of this scope
   }
   YS_CHECK_HIP(hipStreamSynchronize(st));
-  for (int co = 0; co < Cout; co++)
-    for (int ci = 0; ci < Cin; ci++)
-      for (int t = 0; t < taps; t++) dw_oihw[((size_t)co * Cin + ci) * taps + t] = gw[((size_t)co * taps + t) * Cin + ci];
+  if (dw_oihw)
+    for (int co = 0; co < Cout; co++)
+      for (int ci = 0; ci < Cin; ci++)
+        for (int t = 0; t < taps; t++) dw_oihw[((size_t)co * Cin + ci) * taps + t] = gw[((size_t)co * taps + t) * Cin + ci];
   YS_CHECK_HIP(hipGetLastError());
+  if (f8_amax) { float m = 0.f; for (float v : ways) m = v > m ? v : m; *f8_amax = m; }
   return YS_OK;
+}
+
+extern "C" int ys_conv_bwd(ys_ctx* ctx, int dtype, const float* x_nchw, int B, int Cin, int H, int W,
+                           const float* w_oihw, int Cout, int k, int stride, const float* dy_nchw,
+                           float* dx_nchw, float* dw_oihw) {
+  YS_REQUIRE(x_nchw && dw_oihw, "ys_conv_bwd: null argument");
+  return conv_bwd_impl(ctx, dtype, x_nchw, B, Cin, H, W, w_oihw, Cout, k, stride, dy_nchw, dx_nchw, dw_oihw, 0.f, nullptr, nullptr);
+}
+
+extern "C" int ys_conv_f8_dgrad(ys_ctx* ctx, int B, int Cin, int H, int W, const float* w_oihw, int Cout, int k, int stride, const float* dy_nchw,
+                                float prev_amax, float* dx_nchw, float* scales, float* amax) {
+  YS_REQUIRE(dx_nchw && scales && amax, "ys_conv_f8_dgrad: null argument");
+  YS_REQUIRE(Cout >= 32 && Cout % 32 == 0, "ys_conv_f8_dgrad: Cout=%d (the fp8 kernels take multiples of 32 gradient channels)", Cout);
+  YS_REQUIRE(prev_amax >= 0.f && prev_amax < __builtin_inff(), "ys_conv_f8_dgrad: prev_amax must be finite and >= 0");
+  return conv_bwd_impl(ctx, YS_FP8, nullptr, B, Cin, H, W, w_oihw, Cout, k, stride, dy_nchw, dx_nchw, nullptr, prev_amax, scales, amax);
 }
 
 // ------------------------------------------------------------------ YOLOv11-only operators (attn_dw.hip), one call per kernel family
@@ -881,6 +925,212 @@ extern "C" int ys_copy_view(ys_ctx* ctx, int dtype, const float* src, int rows, 
   int ok = 1;
   YS_TRY(check_sentinel(st, dd.p, rows, d_ldc, d_coff, C, es, &ok));
   YS_TRY(check_sentinel(st, ds.p, rows, s_ldc, s_coff, C, es, &ok));
+  YS_CHECK_HIP(hipGetLastError());
+  if (view_intact) *view_intact = ok;
+  return YS_OK;
+}
+
+// ------------------------------------------------------------------ scaling machinery of the fp8 path (f8.hip) and the quantising BatchNorm passes, one call per kernel
+namespace {
+// the YS_AMAX_WAYS slots of one tensor, zeroed, with a sentinel guard behind them
+int alloc_slots(DevBuf& b, hipStream_t st) {
+  YS_TRY(alloc_filled(b, (YS_AMAX_WAYS + kGuardFloats) * 4, st));
+  YS_CHECK_HIP(hipMemsetAsync(b.p, 0, YS_AMAX_WAYS * 4, st));
+  return YS_OK;
+}
+// slots -> host (optional), *amax = their maximum, guard checked
+int fetch_slots(hipStream_t st, const DevBuf& b, float* slots, float* amax, int* ok) {
+  float h[YS_AMAX_WAYS];
+  YS_TRY(d2h(st, h, b.p, sizeof h));
+  YS_TRY(check_guard(st, b.p, YS_AMAX_WAYS, ok));      // synchronizes
+  float m = 0.f;
+  for (int i = 0; i < YS_AMAX_WAYS; i++) { if (slots) slots[i] = h[i]; m = h[i] > m ? h[i] : m; }
+  *amax = m;
+  return YS_OK;
+}
+// *ok &= the kGuardFloats * 4 bytes behind the n bytes of an fp8 image are still the sentinel
+int check_guard_bytes(hipStream_t st, const void* base, size_t n, int* ok) {
+  unsigned char h[kGuardFloats * 4];
+  YS_TRY(d2h(st, h, (const char*)base + n, sizeof h));
+  YS_CHECK_HIP(hipStreamSynchronize(st));
+  for (size_t i = 0; i < sizeof h; i++)
+    if (h[i] != kSentinelByte) *ok = 0;
+  return YS_OK;
+}
+int scalar_to_device(hipStream_t st, DevBuf& b, float v) {
+  YS_TRY(b.alloc(16));
+  YS_TRY(h2d(st, b.p, &v, 4));
+  YS_CHECK_HIP(hipStreamSynchronize(st));     // v is the caller's local
+  return YS_OK;
+}
+}  // namespace
+
+extern "C" int ys_f8_quant(ys_ctx* ctx, int kind, const float* x, int rows, int C, int coff, int pad, float qscale, uint8_t* q8, float* amax, float* slots,
+                           int32_t* view_intact) {
+  YS_REQUIRE(ctx && x && amax, "ys_f8_quant: null argument");
+  YS_REQUIRE(kind >= 0 && kind <= 3, "ys_f8_quant: kind %d", kind);
+  YS_REQUIRE(kind == 2 || q8, "ys_f8_quant: null argument");
+  YS_REQUIRE(rows >= 1 && C >= 1 && coff >= 0 && pad >= 0, "ys_f8_quant: rows=%d C=%d coff=%d pad=%d", rows, C, coff, pad);
+  const bool flat = kind == 3;
+  const int vec = kind == 2 ? 8 : 16;          // elements per thread and trip of the view kernels
+  YS_REQUIRE(flat ? (coff == 0 && pad == 0) : (C % vec == 0 && coff % 8 == 0 && pad % 8 == 0),
+             "ys_f8_quant: kind %d: view (C %d, coff %d, pad %d) must sit on the %d-element grid (the weight form is dense)", kind, C, coff, pad, vec);
+  YS_CHECK_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  const size_t n = (size_t)rows * C;
+  const int ld = coff + C + pad;
+  // bf16 on the host (exact for values that are bf16 already), the rest of the buffer the sentinel
+  std::vector<unsigned short> h((size_t)rows * ld, (unsigned short)(kSentinelByte * 0x0101));
+  for (int r = 0; r < rows; r++)
+    for (int c = 0; c < C; c++) h[(size_t)r * ld + coff + c] = f32_to_bf16_bits(x[(size_t)r * C + c]);
+  DevBuf dx, dq, ds, dsc;
+  YS_TRY(dx.alloc(h.size() * 2));
+  YS_TRY(h2d(st, dx.p, h.data(), h.size() * 2));
+  YS_TRY(alloc_filled(dq, n + kGuardFloats * 4, st));
+  YS_TRY(alloc_slots(ds, st));
+  YS_TRY(scalar_to_device(st, dsc, qscale));
+  if (kind == 2) YS_TRY(ys_f8_view_amax_launch(st, dx.p, rows, C, ld, coff, (unsigned*)ds.p));
+  else if (kind == 3) YS_TRY(ys_f8_quant_weights_launch(st, dx.p, (long)n, (const float*)dsc.p, dq.p));
+  else YS_TRY(ys_f8_quant_view_launch(st, kind, dx.p, rows, C, ld, coff, (const float*)dsc.p, dq.p, (unsigned*)ds.p));
+  if (q8 && kind != 2) YS_TRY(d2h(st, q8, dq.p, n));
+  int ok = 1;
+  YS_TRY(fetch_slots(st, ds, slots, amax, &ok));
+  YS_TRY(check_guard_bytes(st, dq.p, n, &ok));
+  if (kind == 2) YS_TRY(check_guard_bytes(st, dq.p, 0, &ok));          // the amax pass writes no image
+  YS_TRY(check_sentinel(st, dx.p, rows, ld, coff, C, 2, &ok));
+  YS_CHECK_HIP(hipStreamSynchronize(st));
+  YS_CHECK_HIP(hipGetLastError());
+  if (view_intact) *view_intact = ok;
+  return YS_OK;
+}
+
+extern "C" int ys_f8_amax_ways(void) { return YS_AMAX_WAYS; }
+
+extern "C" int ys_f8_scales(ys_ctx* ctx, const float* params, int64_t n_params, const int64_t* layer_off, const int64_t* layer_count, int n_layers,
+                            const int32_t* conv_layer, int n_convs, float* amax_x, float* amax_dy, float* scales, float* amax_w) {
+  YS_REQUIRE(ctx && params && layer_off && layer_count && conv_layer && amax_x && amax_dy && scales && amax_w, "ys_f8_scales: null argument");
+  YS_REQUIRE(n_params >= 1 && n_layers >= 1 && n_convs >= 1, "ys_f8_scales: n_params=%lld n_layers=%d n_convs=%d", (long long)n_params, n_layers, n_convs);
+  std::vector<F8Layer> hl((size_t)n_layers);
+  std::vector<F8Conv> hc((size_t)n_convs);
+  for (int l = 0; l < n_layers; l++) {
+    YS_REQUIRE(layer_off[l] >= 0 && layer_count[l] >= 0 && layer_off[l] + layer_count[l] <= n_params, "ys_f8_scales: layer %d lies outside the parameter array", l);
+    hl[l] = F8Layer{(long)layer_off[l], (long)layer_count[l]};
+  }
+  for (int c = 0; c < n_convs; c++) {
+    YS_REQUIRE(conv_layer[c] >= 0 && conv_layer[c] < n_layers, "ys_f8_scales: convolution %d names layer %d", c, conv_layer[c]);
+    hc[c] = F8Conv{conv_layer[c]};
+  }
+  YS_CHECK_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  const size_t nslot = (size_t)n_convs * YS_AMAX_WAYS;
+  DevBuf dp, dl, dc, daw, dax, dag, dsc;
+  YS_TRY(dp.alloc((size_t)n_params * 4)); YS_TRY(dl.alloc(hl.size() * sizeof(F8Layer))); YS_TRY(dc.alloc(hc.size() * sizeof(F8Conv)));
+  YS_TRY(alloc_filled(daw, ((size_t)n_layers + kGuardFloats) * 4, st));
+  YS_TRY(alloc_filled(dax, (nslot + kGuardFloats) * 4, st)); YS_TRY(alloc_filled(dag, (nslot + kGuardFloats) * 4, st));
+  YS_TRY(alloc_filled(dsc, ((size_t)n_convs * 4 + kGuardFloats) * 4, st));
+  YS_TRY(h2d(st, dp.p, params, (size_t)n_params * 4));
+  YS_TRY(h2d(st, dl.p, hl.data(), hl.size() * sizeof(F8Layer))); YS_TRY(h2d(st, dc.p, hc.data(), hc.size() * sizeof(F8Conv)));
+  YS_TRY(h2d(st, dax.p, amax_x, nslot * 4)); YS_TRY(h2d(st, dag.p, amax_dy, nslot * 4));
+  YS_TRY(h2d(st, dsc.p, scales, (size_t)n_convs * 16));
+  YS_TRY(ys_f8_weight_amax_launch(st, (const float*)dp.p, (const F8Layer*)dl.p, n_layers, (float*)daw.p));
+  YS_TRY(ys_f8_scales_launch(st, (const F8Conv*)dc.p, n_convs, (const float*)daw.p, (unsigned*)dax.p, (unsigned*)dag.p, (float*)dsc.p));
+  YS_TRY(d2h(st, amax_w, daw.p, (size_t)n_layers * 4));
+  YS_TRY(d2h(st, amax_x, dax.p, nslot * 4)); YS_TRY(d2h(st, amax_dy, dag.p, nslot * 4));
+  YS_TRY(d2h(st, scales, dsc.p, (size_t)n_convs * 16));
+  int ok = 1;
+  YS_TRY(check_guard(st, daw.p, (size_t)n_layers, &ok)); YS_TRY(check_guard(st, dax.p, nslot, &ok)); YS_TRY(check_guard(st, dag.p, nslot, &ok));
+  YS_TRY(check_guard(st, dsc.p, (size_t)n_convs * 4, &ok));
+  YS_CHECK_HIP(hipStreamSynchronize(st));
+  YS_CHECK_HIP(hipGetLastError());
+  YS_REQUIRE(ok, "ys_f8_scales: a kernel wrote behind its arrays");
+  return YS_OK;
+}
+
+extern "C" int ys_bn_apply_q8_fwd(ys_ctx* ctx, int act, const float* y, int rows, int C, const float* scale, const float* shift, const float* res, int res_pad,
+                                  int res_coff, int z_pad, int z_coff, int res_shares_z, float qscale, float* z, uint8_t* q8, float* amax, int32_t* view_intact) {
+  YS_REQUIRE(ctx && y && scale && shift && z && q8 && amax, "ys_bn_apply_q8_fwd: null argument");
+  YS_REQUIRE(rows >= 1 && C >= 8 && C % 8 == 0, "ys_bn_apply_q8_fwd: rows=%d C=%d (C must be a multiple of 8)", rows, C);
+  YS_TRY(view_ok("ys_bn_apply_q8_fwd z", YS_BF16, C, z_pad, z_coff));
+  if (res) YS_TRY(view_ok("ys_bn_apply_q8_fwd res", YS_BF16, C, res_pad, res_coff));
+  const bool shared = res && res_shares_z;
+  YS_REQUIRE(!shared || res_coff + C <= z_coff || z_coff + C <= res_coff, "ys_bn_apply_q8_fwd: res and z views overlap");
+  YS_CHECK_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  const int dtype = YS_BF16;
+  const size_t n = (size_t)rows * C;
+  int ldz = z_coff + C + z_pad, ldr = 0;
+  if (shared && res_coff + C + z_pad > ldz) ldz = res_coff + C + z_pad;
+  DevBuf dy, dz, dres, dpar, dq, ds, dsc;
+  YS_TRY(alloc_filled(dz, (size_t)rows * ldz * 2, st));
+  const void* resp = nullptr;
+  if (res) {
+    ldr = shared ? ldz : res_coff + C + res_pad;
+    if (!shared) YS_TRY(alloc_filled(dres, (size_t)rows * ldr * 2, st));
+    resp = shared ? dz.p : dres.p;
+    YS_TRY(stage_view(st, dtype, res, 1, C, rows, (void*)resp, ldr, res_coff));
+  }
+  YS_TRY(dy.alloc(n * 2));
+  YS_TRY(stage_view(st, dtype, y, 1, C, rows, dy.p, C, 0));
+  YS_TRY(dpar.alloc((size_t)2 * C * 4));
+  YS_TRY(h2d(st, dpar.p, scale, (size_t)C * 4)); YS_TRY(h2d(st, (float*)dpar.p + C, shift, (size_t)C * 4));
+  YS_TRY(alloc_filled(dq, n + kGuardFloats * 4, st));
+  YS_TRY(alloc_slots(ds, st));
+  YS_TRY(scalar_to_device(st, dsc, qscale));
+  YS_TRY(ys_bn_act_apply_q8_launch(st, dy.p, rows, C, (const float*)dpar.p, (const float*)dpar.p + C, act, resp, ldr, res_coff, dz.p, ldz, z_coff, dq.p,
+                                   (const float*)dsc.p, (unsigned*)ds.p));
+  YS_TRY(fetch_view(st, dtype, dz.p, ldz, z_coff, 1, C, rows, z));
+  YS_TRY(d2h(st, q8, dq.p, n));
+  int ok = 1;
+  YS_TRY(fetch_slots(st, ds, nullptr, amax, &ok));
+  YS_TRY(check_guard_bytes(st, dq.p, n, &ok));
+  const int views[2][2] = {{z_coff, C}, {res_coff, C}};
+  YS_TRY(check_sentinel_views(st, dz.p, rows, ldz, views, shared ? 2 : 1, 2, &ok));
+  if (dres.p) YS_TRY(check_sentinel(st, dres.p, rows, ldr, res_coff, C, 2, &ok));
+  YS_CHECK_HIP(hipStreamSynchronize(st));
+  YS_CHECK_HIP(hipGetLastError());
+  if (view_intact) *view_intact = ok;
+  return YS_OK;
+}
+
+extern "C" int ys_bn_apply_q8_bwd(ys_ctx* ctx, int act, const float* dz, const float* y, int rows, int C, const float* coef, int dz_pad, int dz_coff, float* rg,
+                                  int rg_pad, int rg_coff, float qscale, float* dy, uint8_t* q8, float* amax, int32_t* view_intact) {
+  YS_REQUIRE(ctx && dz && y && coef && dy && q8 && amax, "ys_bn_apply_q8_bwd: null argument");
+  YS_REQUIRE(rows >= 1 && C >= 8 && C % 8 == 0, "ys_bn_apply_q8_bwd: rows=%d C=%d (C must be a multiple of 8)", rows, C);
+  YS_TRY(view_ok("ys_bn_apply_q8_bwd dz", YS_BF16, C, dz_pad, dz_coff));
+  if (rg) YS_TRY(view_ok("ys_bn_apply_q8_bwd rg", YS_BF16, C, rg_pad, rg_coff));
+  YS_CHECK_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  const int dtype = YS_BF16;
+  const size_t n = (size_t)rows * C;
+  const int ldd = dz_coff + C + dz_pad, ldg = rg ? rg_coff + C + rg_pad : 0;
+  DevBuf ddz, dyb, drg, ddy, dpar, dq, ds, dsc;
+  YS_TRY(alloc_filled(ddz, (size_t)rows * ldd * 2, st));
+  YS_TRY(stage_view(st, dtype, dz, 1, C, rows, ddz.p, ldd, dz_coff));
+  YS_TRY(dyb.alloc(n * 2));
+  YS_TRY(stage_view(st, dtype, y, 1, C, rows, dyb.p, C, 0));
+  if (rg) {
+    YS_TRY(alloc_filled(drg, (size_t)rows * ldg * 2, st));
+    YS_TRY(stage_view(st, dtype, rg, 1, C, rows, drg.p, ldg, rg_coff));
+  }
+  YS_TRY(alloc_filled(ddy, n * 2 + kGuardFloats * 4, st));
+  YS_TRY(dpar.alloc((size_t)4 * C * 4));
+  YS_TRY(h2d(st, dpar.p, coef, (size_t)4 * C * 4));
+  const float* par = (const float*)dpar.p;
+  YS_TRY(alloc_filled(dq, n + kGuardFloats * 4, st));
+  YS_TRY(alloc_slots(ds, st));
+  YS_TRY(scalar_to_device(st, dsc, qscale));
+  YS_TRY(ys_bn_bwd_apply_q8_launch(st, ddz.p, ldd, dz_coff, dyb.p, rows, C, par, par + C, par + 2 * C, par + 3 * C, act, ddy.p, dq.p, (const float*)dsc.p,
+                                   (unsigned*)ds.p, drg.p, ldg, rg_coff));
+  YS_TRY(fetch_view(st, dtype, ddy.p, C, 0, 1, C, rows, dy));
+  if (rg) YS_TRY(fetch_view(st, dtype, drg.p, ldg, rg_coff, 1, C, rows, rg));
+  YS_TRY(d2h(st, q8, dq.p, n));
+  int ok = 1;
+  YS_TRY(fetch_slots(st, ds, nullptr, amax, &ok));
+  YS_TRY(check_guard_bytes(st, dq.p, n, &ok));
+  YS_TRY(check_guard_bytes(st, ddy.p, n * 2, &ok));
+  YS_TRY(check_sentinel(st, ddz.p, rows, ldd, dz_coff, C, 2, &ok));
+  if (rg) YS_TRY(check_sentinel(st, drg.p, rows, ldg, rg_coff, C, 2, &ok));
+  YS_CHECK_HIP(hipStreamSynchronize(st));
   YS_CHECK_HIP(hipGetLastError());
   if (view_intact) *view_intact = ok;
   return YS_OK;

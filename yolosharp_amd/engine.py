@@ -478,6 +478,113 @@ class Engine:
                for c, k in zip(cs, keep)]
         return status, out
 
+    # ---- fp8 path kernel by kernel (ys_f8_quant / ys_f8_scales / ys_bn_apply_q8_fwd / _bwd / ys_conv_f8_fwd / ys_conv_f8_dgrad)
+    F8_KINDS = {"e4m3": 0, "e5m2": 1, "amax": 2, "weights": 3}
+
+    def f8_amax_ways(self):
+        return int(self.lib.ys_f8_amax_ways())
+
+    def f8_quant(self, x, kind, qscale=1.0, coff=0, pad=0):
+        """x [rows][C] (row-major; bf16 on the device) through one quantiser launch -> dict(q8 uint8 [rows][C] or None, amax, slots [ways], view_intact).
+        kind "weights": qscale is amax_w."""
+        x = np.ascontiguousarray(x, np.float32)
+        rows, Cn = x.shape
+        kd = self.F8_KINDS[kind]
+        q8 = None if kd == 2 else np.full((rows, Cn), 0xA5, np.uint8)
+        amax, ok = C.c_float(-1.0), C.c_int32(-1)
+        slots = np.full(self.f8_amax_ways(), np.nan, np.float32)
+        _lib.check(self.lib, self.lib.ys_f8_quant(self.ctx, kd, _ptr(x), rows, Cn, coff, pad, float(qscale), _ptr(q8), C.byref(amax), _ptr(slots), C.byref(ok)))
+        return dict(q8=q8, amax=np.float32(amax.value), slots=slots, view_intact=ok.value)
+
+    def f8_scales(self, params, layers, conv_layer, amax_x, amax_dy, scales):
+        """layers = [(offset, count)]; amax_x / amax_dy [n][ways], scales [n][4] -> (amax_w [n_layers], amax_x, amax_dy, scales) after the two launches."""
+        p = np.ascontiguousarray(params, np.float32)
+        off = np.ascontiguousarray([l[0] for l in layers], np.int64)
+        cnt = np.ascontiguousarray([l[1] for l in layers], np.int64)
+        cl = np.ascontiguousarray(conv_layer, np.int32)
+        ax, ag, sc = (np.array(a, np.float32, order="C") for a in (amax_x, amax_dy, scales))
+        ways = self.f8_amax_ways()
+        assert ax.shape == (len(cl), ways) and ag.shape == ax.shape and sc.shape == (len(cl), 4), (ax.shape, ag.shape, sc.shape)
+        aw = np.full(len(layers), np.nan, np.float32)
+        _lib.check(self.lib, self.lib.ys_f8_scales(self.ctx, _ptr(p), p.size, _ptr(off), _ptr(cnt), len(layers), _ptr(cl), len(cl), _ptr(ax), _ptr(ag), _ptr(sc),
+                                                   _ptr(aw)))
+        return aw, ax, ag, sc
+
+    def bn_apply_q8_fwd(self, y, scale, shift, qscale, act=True, res=None, z_view=(0, 0), res_view=(0, 0), res_shares_z=False):
+        """bn_act_apply_q8_kernel alone: y, res [C][rows]; views = (pad, coff) -> dict(z [C][rows], q8 uint8 [rows][C], amax, view_intact)."""
+        f32 = lambda a: None if a is None else np.ascontiguousarray(a, np.float32)
+        y, res, sc, sh = f32(y), f32(res), f32(scale), f32(shift)
+        Cn, rows = y.shape
+        z, q8 = np.full((Cn, rows), np.nan, np.float32), np.full((rows, Cn), 0xA5, np.uint8)
+        amax, ok = C.c_float(-1.0), C.c_int32(-1)
+        _lib.check(self.lib, self.lib.ys_bn_apply_q8_fwd(self.ctx, int(act), _ptr(y), rows, Cn, _ptr(sc), _ptr(sh), _ptr(res), res_view[0], res_view[1],
+                                                         z_view[0], z_view[1], int(res_shares_z), float(qscale), _ptr(z), _ptr(q8), C.byref(amax), C.byref(ok)))
+        return dict(z=z, q8=q8, amax=np.float32(amax.value), view_intact=ok.value)
+
+    def bn_apply_q8_bwd(self, dz, y, coef, qscale, act=True, rg=None, dz_view=(0, 0), rg_view=(0, 0)):
+        """bn_bwd_apply_q8_kernel alone: dz, y, rg [C][rows], coef [4][C] = scale, shift, k2, k3 -> dict(dy, rg, q8 uint8 [rows][C], amax, view_intact)."""
+        f32 = lambda a: np.ascontiguousarray(a, np.float32)
+        dz, y, coef = f32(dz), f32(y), f32(coef)
+        rg = None if rg is None else np.array(rg, np.float32, order="C")
+        Cn, rows = y.shape
+        dy, q8 = np.full((Cn, rows), np.nan, np.float32), np.full((rows, Cn), 0xA5, np.uint8)
+        amax, ok = C.c_float(-1.0), C.c_int32(-1)
+        _lib.check(self.lib, self.lib.ys_bn_apply_q8_bwd(self.ctx, int(act), _ptr(dz), _ptr(y), rows, Cn, _ptr(coef), dz_view[0], dz_view[1], _ptr(rg), rg_view[0],
+                                                         rg_view[1], float(qscale), _ptr(dy), _ptr(q8), C.byref(amax), C.byref(ok)))
+        return dict(dy=dy, rg=rg, q8=q8, amax=np.float32(amax.value), view_intact=ok.value)
+
+    def conv_f8_fwd(self, x, weight, k, s, bn=None, bias=None, act=True, training=True, prev_amax=0.0):
+        """conv_bn_act(dtype="fp8") with a delayed activation scale (prev_amax = 0: current) -> dict(y, y_raw, coef, stat_rows, scales [4], amax recorded)."""
+        x = np.ascontiguousarray(x, np.float32)
+        w = np.ascontiguousarray(weight, np.float32)
+        B, Cin, H, W = x.shape
+        Cout = w.shape[0]
+        p = k // 2
+        y = np.empty((B, Cout, (H + 2 * p - k) // s + 1, (W + 2 * p - k) // s + 1), np.float32)
+        g = b = rm = rv = y_raw = coef = None
+        if bn is not None:
+            g, b = np.ascontiguousarray(bn["weight"], np.float32), np.ascontiguousarray(bn["bias"], np.float32)
+            rm, rv = bn["running_mean"], bn["running_var"]
+            assert rm.dtype == np.float32 and rv.dtype == np.float32
+            if training:
+                y_raw, coef = np.empty_like(y), np.empty((4, Cout), np.float32)
+        bs = np.ascontiguousarray(bias, np.float32) if bias is not None else None
+        rows, amax, scales = C.c_int32(0), C.c_float(-1.0), np.full(4, np.nan, np.float32)
+        _lib.check(self.lib, self.lib.ys_conv_f8_fwd(self.ctx, _ptr(x), B, Cin, H, W, _ptr(w), Cout, k, s, _ptr(g), _ptr(b), _ptr(rm), _ptr(rv), _ptr(bs), int(act),
+                                                     int(training), float(prev_amax), _ptr(y), _ptr(y_raw), _ptr(coef),
+                                                     C.byref(rows) if y_raw is not None else None, _ptr(scales), C.byref(amax)))
+        return dict(y=y, y_raw=y_raw, coef=coef, stat_rows=rows.value, scales=scales, amax=np.float32(amax.value))
+
+    def conv_f8_dgrad(self, x_shape, weight, k, s, dy, prev_amax=0.0):
+        """The fp8 input gradient of conv2d(x, weight, stride s, padding k // 2) given dy, with a delayed gradient scale -> dict(dx, scales [4], amax recorded)."""
+        w = np.ascontiguousarray(weight, np.float32)
+        dy = np.ascontiguousarray(dy, np.float32)
+        B, Cin, H, W = x_shape
+        dx = np.full(x_shape, np.nan, np.float32)
+        amax, scales = C.c_float(-1.0), np.full(4, np.nan, np.float32)
+        _lib.check(self.lib, self.lib.ys_conv_f8_dgrad(self.ctx, B, Cin, H, W, _ptr(w), w.shape[0], k, s, _ptr(dy), float(prev_amax), _ptr(dx), _ptr(scales),
+                                                       C.byref(amax)))
+        return dict(dx=dx, scales=scales, amax=np.float32(amax.value))
+
+    def conv_labels(self, fn):
+        """fn() with the per-launch profile on -> (its result, the labels of the convolution launches it made, in order per class)."""
+        import os
+        import tempfile
+        self.kernel_profile(True)
+        try:
+            out = fn()
+            self.synchronize()
+            fd, path = tempfile.mkstemp(suffix=".csv")
+            os.close(fd)
+            try:
+                self.kernel_profile_dump(path)
+                lines = open(path).read().splitlines()[1:]
+            finally:
+                os.remove(path)
+        finally:
+            self.kernel_profile(False)
+        return out, [l.split(",")[1] for l in lines if l.startswith("conv_igemm,")]
+
     def colsum(self, x, grad, bstride=None, ld_pad=0, coff=0, dtype="f32"):
         """grad [C] + column sums of x [B][C][rows_per_b] -> (status, grad, view_intact)."""
         x = np.ascontiguousarray(x, np.float32)
