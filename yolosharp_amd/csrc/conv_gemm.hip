@@ -439,33 +439,11 @@ static int conv_gemm_launch_t(hipStream_t st, ConvArgs a, const GemmPlan& p) {
   if (ys_kprof_enabled()) snprintf(lab, sizeof(lab), F8 ? "gemmf8 k%d s%d div1 cin%d cout%d M%d acc%d tile%dx%d grid%dx%d lds%d" : "gemm k%d s%d div1 cin%d cout%d M%d acc%d tile%dx%d grid%dx%d lds%d", a.KH * 10 + a.KW, a.SA, a.Cin, a.Cout, a.M, a.accumulate, WM * MR * 16, WN * NR * 16, p.gx, p.gy, (int)p.lds);
   YsKprofScope prof(st, "conv_igemm", lab);
 #ifdef YS_P2_TIMELINE
-  static unsigned long long* tl_buf = nullptr;
-  const char* tl_path = getenv("YS_P2_TL");
-  if (tl_path) {
-    if (!tl_buf) hipMalloc(&tl_buf, 64 * 64 * 8);
-    hipMemsetAsync(tl_buf, 0, 64 * 64 * 8, st);
-    a.tl = tl_buf;
-  }
+  const char* tl_path = ys_tl_begin(st, a);
 #endif
   YS_LAUNCH_LDS((conv_gemm_kernel<WM, WN, MR, NR, F8, RED>), dim3(p.gx, p.gy), 256, p.lds, st, a, p.g);
 #ifdef YS_P2_TIMELINE
-  if (tl_path) {
-    static unsigned long long h[64 * 64];
-    hipStreamSynchronize(st);
-    hipMemcpy(h, tl_buf, sizeof(h), hipMemcpyDeviceToHost);
-    FILE* f = fopen(tl_path, "a");
-    if (f) {
-      fprintf(f, "# gemm k%d%d s%d cin%d cout%d M%d acc%d tile%dx%d grid%dx%d lds%d mtiles%d nkt%d (stamps: table, then per tile: first request, K loop done, epilogue done; exit)\n", a.KH, a.KW, a.SA, a.Cin, a.Cout, a.M, a.accumulate, WM * MR * 16, WN * NR * 16, p.gx, p.gy, (int)p.lds, p.g.mtiles, p.g.nkt);
-      for (int w = 0; w < 64 && w * 37 < p.gx; w++) {
-        const int n = (int)h[w * 64];
-        if (n <= 0) continue;
-        fprintf(f, "wg%d:", w * 37);
-        for (int i = 1; i < n; i++) fprintf(f, " %llu", h[w * 64 + 1 + i] - h[w * 64 + 1]);
-        fprintf(f, "\n");
-      }
-      fclose(f);
-    }
-  }
+  ys_tl_dump(st, tl_path, a, p.gx, "# gemm k%d%d s%d cin%d cout%d M%d acc%d tile%dx%d grid%dx%d lds%d mtiles%d nkt%d (stamps: table, then per tile: first request, K loop done, epilogue done; exit)", a.KH, a.KW, a.SA, a.Cin, a.Cout, a.M, a.accumulate, WM * MR * 16, WN * NR * 16, p.gx, p.gy, (int)p.lds, p.g.mtiles, p.g.nkt);
 #endif
   return YS_OK;
 }

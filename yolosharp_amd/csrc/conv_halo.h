@@ -3,6 +3,7 @@
 // compile for minutes, so they build side by side).
 #pragma once
 #include "conv_epi.h"
+#include "conv_tl.h"
 #include <atomic>
 #include <cstdlib>
 // ------------------------------------------------------------------ halo-patch form for the 3x3 stride-1 layers (round 5)
@@ -391,33 +392,11 @@ static int conv_halo_launch_t(hipStream_t st, ConvArgs a, const HaloLaunch& p) {
   if (ys_kprof_enabled()) snprintf(lab, sizeof(lab), "halo k33 s1 div1 cin%d cout%d M%d acc%d tile%dx16x%d grid%dx%d lds%d", a.Cin, a.Cout, a.M, a.accumulate, 2 * MR, 2 * NR * 16, p.gx, p.gy, (int)p.lds);
   YsKprofScope prof(st, "conv_igemm", lab);
 #ifdef YS_P2_TIMELINE
-  static unsigned long long* tl_buf = nullptr;
-  const char* tl_path = getenv("YS_P2_TL");
-  if (tl_path) {
-    if (!tl_buf) hipMalloc(&tl_buf, 64 * 64 * 8);
-    hipMemsetAsync(tl_buf, 0, 64 * 64 * 8, st);
-    a.tl = tl_buf;
-  }
+  const char* tl_path = ys_tl_begin(st, a);
 #endif
   YS_LAUNCH_LDS((conv_halo_kernel<NR, RED, HALF, MR>), dim3(p.gx, p.gy), 256, p.lds, st, a, p.h);
 #ifdef YS_P2_TIMELINE
-  if (tl_path) {
-    static unsigned long long h[64 * 64];
-    hipStreamSynchronize(st);
-    hipMemcpy(h, tl_buf, sizeof(h), hipMemcpyDeviceToHost);
-    FILE* f = fopen(tl_path, "a");
-    if (f) {
-      fprintf(f, "# halo k33 cin%d cout%d M%d acc%d tile%dx16x%d grid%dx%d lds%d mtiles%d nchunk%d (stamps: entry, then per tile: prologue issued, K loop done, epilogue done; exit)\n", a.Cin, a.Cout, a.M, a.accumulate, 2 * MR, 2 * NR * 16, p.gx, p.gy, (int)p.lds, p.h.mtiles, p.h.nchunk);
-      for (int w = 0; w < 64 && w * 37 < p.gx; w++) {
-        const int n = (int)h[w * 64];
-        if (n <= 0) continue;
-        fprintf(f, "wg%d:", w * 37);
-        for (int i = 1; i < n; i++) fprintf(f, " %llu", h[w * 64 + 1 + i] - h[w * 64 + 1]);
-        fprintf(f, "\n");
-      }
-      fclose(f);
-    }
-  }
+  ys_tl_dump(st, tl_path, a, p.gx, "# halo k33 cin%d cout%d M%d acc%d tile%dx16x%d grid%dx%d lds%d mtiles%d nchunk%d (stamps: entry, then per tile: prologue issued, K loop done, epilogue done; exit)", a.Cin, a.Cout, a.M, a.accumulate, 2 * MR, 2 * NR * 16, p.gx, p.gy, (int)p.lds, p.h.mtiles, p.h.nchunk);
 #endif
   return YS_OK;
 }
