@@ -142,6 +142,7 @@ namespace YoloSharp.Native
         [DllImport(Lib)] internal static extern int ys_loss_segment(IntPtr model, float[] batchIdx, float[] cls, float[] bboxes, int n,
                                                                     float[] masks /* [B,H/4,W/4] overlap-encoded ids */, int onDevice, int cropMode);
         [DllImport(Lib)] internal static extern int ys_loss_read_items(IntPtr model, [Out] float[] items, int nItems, out float lossSum);
+        [DllImport(Lib)] internal static extern int ys_loss_read_targets(IntPtr model, [Out] int[] targetGtIdx /* [B*A], -1 = background */, [Out] float[] targetScore, out float tss);
         [DllImport(Lib)] internal static extern int ys_process_mask(IntPtr ctx, float[] protos, float[] masksIn, float[] boxes, int onDevice,
                                                                     int n, int nm, int mh, int mw, int ih, int iw, int upsample, int cropMode,
                                                                     [Out] byte[] outMasks);

@@ -285,6 +285,11 @@ YS_API int ys_loss_classify(ys_model* m, const float* cls, int batch, int on_dev
  * obb n_items = 4 (box, cls, dfl, angle; Loss.cs:546).
  * *loss_sum = sum(items)*B (classify: the mean loss itself, the scalar the reference calls backward() on). */
 YS_API int ys_loss_read_items(ys_model* m, float* loss_items, int n_items, float* loss_sum);
+/* The assignment behind the last criterion call, for tests that hold it against a reference assigner: target_gt_idx [B*A] = the label slot within the
+ * anchor's image (labels in order of appearance), -1 = background; target_score [B*A] = the anchor's normalised target score (target_scores.sum(-1),
+ * Loss.cs:138); *tss = target_scores_sum = max(sum, 1) (Loss.cs:444).  On an End2End model: of the one2one pass, which ran last over the shared
+ * workspaces.  Synchronising, read-only; any output may be NULL.  Refused before a criterion has run and on classify models. */
+YS_API int ys_loss_read_targets(ys_model* m, int32_t* target_gt_idx, float* target_score, float* tss);
 
 /* autograd backward of sum(loss*B) through the whole graph (Amp.cs:348,370). Gradients accumulate
  * into the flat fp32 gradient buffer like torch's .grad (call ys_model_zero_grad between steps). */

@@ -59,6 +59,18 @@ int main(void) {
   if (!(isfinite(items[0]) && isfinite(items[1]) && isfinite(items[2]) && items[1] > 0.f) || fabsf(lsum - (items[0] + items[1] + items[2]) * B) > 1e-3f * fabsf(lsum)) {
     fprintf(stderr, "loss items %g %g %g sum %g\n", items[0], items[1], items[2], lsum); return 1;
   }
+  /* the assignment behind the items: a label slot of the anchor's image (image 0 has two labels, image 1 one) or -1; scores on foreground anchors only */
+  int32_t* tgi = (int32_t*)malloc(sizeof(int32_t) * B * A);
+  float* tsc = (float*)malloc(sizeof(float) * B * A);
+  float tss = 0.f;
+  CHECK(ys_loss_read_targets(m, tgi, tsc, &tss));
+  int nfg = 0;
+  for (int i = 0; i < B * A; i++) {
+    if (tgi[i] < -1 || tgi[i] >= (i < A ? 2 : 1) || !(tsc[i] >= 0.f) || (tgi[i] < 0 && tsc[i] != 0.f)) { fprintf(stderr, "anchor %d: slot %d score %g\n", i, tgi[i], tsc[i]); return 1; }
+    nfg += tgi[i] >= 0;
+  }
+  if (nfg == 0 || !(tss >= 1.f)) { fprintf(stderr, "%d foreground anchors, target-score sum %g\n", nfg, tss); return 1; }
+  free(tgi); free(tsc);
   CHECK(ys_model_zero_grad(m));
   CHECK(ys_model_backward(m));
   float g0[16 * 3 * 3 * 3];

@@ -15,6 +15,7 @@ import pytest
 import torch
 
 import kat_ref as K
+import loss_cases as L
 from conftest import BACKENDS
 from oracle import yolo_oracle as O
 
@@ -78,6 +79,24 @@ def test_oracle_matches_kat():
             assert np.abs(got.numpy() - want).max() <= max(tol * 50, 2e-5) * np.abs(want).max(), dt
 
 
+def _grad_per_element(got, want, key, rot=False):
+    """every element, not only the largest: the bound of tests/test_loss_kernels.py (GRAD_R (|ref| + max|ref| / 8)); the known answers are central finite
+    differences in float64"""
+    mx = np.abs(want).max()
+    err = np.abs(got - want)
+    bound = L.GRAD_R[rot] * (np.abs(want) + mx / 8)
+    assert (err <= bound).all(), (key, float((err / bound).max()), float(mx))
+
+
+def _targets_match(crit, fg, gt_idx):
+    """the assignment read back from the engine (ys_loss_read_targets) is the known one: foreground set and label slot, every anchor"""
+    gi, ts, tss = crit.read_targets()
+    fg = np.array(fg, bool)
+    assert np.array_equal(gi >= 0, fg), np.argwhere((gi >= 0) != fg)[:6].tolist()
+    assert np.array_equal(gi[fg], np.array(gt_idx)[fg])
+    assert np.array_equal(ts > 0, fg & (ts > 0)) and tss >= 1.0
+
+
 @pytest.mark.parametrize("backend", BACKENDS)
 def test_engine_loss_matches_kat(backend, engine):
     """HIP v8DetectionLoss on caller-supplied preds (ys_model_set_preds) vs the independent answers: items within 1e-3
@@ -95,6 +114,8 @@ def test_engine_loss_matches_kat(backend, engine):
         want = np.array(want)
         got = m.get_output(key)
         assert np.abs(got - want).max() <= 1e-3 * np.abs(want).max(), (key, np.abs(got - want).max(), np.abs(want).max())
+        _grad_per_element(got, want, key)
+    _targets_match(v8DetectionLoss(m), k["fg"], k["gt_idx"])
     from yolosharp_amd import YsError
     with pytest.raises(YsError):
         m.backward()                                       # no graph state behind caller-supplied preds
@@ -214,6 +235,8 @@ def test_engine_task_losses_match_kat(backend, engine):
     assert np.allclose(loss.sum(), p["total"], rtol=1e-3)
     want = np.array(p["dkpts"])
     assert np.abs(m.get_output("dkpts") - want).max() <= 1e-3 * np.abs(want).max()
+    _grad_per_element(m.get_output("dkpts"), want, "dkpts")
+    _targets_match(v8PoseLoss(m), KAT["fg"], KAT["gt_idx"])        # the pose case is the detection case plus keypoints
     m.close()
     o = t["obb"]
     bx, sc, al, batch = _obb_case()
@@ -226,6 +249,8 @@ def test_engine_task_losses_match_kat(backend, engine):
         want = np.array(o[key])
         got = m.get_output(key)
         assert np.abs(got - want).max() <= 1e-3 * np.abs(want).max(), (key, np.abs(got - want).max(), np.abs(want).max())
+        _grad_per_element(got, want, key, rot=True)
+    _targets_match(v8OBBLoss(m), o["fg"], o["gt_idx"])
     m.close()
 
 

@@ -1,5 +1,5 @@
 // criterion.hip -- the criterion, End2End setup and output accessors of a model handle (ys_model.h): ys_model_get_output / _set_preds, the
-// ys_model_*e2e* / one2one entries, ys_model_reserve_labels and the ys_loss_* ABI.  Host code only: the kernels are loss.hip, segloss.hip, poseloss.hip,
+// ys_model_*e2e* / one2one entries, ys_model_reserve_labels and the ys_loss_* ABI (ys_loss_read_targets: the assignment, for tests).  Host code only: the kernels are loss.hip, segloss.hip, poseloss.hip,
 // classify.hip and e2e.hip, reached through their launchers (ys_kernels.h).  Of the other units of the handle it uses the fields, and plan.hip's dev_alloc and alloc_label_ws.
 //
 // Criteria (Utils/Loss.cs): v8DetectionLoss :330-484, v8OBBLoss :486-684, v8SegmentationLoss :711-780, v8PoseLoss :870-1071, v8ClassificationLoss
@@ -523,6 +523,23 @@ int ys_loss_read(ys_model* m, float loss_items[3], float* loss_sum) {
   YS_TRY(read_scalars(m, h));
   if (loss_items) { loss_items[0] = h[1]; loss_items[1] = h[2]; loss_items[2] = h[3]; }
   if (loss_sum) *loss_sum = h[4];
+  return YS_OK;
+}
+
+// The assignment behind the last criterion call (tests compare it with a reference assigner anchor by anchor): target_gt_idx [B*A] = the label slot within
+// the anchor's image (order of appearance), -1 = background; target_score [B*A] = the anchor's normalised target score (target_scores.sum(-1), Loss.cs:138);
+// *tss = target_scores_sum = max(sum, 1) (Loss.cs:444).  The workspaces are shared by the passes of an End2End criterion, so there this is the one2one pass.
+// Synchronising and read-only; any of the three outputs may be null.
+int ys_loss_read_targets(ys_model* m, int32_t* target_gt_idx, float* target_score, float* tss) {
+  YS_REQUIRE(m && !m->is_block, "ys_loss_read_targets: needs a full model");
+  YS_REQUIRE(!m->cls, "ys_loss_read_targets: a classify model's criterion assigns no targets");
+  YS_REQUIRE(m->have_loss, "ys_loss_read_targets: no loss has run");
+  hipStream_t st = m->ctx->stream;
+  const size_t n = (size_t)m->B * m->A;
+  if (target_gt_idx) YS_CHECK_HIP(hipMemcpyAsync(target_gt_idx, m->fg_gt, n * 4, hipMemcpyDeviceToHost, st));
+  if (target_score) YS_CHECK_HIP(hipMemcpyAsync(target_score, m->tnorm, n * 4, hipMemcpyDeviceToHost, st));
+  if (tss) YS_CHECK_HIP(hipMemcpyAsync(tss, m->e2e ? m->scalars2 : m->scalars, 4, hipMemcpyDeviceToHost, st));
+  YS_CHECK_HIP(hipStreamSynchronize(st));
   return YS_OK;
 }
 

@@ -469,6 +469,16 @@ class v8DetectionLoss:
         loss_detach = np.array(list(items), np.float32)
         return loss_detach * self.model._batch, loss_detach      # (loss * batch_size, loss.detach()), Loss.cs:476
 
+    def read_targets(self):
+        """The assignment behind the last call (ys_loss_read_targets): (target_gt_idx int32 [B,A] = label slot within the image, -1 = background;
+        target_score [B,A] = target_scores.sum(-1); tss = max(target_scores.sum(), 1)).  End2End models: of the one2one pass."""
+        m = self.model
+        gi = np.empty((m._batch, m.A), np.int32)
+        ts = np.empty((m._batch, m.A), np.float32)
+        tss = C.c_float()
+        _lib.check(self.lib, self.lib.ys_loss_read_targets(m.handle, _ptr(gi), _ptr(ts), C.byref(tss)))
+        return gi, ts, tss.value
+
 
 class v8SegmentationLoss(v8DetectionLoss):
     """Loss.cs:688-863.  batch additionally carries "masks" [B, H/4, W/4] (overlap-encoded instance ids,
