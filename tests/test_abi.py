@@ -94,6 +94,14 @@ def test_c_consumer_runs_on_device():
     assert rc == 0 and "abi_smoke OK: device_build=1" in out, out
 
 
+def test_sentinel_checker_can_say_no():
+    """tests/c/sentinel_check.cpp -- a stand-alone host program on csrc/sentinel_check.h alone: the predicate behind every `view_intact` reports a byte changed before a
+    view, behind it, between two views of a shared buffer and in the last row, for element sizes 1, 2 and 4 (every other test only ever sees it answer 1)."""
+    from yolosharp_amd import build
+    r = subprocess.run([build.build_sentinel_check()], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=60)
+    assert r.returncode == 0 and "sentinel_check OK" in r.stdout, r.stdout
+
+
 def test_csharp_shim_binds_only_exported_symbols():
     """bindings/csharp/YoloSharpHip.cs (the P/Invoke file a YoloSharp maintainer drops in): every
     `static extern` it declares must be a symbol of the header -- there is no dotnet here to compile it, so at least the names are pinned."""

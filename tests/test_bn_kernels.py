@@ -1,5 +1,5 @@
 """The BatchNorm training kernels of csrc/batchnorm.hip kernel by kernel against float64, through the stateless entry points ys_bn_train_fwd / ys_bn_train_bwd /
-ys_colsum / ys_upsample2x / ys_copy_view / ys_conv_bn_act_fwd_ex (csrc/ops_api.hip: host arrays staged into sentinel-padded views, the production launchers
+ys_colsum / ys_upsample2x / ys_copy_view / ys_conv_bn_act_fwd_ex (csrc/ops_bn.hip, ops_conv.hip: host arrays staged into sentinel-padded views, the production launchers
 called unchanged) -- no convolution, block or model between the kernel and the comparison.
 
 What is compared.  Every kernel against ITS OWN inputs, so that one kernel's allowed error is not charged to the next:

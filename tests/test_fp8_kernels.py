@@ -1,5 +1,5 @@
 """The fp8 convolution path kernel by kernel against exact references (recipe in csrc/f8.hip), through the stateless entries ys_f8_quant / ys_f8_scales /
-ys_bn_apply_q8_fwd / ys_bn_apply_q8_bwd / ys_conv_f8_fwd / ys_conv_f8_dgrad (csrc/ops_api.hip: the production launchers called unchanged).
+ys_bn_apply_q8_fwd / ys_bn_apply_q8_bwd / ys_conv_f8_fwd / ys_conv_f8_dgrad (csrc/ops_conv.hip and ops_bn.hip: the production launchers called unchanged).
 
 What is held.
   quantisers        every bf16 bit pattern through f8_quant_view_kernel<e4m3 / e5m2> and f8_quant_weights_kernel: the decoded bytes EQUAL

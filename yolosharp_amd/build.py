@@ -18,7 +18,7 @@ EMU = os.path.join(ROOT, "tools", "hipemu")
 BUILD = os.path.join(ROOT, "build")
 
 # (the job pool takes the units in this order: the conv_halo units, minutes each, stay among the first eight so that they start at once)
-SOURCES = ["core.hip", "nms.hip", "conv.hip", "conv_gemm.hip", "conv_halo5.hip", "conv_halo4.hip", "conv_halo5m.hip", "conv_halo4m.hip", "conv_p2_group.hip", "conv_p2_f8.hip", "conv_p2.hip", "conv_p2_plan.hip", "conv_stem.hip", "conv_wgrad.hip", "conv_wgrad_gemm.hip", "elementwise.hip", "batchnorm.hip", "ops_api.hip", "loss.hip", "attn_dw.hip", "segloss.hip", "poseloss.hip", "valmetrics.hip", "classify.hip", "e2e.hip", "augment.hip", "dist.hip", "f8.hip", "graph.hip", "plan.hip", "model.hip", "model_api.hip", "criterion.hip"]
+SOURCES = ["core.hip", "nms.hip", "conv.hip", "conv_gemm.hip", "conv_halo5.hip", "conv_halo4.hip", "conv_halo5m.hip", "conv_halo4m.hip", "conv_p2_group.hip", "conv_p2_f8.hip", "conv_p2.hip", "conv_p2_plan.hip", "conv_stem.hip", "conv_wgrad.hip", "conv_wgrad_gemm.hip", "elementwise.hip", "batchnorm.hip", "ops_conv.hip", "ops_bn.hip", "ops_attn_dw.hip", "ops_augment.hip", "loss.hip", "attn_dw.hip", "segloss.hip", "poseloss.hip", "valmetrics.hip", "classify.hip", "e2e.hip", "augment.hip", "dist.hip", "f8.hip", "graph.hip", "plan.hip", "model.hip", "model_api.hip", "criterion.hip"]
 # bit-exact fp32 sections (NMS IoU arithmetic; the augmenter's label arithmetic in the reference's order) must not be contracted into FMAs
 NO_CONTRACT = {"nms.hip", "valmetrics.hip", "augment.hip"}
 
@@ -134,6 +134,18 @@ def build_abi_smoke(verbose=False):
     return outs
 
 
+def build_sentinel_check(verbose=False):
+    """tests/c/sentinel_check.cpp (a stand-alone host program on csrc/sentinel_check.h alone, the predicate every view_intact rests on): build/sentinel_check."""
+    src = os.path.join(ROOT, "tests", "c", "sentinel_check.cpp")
+    exe = os.path.join(BUILD, "sentinel_check")
+    os.makedirs(BUILD, exist_ok=True)
+    if _newer(exe, [src, os.path.join(CSRC, "sentinel_check.h")]):
+        _run(["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-Werror", "-I", CSRC, src, "-o", exe])
+    if verbose:
+        print("built", exe)
+    return exe
+
+
 if __name__ == "__main__":
     what = sys.argv[1:] or ["device", "emu", "oracle"]
     if "device" in what:
@@ -152,3 +164,4 @@ if __name__ == "__main__":
         build_device(True, variant="abl", defines=["-DYS_GEMM_ABLATE"], out=os.path.join(BUILD, "libyolosharp_hip_abl.so"))
     if "abi" in what or len(sys.argv) == 1:
         build_abi_smoke(True)
+        build_sentinel_check(True)

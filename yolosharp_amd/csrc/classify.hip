@@ -11,7 +11,7 @@
 //   top-k          one wave per row, k <= 16 passes of a wave arg-max over the entries below the previous pick in the order
 //                  (score descending, index ascending): the reference's argsort(descending) with ties to the lower index.
 // Every lane of a wave runs the same trip counts around the wave reductions (the interpreter build needs full waves there).
-#include "ys_internal.h"
+#include "ops_stage.h"
 #include "bn_math.h"
 
 #define CLS_THREADS 256
@@ -241,14 +241,6 @@ int ys_cls_topk_launch(hipStream_t st, const float* x, int rows, int cols, int k
 }
 
 // ---- C ABI: ys_cls_topk (Classifier.Val's argsort, Models/Classifier.cs:95-100)
-namespace {
-struct ClsDevBuf {
-  void* p = nullptr;
-  ~ClsDevBuf() { if (p) (void)hipFree(p); }
-  int alloc(size_t n) { hipError_t e = hipMalloc(&p, n ? n : 16); return e == hipSuccess ? YS_OK : YS_ERR_OOM; }
-};
-}  // namespace
-
 extern "C" int ys_cls_topk(ys_ctx* ctx, const float* scores, int on_device, int rows, int cols, int k, int32_t* idx) {
   YS_REQUIRE(ctx && scores && idx, "ys_cls_topk: null argument");
   YS_REQUIRE(rows >= 0 && cols >= 1 && k >= 1 && k <= CLS_TOPK_MAX && k <= cols, "ys_cls_topk: rows=%d cols=%d k=%d (1 <= k <= min(16, cols))", rows, cols, k);
@@ -256,12 +248,12 @@ extern "C" int ys_cls_topk(ys_ctx* ctx, const float* scores, int on_device, int 
   YS_CHECK_HIP(hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
   if (on_device) return ys_cls_topk_launch(st, scores, rows, cols, k, idx);
-  ClsDevBuf ds, di;
+  DevBuf ds, di;
   YS_TRY(ds.alloc((size_t)rows * cols * 4));
   YS_TRY(di.alloc((size_t)rows * k * 4));
-  YS_CHECK_HIP(hipMemcpyAsync(ds.p, scores, (size_t)rows * cols * 4, hipMemcpyHostToDevice, st));
+  YS_TRY(h2d(st, ds.p, scores, (size_t)rows * cols * 4));
   YS_TRY(ys_cls_topk_launch(st, (const float*)ds.p, rows, cols, k, (int32_t*)di.p));
-  YS_CHECK_HIP(hipMemcpyAsync(idx, di.p, (size_t)rows * k * 4, hipMemcpyDeviceToHost, st));
+  YS_TRY(d2h(st, idx, di.p, (size_t)rows * k * 4));
   YS_CHECK_HIP(hipStreamSynchronize(st));
   return YS_OK;
 }

@@ -1,7 +1,5 @@
 // core.hip -- context, error reporting, memory helpers and the NMS entry point of the C ABI.
-#include "ys_internal.h"
-#include "ys_kernels.h"
-#include <cstring>
+#include "ops_stage.h"
 
 static thread_local char g_err[1024] = "";
 
@@ -128,16 +126,13 @@ void ys_kprof_end(hipStream_t st, const char* name) {
   e.open = nullptr;
 }
 
-// device scratch of the host-pointer convenience paths: freed on every exit path (an early return on a later allocation or copy
-// used to leak the earlier ones)
-namespace {
-struct ScratchBuf {
-  void* p = nullptr;
-  ~ScratchBuf() { if (p) hipFree(p); }
-  hipError_t alloc(size_t n) { return hipMalloc(&p, n ? n : 16); }
-  template <class U> U* as() const { return (U*)p; }
-};
-}  // namespace
+int ys_ctx_reserve_ws(ys_ctx* ctx, void** ws, size_t* ws_bytes, size_t need, const char* who) {
+  if (need <= *ws_bytes) return YS_OK;
+  if (*ws) { YS_CHECK_HIP(hipStreamSynchronize(ctx->stream)); YS_CHECK_HIP(hipFree(*ws)); *ws = nullptr; *ws_bytes = 0; }
+  if (hipMalloc(ws, need) != hipSuccess) { ys_set_error("%s: out of device memory (%zu bytes)", who, need); return YS_ERR_OOM; }
+  *ws_bytes = need;
+  return YS_OK;
+}
 
 extern "C" {
 
@@ -300,11 +295,11 @@ static int nms_batched_impl(ys_ctx* ctx, float* pred, int on_device, int B, int 
   const size_t n_pred = (size_t)B * C * A, n_rows = (size_t)B * max_det * (6 + extra), n_keep = (size_t)B * max_det;
   YsTimer timer(ctx, "nms");
   if (on_device) return ys_nms_launch(ctx, pred, B, C, A, conf_thres, iou_thres, max_det, nc, max_nms, max_wh, out_rows, out_keep, out_count, rotated);
-  ScratchBuf b_pred, b_rows, b_keep, b_cnt;
-  YS_CHECK_HIP(b_pred.alloc(n_pred * 4));
-  YS_CHECK_HIP(b_rows.alloc(n_rows * 4));
-  YS_CHECK_HIP(b_keep.alloc(n_keep * 8));
-  YS_CHECK_HIP(b_cnt.alloc((size_t)B * 4));
+  DevBuf b_pred, b_rows, b_keep, b_cnt;
+  YS_CHECK_HIP(b_pred.alloc_hip(n_pred * 4));
+  YS_CHECK_HIP(b_rows.alloc_hip(n_rows * 4));
+  YS_CHECK_HIP(b_keep.alloc_hip(n_keep * 8));
+  YS_CHECK_HIP(b_cnt.alloc_hip((size_t)B * 4));
   float* d_pred = b_pred.as<float>(); float* d_rows = b_rows.as<float>(); int64_t* d_keep = b_keep.as<int64_t>(); int32_t* d_cnt = b_cnt.as<int32_t>();
   YS_CHECK_HIP(hipMemcpyAsync(d_pred, pred, n_pred * 4, hipMemcpyHostToDevice, ctx->stream));
   int st = ys_nms_launch(ctx, d_pred, B, C, A, conf_thres, iou_thres, max_det, nc, max_nms, max_wh, d_rows, d_keep, d_cnt, rotated);
@@ -341,8 +336,8 @@ static int probiou_impl(ys_ctx* ctx, const float* obb1, const float* obb2, int o
   if (total == 0) return YS_OK;
   YS_CHECK_HIP(hipSetDevice(ctx->device));
   if (on_device) return ys_probiou_launch(ctx->stream, obb1, obb2, n, m, pairwise, ciou, eps, out);
-  ScratchBuf b1, b2, bo;
-  YS_CHECK_HIP(b1.alloc((size_t)n * 20)); YS_CHECK_HIP(b2.alloc((size_t)m * 20)); YS_CHECK_HIP(bo.alloc((size_t)total * 4));
+  DevBuf b1, b2, bo;
+  YS_CHECK_HIP(b1.alloc_hip((size_t)n * 20)); YS_CHECK_HIP(b2.alloc_hip((size_t)m * 20)); YS_CHECK_HIP(bo.alloc_hip((size_t)total * 4));
   YS_CHECK_HIP(hipMemcpyAsync(b1.p, obb1, (size_t)n * 20, hipMemcpyHostToDevice, ctx->stream));
   YS_CHECK_HIP(hipMemcpyAsync(b2.p, obb2, (size_t)m * 20, hipMemcpyHostToDevice, ctx->stream));
   YS_TRY(ys_probiou_launch(ctx->stream, b1.as<float>(), b2.as<float>(), n, m, pairwise, ciou, eps, bo.as<float>()));
@@ -402,11 +397,11 @@ int ys_process_mask(ys_ctx* ctx, const float* protos, const float* masks_in, con
   YsTimer timer(ctx, "process_mask");
   if (on_device) return ys_process_mask_launch(ctx->stream, protos, masks_in, boxes, n, nm, mh, mw, ih, iw, upsample, crop_mode, out);
   const size_t np = (size_t)nm * mh * mw, no = (size_t)n * (upsample ? (size_t)ih * iw : (size_t)mh * mw);
-  ScratchBuf b_p, b_m, b_b, b_o;
-  YS_CHECK_HIP(b_p.alloc(np * 4));
-  YS_CHECK_HIP(b_m.alloc((size_t)n * nm * 4));
-  YS_CHECK_HIP(b_b.alloc((size_t)n * 16));
-  YS_CHECK_HIP(b_o.alloc(no));
+  DevBuf b_p, b_m, b_b, b_o;
+  YS_CHECK_HIP(b_p.alloc_hip(np * 4));
+  YS_CHECK_HIP(b_m.alloc_hip((size_t)n * nm * 4));
+  YS_CHECK_HIP(b_b.alloc_hip((size_t)n * 16));
+  YS_CHECK_HIP(b_o.alloc_hip(no));
   float *d_p = b_p.as<float>(), *d_m = b_m.as<float>(), *d_b = b_b.as<float>(); unsigned char* d_o = b_o.as<unsigned char>();
   hipMemcpyAsync(d_p, protos, np * 4, hipMemcpyHostToDevice, ctx->stream);
   hipMemcpyAsync(d_m, masks_in, (size_t)n * nm * 4, hipMemcpyHostToDevice, ctx->stream);

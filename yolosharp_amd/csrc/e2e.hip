@@ -26,8 +26,7 @@
 //     k >  E2E_RANK_MAX: the general path, a bitonic sort in a global workspace (k padded to a power of two)
 // Values (amax, the k * nc gathered scores) stay in global memory (L2-resident: 33600 anchors are 134 KB per image, more than a
 // workgroup's static LDS), so the kernel is correct for any A >= 1, nc >= 1, max_det >= 1 with k * nc < 2^30.
-#include "ys_internal.h"
-#include "ys_kernels.h"
+#include "ops_stage.h"
 
 #define E2E_T 512            // threads of the per-image selection workgroup
 #define E2E_RANK_MAX 2048    // keys ordered in LDS by rank counting (2 x 16 KB)
@@ -251,4 +250,63 @@ e2e_bn_second_update_kernel(float* __restrict__ st, const float* __restrict__ sn
 int ys_e2e_bn_second_update_launch(hipStream_t st, float* state, const float* snap, const unsigned char* is_count, long n, float momentum) {
   if (n > 0) YS_LAUNCH(e2e_bn_second_update_kernel, ys_cdiv(n, 256), 256, st, state, snap, is_count, n, momentum);
   return YS_OK;
+}
+
+// ---- C ABI: Detect.postprocess / get_topk_index (Modules/Head.cs:117-127, 175-196) on a [B, 4+nc, A] tensor and the thresholding of
+//      Ops.non_max_suppression(end2end: true) (Utils/Ops.cs:258-267)
+static int e2e_topk_impl(const char* fn, ys_ctx* ctx, const float* pred, int on_device, int batch, int nc, int extra, int anchors, int max_det, float* out_rows,
+                         int64_t* out_anchor) {
+  YS_REQUIRE(ctx && pred && out_rows && out_anchor, "%s: null argument", fn);
+  YS_REQUIRE(batch > 0 && nc > 0 && extra >= 0 && anchors > 0 && max_det > 0, "%s: bad shape B=%d nc=%d extra=%d A=%d max_det=%d", fn, batch, nc, extra, anchors, max_det);
+  YS_CHECK_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  const size_t k = (size_t)(max_det < anchors ? max_det : anchors);
+  const size_t n_pred = (size_t)batch * (4 + nc + extra) * anchors, n_rows = (size_t)batch * k * (6 + extra), n_anc = (size_t)batch * k;
+  DevBuf dp, dr, da;
+  YS_TRY(ys_ctx_reserve_ws(ctx, &ctx->e2e_ws, &ctx->e2e_ws_bytes, ys_e2e_topk_ws_bytes(batch, nc, anchors, max_det), fn));
+  YsTimer timer(ctx, "e2e_topk");
+  if (on_device) return ys_e2e_topk_launch(st, pred, batch, nc, anchors, max_det, ctx->e2e_ws, out_rows, (long long*)out_anchor, extra);
+  YS_TRY(dp.alloc(n_pred * 4)); YS_TRY(dr.alloc(n_rows * 4)); YS_TRY(da.alloc(n_anc * 8));
+  YS_TRY(h2d(st, dp.p, pred, n_pred * 4));
+  YS_TRY(ys_e2e_topk_launch(st, (const float*)dp.p, batch, nc, anchors, max_det, ctx->e2e_ws, (float*)dr.p, (long long*)da.p, extra));
+  YS_TRY(d2h(st, out_rows, dr.p, n_rows * 4));
+  YS_TRY(d2h(st, out_anchor, da.p, n_anc * 8));
+  YS_CHECK_HIP(hipStreamSynchronize(st));
+  return YS_OK;
+}
+
+extern "C" int ys_e2e_topk(ys_ctx* ctx, const float* pred, int on_device, int batch, int nc, int anchors, int max_det, float* out_rows,
+                           int64_t* out_anchor) {
+  return e2e_topk_impl("ys_e2e_topk", ctx, pred, on_device, batch, nc, 0, anchors, max_det, out_rows, out_anchor);
+}
+
+extern "C" int ys_e2e_topk_ex(ys_ctx* ctx, const float* pred, int on_device, int batch, int nc, int extra, int anchors, int max_det, float* out_rows,
+                              int64_t* out_anchor) {
+  return e2e_topk_impl("ys_e2e_topk_ex", ctx, pred, on_device, batch, nc, extra, anchors, max_det, out_rows, out_anchor);
+}
+
+static int e2e_select_impl(const char* fn, ys_ctx* ctx, const float* rows, int on_device, int batch, int k, int row_len, float conf_thres, int max_det, int32_t* out_count) {
+  YS_REQUIRE(ctx && rows && out_count, "%s: null argument", fn);
+  // Ops.cs:248-251: ArgumentException for a threshold outside [0,1]
+  YS_REQUIRE(conf_thres >= 0.f && conf_thres <= 1.f, "Invalid Confidence threshold %g, valid values are between 0.0 and 1.0", conf_thres);
+  YS_REQUIRE(batch > 0 && k > 0 && max_det > 0 && row_len >= 6, "%s: bad shape B=%d k=%d max_det=%d row length %d", fn, batch, k, max_det, row_len);
+  YS_CHECK_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  if (on_device) return ys_e2e_select_launch(st, rows, batch, k, conf_thres, max_det, out_count, row_len);
+  DevBuf dr, dc;
+  const size_t nb = (size_t)batch * k * row_len * 4;
+  YS_TRY(dr.alloc(nb)); YS_TRY(dc.alloc((size_t)batch * 4));
+  YS_TRY(h2d(st, dr.p, rows, nb));
+  YS_TRY(ys_e2e_select_launch(st, (const float*)dr.p, batch, k, conf_thres, max_det, (int*)dc.p, row_len));
+  YS_TRY(d2h(st, out_count, dc.p, (size_t)batch * 4));
+  YS_CHECK_HIP(hipStreamSynchronize(st));
+  return YS_OK;
+}
+
+extern "C" int ys_e2e_select(ys_ctx* ctx, const float* rows, int on_device, int batch, int k, float conf_thres, int max_det, int32_t* out_count) {
+  return e2e_select_impl("ys_e2e_select", ctx, rows, on_device, batch, k, 6, conf_thres, max_det, out_count);
+}
+
+extern "C" int ys_e2e_select_ex(ys_ctx* ctx, const float* rows, int on_device, int batch, int k, int row_len, float conf_thres, int max_det, int32_t* out_count) {
+  return e2e_select_impl("ys_e2e_select_ex", ctx, rows, on_device, batch, k, row_len, conf_thres, max_det, out_count);
 }

@@ -14,8 +14,7 @@
 // Gradients of sum(loss*B) w.r.t. the head outputs are written directly (dpd, dps): the loss has
 // closed-form derivatives, CIoU's through forward-mode dual numbers (4 partials).
 // All arithmetic is fp32; pd/ps/dpd/dps are stored in the model dtype T.
-#include "ys_internal.h"
-#include "ys_kernels.h"
+#include "ops_stage.h"
 
 #define LS_THREADS 256
 #define TAL_LIST_CAP 8192   // in-box anchors of one (image, box) pair walked through an LDS list (16 KB of 16-bit indices; A <= 65535 on that path)
@@ -992,5 +991,31 @@ int ys_tal_keep_best_launch(hipStream_t st, const TalKeepArgs& k) {
   if (flat > (long)k.G * k.B) flat = (long)k.G * k.B;
   const dim3 grid = k.B <= TAL_FLAT_MAXB ? dim3((unsigned)flat) : dim3(k.G, k.B);
   YS_LAUNCH(tal_keep_best_kernel, grid, TAL_T, st, k);
+  return YS_OK;
+}
+
+// ---- C ABI: the assigner's second stage on its own (tal_keep_best_kernel, the kernel the End2End Segment criterion runs; Utils/Tal.cs:242-250)
+extern "C" int ys_tal_keep_best(ys_ctx* ctx, const float* align, uint8_t* mask_pos, const int32_t* gt_count, int on_device, int batch, int boxes, int anchors) {
+  YS_REQUIRE(ctx && align && mask_pos && gt_count, "ys_tal_keep_best: null argument");
+  YS_REQUIRE(batch > 0 && boxes > 0 && anchors > 0, "ys_tal_keep_best: bad shape B=%d G=%d A=%d", batch, boxes, anchors);
+  YS_CHECK_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  const size_t n = (size_t)batch * boxes * anchors;
+  TalKeepArgs k{};
+  k.B = batch; k.G = boxes; k.A = anchors;
+  if (on_device) {      // the caller vouches for 0 <= gt_count[b] <= boxes
+    k.align = align; k.mpos = mask_pos; k.gt_count = gt_count;
+    return ys_tal_keep_best_launch(st, k);
+  }
+  for (int b = 0; b < batch; b++) YS_REQUIRE(gt_count[b] >= 0 && gt_count[b] <= boxes, "ys_tal_keep_best: gt_count[%d] = %d outside [0, %d]", b, gt_count[b], boxes);
+  DevBuf da, dm, dc;
+  YS_TRY(da.alloc(n * 4)); YS_TRY(dm.alloc(n)); YS_TRY(dc.alloc((size_t)batch * 4));
+  YS_TRY(h2d(st, da.p, align, n * 4));
+  YS_TRY(h2d(st, dm.p, mask_pos, n));
+  YS_TRY(h2d(st, dc.p, gt_count, (size_t)batch * 4));
+  k.align = (const float*)da.p; k.mpos = (unsigned char*)dm.p; k.gt_count = (const int*)dc.p;
+  YS_TRY(ys_tal_keep_best_launch(st, k));
+  YS_TRY(d2h(st, mask_pos, dm.p, n));
+  YS_CHECK_HIP(hipStreamSynchronize(st));
   return YS_OK;
 }

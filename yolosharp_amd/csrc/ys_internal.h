@@ -70,6 +70,10 @@ struct ys_ctx {
   hipStream_t dist_stream = nullptr; hipEvent_t dist_ready = nullptr, dist_done = nullptr; bool dist_pending = false;
 };
 
+// a context-owned device workspace (e2e_ws, aug_ws) grown to `need` bytes: nothing when it is large enough already, else the stream is synchronized and the
+// block replaced (core.hip).  The context keeps it, so device-resident calls stay asynchronous.  YS_ERR_OOM names `who` and the byte count.
+int ys_ctx_reserve_ws(ys_ctx* ctx, void** ws, size_t* ws_bytes, size_t need, const char* who);
+
 // simple RAII-free timing helper: records events on the ctx stream when profiling is on
 struct YsTimer {
   ys_ctx* c; const char* name; bool on;
