@@ -121,6 +121,13 @@ namespace YoloSharp.Native
         [DllImport(Lib)] internal static extern int ys_augment_letterbox_jitter(IntPtr ctx, IntPtr arena, IntPtr srcs, int nSrc, IntPtr items, int batch, int onDevice,
                                                                                 int imgsz, int maskRatio, IntPtr jitter, IntPtr images, IntPtr masks);
         [DllImport(Lib)] internal static extern int ys_color_jitter(IntPtr ctx, IntPtr src, IntPtr jitter, int batch, int h, int w, int onDevice, IntPtr dst, int dstIsFloat);
+        // The classification input (Data/ClassificationDataset.cs:90-131, Auto_Augment = None): RandomResizedCrop / Resize + CenterCrop, the flips, RandomErasing,
+        // ColorJitter (contrast included) and mul(1 / 255) as one gather from the uploaded uint8 arena; an item is the DRAWN geometry of one output image (the host keeps
+        // the draws).  srcCls [nSrc] fp32 class ids; images fp32 [batch, 3, imgsz, imgsz]; outCls fp32 [batch] (what ys_loss_classify(onDevice = 1) reads).
+        // jitter = IntPtr.Zero: no jitter (the val chain).  The interpolation (nearest), Resize(int) and CenterCrop's rounding are unpinned against TorchVision.NET.
+        [StructLayout(LayoutKind.Sequential)] internal struct YsClsItem { public int src, top, left, ch, cw, oh, ow, oy, ox, flipLr, flipUd, erY, erX, erH, erW; public uint erSeed; }
+        [DllImport(Lib)] internal static extern int ys_augment_classify(IntPtr ctx, IntPtr arena, IntPtr srcs, int nSrc, IntPtr srcCls, IntPtr items, int batch, int onDevice,
+                                                                        int imgsz, IntPtr jitter, IntPtr images, IntPtr outCls);
         // OBB corner labels (Data/YoloDataset.cs:110-129; Utils/Ops.cs:44-54): corners [n, 4, 2] pixels in place of the keypoints, outBboxes [capacity, 5] = (cx, cy, w, h) / imgsz
         // and the angle of the minimum-area rectangle, angle in (0, pi/2], w along the angle (OpenCV >= 4.5.1's form; the choice among equal-area rectangles is unpinned
         // against OpenCV).  boxes [n, 4] alone decides what is kept; flags must be 0.  ys_xyxyxyxy2xywhr is the rectangle on its own: [n, 4, 2] -> [n, 5], pixels and radians.

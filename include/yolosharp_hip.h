@@ -609,6 +609,47 @@ YS_API int ys_augment_letterbox_labels_obb(ys_ctx* ctx, const ys_aug_src* srcs, 
                                            const float* corners, const ys_aug_item* items, int batch, int on_device, int imgsz, int flags, int capacity,
                                            float* out_batch_idx, float* out_cls, float* out_bboxes, int32_t* out_count);
 
+/* ---- The classification input (Data/ClassificationDataset.cs:90-131, GetTensor :70-88) with Auto_Augment = None, as one fused gather per batch:
+ *   train  RandomResizedCrop(imgsz, scale, ratio) (:95) -> RandomHorizontalFlip (:98) -> RandomVerticalFlip (:102) -> RandomErasing (:120; the
+ *          reference's own class, :166-226) -> ColorJitter(brightness = vgain, contrast = vgain, saturation = sgain, hue = hgain) (:122) -> mul(1 / 255.0f) (:79)
+ *   val    Resize(imgsz) (:126) -> CenterCrop(imgsz) (:127) -> mul(1 / 255.0f)
+ *   label  the source's class id, one per image (:80-83)
+ * Same arena and ys_aug_src table as the other augment entries (the mask fields are ignored); src_cls [n_src] fp32 class ids; items / jitter [batch];
+ * images fp32 [batch, 3, imgsz, imgsz]; out_cls fp32 [batch] = src_cls[items[b].src], what ys_loss_classify(..., on_device = 1) reads.  All tables
+ * follow on_device.  imgsz in [1, 16384] (odd sizes take scalar stores).  No cropped, resized or uint8 intermediate image exists.
+ *
+ * An item is the DRAWN geometry, general enough for both chains.  With y' = flip_ud ? imgsz - 1 - y : y and x' likewise,
+ *   out[y][x] = src[top + min(floor((y' + oy) * ((float)ch / (float)oh)), ch - 1)][left + min(floor((x' + ox) * ((float)cw / (float)ow)), cw - 1)]
+ * -- the nearest rule of ys_letterbox / ys_augment_letterbox (ATen legacy nearest, fp32) on the crop window (top, left, ch, cw) of the source, resized
+ * to (oh, ow), of which the imgsz x imgsz window at (oy, ox) is taken.  Train: oh = ow = imgsz, oy = ox = 0.  Val: top = left = 0, (ch, cw) = (H, W),
+ * (oh, ow) the resized size, (oy, ox) the centre-crop offset.
+ * Erase: in the output frame, after the flips and in front of the jitter, a pixel of [er_y, er_y + er_h) x [er_x, er_x + er_w) takes one noise byte
+ * per channel in place of the gathered one.  The reference writes torch.empty(c, h, w).normal_() into the uint8 image; ATen's CPU cast truncates
+ * toward zero and wraps mod 256.  The byte has exactly the distribution of (uint8)(int64)z, z ~ N(0, 1): value k = 0 covers (-1, 1), k > 0 [k, k + 1),
+ * k < 0 (k - 1, k]; thresholds round(2^32 * cumulative probability) for k = -6 .. 6 on one 32-bit word (DEVIATION: the tails beyond +-7, mass 2.6e-12,
+ * fold into +-6).  The word is counter-based, independent of the launch shape (uint32 arithmetic, c = channel, (y, x) = output pixel):
+ *   u = mix32(mix32(er_seed ^ (c * 0x9e3779b9u)) + (y * imgsz + x));   mix32(x): x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16
+ * The reference's torch RNG stream cannot be matched; every draw of this pipeline is the host's.
+ * Jitter: the bytes go through the image's ys_aug_jitter row (the arithmetic of ys_color_jitter), ALL four ops: contrast's mean is taken over the
+ * imgsz x imgsz output in its state in front of the contrast op, by a reduction launch that replays gather, erase and the ops ahead of it (integer
+ * atomics; mean = (float)sum / (float)(imgsz * imgsz): torch.mean's value bit for bit for imgsz * imgsz <= 65536, 224 included; above that the
+ * DEVIATION of ys_color_jitter carries over).  A host-pointer batch without a contrast row, and jitter == NULL (no jitter: the val chain), take one
+ * launch; with device pointers the reduction runs and leaves at once where a row has no contrast.
+ * An item is valid when 0 <= src < n_src and the source has an image; ch, cw >= 1, top, left >= 0, top + ch <= H, left + cw <= W; oh, ow >= 1,
+ * oy, ox >= 0, oy + imgsz <= oh, ox + imgsz <= ow; the flips are 0 or 1; the erase rectangle is all zero (none) or er_h, er_w >= 1 inside
+ * [0, imgsz)^2.  Host pointers: the first invalid item or jitter row is YS_ERR_INVALID_ARG.  Device pointers: that image is all 114 * (1 / 255.0f),
+ * not jittered, and out_cls[b] = -1; the other images of the batch are unaffected.
+ * QUIRKS of the reference a host reproduces in its draws (yolosharp_amd/augment.py draw_classify_items): RandomErasing's gate is a NORMAL draw,
+ * `randn > p` skips (:218): at p = 0.4 an image is erased with probability 0.655; its accept test is strict (h < H and w < W, :201); ten failed tries
+ * erase the image with itself (nothing).  Not built: Auto_Augment (AutoAugment -- the reference's default -- RandAugment, AugMix).
+ * UNPINNED (TorchVision.NET's source is not in the reference tree): the interpolation of RandomResizedCrop / Resize (nearest here, as for
+ * functional.resize elsewhere in this project); whether Resize(int) is smaller-edge or square; CenterCrop's rounding; the accept condition of the
+ * crop tries.  The item is general: a host that knows better fills it differently, the kernel does not change. */
+typedef struct ys_cls_item { int32_t src, top, left, ch, cw, oh, ow, oy, ox, flip_lr, flip_ud, er_y, er_x, er_h, er_w; uint32_t er_seed; } ys_cls_item;   /* 64 bytes */
+YS_API int ys_augment_classify(ys_ctx* ctx, const uint8_t* arena, const ys_aug_src* srcs, int n_src, const float* src_cls,
+                               const ys_cls_item* items, int batch, int on_device, int imgsz, const ys_aug_jitter* jitter,
+                               float* images, float* out_cls);
+
 /* ---- per-operator entry points (unit parity; a TorchSharp-free C# Conv wrapper) ---------------
  * Convs.Conv.forward (Convs.cs:36-62): y = act(BN(conv2d(x))) on fp32 NCHW / OIHW HOST arrays at the
  * edge (the call stages them through HBM).  training != 0 uses batch statistics and updates running stats (momentum 0.03, eps 1e-3). */

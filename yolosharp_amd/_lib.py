@@ -51,6 +51,12 @@ class AugJitter(C.Structure):
     _fields_ = [("order", C.c_int32 * 4), ("factor", C.c_float * 4)]
 
 
+class ClsItem(C.Structure):
+    """ys_cls_item: the drawn geometry of one output image of the classification input (crop window, resized size, window offset, flips, erase rectangle and seed)."""
+    _fields_ = [(n, C.c_int32) for n in ("src", "top", "left", "ch", "cw", "oh", "ow", "oy", "ox", "flip_lr", "flip_ud", "er_y", "er_x", "er_h", "er_w")] + \
+               [("er_seed", C.c_uint32)]
+
+
 class BnFwdCase(C.Structure):
     """ys_bn_fwd_case: one problem of ys_bn_train_fwd (host arrays channel-major [C][rows])."""
     _fields_ = [("y", C.c_void_p), ("gamma", C.c_void_p), ("beta", C.c_void_p), ("run_mean", C.c_void_p), ("run_var", C.c_void_p), ("nbt", C.c_void_p),
@@ -211,6 +217,8 @@ PROTOTYPES = {
     "ys_augment_letterbox_labels_obb": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                                  C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ys_color_jitter": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int]),
+    "ys_augment_classify": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                     C.c_void_p]),
     "ys_block_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "ys_block_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "ys_device_malloc": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]),

@@ -19,6 +19,12 @@ angle in (0, pi/2], w along the angle) and columns 0-3 / imgsz: the batch's boxe
 box alone, the LetterBox pads are not scaled by ratio and that branch clips nothing.  The choice among equal-area rectangles is UNPINNED against OpenCV
 (include/yolosharp_hip.h).  xyxyxyxy2xywhr() is the operator on its own.
 
+The classification input (Data/ClassificationDataset.cs:90-131 with Auto_Augment = None): ClassifyAugmenter uploads the uint8 dataset and the class ids once;
+per batch the host draws what RandomResizedCrop, the two flips, RandomErasing and ColorJitter draw (draw_classify_items; the val chain, Resize + CenterCrop,
+draws nothing: draw_classify_val_items) and ys_augment_classify gathers crop, resize, flips, erase noise, all four jitter ops and mul(1 / 255) in one pass
+(csrc/augment_cls.hip) -> ClassifyDeviceBatch.  Not built: AutoAugment (the reference's default) / RandAugment / AugMix.  TorchVision.NET is not in the
+reference tree: nearest interpolation, smaller-edge Resize(int), CenterCrop's rounding and the crop tries' accept test are torchvision's public ones, UNPINNED.
+
 Not built: the `rand > p` case of Augment.Mosaic (it yields images of unequal sizes).
 kpt_dim = 3 only."""
 import ctypes as C
@@ -33,6 +39,9 @@ ITEM_DTYPE = np.dtype([("src", "<i4", (4,)), ("xc", "<i4"), ("yc", "<i4"), ("M",
 JITTER_DTYPE = np.dtype([("order", "<i4", (4,)), ("factor", "<f4", (4,))])
 assert SRC_DTYPE.itemsize == C.sizeof(_lib.AugSrc) == 32 and ITEM_DTYPE.itemsize == C.sizeof(_lib.AugItem) == 68
 assert JITTER_DTYPE.itemsize == C.sizeof(_lib.AugJitter) == 32
+CLS_ITEM_DTYPE = np.dtype([(n, "<i4") for n in ("src", "top", "left", "ch", "cw", "oh", "ow", "oy", "ox", "flip_lr", "flip_ud", "er_y", "er_x", "er_h", "er_w")] +
+                          [("er_seed", "<u4")])
+assert CLS_ITEM_DTYPE.itemsize == C.sizeof(_lib.ClsItem) == 64
 JITTER_BRIGHTNESS, JITTER_CONTRAST, JITTER_SATURATION, JITTER_HUE = 0, 1, 2, 3      # the op ids of ColorJitter.forward
 YS_AUG_SORT_FLIPPED = 1              # ys_augment_labels: write a flipped box as (min, max)
 YS_AUG_FLIP_KEEP_SIZE = 2            # ys_augment_letterbox_labels: a flip leaves the cxcywh box's w / h alone (the reference writes s - w)
@@ -516,3 +525,218 @@ class MosaicAugmenter:
             if len(idx) < batch_size and drop_last:
                 break
             yield self.batch(idx)
+
+
+# ---------------------------------------------------------------------------------------------------- the classification input
+def make_classify_items(n):
+    return np.zeros((n,), CLS_ITEM_DTYPE)
+
+
+def check_classify_items(items, srcs, s):
+    """The library's item check (include/yolosharp_hip.h ys_augment_classify) on the host: ValueError naming the first invalid item."""
+    items, srcs = np.ascontiguousarray(items, CLS_ITEM_DTYPE), np.ascontiguousarray(srcs, SRC_DTYPE)
+    it = {k: items[k].astype(np.int64) for k in CLS_ITEM_DTYPE.names}
+    ok = (it["src"] >= 0) & (it["src"] < srcs.shape[0])
+    sr = srcs[np.where(ok, it["src"], 0)] if srcs.shape[0] else np.zeros(items.shape, SRC_DTYPE)
+    H, W = sr["h"].astype(np.int64), sr["w"].astype(np.int64)
+    ok &= (H >= 1) & (W >= 1) & (sr["img_off"] >= 0)
+    ok &= (it["ch"] >= 1) & (it["cw"] >= 1) & (it["top"] >= 0) & (it["left"] >= 0) & (it["top"] + it["ch"] <= H) & (it["left"] + it["cw"] <= W)
+    ok &= (it["oh"] >= 1) & (it["ow"] >= 1) & (it["oy"] >= 0) & (it["ox"] >= 0) & (it["oy"] + s <= it["oh"]) & (it["ox"] + s <= it["ow"])
+    ok &= ((it["flip_lr"] == 0) | (it["flip_lr"] == 1)) & ((it["flip_ud"] == 0) | (it["flip_ud"] == 1))
+    none = (it["er_y"] == 0) & (it["er_x"] == 0) & (it["er_h"] == 0) & (it["er_w"] == 0)
+    ok &= none | ((it["er_h"] >= 1) & (it["er_w"] >= 1) & (it["er_y"] >= 0) & (it["er_x"] >= 0) & (it["er_y"] + it["er_h"] <= s) & (it["er_x"] + it["er_w"] <= s))
+    if not ok.all():
+        b = int(np.argmin(ok))
+        raise ValueError("classify item %d is invalid: %s" % (b, {k: int(items[b][k]) for k in CLS_ITEM_DTYPE.names}))
+    return items
+
+
+def _resized_crop_params(rng, H, W, scale, ratio):
+    """torchvision RandomResizedCrop.get_params: (top, left, h, w)."""
+    area = H * W
+    lo, hi = math.log(ratio[0]), math.log(ratio[1])
+    for _ in range(10):
+        target = area * (scale[0] + (scale[1] - scale[0]) * rng.random())
+        aspect = math.exp(lo + (hi - lo) * rng.random())
+        w, h = int(round(math.sqrt(target * aspect))), int(round(math.sqrt(target / aspect)))
+        if 0 < w <= W and 0 < h <= H:
+            return int(rng.integers(0, H - h + 1)), int(rng.integers(0, W - w + 1)), h, w
+    in_ratio = W / H                                                       # the centre fallback with the ratio clamp
+    if in_ratio < min(ratio):
+        w = W
+        h = int(round(w / min(ratio)))
+    elif in_ratio > max(ratio):
+        h = H
+        w = int(round(h * max(ratio)))
+    else:
+        w, h = W, H
+    h, w = min(max(h, 1), H), min(max(w, 1), W)
+    return (H - h) // 2, (W - w) // 2, h, w
+
+
+def _erasing_params(rng, s, p, gate):
+    """The reference's RandomErasing (ClassificationDataset.cs:166-226) on the s x s image: (er_y, er_x, er_h, er_w, er_seed), zeros for no erase."""
+    g = rng.standard_normal() if gate == "normal" else rng.random()
+    if g > p:                                                              # :218 (a NORMAL draw there)
+        return 0, 0, 0, 0, 0
+    lo, hi = math.log(0.3), math.log(3.3)
+    for _ in range(10):
+        area = s * s * (0.02 + (0.33 - 0.02) * rng.random())
+        aspect = math.exp(lo + (hi - lo) * rng.random())
+        h, w = int(round(math.sqrt(area * aspect))), int(round(math.sqrt(area / aspect)))      # Math.Round: half to even, like Python's
+        if not (h < s and w < s):                                          # :201, strict
+            continue
+        seed = int(rng.integers(0, 2 ** 32, dtype=np.uint64))              # in the slot of the reference's noise tensor (:206)
+        y, x = int(rng.integers(s - h + 1)), int(rng.integers(s - w + 1))
+        if h < 1 or w < 1:                                                 # an empty rectangle erases nothing
+            return 0, 0, 0, 0, 0
+        return y, x, h, w, seed
+    return 0, 0, 0, 0, 0                                                   # :213: the image erased with itself
+
+
+def draw_classify_items(rng, indices, shapes, s, scale=(0.08, 1.0), ratio=(3 / 4, 4 / 3), fliplr=0.5, flipud=0.0, erasing=0.4, hsv=(0.015, 0.7, 0.4),
+                        erasing_gate="normal"):
+    """The item table of one classification training batch (ClassificationDataset.build_transforms, :95-122, Auto_Augment = None): per index of `indices`,
+    from ONE stream in the reference's order, what RandomResizedCrop.get_params draws for the source's shapes[idx] = (H, W) -- ten tries of
+    target = H * W * U(scale), aspect = exp(U(log ratio)), accepted iff 0 < w <= W and 0 < h <= H, then top and left; else the centre fallback --
+    RandomHorizontalFlip, then RandomVerticalFlip (each drawn only when its p > 0; flip iff rand < p), RandomErasing (only when erasing > 0; its gate is a
+    NORMAL draw, `randn > p` skips: at p = 0.4 an image is erased with probability 0.655, kept; erasing_gate = "uniform" gives `rand > p`), and one
+    draw_jitter row with contrast = vgain (only when hsv is not None).  -> (items, jitter rows or None)."""
+    assert erasing_gate in ("normal", "uniform"), erasing_gate
+    s = int(s)
+    items = make_classify_items(len(indices))
+    rows = make_jitter(len(indices)) if hsv is not None else None
+    for b, idx in enumerate(indices):
+        H, W = (int(v) for v in shapes[int(idx)])
+        top, left, ch, cw = _resized_crop_params(rng, H, W, scale, ratio)
+        flr = fliplr > 0 and rng.random() < fliplr
+        fud = flipud > 0 and rng.random() < flipud
+        er = _erasing_params(rng, s, erasing, erasing_gate) if erasing > 0 else (0, 0, 0, 0, 0)
+        items[b] = (int(idx), top, left, ch, cw, s, s, 0, 0, int(flr), int(fud)) + er
+        if hsv is not None:
+            hgain, sgain, vgain = hsv
+            rows[b] = draw_jitter(rng, 1, hgain, sgain, vgain, cgain=vgain)[0]
+    return items, rows
+
+
+def draw_classify_val_items(indices, shapes, s):
+    """The val chain's items (:126-127), nothing random: torchvision Resize(int) -- the smaller edge to s, the other to int(s * long / short) -- then
+    CenterCrop(s) at int(round((size - s) / 2.0)).  No flips, no erase; run them without jitter rows."""
+    s = int(s)
+    items = make_classify_items(len(indices))
+    for b, idx in enumerate(indices):
+        H, W = (int(v) for v in shapes[int(idx)])
+        oh, ow = (s, int(s * W / H)) if H <= W else (int(s * H / W), s)
+        items[b] = (int(idx), 0, 0, H, W, oh, ow, int(round((oh - s) / 2.0)), int(round((ow - s) / 2.0)), 0, 0, 0, 0, 0, 0, 0)
+    return items
+
+
+def augment_classify(engine, arena, srcs, src_cls, items, imgsz, jitter=None):
+    """ys_augment_classify on HOST arrays: -> (images fp32 [B, 3, s, s], cls fp32 [B])."""
+    arena = np.ascontiguousarray(arena, np.uint8)
+    srcs, items = np.ascontiguousarray(srcs, SRC_DTYPE), np.ascontiguousarray(items, CLS_ITEM_DTYPE)
+    src_cls = np.ascontiguousarray(src_cls, np.float32).reshape(-1)
+    assert src_cls.shape[0] == srcs.shape[0], (src_cls.shape, srcs.shape)
+    B, s = items.shape[0], int(imgsz)
+    if jitter is not None:
+        jitter = np.ascontiguousarray(jitter, JITTER_DTYPE)
+        assert jitter.shape == (B,), jitter.shape
+    images, cls = np.empty((B, 3, max(s, 0), max(s, 0)), np.float32), np.empty((B,), np.float32)
+    _lib.check(engine.lib, engine.lib.ys_augment_classify(engine.ctx, _ptr(arena), _ptr(srcs), srcs.shape[0], _ptr(src_cls), _ptr(items), B, 0, s, _ptr(jitter),
+                                                          _ptr(images), _ptr(cls)))
+    return images, cls
+
+
+class ClassifyDeviceBatch:
+    """One classification batch that lives in HBM: device pointers to images fp32 [batch, 3, imgsz, imgsz] and cls fp32 [batch] (one class id per image).
+    mode = the chain that produced it: "train" or "val"."""
+
+    def __init__(self, engine, batch, imgsz, images, cls, mode="train"):
+        self.engine, self.batch, self.imgsz, self.images, self.cls, self.mode = engine, int(batch), int(imgsz), images, cls, mode
+
+    def to_host(self):
+        """The same batch as the numpy dict the host path takes (synchronises): images, cls and the collate's batch_idx = 0 .. batch - 1."""
+        e, s = self.engine, self.imgsz
+        return dict(images=e.from_device(self.images, (self.batch, 3, s, s), np.float32), cls=e.from_device(self.cls, (self.batch,), np.float32),
+                    batch_idx=np.arange(self.batch, dtype=np.float32))
+
+
+class ClassifyAugmenter:
+    """ClassificationDataset's input on the device.  The dataset -- uint8 RGB planes [3, h, w] of any sizes and one class id per image -- is uploaded ONCE;
+    a batch uploads its 64-byte items and 32-byte jitter rows only and is one fused gather (ys_augment_classify).  draw() follows draw_classify_items from
+    one numpy Generator; val_batches() walks the dataset in order through the val chain.  The output buffers are reused by the next batch.
+    erasing = 0 and hsv = None each skip their draws.  auto_augment: only None is built (the reference's default is AutoAugment): anything else raises
+    NotImplementedError.  close_mosaic() does nothing -- ClassificationDataset.CloseMosaic is empty -- so Trainer.fit(..., augmenter=this) works unchanged."""
+
+    def __init__(self, engine, images_u8, classes, imgsz, scale=(0.08, 1.0), ratio=(3 / 4, 4 / 3), fliplr=0.5, flipud=0.0, erasing=0.4, hsv=(0.015, 0.7, 0.4),
+                 auto_augment=None, seed=0, max_batch=64, erasing_gate="normal"):
+        if auto_augment is not None:
+            raise NotImplementedError("auto_augment=%r: AutoAugment / RandAugment / AugMix are not built; this is the reference's chain with Auto_Augment = None"
+                                      % (auto_augment,))
+        assert len(images_u8) == len(classes) and len(images_u8) >= 1
+        self.engine, self.s = engine, int(imgsz)
+        self.scale, self.ratio = tuple(float(v) for v in scale), tuple(float(v) for v in ratio)
+        self.fliplr, self.flipud, self.erasing, self.erasing_gate = float(fliplr), float(flipud), float(erasing), erasing_gate
+        self.hsv = tuple(float(g) for g in hsv) if hsv is not None else None
+        assert self.hsv is None or len(self.hsv) == 3
+        self.rng = np.random.default_rng(seed)
+        arena, self.srcs = pack_sources(images_u8)
+        self.shapes = [(int(h), int(w)) for h, w in zip(self.srcs["h"], self.srcs["w"])]
+        self.classes = np.ascontiguousarray(classes, np.float32).reshape(-1)
+        self.count, self.max_batch = len(images_u8), int(max_batch)
+        e, s, B = engine, self.s, self.max_batch
+        self.d_arena, self.d_srcs, self.d_src_cls = e.to_device(arena), e.to_device(self.srcs), e.to_device(self.classes)
+        self.d_items, self.d_jitter = e.malloc(B * CLS_ITEM_DTYPE.itemsize), e.malloc(B * JITTER_DTYPE.itemsize)
+        self.d_images, self.d_ocls = e.malloc(B * 3 * s * s * 4), e.malloc(B * 4)
+
+    def close(self):
+        for name in ("d_arena", "d_srcs", "d_src_cls", "d_items", "d_jitter", "d_images", "d_ocls"):
+            p = getattr(self, name, None)
+            if p is not None:
+                self.engine.free(p)
+            setattr(self, name, None)
+
+    def close_mosaic(self, closed):
+        """ClassificationDataset.CloseMosaic is empty: nothing changes."""
+
+    def draw(self, indices):
+        """(items, jitter rows or None) of one training batch for the dataset indices `indices`."""
+        return draw_classify_items(self.rng, indices, self.shapes, self.s, self.scale, self.ratio, self.fliplr, self.flipud, self.erasing, self.hsv,
+                                   self.erasing_gate)
+
+    def run(self, items, rows=None, mode="train"):
+        """Validate on the host (the device cannot refuse aloud), upload `items` (and the jitter rows; None = no jitter) and launch on the engine's stream
+        (asynchronous) -> ClassifyDeviceBatch."""
+        e, lib = self.engine, self.engine.lib
+        items = check_classify_items(items, self.srcs, self.s)
+        B = int(items.shape[0])
+        assert 0 < B <= self.max_batch
+        _lib.check(lib, lib.ys_memcpy_h2d(e.ctx, self.d_items, _ptr(items), items.nbytes))
+        d_jit = None
+        if rows is not None:
+            rows = check_jitter(rows, allow_contrast=True)
+            if rows.shape != (B,):
+                raise ValueError("%d jitter rows for %d items" % (rows.shape[0], B))
+            _lib.check(lib, lib.ys_memcpy_h2d(e.ctx, self.d_jitter, _ptr(rows), rows.nbytes))
+            d_jit = self.d_jitter
+        _lib.check(lib, lib.ys_augment_classify(e.ctx, self.d_arena, self.d_srcs, self.count, self.d_src_cls, self.d_items, B, 1, self.s, d_jit, self.d_images,
+                                                self.d_ocls))
+        return ClassifyDeviceBatch(e, B, self.s, self.d_images, self.d_ocls, mode=mode)
+
+    def batch(self, indices):
+        return self.run(*self.draw(indices))
+
+    def batches(self, batch_size, shuffle=True, drop_last=True):
+        """One training epoch: the dataset indices in (shuffled) order, `batch_size` at a time."""
+        order = self.rng.permutation(self.count) if shuffle else np.arange(self.count)
+        for i in range(0, self.count, batch_size):
+            idx = order[i:i + batch_size]
+            if len(idx) < batch_size and drop_last:
+                break
+            yield self.batch(idx)
+
+    def val_batches(self, batch_size):
+        """The whole dataset in order through the val chain (Resize + CenterCrop), `batch_size` at a time, the last batch short."""
+        for i in range(0, self.count, batch_size):
+            idx = np.arange(i, min(i + batch_size, self.count))
+            yield self.run(draw_classify_val_items(idx, self.shapes, self.s), None, mode="val")

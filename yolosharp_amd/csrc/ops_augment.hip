@@ -1,6 +1,6 @@
 // ops_augment.hip -- the training input's entry points of the C ABI (augment.hip), the ones a host calls every step with device pointers (on_device != 0) and
 // the tests with host arrays: Mosaic4 + RandomPerspective + flips + Normalize + collate (Data/Augment.cs:158-274, 315-695, 860-966; Data/YoloDataset.cs:102-151;
-// Data/YoloDataLoader.cs:18-44), the LetterBox (close-mosaic) branch (Data/YoloDataset.cs:378-429; Data/Augment.cs:698-778, 860-966), ColorJitter, OBB labels.
+// Data/YoloDataLoader.cs:18-44), the LetterBox (close-mosaic) branch (Data/YoloDataset.cs:378-429; Data/Augment.cs:698-778, 860-966), ColorJitter, OBB labels, and the classification input (Data/ClassificationDataset.cs:90-131; augment_cls.hip).
 #include "ops_stage.h"
 
 namespace {
@@ -301,6 +301,52 @@ extern "C" int ys_xyxyxyxy2xywhr(ys_ctx* ctx, const float* corners, int n, int o
   YS_TRY(h2d(st, dc.p, corners, (size_t)n * 32));
   YS_TRY(ys_xyxyxyxy2xywhr_launch(st, (const float*)dc.p, n, (float*)dout.p));
   YS_TRY(d2h(st, out, dout.p, (size_t)n * 20));
+  YS_CHECK_HIP(hipStreamSynchronize(st));
+  return YS_OK;
+}
+
+// ---- the classification input (augment_cls.hip; Data/ClassificationDataset.cs:90-131): crop / resize / flips / erase / ColorJitter / mul(1 / 255) as one
+//      gather, and the class ids.  The contrast reduction's per-image sums live in the augmenter's workspace, zeroed on the stream each call.
+extern "C" int ys_augment_classify(ys_ctx* ctx, const uint8_t* arena, const ys_aug_src* srcs, int n_src, const float* src_cls, const ys_cls_item* items,
+                                   int batch, int on_device, int imgsz, const ys_aug_jitter* jitter, float* images, float* out_cls) {
+  const char* fn = "ys_augment_classify";
+  YS_REQUIRE(ctx && arena && srcs && src_cls && items && images && out_cls, "%s: null argument", fn);
+  YS_REQUIRE(batch > 0 && batch <= 65535 && n_src > 0, "%s: bad shape batch=%d (1..65535) n_src=%d", fn, batch, n_src);
+  YS_REQUIRE(imgsz >= 1 && imgsz <= 16384, "%s: imgsz %d must be in [1, 16384]", fn, imgsz);
+  YS_CHECK_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  YS_TRY(aug_reserve_ws(ctx, batch));
+  YsTimer timer(ctx, "augment_classify");
+  if (on_device) {                                         // the host cannot read the rows: the reduction runs and leaves at once where a row has no contrast
+    if (jitter) YS_CHECK_HIP(hipMemsetAsync(ctx->aug_ws, 0, (size_t)batch * 8, st));
+    return ys_aug_classify_launch(st, arena, srcs, n_src, src_cls, items, batch, imgsz, jitter, 1, ctx->aug_ws, images, out_cls);
+  }
+  for (int b = 0; b < batch; b++) {
+    const ys_cls_item& it = items[b];
+    YS_REQUIRE(ys_aug_cls_item_ok_host(&it, srcs, n_src, imgsz), "%s: item %d is invalid: src %d of %d, crop (top %d, left %d, %d x %d), resized %d x %d, window "
+               "(%d, %d) + %d, flips (%d, %d), erase (y %d, x %d, %d x %d)", fn, b, it.src, n_src, it.top, it.left, it.ch, it.cw, it.oh, it.ow, it.oy, it.ox, imgsz,
+               it.flip_lr, it.flip_ud, it.er_y, it.er_x, it.er_h, it.er_w);
+  }
+  int contrast = 0;
+  if (jitter) YS_TRY(aug_check_jitter(fn, jitter, batch, 1, &contrast));
+  const size_t arena_bytes = aug_arena_bytes(srcs, n_src), src_bytes = (size_t)n_src * sizeof(ys_aug_src), item_bytes = (size_t)batch * sizeof(ys_cls_item);
+  const size_t jit_bytes = (size_t)batch * sizeof(ys_aug_jitter), n_img = (size_t)batch * 3 * imgsz * imgsz;
+  DevBuf da, ds, dc, di, dj, dimg, dcls;
+  YS_TRY(da.alloc(arena_bytes)); YS_TRY(ds.alloc(src_bytes)); YS_TRY(dc.alloc((size_t)n_src * 4)); YS_TRY(di.alloc(item_bytes));
+  YS_TRY(dimg.alloc(n_img * 4)); YS_TRY(dcls.alloc((size_t)batch * 4));
+  YS_TRY(h2d(st, da.p, arena, arena_bytes));
+  YS_TRY(h2d(st, ds.p, srcs, src_bytes));
+  YS_TRY(h2d(st, dc.p, src_cls, (size_t)n_src * 4));
+  YS_TRY(h2d(st, di.p, items, item_bytes));
+  if (jitter) {
+    YS_TRY(dj.alloc(jit_bytes));
+    YS_TRY(h2d(st, dj.p, jitter, jit_bytes));
+  }
+  if (contrast) YS_CHECK_HIP(hipMemsetAsync(ctx->aug_ws, 0, (size_t)batch * 8, st));
+  YS_TRY(ys_aug_classify_launch(st, da.as<unsigned char>(), ds.as<ys_aug_src>(), n_src, dc.as<float>(), di.as<ys_cls_item>(), batch, imgsz,
+                                jitter ? dj.as<ys_aug_jitter>() : nullptr, contrast, ctx->aug_ws, dimg.as<float>(), dcls.as<float>()));
+  YS_TRY(d2h(st, images, dimg.p, n_img * 4));
+  YS_TRY(d2h(st, out_cls, dcls.p, (size_t)batch * 4));
   YS_CHECK_HIP(hipStreamSynchronize(st));
   return YS_OK;
 }

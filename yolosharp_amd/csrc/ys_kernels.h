@@ -455,3 +455,9 @@ int ys_color_jitter_launch(hipStream_t st, const unsigned char* src, const ys_au
 int ys_aug_letterbox_labels_launch(hipStream_t st, const ys_aug_src* srcs, int n_src, const int* lab_off, const float* cls, const float* boxes,
                                    const float* kpts, int K, const ys_aug_item* items, int B, int s, int flags, int capacity, void* ws, float* o_bidx,
                                    float* o_cls, float* o_box, float* o_kpt, int* o_count, int obb = 0);
+// ---- augment_cls.hip: the classification input (Data/ClassificationDataset.cs:90-131): crop / resize / flips / erase / ColorJitter (contrast included)
+// / mul(1 / 255) as one gather, and the images' class ids.  sums: B zeroed 64-bit counters (the contrast reduction; with_contrast = 0 skips it)
+struct ys_cls_item;
+int ys_aug_cls_item_ok_host(const ys_cls_item* it, const ys_aug_src* srcs, int n_src, int s);
+int ys_aug_classify_launch(hipStream_t st, const unsigned char* arena, const ys_aug_src* srcs, int n_src, const float* src_cls, const ys_cls_item* items,
+                           int B, int s, const ys_aug_jitter* jitter, int with_contrast, void* sums, float* images, float* out_cls);

@@ -479,10 +479,24 @@ class Classifier:
     def Val(self, batches):
         """batches: iterable of dicts (images [B,3,H,W] in [0,1], batch_idx, cls [B]).  Returns (summed loss items [1], [top1, top5]):
         eval forward, the criterion on the eval logits, the top-min(nc, 5) classes of the softmax per image (ys_cls_topk), then top-1 /
-        top-5 accuracy over the set.  Batches with an empty batch_idx are skipped (Classifier.cs:83-86)."""
+        top-5 accuracy over the set.  Batches with an empty batch_idx are skipped (Classifier.cs:83-86).  A batch may also be an
+        augment.ClassifyDeviceBatch (ClassifyAugmenter.val_batches): the eval forward runs from its device pointer and the criterion on its device labels."""
+        from .augment import ClassifyDeviceBatch
         loss_sum, tops, targets = None, [], []
         k = min(self.model.nc, 5)
         for data in batches:
+            if isinstance(data, ClassifyDeviceBatch):                # images and class ids already in HBM (ClassifyAugmenter.val_batches)
+                m = self.model
+                assert data.imgsz == m.height == m.width, (data.imgsz, m.height, m.width)
+                m.eval()
+                m.forward_device(data.images, data.batch)
+                inference, _ = m._outputs()
+                self.loss.forward_device(data.cls, data.batch)
+                _, items = self.loss.read()
+                loss_sum = items if loss_sum is None else loss_sum + items
+                tops.append(self.engine.cls_topk(inference["cls"], k))
+                targets.append(self.engine.from_device(data.cls, (data.batch,), np.float32))
+                continue
             if np.asarray(data["batch_idx"]).size < 1:
                 continue
             inference, _ = self.amp.Evaluate(np.ascontiguousarray(data["images"], np.float32))

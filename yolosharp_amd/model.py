@@ -615,9 +615,20 @@ class AMPWrapper:
 
     def TrainStepDevice(self, batch, loss_func: v8DetectionLoss):
         """TrainStep on an augment.DeviceBatch: images and labels are already in HBM, nothing is copied to the device.  The criterion reads all
-        `capacity` rows (those behind the batch's count carry batch_idx -1 and are skipped)."""
+        `capacity` rows (those behind the batch's count carry batch_idx -1 and are skipped).
+        A classification model (TASK 4) takes an augment.ClassifyDeviceBatch instead -- images and one class id per image -- and only that."""
+        from .augment import ClassifyDeviceBatch
         m = self.model
         assert batch.imgsz == m.height == m.width, (batch.imgsz, m.height, m.width)
+        if isinstance(batch, ClassifyDeviceBatch):
+            if m.TASK != 4:
+                raise ValueError("TrainStepDevice: a classification batch for a model of task %d" % m.TASK)
+            m.train()
+            m.forward_device(batch.images, batch.batch)
+            loss_func.forward_device(batch.cls, batch.batch)
+            loss, items = loss_func.read()
+            self.Step()
+            return loss, items
         if m.TASK not in (0, 1, 2, 3):
             raise ValueError("TrainStepDevice: the device augmenter produces Detect, Segment, OBB and Pose batches")
         box_dim = getattr(batch, "box_dim", 4)

@@ -94,11 +94,13 @@ class Trainer:
         warm-up index i only advances on batches that trained: the reference's `continue` on an empty batch skips its i++.
         A batch is a numpy dict or an augment.DeviceBatch (images and labels already in HBM).  A device batch's label count is a device number the
         loop does not read: it is skipped only when its INPUT label count (the labels of its tiles before the filters) is 0."""
-        from .augment import DeviceBatch
+        from .augment import ClassifyDeviceBatch, DeviceBatch
         items_sum, i = None, 0
         for data in batches:
             self.amp.lrs = self.sched.begin_iteration(epoch, i)
-            if isinstance(data, DeviceBatch):
+            if isinstance(data, ClassifyDeviceBatch):                             # one class id per image: never empty
+                _, items = self.amp.TrainStepDevice(data, self.crit)
+            elif isinstance(data, DeviceBatch):
                 if data.n_input < 1:
                     continue
                 _, items = self.amp.TrainStepDevice(data, self.crit)
@@ -122,7 +124,8 @@ class Trainer:
         """train_batches / val_batches: callables returning an iterable of batches for an epoch.  Returns the history.
         augmenter: the augment.MosaicAugmenter train_batches draws from.  Before each epoch's train_batches() it is told
         `augmenter.close_mosaic(epoch > close_mosaic)` -- trainDataSet.CloseMosaic(epoch > config.CloseMosaic), YoloBaseTaskModel.cs:180, with
-        Config.CloseMosaic's default of 0: the LetterBox pipeline from epoch 1 on.  Without an augmenter nothing changes."""
+        Config.CloseMosaic's default of 0: the LetterBox pipeline from epoch 1 on.  Without an augmenter nothing changes.  An
+        augment.ClassifyAugmenter takes the same call and ignores it (ClassificationDataset.CloseMosaic is empty)."""
         hist = []
         for epoch in range(1, self.epochs + 1):
             if augmenter is not None:
