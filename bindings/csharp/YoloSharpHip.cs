@@ -128,6 +128,16 @@ namespace YoloSharp.Native
         [StructLayout(LayoutKind.Sequential)] internal struct YsClsItem { public int src, top, left, ch, cw, oh, ow, oy, ox, flipLr, flipUd, erY, erX, erH, erW; public uint erSeed; }
         [DllImport(Lib)] internal static extern int ys_augment_classify(IntPtr ctx, IntPtr arena, IntPtr srcs, int nSrc, IntPtr srcCls, IntPtr items, int batch, int onDevice,
                                                                         int imgsz, IntPtr jitter, IntPtr images, IntPtr outCls);
+        // Auto_Augment = AutoAugment (the reference's default) / RandAugment (Data/ClassificationDataset.cs:105-116): one YsAaRow per image = two operator slots run
+        // between the flips and RandomErasing; op id in torchvision's _augmentation_space order (-1 nothing, 0 ShearX .. 13 Invert), arg = 1 + m for the blends / bits /
+        // threshold, theta = torchvision's inverse affine matrix rounded to fp32 (the host keeps the policy, probability, sign and magnitude draws).  aa = IntPtr.Zero is
+        // ys_augment_classify.  ys_auto_augment_ops is the two slots on their own on uint8 [b, 3, h, w].  AugMix is not built; the policy table, the magnitude spaces and
+        // the operator arithmetic are torchvision's public ones, unpinned against TorchVision.NET.
+        [StructLayout(LayoutKind.Sequential)] internal struct YsAaRow { public int op0, op1; public float arg0, arg1;
+                                                                        public float t00, t01, t02, t03, t04, t05, t10, t11, t12, t13, t14, t15; }
+        [DllImport(Lib)] internal static extern int ys_augment_classify_aa(IntPtr ctx, IntPtr arena, IntPtr srcs, int nSrc, IntPtr srcCls, IntPtr items, int batch, int onDevice,
+                                                                           int imgsz, IntPtr aa, IntPtr jitter, IntPtr images, IntPtr outCls);
+        [DllImport(Lib)] internal static extern int ys_auto_augment_ops(IntPtr ctx, IntPtr src, int batch, int h, int w, IntPtr rows, int onDevice, IntPtr dst);
         // OBB corner labels (Data/YoloDataset.cs:110-129; Utils/Ops.cs:44-54): corners [n, 4, 2] pixels in place of the keypoints, outBboxes [capacity, 5] = (cx, cy, w, h) / imgsz
         // and the angle of the minimum-area rectangle, angle in (0, pi/2], w along the angle (OpenCV >= 4.5.1's form; the choice among equal-area rectangles is unpinned
         // against OpenCV).  boxes [n, 4] alone decides what is kept; flags must be 0.  ys_xyxyxyxy2xywhr is the rectangle on its own: [n, 4, 2] -> [n, 5], pixels and radians.

@@ -650,6 +650,50 @@ YS_API int ys_augment_classify(ys_ctx* ctx, const uint8_t* arena, const ys_aug_s
                                const ys_cls_item* items, int batch, int on_device, int imgsz, const ys_aug_jitter* jitter,
                                float* images, float* out_cls);
 
+/* ---- AutoAugment / RandAugment for the classification input (Data/ClassificationDataset.cs:105-116: with Config.Auto_Augment = AutoAugment, the reference's
+ * default (Data/Config.cs:228), or RandAugment the transform stands between the flips and RandomErasing).  The operators are torchvision's tensor / uint8
+ * path with nearest interpolation and fill = None (out-of-image is 0).  An image brings one ys_aa_row: two slots, run in order, each an op id, its argument
+ * and -- for the affine ops -- torchvision's INVERSE matrix theta, which the host builds in float64 with _get_inverse_affine_matrix(center, angle, translate,
+ * scale = 1, shear) and rounds to fp32: Rotate center [0, 0], angle = -magnitude; ShearX center [-w/2, -h/2], shear [degrees(atan(m)), 0]; ShearY likewise
+ * with the second component; TranslateX / Y translate [int(m), 0] / [0, int(m)], center [0, 0].  Op ids, torchvision's _augmentation_space order:
+ *   -1 none (the slot's probability draw failed, RandAugment's Identity)   0 ShearX  1 ShearY  2 TranslateX  3 TranslateY  4 Rotate   (theta)
+ *    5 Brightness  6 Color (saturation)  7 Contrast  8 Sharpness   (arg = 1 + m)      9 Posterize (arg = bits)  10 Solarize (arg = threshold)
+ *   11 AutoContrast  12 Equalize  13 Invert
+ * Arithmetic, every fp32 operation rounded on its own, divisions correctly rounded (w, h = the image's width and height as fp32):
+ *   affine   r[0..2] = theta[0..2] / (0.5f * w), r[3..5] = theta[3..5] / (0.5f * h); bx = (float)x + (-w * 0.5f + 0.5f), by = (float)y + (-h * 0.5f + 0.5f);
+ *            gx = (bx * r0 + by * r1) + r2, gy = (bx * r3 + by * r4) + r5; ux = ((gx + 1) * w - 1) / 2, uy likewise; ix = nearbyint(ux), iy = nearbyint(uy)
+ *            (half to even); out[y][x] = in[iy][ix] inside the image, 0 outside
+ *   blends   blend(a, b, f) of ys_color_jitter with b = 0 (Brightness), the pixel's gray (Color), the fp32 mean of gray over the image in its state in
+ *            front of THIS op (Contrast; the DEVIATION of ys_color_jitter above 65536 pixels carries over), or the 3 x 3 filter [[1,1,1],[1,5,1],[1,1,1]] / 13
+ *            rounded to nearest on the interior and the input itself on the border row and column (Sharpness; h <= 2 or w <= 2: the image is unchanged).
+ *            The filter's sum S is an integer and S / 13 is never within 1 / 26 of a half, so the byte is (S + 6) / 13 in integers for any summation order.
+ *   Posterize v & -(1 << (8 - bits)), bits = (int)arg in 0 .. 8;   Solarize (float)v >= arg ? 255 - v : v;   Invert 255 - v
+ *   AutoContrast  per channel: scale = (1.0f / (max - min)) * 255.0f (torchvision writes bound / (max - min) with a Python number on top, which torch
+ *                 evaluates as reciprocal() * bound: two roundings, e.g. max - min = 179 gives 1.42458093 where one division gives 1.42458105),
+ *                 (min, scale) = (0, 1) where max == min; trunc(clamp(((float)v - min) * scale, 0, 255))
+ *   Equalize      per channel, in integers: step = (N - hist[last non-empty bin]) / 255 (floor); step == 0 leaves the channel unchanged; else lut[0] = 0,
+ *                 lut[v] = min((cumsum_inclusive[v - 1] + step / 2) / step, 255)
+ * A row is invalid when an op id is outside -1 .. 13, Posterize's bits are outside 0 .. 8, or an arg or theta entry (of either slot, used or not) is not finite.
+ *
+ * ys_auto_augment_ops: the two slots on their own, in uint8 [B, 3, H, W] -> out uint8, any H, W in 1 .. 16384, in and out not overlapping.  A slot is a
+ * statistics launch (histograms in LDS and gray sums, flushed with integer atomics into zeroed per-image rows: deterministic; images whose slot needs none
+ * leave at once; skipped for a host-resident table no row of which needs it) and an apply launch.  Host pointers: the first invalid row is
+ * YS_ERR_INVALID_ARG.  Device pointers: that image is all 114.
+ *
+ * ys_augment_classify_aa: ys_augment_classify with the rows `aa` [batch] (following on_device): crop -> flips -> slot 0 -> slot 1 -> erase -> jitter ->
+ * mul(1 / 255.0f), every stage on the imgsz x imgsz image.  aa == NULL IS ys_augment_classify.  Otherwise crop + flips are staged as uint8
+ * [batch, 3, imgsz, imgsz] in the context's workspace (a quarter of the output's bytes, and a second image to ping-pong), the slots run on them and the
+ * erase + jitter launches read the staged bytes in place of the source: seven launches at most, none per image, and the host never waits.  Invalid rows:
+ * YS_ERR_INVALID_ARG naming the row with host pointers; with device pointers that image is all 114 * (1 / 255.0f), class -1, its neighbours untouched.
+ * UNPINNED: TorchVision.NET's source is not in the reference tree and torchvision is not available to this project's tests: the operator arithmetic
+ * above, the ImageNet policy table and the magnitude spaces (yolosharp_amd/augment.py) are torchvision's public ones as this project restates them
+ * (tests/aa_ref.py, written with torch's own operators); the reference's torch RNG stream cannot be matched in any case.  Not built: AugMix. */
+typedef struct ys_aa_row { int32_t op[2]; float arg[2]; float theta[2][6]; } ys_aa_row;   /* 64 bytes */
+YS_API int ys_augment_classify_aa(ys_ctx* ctx, const uint8_t* arena, const ys_aug_src* srcs, int n_src, const float* src_cls,
+                                  const ys_cls_item* items, int batch, int on_device, int imgsz, const ys_aa_row* aa,
+                                  const ys_aug_jitter* jitter, float* images, float* out_cls);
+YS_API int ys_auto_augment_ops(ys_ctx* ctx, const uint8_t* in, int B, int H, int W, const ys_aa_row* rows, int on_device, uint8_t* out);
+
 /* ---- per-operator entry points (unit parity; a TorchSharp-free C# Conv wrapper) ---------------
  * Convs.Conv.forward (Convs.cs:36-62): y = act(BN(conv2d(x))) on fp32 NCHW / OIHW HOST arrays at the
  * edge (the call stages them through HBM).  training != 0 uses batch statistics and updates running stats (momentum 0.03, eps 1e-3). */

@@ -1,6 +1,7 @@
 """Classification train / eval throughput on one device: prints ONE JSON line.
 
   python tools/cls_bench.py [--family 8|11] [--batch 256] [--size 224] [--nc 1000] [--steps 20] [--warmup 5] [--input resident|device]
+                             [--auto-augment autoaugment|randaugment]
 
 A YOLOv8n-cls (or, with --family 11, YOLOv11n-cls) bf16 train step -- forward, v8ClassificationLoss, backward, AdamW, zero_grad -- on
 synthetic device-resident images and labels, then the eval forward (softmax) and ys_cls_topk(k = 5).  The line holds ms_per_step,
@@ -10,6 +11,9 @@ images/s, eval images/s and, from a few further profiled (untimed) steps, the pe
 "device_input" the ms per ys_augment_classify call with and without contrast rows (items and rows uploaded once, outside the timed loop), the bytes it
 writes per second against the 6.3 TB/s this project measured for HBM, the train step fed from it (draws on the host, upload of items and rows, the gather,
 then the step) beside the resident-tensor step of the same process, and the torch-on-CPU restatement's ms per batch for scale.
+--auto-augment autoaugment | randaugment (with --input device) gives the augmenter that policy (ys_augment_classify_aa): "augment_ms_aa" is the call with the
+drawn ys_aa_row table and contrast rows, "augment_ms_aa_empty_rows" the same call with every slot empty (staging, two copies and the statistics launches that
+leave at once), "aa_active_slots" the share of slots that run an op; the fed train step then includes the policy's draws.
 """
 import argparse
 import json
@@ -37,6 +41,7 @@ def main():
     ap.add_argument("--profile-steps", type=int, default=3)
     ap.add_argument("--input", default="resident", choices=("resident", "device"))
     ap.add_argument("--dataset", type=int, default=512, help="--input device: images of the synthetic uint8 dataset")
+    ap.add_argument("--auto-augment", default=None, choices=("autoaugment", "randaugment"), help="--input device: the augmenter's Auto_Augment policy")
     a = ap.parse_args()
 
     from yolosharp_amd import Engine
@@ -176,17 +181,23 @@ def device_input(a, eng, m, crit, amp, resident_ms):
     shapes = [(256, 256), (256, 341), (341, 256), (256, 384), (288, 512), (300, 400)]
     imgs = [g.integers(0, 256, (3,) + shapes[i % len(shapes)], dtype=np.uint8) for i in range(a.dataset)]
     classes = g.integers(0, nc, a.dataset).astype(np.float32)
-    aug = A.ClassifyAugmenter(eng, imgs, classes, S, seed=0, max_batch=B)
+    policy = {None: None, "autoaugment": A.AutoAugment(), "randaugment": A.RandAugment()}[a.auto_augment]
+    aug = A.ClassifyAugmenter(eng, imgs, classes, S, seed=0, max_batch=B, auto_augment=policy)
     idx = g.integers(0, a.dataset, B)
-    items, rows = aug.draw(idx)
+    drawn = aug.draw(idx)
+    items, rows, aa = drawn if policy is not None else drawn + (None,)
     plain = rows.copy()
     plain["order"][plain["order"] == A.JITTER_CONTRAST] = -1           # the same rows without their contrast op: one launch
 
-    def time_calls(r):
-        aug.run(items, r)                                              # uploads items and rows
+    def time_calls(r, aa_rows=None):
+        aug.run(items, r, aa_rows)                                     # uploads items and rows
         d_jit = aug.d_jitter if r is not None else None
 
         def call():
+            if aa_rows is not None:
+                _lib.check(eng.lib, eng.lib.ys_augment_classify_aa(eng.ctx, aug.d_arena, aug.d_srcs, aug.count, aug.d_src_cls, aug.d_items, B, 1, S, aug.d_aa, d_jit,
+                                                                   aug.d_images, aug.d_ocls))
+                return
             _lib.check(eng.lib, eng.lib.ys_augment_classify(eng.ctx, aug.d_arena, aug.d_srcs, aug.count, aug.d_src_cls, aug.d_items, B, 1, S, d_jit, aug.d_images,
                                                             aug.d_ocls))
         for _ in range(a.warmup):
@@ -199,6 +210,10 @@ def device_input(a, eng, m, crit, amp, resident_ms):
         return (time.perf_counter() - t0) * 1e3 / a.steps
 
     ms_contrast, ms_plain, ms_none = time_calls(rows), time_calls(plain), time_calls(None)
+    aa_out = {}
+    if policy is not None:
+        aa_out = {"auto_augment": a.auto_augment, "augment_ms_aa": round(time_calls(rows, aa), 4),
+                  "augment_ms_aa_empty_rows": round(time_calls(rows, A.make_aa_rows(B)), 4), "aa_active_slots": round(float((aa["op"] >= 0).mean()), 3)}
     written = B * 3 * S * S * 4
 
     def step():
@@ -223,7 +238,7 @@ def device_input(a, eng, m, crit, amp, resident_ms):
     draw_ms = (time.perf_counter() - t0) * 1e3 / 3
     cpu_ms = _cpu_restatement_ms(imgs, items, rows, S)
     aug.close()
-    return {"augment_ms_contrast": round(ms_contrast, 4), "augment_ms_no_contrast": round(ms_plain, 4), "augment_ms_no_jitter": round(ms_none, 4),
+    return {**aa_out, "augment_ms_contrast": round(ms_contrast, 4), "augment_ms_no_contrast": round(ms_plain, 4), "augment_ms_no_jitter": round(ms_none, 4),
             "bytes_written": written, "write_GB/s_contrast": round(written / ms_contrast / 1e6, 1), "write_GB/s_no_contrast": round(written / ms_plain / 1e6, 1),
             "hbm_fraction_contrast": round(written / (ms_contrast * 1e-3) / HBM_BYTES_PER_S, 4),
             "hbm_fraction_no_contrast": round(written / (ms_plain * 1e-3) / HBM_BYTES_PER_S, 4),

@@ -57,6 +57,11 @@ class ClsItem(C.Structure):
                [("er_seed", C.c_uint32)]
 
 
+class AaRow(C.Structure):
+    """ys_aa_row: the AutoAugment / RandAugment draws of one output image: two slots of (op id or -1, argument, inverse affine matrix)."""
+    _fields_ = [("op", C.c_int32 * 2), ("arg", C.c_float * 2), ("theta", (C.c_float * 6) * 2)]
+
+
 class BnFwdCase(C.Structure):
     """ys_bn_fwd_case: one problem of ys_bn_train_fwd (host arrays channel-major [C][rows])."""
     _fields_ = [("y", C.c_void_p), ("gamma", C.c_void_p), ("beta", C.c_void_p), ("run_mean", C.c_void_p), ("run_var", C.c_void_p), ("nbt", C.c_void_p),
@@ -219,6 +224,9 @@ PROTOTYPES = {
     "ys_color_jitter": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int]),
     "ys_augment_classify": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                      C.c_void_p]),
+    "ys_augment_classify_aa": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_void_p]),
+    "ys_auto_augment_ops": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "ys_block_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "ys_block_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "ys_device_malloc": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]),

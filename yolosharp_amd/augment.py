@@ -22,12 +22,17 @@ box alone, the LetterBox pads are not scaled by ratio and that branch clips noth
 The classification input (Data/ClassificationDataset.cs:90-131 with Auto_Augment = None): ClassifyAugmenter uploads the uint8 dataset and the class ids once;
 per batch the host draws what RandomResizedCrop, the two flips, RandomErasing and ColorJitter draw (draw_classify_items; the val chain, Resize + CenterCrop,
 draws nothing: draw_classify_val_items) and ys_augment_classify gathers crop, resize, flips, erase noise, all four jitter ops and mul(1 / 255) in one pass
-(csrc/augment_cls.hip) -> ClassifyDeviceBatch.  Not built: AutoAugment (the reference's default) / RandAugment / AugMix.  TorchVision.NET is not in the
-reference tree: nearest interpolation, smaller-edge Resize(int), CenterCrop's rounding and the crop tries' accept test are torchvision's public ones, UNPINNED.
+(csrc/augment_cls.hip) -> ClassifyDeviceBatch.  Auto_Augment = AutoAugment (the reference's default, Data/Config.cs:228) / RandAugment:
+ClassifyAugmenter(auto_augment=AutoAugment() / RandAugment()) draws one ys_aa_row per image between the flips and the erasing draws (draw_auto_augment: the
+sub-policy, probabilities, signs and magnitudes of torchvision's get_params, the affine ops as their inverse matrix) and ys_augment_classify_aa runs the two
+operator slots on the staged uint8 image (csrc/augment_aa.hip); auto_augment_ops() is the operators on their own.  Not built: AugMix.  TorchVision.NET is not
+in the reference tree: nearest interpolation, smaller-edge Resize(int), CenterCrop's rounding, the crop tries' accept test, the AutoAugment policy table,
+magnitude spaces and operator arithmetic are torchvision's public ones, UNPINNED.
 
 Not built: the `rand > p` case of Augment.Mosaic (it yields images of unequal sizes).
 kpt_dim = 3 only."""
 import ctypes as C
+import functools
 import math
 
 import numpy as np
@@ -42,6 +47,8 @@ assert JITTER_DTYPE.itemsize == C.sizeof(_lib.AugJitter) == 32
 CLS_ITEM_DTYPE = np.dtype([(n, "<i4") for n in ("src", "top", "left", "ch", "cw", "oh", "ow", "oy", "ox", "flip_lr", "flip_ud", "er_y", "er_x", "er_h", "er_w")] +
                           [("er_seed", "<u4")])
 assert CLS_ITEM_DTYPE.itemsize == C.sizeof(_lib.ClsItem) == 64
+AA_ROW_DTYPE = np.dtype([("op", "<i4", (2,)), ("arg", "<f4", (2,)), ("theta", "<f4", (2, 6))])
+assert AA_ROW_DTYPE.itemsize == C.sizeof(_lib.AaRow) == 64
 JITTER_BRIGHTNESS, JITTER_CONTRAST, JITTER_SATURATION, JITTER_HUE = 0, 1, 2, 3      # the op ids of ColorJitter.forward
 YS_AUG_SORT_FLIPPED = 1              # ys_augment_labels: write a flipped box as (min, max)
 YS_AUG_FLIP_KEEP_SIZE = 2            # ys_augment_letterbox_labels: a flip leaves the cxcywh box's w / h alone (the reference writes s - w)
@@ -595,28 +602,33 @@ def _erasing_params(rng, s, p, gate):
 
 
 def draw_classify_items(rng, indices, shapes, s, scale=(0.08, 1.0), ratio=(3 / 4, 4 / 3), fliplr=0.5, flipud=0.0, erasing=0.4, hsv=(0.015, 0.7, 0.4),
-                        erasing_gate="normal"):
+                        erasing_gate="normal", auto_augment=None):
     """The item table of one classification training batch (ClassificationDataset.build_transforms, :95-122, Auto_Augment = None): per index of `indices`,
     from ONE stream in the reference's order, what RandomResizedCrop.get_params draws for the source's shapes[idx] = (H, W) -- ten tries of
     target = H * W * U(scale), aspect = exp(U(log ratio)), accepted iff 0 < w <= W and 0 < h <= H, then top and left; else the centre fallback --
     RandomHorizontalFlip, then RandomVerticalFlip (each drawn only when its p > 0; flip iff rand < p), RandomErasing (only when erasing > 0; its gate is a
     NORMAL draw, `randn > p` skips: at p = 0.4 an image is erased with probability 0.655, kept; erasing_gate = "uniform" gives `rand > p`), and one
-    draw_jitter row with contrast = vgain (only when hsv is not None).  -> (items, jitter rows or None)."""
+    draw_jitter row with contrast = vgain (only when hsv is not None).  -> (items, jitter rows or None).
+    auto_augment = an AutoAugment / RandAugment policy object: the image's ys_aa_row (draw_auto_augment on the s x s image) is drawn in the reference's
+    position, after the flips and in front of the erasing draws (:105-120) -> (items, jitter rows or None, aa rows).  None draws nothing and returns the pair."""
     assert erasing_gate in ("normal", "uniform"), erasing_gate
     s = int(s)
     items = make_classify_items(len(indices))
     rows = make_jitter(len(indices)) if hsv is not None else None
+    aa = make_aa_rows(len(indices)) if auto_augment is not None else None
     for b, idx in enumerate(indices):
         H, W = (int(v) for v in shapes[int(idx)])
         top, left, ch, cw = _resized_crop_params(rng, H, W, scale, ratio)
         flr = fliplr > 0 and rng.random() < fliplr
         fud = flipud > 0 and rng.random() < flipud
+        if auto_augment is not None:
+            aa[b] = draw_auto_augment(rng, 1, (s, s), auto_augment)[0]
         er = _erasing_params(rng, s, erasing, erasing_gate) if erasing > 0 else (0, 0, 0, 0, 0)
         items[b] = (int(idx), top, left, ch, cw, s, s, 0, 0, int(flr), int(fud)) + er
         if hsv is not None:
             hgain, sgain, vgain = hsv
             rows[b] = draw_jitter(rng, 1, hgain, sgain, vgain, cgain=vgain)[0]
-    return items, rows
+    return (items, rows) if auto_augment is None else (items, rows, aa)
 
 
 def draw_classify_val_items(indices, shapes, s):
@@ -631,8 +643,193 @@ def draw_classify_val_items(indices, shapes, s):
     return items
 
 
-def augment_classify(engine, arena, srcs, src_cls, items, imgsz, jitter=None):
-    """ys_augment_classify on HOST arrays: -> (images fp32 [B, 3, s, s], cls fp32 [B])."""
+# ---------------------------------------------------------------------------------------------------- AutoAugment / RandAugment
+# torchvision.transforms.AutoAugment / RandAugment (autoaugment.py) as the host's draws: the op ids are _augmentation_space's order, -1 = nothing.
+AA_OPS = ("ShearX", "ShearY", "TranslateX", "TranslateY", "Rotate", "Brightness", "Color", "Contrast", "Sharpness", "Posterize", "Solarize", "AutoContrast",
+          "Equalize", "Invert")
+AA_ID = {name: i for i, name in enumerate(AA_OPS)}
+AA_NONE = -1
+AA_SIGNED = frozenset(("ShearX", "ShearY", "TranslateX", "TranslateY", "Rotate", "Brightness", "Color", "Contrast", "Sharpness"))
+# AutoAugmentPolicy.IMAGENET: ((op, p, magnitude id or None), (op, p, magnitude id or None)); the last five repeat earlier rows, as in torchvision
+IMAGENET_POLICY = (
+    (("Posterize", 0.4, 8), ("Rotate", 0.6, 9)), (("Solarize", 0.6, 5), ("AutoContrast", 0.6, None)), (("Equalize", 0.8, None), ("Equalize", 0.6, None)),
+    (("Posterize", 0.6, 7), ("Posterize", 0.6, 6)), (("Equalize", 0.4, None), ("Solarize", 0.2, 4)), (("Equalize", 0.4, None), ("Rotate", 0.8, 8)),
+    (("Solarize", 0.6, 3), ("Equalize", 0.6, None)), (("Posterize", 0.8, 5), ("Equalize", 1.0, None)), (("Rotate", 0.2, 3), ("Solarize", 0.6, 8)),
+    (("Equalize", 0.6, None), ("Posterize", 0.4, 6)), (("Rotate", 0.8, 8), ("Color", 0.4, 0)), (("Rotate", 0.4, 9), ("Equalize", 0.6, None)),
+    (("Equalize", 0.0, None), ("Equalize", 0.8, None)), (("Invert", 0.6, None), ("Equalize", 1.0, None)), (("Color", 0.6, 4), ("Contrast", 1.0, 8)),
+    (("Rotate", 0.8, 8), ("Color", 1.0, 2)), (("Color", 0.8, 8), ("Solarize", 0.8, 7)), (("Sharpness", 0.4, 7), ("Invert", 0.6, None)),
+    (("ShearX", 0.6, 5), ("Equalize", 1.0, None)), (("Color", 0.4, 0), ("Equalize", 0.6, None)), (("Equalize", 0.4, None), ("Solarize", 0.2, 4)),
+    (("Solarize", 0.6, 5), ("AutoContrast", 0.6, None)), (("Invert", 0.6, None), ("Equalize", 1.0, None)), (("Color", 0.6, 4), ("Contrast", 1.0, 8)),
+    (("Equalize", 0.8, None), ("Equalize", 0.6, None)))
+RAND_AUGMENT_OPS = ("Identity", "ShearX", "ShearY", "TranslateX", "TranslateY", "Rotate", "Brightness", "Color", "Contrast", "Sharpness", "Posterize", "Solarize",
+                    "AutoContrast", "Equalize")
+
+
+class AutoAugment:
+    """torchvision.transforms.AutoAugment(AutoAugmentPolicy.IMAGENET), what the reference appends for Auto_Augment = AutoAugment
+    (Data/ClassificationDataset.cs:105-116): one of 25 sub-policies per image, two ops each with a probability and one of 10 magnitude bins."""
+    bins = 10
+
+    def __init__(self, policy=IMAGENET_POLICY):
+        self.policy = tuple(policy)
+        assert all(len(row) == 2 and all(op in AA_ID and (m is None or 0 <= m < self.bins) for op, _, m in row) for row in self.policy)
+
+
+class RandAugment:
+    """torchvision.transforms.RandAugment(num_ops, magnitude, num_magnitude_bins): num_ops ops drawn uniformly from RAND_AUGMENT_OPS, every one at bin
+    `magnitude` of `bins`.  A ys_aa_row has two slots: num_ops is 1 or 2."""
+
+    def __init__(self, num_ops=2, magnitude=9, bins=31):
+        if num_ops not in (1, 2):
+            raise ValueError("RandAugment(num_ops=%r): an image has two operator slots, num_ops must be 1 or 2" % (num_ops,))
+        if not 0 <= int(magnitude) < int(bins):
+            raise ValueError("RandAugment(magnitude=%r, bins=%r): the magnitude is a bin index" % (magnitude, bins))
+        self.num_ops, self.magnitude, self.bins = int(num_ops), int(magnitude), int(bins)
+
+
+def _linspace_f32(start, end, steps):
+    """torch.linspace(start, end, steps) in fp32: step = (end - start) / (steps - 1) rounded to fp32; the first half counts up from start, the second down
+    from end, each value ONE fused multiply-add (the product exact, one rounding) as torch's CPU kernel computes it."""
+    f = np.float32
+    start, end = f(start), f(end)
+    step = np.float64((end - start) / f(steps - 1))
+    i = np.arange(steps)
+    return np.where(i < steps // 2, np.float64(start) + step * i, np.float64(end) - step * (steps - 1 - i)).astype(f)
+
+
+def aa_magnitudes(op, bins, h, w):
+    """_augmentation_space(bins, (h, w))[op] as Python floats (the fp32 linspace value, then float), or None for an op without a magnitude."""
+    m = _aa_magnitudes(op, int(bins), int(h), int(w))
+    return list(m) if m is not None else None
+
+
+@functools.lru_cache(maxsize=None)
+def _aa_magnitudes(op, bins, h, w):
+    if op in ("ShearX", "ShearY"):
+        m = _linspace_f32(0.0, 0.3, bins)
+    elif op == "TranslateX":
+        m = _linspace_f32(0.0, 150.0 / 331.0 * w, bins)
+    elif op == "TranslateY":
+        m = _linspace_f32(0.0, 150.0 / 331.0 * h, bins)
+    elif op == "Rotate":
+        m = _linspace_f32(0.0, 30.0, bins)
+    elif op in ("Brightness", "Color", "Contrast", "Sharpness"):
+        m = _linspace_f32(0.0, 0.9, bins)
+    elif op == "Posterize":
+        m = 8 - np.rint(np.arange(bins, dtype=np.float32) / np.float32((bins - 1) / 4)).astype(np.int32)      # torch.round: half to even, like rint
+    elif op == "Solarize":
+        m = _linspace_f32(255.0, 0.0, bins)
+    else:
+        return None
+    return tuple(float(v) for v in m)
+
+
+def inverse_affine_matrix(center, angle, translate, scale, shear):
+    """torchvision.transforms.functional._get_inverse_affine_matrix in Python floats: the six entries of the inverse of
+    T * C * RotateScaleShear * C^-1 (angles in degrees)."""
+    rot, sx, sy = math.radians(angle), math.radians(shear[0]), math.radians(shear[1])
+    cx, cy = center
+    tx, ty = translate
+    a = math.cos(rot - sy) / math.cos(sy)
+    b = -math.cos(rot - sy) * math.tan(sx) / math.cos(sy) - math.sin(rot)
+    c = math.sin(rot - sy) / math.cos(sy)
+    d = -math.sin(rot - sy) * math.tan(sx) / math.cos(sy) + math.cos(rot)
+    m = [d, -b, 0.0, -c, a, 0.0]
+    m = [x / scale for x in m]
+    m[2] += m[0] * (-cx - tx) + m[1] * (-cy - ty)
+    m[5] += m[3] * (-cx - tx) + m[4] * (-cy - ty)
+    m[2] += cx
+    m[5] += cy
+    return m
+
+
+def make_aa_rows(n):
+    """n rows with both slots empty (op -1, identity theta)."""
+    rows = np.zeros((n,), AA_ROW_DTYPE)
+    rows["op"] = AA_NONE
+    rows["theta"][:] = (1.0, 0.0, 0.0, 0.0, 1.0, 0.0)
+    return rows
+
+
+def set_aa_slot(row, k, op, magnitude, hw):
+    """Slot k of one row = torchvision's _apply_op(img, op, magnitude) on an image of hw = (h, w): the op id, its argument (1 + m for the blends, the
+    bits for Posterize, the threshold for Solarize) and, for the affine ops, the inverse matrix rounded to fp32.  op None / "Identity": nothing."""
+    h, w = hw
+    row["op"][k], row["arg"][k], row["theta"][k] = AA_NONE, 0.0, (1.0, 0.0, 0.0, 0.0, 1.0, 0.0)
+    if op is None or op == "Identity":
+        return
+    row["op"][k] = AA_ID[op]
+    m = float(magnitude)
+    if op == "ShearX":
+        row["theta"][k] = inverse_affine_matrix([-w * 0.5, -h * 0.5], 0.0, [0.0, 0.0], 1.0, [math.degrees(math.atan(m)), 0.0])
+    elif op == "ShearY":
+        row["theta"][k] = inverse_affine_matrix([-w * 0.5, -h * 0.5], 0.0, [0.0, 0.0], 1.0, [0.0, math.degrees(math.atan(m))])
+    elif op == "TranslateX":
+        row["theta"][k] = inverse_affine_matrix([0.0, 0.0], 0.0, [1.0 * int(m), 0.0], 1.0, [0.0, 0.0])
+    elif op == "TranslateY":
+        row["theta"][k] = inverse_affine_matrix([0.0, 0.0], 0.0, [0.0, 1.0 * int(m)], 1.0, [0.0, 0.0])
+    elif op == "Rotate":
+        row["theta"][k] = inverse_affine_matrix([0.0, 0.0], -m, [0.0, 0.0], 1.0, [0.0, 0.0])
+    elif op in ("Brightness", "Color", "Contrast", "Sharpness"):
+        row["arg"][k] = 1.0 + m
+    elif op == "Posterize":
+        row["arg"][k] = int(m)
+    elif op == "Solarize":
+        row["arg"][k] = m
+
+
+def check_aa_rows(rows):
+    """The library's row check (include/yolosharp_hip.h ys_aa_row) on the host: ValueError naming the first invalid row."""
+    rows = np.ascontiguousarray(rows, AA_ROW_DTYPE)
+    ok = ((rows["op"] >= AA_NONE) & (rows["op"] <= 13)).all(axis=1) & np.isfinite(rows["arg"]).all(axis=1) & np.isfinite(rows["theta"]).all(axis=(1, 2))
+    ok &= ((rows["op"] != AA_ID["Posterize"]) | ((rows["arg"] >= 0) & (rows["arg"] <= 8))).all(axis=1)
+    if not ok.all():
+        b = int(np.argmin(ok))
+        raise ValueError("aa row %d is invalid: op %s arg %s theta %s" % (b, rows[b]["op"].tolist(), rows[b]["arg"].tolist(), rows[b]["theta"].tolist()))
+    return rows
+
+
+def draw_auto_augment(rng, n, hw, policy):
+    """n ys_aa_row for images of hw = (h, w), per image in torchvision's draw order.  AutoAugment.get_params: one sub-policy index, two uniform
+    probabilities, two sign bits; slot i runs iff prob[i] <= p; a signed magnitude is negated iff its sign bit is 0.  RandAugment.forward: per op one
+    index into RAND_AUGMENT_OPS, then -- only for a signed op -- one bit; the magnitude is negated iff the bit is 1."""
+    rows = make_aa_rows(n)
+    for b in range(n):
+        if isinstance(policy, AutoAugment):
+            pid = int(rng.integers(len(policy.policy)))
+            probs = rng.random(2)
+            signs = rng.integers(0, 2, 2)
+            for k, (op, p, mid) in enumerate(policy.policy[pid]):
+                if probs[k] <= p:
+                    m = _aa_magnitudes(op, policy.bins, int(hw[0]), int(hw[1]))[mid] if mid is not None else 0.0
+                    if op in AA_SIGNED and int(signs[k]) == 0:
+                        m *= -1.0
+                    set_aa_slot(rows[b], k, op, m, hw)
+        elif isinstance(policy, RandAugment):
+            for k in range(policy.num_ops):
+                op = RAND_AUGMENT_OPS[int(rng.integers(len(RAND_AUGMENT_OPS)))]
+                mags = _aa_magnitudes(op, policy.bins, int(hw[0]), int(hw[1]))
+                m = mags[policy.magnitude] if mags is not None else 0.0
+                if op in AA_SIGNED and int(rng.integers(0, 2)):
+                    m *= -1.0
+                set_aa_slot(rows[b], k, op, m, hw)
+        else:
+            raise TypeError("auto_augment policy %r: pass augment.AutoAugment() or augment.RandAugment()" % (policy,))
+    return rows
+
+
+def auto_augment_ops(engine, images_u8, rows):
+    """ys_auto_augment_ops on HOST arrays: uint8 [B, 3, h, w] through the two slots of each image's row -> uint8 [B, 3, h, w]."""
+    img = np.ascontiguousarray(images_u8, np.uint8)
+    rows = np.ascontiguousarray(rows, AA_ROW_DTYPE)
+    assert img.ndim == 4 and img.shape[1] == 3 and rows.shape == (img.shape[0],), (img.shape, rows.shape)
+    out = np.empty_like(img)
+    _lib.check(engine.lib, engine.lib.ys_auto_augment_ops(engine.ctx, _ptr(img), img.shape[0], img.shape[2], img.shape[3], _ptr(rows), 0, _ptr(out)))
+    return out
+
+
+def augment_classify(engine, arena, srcs, src_cls, items, imgsz, jitter=None, aa=None):
+    """ys_augment_classify (aa = None) / ys_augment_classify_aa (aa = the batch's ys_aa_row table) on HOST arrays: -> (images fp32 [B, 3, s, s], cls fp32 [B])."""
     arena = np.ascontiguousarray(arena, np.uint8)
     srcs, items = np.ascontiguousarray(srcs, SRC_DTYPE), np.ascontiguousarray(items, CLS_ITEM_DTYPE)
     src_cls = np.ascontiguousarray(src_cls, np.float32).reshape(-1)
@@ -642,6 +839,12 @@ def augment_classify(engine, arena, srcs, src_cls, items, imgsz, jitter=None):
         jitter = np.ascontiguousarray(jitter, JITTER_DTYPE)
         assert jitter.shape == (B,), jitter.shape
     images, cls = np.empty((B, 3, max(s, 0), max(s, 0)), np.float32), np.empty((B,), np.float32)
+    if aa is not None:
+        aa = np.ascontiguousarray(aa, AA_ROW_DTYPE)
+        assert aa.shape == (B,), aa.shape
+        _lib.check(engine.lib, engine.lib.ys_augment_classify_aa(engine.ctx, _ptr(arena), _ptr(srcs), srcs.shape[0], _ptr(src_cls), _ptr(items), B, 0, s, _ptr(aa),
+                                                                 _ptr(jitter), _ptr(images), _ptr(cls)))
+        return images, cls
     _lib.check(engine.lib, engine.lib.ys_augment_classify(engine.ctx, _ptr(arena), _ptr(srcs), srcs.shape[0], _ptr(src_cls), _ptr(items), B, 0, s, _ptr(jitter),
                                                           _ptr(images), _ptr(cls)))
     return images, cls
@@ -665,14 +868,16 @@ class ClassifyAugmenter:
     """ClassificationDataset's input on the device.  The dataset -- uint8 RGB planes [3, h, w] of any sizes and one class id per image -- is uploaded ONCE;
     a batch uploads its 64-byte items and 32-byte jitter rows only and is one fused gather (ys_augment_classify).  draw() follows draw_classify_items from
     one numpy Generator; val_batches() walks the dataset in order through the val chain.  The output buffers are reused by the next batch.
-    erasing = 0 and hsv = None each skip their draws.  auto_augment: only None is built (the reference's default is AutoAugment): anything else raises
-    NotImplementedError.  close_mosaic() does nothing -- ClassificationDataset.CloseMosaic is empty -- so Trainer.fit(..., augmenter=this) works unchanged."""
+    erasing = 0 and hsv = None each skip their draws.  auto_augment: None, AutoAugment() (the reference's default) or RandAugment(...) -- a policy OBJECT,
+    like the transform the reference appends; then a batch also uploads one 64-byte ys_aa_row per image and runs ys_augment_classify_aa.  A string raises
+    NotImplementedError (AugMix has no object: it is not built).  close_mosaic() does nothing -- ClassificationDataset.CloseMosaic is empty -- so Trainer.fit(..., augmenter=this) works unchanged."""
 
     def __init__(self, engine, images_u8, classes, imgsz, scale=(0.08, 1.0), ratio=(3 / 4, 4 / 3), fliplr=0.5, flipud=0.0, erasing=0.4, hsv=(0.015, 0.7, 0.4),
                  auto_augment=None, seed=0, max_batch=64, erasing_gate="normal"):
-        if auto_augment is not None:
-            raise NotImplementedError("auto_augment=%r: AutoAugment / RandAugment / AugMix are not built; this is the reference's chain with Auto_Augment = None"
-                                      % (auto_augment,))
+        if auto_augment is not None and not isinstance(auto_augment, (AutoAugment, RandAugment)):
+            raise NotImplementedError("auto_augment=%r: pass a policy object, augment.AutoAugment() or augment.RandAugment(num_ops, magnitude, bins); AugMix is "
+                                      "not built" % (auto_augment,))
+        self.auto_augment = auto_augment
         assert len(images_u8) == len(classes) and len(images_u8) >= 1
         self.engine, self.s = engine, int(imgsz)
         self.scale, self.ratio = tuple(float(v) for v in scale), tuple(float(v) for v in ratio)
@@ -688,9 +893,10 @@ class ClassifyAugmenter:
         self.d_arena, self.d_srcs, self.d_src_cls = e.to_device(arena), e.to_device(self.srcs), e.to_device(self.classes)
         self.d_items, self.d_jitter = e.malloc(B * CLS_ITEM_DTYPE.itemsize), e.malloc(B * JITTER_DTYPE.itemsize)
         self.d_images, self.d_ocls = e.malloc(B * 3 * s * s * 4), e.malloc(B * 4)
+        self.d_aa = e.malloc(B * AA_ROW_DTYPE.itemsize) if auto_augment is not None else None
 
     def close(self):
-        for name in ("d_arena", "d_srcs", "d_src_cls", "d_items", "d_jitter", "d_images", "d_ocls"):
+        for name in ("d_arena", "d_srcs", "d_src_cls", "d_items", "d_jitter", "d_aa", "d_images", "d_ocls"):
             p = getattr(self, name, None)
             if p is not None:
                 self.engine.free(p)
@@ -700,13 +906,13 @@ class ClassifyAugmenter:
         """ClassificationDataset.CloseMosaic is empty: nothing changes."""
 
     def draw(self, indices):
-        """(items, jitter rows or None) of one training batch for the dataset indices `indices`."""
+        """(items, jitter rows or None) of one training batch for the dataset indices `indices`; with an auto_augment policy (items, rows, aa rows)."""
         return draw_classify_items(self.rng, indices, self.shapes, self.s, self.scale, self.ratio, self.fliplr, self.flipud, self.erasing, self.hsv,
-                                   self.erasing_gate)
+                                   self.erasing_gate, self.auto_augment)
 
-    def run(self, items, rows=None, mode="train"):
-        """Validate on the host (the device cannot refuse aloud), upload `items` (and the jitter rows; None = no jitter) and launch on the engine's stream
-        (asynchronous) -> ClassifyDeviceBatch."""
+    def run(self, items, rows=None, aa=None, mode="train"):
+        """Validate on the host (the device cannot refuse aloud), upload `items` (the jitter rows; None = no jitter; the AutoAugment rows `aa`; None = none)
+        and launch on the engine's stream (asynchronous) -> ClassifyDeviceBatch."""
         e, lib = self.engine, self.engine.lib
         items = check_classify_items(items, self.srcs, self.s)
         B = int(items.shape[0])
@@ -719,6 +925,16 @@ class ClassifyAugmenter:
                 raise ValueError("%d jitter rows for %d items" % (rows.shape[0], B))
             _lib.check(lib, lib.ys_memcpy_h2d(e.ctx, self.d_jitter, _ptr(rows), rows.nbytes))
             d_jit = self.d_jitter
+        if aa is not None:
+            aa = check_aa_rows(aa)
+            if aa.shape != (B,):
+                raise ValueError("%d aa rows for %d items" % (aa.shape[0], B))
+            if self.d_aa is None:
+                self.d_aa = e.malloc(self.max_batch * AA_ROW_DTYPE.itemsize)
+            _lib.check(lib, lib.ys_memcpy_h2d(e.ctx, self.d_aa, _ptr(aa), aa.nbytes))
+            _lib.check(lib, lib.ys_augment_classify_aa(e.ctx, self.d_arena, self.d_srcs, self.count, self.d_src_cls, self.d_items, B, 1, self.s, self.d_aa, d_jit,
+                                                       self.d_images, self.d_ocls))
+            return ClassifyDeviceBatch(e, B, self.s, self.d_images, self.d_ocls, mode=mode)
         _lib.check(lib, lib.ys_augment_classify(e.ctx, self.d_arena, self.d_srcs, self.count, self.d_src_cls, self.d_items, B, 1, self.s, d_jit, self.d_images,
                                                 self.d_ocls))
         return ClassifyDeviceBatch(e, B, self.s, self.d_images, self.d_ocls, mode=mode)
@@ -739,4 +955,4 @@ class ClassifyAugmenter:
         """The whole dataset in order through the val chain (Resize + CenterCrop), `batch_size` at a time, the last batch short."""
         for i in range(0, self.count, batch_size):
             idx = np.arange(i, min(i + batch_size, self.count))
-            yield self.run(draw_classify_val_items(idx, self.shapes, self.s), None, mode="val")
+            yield self.run(draw_classify_val_items(idx, self.shapes, self.s), None, None, mode="val")

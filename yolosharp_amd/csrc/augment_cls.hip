@@ -1,5 +1,6 @@
 // augment_cls.hip -- the classification training and validation input on the device: ClassificationDataset's chain with Auto_Augment = None
-// (Data/ClassificationDataset.cs:90-131, GetTensor :70-88) as ONE fused gather per batch.  No cropped, resized or uint8 intermediate image exists.
+// (Data/ClassificationDataset.cs:90-131, GetTensor :70-88) as ONE fused gather per batch: no cropped, resized or uint8 intermediate image exists -- and
+// with AutoAugment / RandAugment rows the same chain around the operator slots of augment_aa.hip (the last paragraph below).
 //
 //   train: RandomResizedCrop(imgsz, scale, ratio) (:95) -> RandomHorizontalFlip (:98) -> RandomVerticalFlip (:102) -> RandomErasing (:120, the
 //          reference's own class :166-226) -> ColorJitter(vgain, vgain, sgain, hgain) (:122) -> mul(1 / 255.0f) (:79)
@@ -35,9 +36,17 @@
 // A thread takes four consecutive output x of one row and writes three 16-byte stores (s % 4 == 0 and an aligned base; scalar stores otherwise), as
 // aug_letterbox_kernel does; blockIdx.z is the image.
 // A refused item or jitter row (aug_cls_item_ok; aug_jitter_state == 0) gives the all-114 image, not jittered, and class -1.
+//
+// Auto_Augment = AutoAugment / RandAugment (:105-116; ys_augment_classify_aa with rows): the two operator slots stand between the flips and the erase and
+// need the whole image (histograms, means, warps, a stencil), so that chain has intermediates -- the plain one keeps none:
+//   aug_cls_stage_kernel          crop + flips of every image as uint8 [B, 3, s, s] in the context's workspace (a quarter of the output's bytes)
+//   augment_aa.hip                slot 0 into a second such image, slot 1 back into the first (a statistics and an apply launch each)
+//   aug_cls_gray_sum_kernel<true> / aug_cls_apply_kernel<true>   the two launches above with the staged bytes in place of the source gather (STAGED): the
+//                                 erase rectangle, the noise, the jitter and the stores are the same code.  A refused ys_aa_row refuses the image too.
 #include "ys_internal.h"
 #include "ys_kernels.h"
 #include "aug_jitter.h"
+#include "aug_aa.h"
 #include <cmath>
 
 #define AUGC_T 256
@@ -92,13 +101,21 @@ __device__ __forceinline__ AugClsGeom aug_cls_geom(const unsigned char* __restri
   return g;
 }
 
-// the quad's four pixels at (x0 .. x0 + 3, y) after gather and erase: three bytes each as fp32; positions at or past s stay 114 and are never stored
-__device__ __forceinline__ void aug_cls_quad(const AugClsGeom& g, int s, int x0, int y, AugPx& p0, AugPx& p1, AugPx& p2, AugPx& p3) {
+// the quad's four pixels at (x0 .. x0 + 3, y) after gather and erase: three bytes each as fp32; positions at or past s stay 114 and are never stored.
+// STAGED: the bytes outside the erase rectangle come from `staged`, the image's uint8 [3, s, s] planes (crop and flips done, the AutoAugment slots run)
+template <bool STAGED>
+__device__ __forceinline__ void aug_cls_quad(const AugClsGeom& g, const unsigned char* __restrict__ staged, int s, int x0, int y, AugPx& p0, AugPx& p1,
+                                             AugPx& p2, AugPx& p3) {
   float v[3][4];
-  const int ly = g.fud ? s - 1 - y : y;
-  int iy = (int)floorf((float)(ly + g.oy) * g.sy);
-  iy = iy < g.ch - 1 ? iy : g.ch - 1;
-  const unsigned char* __restrict__ row = g.base + (long long)iy * g.W;
+  const unsigned char* __restrict__ row;
+  if (STAGED) {
+    row = staged + (long long)y * s;
+  } else {
+    const int ly = g.fud ? s - 1 - y : y;
+    int iy = (int)floorf((float)(ly + g.oy) * g.sy);
+    iy = iy < g.ch - 1 ? iy : g.ch - 1;
+    row = g.base + (long long)iy * g.W;
+  }
   const bool er_row = y >= g.er_y0 && y < g.er_y1;
 #pragma unroll
   for (int j = 0; j < 4; j++) {
@@ -109,6 +126,9 @@ __device__ __forceinline__ void aug_cls_quad(const AugClsGeom& g, int s, int x0,
         const unsigned pix = (unsigned)y * (unsigned)s + (unsigned)x;
 #pragma unroll
         for (int c = 0; c < 3; c++) v[c][j] = aug_cls_noise(g.seed, (unsigned)c, pix);
+      } else if (STAGED) {
+#pragma unroll
+        for (int c = 0; c < 3; c++) v[c][j] = (float)row[(long long)c * s * s + x];
       } else {
         const int lx = g.flr ? s - 1 - x : x;
         int ix = (int)floorf((float)(lx + g.ox) * g.sx);
@@ -122,15 +142,48 @@ __device__ __forceinline__ void aug_cls_quad(const AugClsGeom& g, int s, int x0,
   p2.c0 = v[0][2]; p2.c1 = v[1][2]; p2.c2 = v[2][2]; p3.c0 = v[0][3]; p3.c1 = v[1][3]; p3.c2 = v[2][3];
 }
 
-// contrast, launch 1 of 2: sums[b] += the gray bytes of output image b in its state in front of the contrast op
+// AutoAugment, launch 1: crop + flips of every image as uint8 [B, 3, s, s] -- what the slots read; no erase, no jitter.  A refused item stages 114
+__global__ void __launch_bounds__(AUGC_T)
+aug_cls_stage_kernel(const unsigned char* __restrict__ arena, const ys_aug_src* __restrict__ srcs, int n_src, const ys_cls_item* __restrict__ items, int s,
+                     int vec, unsigned char* __restrict__ staged) {
+  const ys_cls_item& it = items[blockIdx.z];
+  const int qpr = (s + 3) >> 2;
+  const unsigned i = blockIdx.x * AUGC_T + threadIdx.x;
+  if (i >= (unsigned)qpr * (unsigned)s) return;
+  const int y = (int)(i / (unsigned)qpr), x0 = (int)(i - (unsigned)y * (unsigned)qpr) * 4;
+  AugPx p[4];
+  p[0].c0 = p[0].c1 = p[0].c2 = 114.0f; p[1] = p[0]; p[2] = p[0]; p[3] = p[0];
+  if (aug_cls_item_ok(it, srcs, n_src, s)) {
+    AugClsGeom g = aug_cls_geom(arena, srcs[it.src], it);
+    g.er_y0 = g.er_y1 = g.er_x0 = g.er_x1 = 0;                 // the erase comes after the slots
+    aug_cls_quad<false>(g, nullptr, s, x0, y, p[0], p[1], p[2], p[3]);
+  }
+  const long long plane = (long long)s * s;
+  unsigned char* dst = staged + (long long)blockIdx.z * 3 * plane + (long long)y * s + x0;
+  if (vec) {
+    *(unsigned*)dst = (unsigned)p[0].c0 | ((unsigned)p[1].c0 << 8) | ((unsigned)p[2].c0 << 16) | ((unsigned)p[3].c0 << 24);
+    *(unsigned*)(dst + plane) = (unsigned)p[0].c1 | ((unsigned)p[1].c1 << 8) | ((unsigned)p[2].c1 << 16) | ((unsigned)p[3].c1 << 24);
+    *(unsigned*)(dst + 2 * plane) = (unsigned)p[0].c2 | ((unsigned)p[1].c2 << 8) | ((unsigned)p[2].c2 << 16) | ((unsigned)p[3].c2 << 24);
+  } else {
+    for (int j = 0; j < 4 && x0 + j < s; j++) {
+      dst[j] = (unsigned char)p[j].c0; dst[plane + j] = (unsigned char)p[j].c1; dst[2 * plane + j] = (unsigned char)p[j].c2;
+    }
+  }
+}
+
+// contrast, launch 1 of 2: sums[b] += the gray bytes of output image b in its state in front of the contrast op.  STAGED (the AutoAugment chain): the
+// bytes come from `staged` and a refused ys_aa_row refuses the image
+template <bool STAGED>
 __global__ void __launch_bounds__(AUGC_T)
 aug_cls_gray_sum_kernel(const unsigned char* __restrict__ arena, const ys_aug_src* __restrict__ srcs, int n_src, const ys_cls_item* __restrict__ items,
-                        const ys_aug_jitter* __restrict__ jitter, int s, unsigned long long* __restrict__ sums) {
+                        const ys_aug_jitter* __restrict__ jitter, int s, unsigned long long* __restrict__ sums, const unsigned char* __restrict__ staged,
+                        const ys_aa_row* __restrict__ aa) {
   __shared__ unsigned s_red[AUGC_T];
   const ys_aug_jitter* __restrict__ J = jitter + blockIdx.z;
   if (aug_jitter_state(*J) != 2) return;                  // wave-uniform, block-uniform
   const ys_cls_item& it = items[blockIdx.z];
   if (!aug_cls_item_ok(it, srcs, n_src, s)) return;
+  if (STAGED && !aug_aa_row_ok(aa[blockIdx.z])) return;
   const int qpr = (s + 3) >> 2;
   const unsigned i = blockIdx.x * AUGC_T + threadIdx.x;
   unsigned sum = 0;
@@ -138,7 +191,7 @@ aug_cls_gray_sum_kernel(const unsigned char* __restrict__ arena, const ys_aug_sr
     const int y = (int)(i / (unsigned)qpr), x0 = (int)(i - (unsigned)y * (unsigned)qpr) * 4;
     const AugClsGeom g = aug_cls_geom(arena, srcs[it.src], it);
     AugPx p0, p1, p2, p3;
-    aug_cls_quad(g, s, x0, y, p0, p1, p2, p3);
+    aug_cls_quad<STAGED>(g, STAGED ? staged + (long long)blockIdx.z * 3 * s * s : nullptr, s, x0, y, p0, p1, p2, p3);
     aug_jitter_quad(J, 0.0f, true, p0, p1, p2, p3);
     sum = (unsigned)aug_jit_gray(p0);
     if (x0 + 1 < s) sum += (unsigned)aug_jit_gray(p1);
@@ -155,15 +208,17 @@ aug_cls_gray_sum_kernel(const unsigned char* __restrict__ arena, const ys_aug_sr
 }
 
 // launch 2 of 2 (the only one for a batch without contrast rows): the whole chain, the fp32 image and the image's class id
+template <bool STAGED>
 __global__ void __launch_bounds__(AUGC_T)
 aug_cls_apply_kernel(const unsigned char* __restrict__ arena, const ys_aug_src* __restrict__ srcs, int n_src, const float* __restrict__ src_cls,
                      const ys_cls_item* __restrict__ items, const ys_aug_jitter* __restrict__ jitter, int s, int vec,
-                     const unsigned long long* __restrict__ sums, float* __restrict__ images, float* __restrict__ out_cls) {
+                     const unsigned long long* __restrict__ sums, float* __restrict__ images, float* __restrict__ out_cls,
+                     const unsigned char* __restrict__ staged, const ys_aa_row* __restrict__ aa) {
   // wave-uniform: the item, its jitter row and whether the image is refused
   const ys_cls_item& it = items[blockIdx.z];
   const ys_aug_jitter* __restrict__ J = jitter ? jitter + blockIdx.z : nullptr;
   const int jstate = J ? aug_jitter_state(*J) : 1;
-  const bool ok = jstate != 0 && aug_cls_item_ok(it, srcs, n_src, s);
+  const bool ok = jstate != 0 && aug_cls_item_ok(it, srcs, n_src, s) && (!STAGED || aug_aa_row_ok(aa[blockIdx.z]));
   if (blockIdx.x == 0 && threadIdx.x == 0) out_cls[blockIdx.z] = ok ? src_cls[it.src] : -1.0f;
   const int qpr = (s + 3) >> 2;
   const unsigned i = blockIdx.x * AUGC_T + threadIdx.x;
@@ -172,7 +227,7 @@ aug_cls_apply_kernel(const unsigned char* __restrict__ arena, const ys_aug_src* 
   AugPx p0, p1, p2, p3;
   if (ok) {
     const AugClsGeom g = aug_cls_geom(arena, srcs[it.src], it);
-    aug_cls_quad(g, s, x0, y, p0, p1, p2, p3);
+    aug_cls_quad<STAGED>(g, STAGED ? staged + (long long)blockIdx.z * 3 * s * s : nullptr, s, x0, y, p0, p1, p2, p3);
     if (J) {
       const float mean = jstate == 2 ? (float)sums[blockIdx.z] / (float)((long long)s * s) : 0.0f;
       aug_jitter_quad(J, mean, false, p0, p1, p2, p3);
@@ -204,8 +259,29 @@ int ys_aug_classify_launch(hipStream_t st, const unsigned char* arena, const ys_
                            int B, int s, const ys_aug_jitter* jitter, int with_contrast, void* sums, float* images, float* out_cls) {
   const long quads = (long)((s + 3) / 4) * s;
   const dim3 grid(ys_cdiv(quads, AUGC_T), 1, B);
-  if (jitter && with_contrast) YS_LAUNCH(aug_cls_gray_sum_kernel, grid, AUGC_T, st, arena, srcs, n_src, items, jitter, s, (unsigned long long*)sums);
-  YS_LAUNCH(aug_cls_apply_kernel, grid, AUGC_T, st, arena, srcs, n_src, src_cls, items, jitter, s, (s % 4 == 0 && ((size_t)images & 15) == 0) ? 1 : 0,
-            (const unsigned long long*)sums, images, out_cls);
+  const unsigned char* no_stage = nullptr;
+  const ys_aa_row* no_aa = nullptr;
+  if (jitter && with_contrast)
+    YS_LAUNCH(aug_cls_gray_sum_kernel<false>, grid, AUGC_T, st, arena, srcs, n_src, items, jitter, s, (unsigned long long*)sums, no_stage, no_aa);
+  YS_LAUNCH(aug_cls_apply_kernel<false>, grid, AUGC_T, st, arena, srcs, n_src, src_cls, items, jitter, s, (s % 4 == 0 && ((size_t)images & 15) == 0) ? 1 : 0,
+            (const unsigned long long*)sums, images, out_cls, no_stage, no_aa);
+  return YS_OK;
+}
+
+// the chain with the AutoAugment / RandAugment slots between the flips and the erase: crop + flips staged as uint8 (stage_a), slot 0 into stage_b, slot 1 back
+// into stage_a (augment_aa.hip), then the two launches above on the staged bytes -- seven launches at most.  stage_a / stage_b: B * 3 * s * s bytes each,
+// 4-byte aligned; aa_stats: ys_aa_stats_bytes(B) zeroed bytes; stats_mask: ys_aa_slots_launch
+int ys_aug_classify_aa_launch(hipStream_t st, const unsigned char* arena, const ys_aug_src* srcs, int n_src, const float* src_cls, const ys_cls_item* items,
+                              int B, int s, const ys_aa_row* aa, int stats_mask, void* aa_stats, unsigned char* stage_a, unsigned char* stage_b,
+                              const ys_aug_jitter* jitter, int with_contrast, void* sums, float* images, float* out_cls) {
+  const long quads = (long)((s + 3) / 4) * s;
+  const dim3 grid(ys_cdiv(quads, AUGC_T), 1, B);
+  YS_LAUNCH(aug_cls_stage_kernel, grid, AUGC_T, st, arena, srcs, n_src, items, s, (s % 4 == 0 && ((size_t)stage_a & 3) == 0) ? 1 : 0, stage_a);
+  YS_TRY(ys_aa_slots_launch(st, stage_a, stage_b, stage_a, aa, B, s, s, stats_mask, aa_stats));
+  const unsigned char* staged = stage_a;
+  if (jitter && with_contrast)
+    YS_LAUNCH(aug_cls_gray_sum_kernel<true>, grid, AUGC_T, st, arena, srcs, n_src, items, jitter, s, (unsigned long long*)sums, staged, aa);
+  YS_LAUNCH(aug_cls_apply_kernel<true>, grid, AUGC_T, st, arena, srcs, n_src, src_cls, items, jitter, s, (s % 4 == 0 && ((size_t)images & 15) == 0) ? 1 : 0,
+            (const unsigned long long*)sums, images, out_cls, staged, aa);
   return YS_OK;
 }

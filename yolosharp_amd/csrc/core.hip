@@ -225,6 +225,7 @@ int ys_ctx_destroy(ys_ctx* ctx) {
   if (ctx->nms_ws) hipFree(ctx->nms_ws);
   if (ctx->e2e_ws) hipFree(ctx->e2e_ws);
   if (ctx->aug_ws) hipFree(ctx->aug_ws);
+  if (ctx->aa_ws) hipFree(ctx->aa_ws);
   if (ctx->ev0) hipEventDestroy(ctx->ev0);
   if (ctx->ev1) hipEventDestroy(ctx->ev1);
   if (ctx->own_stream && ctx->stream) hipStreamDestroy(ctx->stream);

@@ -307,19 +307,46 @@ extern "C" int ys_xyxyxyxy2xywhr(ys_ctx* ctx, const float* corners, int n, int o
 
 // ---- the classification input (augment_cls.hip; Data/ClassificationDataset.cs:90-131): crop / resize / flips / erase / ColorJitter / mul(1 / 255) as one
 //      gather, and the class ids.  The contrast reduction's per-image sums live in the augmenter's workspace, zeroed on the stream each call.
-extern "C" int ys_augment_classify(ys_ctx* ctx, const uint8_t* arena, const ys_aug_src* srcs, int n_src, const float* src_cls, const ys_cls_item* items,
-                                   int batch, int on_device, int imgsz, const ys_aug_jitter* jitter, float* images, float* out_cls) {
-  const char* fn = "ys_augment_classify";
+//      aa != NULL (ys_augment_classify_aa): the AutoAugment / RandAugment slots between the flips and the erase, on uint8 images staged in the context's
+//      second workspace (AaWs), whose statistics rows are zeroed on the stream each call.
+namespace {
+// the context's AutoAugment workspace: statistics rows | image A | image B (each image B * 3 * h * w bytes, 16-byte aligned)
+struct AaWs { void* stats; unsigned char *a, *b; size_t stats_bytes; };
+int aa_reserve_ws(ys_ctx* ctx, int batch, int h, int w, AaWs* ws) {
+  const size_t sb = (ys_aa_stats_bytes(batch) + 15) & ~(size_t)15, ib = ((size_t)batch * 3 * h * w + 15) & ~(size_t)15;
+  YS_TRY(ys_ctx_reserve_ws(ctx, &ctx->aa_ws, &ctx->aa_ws_bytes, sb + 2 * ib, "ys_auto_augment"));
+  ws->stats = ctx->aa_ws; ws->a = (unsigned char*)ctx->aa_ws + sb; ws->b = ws->a + ib; ws->stats_bytes = sb;
+  return YS_OK;
+}
+// the checks a host-resident ys_aa_row table allows; *stats_mask bit k = some row's slot k needs the statistics launch
+int aa_check_rows(const char* fn, const ys_aa_row* rows, int batch, int* stats_mask) {
+  int mask = 0;
+  for (int b = 0; b < batch; b++) {
+    const ys_aa_row& r = rows[b];
+    YS_REQUIRE(ys_aa_row_ok_host(&r), "%s: aa row %d is invalid: ops (%d, %d) must be in -1 .. 13, args (%g, %g) and theta finite, Posterize bits in 0 .. 8", fn, b,
+               r.op[0], r.op[1], (double)r.arg[0], (double)r.arg[1]);
+    for (int k = 0; k < 2; k++) mask |= ys_aa_row_needs_stats_host(&r, k) << k;
+  }
+  *stats_mask = mask;
+  return YS_OK;
+}
+
+int aug_classify_impl(const char* fn, ys_ctx* ctx, const uint8_t* arena, const ys_aug_src* srcs, int n_src, const float* src_cls, const ys_cls_item* items,
+                      int batch, int on_device, int imgsz, const ys_aa_row* aa, const ys_aug_jitter* jitter, float* images, float* out_cls) {
   YS_REQUIRE(ctx && arena && srcs && src_cls && items && images && out_cls, "%s: null argument", fn);
   YS_REQUIRE(batch > 0 && batch <= 65535 && n_src > 0, "%s: bad shape batch=%d (1..65535) n_src=%d", fn, batch, n_src);
   YS_REQUIRE(imgsz >= 1 && imgsz <= 16384, "%s: imgsz %d must be in [1, 16384]", fn, imgsz);
   YS_CHECK_HIP(hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
   YS_TRY(aug_reserve_ws(ctx, batch));
+  AaWs aws{};
+  if (aa) YS_TRY(aa_reserve_ws(ctx, batch, imgsz, imgsz, &aws));
   YsTimer timer(ctx, "augment_classify");
-  if (on_device) {                                         // the host cannot read the rows: the reduction runs and leaves at once where a row has no contrast
+  if (on_device) {                                         // the host cannot read the rows: the reductions run and leave at once where a row needs none
     if (jitter) YS_CHECK_HIP(hipMemsetAsync(ctx->aug_ws, 0, (size_t)batch * 8, st));
-    return ys_aug_classify_launch(st, arena, srcs, n_src, src_cls, items, batch, imgsz, jitter, 1, ctx->aug_ws, images, out_cls);
+    if (!aa) return ys_aug_classify_launch(st, arena, srcs, n_src, src_cls, items, batch, imgsz, jitter, 1, ctx->aug_ws, images, out_cls);
+    YS_CHECK_HIP(hipMemsetAsync(aws.stats, 0, aws.stats_bytes, st));
+    return ys_aug_classify_aa_launch(st, arena, srcs, n_src, src_cls, items, batch, imgsz, aa, 3, aws.stats, aws.a, aws.b, jitter, 1, ctx->aug_ws, images, out_cls);
   }
   for (int b = 0; b < batch; b++) {
     const ys_cls_item& it = items[b];
@@ -327,11 +354,12 @@ extern "C" int ys_augment_classify(ys_ctx* ctx, const uint8_t* arena, const ys_a
                "(%d, %d) + %d, flips (%d, %d), erase (y %d, x %d, %d x %d)", fn, b, it.src, n_src, it.top, it.left, it.ch, it.cw, it.oh, it.ow, it.oy, it.ox, imgsz,
                it.flip_lr, it.flip_ud, it.er_y, it.er_x, it.er_h, it.er_w);
   }
-  int contrast = 0;
+  int contrast = 0, stats_mask = 0;
+  if (aa) YS_TRY(aa_check_rows(fn, aa, batch, &stats_mask));
   if (jitter) YS_TRY(aug_check_jitter(fn, jitter, batch, 1, &contrast));
   const size_t arena_bytes = aug_arena_bytes(srcs, n_src), src_bytes = (size_t)n_src * sizeof(ys_aug_src), item_bytes = (size_t)batch * sizeof(ys_cls_item);
   const size_t jit_bytes = (size_t)batch * sizeof(ys_aug_jitter), n_img = (size_t)batch * 3 * imgsz * imgsz;
-  DevBuf da, ds, dc, di, dj, dimg, dcls;
+  DevBuf da, ds, dc, di, dj, daa, dimg, dcls;
   YS_TRY(da.alloc(arena_bytes)); YS_TRY(ds.alloc(src_bytes)); YS_TRY(dc.alloc((size_t)n_src * 4)); YS_TRY(di.alloc(item_bytes));
   YS_TRY(dimg.alloc(n_img * 4)); YS_TRY(dcls.alloc((size_t)batch * 4));
   YS_TRY(h2d(st, da.p, arena, arena_bytes));
@@ -343,10 +371,59 @@ extern "C" int ys_augment_classify(ys_ctx* ctx, const uint8_t* arena, const ys_a
     YS_TRY(h2d(st, dj.p, jitter, jit_bytes));
   }
   if (contrast) YS_CHECK_HIP(hipMemsetAsync(ctx->aug_ws, 0, (size_t)batch * 8, st));
-  YS_TRY(ys_aug_classify_launch(st, da.as<unsigned char>(), ds.as<ys_aug_src>(), n_src, dc.as<float>(), di.as<ys_cls_item>(), batch, imgsz,
-                                jitter ? dj.as<ys_aug_jitter>() : nullptr, contrast, ctx->aug_ws, dimg.as<float>(), dcls.as<float>()));
+  if (aa) {
+    YS_TRY(daa.alloc((size_t)batch * sizeof(ys_aa_row)));
+    YS_TRY(h2d(st, daa.p, aa, (size_t)batch * sizeof(ys_aa_row)));
+    if (stats_mask) YS_CHECK_HIP(hipMemsetAsync(aws.stats, 0, aws.stats_bytes, st));
+    YS_TRY(ys_aug_classify_aa_launch(st, da.as<unsigned char>(), ds.as<ys_aug_src>(), n_src, dc.as<float>(), di.as<ys_cls_item>(), batch, imgsz,
+                                     daa.as<ys_aa_row>(), stats_mask, aws.stats, aws.a, aws.b, jitter ? dj.as<ys_aug_jitter>() : nullptr, contrast, ctx->aug_ws,
+                                     dimg.as<float>(), dcls.as<float>()));
+  } else {
+    YS_TRY(ys_aug_classify_launch(st, da.as<unsigned char>(), ds.as<ys_aug_src>(), n_src, dc.as<float>(), di.as<ys_cls_item>(), batch, imgsz,
+                                  jitter ? dj.as<ys_aug_jitter>() : nullptr, contrast, ctx->aug_ws, dimg.as<float>(), dcls.as<float>()));
+  }
   YS_TRY(d2h(st, images, dimg.p, n_img * 4));
   YS_TRY(d2h(st, out_cls, dcls.p, (size_t)batch * 4));
+  YS_CHECK_HIP(hipStreamSynchronize(st));
+  return YS_OK;
+}
+}  // namespace
+
+extern "C" int ys_augment_classify(ys_ctx* ctx, const uint8_t* arena, const ys_aug_src* srcs, int n_src, const float* src_cls, const ys_cls_item* items,
+                                   int batch, int on_device, int imgsz, const ys_aug_jitter* jitter, float* images, float* out_cls) {
+  return aug_classify_impl("ys_augment_classify", ctx, arena, srcs, n_src, src_cls, items, batch, on_device, imgsz, nullptr, jitter, images, out_cls);
+}
+
+// the same with the AutoAugment / RandAugment rows of the batch; aa == NULL is the entry above
+extern "C" int ys_augment_classify_aa(ys_ctx* ctx, const uint8_t* arena, const ys_aug_src* srcs, int n_src, const float* src_cls, const ys_cls_item* items,
+                                      int batch, int on_device, int imgsz, const ys_aa_row* aa, const ys_aug_jitter* jitter, float* images, float* out_cls) {
+  return aug_classify_impl("ys_augment_classify_aa", ctx, arena, srcs, n_src, src_cls, items, batch, on_device, imgsz, aa, jitter, images, out_cls);
+}
+
+// ---- the two slots on their own (augment_aa.hip): uint8 [B, 3, H, W] -> uint8, any H x W.  in and out must not overlap
+extern "C" int ys_auto_augment_ops(ys_ctx* ctx, const uint8_t* in, int B, int H, int W, const ys_aa_row* rows, int on_device, uint8_t* out) {
+  const char* fn = "ys_auto_augment_ops";
+  YS_REQUIRE(ctx && in && rows && out, "%s: null argument", fn);
+  YS_REQUIRE(B > 0 && B <= 65535 && H > 0 && W > 0 && H <= 16384 && W <= 16384, "%s: bad shape batch=%d (1..65535) h=%d w=%d (1..16384)", fn, B, H, W);
+  YS_CHECK_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  AaWs aws{};
+  YS_TRY(aa_reserve_ws(ctx, B, H, W, &aws));
+  YsTimer timer(ctx, "auto_augment_ops");
+  if (on_device) {
+    YS_CHECK_HIP(hipMemsetAsync(aws.stats, 0, aws.stats_bytes, st));
+    return ys_aa_slots_launch(st, in, aws.a, out, rows, B, H, W, 3, aws.stats);
+  }
+  int stats_mask = 0;
+  YS_TRY(aa_check_rows(fn, rows, B, &stats_mask));
+  const size_t n_px = (size_t)B * 3 * H * W;
+  DevBuf drows;
+  YS_TRY(drows.alloc((size_t)B * sizeof(ys_aa_row)));
+  YS_TRY(h2d(st, aws.b, in, n_px));                        // image B of the workspace holds the input, and then the output
+  YS_TRY(h2d(st, drows.p, rows, (size_t)B * sizeof(ys_aa_row)));
+  if (stats_mask) YS_CHECK_HIP(hipMemsetAsync(aws.stats, 0, aws.stats_bytes, st));
+  YS_TRY(ys_aa_slots_launch(st, aws.b, aws.a, aws.b, drows.as<ys_aa_row>(), B, H, W, stats_mask, aws.stats));
+  YS_TRY(d2h(st, out, aws.b, n_px));
   YS_CHECK_HIP(hipStreamSynchronize(st));
   return YS_OK;
 }

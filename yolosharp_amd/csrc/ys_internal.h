@@ -62,6 +62,9 @@ struct ys_ctx {
   // ys_augment_* workspace (per-image parameters + label counts; grown on demand)
   void* aug_ws = nullptr;
   size_t aug_ws_bytes = 0;
+  // the AutoAugment slots' workspace (per-image statistics rows + the uint8 images between the slots; grown on demand)
+  void* aa_ws = nullptr;
+  size_t aa_ws_bytes = 0;
   // scratch for per-operator entry points
   std::map<std::string, float> last_ms;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;

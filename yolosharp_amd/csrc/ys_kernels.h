@@ -461,3 +461,15 @@ struct ys_cls_item;
 int ys_aug_cls_item_ok_host(const ys_cls_item* it, const ys_aug_src* srcs, int n_src, int s);
 int ys_aug_classify_launch(hipStream_t st, const unsigned char* arena, const ys_aug_src* srcs, int n_src, const float* src_cls, const ys_cls_item* items,
                            int B, int s, const ys_aug_jitter* jitter, int with_contrast, void* sums, float* images, float* out_cls);
+// ---- augment_aa.hip: the AutoAugment / RandAugment operators on uint8 planes [B, 3, H, W], two slots per image (ys_aa_row): in -> slot 0 -> mid -> slot 1 ->
+// out, a statistics and an apply launch per slot.  stats: ys_aa_stats_bytes(B) zeroed bytes; stats_mask bit k: slot k's statistics launch runs.
+// ys_aug_classify_aa_launch (augment_cls.hip): the classification chain with the slots between its flips and its erase; stage_a / stage_b: B * 3 * s * s bytes
+struct ys_aa_row;
+int ys_aa_row_ok_host(const ys_aa_row* row);
+int ys_aa_row_needs_stats_host(const ys_aa_row* row, int slot);
+size_t ys_aa_stats_bytes(int B);
+int ys_aa_slots_launch(hipStream_t st, const unsigned char* in, unsigned char* mid, unsigned char* out, const ys_aa_row* rows, int B, int H, int W,
+                       int stats_mask, void* stats);
+int ys_aug_classify_aa_launch(hipStream_t st, const unsigned char* arena, const ys_aug_src* srcs, int n_src, const float* src_cls, const ys_cls_item* items,
+                              int B, int s, const ys_aa_row* aa, int stats_mask, void* aa_stats, unsigned char* stage_a, unsigned char* stage_b,
+                              const ys_aug_jitter* jitter, int with_contrast, void* sums, float* images, float* out_cls);
