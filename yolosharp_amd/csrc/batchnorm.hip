@@ -98,6 +98,26 @@ bn_act_apply_kernel(const T* __restrict__ y, long rows, int C, const float* __re
   // maximum of non-negative floats is order-independent, so the atomic keeps the step deterministic
   if (amax) ys_amax_update(amax, mx);
 }
+// (row, channel vector) of a grid-stride pass over rows x CG vectors.  The thread's first vector is divided once; every further trip adds the launch-constant
+// stride as (quotient, remainder) of CG with a carry, so no division is left inside the loop (it was a 64-bit division by a run-time value per 16-byte vector).
+// I = unsigned where rows * CG < 2^31 (the launcher's `small`; i + stride stays below 2^32: the bounded grid's stride is 2^19 vectors), long otherwise.
+template <class I>
+struct EwWalk {
+  I i, n, row, step, qs;
+  int cv, rs, CG;
+  __device__ EwWalk(long rows, int CG_) : CG(CG_) {
+    n = (I)(rows * CG_);
+    i = (I)blockIdx.x * (I)EW_THREADS + (I)threadIdx.x;
+    step = (I)gridDim.x * (I)EW_THREADS;
+    row = i / (I)CG_; cv = (int)(i - row * (I)CG_);
+    qs = step / (I)CG_; rs = (int)(step - qs * (I)CG_);
+  }
+  __device__ bool more() const { return i < n; }
+  __device__ void next() {
+    i += step; row += qs; cv += rs;
+    if (cv >= CG) { cv -= CG; row += 1; }
+  }
+};
 // amax bookkeeping of a grid-stride pass: workgroup maximum through LDS, then ONE slot update per workgroup
 __device__ inline void ys_amax_update_wg(unsigned* slots, float mx) {
   __shared__ float s_wmax[EW_THREADS / 64];
@@ -133,23 +153,25 @@ template <bool ACT>
 __global__ void __launch_bounds__(EW_THREADS)
 bn_act_apply_q8_kernel(const bf16_t* __restrict__ y, long rows, int C, const float* __restrict__ scale, const float* __restrict__ shift,
                        const bf16_t* __restrict__ res, int res_ldc, int res_coff, bf16_t* __restrict__ z, int z_ldc, int z_coff,
-                       unsigned char* __restrict__ q8, const float* __restrict__ qscale, unsigned* __restrict__ amax) {
+                       unsigned char* __restrict__ q8, const float* __restrict__ qscale, int small, unsigned* __restrict__ amax) {
   const int CG = C / 8;
-  const long n = rows * CG;
   const float qs = qscale[0];
   float mx = 0.f;
-  for (long i = (long)blockIdx.x * EW_THREADS + threadIdx.x; i < n; i += (long)gridDim.x * EW_THREADS) {
-    const long row = i / CG; const int c = (int)(i - row * CG) * 8;
-    float f[8], r[8], sc[8], sh[8];             // loaded here, not through bn_act_apply_vec: with the arrays inside the helper this loop zero-fills r per trip (+1..3 VGPRs)
-    ys_unpack<bf16_t>(ys_ld16(y + row * C + c), f);
-    if (res) ys_unpack<bf16_t>(ys_ld16(res + row * res_ldc + res_coff + c), r);
-    ys_ldcoef<8>(scale + c, sc);
-    ys_ldcoef<8>(shift + c, sh);
-    bn_apply_vec<bf16_t, ACT>(f, sc, sh, res != nullptr, r);
-    const uint4 pk = ys_pack<bf16_t>(f);
-    ys_st16(z + row * z_ldc + z_coff + c, pk);
-    bn_q8_store<0>(pk, qs, q8 + row * C + c, mx);
-  }
+  auto pass = [&](auto w) {
+    for (; w.more(); w.next()) {
+      const long row = (long)w.row; const int c = w.cv * 8;
+      float f[8], r[8], sc[8], sh[8];             // loaded here, not through bn_act_apply_vec: with the arrays inside the helper this loop zero-fills r per trip (+1..3 VGPRs)
+      ys_unpack<bf16_t>(ys_ld16(y + row * C + c), f);
+      if (res) ys_unpack<bf16_t>(ys_ld16(res + row * res_ldc + res_coff + c), r);
+      ys_ldcoef<8>(scale + c, sc);
+      ys_ldcoef<8>(shift + c, sh);
+      bn_apply_vec<bf16_t, ACT>(f, sc, sh, res != nullptr, r);
+      const uint4 pk = ys_pack<bf16_t>(f);
+      ys_st16(z + row * z_ldc + z_coff + c, pk);
+      bn_q8_store<0>(pk, qs, q8 + row * C + c, mx);
+    }
+  };
+  if (small) pass(EwWalk<unsigned>(rows, CG)); else pass(EwWalk<long>(rows, CG));
   if (amax) ys_amax_update_wg(amax, mx);
 }
 // bounded grid of the grid-stride passes: `per` vectors per thread, at most 2048 workgroups
@@ -161,9 +183,11 @@ static int bounded_grid(long n, long per) {
 int ys_bn_act_apply_q8_launch(hipStream_t st, const void* y, long rows, int C, const float* scale, const float* shift, int act,
                               const void* res, int res_ldc, int res_coff, void* z, int z_ldc, int z_coff, void* q8,
                               const float* qscale, unsigned* amax) {
-  const int g = bounded_grid(rows * (C / 8), 4);
+  const long n = rows * (C / 8);
+  const int g = bounded_grid(n, 4);
+  const int small = n < (1L << 31) ? 1 : 0;
   YS_DISPATCH_ACT(act, YS_LAUNCH((bn_act_apply_q8_kernel<AF>), g, EW_THREADS, st, (const bf16_t*)y, rows, C, scale, shift, (const bf16_t*)res,
-                                 res_ldc, res_coff, (bf16_t*)z, z_ldc, z_coff, (unsigned char*)q8, qscale, amax));
+                                 res_ldc, res_coff, (bf16_t*)z, z_ldc, z_coff, (unsigned char*)q8, qscale, small, amax));
   return YS_OK;
 }
 
@@ -187,7 +211,7 @@ int ys_bn_act_apply_launch(hipStream_t st, int dtype, const void* y, long rows, 
 template <class T, bool ACT>
 __global__ void __launch_bounds__(EW_THREADS)
 bn_fin_apply_kernel(const T* __restrict__ y, long rows, int C, BnAccFin f, const T* __restrict__ res, int res_ldc, int res_coff,
-                    T* __restrict__ z, int z_ldc, int z_coff) {
+                    T* __restrict__ z, int z_ldc, int z_coff, int small) {
   constexpr int EPL = Elem<T>::EPL;
   YS_DYN_LDS(lds);
   float* s_sc = (float*)lds;                   // [C] scale, [C] shift
@@ -204,22 +228,26 @@ bn_fin_apply_kernel(const T* __restrict__ y, long rows, int C, BnAccFin f, const
   }
   __syncthreads();
   const int CG = C / EPL;
-  const long n = rows * CG;
-  for (long i = (long)blockIdx.x * EW_THREADS + threadIdx.x; i < n; i += (long)gridDim.x * EW_THREADS) {
-    const long row = i / CG; const int c = (int)(i - row * CG) * EPL;
-    float v[EPL], r[EPL];
-    ys_unpack<T>(ys_ld16(y + row * C + c), v);
-    if (res) ys_unpack<T>(ys_ld16(res + row * res_ldc + res_coff + c), r);
-    bn_apply_vec<T, ACT>(v, s_sc + c, s_sh + c, res != nullptr, r);
-    ys_st16(z + row * z_ldc + z_coff + c, ys_pack<T>(v));
-  }
+  auto pass = [&](auto w) {
+    for (; w.more(); w.next()) {
+      const long row = (long)w.row; const int c = w.cv * EPL;
+      float v[EPL], r[EPL];
+      ys_unpack<T>(ys_ld16(y + row * C + c), v);
+      if (res) ys_unpack<T>(ys_ld16(res + row * res_ldc + res_coff + c), r);
+      bn_apply_vec<T, ACT>(v, s_sc + c, s_sh + c, res != nullptr, r);
+      ys_st16(z + row * z_ldc + z_coff + c, ys_pack<T>(v));
+    }
+  };
+  if (small) pass(EwWalk<unsigned>(rows, CG)); else pass(EwWalk<long>(rows, CG));
 }
 int ys_bn_fin_apply_launch(hipStream_t st, int dtype, const void* y, long rows, int C, const BnAccFin& f, int act, const void* res, int res_ldc, int res_coff,
                            void* z, int z_ldc, int z_coff) {
-  const int g = bounded_grid(rows * (C / (dtype == YS_BF16 ? 8 : 4)), 2);
+  const long n = rows * (C / (dtype == YS_BF16 ? 8 : 4));
+  const int g = bounded_grid(n, 2);
+  const int small = n < (1L << 31) ? 1 : 0;
   const size_t lds = (size_t)2 * C * sizeof(float);
   YS_DISPATCH_T_ACT(dtype, act, YS_LAUNCH_LDS((bn_fin_apply_kernel<TT, AF>), g, EW_THREADS, lds, st, (const TT*)y, rows, C, f, (const TT*)res, res_ldc,
-                                              res_coff, (TT*)z, z_ldc, z_coff));
+                                              res_coff, (TT*)z, z_ldc, z_coff, small));
   return YS_OK;
 }
 
@@ -495,27 +523,31 @@ __global__ void __launch_bounds__(EW_THREADS)
 bn_bwd_apply_q8_kernel(const bf16_t* __restrict__ dz, int dz_ldc, int dz_coff, const bf16_t* __restrict__ y, long rows, int C,
                        const float* __restrict__ scale, const float* __restrict__ shift, const float* __restrict__ k2,
                        const float* __restrict__ k3, bf16_t* __restrict__ dy, unsigned char* __restrict__ q8,
-                       const float* __restrict__ qscale, unsigned* __restrict__ amax, bf16_t* __restrict__ rg, int rg_ldc, int rg_coff) {
+                       const float* __restrict__ qscale, int small, unsigned* __restrict__ amax, bf16_t* __restrict__ rg, int rg_ldc, int rg_coff) {
   const int CG = C / 8;
-  const long n = rows * CG;
   const float qs = qscale[0];
   float mx = 0.f;
-  for (long i = (long)blockIdx.x * EW_THREADS + threadIdx.x; i < n; i += (long)gridDim.x * EW_THREADS) {
-    const long row = i / CG; const int c = (int)(i - row * CG) * 8;
-    float f[8];
-    bn_bwd_apply_vec<bf16_t, ACT>(dz, dz_ldc, dz_coff, y, row, c, C, scale, shift, k2, k3, rg, rg_ldc, rg_coff, f);
-    const uint4 pk = ys_pack<bf16_t>(f);
-    ys_st16(dy + row * C + c, pk);
-    bn_q8_store<1>(pk, qs, q8 + row * C + c, mx);   // quantise what the bf16 consumers (wgrad) see: the rounded value
-  }
+  auto pass = [&](auto w) {
+    for (; w.more(); w.next()) {
+      const long row = (long)w.row; const int c = w.cv * 8;
+      float f[8];
+      bn_bwd_apply_vec<bf16_t, ACT>(dz, dz_ldc, dz_coff, y, row, c, C, scale, shift, k2, k3, rg, rg_ldc, rg_coff, f);
+      const uint4 pk = ys_pack<bf16_t>(f);
+      ys_st16(dy + row * C + c, pk);
+      bn_q8_store<1>(pk, qs, q8 + row * C + c, mx);   // quantise what the bf16 consumers (wgrad) see: the rounded value
+    }
+  };
+  if (small) pass(EwWalk<unsigned>(rows, CG)); else pass(EwWalk<long>(rows, CG));
   if (amax) ys_amax_update_wg(amax, mx);
 }
 int ys_bn_bwd_apply_q8_launch(hipStream_t st, const void* dz, int dz_ldc, int dz_coff, const void* y, long rows, int C,
                               const float* scale, const float* shift, const float* k2, const float* k3, int act, void* dy,
                               void* q8, const float* qscale, unsigned* amax, void* rg, int rg_ldc, int rg_coff) {
-  const int g = bounded_grid(rows * (C / 8), 4);
+  const long n = rows * (C / 8);
+  const int g = bounded_grid(n, 4);
+  const int small = n < (1L << 31) ? 1 : 0;
   YS_DISPATCH_ACT(act, YS_LAUNCH((bn_bwd_apply_q8_kernel<AF>), g, EW_THREADS, st, (const bf16_t*)dz, dz_ldc, dz_coff, (const bf16_t*)y, rows, C, scale, shift,
-                                 k2, k3, (bf16_t*)dy, (unsigned char*)q8, qscale, amax, (bf16_t*)rg, rg_ldc, rg_coff));
+                                 k2, k3, (bf16_t*)dy, (unsigned char*)q8, qscale, small, amax, (bf16_t*)rg, rg_ldc, rg_coff));
   return YS_OK;
 }
 

@@ -203,6 +203,14 @@ wgrad_reduce_kernel(const float* __restrict__ partial, int splits, long n, int c
 //   TAPS == 1: 4 waves split the 32-pixel K-blocks and are combined through LDS at the end.
 // K order inside a tile is the tile-local pixel index p = ty*TW + tx for both operands; pixels outside the image (or the
 // tile's 32-pixel rounding) read a zero dy row.  Partials go to partial[blockIdx.x][Cout][taps][Cin] (fixed-order reduce).
+// a value that is the same in every lane, kept in a scalar register (the compiler otherwise computed the tile origin's products per lane)
+__device__ __forceinline__ unsigned wg_uniform(unsigned v) {
+#ifdef YS_EMU_BUILD
+  return v;
+#else
+  return (unsigned)__builtin_amdgcn_readfirstlane((int)v);
+#endif
+}
 #define YS_WG_TWO_MAX 2        // 9-wave weight-gradient tiles of up to this many MFMA fragments run two workgroups per CU (96 registers).  4 measured (round 4): the 2 x 2 tile spills 32 B and the 32 -> 32 layers go 29.4 -> 42.0 us (400 partial slabs instead of 229) -- stays 2
 template <int MRA, int NRB, int TAPS>
 __global__ void __launch_bounds__(TAPS == 9 ? 576 : 256, (TAPS == 9 && MRA * NRB <= YS_WG_TWO_MAX) ? 5 : 1)   // small 9-wave tiles: 96 registers = two workgroups per CU
@@ -219,8 +227,7 @@ conv_wgrad_tr_kernel(WgradArgs a) {
   const int TW = 1 << a.TWS, TP = a.TH * TW;
   const int nkb = (TP + 31) >> 5;
   const int ZR = nkb * 32;                              // zero row of the dy image
-  char* sDb = (char*)lds;                               // [ZR + 1][pdb]
-  char* sXb = sDb + (size_t)(ZR + 1) * a.pdb;           // [PH*PW][pxb]
+  char* sDb = (char*)lds;                               // [ZR + 1][pdb], then the patch [PH*PW][pxb]
   const int ci_tiles = (a.Cin + CIT - 1) / CIT;
   const int co0 = (blockIdx.y / ci_tiles) * COT;
   const int ci0 = (blockIdx.y % ci_tiles) * CIT;
@@ -236,32 +243,76 @@ conv_wgrad_tr_kernel(WgradArgs a) {
   const ys_rsrcv_t rsD = ys_make_rsrcv(dyb + (long)a.dy_coff * 2L, a.dybytes);
   const ys_rsrcv_t rsX = ys_make_rsrcv(xb + (long)a.in_coff * 2L, a.xbytes);
   uint4 rd[ND], rx[NX];
-  auto fetch = [&](int tile) {
-    int t = tile;
-    const int txi = t % a.tiles_x; t /= a.tiles_x;
-    const int tyi = t % a.tiles_y;
-    const int b = t / a.tiles_y;
+  // Nothing in a unit's address depends on the tile except the tile's origin, so each thread derives its units' records ONCE (the per-tile form divided by PW and
+  // walked a 64-bit address chain for every unit of every tile: more vector instructions than the K loop on the small tiles):
+  //   off  byte offset from the tile's origin in the view (row, column, channel unit).  32-bit wrapping arithmetic throughout: both views are below 2 GB
+  //        (wgrad_view_bytes), so origin + off of a unit inside the image IS its offset, whatever the origin of a border tile wrapped to
+  //   rc   row << 16 | column inside the tile / patch; a unit that does not exist (beyond the tile / patch, channel outside the layer) carries YS_WG_NOUNIT, a
+  //        row and column beyond any tile, so the tile's two bounds compares reject it with the pixels outside the image
+  //   lds  byte offset of the unit's LDS slot; YS_WG_NOUNIT beyond the tile / patch (nothing is stored there)
+  constexpr unsigned YS_WG_NOUNIT = 0xffffffffu;
+  unsigned doff[ND], drc[ND], dlds[ND], xoff[NX], xrc[NX], xlds[NX];
+#pragma unroll
+  for (int k = 0; k < ND; k++) {
+    const int idx = tid + NT * k;
+    const int p = idx / DV, u = idx - p * DV;
+    const int ty = p >> a.TWS, tx = p & (TW - 1);
+    const int c = co0 + u * 8;
+    const bool slot = idx < TP * DV;
+    doff[k] = (((unsigned)ty * (unsigned)a.Wout + (unsigned)tx) * (unsigned)a.dy_ldc + (unsigned)c) * 2u;
+    drc[k] = (slot && c < a.Cout) ? ((unsigned)ty << 16 | (unsigned)tx) : YS_WG_NOUNIT;
+    dlds[k] = slot ? (unsigned)(p * a.pdb + u * 16) : YS_WG_NOUNIT;
+#ifndef YS_EMU_BUILD
+    asm volatile("" : "+v"(doff[k]), "+v"(drc[k]), "+v"(dlds[k]));   // held in registers from here on: the compiler otherwise sinks the multiplies back into the tile loop
+#endif
+  }
+#pragma unroll
+  for (int k = 0; k < NX; k++) {
+    const int idx = tid + NT * k;
+    const int pix = idx / XV, u = idx - pix * XV;
+    const int r = pix / a.PW, cc = pix - r * a.PW;
+    const int c = ci0 + u * 8;
+    const bool slot = idx < npatch;
+    xoff[k] = (((unsigned)r * (unsigned)a.Win + (unsigned)cc) * (unsigned)a.in_ldc + (unsigned)c) * 2u;
+    xrc[k] = (slot && c < a.Cin) ? ((unsigned)r << 16 | (unsigned)cc) : YS_WG_NOUNIT;
+    xlds[k] = slot ? (unsigned)((ZR + 1) * a.pdb + pix * a.pxb + u * 16) : YS_WG_NOUNIT;
+#ifndef YS_EMU_BUILD
+    asm volatile("" : "+v"(xoff[k]), "+v"(xrc[k]), "+v"(xlds[k]));
+#endif
+  }
+  // Per tile: one uniform origin and the uniform row / column windows of the image inside the tile and the patch, then per unit one add, two unsigned compares
+  // and the select of the out-of-range offset (conv_p2.h pfetch).  Every unit still issues its load.
+  auto fetch = [&](int txi, int tyi, int b) {
     const int oy0 = tyi * a.TH, ox0 = txi * TW;
+    const unsigned dh = (unsigned)((a.Hout - oy0) < a.TH ? (a.Hout - oy0) : a.TH), dw = (unsigned)((a.Wout - ox0) < TW ? (a.Wout - ox0) : TW);
+    const unsigned dorg = wg_uniform((((unsigned)b * (unsigned)a.dy_bstride + (unsigned)oy0 * (unsigned)a.Wout + (unsigned)ox0) * (unsigned)a.dy_ldc) * 2u);
 #pragma unroll
     for (int k = 0; k < ND; k++) {
-      const int idx = tid + NT * k;
-      const int p = idx / DV, u = idx - p * DV;
-      const int oy = oy0 + (p >> a.TWS), ox = ox0 + (p & (TW - 1));
-      const int c = co0 + u * 8;
-      const bool ok = (bool)((int)(idx < TP * DV) & (int)(oy < a.Hout) & (int)(ox < a.Wout) & (int)(c < a.Cout));
-      rd[k] = ys_bufld16(rsD, ok ? (unsigned)(((((long)b * a.dy_bstride + (long)oy * a.Wout + ox) * a.dy_ldc) + c) * 2L) : YS_BUF_OOB);
+      const bool ok = (bool)((int)((drc[k] >> 16) < dh) & (int)((drc[k] & 0xffffu) < dw));
+      rd[k] = ys_bufld16(rsD, ok ? dorg + doff[k] : YS_BUF_OOB);
     }
+    // rows [rlo, rlo + rn) and columns [clo, clo + cn) of the patch lie inside the image (the rest is the zero padding)
     const int iy0 = oy0 * S - a.pad, ix0 = ox0 * S - a.pad;
+    const unsigned rlo = iy0 < 0 ? (unsigned)-iy0 : 0u, clo = ix0 < 0 ? (unsigned)-ix0 : 0u;
+    const unsigned rn = (unsigned)((a.Hin - iy0) < a.PH ? (a.Hin - iy0) : a.PH) - rlo, cn = (unsigned)((a.Win - ix0) < a.PW ? (a.Win - ix0) : a.PW) - clo;
+    const unsigned xorg = wg_uniform((((unsigned)b * (unsigned)a.in_bstride + (unsigned)iy0 * (unsigned)a.Win + (unsigned)ix0) * (unsigned)a.in_ldc) * 2u);
 #pragma unroll
     for (int k = 0; k < NX; k++) {
-      const int idx = tid + NT * k;
-      const int pix = idx / XV, u = idx - pix * XV;
-      const int r = pix / a.PW, cc = pix - r * a.PW;
-      const int iy = iy0 + r, ix = ix0 + cc;
-      const int c = ci0 + u * 8;
-      const bool ok = (bool)((int)(idx < npatch) & (int)((unsigned)iy < (unsigned)a.Hin) & (int)((unsigned)ix < (unsigned)a.Win) & (int)(c < a.Cin));
-      rx[k] = ys_bufld16(rsX, ok ? (unsigned)(((((long)b * a.in_bstride + (long)iy * a.Win + ix) * a.in_ldc) + c) * 2L) : YS_BUF_OOB);
+      const bool ok = (bool)((int)(((xrc[k] >> 16) - rlo) < rn) & (int)(((xrc[k] & 0xffffu) - clo) < cn));
+      rx[k] = ys_bufld16(rsX, ok ? xorg + xoff[k] : YS_BUF_OOB);
     }
+  };
+  // tiles tile, tile + gridDim.x, ...: the coordinates advance by the decoded grid stride with carries (conv_p2_body's advance), no division per tile
+  int stx, sty, stb;
+  {
+    const int G = (int)gridDim.x;
+    stx = G % a.tiles_x; const int rem = G / a.tiles_x;
+    sty = rem % a.tiles_y; stb = rem / a.tiles_y;
+  }
+  auto advance = [&](int& txi, int& tyi, int& b) {
+    txi += stx; if (txi >= a.tiles_x) { txi -= a.tiles_x; tyi++; }
+    tyi += sty; if (tyi >= a.tiles_y) { tyi -= a.tiles_y; b++; }
+    b += stb;
   };
 
   f32x4 acc[MRA][NRB];
@@ -293,26 +344,27 @@ conv_wgrad_tr_kernel(WgradArgs a) {
   const char* lb = (const char*)lds;
 
   int tile = blockIdx.x;
-  if (tile < a.ntiles) fetch(tile);
+  int txi, tyi, b;
+  {
+    int t = tile;
+    txi = t % a.tiles_x; t /= a.tiles_x;
+    tyi = t % a.tiles_y; b = t / a.tiles_y;
+  }
+  int ntx = txi, nty = tyi, nb = b;
+  if (tile < a.ntiles) fetch(txi, tyi, b);
   while (tile < a.ntiles) {
     ys_barrier_lds();                                   // every wave finished reading the previous tile
 #pragma unroll
-    for (int k = 0; k < ND; k++) {
-      const int idx = tid + NT * k;
-      if (idx < TP * DV) { const int p = idx / DV; *(uint4*)(sDb + (size_t)p * a.pdb + (idx - p * DV) * 16) = rd[k]; }
-    }
+    for (int k = 0; k < ND; k++)
+      if (dlds[k] != YS_WG_NOUNIT) *(uint4*)((char*)lds + dlds[k]) = rd[k];
 #pragma unroll
-    for (int k = 0; k < NX; k++) {
-      const int idx = tid + NT * k;
-      if (idx < npatch) { const int pix = idx / XV; *(uint4*)(sXb + (size_t)pix * a.pxb + (idx - pix * XV) * 16) = rx[k]; }
-    }
+    for (int k = 0; k < NX; k++)
+      if (xlds[k] != YS_WG_NOUNIT) *(uint4*)((char*)lds + xlds[k]) = rx[k];
     ys_barrier_lds();
-    int t = tile;
-    const int txi = t % a.tiles_x; t /= a.tiles_x;
-    const int tyi = t % a.tiles_y;
     const int oy0 = tyi * a.TH, ox0 = txi * TW;
     const int ntile = tile + gridDim.x;
-    if (ntile < a.ntiles) fetch(ntile);                 // in flight while this tile is consumed
+    advance(ntx, nty, nb);
+    if (ntile < a.ntiles) fetch(ntx, nty, nb);          // in flight while this tile is consumed
     // rows of the tile that hold image pixels (tile-local), and this lane's column validity
     const int tylim = (a.Hout - oy0) < a.TH ? (a.Hout - oy0) : a.TH;
     const bool colok0 = (ox0 + tx0[0]) < a.Wout, colok1 = (ox0 + tx0[1]) < a.Wout;
@@ -344,7 +396,7 @@ conv_wgrad_tr_kernel(WgradArgs a) {
 #pragma unroll
         for (int j = 0; j < NRB; j++) acc[i][j] = ys_mma<bf16_t>(fa[i], fb[j], acc[i][j]);
     }
-    tile = ntile;
+    tile = ntile; txi = ntx; tyi = nty;
   }
 
   float* outp = a.partial + (long)blockIdx.x * a.Cout * a.KH * a.KW * a.Cin;
