@@ -124,6 +124,11 @@ def test_segmenter_val(backend, engine):
     rbox = M.val_summary(M.ap_per_class(np.concatenate(tps), conf, pc, tc))
     rmask = M.val_summary(M.ap_per_class(np.concatenate(tpms), conf, pc, tc))
     assert np.allclose(box, rbox, atol=1e-6) and np.allclose(mask, rmask, atol=1e-6), (box, rbox, mask, rmask)
+    # a set whose every batch is skipped (Segmenter.cs:105-108): zeros, like the other tasks
+    empty = dict(d, batch_idx=np.zeros(0, np.float32), cls=np.zeros(0, np.float32), bboxes=np.zeros((0, 4), np.float32))
+    z_items, z_box, z_mask = Segmenter(m).Val([empty])
+    assert z_items.shape == (5,) and z_items.dtype == np.float32 and not z_items.any()
+    assert z_box == (0.0, 0.0, 0.0, 0.0) and z_mask == (0.0, 0.0, 0.0, 0.0)
     m.close()
 
 

@@ -1,9 +1,12 @@
 """Validation matching on the device: Metrics.box_iou (Metrics.cs:16-34) and match_predictions
 (YoloBaseTaskModel.cs:377-446) per image, batched.  Integer / boolean outputs are compared exactly with the oracle."""
+import functools
+
 import numpy as np
 import pytest
 import torch
 
+import e2e_pose_ref as R
 from conftest import BACKENDS
 from oracle import yolo_oracle as O
 
@@ -75,6 +78,104 @@ def test_match_quirks(backend, engine):
     assert got[0, 0] and not got[1, 0]                      # threshold 0.5: d0 takes gt0 (lowest index), d1 is a duplicate
     assert got[1, 9] and not got[0, 9]                      # threshold 0.95: only d1 clears it
     assert not got[2].any() and got[3, :7].all() and not got[3, 7:].any() and not got[4].any()
+
+
+# Metric values the strided scene places its detections at: each is 0.025 from the nearest threshold of linspace(0.5, 0.95, 10), and each of the
+# three metrics reaches them by a perturbation that does not depend on the label's size:
+#   box IoU of a box shifted by f * w along x (or f * h along y):          (1 - f) / (1 + f)
+#   probiou of an oriented box shifted by f * w along its own w axis:     bd = 12 f^2 / 8, iou = 1 - sqrt(1 - exp(-bd))   (equal covariances: t3 = 0)
+#   OKS with every keypoint moved by r, K != 17 (sigma = 1 / K):           exp(-r^2 / ((2 / K)^2 * area * 2))
+_LEVELS = np.array([0.975, 0.875, 0.775, 0.675, 0.575, 0.35])
+
+
+@functools.lru_cache(maxsize=None)
+def _strided_scene(kind, seed=0):
+    """B = 2, max_det = 300: image 0 has 270 labels on a non-overlapping 17 x 16 grid and count = 300 -- both beyond the 256 threads of a workgroup, so every
+    grid-stride loop of the matching kernels takes a second trip -- image 1 has 3 labels and count = 1; the labels of image 1 sit between those of image 0
+    in collate order.  Detections of image 0 are copies of its labels placed at _LEVELS (every label once, label 7 thirteen times, 17 more at random), every
+    13th with another class, in random order.  kind: "box" rows [.., 6], "rot" rows [.., 7] + 5-column labels, "pose" rows [.., 6 + 5 * 2] + keypoints."""
+    g = np.random.default_rng(seed)
+    B, max_det, nc, K, n0, cols = 2, 300, 3, 5, 270, 17
+    WH = np.array([640.0, 640.0])
+    cell = WH / np.array([cols, 16])
+    k = np.arange(n0)
+    ctr = np.concatenate(((np.stack((k % cols, k // cols), 1) + 0.5) * cell, g.uniform(100, 500, (3, 2))))
+    wh = np.concatenate((g.uniform(0.45, 0.6, (n0, 2)) * cell, g.uniform(40, 90, (3, 2))))
+    ang = g.uniform(-np.pi / 4, 3 * np.pi / 4, n0 + 3)
+    cls = g.integers(0, nc, n0 + 3).astype(np.float32)
+    unit = g.uniform(-0.4, 0.4, (K, 2))                                                # one keypoint layout, scaled into every box
+    kpt = ctr[:, None] + (unit + g.normal(0, 0.03, (n0 + 3, K, 2))) * wh[:, None]
+    order = np.concatenate((k[:100], [n0], k[100:], [n0 + 1, n0 + 2]))                 # collate order: image 1's labels in between
+    batch = {"batch_idx": (order >= n0).astype(np.float32), "cls": cls[order],
+             "bboxes": np.concatenate((ctr / WH, wh / WH) + ((ang[:, None],) if kind == "rot" else ()), 1)[order].astype(np.float32)}
+    if kind == "pose":
+        batch["keypoints"] = (kpt / WH)[order].astype(np.float32)
+
+    def det(j, lv, lk, axis, sign, wrong, score):
+        """label j at box / probiou level lv along `axis` (0: w, 1: h), keypoints at OKS level lk"""
+        if kind == "rot":
+            f = np.sqrt(-np.log(1 - (1 - lv) ** 2) / 1.5)
+            c, s = np.cos(ang[j]), np.sin(ang[j])
+            c_ = ctr[j] + sign * f * wh[j, axis] * (np.array([c, s]) if axis == 0 else np.array([-s, c]))
+            return np.concatenate((c_, wh[j], [score, (cls[j] + wrong) % nc, ang[j]]))
+        c_ = ctr[j].copy()
+        c_[axis] += sign * (1 - lv) / (1 + lv) * wh[j, axis]
+        row = np.concatenate((c_ - wh[j] / 2, c_ + wh[j] / 2, [score, (cls[j] + wrong) % nc]))
+        if kind == "pose":
+            r = np.sqrt(-np.log(lk) * (2.0 / K) ** 2 * wh[j, 0] * wh[j, 1] * 0.53 * 2)
+            row = np.concatenate((row, (kpt[j] + r * np.array([np.cos(j), np.sin(j)])).reshape(-1)))
+        return row
+    src = g.permutation(np.concatenate((k, np.full(13, 7), g.integers(0, n0, 17))))
+    lv, lk = g.choice(_LEVELS, max_det), g.choice(_LEVELS, max_det)
+    axis, sign = g.integers(0, 2, max_det), g.choice([-1.0, 1.0], max_det)
+    rows = np.zeros((B, max_det, {"box": 6, "rot": 7, "pose": 6 + 2 * K}[kind]), np.float32)
+    for d in range(max_det):
+        rows[0, d] = det(src[d], lv[d], lk[d], axis[d], sign[d], d % 13 == 12, 0.99 - 0.003 * d)
+    for d in range(4):                                                                  # image 1: one detection counts, rows behind it are never read
+        rows[1, d] = det(n0 + d % 3, 0.875, 0.775, 0, 1.0, 0, 0.9)
+    return rows, np.array([max_det, 1], np.int32), batch, 640.0, 640.0
+
+
+def _check_strided(got, want, count):
+    for b in range(2):
+        assert got[b].shape == (count[b], 10) and np.array_equal(got[b], want[b]), (b, np.argwhere(got[b] != want[b])[:8])
+    assert want[0][:, 0].sum() >= 135 and 0 < want[0][:, 9].sum() < want[0][:, 0].sum()    # half of the 270 labels matched at 0.5, fewer at 0.95
+    assert want[0][256:, 0].any() and want[1][0, 0]                                      # ... some of them credited in a loop's second trip
+
+
+@pytest.mark.parametrize("backend", BACKENDS)
+@pytest.mark.parametrize("kind", ["box", "rot", "pose"])
+def test_val_match_strided(backend, engine, kind):
+    """The three batched entry points on a scene whose labels and detections both exceed the workgroup size, against the oracle alone (the library's
+    per-image path runs the same device helpers).  Box matching is compared exactly as it is; for probiou and OKS the scene keeps every oracle metric
+    1e-4 clear of every threshold, which is asserted."""
+    rows, count, batch, Wd, Hd = _strided_scene(kind)
+    t = torch.from_numpy
+    tb = {k: t(v) for k, v in batch.items()}
+    thr = torch.linspace(0.5, 0.95, 10)
+    if kind == "box":
+        got = engine.val_match(rows, count, batch, Wd, Hd)
+        want = [O.val_match_image(t(rows[b, :count[b]]), tb, b, Wd, Hd).numpy().astype(bool) for b in range(2)]
+        return _check_strided(got, want, count)
+    got = engine.val_match_rotated(rows, count, batch, Wd, Hd) if kind == "rot" else engine.val_match_pose(rows, count, batch, Wd, Hd, 5, 2)
+    want = []
+    for b in range(2):
+        sel, r = tb["batch_idx"] == b, t(rows[b, :count[b]])
+        if kind == "rot":
+            gt = torch.cat((tb["bboxes"][sel, :4] * torch.tensor([Wd, Hd, Wd, Hd]), tb["bboxes"][sel, 4:5]), 1)
+            metrics = [O.batch_probiou(gt, torch.cat((r[:, :4], r[:, 6:7]), 1))]
+            want.append([O.match_predictions(r[:, 5], tb["cls"][sel], metrics[0]).numpy().astype(bool)])
+        else:
+            iou, oks, wb, wp = R.val_image(r, tb["cls"][sel], tb["bboxes"][sel], tb["keypoints"][sel], Wd, Hd, 5, 2)
+            metrics = [iou, oks]
+            want.append([wb.numpy().astype(bool), wp.numpy().astype(bool)])
+        for m in metrics:
+            assert float((m[..., None] - thr).abs().min()) > 1e-4
+    if kind == "rot":
+        return _check_strided(got, [w[0] for w in want], count)
+    for i in range(2):
+        _check_strided(got[i], [w[i] for w in want], count)
+    assert not np.array_equal(want[0][0], want[0][1])                                   # the two metrics credit different detections
 
 
 @pytest.mark.parametrize("backend", BACKENDS)

@@ -16,6 +16,7 @@
 //   nms_greedy_big : n > 4096: serial workgroup-parallel sweep per kept box (O(kept*n), no n^2 matrix)
 // Compiled with -ffp-contract=off: every fp32 op below rounds exactly like the CPU reference.
 #include "ys_internal.h"
+#include "probiou.h"
 #include <atomic>
 #include <cstdio>
 #include <cstdlib>
@@ -437,22 +438,7 @@ nms_greedy_big_body(const float* __restrict__ pred, int C, int A, int nc, float 
   if (tid == 0) out_count[b] = kept;
 }
 
-// ------------------------------------------------------------------ oriented boxes: probiou + nms_rotated
-// Metrics.batch_probiou (Metrics.cs:223-258), operation for operation in fp32: box 1 = (x1, y1, a1, b1, c1), box 2 likewise
-__device__ inline float nms_probiou(float x1, float y1, float a1, float b1, float c1, float x2, float y2, float a2, float b2, float c2, float eps) {
-  const float sa = a1 + a2, sb = b1 + b2, sc = c1 + c2;
-  const float dy = y1 - y2, dx = x1 - x2;
-  const float det = sa * sb - sc * sc;
-  const float t1 = ((sa * (dy * dy) + sb * (dx * dx)) / (det + eps)) * 0.25f;
-  const float t2 = ((sc * (x2 - x1) * dy) / (det + eps)) * 0.5f;
-  const float d1 = fmaxf(a1 * b1 - c1 * c1, 0.f), d2 = fmaxf(a2 * b2 - c2 * c2, 0.f);
-  const float t3 = logf(det / (4.0f * sqrtf(d1 * d2) + eps) + eps) * 0.5f;
-  float bd = t1 + t2 + t3;
-  bd = fminf(fmaxf(bd, eps), 100.0f);
-  const float hd = sqrtf(1.0f - expf(-bd) + eps);
-  return 1.0f - hd;
-}
-
+// ------------------------------------------------------------------ oriented boxes: probiou + nms_rotated (nms_probiou / nms_obb_cov: probiou.h)
 // Ops.nms_rotated (Ops.cs:373-401, use_triu): in score order, candidate j is dropped iff ANY earlier candidate i < j has
 // probiou(i, j) >= threshold -- not the greedy rule of torchvision.nms: a dropped box still drops others.  One thread per j,
 // the earlier boxes staged through LDS in tiles of 256; O(n^2 / 2) evaluations per image, any n up to max_nms.
@@ -535,14 +521,6 @@ nms_rot_pick_kernel(const float* __restrict__ pred, int C, int A, int nc, int ma
   if (tid == 0) out_count[b] = kept;
 }
 
-// covariance terms of an oriented box (cx, cy, w, h, angle) -- _get_covariance_matrix (Metrics.cs:260-276), operation for operation in fp32
-__device__ inline void nms_obb_cov(const float* q, float& a, float& b, float& c) {
-  const float ga = q[2] * q[2] / 12.0f, gb = q[3] * q[3] / 12.0f;
-  const float cs = cosf(q[4]), sn = sinf(q[4]);
-  const float cos2 = cs * cs, sin2 = sn * sn;
-  a = ga * cos2 + gb * sin2; b = ga * sin2 + gb * cos2; c = (ga - gb) * cs * sn;
-}
-
 // Metrics.probiou (pairwise, Metrics.cs:137-177; CIoU adds only the aspect-ratio term) and Metrics.batch_probiou (N x M)
 __global__ void __launch_bounds__(256)
 probiou_kernel(const float* __restrict__ o1, const float* __restrict__ o2, long n, long m, int pairwise, int ciou, float eps, float* __restrict__ out) {
@@ -561,84 +539,6 @@ probiou_kernel(const float* __restrict__ o1, const float* __restrict__ o2, long 
     iou = iou - v * alpha;
   }
   out[idx] = iou;
-}
-
-// ------------------------------------------------------------------ the per-image part of Obber.Val (Models/Obber.cs:102-114) for a whole batch
-// val_match_kernel (valmetrics.hip) with Metrics.batch_probiou in place of box_iou: one workgroup per image; GT = bboxes[batch_idx == b] as
-// (cx W, cy H, w W, h H, angle) in collate order, prediction d = rows[b][d] columns 0..3 + column angle_col; obb1 = GT, obb2 = prediction
-// (Obber.cs:112).  The kernel lives here because it must evaluate the SAME nms_obb_cov / nms_probiou as probiou_kernel: `correct` then equals
-// ys_batch_probiou + ys_match_predictions per image bit for bit.  Each label's covariance terms are computed once into ws_gt (a pure function of
-// the label, so staging changes no value).  match_predictions restated as in valmetrics.hip: best(d) = the class-matching label with the largest IoU
-// (lower label index among equals), label l is credited at threshold t to the smallest d with best(d) == l and iou >= t.
-#define VMR_THREADS 256
-#define VMR_NT 10
-struct VmrThr { float t[VMR_NT]; };
-__global__ void __launch_bounds__(VMR_THREADS)
-val_match_rot_kernel(const float* __restrict__ rows, const int* __restrict__ count, int max_det, int row_stride, int angle_col,
-                     const float* __restrict__ batch_idx, const float* __restrict__ cls, const float* __restrict__ bboxes, int n_labels,
-                     float img_w, float img_h, VmrThr thr, int lcap, int* __restrict__ ws_lab /*[B][lcap]*/, float* __restrict__ ws_gt /*[B][lcap][5]*/,
-                     float* __restrict__ ws_best /*[B][max_det][2]*/, unsigned char* __restrict__ correct /*[B][max_det][10]*/, int* __restrict__ overflow) {
-  __shared__ int s_nl;
-  const int b = blockIdx.x, tid = threadIdx.x;
-  int* lab = ws_lab + (long)b * lcap;
-  float* gtc = ws_gt + (long)b * lcap * 5;
-  float* best = ws_best + (long)b * max_det * 2;
-  unsigned char* cor = correct + (long)b * max_det * VMR_NT;
-  const int D = count[b] < max_det ? count[b] : max_det;
-  for (int i = tid; i < max_det * VMR_NT; i += VMR_THREADS) cor[i] = 0;
-  // labels of this image, in collate order (boolean-mask indexing keeps the order, Obber.cs:104-108)
-  if (tid == 0) {
-    int k = 0;
-    for (int j = 0; j < n_labels; j++)
-      if ((int)batch_idx[j] == b) { if (k < lcap) lab[k] = j; k++; }
-    if (k > lcap) { atomicMax(overflow, k); k = lcap; }
-    s_nl = k;
-  }
-  __syncthreads();
-  const int L = s_nl;
-  for (int k = tid; k < L; k += VMR_THREADS) {
-    const int j = lab[k];
-    const float g[5] = {bboxes[5 * j] * img_w, bboxes[5 * j + 1] * img_h, bboxes[5 * j + 2] * img_w, bboxes[5 * j + 3] * img_h, bboxes[5 * j + 4]};
-    float a, bq, c;
-    nms_obb_cov(g, a, bq, c);
-    gtc[5 * k] = g[0]; gtc[5 * k + 1] = g[1]; gtc[5 * k + 2] = a; gtc[5 * k + 3] = bq; gtc[5 * k + 4] = c;
-  }
-  __syncthreads();
-  // best class-matching label per detection
-  for (int d = tid; d < D; d += VMR_THREADS) {
-    const float* pr = rows + ((long)b * max_det + d) * row_stride;
-    const float p[5] = {pr[0], pr[1], pr[2], pr[3], pr[angle_col]};
-    const float pc = pr[5];
-    float a2, b2, c2;
-    nms_obb_cov(p, a2, b2, c2);
-    float bi = -1.f; int bl = -1;
-    for (int k = 0; k < L; k++) {
-      if (cls[lab[k]] != pc) continue;
-      const float* g = gtc + 5 * k;
-      const float iou = nms_probiou(g[0], g[1], g[2], g[3], g[4], p[0], p[1], a2, b2, c2, 1e-7f);
-      if (iou > bi) { bi = iou; bl = k; }
-    }
-    best[2 * d] = bi;
-    best[2 * d + 1] = (float)bl;
-  }
-  __syncthreads();
-  // every (label, threshold): the first detection that chose this label and clears the threshold
-  for (int e = tid; e < L * VMR_NT; e += VMR_THREADS) {
-    const int k = e / VMR_NT, ti = e - k * VMR_NT;
-    const float t = thr.t[ti];
-    for (int d = 0; d < D; d++)
-      if ((int)best[2 * d + 1] == k && best[2 * d] >= t) { cor[d * VMR_NT + ti] = 1; break; }
-  }
-}
-
-int ys_val_match_rot_launch(hipStream_t st, const float* rows, const int* count, int B, int max_det, int row_stride, int angle_col,
-                            const float* batch_idx, const float* cls, const float* bboxes, int n_labels, float img_w, float img_h,
-                            const float* thr10, int lcap, int* ws_lab, float* ws_gt, float* ws_best, unsigned char* correct, int* overflow) {
-  VmrThr thr;
-  for (int i = 0; i < VMR_NT; i++) thr.t[i] = thr10[i];
-  YS_LAUNCH(val_match_rot_kernel, B, VMR_THREADS, st, rows, count, max_det, row_stride, angle_col, batch_idx, cls, bboxes, n_labels, img_w, img_h, thr,
-            lcap, ws_lab, ws_gt, ws_best, correct, overflow);
-  return YS_OK;
 }
 
 int ys_probiou_launch(hipStream_t st, const float* o1, const float* o2, long n, long m, int pairwise, int ciou, float eps, float* out) {

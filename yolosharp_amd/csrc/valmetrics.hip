@@ -11,9 +11,12 @@
 //   best(d)  = the class-matching label with the largest IoU for detection d (independent of t),
 //   label l is credited to the smallest d with best(d) == l and iou(best(d), d) >= t,   correct[d][t] = 1 for those d.
 // Equal IoUs are ordered by the sort implementation upstream (unpinned); here the lower label index wins.
+// The three stages -- gather the image's labels, best label per detection, credit per (label, threshold) -- are stated once (vm_gather_labels, VmBest,
+// vm_credit) and called by the four matching kernels, which differ in the metric only: box IoU (val_match_kernel), probiou (val_match_rot_kernel), box IoU
+// and OKS (val_match_pose_kernel), a supplied matrix (match_iou_kernel).
 // Compiled with -ffp-contract=off: the IoU arithmetic is the reference's operation order in plain fp32.
-#include "ys_internal.h"
-#include "ys_kernels.h"
+#include "ops_stage.h"
+#include "probiou.h"
 
 #define VM_THREADS 256
 #define VM_NT 10          // IoU thresholds linspace(0.5, 0.95, 10)
@@ -65,83 +68,140 @@ kpt_iou_kernel(const float* __restrict__ k1, int n, const float* __restrict__ k2
   out[i] = vm_oks(k1 + (long)r * K * 3, k2 + (long)c * K * D, area[r], K, D, sg, eps);
 }
 
-// one workgroup per image
+// ---- match_predictions' shared stages.  ws_lab [B][n_labels] (an image can hold all labels of the batch), ws_best [B][max_det][2 per metric],
+// correct [B][max_det][10].
+__device__ inline int vm_count(int count, int max_det) { return count < max_det ? (count > 0 ? count : 0) : max_det; }
+__device__ inline void vm_clear(unsigned char* __restrict__ cor, int n) {
+  for (int i = threadIdx.x; i < n; i += VM_THREADS) cor[i] = 0;
+}
+// stage 1: the labels of image b in collate order (boolean-mask indexing keeps the order, Detector.cs:110-112); *s_nl = their number, valid after the
+// caller's barrier
+__device__ inline void vm_gather_labels(const float* __restrict__ batch_idx, int n_labels, int b, int* __restrict__ lab, int* s_nl) {
+  if (threadIdx.x != 0) return;
+  int k = 0;
+  for (int j = 0; j < n_labels; j++)
+    if ((int)batch_idx[j] == b) lab[k++] = j;
+  *s_nl = k;
+}
+// stage 2: the class-matching label with the largest metric; the lower label index wins among equals
+struct VmBest {
+  float v = -1.f; int k = -1;
+  __device__ void offer(float metric, int label) { if (metric > v) { v = metric; k = label; } }
+  __device__ void store(float* __restrict__ best) const { best[0] = v; best[1] = (float)k; }
+};
+// stage 3: every (metric, label, threshold): the first detection that chose this label and clears the threshold.  A `best` row holds NM (value, label) pairs
+template <int NM>
+__device__ inline void vm_credit(const float* __restrict__ best, int L, int D, const VmThr& thr, unsigned char* __restrict__ cor0, unsigned char* __restrict__ cor1) {
+  for (int e = threadIdx.x; e < NM * L * VM_NT; e += VM_THREADS) {
+    const int mt = NM > 1 ? e / (L * VM_NT) : 0, r = e - mt * L * VM_NT;
+    const int k = r / VM_NT, ti = r - k * VM_NT;
+    const float t = thr.t[ti];
+    unsigned char* cor = mt ? cor1 : cor0;
+    for (int d = 0; d < D; d++)
+      if ((int)best[2 * (NM * d + mt) + 1] == k && best[2 * (NM * d + mt)] >= t) { cor[d * VM_NT + ti] = 1; break; }
+  }
+}
+
+// The per-image part of Detector.Val for a whole batch: one workgroup per image
 __global__ void __launch_bounds__(VM_THREADS)
 val_match_kernel(const float* __restrict__ rows, const int* __restrict__ count, int max_det, int row_stride,
                  const float* __restrict__ batch_idx, const float* __restrict__ cls, const float* __restrict__ bboxes, int n_labels,
-                 float img_w, float img_h, VmThr thr, int lcap, int* __restrict__ ws_lab /*[B][lcap]*/,
-                 float* __restrict__ ws_best /*[B][max_det][2]*/, unsigned char* __restrict__ correct /*[B][max_det][10]*/, int* __restrict__ overflow) {
+                 float img_w, float img_h, VmThr thr, int* __restrict__ ws_lab, float* __restrict__ ws_best, unsigned char* __restrict__ correct) {
   __shared__ int s_nl;
   const int b = blockIdx.x, tid = threadIdx.x;
-  int* lab = ws_lab + (long)b * lcap;
+  int* lab = ws_lab + (long)b * n_labels;
   float* best = ws_best + (long)b * max_det * 2;
   unsigned char* cor = correct + (long)b * max_det * VM_NT;
-  const int D = count[b] < max_det ? count[b] : max_det;
-  for (int i = tid; i < max_det * VM_NT; i += VM_THREADS) cor[i] = 0;
-  // labels of this image, in collate order (boolean-mask indexing keeps the order, Detector.cs:110-112)
-  if (tid == 0) {
-    int k = 0;
-    for (int j = 0; j < n_labels; j++)
-      if ((int)batch_idx[j] == b) { if (k < lcap) lab[k] = j; k++; }
-    if (k > lcap) { atomicMax(overflow, k); k = lcap; }
-    s_nl = k;
-  }
+  const int D = vm_count(count[b], max_det);
+  vm_clear(cor, max_det * VM_NT);
+  vm_gather_labels(batch_idx, n_labels, b, lab, &s_nl);
   __syncthreads();
   const int L = s_nl;
-  // best class-matching label per detection
   for (int d = tid; d < D; d += VM_THREADS) {
     const float* pr = rows + ((long)b * max_det + d) * row_stride;
     const float px1 = pr[0], py1 = pr[1], px2 = pr[2], py2 = pr[3], pc = pr[5];
-    float bi = -1.f; int bl = -1;
+    VmBest bi;
     for (int k = 0; k < L; k++) {
       const int j = lab[k];
       if (cls[j] != pc) continue;
       const float cx = bboxes[4 * j] * img_w, cy = bboxes[4 * j + 1] * img_h, w = bboxes[4 * j + 2] * img_w, h = bboxes[4 * j + 3] * img_h;
-      const float iou = vm_iou(cx - w / 2, cy - h / 2, cx + w / 2, cy + h / 2, px1, py1, px2, py2, 1e-7f);
-      if (iou > bi) { bi = iou; bl = k; }
+      bi.offer(vm_iou(cx - w / 2, cy - h / 2, cx + w / 2, cy + h / 2, px1, py1, px2, py2, 1e-7f), k);
     }
-    best[2 * d] = bi;
-    best[2 * d + 1] = (float)bl;
+    bi.store(best + 2 * d);
   }
   __syncthreads();
-  // every (label, threshold): the first detection that chose this label and clears the threshold
-  for (int e = tid; e < L * VM_NT; e += VM_THREADS) {
-    const int k = e / VM_NT, ti = e - k * VM_NT;
-    const float t = thr.t[ti];
-    for (int d = 0; d < D; d++)
-      if ((int)best[2 * d + 1] == k && best[2 * d] >= t) { cor[d * VM_NT + ti] = 1; break; }
-  }
+  vm_credit<1>(best, L, D, thr, cor, nullptr);
 }
 
-// The per-image part of PoseDetector.Val (Models/PoseDetector.cs:131-165) for a whole batch: val_match_kernel with two metrics.  One workgroup per image
-// gathers the image's labels in collate order and computes, once per label, what :140-156 compute per image: the xyxy box of bboxes * (W, H, W, H), area =
-// (x2 - x1) * (y2 - y1) * 0.53f and the keypoints * (W, H, 1) with the "seen" column of ones for 2-column labels.  Those are pure functions of the label, so
-// they live in workspaces indexed by the LABEL (ws_gt [n_labels][5], ws_kp [n_labels][K][3]): a label belongs to one image, no two workgroups write one word.
-// Per detection: the best class-matching label by vm_iou and the best by vm_oks (lower label index among equals); per (label, threshold) and metric: the
-// first detection that chose the label.  Same operations as ys_box_iou / ys_kpt_iou + ys_match_predictions per image, so both outputs equal that path bit for bit.
+// The per-image part of Obber.Val (Models/Obber.cs:102-114) for a whole batch: val_match_kernel with Metrics.batch_probiou in place of box_iou.  GT =
+// bboxes[batch_idx == b] as (cx W, cy H, w W, h H, angle) in collate order, prediction d = rows[b][d] columns 0..3 + column angle_col; obb1 = GT, obb2 =
+// prediction (Obber.cs:112).  nms_obb_cov / nms_probiou are probiou_kernel's (probiou.h), so `correct` equals ys_batch_probiou + ys_match_predictions per
+// image bit for bit.  Each label's covariance terms are computed once into ws_gt [n_labels][5], indexed by the LABEL (a pure function of the label, and a
+// label belongs to one image: no two workgroups write one word).
+__global__ void __launch_bounds__(VM_THREADS)
+val_match_rot_kernel(const float* __restrict__ rows, const int* __restrict__ count, int max_det, int row_stride, int angle_col,
+                     const float* __restrict__ batch_idx, const float* __restrict__ cls, const float* __restrict__ bboxes, int n_labels,
+                     float img_w, float img_h, VmThr thr, int* __restrict__ ws_lab, float* __restrict__ ws_gt, float* __restrict__ ws_best,
+                     unsigned char* __restrict__ correct) {
+  __shared__ int s_nl;
+  const int b = blockIdx.x, tid = threadIdx.x;
+  int* lab = ws_lab + (long)b * n_labels;
+  float* best = ws_best + (long)b * max_det * 2;
+  unsigned char* cor = correct + (long)b * max_det * VM_NT;
+  const int D = vm_count(count[b], max_det);
+  vm_clear(cor, max_det * VM_NT);
+  vm_gather_labels(batch_idx, n_labels, b, lab, &s_nl);
+  __syncthreads();
+  const int L = s_nl;
+  for (int k = tid; k < L; k += VM_THREADS) {
+    const int j = lab[k];
+    const float g[5] = {bboxes[5 * j] * img_w, bboxes[5 * j + 1] * img_h, bboxes[5 * j + 2] * img_w, bboxes[5 * j + 3] * img_h, bboxes[5 * j + 4]};
+    float a, bq, c;
+    nms_obb_cov(g, a, bq, c);
+    float* gt = ws_gt + 5L * j;
+    gt[0] = g[0]; gt[1] = g[1]; gt[2] = a; gt[3] = bq; gt[4] = c;
+  }
+  __syncthreads();
+  for (int d = tid; d < D; d += VM_THREADS) {
+    const float* pr = rows + ((long)b * max_det + d) * row_stride;
+    const float p[5] = {pr[0], pr[1], pr[2], pr[3], pr[angle_col]};
+    const float pc = pr[5];
+    float a2, b2, c2;
+    nms_obb_cov(p, a2, b2, c2);
+    VmBest bi;
+    for (int k = 0; k < L; k++) {
+      const long j = lab[k];
+      if (cls[j] != pc) continue;
+      const float* g = ws_gt + 5 * j;
+      bi.offer(nms_probiou(g[0], g[1], g[2], g[3], g[4], p[0], p[1], a2, b2, c2, 1e-7f), k);
+    }
+    bi.store(best + 2 * d);
+  }
+  __syncthreads();
+  vm_credit<1>(best, L, D, thr, cor, nullptr);
+}
+
+// The per-image part of PoseDetector.Val (Models/PoseDetector.cs:131-165) for a whole batch: val_match_kernel with two metrics.  Computed once per label,
+// what :140-156 compute per image: the xyxy box of bboxes * (W, H, W, H), area = (x2 - x1) * (y2 - y1) * 0.53f and the keypoints * (W, H, 1) with the
+// "seen" column of ones for 2-column labels, in workspaces indexed by the label like ws_gt above (ws_gt [n_labels][5], ws_kp [n_labels][K][3]).
+// Per detection: the best class-matching label by vm_iou and the best by vm_oks, in a ws_best row of four.  Same operations as ys_box_iou / ys_kpt_iou +
+// ys_match_predictions per image, so both outputs equal that path bit for bit.
 __global__ void __launch_bounds__(VM_THREADS)
 val_match_pose_kernel(const float* __restrict__ rows, const int* __restrict__ count, int max_det, int row_stride, int kpt_col, int K, int D,
                       const float* __restrict__ batch_idx, const float* __restrict__ cls, const float* __restrict__ bboxes,
                       const float* __restrict__ keypoints /*[n_labels][K][LD]*/, int LD, int n_labels, float img_w, float img_h, VmThr thr, KptSigma sg,
-                      int lcap, int* __restrict__ ws_lab /*[B][lcap]*/, float* __restrict__ ws_gt /*[n_labels][5]*/, float* __restrict__ ws_kp /*[n_labels][K][3]*/,
-                      float* __restrict__ ws_best /*[B][max_det][4]*/, unsigned char* __restrict__ correct_box /*[B][max_det][10]*/,
-                      unsigned char* __restrict__ correct_pose /*[B][max_det][10]*/, int* __restrict__ overflow) {
+                      int* __restrict__ ws_lab, float* __restrict__ ws_gt, float* __restrict__ ws_kp, float* __restrict__ ws_best,
+                      unsigned char* __restrict__ correct_box, unsigned char* __restrict__ correct_pose) {
   __shared__ int s_nl;
   const int b = blockIdx.x, tid = threadIdx.x;
-  int* lab = ws_lab + (long)b * lcap;
+  int* lab = ws_lab + (long)b * n_labels;
   float* best = ws_best + (long)b * max_det * 4;
   unsigned char* cob = correct_box + (long)b * max_det * VM_NT;
   unsigned char* cop = correct_pose + (long)b * max_det * VM_NT;
-  const int Dn = count[b] < max_det ? (count[b] > 0 ? count[b] : 0) : max_det;
-  for (int i = tid; i < max_det * VM_NT; i += VM_THREADS) { cob[i] = 0; cop[i] = 0; }
-  // labels of this image, in collate order (boolean-mask indexing keeps the order, PoseDetector.cs:138-141)
-  if (tid == 0) {
-    int k = 0;
-    for (int j = 0; j < n_labels; j++)
-      if ((int)batch_idx[j] == b) { if (k < lcap) lab[k] = j; k++; }
-    if (k > lcap) { atomicMax(overflow, k); k = lcap; }
-    s_nl = k;
-  }
+  const int Dn = vm_count(count[b], max_det);
+  vm_clear(cob, max_det * VM_NT);
+  vm_clear(cop, max_det * VM_NT);
+  vm_gather_labels(batch_idx, n_labels, b, lab, &s_nl);
   __syncthreads();
   const int L = s_nl;
   for (int k = tid; k < L; k += VM_THREADS) {                    // PoseDetector.cs:140, 148, 156
@@ -159,32 +219,22 @@ val_match_pose_kernel(const float* __restrict__ rows, const int* __restrict__ co
     dst[0] = src[0] * img_w; dst[1] = src[1] * img_h; dst[2] = LD == 3 ? src[2] : 1.0f;      // (w, h, 1): the third factor is exact
   }
   __syncthreads();
-  // best class-matching label per detection, by box IoU and by OKS
   for (int d = tid; d < Dn; d += VM_THREADS) {
     const float* pr = rows + ((long)b * max_det + d) * row_stride;
     const float px1 = pr[0], py1 = pr[1], px2 = pr[2], py2 = pr[3], pc = pr[5];
-    float bi = -1.f, bo = -1.f; int bl = -1, ol = -1;
+    VmBest bi, bo;
     for (int k = 0; k < L; k++) {
       const long j = lab[k];
       if (cls[j] != pc) continue;
       const float* g = ws_gt + 5 * j;
-      const float iou = vm_iou(g[0], g[1], g[2], g[3], px1, py1, px2, py2, 1e-7f);
-      if (iou > bi) { bi = iou; bl = k; }
-      const float oks = vm_oks(ws_kp + j * K * 3, pr + kpt_col, g[4], K, D, sg, 1e-7f);
-      if (oks > bo) { bo = oks; ol = k; }
+      bi.offer(vm_iou(g[0], g[1], g[2], g[3], px1, py1, px2, py2, 1e-7f), k);
+      bo.offer(vm_oks(ws_kp + j * K * 3, pr + kpt_col, g[4], K, D, sg, 1e-7f), k);
     }
-    best[4 * d] = bi; best[4 * d + 1] = (float)bl; best[4 * d + 2] = bo; best[4 * d + 3] = (float)ol;
+    bi.store(best + 4 * d);
+    bo.store(best + 4 * d + 2);
   }
   __syncthreads();
-  // every (metric, label, threshold): the first detection that chose this label and clears the threshold
-  for (int e = tid; e < 2 * L * VM_NT; e += VM_THREADS) {
-    const int mt = e / (L * VM_NT), r = e - mt * L * VM_NT;
-    const int k = r / VM_NT, ti = r - k * VM_NT;
-    const float t = thr.t[ti];
-    unsigned char* cor = mt ? cop : cob;
-    for (int d = 0; d < Dn; d++)
-      if ((int)best[4 * d + 2 * mt + 1] == k && best[4 * d + 2 * mt] >= t) { cor[d * VM_NT + ti] = 1; break; }
-  }
+  vm_credit<2>(best, L, Dn, thr, cob, cop);
 }
 
 // Metrics.mask_iou (Utils/Metrics.cs:120-125) as Segmenter.Val calls it (Models/Segmenter.cs:131-143): mask1[k] = (gt_ids == k + 1)
@@ -223,31 +273,20 @@ mask_iou_kernel(const float* __restrict__ gt_ids, int nl, const unsigned char* _
   }
 }
 
-// match_predictions (Models/YoloBaseTaskModel.cs:377-446) on a caller-supplied IoU matrix [L][D]; same restatement as
-// val_match_kernel above (one workgroup).
+// match_predictions (Models/YoloBaseTaskModel.cs:377-446) on a caller-supplied IoU matrix [L][D]: stages 2 and 3 (one workgroup).
 __global__ void __launch_bounds__(VM_THREADS)
 match_iou_kernel(const float* __restrict__ pred_cls, int D, const float* __restrict__ true_cls, int L, const float* __restrict__ iou,
                  VmThr thr, float* __restrict__ best /*[D][2]*/, unsigned char* __restrict__ cor /*[D][10]*/) {
-  const int tid = threadIdx.x;
-  for (int i = tid; i < D * VM_NT; i += VM_THREADS) cor[i] = 0;
-  for (int d = tid; d < D; d += VM_THREADS) {
+  vm_clear(cor, D * VM_NT);
+  for (int d = threadIdx.x; d < D; d += VM_THREADS) {
     const float pc = pred_cls[d];
-    float bi = -1.f; int bl = -1;
-    for (int k = 0; k < L; k++) {
-      if (true_cls[k] != pc) continue;
-      const float v = iou[(long)k * D + d];
-      if (v > bi) { bi = v; bl = k; }
-    }
-    best[2 * d] = bi;
-    best[2 * d + 1] = (float)bl;
+    VmBest bi;
+    for (int k = 0; k < L; k++)
+      if (true_cls[k] == pc) bi.offer(iou[(long)k * D + d], k);
+    bi.store(best + 2 * d);
   }
   __syncthreads();
-  for (int e = tid; e < L * VM_NT; e += VM_THREADS) {
-    const int k = e / VM_NT, ti = e - k * VM_NT;
-    const float t = thr.t[ti];
-    for (int d = 0; d < D; d++)
-      if ((int)best[2 * d + 1] == k && best[2 * d] >= t) { cor[d * VM_NT + ti] = 1; break; }
-  }
+  vm_credit<1>(best, L, D, thr, cor, nullptr);
 }
 
 // torch.linspace(0.5, 0.95, 10) in fp32 (ATen: step = (end-start)/(steps-1); first half start + step*i, second half
@@ -260,6 +299,43 @@ static VmThr vm_thresholds() {
   return t;
 }
 
+// Staging of the validation entry points: device pointers are used as they are, host arrays are copied to scratch that lives as long as the stage.
+// rc: the first failure (its error text is set); finish() copies the outputs back and waits for the stream whenever scratch is in use.
+namespace {
+struct VmStage {
+  const char* who; hipStream_t st; bool on_device; int rc = YS_OK;
+  struct Back { void* host; const void* dev; size_t bytes; };
+  std::vector<void*> tmp; std::vector<Back> back;
+  VmStage(const char* w, ys_ctx* ctx, int od) : who(w), st(ctx->stream), on_device(od != 0) {}
+  ~VmStage() { for (void* p : tmp) (void)hipFree(p); }
+  void* alloc(size_t bytes) {
+    void* p = nullptr;
+    if (rc != YS_OK) return nullptr;
+    if (hipMalloc(&p, bytes ? bytes : 4) != hipSuccess) { ys_set_error("%s: out of device memory", who); rc = YS_ERR_OOM; return nullptr; }
+    tmp.push_back(p);
+    return p;
+  }
+  const void* in(const void* host, size_t bytes) {
+    if (on_device || !host) return host;
+    void* d = alloc(bytes);
+    if (d && bytes) rc = h2d(st, d, host, bytes);
+    return d;
+  }
+  void* out(void* host, size_t bytes) {
+    if (on_device) return host;
+    void* d = alloc(bytes);
+    back.push_back(Back{host, d, bytes});
+    return d;
+  }
+  int finish() {
+    YS_CHECK_HIP(hipGetLastError());
+    for (const Back& o : back) YS_TRY(d2h(st, o.host, o.dev, o.bytes));
+    if (!tmp.empty()) YS_CHECK_HIP(hipStreamSynchronize(st));      // the scratch is released when the stage goes out of scope
+    return YS_OK;
+  }
+};
+}  // namespace
+
 extern "C" {
 
 int ys_box_iou(ys_ctx* ctx, const float* box1, int n, const float* box2, int m, float eps, int on_device, float* iou) {
@@ -267,41 +343,14 @@ int ys_box_iou(ys_ctx* ctx, const float* box1, int n, const float* box2, int m, 
   if ((long)n * m == 0) return YS_OK;
   YS_REQUIRE(box1 && box2, "ys_box_iou: null boxes");
   YS_CHECK_HIP(hipSetDevice(ctx->device));
-  hipStream_t st = ctx->stream;
-  if (on_device) {
-    YS_LAUNCH(box_iou_kernel, ys_cdiv((long)n * m, VM_THREADS), VM_THREADS, st, box1, n, box2, m, eps, iou);
-    return YS_OK;
-  }
-  float *d1 = nullptr, *d2 = nullptr, *d3 = nullptr;
-  YS_CHECK_HIP(hipMalloc(&d1, (size_t)n * 16));
-  YS_CHECK_HIP(hipMalloc(&d2, (size_t)m * 16));
-  YS_CHECK_HIP(hipMalloc(&d3, (size_t)n * m * 4));
-  hipMemcpyAsync(d1, box1, (size_t)n * 16, hipMemcpyHostToDevice, st);
-  hipMemcpyAsync(d2, box2, (size_t)m * 16, hipMemcpyHostToDevice, st);
-  YS_LAUNCH(box_iou_kernel, ys_cdiv((long)n * m, VM_THREADS), VM_THREADS, st, (const float*)d1, n, (const float*)d2, m, eps, d3);
-  hipError_t e = hipMemcpyAsync(iou, d3, (size_t)n * m * 4, hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  hipFree(d1); hipFree(d2); hipFree(d3);
-  if (e != hipSuccess) { ys_set_error("ys_box_iou: %s", hipGetErrorString(e)); return YS_ERR_HIP; }
-  return YS_OK;
+  VmStage sg("ys_box_iou", ctx, on_device);
+  const float* d1 = (const float*)sg.in(box1, (size_t)n * 16);
+  const float* d2 = (const float*)sg.in(box2, (size_t)m * 16);
+  float* d_iou = (float*)sg.out(iou, (size_t)n * m * 4);
+  YS_TRY(sg.rc);
+  YS_LAUNCH(box_iou_kernel, ys_cdiv((long)n * m, VM_THREADS), VM_THREADS, sg.st, d1, n, d2, m, eps, d_iou);
+  return sg.finish();
 }
-
-// scratch + staging helper for the small validation calls: device pointers are used as they are, host arrays are staged
-namespace {
-struct VmStage {
-  hipStream_t st; bool on_device; std::vector<void*> tmp; bool ok = true;
-  VmStage(hipStream_t s, int od) : st(s), on_device(od != 0) {}
-  ~VmStage() { for (void* p : tmp) hipFree(p); }
-  void* alloc(size_t bytes) { void* p = nullptr; if (hipMalloc(&p, bytes ? bytes : 4) != hipSuccess) { ok = false; return nullptr; } tmp.push_back(p); return p; }
-  const void* in(const void* host, size_t bytes) {
-    if (on_device || !host) return host;
-    void* d = alloc(bytes);
-    if (d && bytes && hipMemcpyAsync(d, host, bytes, hipMemcpyHostToDevice, st) != hipSuccess) ok = false;
-    return d;
-  }
-  void* out(void* host, size_t bytes) { return on_device ? host : alloc(bytes); }
-};
-}  // namespace
 
 int ys_mask_iou(ys_ctx* ctx, const float* gt_ids, int nl, const uint8_t* pred_masks, int n, int npix, float eps, int on_device, float* iou) {
   YS_REQUIRE(ctx && iou && nl >= 0 && n >= 0 && npix > 0, "ys_mask_iou: bad argument");
@@ -310,19 +359,13 @@ int ys_mask_iou(ys_ctx* ctx, const float* gt_ids, int nl, const uint8_t* pred_ma
   YS_REQUIRE(npix < (1 << 24), "ys_mask_iou: %d pixels exceed the exact-integer range of the fp32 reference", npix);
   YS_REQUIRE(nl <= 8192, "ys_mask_iou: %d labels exceed the LDS histogram capacity (8192)", nl);
   YS_CHECK_HIP(hipSetDevice(ctx->device));
-  hipStream_t st = ctx->stream;
-  VmStage sg(st, on_device);
+  VmStage sg("ys_mask_iou", ctx, on_device);
   const float* d_ids = (const float*)sg.in(gt_ids, (size_t)npix * 4);
   const unsigned char* d_pm = (const unsigned char*)sg.in(pred_masks, (size_t)n * npix);
   float* d_iou = (float*)sg.out(iou, (size_t)nl * n * 4);
-  if (!sg.ok) { ys_set_error("ys_mask_iou: out of device memory"); return YS_ERR_OOM; }
-  YS_LAUNCH_LDS(mask_iou_kernel, n, VM_THREADS, (size_t)2 * nl * sizeof(int) + 16, st, d_ids, nl, d_pm, n, npix, eps, d_iou);
-  YS_CHECK_HIP(hipGetLastError());
-  if (!on_device) {
-    YS_CHECK_HIP(hipMemcpyAsync(iou, d_iou, (size_t)nl * n * 4, hipMemcpyDeviceToHost, st));
-    YS_CHECK_HIP(hipStreamSynchronize(st));
-  }
-  return YS_OK;
+  YS_TRY(sg.rc);
+  YS_LAUNCH_LDS(mask_iou_kernel, n, VM_THREADS, (size_t)2 * nl * sizeof(int) + 16, sg.st, d_ids, nl, d_pm, n, npix, eps, d_iou);
+  return sg.finish();
 }
 
 // OKS_SIGMA (PoseDetector.cs:12-19) when K == 17, else 1 / K (Metrics.cs:205)
@@ -341,21 +384,14 @@ int ys_kpt_iou(ys_ctx* ctx, const float* kpt1, int n, const float* kpt2, int m, 
   if ((long)n * m == 0) return YS_OK;
   YS_REQUIRE(kpt1 && kpt2 && area, "ys_kpt_iou: null argument");
   YS_CHECK_HIP(hipSetDevice(ctx->device));
-  hipStream_t st = ctx->stream;
-  VmStage sg(st, on_device);
+  VmStage sg("ys_kpt_iou", ctx, on_device);
   const float* d1 = (const float*)sg.in(kpt1, (size_t)n * kpt_num * 3 * 4);
   const float* d2 = (const float*)sg.in(kpt2, (size_t)m * kpt_num * kpt_dim * 4);
   const float* da = (const float*)sg.in(area, (size_t)n * 4);
   float* d_iou = (float*)sg.out(iou, (size_t)n * m * 4);
-  if (!sg.ok) { ys_set_error("ys_kpt_iou: out of device memory"); return YS_ERR_OOM; }
-  const KptSigma ks = vm_sigmas(kpt_num);
-  YS_LAUNCH(kpt_iou_kernel, ys_cdiv((long)n * m, VM_THREADS), VM_THREADS, st, d1, n, d2, m, da, kpt_num, kpt_dim, ks, eps, d_iou);
-  YS_CHECK_HIP(hipGetLastError());
-  if (!on_device) {
-    YS_CHECK_HIP(hipMemcpyAsync(iou, d_iou, (size_t)n * m * 4, hipMemcpyDeviceToHost, st));
-    YS_CHECK_HIP(hipStreamSynchronize(st));
-  }
-  return YS_OK;
+  YS_TRY(sg.rc);
+  YS_LAUNCH(kpt_iou_kernel, ys_cdiv((long)n * m, VM_THREADS), VM_THREADS, sg.st, d1, n, d2, m, da, kpt_num, kpt_dim, vm_sigmas(kpt_num), eps, d_iou);
+  return sg.finish();
 }
 
 int ys_match_predictions(ys_ctx* ctx, const float* pred_cls, int n, const float* true_cls, int nl, const float* iou, int on_device,
@@ -364,19 +400,35 @@ int ys_match_predictions(ys_ctx* ctx, const float* pred_cls, int n, const float*
   if (n == 0) return YS_OK;
   YS_REQUIRE(pred_cls && correct && (nl == 0 || (true_cls && iou)), "ys_match_predictions: null argument");
   YS_CHECK_HIP(hipSetDevice(ctx->device));
-  hipStream_t st = ctx->stream;
-  VmStage sg(st, on_device);
+  VmStage sg("ys_match_predictions", ctx, on_device);
   const float* d_pc = (const float*)sg.in(pred_cls, (size_t)n * 4);
   const float* d_tc = (const float*)sg.in(true_cls, (size_t)nl * 4);
   const float* d_iou = (const float*)sg.in(iou, (size_t)nl * n * 4);
   unsigned char* d_cor = (unsigned char*)sg.out(correct, (size_t)n * VM_NT);
   float* d_best = (float*)sg.alloc((size_t)n * 8);
-  if (!sg.ok) { ys_set_error("ys_match_predictions: out of device memory"); return YS_ERR_OOM; }
-  YS_LAUNCH(match_iou_kernel, 1, VM_THREADS, st, d_pc, n, d_tc, nl, d_iou, vm_thresholds(), d_best, d_cor);
-  if (!on_device) YS_CHECK_HIP(hipMemcpyAsync(correct, d_cor, (size_t)n * VM_NT, hipMemcpyDeviceToHost, st));
-  YS_CHECK_HIP(hipStreamSynchronize(st));      // the scratch buffers are released on return
-  return YS_OK;
+  YS_TRY(sg.rc);
+  YS_LAUNCH(match_iou_kernel, 1, VM_THREADS, sg.st, d_pc, n, d_tc, nl, d_iou, vm_thresholds(), d_best, d_cor);
+  return sg.finish();
 }
+
+// what the three batched entry points stage alike: rows [batch][max_det][row_stride], count [batch], the label arrays (bboxes of box_cols columns), and the
+// scratch ws_lab [batch][n_labels] / ws_best [batch][max_det][2 per metric]
+namespace {
+struct VmBatch {
+  const float *rows, *bi, *cl, *bb; const int* cnt; int* lab; float* best; size_t ncor;
+  VmBatch(VmStage& sg, const float* rows_, const int32_t* count, int batch, int max_det, int row_stride, const float* batch_idx, const float* cls,
+          const float* bboxes, int box_cols, int n_labels, int metrics) {
+    ncor = (size_t)batch * max_det * VM_NT;
+    lab = (int*)sg.alloc((size_t)batch * n_labels * 4);
+    best = (float*)sg.alloc((size_t)batch * max_det * 8 * metrics);
+    rows = (const float*)sg.in(rows_, (size_t)batch * max_det * row_stride * 4);
+    cnt = (const int*)sg.in(count, (size_t)batch * 4);
+    bi = (const float*)sg.in(batch_idx, (size_t)n_labels * 4);
+    cl = (const float*)sg.in(cls, (size_t)n_labels * 4);
+    bb = (const float*)sg.in(bboxes, (size_t)n_labels * box_cols * 4);
+  }
+};
+}  // namespace
 
 int ys_val_match_batched(ys_ctx* ctx, const float* rows, const int32_t* count, int on_device, int batch, int max_det, int row_stride,
                          const float* batch_idx, const float* cls, const float* bboxes, int n_labels, float img_w, float img_h,
@@ -385,49 +437,16 @@ int ys_val_match_batched(ys_ctx* ctx, const float* rows, const int32_t* count, i
   YS_REQUIRE(batch > 0 && max_det > 0 && row_stride >= 6 && n_labels >= 0, "ys_val_match_batched: bad shape");
   YS_REQUIRE(n_labels == 0 || (batch_idx && cls && bboxes), "ys_val_match_batched: null label arrays");
   YS_CHECK_HIP(hipSetDevice(ctx->device));
-  hipStream_t st = ctx->stream;
-  const int lcap = n_labels > 0 ? n_labels : 1;          // an image can hold all labels of the batch
-  const size_t nrow = (size_t)batch * max_det * row_stride, ncor = (size_t)batch * max_det * VM_NT;
-  const float *d_rows = rows, *d_bi = batch_idx, *d_cl = cls, *d_bb = bboxes;
-  const int* d_cnt = count;
-  unsigned char* d_cor = correct;
-  std::vector<void*> tmp;
-  auto dalloc = [&](size_t bytes) -> void* { void* p = nullptr; if (hipMalloc(&p, bytes ? bytes : 4) != hipSuccess) return nullptr; tmp.push_back(p); return p; };
-  int* d_lab = (int*)dalloc((size_t)batch * lcap * 4);
-  float* d_best = (float*)dalloc((size_t)batch * max_det * 8);
-  int* d_ovf = (int*)dalloc(4);
-  bool ok = d_lab && d_best && d_ovf;
-  if (ok && !on_device) {
-    float* a = (float*)dalloc(nrow * 4); int* c = (int*)dalloc((size_t)batch * 4);
-    float* b1 = (float*)dalloc((size_t)lcap * 4); float* b2 = (float*)dalloc((size_t)lcap * 4); float* b3 = (float*)dalloc((size_t)lcap * 16);
-    unsigned char* co = (unsigned char*)dalloc(ncor);
-    ok = a && c && b1 && b2 && b3 && co;
-    if (ok) {
-      hipMemcpyAsync(a, rows, nrow * 4, hipMemcpyHostToDevice, st);
-      hipMemcpyAsync(c, count, (size_t)batch * 4, hipMemcpyHostToDevice, st);
-      if (n_labels > 0) {
-        hipMemcpyAsync(b1, batch_idx, (size_t)n_labels * 4, hipMemcpyHostToDevice, st);
-        hipMemcpyAsync(b2, cls, (size_t)n_labels * 4, hipMemcpyHostToDevice, st);
-        hipMemcpyAsync(b3, bboxes, (size_t)n_labels * 16, hipMemcpyHostToDevice, st);
-      }
-      d_rows = a; d_cnt = c; d_bi = b1; d_cl = b2; d_bb = b3; d_cor = co;
-    }
-  }
-  int rc = YS_OK;
-  if (!ok) { ys_set_error("ys_val_match_batched: out of device memory"); rc = YS_ERR_OOM; }
-  if (rc == YS_OK) {
-    hipMemsetAsync(d_ovf, 0, 4, st);
-    YS_LAUNCH(val_match_kernel, batch, VM_THREADS, st, d_rows, d_cnt, max_det, row_stride, d_bi, d_cl, d_bb, n_labels, img_w, img_h,
-              vm_thresholds(), lcap, d_lab, d_best, d_cor, d_ovf);
-    hipError_t e = on_device ? hipSuccess : hipMemcpyAsync(correct, d_cor, ncor, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);      // the scratch buffers are released below
-    if (e != hipSuccess) { ys_set_error("ys_val_match_batched: %s", hipGetErrorString(e)); rc = YS_ERR_HIP; }
-  }
-  for (void* p : tmp) hipFree(p);
-  return rc;
+  VmStage sg("ys_val_match_batched", ctx, on_device);
+  const VmBatch v(sg, rows, count, batch, max_det, row_stride, batch_idx, cls, bboxes, 4, n_labels, 1);
+  unsigned char* d_cor = (unsigned char*)sg.out(correct, v.ncor);
+  YS_TRY(sg.rc);
+  YS_LAUNCH(val_match_kernel, batch, VM_THREADS, sg.st, v.rows, v.cnt, max_det, row_stride, v.bi, v.cl, v.bb, n_labels, img_w, img_h, vm_thresholds(),
+            v.lab, v.best, d_cor);
+  return sg.finish();
 }
 
-// Obber.Val's per-image part (Models/Obber.cs:102-114) for a batch: val_match_rot_kernel (nms.hip, beside the probiou it shares with ys_batch_probiou)
+// Obber.Val's per-image part (Models/Obber.cs:102-114) for a batch: val_match_rot_kernel above
 int ys_val_match_rotated_batched(ys_ctx* ctx, const float* rows, const int32_t* count, int on_device, int batch, int max_det, int row_stride,
                                  int angle_col, const float* batch_idx, const float* cls, const float* bboxes, int n_labels, float img_w,
                                  float img_h, uint8_t* correct) {
@@ -436,28 +455,14 @@ int ys_val_match_rotated_batched(ys_ctx* ctx, const float* rows, const int32_t* 
   YS_REQUIRE(angle_col >= 6 && angle_col < row_stride, "ys_val_match_rotated_batched: angle column %d outside [6, %d)", angle_col, row_stride);
   YS_REQUIRE(n_labels == 0 || (batch_idx && cls && bboxes), "ys_val_match_rotated_batched: null label arrays");
   YS_CHECK_HIP(hipSetDevice(ctx->device));
-  hipStream_t st = ctx->stream;
-  const int lcap = n_labels > 0 ? n_labels : 1;          // an image can hold all labels of the batch
-  const size_t nrow = (size_t)batch * max_det * row_stride, ncor = (size_t)batch * max_det * VM_NT;
-  VmStage sg(st, on_device);
-  int* d_lab = (int*)sg.alloc((size_t)batch * lcap * 4);
-  float* d_gt = (float*)sg.alloc((size_t)batch * lcap * 20);
-  float* d_best = (float*)sg.alloc((size_t)batch * max_det * 8);
-  int* d_ovf = (int*)sg.alloc(4);
-  const float* d_rows = (const float*)sg.in(rows, nrow * 4);
-  const int* d_cnt = (const int*)sg.in(count, (size_t)batch * 4);
-  const float* d_bi = (const float*)sg.in(batch_idx, (size_t)n_labels * 4);
-  const float* d_cl = (const float*)sg.in(cls, (size_t)n_labels * 4);
-  const float* d_bb = (const float*)sg.in(bboxes, (size_t)n_labels * 20);
-  unsigned char* d_cor = (unsigned char*)sg.out(correct, ncor);
-  if (!sg.ok) { ys_set_error("ys_val_match_rotated_batched: out of device memory"); return YS_ERR_OOM; }
-  YS_CHECK_HIP(hipMemsetAsync(d_ovf, 0, 4, st));
-  const VmThr thr = vm_thresholds();
-  YS_TRY(ys_val_match_rot_launch(st, d_rows, d_cnt, batch, max_det, row_stride, angle_col, d_bi, d_cl, d_bb, n_labels, img_w, img_h, thr.t, lcap,
-                                 d_lab, d_gt, d_best, d_cor, d_ovf));
-  if (!on_device) YS_CHECK_HIP(hipMemcpyAsync(correct, d_cor, ncor, hipMemcpyDeviceToHost, st));
-  YS_CHECK_HIP(hipStreamSynchronize(st));      // the scratch buffers are released on return
-  return YS_OK;
+  VmStage sg("ys_val_match_rotated_batched", ctx, on_device);
+  const VmBatch v(sg, rows, count, batch, max_det, row_stride, batch_idx, cls, bboxes, 5, n_labels, 1);
+  float* d_gt = (float*)sg.alloc((size_t)n_labels * 20);
+  unsigned char* d_cor = (unsigned char*)sg.out(correct, v.ncor);
+  YS_TRY(sg.rc);
+  YS_LAUNCH(val_match_rot_kernel, batch, VM_THREADS, sg.st, v.rows, v.cnt, max_det, row_stride, angle_col, v.bi, v.cl, v.bb, n_labels, img_w, img_h,
+            vm_thresholds(), v.lab, d_gt, v.best, d_cor);
+  return sg.finish();
 }
 
 // PoseDetector.Val's per-image part (Models/PoseDetector.cs:131-165) for a batch: val_match_pose_kernel above
@@ -473,35 +478,18 @@ int ys_val_match_pose_batched(ys_ctx* ctx, const float* rows, const int32_t* cou
              kpt_col + kpt_num * kpt_dim, row_stride);
   YS_REQUIRE(n_labels == 0 || (batch_idx && cls && bboxes && keypoints), "ys_val_match_pose_batched: null label arrays");
   YS_CHECK_HIP(hipSetDevice(ctx->device));
-  hipStream_t st = ctx->stream;
-  const int lcap = n_labels > 0 ? n_labels : 1;          // an image can hold all labels of the batch
-  const size_t nrow = (size_t)batch * max_det * row_stride, ncor = (size_t)batch * max_det * VM_NT;
+  VmStage sg("ys_val_match_pose_batched", ctx, on_device);
+  const VmBatch v(sg, rows, count, batch, max_det, row_stride, batch_idx, cls, bboxes, 4, n_labels, 2);
   const size_t nkp = (size_t)n_labels * kpt_num;
-  VmStage sg(st, on_device);
-  int* d_lab = (int*)sg.alloc((size_t)batch * lcap * 4);
-  float* d_gt = (float*)sg.alloc((size_t)lcap * 20);
-  float* d_kp = (float*)sg.alloc((size_t)lcap * kpt_num * 12);
-  float* d_best = (float*)sg.alloc((size_t)batch * max_det * 16);
-  int* d_ovf = (int*)sg.alloc(4);
-  const float* d_rows = (const float*)sg.in(rows, nrow * 4);
-  const int* d_cnt = (const int*)sg.in(count, (size_t)batch * 4);
-  const float* d_bi = (const float*)sg.in(batch_idx, (size_t)n_labels * 4);
-  const float* d_cl = (const float*)sg.in(cls, (size_t)n_labels * 4);
-  const float* d_bb = (const float*)sg.in(bboxes, (size_t)n_labels * 16);
+  float* d_gt = (float*)sg.alloc((size_t)n_labels * 20);
+  float* d_kp = (float*)sg.alloc(nkp * 12);
   const float* d_kl = (const float*)sg.in(keypoints, nkp * label_kpt_dim * 4);
-  unsigned char* d_cb = (unsigned char*)sg.out(correct_box, ncor);
-  unsigned char* d_cp = (unsigned char*)sg.out(correct_pose, ncor);
-  if (!sg.ok) { ys_set_error("ys_val_match_pose_batched: out of device memory"); return YS_ERR_OOM; }
-  YS_CHECK_HIP(hipMemsetAsync(d_ovf, 0, 4, st));
-  YS_LAUNCH(val_match_pose_kernel, batch, VM_THREADS, st, d_rows, d_cnt, max_det, row_stride, kpt_col, kpt_num, kpt_dim, d_bi, d_cl, d_bb, d_kl,
-            label_kpt_dim, n_labels, img_w, img_h, vm_thresholds(), vm_sigmas(kpt_num), lcap, d_lab, d_gt, d_kp, d_best, d_cb, d_cp, d_ovf);
-  YS_CHECK_HIP(hipGetLastError());
-  if (!on_device) {
-    YS_CHECK_HIP(hipMemcpyAsync(correct_box, d_cb, ncor, hipMemcpyDeviceToHost, st));
-    YS_CHECK_HIP(hipMemcpyAsync(correct_pose, d_cp, ncor, hipMemcpyDeviceToHost, st));
-  }
-  YS_CHECK_HIP(hipStreamSynchronize(st));      // the scratch buffers are released on return
-  return YS_OK;
+  unsigned char* d_cb = (unsigned char*)sg.out(correct_box, v.ncor);
+  unsigned char* d_cp = (unsigned char*)sg.out(correct_pose, v.ncor);
+  YS_TRY(sg.rc);
+  YS_LAUNCH(val_match_pose_kernel, batch, VM_THREADS, sg.st, v.rows, v.cnt, max_det, row_stride, kpt_col, kpt_num, kpt_dim, v.bi, v.cl, v.bb, d_kl,
+            label_kpt_dim, n_labels, img_w, img_h, vm_thresholds(), vm_sigmas(kpt_num), v.lab, d_gt, d_kp, v.best, d_cb, d_cp);
+  return sg.finish();
 }
 
 }  // extern "C"

@@ -109,8 +109,3 @@ struct YsKprofScope {
 int ys_nms_launch(ys_ctx* ctx, float* pred_dev, int B, int C, int A, float conf, float iou, int max_det,
                   int nc, int max_nms, int max_wh, float* out_rows, int64_t* out_keep, int32_t* out_count, int rotated = 0);
 int ys_probiou_launch(hipStream_t st, const float* o1, const float* o2, long n, long m, int pairwise, int ciou, float eps, float* out);
-// the per-image part of Obber.Val for a batch (nms.hip, next to the probiou it shares): thr10 = the ten IoU thresholds; ws_lab [B][lcap] ints,
-// ws_gt [B][lcap][5], ws_best [B][max_det][2] floats; correct [B][max_det][10]; 5 <= angle_col < row_stride
-int ys_val_match_rot_launch(hipStream_t st, const float* rows, const int* count, int B, int max_det, int row_stride, int angle_col,
-                            const float* batch_idx, const float* cls, const float* bboxes, int n_labels, float img_w, float img_h,
-                            const float* thr10, int lcap, int* ws_lab, float* ws_gt, float* ws_best, unsigned char* correct, int* overflow);

@@ -4,11 +4,15 @@ Everything per image / per anchor runs on the device (eval forward + decode, NMS
 epoch-level ap_per_class (small) and the reference's integer truncation of the results stay on the host.  The model must have
 been created with (height, width) = the padded image size: the reference pads bottom/right with 114 to a multiple of 32
 before dividing by 255 (Detector.cs:35-41), this does the same."""
+import contextlib
+
 import numpy as np
 
 from . import _lib
 from . import metrics as M
-from .model import AMPWrapper, v8DetectionLoss
+from . import model as _model
+from .engine import flatten_labels
+from .model import AMPWrapper
 
 
 class YoloResult:
@@ -43,6 +47,98 @@ def clip_boxes(boxes, shape):
     return b
 
 
+_ZERO4 = (0.0, 0.0, 0.0, 0.0)
+
+
+def _sum(acc, items):
+    return items if acc is None else acc + items
+
+
+def _eval_forward(model, crit, data, fetch=True):
+    """The prologue of every Val loop (Detector.cs:91-97): None for a batch with an empty batch_idx, else the eval forward and the criterion on the
+    eval-mode preds -- one forward serves loss and post-process -- as (images, inference (None when not fetched), loss items)."""
+    if np.asarray(data["batch_idx"]).size < 1:
+        return None
+    images = np.ascontiguousarray(data["images"], np.float32)
+    model.eval()
+    inference = model.forward(images, fetch=fetch)[0]
+    return images, inference, crit.forward(None, data)[1]
+
+
+def _gt_xyxy(bboxes, W, H):
+    """Normalised cxcywh labels -> xyxy pixels (Detector.cs:110-112)."""
+    gt = bboxes * np.array([W, H, W, H], np.float32)
+    return np.concatenate((gt[:, :2] - gt[:, 2:] / 2, gt[:, :2] + gt[:, 2:] / 2), 1).astype(np.float32)
+
+
+class _ValStats:
+    """What a detection-style Val accumulates: the summed loss items and per image (tp per metric, conf, pred_cls, true_cls).  result() is Val's return
+    value: (loss items, (P, R, mAP50, mAP50-95) per metric) from one ap_per_class per metric; zeros when no batch was taken."""
+
+    def __init__(self, items, metrics):
+        self.items, self.loss = items, None
+        self.tps, self.cols = [[] for _ in range(metrics)], ([], [], [])
+
+    def add_image(self, tps, rows, true_cls):
+        for acc, v in zip(self.tps + list(self.cols), list(tps) + [rows[:, 4], rows[:, 5], true_cls]):
+            acc.append(v)
+
+    def result(self):
+        if not self.tps[0]:
+            return (np.zeros(self.items, np.float32),) + (_ZERO4,) * len(self.tps)
+        conf, pc, tc = (np.concatenate(c) for c in self.cols)
+        return (self.loss,) + tuple(M.val_summary(M.ap_per_class(np.concatenate(tp), conf, pc, tc)) for tp in self.tps)
+
+
+class _DeviceMatch:
+    """The device scratch of a device-resident Val loop and the calls on it, as a context manager: `cnt` [B], one `correct` [B, max_rows, 10] per metric
+    and, when NMS produces the rows, `rows` [B, max_rows, row_len] and `keep` -- grown when a larger batch arrives, freed on every exit.
+    select(B, bufs) fills bufs["cnt"] and returns the device pointer of the rows: ys_nms_batched into bufs["rows"], or ys_e2e_select(_ex) on the head's own
+    rows.  match() runs it and then the per-image part as ONE launch (fn = ys_val_match_batched / _rotated_batched / _pose_batched, mid = its arguments
+    between the row stride and the labels); only the rows, their counts and `correct` come back per batch."""
+
+    def __init__(self, eng, select, fn, mid, row_len, max_rows, metrics=1, nms=False):
+        self.eng, self.select, self.fn, self.mid, self.row_len, self.max_rows = eng, select, fn, mid, row_len, max_rows
+        self.cor = ["cor%d" % i for i in range(metrics)]
+        self.size = dict({"cnt": 4}, **{n: max_rows * 10 for n in self.cor})
+        if nms:
+            self.size.update(rows=max_rows * row_len * 4, keep=max_rows * 8)
+        self.bufs, self.cap = {}, 0
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.free()
+
+    def free(self):
+        while self.bufs:
+            self.eng.free(self.bufs.popitem()[1])
+        self.cap = 0
+
+    def match(self, B, labels, img_w, img_h):
+        """-> (rows [count[b], row_len] per image, per metric the bool [count[b], 10] per image)"""
+        eng, bufs, shape = self.eng, self.bufs, (B, self.max_rows, self.row_len)
+        if B > self.cap:
+            self.free()
+            for n, per_image in self.size.items():
+                bufs[n] = eng.malloc(B * per_image)
+            self.cap = B
+        d_rows = self.select(B, bufs)
+        d_lab = []
+        try:                       # the per-batch label buffers are released on the error paths too
+            for a in labels:
+                d_lab.append(eng.to_device(a))
+            eng.val_match_call(self.fn, d_rows, bufs["cnt"], 1, shape, self.mid, labels, d_lab, img_w, img_h, [bufs[n] for n in self.cor])
+            rows = eng.from_device(d_rows, shape, np.float32)
+            cnt = eng.from_device(bufs["cnt"], (B,), np.int32)
+            cors = [eng.from_device(bufs[n], shape[:2] + (10,), np.uint8) for n in self.cor]
+        finally:
+            for p_ in d_lab:
+                eng.free(p_)
+        return [rows[b, :cnt[b]] for b in range(B)], [[c[b, :cnt[b]].astype(bool) for b in range(B)] for c in cors]
+
+
 class Detector:
     def __init__(self, model, end2end=None):
         """end2end (default: the model's own flag): Config.End2End (Config.cs:239) -- the model was built with end2end=True, predictions come
@@ -61,77 +157,71 @@ class Detector:
         output, _ = self.engine.non_max_suppression(inference["boxes"], predict_threshold, iou_threshold, end2end=self.end2end)
         return [YoloResult(r) for r in output[0]]
 
+    # what a task supplies to the shared Val loop: the criterion, the item count of its loss, the number of metrics, the label layout, the NMS kind
+    LOSS, ITEMS, METRICS, BOX_COLS, KPTS, ROTATED = "v8DetectionLoss", 3, 1, 4, False, False
+
     def Val(self, batches, conf_thres=0.1, iou_thres=0.7, max_det=300):
         """batches: iterable of dicts (images [B,3,H,W] in [0,1], batch_idx, cls, bboxes).  Returns
         (SUM over batches of the loss items, (P, R, mAP50, mAP50-95)) like Detector.Val (Detector.cs:76-154; :126 adds the items up).
         The predictions never leave the device between the eval forward, NMS and the matching (ys_model_pred_device ->
         ys_nms_batched -> ys_val_match_batched, all on device pointers); only the kept rows, their count and the `correct`
         matrix come back per batch, for the epoch-level ap_per_class on the host."""
-        crit = v8DetectionLoss(self.model)
-        eng, m = self.engine, self.model
-        tps, confs, pcls, tcls = [], [], [], []
-        loss_sum, count = None, 0
-        nc = m.nc
-        Cc = 4 + nc + m.NM
-        stride = Cc - nc + 2
-        if self.end2end:          # the rows are the head's own [B, k, 6] (ys_model_det_device); the thresholding keeps a prefix of them
-            d_det, max_rows = m.det_device()
-        else:
-            max_rows = max_det
-        d_rows = d_keep = d_cnt = d_cor = None
-        cap_b = 0
-        try:
+        return self._val(batches, conf_thres, iou_thres, max_det)
+
+    def _val(self, batches, conf_thres, iou_thres, max_det):
+        """THE Val loop of the detection-style tasks: per batch the prologue, the rows and their per-image matching -- on the device (_device_match) or by
+        the task's host per-image function (_match_image) -- into one _ValStats."""
+        crit = getattr(_model, self.LOSS)(self.model)
+        stats = _ValStats(self.ITEMS, self.METRICS)
+        device = self._device_match(conf_thres, iou_thres, max_det)
+        with device if device is not None else contextlib.nullcontext():
             for data in batches:
-                if np.asarray(data["batch_idx"]).size < 1:          # Detector.cs:91-94
+                step = _eval_forward(self.model, crit, data, fetch=device is None)
+                if step is None:
                     continue
-                images = np.ascontiguousarray(data["images"], np.float32)
-                B = images.shape[0]
-                # eval forward, then the criterion on the eval-mode preds (Detector.cs:95-97): one forward serves loss and NMS
-                m.eval()
-                m.forward(images, fetch=False)
-                _, items = crit.forward(None, data)
-                loss_sum = items if loss_sum is None else loss_sum + items
-                if B > cap_b:
-                    for p_ in (d_rows, d_keep, d_cnt, d_cor):
-                        if p_ is not None:
-                            eng.free(p_)
-                    if not self.end2end:
-                        d_rows, d_keep = eng.malloc(B * max_det * stride * 4), eng.malloc(B * max_det * 8)
-                    d_cnt, d_cor = eng.malloc(B * 4), eng.malloc(B * max_rows * 10)
-                    cap_b = B
-                if self.end2end:
-                    _lib.check(eng.lib, eng.lib.ys_e2e_select(eng.ctx, d_det, 1, B, max_rows, float(conf_thres), int(max_det), d_cnt))
-                    rows_dev = d_det
+                images, inference, items = step
+                stats.loss = _sum(stats.loss, items)
+                B, _, H, W = images.shape
+                labels = flatten_labels(data, self.BOX_COLS, self.model.kpt_num if self.KPTS else None, seen=device is None)
+                if device is not None:
+                    output, tps = device.match(B, labels, W, H)
                 else:
-                    eng.nms_device(m.pred_device(), B, Cc, m.A, conf_thres, iou_thres, max_det, nc, d_rows, d_keep, d_cnt)
-                    rows_dev = d_rows
-                bi = np.ascontiguousarray(np.asarray(data["batch_idx"], np.float32).reshape(-1))
-                cl = np.ascontiguousarray(np.asarray(data["cls"], np.float32).reshape(-1))
-                bb = np.ascontiguousarray(np.asarray(data["bboxes"], np.float32).reshape(-1, 4))
-                d_lab = []
-                try:                       # the per-batch label buffers are released on the error paths too
-                    for a in (bi, cl, bb):
-                        d_lab.append(eng.to_device(a))
-                    _lib.check(eng.lib, eng.lib.ys_val_match_batched(eng.ctx, rows_dev, d_cnt, 1, B, max_rows, stride, d_lab[0], d_lab[1], d_lab[2],
-                                                                     bi.shape[0], float(images.shape[3]), float(images.shape[2]), d_cor))
-                    rows = eng.from_device(rows_dev, (B, max_rows, stride), np.float32)
-                    cnt = eng.from_device(d_cnt, (B,), np.int32)
-                    cor = eng.from_device(d_cor, (B, max_rows, 10), np.uint8)
-                finally:
-                    for p_ in d_lab:
-                        eng.free(p_)
-                for b in range(B):
-                    tps.append(cor[b, :cnt[b]].astype(bool)); confs.append(rows[b, :cnt[b], 4]); pcls.append(rows[b, :cnt[b], 5])
-                    tcls.append(cl[bi == b])
-                count += B
-        finally:
-            for p_ in (d_rows, d_keep, d_cnt, d_cor):
-                if p_ is not None:
-                    eng.free(p_)
-        if not tps:
-            return np.zeros(3, np.float32), (0.0, 0.0, 0.0, 0.0)
-        stats = M.ap_per_class(np.concatenate(tps), np.concatenate(confs), np.concatenate(pcls), np.concatenate(tcls))
-        return loss_sum, M.val_summary(stats)
+                    output, _ = self.engine.non_max_suppression(inference["boxes"], conf_thres, iou_thres, max_det=max_det, nc=self.model.nc,
+                                                                rotated=self.ROTATED, end2end=self.end2end)
+                    ctx = self._batch_context(data, B)
+                    tps = list(zip(*[self._match_image(rows, b, [a[labels[0] == b] for a in labels], W, H, ctx) for b, rows in enumerate(output)]))
+                for b, rows in enumerate(output):
+                    stats.add_image([tp[b] for tp in tps], rows, labels[1][labels[0] == b])
+        return stats.result()
+
+    def _batch_context(self, data, B):
+        return None
+
+    def _device_match(self, conf_thres, iou_thres, max_det):
+        """The device-resident path (None: the host per-image path).  Detect takes it always: NMS on ys_model_pred_device, or the End2End rows."""
+        eng, m = self.engine, self.model
+        fn = eng.lib.ys_val_match_batched
+        if self.end2end:
+            return self._e2e_match(fn, (), 6 + m.NM, conf_thres, max_det)
+        Cc = 4 + m.nc + m.NM
+
+        def nms(B, bufs):
+            eng.nms_device(m.pred_device(), B, Cc, m.A, conf_thres, iou_thres, max_det, m.nc, bufs["rows"], bufs["keep"], bufs["cnt"])
+            return bufs["rows"]
+        return _DeviceMatch(eng, nms, fn, (), 6 + m.NM, max_det, nms=True)
+
+    def _e2e_match(self, fn, mid, row_len, conf_thres, max_det, metrics=1):
+        """End2End: the rows are the head's own [B, k, row_len] (ys_model_det_device); the thresholding keeps a prefix of them (Ops.cs:258-267)."""
+        eng = self.engine
+        d_det, k = self.model.det_device()
+
+        def select(B, bufs):
+            if row_len == 6:
+                _lib.check(eng.lib, eng.lib.ys_e2e_select(eng.ctx, d_det, 1, B, k, float(conf_thres), int(max_det), bufs["cnt"]))
+            else:
+                _lib.check(eng.lib, eng.lib.ys_e2e_select_ex(eng.ctx, d_det, 1, B, k, row_len, float(conf_thres), int(max_det), bufs["cnt"]))
+            return d_det
+        return _DeviceMatch(eng, select, fn, mid, row_len, k, metrics)
 
 
 class Segmenter(Detector):
@@ -159,48 +249,29 @@ class Segmenter(Detector):
                 results.append((res, mk))
         return results
 
+    LOSS, ITEMS, METRICS = "v8SegmentationLoss", 5, 2
+
     def Val(self, batches, conf_thres=0.01, iou_thres=0.7, max_det=300):
         """Models/Segmenter.cs:85-185: per batch eval forward + loss, NMS (conf 0.01, IoU 0.7), and per image
         process_mask at the prototype resolution (:126 passes the proto size as `shape`, so the boxes are NOT rescaled -- kept),
         box IoU matching and mask IoU matching (Metrics.mask_iou on the overlap-encoded `masks`, :131-143) -- all on the device;
         the two epoch-level ap_per_class reductions stay on the host.  batches: dicts with images [B,3,H,W] in [0,1], batch_idx,
         cls, bboxes, masks [B,H/4,W/4].  Returns (summed loss items [5], box (P,R,mAP50,mAP50-95), mask (P,R,mAP50,mAP50-95))."""
-        from .model import v8SegmentationLoss
-        crit = v8SegmentationLoss(self.model)
-        tps, tpms, confs, pcls, tcls = [], [], [], [], []
-        loss_sum = None
-        nc = self.model.nc
-        for data in batches:
-            if np.asarray(data["batch_idx"]).size < 1:          # Segmenter.cs:105-108
-                continue
-            images = np.ascontiguousarray(data["images"], np.float32)
-            B, _, H, W = images.shape
-            inference, _ = self.amp.Evaluate(images)                # Segmenter.cs:110-112: eval preds feed loss and NMS
-            _, items = crit.forward(None, data)
-            loss_sum = items if loss_sum is None else loss_sum + items
-            proto = self.model.get_output("proto")
-            mh, mw = proto.shape[2:]
-            output, _ = self.engine.non_max_suppression(inference["boxes"], conf_thres, iou_thres, max_det=max_det, nc=nc, end2end=self.end2end)
-            bi = np.asarray(data["batch_idx"], np.float32).reshape(-1)
-            cl = np.asarray(data["cls"], np.float32).reshape(-1)
-            bb = np.asarray(data["bboxes"], np.float32).reshape(-1, 4)
-            gm = np.asarray(data["masks"], np.float32).reshape(B, mh, mw)
-            for b, rows in enumerate(output):
-                sel = bi == b
-                true_cls = cl[sel]
-                nl = int(sel.sum())
-                masks = self.engine.process_mask(proto[b], rows[:, 6:], rows[:, :4], (mw, mh)) if len(rows) else np.zeros((0, mh, mw), bool)
-                gt = bb[sel] * np.array([W, H, W, H], np.float32)
-                gt_xyxy = np.concatenate((gt[:, :2] - gt[:, 2:] / 2, gt[:, :2] + gt[:, 2:] / 2), 1).astype(np.float32)
-                iou = self.engine.box_iou(gt_xyxy, rows[:, :4])
-                tps.append(self.engine.match_predictions(rows[:, 5], true_cls, iou))
-                miou = self.engine.mask_iou(gm[b], nl, masks)
-                tpms.append(self.engine.match_predictions(rows[:, 5], true_cls, miou))
-                confs.append(rows[:, 4]); pcls.append(rows[:, 5]); tcls.append(true_cls)
-        conf, pc, tc = np.concatenate(confs), np.concatenate(pcls), np.concatenate(tcls)
-        box = M.val_summary(M.ap_per_class(np.concatenate(tps), conf, pc, tc))
-        mask = M.val_summary(M.ap_per_class(np.concatenate(tpms), conf, pc, tc))
-        return loss_sum, box, mask
+        return self._val(batches, conf_thres, iou_thres, max_det)
+
+    def _device_match(self, conf_thres, iou_thres, max_det):
+        return None
+
+    def _batch_context(self, data, B):
+        proto = self.model.get_output("proto")
+        return proto, np.asarray(data["masks"], np.float32).reshape((B,) + proto.shape[2:])
+
+    def _match_image(self, rows, b, lab, W, H, ctx):
+        eng, (_, cl, bb), (proto, gm) = self.engine, lab, ctx
+        mh, mw = proto.shape[2:]
+        masks = eng.process_mask(proto[b], rows[:, 6:], rows[:, :4], (mw, mh)) if len(rows) else np.zeros((0, mh, mw), bool)
+        tp = eng.match_predictions(rows[:, 5], cl, eng.box_iou(_gt_xyxy(bb, W, H), rows[:, :4]))
+        return tp, eng.match_predictions(rows[:, 5], cl, eng.mask_iou(gm[b], len(cl), masks))
 
 
 class Obber(Detector):
@@ -226,93 +297,22 @@ class Obber(Detector):
             results.append(res)
         return results
 
-    def Val(self, batches, conf_thres=0.01, iou_thres=0.7, max_det=300):
-        from .model import v8OBBLoss
-        if self.end2end:
-            return self._val_end2end(batches, conf_thres, max_det)
-        crit = v8OBBLoss(self.model)
-        tps, confs, pcls, tcls = [], [], [], []
-        loss_sum = None
-        nc = self.model.nc
-        for data in batches:
-            if np.asarray(data["batch_idx"]).size < 1:
-                continue
-            images = np.ascontiguousarray(data["images"], np.float32)
-            B, _, H, W = images.shape
-            inference, _ = self.amp.Evaluate(images)
-            _, items = crit.forward(None, data)
-            loss_sum = items if loss_sum is None else loss_sum + items
-            output, _ = self.engine.non_max_suppression(inference["boxes"], conf_thres, iou_thres, max_det=max_det, nc=nc, rotated=True)
-            bi = np.asarray(data["batch_idx"], np.float32).reshape(-1)
-            cl = np.asarray(data["cls"], np.float32).reshape(-1)
-            bb = np.asarray(data["bboxes"], np.float32).reshape(-1, 5)
-            for b, rows in enumerate(output):
-                sel = bi == b
-                gt = np.concatenate((bb[sel, :4] * np.array([W, H, W, H], np.float32), bb[sel, 4:5]), 1).astype(np.float32)   # Obber.cs:108
-                pred = np.concatenate((rows[:, :4], rows[:, 6:7]), 1).astype(np.float32)                                      # Obber.cs:102
-                iou = self.engine.batch_probiou(gt, pred) if len(gt) and len(pred) else np.zeros((len(gt), len(pred)), np.float32)
-                tps.append(self.engine.match_predictions(rows[:, 5], cl[sel], iou))
-                confs.append(rows[:, 4]); pcls.append(rows[:, 5]); tcls.append(cl[sel])
-        if not tps:
-            return np.zeros(4, np.float32), (0.0, 0.0, 0.0, 0.0)
-        stats = M.ap_per_class(np.concatenate(tps), np.concatenate(confs), np.concatenate(pcls), np.concatenate(tcls))
-        return loss_sum, M.val_summary(stats)
+    LOSS, ITEMS, BOX_COLS, ROTATED = "v8OBBLoss", 4, 5, True
 
-    def _val_end2end(self, batches, conf_thres, max_det):
-        """Val on an End2End model: the rows are the head's own [B, k, 7] (ys_model_det_device); thresholding keeps a prefix of them and the per-image
-        probiou + match_predictions run as one launch on the device pointers.  Only rows, counts and `correct` come back per batch."""
-        from .model import v8OBBLoss
-        crit = v8OBBLoss(self.model)
-        eng, m = self.engine, self.model
-        tps, confs, pcls, tcls = [], [], [], []
-        loss_sum = None
-        d_det, k = m.det_device()
-        d_cnt = d_cor = None
-        cap_b = 0
-        try:
-            for data in batches:
-                if np.asarray(data["batch_idx"]).size < 1:
-                    continue
-                images = np.ascontiguousarray(data["images"], np.float32)
-                B, _, H, W = images.shape
-                m.eval()
-                m.forward(images, fetch=False)
-                _, items = crit.forward(None, data)                 # Obber.cs:94-95: E2EOBBLoss on the eval preds
-                loss_sum = items if loss_sum is None else loss_sum + items
-                if B > cap_b:
-                    for p_ in (d_cnt, d_cor):
-                        if p_ is not None:
-                            eng.free(p_)
-                    d_cnt = d_cor = None
-                    d_cnt, d_cor = eng.malloc(B * 4), eng.malloc(B * k * 10)
-                    cap_b = B
-                _lib.check(eng.lib, eng.lib.ys_e2e_select_ex(eng.ctx, d_det, 1, B, k, 7, float(conf_thres), int(max_det), d_cnt))
-                bi = np.ascontiguousarray(np.asarray(data["batch_idx"], np.float32).reshape(-1))
-                cl = np.ascontiguousarray(np.asarray(data["cls"], np.float32).reshape(-1))
-                bb = np.ascontiguousarray(np.asarray(data["bboxes"], np.float32).reshape(-1, 5))
-                d_lab = []
-                try:
-                    for a in (bi, cl, bb):
-                        d_lab.append(eng.to_device(a))
-                    _lib.check(eng.lib, eng.lib.ys_val_match_rotated_batched(eng.ctx, d_det, d_cnt, 1, B, k, 7, 6, d_lab[0], d_lab[1], d_lab[2],
-                                                                             bi.shape[0], float(W), float(H), d_cor))
-                    rows = eng.from_device(d_det, (B, k, 7), np.float32)
-                    cnt = eng.from_device(d_cnt, (B,), np.int32)
-                    cor = eng.from_device(d_cor, (B, k, 10), np.uint8)
-                finally:
-                    for p_ in d_lab:
-                        eng.free(p_)
-                for b in range(B):
-                    tps.append(cor[b, :cnt[b]].astype(bool)); confs.append(rows[b, :cnt[b], 4]); pcls.append(rows[b, :cnt[b], 5])
-                    tcls.append(cl[bi == b])
-        finally:
-            for p_ in (d_cnt, d_cor):
-                if p_ is not None:
-                    eng.free(p_)
-        if not tps:
-            return np.zeros(4, np.float32), (0.0, 0.0, 0.0, 0.0)
-        stats = M.ap_per_class(np.concatenate(tps), np.concatenate(confs), np.concatenate(pcls), np.concatenate(tcls))
-        return loss_sum, M.val_summary(stats)
+    def Val(self, batches, conf_thres=0.01, iou_thres=0.7, max_det=300):
+        return self._val(batches, conf_thres, iou_thres, max_det)
+
+    def _device_match(self, conf_thres, iou_thres, max_det):
+        if not self.end2end:
+            return None
+        return self._e2e_match(self.engine.lib.ys_val_match_rotated_batched, (6,), 7, conf_thres, max_det)      # E2EOBBLoss on the eval preds (Obber.cs:94-95)
+
+    def _match_image(self, rows, b, lab, W, H, ctx):
+        eng, (_, cl, bb) = self.engine, lab
+        gt = np.concatenate((bb[:, :4] * np.array([W, H, W, H], np.float32), bb[:, 4:5]), 1).astype(np.float32)      # Obber.cs:108
+        pred = np.concatenate((rows[:, :4], rows[:, 6:7]), 1).astype(np.float32)                                   # Obber.cs:102
+        iou = eng.batch_probiou(gt, pred) if len(gt) and len(pred) else np.zeros((len(gt), len(pred)), np.float32)
+        return (eng.match_predictions(rows[:, 5], cl, iou),)
 
 
 class KeyPoint:
@@ -343,107 +343,25 @@ class PoseDetector(Detector):
             results.append(res)
         return results
 
-    def Val(self, batches, conf_thres=0.01, iou_thres=0.7, max_det=300):
-        from .model import v8PoseLoss
-        if self.end2end:
-            return self._val_end2end(batches, conf_thres, max_det)
-        crit = v8PoseLoss(self.model)
-        tps, tpps, confs, pcls, tcls = [], [], [], [], []
-        loss_sum = None
-        nc, K, D = self.model.nc, self.model.kpt_num, self.model.kpt_dim
-        for data in batches:
-            if np.asarray(data["batch_idx"]).size < 1:
-                continue
-            images = np.ascontiguousarray(data["images"], np.float32)
-            B, _, H, W = images.shape
-            inference, _ = self.amp.Evaluate(images)
-            _, items = crit.forward(None, data)
-            loss_sum = items if loss_sum is None else loss_sum + items
-            output, _ = self.engine.non_max_suppression(inference["boxes"], conf_thres, iou_thres, max_det=max_det, nc=nc)
-            bi = np.asarray(data["batch_idx"], np.float32).reshape(-1)
-            cl = np.asarray(data["cls"], np.float32).reshape(-1)
-            bb = np.asarray(data["bboxes"], np.float32).reshape(-1, 4)
-            kp = np.asarray(data["keypoints"], np.float32).reshape(len(bi), K, -1)
-            if kp.shape[2] == 2:                                   # PoseDetector.cs:144-148: "seen" column of ones
-                kp = np.concatenate((kp, np.ones(kp.shape[:2] + (1,), np.float32)), 2)
-            for b, rows in enumerate(output):
-                sel = bi == b
-                gt = bb[sel] * np.array([W, H, W, H], np.float32)
-                gt_xyxy = np.concatenate((gt[:, :2] - gt[:, 2:] / 2, gt[:, :2] + gt[:, 2:] / 2), 1).astype(np.float32)
-                tps.append(self.engine.match_predictions(rows[:, 5], cl[sel], self.engine.box_iou(gt_xyxy, rows[:, :4])))
-                gk = (kp[sel] * np.array([W, H, 1.0], np.float32)).astype(np.float32)                       # PoseDetector.cs:153-155
-                area = ((gt_xyxy[:, 2] - gt_xyxy[:, 0]) * (gt_xyxy[:, 3] - gt_xyxy[:, 1]) * np.float32(0.53)).astype(np.float32)
-                oks = self.engine.kpt_iou(gk, rows[:, 6:].reshape(-1, K, D), area)
-                tpps.append(self.engine.match_predictions(rows[:, 5], cl[sel], oks))
-                confs.append(rows[:, 4]); pcls.append(rows[:, 5]); tcls.append(cl[sel])
-        if not tps:
-            return np.zeros(5, np.float32), (0.0, 0.0, 0.0, 0.0), (0.0, 0.0, 0.0, 0.0)
-        conf, pc, tc = np.concatenate(confs), np.concatenate(pcls), np.concatenate(tcls)
-        box = M.val_summary(M.ap_per_class(np.concatenate(tps), conf, pc, tc))
-        pose = M.val_summary(M.ap_per_class(np.concatenate(tpps), conf, pc, tc))
-        return loss_sum, box, pose
+    LOSS, ITEMS, METRICS, KPTS = "v8PoseLoss", 5, 2, True
 
-    def _val_end2end(self, batches, conf_thres, max_det):
-        """Val on an End2End model: the rows are the head's own [B, k, 6+nk] (ys_model_det_device); thresholding keeps a prefix of them and the per-image
-        box_iou / kpt_iou + two match_predictions run as one launch on the device pointers.  Only rows, counts and the two `correct` arrays come back per batch."""
-        from .model import v8PoseLoss
-        crit = v8PoseLoss(self.model)
-        eng, m = self.engine, self.model
-        K, D = m.kpt_num, m.kpt_dim
-        rl = 6 + K * D
-        tps, tpps, confs, pcls, tcls = [], [], [], [], []
-        loss_sum = None
-        d_det, k = m.det_device()
-        d_cnt = d_cob = d_cop = None
-        cap_b = 0
-        try:
-            for data in batches:
-                if np.asarray(data["batch_idx"]).size < 1:
-                    continue
-                images = np.ascontiguousarray(data["images"], np.float32)
-                B, _, H, W = images.shape
-                m.eval()
-                m.forward(images, fetch=False)
-                _, items = crit.forward(None, data)                 # PoseDetector.cs:123-124: E2EPoseLoss on the eval preds
-                loss_sum = items if loss_sum is None else loss_sum + items
-                if B > cap_b:
-                    for p_ in (d_cnt, d_cob, d_cop):
-                        if p_ is not None:
-                            eng.free(p_)
-                    d_cnt = d_cob = d_cop = None
-                    d_cnt, d_cob, d_cop = eng.malloc(B * 4), eng.malloc(B * k * 10), eng.malloc(B * k * 10)
-                    cap_b = B
-                _lib.check(eng.lib, eng.lib.ys_e2e_select_ex(eng.ctx, d_det, 1, B, k, rl, float(conf_thres), int(max_det), d_cnt))
-                bi = np.ascontiguousarray(np.asarray(data["batch_idx"], np.float32).reshape(-1))
-                cl = np.ascontiguousarray(np.asarray(data["cls"], np.float32).reshape(-1))
-                bb = np.ascontiguousarray(np.asarray(data["bboxes"], np.float32).reshape(-1, 4))
-                kp = np.ascontiguousarray(np.asarray(data["keypoints"], np.float32).reshape(len(bi), K, -1))
-                d_lab = []
-                try:
-                    for a in (bi, cl, bb, kp):
-                        d_lab.append(eng.to_device(a))
-                    _lib.check(eng.lib, eng.lib.ys_val_match_pose_batched(eng.ctx, d_det, d_cnt, 1, B, k, rl, 6, K, D, d_lab[0], d_lab[1], d_lab[2], d_lab[3],
-                                                                          kp.shape[2], bi.shape[0], float(W), float(H), d_cob, d_cop))
-                    rows = eng.from_device(d_det, (B, k, rl), np.float32)
-                    cnt = eng.from_device(d_cnt, (B,), np.int32)
-                    cob = eng.from_device(d_cob, (B, k, 10), np.uint8)
-                    cop = eng.from_device(d_cop, (B, k, 10), np.uint8)
-                finally:
-                    for p_ in d_lab:
-                        eng.free(p_)
-                for b in range(B):
-                    tps.append(cob[b, :cnt[b]].astype(bool)); tpps.append(cop[b, :cnt[b]].astype(bool))
-                    confs.append(rows[b, :cnt[b], 4]); pcls.append(rows[b, :cnt[b], 5]); tcls.append(cl[bi == b])
-        finally:
-            for p_ in (d_cnt, d_cob, d_cop):
-                if p_ is not None:
-                    eng.free(p_)
-        if not tps:
-            return np.zeros(5, np.float32), (0.0, 0.0, 0.0, 0.0), (0.0, 0.0, 0.0, 0.0)
-        conf, pc, tc = np.concatenate(confs), np.concatenate(pcls), np.concatenate(tcls)
-        box = M.val_summary(M.ap_per_class(np.concatenate(tps), conf, pc, tc))
-        pose = M.val_summary(M.ap_per_class(np.concatenate(tpps), conf, pc, tc))
-        return loss_sum, box, pose
+    def Val(self, batches, conf_thres=0.01, iou_thres=0.7, max_det=300):
+        return self._val(batches, conf_thres, iou_thres, max_det)
+
+    def _device_match(self, conf_thres, iou_thres, max_det):
+        if not self.end2end:
+            return None
+        K, D = self.model.kpt_num, self.model.kpt_dim                 # E2EPoseLoss on the eval preds (PoseDetector.cs:123-124)
+        return self._e2e_match(self.engine.lib.ys_val_match_pose_batched, (6, K, D), 6 + K * D, conf_thres, max_det, metrics=2)
+
+    def _match_image(self, rows, b, lab, W, H, ctx):
+        eng, (_, cl, bb, kp) = self.engine, lab
+        gt_xyxy = _gt_xyxy(bb, W, H)
+        tp = eng.match_predictions(rows[:, 5], cl, eng.box_iou(gt_xyxy, rows[:, :4]))
+        gk = (kp * np.array([W, H, 1.0], np.float32)).astype(np.float32)                                         # PoseDetector.cs:153-155
+        area = ((gt_xyxy[:, 2] - gt_xyxy[:, 0]) * (gt_xyxy[:, 3] - gt_xyxy[:, 1]) * np.float32(0.53)).astype(np.float32)
+        oks = eng.kpt_iou(gk, rows[:, 6:].reshape(-1, self.model.kpt_num, self.model.kpt_dim), area)
+        return tp, eng.match_predictions(rows[:, 5], cl, oks)
 
 
 class ClassifyResult:
@@ -492,16 +410,15 @@ class Classifier:
                 m.forward_device(data.images, data.batch)
                 inference, _ = m._outputs()
                 self.loss.forward_device(data.cls, data.batch)
-                _, items = self.loss.read()
-                loss_sum = items if loss_sum is None else loss_sum + items
+                loss_sum = _sum(loss_sum, self.loss.read()[1])
                 tops.append(self.engine.cls_topk(inference["cls"], k))
                 targets.append(self.engine.from_device(data.cls, (data.batch,), np.float32))
                 continue
-            if np.asarray(data["batch_idx"]).size < 1:
+            step = _eval_forward(self.model, self.loss, data)
+            if step is None:
                 continue
-            inference, _ = self.amp.Evaluate(np.ascontiguousarray(data["images"], np.float32))
-            _, items = self.loss.forward(None, data)
-            loss_sum = items if loss_sum is None else loss_sum + items
+            _, inference, items = step
+            loss_sum = _sum(loss_sum, items)
             tops.append(self.engine.cls_topk(inference["cls"], k))
             targets.append(np.asarray(data["cls"], np.float32).reshape(-1))
         if not tops:

@@ -21,6 +21,20 @@ def _ptr(a):
     return a.ctypes.data_as(C.c_void_p) if a is not None else None
 
 
+def flatten_labels(batch, box_cols=4, kpt_num=None, seen=False):
+    """A collate dict's labels as contiguous fp32 arrays: (batch_idx [N], cls [N], bboxes [N, box_cols]) and, with kpt_num, keypoints [N, K, 2|3];
+    seen: 2-column keypoints get the "seen" column of ones (PoseDetector.cs:144-148), which the device kernel appends itself."""
+    def flat(key, *shape):
+        return np.ascontiguousarray(np.asarray(batch[key], np.float32).reshape(shape))
+    labels = flat("batch_idx", -1), flat("cls", -1), flat("bboxes", -1, box_cols)
+    if kpt_num is None:
+        return labels
+    kp = flat("keypoints", labels[0].shape[0], int(kpt_num), -1)
+    if seen and kp.shape[2] == 2:
+        kp = np.concatenate((kp, np.ones(kp.shape[:2] + (1,), np.float32)), 2)
+    return labels + (kp,)
+
+
 _DTYPE_CODES = {"f32": 0, "float32": 0, "bf16": 1, "bfloat16": 1, "fp8": 2, "float8": 2, 0: 0, 1: 1, 2: 2}   # same names as model.DTYPES
 
 
@@ -218,67 +232,53 @@ class Engine:
         _lib.check(self.lib, self.lib.ys_kpt_iou(self.ctx, _ptr(k1), n, _ptr(k2), k2.shape[0], _ptr(ar), K, k2.shape[2], eps, 0, _ptr(out)))
         return out
 
+    def val_match_call(self, fn, rows, count, on_device, shape, mid, labels, label_ptrs, img_w, img_h, correct):
+        """THE call of the three batched matching entry points, which share their argument order: (ctx, rows, count, on_device, B, max_det, row_stride, *mid,
+        label arrays [, their keypoint width], n_labels, img_w, img_h, one `correct` per metric).  shape = (B, max_det, row_stride); labels = the
+        flatten_labels tuple (for the sizes); rows / count / label_ptrs / correct: host or device pointers, as on_device says."""
+        tail = ((labels[3].shape[2],) if len(labels) > 3 else ()) + (labels[0].shape[0], float(img_w), float(img_h))
+        _lib.check(self.lib, fn(self.ctx, rows, count, int(on_device), *shape, *mid, *label_ptrs, *tail, *correct))
+
+    def _val_match(self, fn, rows, count, labels, mid, img_w, img_h, metrics=1, on_device=False):
+        """rows [B,max_det,stride] / count [B] through val_match_call -> per metric a list of bool [count[b], 10]; on_device: on device copies of every argument."""
+        rows = np.ascontiguousarray(rows, np.float32)
+        count = np.ascontiguousarray(count, np.int32)
+        cors = [np.zeros(rows.shape[:2] + (10,), np.uint8) for _ in range(metrics)]
+        if not on_device:
+            self.val_match_call(fn, _ptr(rows), _ptr(count), 0, rows.shape, mid, labels, [_ptr(a) for a in labels], img_w, img_h, [_ptr(c) for c in cors])
+        else:
+            dev = []
+            try:
+                for a in (rows, count) + tuple(labels):
+                    dev.append(self.to_device(a) if a.size else self.malloc(4))
+                for c in cors:
+                    dev.append(self.malloc(c.size))
+                nl = 2 + len(labels)
+                self.val_match_call(fn, dev[0], dev[1], 1, rows.shape, mid, labels, dev[2:nl], img_w, img_h, dev[nl:])
+                cors = [self.from_device(p_, c.shape, np.uint8) for p_, c in zip(dev[nl:], cors)]
+            finally:
+                for p_ in dev:
+                    self.free(p_)
+        return [[c[b, :count[b]].astype(bool) for b in range(rows.shape[0])] for c in cors]
+
     def val_match(self, rows, count, batch, img_w, img_h):
         """rows [B,max_det,6+extra] / count [B]: the padded NMS outputs (x1,y1,x2,y2,conf,cls,...); batch = collate dict
         (batch_idx, cls, bboxes normalised cxcywh).  Returns a list of bool [count[b], 10] (match_predictions per image)."""
-        rows = np.ascontiguousarray(rows, np.float32)
-        count = np.ascontiguousarray(count, np.int32)
-        B, max_det, stride = rows.shape
-        bi = np.ascontiguousarray(np.asarray(batch["batch_idx"], np.float32).reshape(-1))
-        cl = np.ascontiguousarray(np.asarray(batch["cls"], np.float32).reshape(-1))
-        bb = np.ascontiguousarray(np.asarray(batch["bboxes"], np.float32).reshape(-1, 4))
-        cor = np.zeros((B, max_det, 10), np.uint8)
-        _lib.check(self.lib, self.lib.ys_val_match_batched(self.ctx, _ptr(rows), _ptr(count), 0, B, max_det, stride, _ptr(bi), _ptr(cl),
-                                                           _ptr(bb), bi.shape[0], float(img_w), float(img_h), _ptr(cor)))
-        return [cor[b, :count[b]].astype(bool) for b in range(B)]
+        return self._val_match(self.lib.ys_val_match_batched, rows, count, flatten_labels(batch), (), img_w, img_h)[0]
 
     def val_match_rotated(self, rows, count, batch, img_w, img_h, angle_col=6):
         """Obber.Val's per-image part (Obber.cs:102-114) in one launch: rows [B,max_det,7+] / count [B] = oriented rows (cx,cy,w,h,conf,cls,angle);
         batch = collate dict (batch_idx, cls, bboxes [N,5] normalised cxcywh + angle).  Returns a list of bool [count[b], 10]: match_predictions on
         Metrics.batch_probiou(GT, prediction) per image, bit for bit what batch_probiou + match_predictions below give (ys_val_match_rotated_batched)."""
-        rows = np.ascontiguousarray(rows, np.float32)
-        count = np.ascontiguousarray(count, np.int32)
-        B, max_det, stride = rows.shape
-        bi = np.ascontiguousarray(np.asarray(batch["batch_idx"], np.float32).reshape(-1))
-        cl = np.ascontiguousarray(np.asarray(batch["cls"], np.float32).reshape(-1))
-        bb = np.ascontiguousarray(np.asarray(batch["bboxes"], np.float32).reshape(-1, 5))
-        cor = np.zeros((B, max_det, 10), np.uint8)
-        _lib.check(self.lib, self.lib.ys_val_match_rotated_batched(self.ctx, _ptr(rows), _ptr(count), 0, B, max_det, stride, int(angle_col), _ptr(bi),
-                                                                   _ptr(cl), _ptr(bb), bi.shape[0], float(img_w), float(img_h), _ptr(cor)))
-        return [cor[b, :count[b]].astype(bool) for b in range(B)]
+        return self._val_match(self.lib.ys_val_match_rotated_batched, rows, count, flatten_labels(batch, 5), (int(angle_col),), img_w, img_h)[0]
 
     def val_match_pose(self, rows, count, batch, img_w, img_h, kpt_num, kpt_dim, kpt_col=6, on_device=False):
         """PoseDetector.Val's per-image part (PoseDetector.cs:131-165) in one launch: rows [B,max_det,6+K*D] / count [B] = rows (x1,y1,x2,y2,conf,cls,
         keypoints); batch = collate dict (batch_idx, cls, bboxes [N,4] normalised cxcywh, keypoints [N,K,2|3] normalised).  Returns two lists of bool
         [count[b], 10]: match_predictions on Metrics.box_iou and on Metrics.kpt_iou (area = w * h * 0.53) per image, bit for bit what box_iou / kpt_iou +
         match_predictions give (ys_val_match_pose_batched).  on_device: the same call on device copies of every argument."""
-        rows = np.ascontiguousarray(rows, np.float32)
-        count = np.ascontiguousarray(count, np.int32)
-        B, max_det, stride = rows.shape
-        bi = np.ascontiguousarray(np.asarray(batch["batch_idx"], np.float32).reshape(-1))
-        cl = np.ascontiguousarray(np.asarray(batch["cls"], np.float32).reshape(-1))
-        bb = np.ascontiguousarray(np.asarray(batch["bboxes"], np.float32).reshape(-1, 4))
-        kp = np.ascontiguousarray(np.asarray(batch["keypoints"], np.float32).reshape(bi.shape[0], int(kpt_num), -1))
-        ld = kp.shape[2]
-        cob, cop = np.zeros((B, max_det, 10), np.uint8), np.zeros((B, max_det, 10), np.uint8)
-        args = (B, max_det, stride, int(kpt_col), int(kpt_num), int(kpt_dim))
-        tail = (ld, bi.shape[0], float(img_w), float(img_h))
-        if not on_device:
-            _lib.check(self.lib, self.lib.ys_val_match_pose_batched(self.ctx, _ptr(rows), _ptr(count), 0, *args, _ptr(bi), _ptr(cl), _ptr(bb), _ptr(kp),
-                                                                    *tail, _ptr(cob), _ptr(cop)))
-        else:
-            dev = []
-            try:
-                for a in (rows, count, bi, cl, bb, kp):
-                    dev.append(self.to_device(a) if a.size else self.malloc(4))
-                for _ in range(2):
-                    dev.append(self.malloc(cob.size))
-                _lib.check(self.lib, self.lib.ys_val_match_pose_batched(self.ctx, dev[0], dev[1], 1, *args, dev[2], dev[3], dev[4], dev[5], *tail, dev[6], dev[7]))
-                cob, cop = self.from_device(dev[6], cob.shape, np.uint8), self.from_device(dev[7], cop.shape, np.uint8)
-            finally:
-                for p_ in dev:
-                    self.free(p_)
-        return [cob[b, :count[b]].astype(bool) for b in range(B)], [cop[b, :count[b]].astype(bool) for b in range(B)]
+        return tuple(self._val_match(self.lib.ys_val_match_pose_batched, rows, count, flatten_labels(batch, 4, kpt_num),
+                                     (int(kpt_col), int(kpt_num), int(kpt_dim)), img_w, img_h, metrics=2, on_device=on_device))
 
     def mask_iou(self, gt_ids, nl, pred_masks, eps=1e-7):
         """Metrics.mask_iou (Metrics.cs:120-125) on (gt_ids == k+1), k < nl, vs pred_masks bool/uint8 [n, h, w] -> [nl, n] fp32."""
