@@ -16,6 +16,7 @@ import torch
 
 import kat_ref as K
 import loss_cases as L
+import mask_kpt_cases as MK
 from conftest import BACKENDS
 from oracle import yolo_oracle as O
 
@@ -79,12 +80,12 @@ def test_oracle_matches_kat():
             assert np.abs(got.numpy() - want).max() <= max(tol * 50, 2e-5) * np.abs(want).max(), dt
 
 
-def _grad_per_element(got, want, key, rot=False):
-    """every element, not only the largest: the bound of tests/test_loss_kernels.py (GRAD_R (|ref| + max|ref| / 8)); the known answers are central finite
-    differences in float64"""
+def _grad_per_element(got, want, key, rot=False, R=None):
+    """every element, not only the largest: the bound of tests/test_loss_kernels.py (GRAD_R (|ref| + max|ref| / 8)), for the mask gradients with the
+    constants of tests/mask_kpt_cases.py; the known answers are central finite differences in float64"""
     mx = np.abs(want).max()
     err = np.abs(got - want)
-    bound = L.GRAD_R[rot] * (np.abs(want) + mx / 8)
+    bound = (L.GRAD_R[rot] if R is None else R) * (np.abs(want) + mx / 8)
     assert (err <= bound).all(), (key, float((err / bound).max()), float(mx))
 
 
@@ -300,6 +301,7 @@ def test_engine_segment_loss_matches_kat(backend, engine):
         want = np.array(g[wk])
         got = m.get_output(key)
         assert np.abs(got - want).max() <= 1e-3 * np.abs(want).max(), (key, np.abs(got - want).max(), np.abs(want).max())
+        _grad_per_element(got, want, key, R=MK.GRAD_R[key])
     m.close()
 
 
