@@ -212,30 +212,238 @@ __device__ __forceinline__ unsigned wg_uniform(unsigned v) {
 #endif
 }
 #define YS_WG_TWO_MAX 2        // 9-wave weight-gradient tiles of up to this many MFMA fragments run two workgroups per CU (96 registers).  4 measured (round 4): the 2 x 2 tile spills 32 B and the 32 -> 32 layers go 29.4 -> 42.0 us (400 partial slabs instead of 229) -- stays 2
-template <int MRA, int NRB, int TAPS>
+// RING variants: the LDS holds a ring of stages, each the same image of one tile (dy [ZR + 1][pdb], patch [PH * PW][pxb]); the operands go global -> LDS by DMA
+// (ys_bufld_lds16_nom0), so that the tiles of the next one or two trips are in flight while one is multiplied and no register holds an operand on its way.
+struct WgRing {
+  int ns;            // stages: 2 or 3 (wgrad_tr_plan, YS_WG_RING_MAX; a launch whose ring does not fit runs the register-fetch variant)
+  int kd, kx;        // requests a wave issues per tile into the dy image / into the patch, fillers included: kd + kx for EVERY wave, which is what the counted wait counts
+  int nrd, nrx;      // 1 KB requests that cover the dy image (zero row and pitch padding included) / the patch
+  unsigned stage;    // bytes from one stage to the next: (nrd + nrx) KB and, where a wave has filler requests, the spare KB they land in
+};
+constexpr int wg_pitch_bytes(int ch) {       // smallest row pitch >= ch*2 bytes whose 32-byte slot count is odd (8 rows -> 8 bank slots)
+  int s = (ch * 2 + 31) / 32;
+  if (!(s & 1)) s++;
+  return s * 32;
+}
+// stride-2 patches are read every other row: a pitch of 16 (mod 32) bytes makes the 2-row step an odd slot count
+constexpr int wg_pitch_s2_bytes(int ch) { return ((ch * 2 + 15) / 32) * 32 + 16; }
+// patch units per thread of the register fetch (host keeps PH*PW*XV <= this x threads: the plans of both fetches come from one tile search)
+constexpr int wg_nx(int nrb, bool k3) { return k3 ? 5 : (128 * nrb * 2 + 255) / 256; }
+// most requests per wave and tile a plan can ask of the ring variants (9 waves; the record arrays' compile-time size): the largest dy image / patch the tile search admits
+constexpr int wg_kdmax(int mra) { return ((257 * wg_pitch_bytes(mra * 16) + 1023) / 1024 + 8) / 9; }
+constexpr int wg_kxmax(int nrb) {
+  const int pix = wg_nx(nrb, true) * 576 / (nrb * 2);
+  const int pb = wg_pitch_s2_bytes(nrb * 16) > wg_pitch_bytes(nrb * 16) ? wg_pitch_s2_bytes(nrb * 16) : wg_pitch_bytes(nrb * 16);
+  return ((pix * pb + 1023) / 1024 + 8) / 9;
+}
+template <int MRA, int NRB, int TAPS, bool RING>
 __global__ void __launch_bounds__(TAPS == 9 ? 576 : 256, (TAPS == 9 && MRA * NRB <= YS_WG_TWO_MAX) ? 5 : 1)   // small 9-wave tiles: 96 registers = two workgroups per CU
-conv_wgrad_tr_kernel(WgradArgs a) {
+conv_wgrad_tr_kernel(WgradArgs a, WgRing rg) {
   constexpr int NT = TAPS == 9 ? 576 : 256;
   constexpr int NW = NT / 64;
   constexpr int COT = MRA * 16, CIT = NRB * 16;
   constexpr int DV = COT / 8, XV = CIT / 8;            // 16-byte units per pixel row
   constexpr int TPMAX = TAPS == 9 ? 256 : 128;
-  constexpr int ND = (TPMAX * DV + NT - 1) / NT;       // dy units fetched per thread
-  constexpr int NX = TAPS == 9 ? 5 : (TPMAX * XV + NT - 1) / NT;   // patch units per thread (host keeps PH*PW*XV <= NX*NT)
   YS_DYN_LDS(lds);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 15, q = lane >> 4;
   const int TW = 1 << a.TWS, TP = a.TH * TW;
   const int nkb = (TP + 31) >> 5;
   const int ZR = nkb * 32;                              // zero row of the dy image
-  char* sDb = (char*)lds;                               // [ZR + 1][pdb], then the patch [PH*PW][pxb]
+  const unsigned xbase = RING ? (unsigned)rg.nrd * 1024u : (unsigned)((ZR + 1) * a.pdb);   // a stage: [ZR + 1][pdb], then the patch [PH*PW][pxb] (RING: from the next KB boundary, a request has one descriptor)
   const int ci_tiles = (a.Cin + CIT - 1) / CIT;
   const int co0 = (blockIdx.y / ci_tiles) * COT;
   const int ci0 = (blockIdx.y % ci_tiles) * CIT;
   const char* dyb = (const char*)a.dy;
   const char* xb = (const char*)a.x;
   const int S = a.stride;
-  const int npatch = a.PH * a.PW * XV;
+  constexpr unsigned YS_WG_NOUNIT = 0xffffffffu;
 
+  // tiles tile, tile + gridDim.x, ...: the coordinates advance by the decoded grid stride with carries (conv_p2_body's advance), no division per tile
+  int stx, sty, stb;
+  {
+    const int G = (int)gridDim.x;
+    stx = G % a.tiles_x; const int rem = G / a.tiles_x;
+    sty = rem % a.tiles_y; stb = rem / a.tiles_y;
+  }
+  auto advance = [&](int& txi, int& tyi, int& b) {
+    txi += stx; if (txi >= a.tiles_x) { txi -= a.tiles_x; tyi++; }
+    tyi += sty; if (tyi >= a.tiles_y) { tyi -= a.tiles_y; b++; }
+    b += stb;
+  };
+
+  f32x4 acc[MRA][NRB];
+#pragma unroll
+  for (int i = 0; i < MRA; i++)
+#pragma unroll
+    for (int j = 0; j < NRB; j++) acc[i][j] = f32x4_zero();
+
+  const int tap = TAPS == 9 ? wave : 0;
+  const int kh = tap / 3, kw = tap - kh * 3;
+  const int rr = li >> 2, c4 = li & 3;                  // this lane's row / 4-column group inside a [4][16] block
+  // K order: MFMA k = 8q + 4h + j  <->  tile pixel p = 32*kb + 16h + 4q + j (any bijection works as long as both operands
+  // use it); this one makes the 32 lanes the LDS services together (q, q+1) read 8 consecutive rows -> distinct banks with
+  // the odd-slot row pitch.  Per lane and h the pixel advances by 32 per K-block: constant LDS strides, no per-step divides.
+  unsigned dof[2], xof[2];
+  int ty0[2], tx0[2];
+#pragma unroll
+  for (int h = 0; h < 2; h++) {
+    const int p0 = 16 * h + 4 * q + rr;
+    ty0[h] = p0 >> a.TWS; tx0[h] = p0 & (TW - 1);
+    dof[h] = (unsigned)(p0 * a.pdb + c4 * 8);
+    xof[h] = xbase + (unsigned)(((ty0[h] * S + kh) * a.PW + tx0[h] * S + kw) * a.pxb + c4 * 8);
+  }
+  const unsigned dstep = 32u * (unsigned)a.pdb;                          // 32 pixels further down the dy image
+  const unsigned xstep = (unsigned)((32 >> a.TWS) * S * a.PW * a.pxb);   // 32/TW tile rows further down the patch
+  const unsigned zof = (unsigned)(ZR * a.pdb + c4 * 8);
+  const unsigned xzero = xbase + (unsigned)(c4 * 8);
+  const int rows_kb = 32 >> a.TWS;
+  // the K loop of one tile on the stage at lb
+  auto multiply = [&](const char* lb, int txi, int tyi) {
+    const int oy0 = tyi * a.TH, ox0 = txi * TW;
+    // rows of the tile that hold image pixels (tile-local), and this lane's column validity
+    const int tylim = (a.Hout - oy0) < a.TH ? (a.Hout - oy0) : a.TH;
+    const bool colok0 = (ox0 + tx0[0]) < a.Wout, colok1 = (ox0 + tx0[1]) < a.Wout;
+    for (int kb = (TAPS == 9 ? 0 : wave); kb < nkb; kb += (TAPS == 9 ? 1 : NW)) {
+      // the transpose reads land asynchronously: their destination registers must not be touched before ys_lds_tr_wait
+      uint2 ra[2][MRA], rb[2][NRB];
+#pragma unroll
+      for (int h = 0; h < 2; h++) {
+        const int ty = ty0[h] + kb * rows_kb;
+        const bool ok = (h == 0 ? colok0 : colok1) && ty < tylim;
+        const unsigned d = ok ? dof[h] + (unsigned)kb * dstep : zof;
+        const unsigned x = ty < a.TH ? xof[h] + (unsigned)kb * xstep : xzero;   // rounding pixels: any initialised row
+#pragma unroll
+        for (int i = 0; i < MRA; i++) ra[h][i] = ys_lds_tr_b64(lb + d + i * 32);
+#pragma unroll
+        for (int j = 0; j < NRB; j++) rb[h][j] = ys_lds_tr_b64(lb + x + j * 32);
+      }
+#pragma unroll
+      for (int i = 0; i < MRA; i++) ys_lds_tr_wait(ra[0][i], ra[1][i]);
+#pragma unroll
+      for (int j = 0; j < NRB; j++) ys_lds_tr_wait(rb[0][j], rb[1][j]);
+      uint4 fa[MRA], fb[NRB];
+#pragma unroll
+      for (int i = 0; i < MRA; i++) fa[i] = make_uint4(ra[0][i].x, ra[0][i].y, ra[1][i].x, ra[1][i].y);
+#pragma unroll
+      for (int j = 0; j < NRB; j++) fb[j] = make_uint4(rb[0][j].x, rb[0][j].y, rb[1][j].x, rb[1][j].y);
+#pragma unroll
+      for (int i = 0; i < MRA; i++)
+#pragma unroll
+        for (int j = 0; j < NRB; j++) acc[i][j] = ys_mma<bf16_t>(fa[i], fb[j], acc[i][j]);
+    }
+  };
+
+  int tile = blockIdx.x;
+  int txi, tyi, b;
+  {
+    int t = tile;
+    txi = t % a.tiles_x; t /= a.tiles_x;
+    tyi = t % a.tiles_y; b = t / a.tiles_y;
+  }
+  int ntx = txi, nty = tyi, nb = b;                     // the tile whose operands are requested next
+
+  if constexpr (RING) {
+  // ------------------------------------------------------------------------------------------------ DMA into a ring of stages
+  // A request of a wave lands 64 x 16 contiguous bytes at a wave-uniform LDS address, so a stage is cut into 1 KB requests and the lane that falls on 16-byte slot s
+  // owns whatever (pixel, channel unit) lives there.  Pad slots of a row pitch, the zero row, the 32-pixel rounding rows, pixels outside the image and channels outside
+  // the layer carry the out-of-range offset: the hardware writes zeros (ys_hip.h), so the zero row is rewritten with every tile and needs no store of its own.
+  // Request r of the dy image belongs to wave r % NW, likewise the patch's; every wave issues kd + kx requests per tile, the ones beyond the image / patch being
+  // all-out-of-range FILLERS aimed at the stage's spare KB -- a fixed count per wave, which is what lets the tile loop wait with a counted vmcnt.
+  // The records are those of the register fetch (below), indexed by request instead of by tid + NT * k, without the LDS-slot word.
+  static_assert(TAPS == 9, "the 4-wave 1x1 launches keep the register fetch (wgrad_tr_plan)");
+  constexpr int KDMAX = wg_kdmax(MRA), KXMAX = wg_kxmax(NRB);
+  const ys_rsrc_t rsD = ys_make_rsrc(dyb + (long)a.dy_coff * 2L, a.dybytes);
+  const ys_rsrc_t rsX = ys_make_rsrc(xb + (long)a.in_coff * 2L, a.xbytes);
+  const unsigned wv = wg_uniform((unsigned)wave);
+  const unsigned spare = (unsigned)(rg.nrd + rg.nrx);
+  unsigned doff[KDMAX], drc[KDMAX], xoff[KXMAX], xrc[KXMAX];
+#pragma unroll
+  for (int k = 0; k < KDMAX; k++) {
+    doff[k] = 0u; drc[k] = YS_WG_NOUNIT;
+    if (k < rg.kd) {
+      const unsigned byte = (wv + (unsigned)(NW * k)) * 1024u + (unsigned)lane * 16u;     // a filler (request >= nrd) lies beyond the zero row: no unit
+      const unsigned p = byte / (unsigned)a.pdb, u = (byte - p * (unsigned)a.pdb) >> 4;
+      const unsigned ty = p >> a.TWS, tx = p & (unsigned)(TW - 1);
+      const int c = co0 + (int)u * 8;
+      doff[k] = ((ty * (unsigned)a.Wout + tx) * (unsigned)a.dy_ldc + (unsigned)c) * 2u;
+      if (p < (unsigned)TP && u < (unsigned)DV && c < a.Cout) drc[k] = ty << 16 | tx;
+    }
+#ifndef YS_EMU_BUILD
+    asm volatile("" : "+v"(doff[k]), "+v"(drc[k]));   // held in registers from here on: the compiler otherwise sinks the divisions into the tile loop
+#endif
+  }
+#pragma unroll
+  for (int k = 0; k < KXMAX; k++) {
+    xoff[k] = 0u; xrc[k] = YS_WG_NOUNIT;
+    if (k < rg.kx) {
+      const unsigned byte = (wv + (unsigned)(NW * k)) * 1024u + (unsigned)lane * 16u;
+      const unsigned pix = byte / (unsigned)a.pxb, u = (byte - pix * (unsigned)a.pxb) >> 4;
+      const unsigned r = pix / (unsigned)a.PW, cc = pix - r * (unsigned)a.PW;
+      const int c = ci0 + (int)u * 8;
+      xoff[k] = ((r * (unsigned)a.Win + cc) * (unsigned)a.in_ldc + (unsigned)c) * 2u;
+      if (pix < (unsigned)(a.PH * a.PW) && u < (unsigned)XV && c < a.Cin) xrc[k] = r << 16 | cc;
+    }
+#ifndef YS_EMU_BUILD
+    asm volatile("" : "+v"(xoff[k]), "+v"(xrc[k]));
+#endif
+  }
+  // the requests of one tile into the stage at sb.  Per tile the uniform origins and windows, per unit one add, two unsigned compares and a select, as the register fetch.
+  auto request = [&](int txi, int tyi, int b, char* sb) {
+    const int oy0 = tyi * a.TH, ox0 = txi * TW;
+    const unsigned dh = (unsigned)((a.Hout - oy0) < a.TH ? (a.Hout - oy0) : a.TH), dw = (unsigned)((a.Wout - ox0) < TW ? (a.Wout - ox0) : TW);
+    const unsigned dorg = wg_uniform((((unsigned)b * (unsigned)a.dy_bstride + (unsigned)oy0 * (unsigned)a.Wout + (unsigned)ox0) * (unsigned)a.dy_ldc) * 2u);
+#pragma unroll
+    for (int k = 0; k < KDMAX; k++)
+      if (k < rg.kd) {
+        const bool ok = (bool)((int)((drc[k] >> 16) < dh) & (int)((drc[k] & 0xffffu) < dw));
+        const unsigned rq = wv + (unsigned)(NW * k);
+        ys_bufld_lds16_nom0(rsD, ok ? dorg + doff[k] : YS_BUF_OOB, 0u, sb + (rq < (unsigned)rg.nrd ? rq : spare) * 1024u);
+      }
+    const int iy0 = oy0 * S - a.pad, ix0 = ox0 * S - a.pad;
+    const unsigned rlo = iy0 < 0 ? (unsigned)-iy0 : 0u, clo = ix0 < 0 ? (unsigned)-ix0 : 0u;
+    const unsigned rn = (unsigned)((a.Hin - iy0) < a.PH ? (a.Hin - iy0) : a.PH) - rlo, cn = (unsigned)((a.Win - ix0) < a.PW ? (a.Win - ix0) : a.PW) - clo;
+    const unsigned xorg = wg_uniform((((unsigned)b * (unsigned)a.in_bstride + (unsigned)iy0 * (unsigned)a.Win + (unsigned)ix0) * (unsigned)a.in_ldc) * 2u);
+#pragma unroll
+    for (int k = 0; k < KXMAX; k++)
+      if (k < rg.kx) {
+        const bool ok = (bool)((int)(((xrc[k] >> 16) - rlo) < rn) & (int)(((xrc[k] & 0xffffu) - clo) < cn));
+        const unsigned rq = wv + (unsigned)(NW * k);
+        ys_bufld_lds16_nom0(rsX, ok ? xorg + xoff[k] : YS_BUF_OOB, 0u, sb + (rq < (unsigned)rg.nrx ? (unsigned)rg.nrd + rq : spare) * 1024u);
+      }
+  };
+  // Tile t (t = 0, 1, ... of this workgroup) lives in stage t % ns.  Prologue: the first ns - 1 tiles, those that exist.  One trip for tile t:
+  //   1. wait until this wave's own requests of tile t have landed: vmcnt(kd + kx) when tile t + 1 is in flight behind it (ns = 3), else vmcnt(0).  The count is a
+  //      per-launch uniform, waited through the uniform switch of ys_wait_vm_dyn (kd + kx <= 15 where ns = 3: wgrad_tr_plan)
+  //   2. ys_barrier_lds(): every wave's have, and every wave finished reading stage (t - 1) % ns in the previous trip.  It does not wait on vmcnt
+  //   3. request tile t + ns - 1 into stage (t - 1) % ns
+  //   4. multiply stage t % ns
+  const int G = (int)gridDim.x;
+  const int nper = rg.kd + rg.kx;
+  char* const lb0 = (char*)lds;
+  unsigned cst = 0u, fst = 0u;                          // byte offsets of the stage being multiplied / requested next
+  int ftile = tile;
+#pragma unroll 1
+  for (int j = 0; j < rg.ns - 1; j++) {
+    if (ftile < a.ntiles) request(ntx, nty, nb, lb0 + fst);
+    ftile += G; advance(ntx, nty, nb);
+    fst += rg.stage;
+  }
+  while (tile < a.ntiles) {
+    if (rg.ns == 3 && tile + G < a.ntiles) ys_wait_vm_dyn(nper); else ys_wait_vm<0>();
+    ys_barrier_lds();
+    if (ftile < a.ntiles) request(ntx, nty, nb, lb0 + fst);
+    ftile += G; advance(ntx, nty, nb);
+    fst += rg.stage; if (fst == (unsigned)rg.ns * rg.stage) fst = 0u;
+    multiply(lb0 + cst, txi, tyi);
+    tile += G; advance(txi, tyi, b);
+    cst += rg.stage; if (cst == (unsigned)rg.ns * rg.stage) cst = 0u;
+  }
+  } else {
+  // ------------------------------------------------------------------------------------------------ one stage, fetched through registers
+  constexpr int ND = (TPMAX * DV + NT - 1) / NT;       // dy units fetched per thread
+  constexpr int NX = wg_nx(NRB, TAPS == 9);            // patch units per thread (host keeps PH*PW*XV <= NX*NT)
+  const int npatch = a.PH * a.PW * XV;
+  char* sDb = (char*)lds;
   for (int i = tid; i < a.pdb / 4; i += NT) ((unsigned*)(sDb + (size_t)ZR * a.pdb))[i] = 0u;
 
   // both operands through buffer descriptors: every unit's load is unconditional, padding / unused units carry the out-of-range
@@ -250,7 +458,6 @@ conv_wgrad_tr_kernel(WgradArgs a) {
   //   rc   row << 16 | column inside the tile / patch; a unit that does not exist (beyond the tile / patch, channel outside the layer) carries YS_WG_NOUNIT, a
   //        row and column beyond any tile, so the tile's two bounds compares reject it with the pixels outside the image
   //   lds  byte offset of the unit's LDS slot; YS_WG_NOUNIT beyond the tile / patch (nothing is stored there)
-  constexpr unsigned YS_WG_NOUNIT = 0xffffffffu;
   unsigned doff[ND], drc[ND], dlds[ND], xoff[NX], xrc[NX], xlds[NX];
 #pragma unroll
   for (int k = 0; k < ND; k++) {
@@ -302,55 +509,6 @@ conv_wgrad_tr_kernel(WgradArgs a) {
       rx[k] = ys_bufld16(rsX, ok ? xorg + xoff[k] : YS_BUF_OOB);
     }
   };
-  // tiles tile, tile + gridDim.x, ...: the coordinates advance by the decoded grid stride with carries (conv_p2_body's advance), no division per tile
-  int stx, sty, stb;
-  {
-    const int G = (int)gridDim.x;
-    stx = G % a.tiles_x; const int rem = G / a.tiles_x;
-    sty = rem % a.tiles_y; stb = rem / a.tiles_y;
-  }
-  auto advance = [&](int& txi, int& tyi, int& b) {
-    txi += stx; if (txi >= a.tiles_x) { txi -= a.tiles_x; tyi++; }
-    tyi += sty; if (tyi >= a.tiles_y) { tyi -= a.tiles_y; b++; }
-    b += stb;
-  };
-
-  f32x4 acc[MRA][NRB];
-#pragma unroll
-  for (int i = 0; i < MRA; i++)
-#pragma unroll
-    for (int j = 0; j < NRB; j++) acc[i][j] = f32x4_zero();
-
-  const int tap = TAPS == 9 ? wave : 0;
-  const int kh = tap / 3, kw = tap - kh * 3;
-  const int rr = li >> 2, c4 = li & 3;                  // this lane's row / 4-column group inside a [4][16] block
-  // K order: MFMA k = 8q + 4h + j  <->  tile pixel p = 32*kb + 16h + 4q + j (any bijection works as long as both operands
-  // use it); this one makes the 32 lanes the LDS services together (q, q+1) read 8 consecutive rows -> distinct banks with
-  // the odd-slot row pitch.  Per lane and h the pixel advances by 32 per K-block: constant LDS strides, no per-step divides.
-  unsigned dof[2], xof[2];
-  int ty0[2], tx0[2];
-#pragma unroll
-  for (int h = 0; h < 2; h++) {
-    const int p0 = 16 * h + 4 * q + rr;
-    ty0[h] = p0 >> a.TWS; tx0[h] = p0 & (TW - 1);
-    dof[h] = (unsigned)(p0 * a.pdb + c4 * 8);
-    xof[h] = (unsigned)((size_t)(ZR + 1) * a.pdb) + (unsigned)(((ty0[h] * S + kh) * a.PW + tx0[h] * S + kw) * a.pxb + c4 * 8);
-  }
-  const unsigned dstep = 32u * (unsigned)a.pdb;                          // 32 pixels further down the dy image
-  const unsigned xstep = (unsigned)((32 >> a.TWS) * S * a.PW * a.pxb);   // 32/TW tile rows further down the patch
-  const unsigned zof = (unsigned)(ZR * a.pdb + c4 * 8);
-  const unsigned xzero = (unsigned)((ZR + 1) * a.pdb + c4 * 8);
-  const int rows_kb = 32 >> a.TWS;
-  const char* lb = (const char*)lds;
-
-  int tile = blockIdx.x;
-  int txi, tyi, b;
-  {
-    int t = tile;
-    txi = t % a.tiles_x; t /= a.tiles_x;
-    tyi = t % a.tiles_y; b = t / a.tiles_y;
-  }
-  int ntx = txi, nty = tyi, nb = b;
   if (tile < a.ntiles) fetch(txi, tyi, b);
   while (tile < a.ntiles) {
     ys_barrier_lds();                                   // every wave finished reading the previous tile
@@ -361,42 +519,12 @@ conv_wgrad_tr_kernel(WgradArgs a) {
     for (int k = 0; k < NX; k++)
       if (xlds[k] != YS_WG_NOUNIT) *(uint4*)((char*)lds + xlds[k]) = rx[k];
     ys_barrier_lds();
-    const int oy0 = tyi * a.TH, ox0 = txi * TW;
     const int ntile = tile + gridDim.x;
     advance(ntx, nty, nb);
     if (ntile < a.ntiles) fetch(ntx, nty, nb);          // in flight while this tile is consumed
-    // rows of the tile that hold image pixels (tile-local), and this lane's column validity
-    const int tylim = (a.Hout - oy0) < a.TH ? (a.Hout - oy0) : a.TH;
-    const bool colok0 = (ox0 + tx0[0]) < a.Wout, colok1 = (ox0 + tx0[1]) < a.Wout;
-    for (int kb = (TAPS == 9 ? 0 : wave); kb < nkb; kb += (TAPS == 9 ? 1 : NW)) {
-      // the transpose reads land asynchronously: their destination registers must not be touched before ys_lds_tr_wait
-      uint2 ra[2][MRA], rb[2][NRB];
-#pragma unroll
-      for (int h = 0; h < 2; h++) {
-        const int ty = ty0[h] + kb * rows_kb;
-        const bool ok = (h == 0 ? colok0 : colok1) && ty < tylim;
-        const unsigned d = ok ? dof[h] + (unsigned)kb * dstep : zof;
-        const unsigned x = ty < a.TH ? xof[h] + (unsigned)kb * xstep : xzero;   // rounding pixels: any initialised row
-#pragma unroll
-        for (int i = 0; i < MRA; i++) ra[h][i] = ys_lds_tr_b64(lb + d + i * 32);
-#pragma unroll
-        for (int j = 0; j < NRB; j++) rb[h][j] = ys_lds_tr_b64(lb + x + j * 32);
-      }
-#pragma unroll
-      for (int i = 0; i < MRA; i++) ys_lds_tr_wait(ra[0][i], ra[1][i]);
-#pragma unroll
-      for (int j = 0; j < NRB; j++) ys_lds_tr_wait(rb[0][j], rb[1][j]);
-      uint4 fa[MRA], fb[NRB];
-#pragma unroll
-      for (int i = 0; i < MRA; i++) fa[i] = make_uint4(ra[0][i].x, ra[0][i].y, ra[1][i].x, ra[1][i].y);
-#pragma unroll
-      for (int j = 0; j < NRB; j++) fb[j] = make_uint4(rb[0][j].x, rb[0][j].y, rb[1][j].x, rb[1][j].y);
-#pragma unroll
-      for (int i = 0; i < MRA; i++)
-#pragma unroll
-        for (int j = 0; j < NRB; j++) acc[i][j] = ys_mma<bf16_t>(fa[i], fb[j], acc[i][j]);
-    }
+    multiply((const char*)lds, txi, tyi);
     tile = ntile; txi = ntx; tyi = nty;
+  }
   }
 
   float* outp = a.partial + (long)blockIdx.x * a.Cout * a.KH * a.KW * a.Cin;
@@ -433,12 +561,13 @@ conv_wgrad_tr_kernel(WgradArgs a) {
 }
 
 // host-side plan of the LDS-tile wgrad kernel
-struct WgPlan { int ok, taps9, mra, nrb, th, tws, tx, ty, ph, pw, pdb, pxb, gx; size_t lds; };
-static int wg_pitch_bytes(int ch) {       // smallest row pitch >= ch*2 bytes whose 32-byte slot count is odd (8 rows -> 8 bank slots)
-  int s = (ch * 2 + 31) / 32;
-  if (!(s & 1)) s++;
-  return s * 32;
-}
+// ns = stages of the LDS ring (2 or 3: the DMA variants, `ring` filled in); 1 = one stage fetched through registers.  lds = the launch's whole dynamic LDS.
+struct WgPlan { int ok, taps9, mra, nrb, th, tws, tx, ty, ph, pw, pdb, pxb, gx, ns; size_t lds; WgRing ring; };
+// The deepest ring a plan may choose.  Measured on the MI355X (profiles/README.md, "conv_wgrad_tr: DMA ring"): with the tile kept, three stages were never faster
+// than two in any launch class of the headline step and slower in some, so the product plans two; -DYS_WG_RING_MAX=3 is the other arm of that comparison.
+#ifndef YS_WG_RING_MAX
+#define YS_WG_RING_MAX 2
+#endif
 // descriptor ranges of the dy / x views (bytes from the first channel to the end of the last image); false if either is >= 2 GB
 static bool wgrad_view_bytes(const WgradArgs& a, unsigned& dyb, unsigned& xb) {
   const long dpix = (long)(a.B - 1) * a.dy_bstride + (long)a.Hout * a.Wout, xpix = (long)(a.B - 1) * a.in_bstride + (long)a.Hin * a.Win;
@@ -478,11 +607,10 @@ static WgPlan wgrad_tr_plan(const WgradArgs& a) {
   }
   const int nt = k3 ? 576 : 256, tpmax = k3 ? 256 : 128;
   const int cot = p.mra * 16, cit = p.nrb * 16, xv = cit / 8;
-  const int nxu = (k3 ? 5 : (tpmax * xv + nt - 1) / nt) * nt;
+  const int nxu = wg_nx(p.nrb, k3) * nt;
   const int S = a.stride;
   p.pdb = wg_pitch_bytes(cot);
-  // stride-2 patches are read every other row: a pitch of 16 (mod 32) bytes makes the 2-row step an odd slot count
-  p.pxb = S == 1 ? wg_pitch_bytes(cit) : ((cit * 2 + 15) / 32) * 32 + 16;
+  p.pxb = S == 1 ? wg_pitch_bytes(cit) : wg_pitch_s2_bytes(cit);
   double best = 1e30;
   for (int tws = 2; tws <= 5; tws++) {
     const int tw = 1 << tws;
@@ -518,10 +646,33 @@ static WgPlan wgrad_tr_plan(const WgradArgs& a) {
   const long per = (ntiles + gx - 1) / gx;                // equal tile counts: no idle tail workgroups, fewer partials
   gx = (ntiles + per - 1) / per;
   p.gx = (int)gx;
+  // The ring (9-wave 3x3 launches).  The tile, the workgroups per CU and the grid above are the single-stage plan's and stay: the partial slabs and the order of
+  // every sum are then those of the register fetch, whichever fetch runs.  A stage is the same image cut into 1 KB requests (the patch from a KB boundary); the ring
+  // takes the most stages, up to YS_WG_RING_MAX, that per_cu workgroups hold under the same 150 KB.  Where not even two fit (stages above 75 KB) the launch keeps the
+  // register fetch rather than a smaller tile or fewer workgroups, both of which move the slabs.  The 4-wave 1x1 launches keep it too: with the DMA fetch their 8 x 8
+  // and 20 x 4 tile classes measured 5-20 % slower, and the 16 x 8 / 32 x 4 classes run two to four workgroups per CU, which leaves a ring no room.
+  // And a launch whose workgroups walk ONE tile each keeps it: a ring overlaps the fetch of a tile with the multiplication of the one before, and there is none.
+  p.ns = 1;
+  if (k3 && per >= 2) {
+    const int nw = nt / 64, nkb = (p.th * (1 << p.tws) + 31) / 32;
+    WgRing r{};
+    r.nrd = ys_cdiv((nkb * 32 + 1) * p.pdb, 1024); r.nrx = ys_cdiv(p.ph * p.pw * p.pxb, 1024);
+    r.kd = ys_cdiv(r.nrd, nw); r.kx = ys_cdiv(r.nrx, nw);
+    const int fillers = r.kd * nw - r.nrd + r.kx * nw - r.nrx;
+    r.stage = (unsigned)(r.nrd + r.nrx + (fillers ? 1 : 0)) * 1024u;
+    if (r.kd <= wg_kdmax(p.mra) && r.kx <= wg_kxmax(p.nrb))
+      for (int ns = YS_WG_RING_MAX; ns >= 2; ns--) {
+        const size_t lds = (size_t)ns * r.stage;
+        if (lds * per_cu > 150 * 1024) continue;
+        if (ns == 3 && r.kd + r.kx > 15) continue;      // the counted wait of the tile loop goes through ys_wait_vm_dyn (0..15)
+        r.ns = ns; p.ns = ns; p.lds = lds; p.ring = r;
+        break;
+      }
+  }
   return p;
 }
 
-template <int MRA, int NRB, int TAPS>
+template <int MRA, int NRB, int TAPS, bool RING>
 static void wgrad_tr_launch_t(hipStream_t st, WgradArgs a, const WgPlan& p) {
   a.TH = p.th; a.TWS = p.tws; a.tiles_x = p.tx; a.tiles_y = p.ty; a.ntiles = p.tx * p.ty * a.B;
   wgrad_view_bytes(a, a.dybytes, a.xbytes);
@@ -531,17 +682,31 @@ static void wgrad_tr_launch_t(hipStream_t st, WgradArgs a, const WgPlan& p) {
   int dev_id = 0;
   (void)hipGetDevice(&dev_id);
   if (!(attr_done.load(std::memory_order_relaxed) & (1u << (dev_id & 31)))) {
-    hipFuncSetAttribute((const void*)conv_wgrad_tr_kernel<MRA, NRB, TAPS>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    hipFuncSetAttribute((const void*)conv_wgrad_tr_kernel<MRA, NRB, TAPS, RING>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     attr_done.fetch_or(1u << (dev_id & 31), std::memory_order_relaxed);
   }
   char lab[160] = "";
-  if (ys_kprof_enabled()) snprintf(lab, sizeof(lab), "wgrad_tr k%d s%d cin%d cout%d M%d tile%dx%d grid%dx%d lds%d", a.KH, a.stride, a.Cin, a.Cout, a.M, p.th, 1 << p.tws, p.gx, gy, (int)p.lds);
+  if (ys_kprof_enabled()) {       // a ring launch says so at the end of its label (" ring2"); the register fetch keeps the label it always had
+    const int n = snprintf(lab, sizeof(lab), "wgrad_tr k%d s%d cin%d cout%d M%d tile%dx%d grid%dx%d lds%d", a.KH, a.stride, a.Cin, a.Cout, a.M, p.th, 1 << p.tws, p.gx, gy, (int)p.lds);
+    if (RING && n > 0 && n < (int)sizeof(lab)) snprintf(lab + n, sizeof(lab) - n, " ring%d", p.ns);
+  }
   YsKprofScope prof(st, "conv_wgrad", lab);
-  YS_LAUNCH_LDS((conv_wgrad_tr_kernel<MRA, NRB, TAPS>), dim3(p.gx, gy), (TAPS == 9 ? 576 : 256), p.lds, st, a);
+  YS_LAUNCH_LDS((conv_wgrad_tr_kernel<MRA, NRB, TAPS, RING>), dim3(p.gx, gy), (TAPS == 9 ? 576 : 256), p.lds, st, a, p.ring);
 }
 
 static bool wgrad_tr_dispatch(hipStream_t st, const WgradArgs& a, const WgPlan& p) {
-#define WT(M_, N_) if (p.mra == M_ && p.nrb == N_) { if (p.taps9) wgrad_tr_launch_t<M_, N_, 9>(st, a, p); else wgrad_tr_launch_t<M_, N_, 1>(st, a, p); return true; }
+  // the 9-wave table is wgrad_tr_plan's ok_pairs: the other fragment tiles (4x3, 4x4, 5x2, 5x3, 5x4) spill with nine taps, are never planned and are not built
+#define WT(M_, N_) if (p.mra == M_ && p.nrb == N_) { if (p.ns > 1) wgrad_tr_launch_t<M_, N_, 9, true>(st, a, p); else wgrad_tr_launch_t<M_, N_, 9, false>(st, a, p); return true; }
+  if (p.taps9) {
+    WT(1, 1) WT(1, 2) WT(1, 3) WT(1, 4)
+    WT(2, 1) WT(2, 2) WT(2, 3) WT(2, 4)
+    WT(3, 1) WT(3, 2) WT(3, 3) WT(3, 4)
+    WT(4, 1) WT(4, 2)
+    WT(5, 1)
+    return false;
+  }
+#undef WT
+#define WT(M_, N_) if (p.mra == M_ && p.nrb == N_) { wgrad_tr_launch_t<M_, N_, 1, false>(st, a, p); return true; }
   WT(1, 1) WT(1, 2) WT(1, 3) WT(1, 4)
   WT(2, 1) WT(2, 2) WT(2, 3) WT(2, 4)
   WT(3, 1) WT(3, 2) WT(3, 3) WT(3, 4)
