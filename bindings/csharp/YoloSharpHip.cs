@@ -22,7 +22,7 @@ namespace YoloSharp.Native
     [StructLayout(LayoutKind.Sequential)]
     internal struct YsModelDesc
     {
-        public int family;     // 8 = Yolov8 (Models/Yolo.cs:10), 11 = Yolov11
+        public int family;     // 5 = Yolov5u (Models/Yolo.cs:137; task 0 only), 8 = Yolov8 (Models/Yolo.cs:10), 11 = Yolov11
         public int size;       // YoloSize n,s,m,l,x = 0..4 (Types/YoloTypes.cs)
         public int task;       // 0 detect, 1 segment, 2 obb, 3 pose, 4 classify (Yolov8Classify / Yolov11Classify; Float32 or BFloat16)
         public int nc, reg_max, height, width, max_batch;
@@ -173,7 +173,7 @@ namespace YoloSharp.Native
                                                                 int onDevice, [Out] float[] iou);
         [DllImport(Lib)] internal static extern int ys_match_predictions(IntPtr ctx, float[] predCls, int n, float[] trueCls, int nl, float[] iou,
                                                                          int onDevice, [Out] byte[] correct);
-        // per-block handles (Modules.Conv / Bottleneck / C2f / C3k2 / SPPF / C2PSA / Proto as standalone Module<Tensor,Tensor>)
+        // per-block handles (Modules.Conv / Bottleneck / C2f / C3k2 / SPPF / C2PSA / Proto / C3 as standalone Module<Tensor,Tensor>; kind 0..7 in that order)
         [StructLayout(LayoutKind.Sequential)] internal struct BlockDesc {
             public int kind, c1, c2, n, shortcut, c3k; public float e; public int k, s, act, height, width, maxBatch, dtype; }
         [DllImport(Lib)] internal static extern int ys_block_create(IntPtr ctx, ref BlockDesc desc, out IntPtr block);
@@ -186,6 +186,11 @@ namespace YoloSharp.Native
         [DllImport(Lib)] internal static extern int ys_head_forward(IntPtr head, IntPtr[] xNchw3, int onDevice, int batch);   // pinned float[] or device pointers
         [DllImport(Lib)] internal static extern int ys_head_set_grads(IntPtr head, float[] dBoxes, float[] dScores, float[] dExtra, float[] dProto);
         [DllImport(Lib)] internal static extern int ys_head_backward(IntPtr head, int onDevice, IntPtr[] dxNchw3);
+
+        // the Yolov5u stem Conv(3, c, 6, 2, 2) on the kernels a bf16 model runs for model.0 (unit parity; scale == null: training form)
+        [DllImport(Lib)] internal static extern int ys_stem6_fwd(IntPtr ctx, float[] xNchw, int batch, int h, int w, float[] wOihw, int cout, int statMode,
+                                                                 float[] scale, float[] shift, int act, [Out] float[] yNchw, [Out] double[] stats);
+        [DllImport(Lib)] internal static extern int ys_stem6_wgrad(IntPtr ctx, float[] xNchw, int batch, int h, int w, float[] dyNchw, int cout, [Out] float[] dwOihw);
 
         [DllImport(Lib)] internal static extern int ys_nms_batched(IntPtr ctx, float[] pred, int onDevice, int batch, int channels, int anchors,
                                                                    float conf, float iou, int maxDet, int nc, int maxNms, int maxWh,

@@ -39,7 +39,8 @@ enum ys_status {
  * forward / input-gradient convolutions on the fp8 MFMA path -- e4m3 weights (current per-tensor scale) and activations, e5m2
  * gradients (delayed per-tensor scales), fp32 accumulation; layers whose channel count is not a multiple of 32 stay in bf16. */
 enum ys_dtype { YS_F32 = 0, YS_BF16 = 1, YS_FP8 = 2 };
-enum ys_family { YS_YOLOV8 = 8, YS_YOLOV11 = 11 };   /* Models/Yolo.cs:10-135, :200-258 */
+enum ys_family { YS_YOLOV5U = 5, YS_YOLOV8 = 8, YS_YOLOV11 = 11 };   /* Models/Yolo.cs:137-198, :10-135, :200-258.  YS_YOLOV5U: the detect task only
+                                                                        (with End2End); its other tasks are refused with YS_ERR_UNSUPPORTED */
 enum ys_size { YS_N = 0, YS_S = 1, YS_M = 2, YS_L = 3, YS_X = 4 }; /* Types/YoloTypes.cs YoloSize; Yolo.cs:43-51 */
 enum ys_task { YS_DETECT = 0, YS_SEGMENT = 1, YS_OBB = 2, YS_POSE = 3,
                YS_CLASSIFY = 4 };   /* Config.cs TaskType.  YS_CLASSIFY: Yolov8Classify / Yolov11Classify (Models/Yolo.cs:537-573),
@@ -82,6 +83,9 @@ typedef struct ys_model_desc {
   int32_t kpt_dim;    /* YS_POSE: 2 = (x, y), 3 = (x, y, visibility) (0 = 3) */
 } ys_model_desc;
 
+/* Built: YS_YOLOV8 / YS_YOLOV11 for all five tasks; YS_YOLOV5U (Yolo.cs:137-198: Conv(3, c, 6, 2, 2) stem, C3 blocks, SPPF, the Yolov8 Detect head as
+ * model.24) for YS_DETECT in YS_F32 / YS_BF16 -- its segment / obb / pose / classify tasks and YS_FP8 return YS_ERR_UNSUPPORTED.  The size parameter is
+ * honoured for every family (the reference's Detector.cs:17 never passes yoloSize for Yolov5u, so a reference v5u detector is always size n). */
 YS_API int ys_model_create(ys_ctx* ctx, const ys_model_desc* desc, ys_model** out);
 YS_API int ys_model_destroy(ys_model* m);
 
@@ -115,6 +119,9 @@ YS_API int ys_model_forward_u8(ys_model* m, const uint8_t* images, int on_device
 /* Classify models (Head.cs:635-643) have their own keys, all [B, nc]: "cls" = the logits after a training forward, softmax(logits, 1)
  * after an eval forward; "logits" = the logits in both modes; "dcls" = d(loss)/d(logits) after ys_loss_classify.  Every other key
  * is refused on a classify model (YS_ERR_INVALID_ARG), and these keys on the other tasks. */
+/* "model0_raw" (full models, after a training-mode forward): the raw (pre-BatchNorm) output of model.0, [B, c, H/2, W/2], as stored; "model0_dy" (after the
+ * backward; refused where the BatchNorm backward runs inside the stem's weight-gradient kernel): the gradient w.r.t. it.  The tensors the stem routes
+ * (STEM_DIRECT = 1 / 0) are compared on. */
 YS_API int ys_model_get_output(ys_model* m, const char* key, float* host, size_t count);
 /* The criterion's `preds` argument supplied by the caller (Utils/Loss.cs:411 `forward(preds, batch)`): host fp32 head outputs in the
  * reference layout -- boxes [B,4*reg_max,A], scores [B,nc,A], and for Segment models mask_coefficient [B,nm,A] + proto
@@ -147,7 +154,7 @@ YS_API int ys_model_reserve_labels(ys_model* m, int per_image);
  * ys_model_one2one_init = YoloBaseTaskModel.One2one_Init -> Detect.one2one_init (Modules/Head.cs:152-167): the one2one towers are the SAME
  * modules as cv2 / cv3 (the reference copies references, SaveWeight drops the one2one keys), so the model gains NO tensor: ys_model_num_tensors /
  * tensor_info / num_params are unchanged and weight files move freely between End2End and plain models.  max_det: rows of the post-process
- * (0 = 300, Head.cs:13).  YS_DETECT models of both families and every dtype; Segment / OBB / Pose / Classify models and the standalone block /
+ * (0 = 300, Head.cs:13).  YS_DETECT models of every family (YS_YOLOV5U carries the same Detect head) and every dtype built for it; Segment / OBB / Pose / Classify models and the standalone block /
  * head handles return YS_ERR_UNSUPPORTED (Segment models take ys_model_e2e_init, OBB models ys_model_e2e_obb_init, Pose models ys_model_e2e_pose_init below).  Call it once, after ys_model_create.  From then on:
  *   training forward (Head.cs:89-106): "one2one_boxes" / "one2one_scores" are outputs (the same values as "boxes" / "scores": same modules,
  *     same input values); the BatchNorm units of the towers update their running statistics twice, num_batches_tracked += 2.
@@ -714,6 +721,19 @@ YS_API int ys_conv_bn_act_fwd_ex(ys_ctx* ctx, int dtype, const float* x_nchw, in
                                  const float* bias, int act_silu, int training, int stat_mode, float* y_nchw,
                                  float* y_raw, float* coef, int32_t* stat_rows);
 
+/* The Yolov5u stem Conv(3, Cout, k = 6, s = 2, p = 2) (Models/Yolo.cs:163) on exactly the kernels a bf16 model runs for its model.0 (csrc/conv_stem6.hip), which
+ * read the fp32 NCHW image themselves.  Cout in {16, 32, 48, 64, 80}; any other shape returns YS_ERR_UNSUPPORTED (a model runs such a layer on the generic
+ * kernels).  fp32 HOST arrays; Ho = (H - 2) / 2 + 1, Wo = (W - 2) / 2 + 1.
+ * ys_stem6_fwd: scale == NULL is the training form -- y_nchw [B,Cout,Ho,Wo] = the raw convolution output as the bf16 values the kernel stored, stats [2][Cout] =
+ *   the per-channel sum and sum of squares of those values as the kernel produced them (stat_mode 0: fp32 rows, one per workgroup, added up here in double;
+ *   stat_mode 1: the 2^-20 fixed-point accumulators, exact sums of the workgroups' rounded partials).  Otherwise eval: y = act(scale * conv + shift) with
+ *   act != 0 = SiLU, stats unused (may be NULL).
+ * ys_stem6_wgrad: dw_oihw [Cout,3,6,6] = the weight gradient for dy_nchw [B,Cout,Ho,Wo] (rounded to bf16 on the way in, like x): the kernel's partial slabs
+ *   followed by the split reduction a model's backward segment runs. */
+YS_API int ys_stem6_fwd(ys_ctx* ctx, const float* x_nchw, int B, int H, int W, const float* w_oihw, int Cout, int stat_mode,
+                        const float* scale, const float* shift, int act, float* y_nchw, double* stats);
+YS_API int ys_stem6_wgrad(ys_ctx* ctx, const float* x_nchw, int B, int H, int W, const float* dy_nchw, int Cout, float* dw_oihw);
+
 /* autograd of the same conv2d (Amp.cs:348,370): given dy [B,Cout,Ho,Wo] returns dx [B,Cin,H,W] (optional, may be
  * NULL) and dw [Cout,Cin,k,k]; all fp32 host arrays. */
 YS_API int ys_conv_bwd(ys_ctx* ctx, int dtype, const float* x_nchw, int B, int Cin, int H, int W,
@@ -865,10 +885,11 @@ YS_API int ys_conv_f8_dgrad(ys_ctx* ctx, int B, int Cin, int H, int W, const flo
  *        YS_BLOCK_SPPF        Block.SPPF        (Block.cs:236-285)  c1 == c2
  *        YS_BLOCK_C2PSA       Block.C2PSA       (Block.cs:664-810)  c1 == c2, (c1/2) % 64 == 0, n PSABlocks
  *        YS_BLOCK_PROTO       Block.Proto       (Block.cs:51-84)    c1 -> n (= c_, hidden) -> c2 masks, output 2H x 2W
+ *        YS_BLOCK_C3          Block.C3          (Block.cs:404-442)  n Bottlenecks(k = (1, 3), e = 1.0) on int(c2 * 0.5) channels, shortcut
  *      Channel counts (c1, c2 and every hidden width) must be multiples of 4 (f32) / 8 (bf16): the widths the YOLO graphs use. */
 typedef enum ys_block_kind {
   YS_BLOCK_CONV = 0, YS_BLOCK_BOTTLENECK = 1, YS_BLOCK_C2F = 2, YS_BLOCK_C3K2 = 3, YS_BLOCK_SPPF = 4, YS_BLOCK_C2PSA = 5,
-  YS_BLOCK_PROTO = 6
+  YS_BLOCK_PROTO = 6, YS_BLOCK_C3 = 7
 } ys_block_kind;
 
 typedef struct ys_block_desc {

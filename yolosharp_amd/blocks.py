@@ -7,6 +7,7 @@
   SPPF        <- YoloSharp/Modules/Block.cs:236-285   SPPF(c1, c2)
   C2PSA       <- YoloSharp/Modules/Block.cs:664-810   C2PSA(c1, c2, n)
   Proto       <- YoloSharp/Modules/Block.cs:51-84     Proto(c1, c_, c2)
+  C3          <- YoloSharp/Modules/Block.cs:404-442   C3(c1, c2, n, shortcut)
 
 Each instance owns one `ys_block_create` handle: `forward(x)` is `Module<Tensor,Tensor>.forward` on an fp32 NCHW array,
 `backward(dy)` is autograd's backward of that call (returns dx, accumulates the parameter gradients read by `grads()`).
@@ -21,7 +22,7 @@ from . import _lib
 from .engine import Engine, _ptr
 from .model import DTYPES, Yolov8
 
-KINDS = {"Conv": 0, "Bottleneck": 1, "C2f": 2, "C3k2": 3, "SPPF": 4, "C2PSA": 5, "Proto": 6}
+KINDS = {"Conv": 0, "Bottleneck": 1, "C2f": 2, "C3k2": 3, "SPPF": 4, "C2PSA": 5, "Proto": 6, "C3": 7}
 
 
 class _Block(Yolov8):
@@ -87,6 +88,13 @@ class C2f(_Block):
     KIND = "C2f"
 
     def __init__(self, engine, c1, c2, n=1, shortcut=False, *, height, width, max_batch=1, dtype="bf16"):
+        self._create(engine, c1, c2, height, width, max_batch, dtype, n=n, shortcut=shortcut)
+
+
+class C3(_Block):
+    KIND = "C3"
+
+    def __init__(self, engine, c1, c2, n=1, shortcut=True, *, height, width, max_batch=1, dtype="bf16"):
         self._create(engine, c1, c2, height, width, max_batch, dtype, n=n, shortcut=shortcut)
 
 

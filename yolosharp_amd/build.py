@@ -18,7 +18,7 @@ EMU = os.path.join(ROOT, "tools", "hipemu")
 BUILD = os.path.join(ROOT, "build")
 
 # (the job pool takes the units in this order: the conv_halo units, minutes each, stay among the first eight so that they start at once)
-SOURCES = ["core.hip", "nms.hip", "conv.hip", "conv_gemm.hip", "conv_halo5.hip", "conv_halo4.hip", "conv_halo5m.hip", "conv_halo4m.hip", "conv_p2_group.hip", "conv_p2_f8.hip", "conv_p2.hip", "conv_p2_plan.hip", "conv_stem.hip", "conv_wgrad.hip", "conv_wgrad_gemm.hip", "elementwise.hip", "batchnorm.hip", "ops_conv.hip", "ops_bn.hip", "ops_attn_dw.hip", "ops_augment.hip", "loss.hip", "attn_dw.hip", "segloss.hip", "poseloss.hip", "valmetrics.hip", "classify.hip", "e2e.hip", "augment.hip", "augment_cls.hip", "augment_aa.hip", "dist.hip", "f8.hip", "graph.hip", "plan.hip", "model.hip", "model_api.hip", "criterion.hip"]
+SOURCES = ["core.hip", "nms.hip", "conv.hip", "conv_gemm.hip", "conv_halo5.hip", "conv_halo4.hip", "conv_halo5m.hip", "conv_halo4m.hip", "conv_p2_group.hip", "conv_p2_f8.hip", "conv_p2.hip", "conv_p2_plan.hip", "conv_stem.hip", "conv_stem6.hip", "conv_wgrad.hip", "conv_wgrad_gemm.hip", "elementwise.hip", "batchnorm.hip", "ops_conv.hip", "ops_bn.hip", "ops_attn_dw.hip", "ops_augment.hip", "loss.hip", "attn_dw.hip", "segloss.hip", "poseloss.hip", "valmetrics.hip", "classify.hip", "e2e.hip", "augment.hip", "augment_cls.hip", "augment_aa.hip", "dist.hip", "f8.hip", "graph.hip", "plan.hip", "model.hip", "model_api.hip", "criterion.hip"]
 # bit-exact fp32 sections (NMS IoU arithmetic; the augmenter's label arithmetic in the reference's order) must not be contracted into FMAs
 NO_CONTRACT = {"nms.hip", "valmetrics.hip", "augment.hip", "augment_cls.hip", "augment_aa.hip"}
 

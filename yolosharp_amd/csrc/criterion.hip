@@ -60,6 +60,26 @@ int ys_model_get_output(ys_model* m, const char* key, float* host, size_t count)
       YS_TRY(ys_unpack_nchw_launch(st, m->dtype, k == "dcls" ? b.grad : b.act, b.ldc, 0, B, m->d.nc, 1, m->out_stage));
       YS_CHECK_HIP(hipMemcpyAsync(host, m->out_stage, count * 4, hipMemcpyDeviceToHost, st));
     }
+  } else if (k == "model0_raw" || k == "model0_dy") {
+    // model.0 after a training-mode forward, [B, c, H/2, W/2] as stored: "model0_raw" its raw (pre-BatchNorm) output, "model0_dy" -- after the backward -- the
+    // gradient w.r.t. that output, i.e. the two operands its weight gradient is formed from.  What the stem routes (conv_stem.hip / conv_stem6.hip against the
+    // packed copy + generic kernels) are compared on.  model.0 is the last unit of the backward: nothing overwrites its dy before the next backward
+    YS_REQUIRE(!m->is_head && !m->convs.empty() && m->convs[0].first && m->convs[0].bn, "ys_model_get_output(%s): not a full model", key);
+    YS_REQUIRE(m->fwd_training && m->training, "ys_model_get_output(%s): the last forward did not run in training mode", key);
+    const ConvL& c = m->convs[0];
+    const bool want_dy = k == "model0_dy";
+    YS_REQUIRE(!want_dy || !ysm::stem_bnb_planned(m), "ys_model_get_output(model0_dy): this model forms model.0's dy inside its weight-gradient kernel (STEM_BNB_FUSE)");
+    if (want_dy) YS_TRY(ysm::join_wgrad_stream(m));
+    const long rpb = (long)c.Hout * c.Wout;
+    YS_REQUIRE(count == (size_t)B * c.cout * rpb, "ys_model_get_output(%s): expected %zu elements", key, (size_t)B * c.cout * rpb);
+    const void* src = want_dy ? ((m->overlap && c.dy_own) ? c.dy_own : m->dy_scratch) : (const void*)((const char*)m->y_all + (size_t)c.y_off * m->es);
+    float* tmp = nullptr;
+    YS_CHECK_HIP(hipMalloc((void**)&tmp, count * 4));
+    int rc = ys_unpack_nchw_launch(st, m->dtype, src, c.cout, 0, B, c.cout, rpb, tmp);
+    if (rc == YS_OK && hipMemcpyAsync(host, tmp, count * 4, hipMemcpyDeviceToHost, st) != hipSuccess) rc = YS_ERR_HIP;
+    if (hipStreamSynchronize(st) != hipSuccess && rc == YS_OK) rc = YS_ERR_HIP;
+    (void)hipFree(tmp);
+    if (rc != YS_OK) return rc;
   } else if (k == "det") {
     // End2End eval forward: Detect.postprocess (Head.cs:117-127) -> [B, k, 6] = (x1, y1, x2, y2, score, class), k = min(max_det, A); End2End Segment: + the
     // nm mask coefficients of the anchor (Head.cs:321-339); OBB: + the angle (Head.cs:439-452); Pose: + the nk decoded keypoint values (Head.cs:550-563)

@@ -23,10 +23,10 @@ namespace {
 
 // one Conv unit (conv+BN+act) or plain biased Conv2d; returns conv index and appends the op
 int add_conv(ys_model* m, const std::string& name, View in, View out, int cin, int cout, int k, int s, bool bn, bool act,
-             int Hin, int Win, int seg, const View* res = nullptr, bool dw = false) {
+             int Hin, int Win, int seg, const View* res = nullptr, bool dw = false, int pad = -1) {
   ConvL c; c.name = name; c.in = in; c.out = out; c.cin = cin; c.cout = cout; c.k = k; c.s = s; c.bn = bn; c.act = act; c.dw = dw;
   c.cin_pad = in.C; c.Hin = Hin; c.Win = Win;
-  const int p = k / 2;
+  const int p = c.pad = pad < 0 ? k / 2 : pad;      // autopad (Convs.cs:36-62) unless the module names its padding (Yolov5u's model.0: k = 6, p = 2)
   c.Hout = (Hin + 2 * p - k) / s + 1; c.Wout = (Win + 2 * p - k) / s + 1;
   c.cout_ld = (cout + m->epl - 1) / m->epl * m->epl;
   c.cout_real = cout;
@@ -42,25 +42,26 @@ int add_conv(ys_model* m, const std::string& name, View in, View out, int cin, i
 // registration-list entry of member `mem` of a fused convolution (plain convolutions: the index itself)
 inline int reg_entry(int conv, int mem) { return conv | (mem << 20); }
 int add_conv_reg(ys_model* m, const std::string& name, View in, View out, int cin, int cout, int k, int s, bool bn, bool act,
-                 int Hin, int Win, int seg, const View* res = nullptr, bool dw = false) {
-  const int i = add_conv(m, name, in, out, cin, cout, k, s, bn, act, Hin, Win, seg, res, dw);
+                 int Hin, int Win, int seg, const View* res = nullptr, bool dw = false, int pad = -1) {
+  const int i = add_conv(m, name, in, out, cin, cout, k, s, bn, act, Hin, Win, seg, res, dw, pad);
   m->reg.push_back(i);
   return i;
 }
 
-// Bottleneck (Block.cs:572-608) 3x3,3x3 with hidden = int(c*e); returns conv indices {cv1, cv2}
-std::pair<int, int> add_bottleneck(ys_model* m, const std::string& name, View in, View out, int c, float e, bool shortcut, int H, int W, int seg) {
+// Bottleneck (Block.cs:572-608) k1 x k1, k2 x k2 (the default k = (3, 3)) with hidden = int(c*e); returns conv indices {cv1, cv2}
+std::pair<int, int> add_bottleneck(ys_model* m, const std::string& name, View in, View out, int c, float e, bool shortcut, int H, int W, int seg,
+                                   int k1 = 3, int k2 = 3) {
   const int c_ = (int)(c * e);
   const int tmp = new_buf(m, H, W, c_);
-  const int a = add_conv(m, name + ".cv1", in, View{tmp, 0, c_}, c, c_, 3, 1, true, true, H, W, seg);
-  const int b = add_conv(m, name + ".cv2", View{tmp, 0, c_}, out, c_, c, 3, 1, true, true, H, W, seg, shortcut ? &in : nullptr);
+  const int a = add_conv(m, name + ".cv1", in, View{tmp, 0, c_}, c, c_, k1, 1, true, true, H, W, seg);
+  const int b = add_conv(m, name + ".cv2", View{tmp, 0, c_}, out, c_, c, k2, 1, true, true, H, W, seg, shortcut ? &in : nullptr);
   return {a, b};
 }
 
-// C3k (Block.cs:611-620 over C3 :404-442): cv3(cat(m(cv1(x)), cv2(x))), m = n Bottlenecks(c_, c_, 3x3, e=1.0); registration
-// order cv1, cv2, cv3, m.* ; appends its conv indices (registration order) to `regs`
-void add_c3k(ys_model* m, const std::string& name, View in, View out, int c1, int c2, int n, bool shortcut, int H, int W, int seg,
-             std::vector<int>& regs) {
+// C3 (Block.cs:404-442): cv3(cat(m(cv1(x)), cv2(x))), m = n Bottlenecks(c_, c_, k = (k1, 3), e=1.0), c_ = int(c2 * 0.5); registration
+// order cv1, cv2, cv3, m.* ; appends its conv indices (registration order) to `regs`.  C3 itself has k1 = 1 (:429), C3k (Block.cs:611-620) k1 = 3
+void add_c3_body(ys_model* m, const std::string& name, View in, View out, int c1, int c2, int n, bool shortcut, int k1, int H, int W, int seg,
+                 std::vector<int>& regs) {
   const int c_ = (int)(c2 * 0.5f);
   const int cat = new_buf(m, H, W, 2 * c_);
   int cur = new_buf(m, H, W, c_);
@@ -71,13 +72,21 @@ void add_c3k(ys_model* m, const std::string& name, View in, View out, int c1, in
     View bout;
     if (i == n - 1) bout = View{cat, 0, c_};
     else { cur = new_buf(m, H, W, c_); bout = View{cur, 0, c_}; }
-    auto pr = add_bottleneck(m, name + ".m." + std::to_string(i), bin, bout, c_, 1.0f, shortcut, H, W, seg);
+    auto pr = add_bottleneck(m, name + ".m." + std::to_string(i), bin, bout, c_, 1.0f, shortcut, H, W, seg, k1, 3);
     mids.push_back(pr.first); mids.push_back(pr.second);
   }
   const int i2 = add_conv(m, name + ".cv2", in, View{cat, c_, c_}, c1, c_, 1, 1, true, true, H, W, seg);
   const int i3 = add_conv(m, name + ".cv3", View{cat, 0, 2 * c_}, out, 2 * c_, c2, 1, 1, true, true, H, W, seg);
   regs.push_back(i1); regs.push_back(i2); regs.push_back(i3);
   for (int i : mids) regs.push_back(i);
+}
+void add_c3k(ys_model* m, const std::string& name, View in, View out, int c1, int c2, int n, bool shortcut, int H, int W, int seg,
+             std::vector<int>& regs) {
+  add_c3_body(m, name, in, out, c1, c2, n, shortcut, 3, H, W, seg, regs);
+}
+// C3 as a module of its own (Yolov5u, ys_block_create): registered straight into the model's list
+void add_c3(ys_model* m, const std::string& name, View in, View out, int c1, int c2, int n, bool shortcut, int H, int W, int seg) {
+  add_c3_body(m, name, in, out, c1, c2, n, shortcut, 1, H, W, seg, m->reg);
 }
 
 // C2f (Block.cs:371-399): cv1 1x1 -> chunk -> n Bottlenecks (3x3,3x3, e=1.0) -> cat -> cv2 1x1, and C3k2 (Block.cs:623-662): the same with hidden width
@@ -502,6 +511,59 @@ int build_v11_detect(ys_model* m) {
   return add_detect(m, "model.23", pv, ch, hh, ww, false, SH);
 }
 
+// Yolov5u detect (Yolo.cs:137-198): Conv(3, c, 6, 2, 2) stem, C3 backbone / neck, SPPF, Detect (the v8 head, legacy = true) as model.24.  Widths and depths are
+// :147-158: int(w * width_multiple) with NO max_channels clamp, depths int(d * depth_multiple) in float arithmetic.  Skip router :139 outputIndexs
+// {4, 6, 10, 14, 17, 20, 23} with Yolov8's concatIndex {1, 0, 3, 2}: cat12 = [up(L10) | L6], cat16 = [up(L14) | L4], cat19 = [L18 | L14], cat22 = [L21 | L10]
+int build_v5u_detect(ys_model* m) {
+  static const float dm[5] = {0.34f, 0.34f, 0.67f, 1.0f, 1.34f};
+  static const float wm[5] = {0.25f, 0.5f, 0.75f, 1.0f, 1.25f};
+  const int base_w[5] = {64, 128, 256, 512, 1024};
+  const ys_model_desc& d = m->d;
+  int w[5], dep[3];
+  for (int i = 0; i < 5; i++) w[i] = (int)(base_w[i] * wm[d.size]);
+  dep[0] = (int)(3 * dm[d.size]); dep[1] = (int)(6 * dm[d.size]); dep[2] = (int)(9 * dm[d.size]);
+  for (int i = 0; i < 5; i++)
+    if (w[i] % m->epl || ((int)(w[i] * 0.5f)) % m->epl) { ys_set_error("model: width %d not a multiple of %d", w[i], m->epl); return YS_ERR_UNSUPPORTED; }
+  const int H = d.height, W = d.width;
+  const int H2 = H / 2, W2 = W / 2, H4 = H / 4, W4 = W / 4, H8 = H / 8, W8 = W / 8, H16 = H / 16, W16 = W / 16, H32 = H / 32, W32 = W / 32;
+  new_input_buf(m);
+  const int cat12 = new_buf(m, H16, W16, w[3] + w[3]);   // [up(L10) | L6]
+  const int cat16 = new_buf(m, H8, W8, w[2] + w[2]);     // [up(L14) | L4]
+  const int cat19 = new_buf(m, H16, W16, w[2] + w[2]);   // [L18 | L14]
+  const int cat22 = new_buf(m, H32, W32, w[3] + w[3]);   // [L21 | L10]
+  const int b0 = new_buf(m, H2, W2, w[0]), b1 = new_buf(m, H4, W4, w[1]), b2 = new_buf(m, H4, W4, w[1]);
+  const int b3 = new_buf(m, H8, W8, w[2]), b5 = new_buf(m, H16, W16, w[3]), b7 = new_buf(m, H32, W32, w[4]);
+  const int b8 = new_buf(m, H32, W32, w[4]), b9 = new_buf(m, H32, W32, w[4]), b13 = new_buf(m, H16, W16, w[3]);
+  const int b17 = new_buf(m, H8, W8, w[2]), b20 = new_buf(m, H16, W16, w[3]), b23 = new_buf(m, H32, W32, w[4]);
+  const View v4{cat16, w[2], w[2]}, v6{cat12, w[3], w[3]}, v10{cat22, w[3], w[3]}, v14{cat19, w[2], w[2]};
+  const int SB = 2, SN = 1, SH = 0, SS = 3;   // backward segments: see build_v8_detect
+  int ci = add_conv_reg(m, "model.0", View{m->in_buf, 0, m->epl}, View{b0, 0, w[0]}, 3, w[0], 6, 2, true, true, H, W, SS, nullptr, false, 2);
+  m->convs[ci].first = true;
+  add_conv_reg(m, "model.1", View{b0, 0, w[0]}, View{b1, 0, w[1]}, w[0], w[1], 3, 2, true, true, H2, W2, SS);
+  add_c3(m, "model.2", View{b1, 0, w[1]}, View{b2, 0, w[1]}, w[1], w[1], dep[0], true, H4, W4, SS);
+  add_conv_reg(m, "model.3", View{b2, 0, w[1]}, View{b3, 0, w[2]}, w[1], w[2], 3, 2, true, true, H4, W4, SS);
+  add_c3(m, "model.4", View{b3, 0, w[2]}, v4, w[2], w[2], dep[1], true, H8, W8, SS);
+  add_conv_reg(m, "model.5", v4, View{b5, 0, w[3]}, w[2], w[3], 3, 2, true, true, H8, W8, SB);
+  add_c3(m, "model.6", View{b5, 0, w[3]}, v6, w[3], w[3], dep[2], true, H16, W16, SB);
+  add_conv_reg(m, "model.7", v6, View{b7, 0, w[4]}, w[3], w[4], 3, 2, true, true, H16, W16, SB);
+  add_c3(m, "model.8", View{b7, 0, w[4]}, View{b8, 0, w[4]}, w[4], w[4], dep[0], true, H32, W32, SB);
+  add_sppf(m, "model.9", View{b8, 0, w[4]}, View{b9, 0, w[4]}, w[4], H32, W32, SB);
+  add_conv_reg(m, "model.10", View{b9, 0, w[4]}, v10, w[4], w[3], 1, 1, true, true, H32, W32, SN);
+  { Op op; op.type = OP_UPSAMPLE; op.in = v10; op.out = View{cat12, 0, w[3]}; op.H = H32; op.W = W32; op.seg = SN; m->ops.push_back(op); }
+  add_c3(m, "model.13", View{cat12, 0, 2 * w[3]}, View{b13, 0, w[3]}, w[4], w[3], dep[0], false, H16, W16, SN);
+  add_conv_reg(m, "model.14", View{b13, 0, w[3]}, v14, w[3], w[2], 1, 1, true, true, H16, W16, SN);
+  { Op op; op.type = OP_UPSAMPLE; op.in = v14; op.out = View{cat16, 0, w[2]}; op.H = H16; op.W = W16; op.seg = SN; m->ops.push_back(op); }
+  add_c3(m, "model.17", View{cat16, 0, 2 * w[2]}, View{b17, 0, w[2]}, w[3], w[2], dep[0], false, H8, W8, SN);
+  add_conv_reg(m, "model.18", View{b17, 0, w[2]}, View{cat19, 0, w[2]}, w[2], w[2], 3, 2, true, true, H8, W8, SN);
+  add_c3(m, "model.20", View{cat19, 0, 2 * w[2]}, View{b20, 0, w[3]}, w[3], w[3], dep[0], false, H16, W16, SN);
+  add_conv_reg(m, "model.21", View{b20, 0, w[3]}, View{cat22, 0, w[3]}, w[3], w[3], 3, 2, true, true, H16, W16, SN);
+  add_c3(m, "model.23", View{cat22, 0, 2 * w[3]}, View{b23, 0, w[4]}, w[4], w[4], dep[0], false, H32, W32, SN);
+  const int ch[3] = {w[2], w[3], w[4]};
+  const int hh[3] = {H8, H16, H32}, ww[3] = {W8, W16, W32};
+  const int pv[3] = {b17, b20, b23};
+  return add_detect(m, "model.24", pv, ch, hh, ww, true, SH);
+}
+
 // Standalone block graph (ys_block_create): input buffer -> one module -> output buffer.  Modules are built with the
 // prefix "block" and the tensor names are made module-relative afterwards (layout_block_names).
 int build_block(ys_model* m, const ys_block_desc& bd) {
@@ -540,6 +602,11 @@ int build_block(ys_model* m, const ys_block_desc& bd) {
     case YS_BLOCK_C2F:
       if (bd.n < 1 || bad((int)(c2 * 0.5f), "C2f hidden width")) { if (bd.n < 1) ys_set_error("ys_block_create: n = %d", bd.n); return YS_ERR_UNSUPPORTED; }
       add_c2f(m, nm, vin, vout, c1, c2, bd.n, bd.shortcut != 0, H, W, 0);
+      break;
+    case YS_BLOCK_C3:
+      if (bd.n < 1) { ys_set_error("ys_block_create: n = %d", bd.n); return YS_ERR_UNSUPPORTED; }
+      if (bad((int)(c2 * 0.5f), "C3 hidden width")) return YS_ERR_UNSUPPORTED;
+      add_c3(m, nm, vin, vout, c1, c2, bd.n, bd.shortcut != 0, H, W, 0);
       break;
     case YS_BLOCK_C3K2: {
       const int c = (int)(c2 * e);

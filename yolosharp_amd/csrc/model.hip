@@ -78,7 +78,7 @@ static ConvArgs fwd_args(ys_model* m, const ConvL& c, int B) {
   ConvArgs a{};
   a.x = ib.act; a.w = (char*)m->wf_all + (size_t)c.wf_off * m->es;
   a.B = B; a.Hin = c.Hin; a.Win = c.Win; a.Cin = c.cin_pad; a.Hout = c.Hout; a.Wout = c.Wout; a.Cout = c.cout; a.KH = a.KW = c.k;
-  a.SA = c.s; a.DIVS = 0; a.DIVM = 0; a.PAD = c.k / 2;
+  a.SA = c.s; a.DIVS = 0; a.DIVM = 0; a.PAD = c.pad;
   a.in_ldc = ib.ldc; a.in_coff = c.in.coff; a.in_bstride = ib.rows_per_b;
   a.M = B * c.Hout * c.Wout;
   return a;
@@ -127,11 +127,12 @@ static int run_conv_fwd(ys_model* m, const ConvL& c, int B, const ConvL* next = 
   if (c.first && m->in_f32) {      // model.0 straight from the fp32 image planes (conv_stem.hip)
     const long Ms = (long)B * c.Hout * c.Wout;
     const void* wf = (char*)m->wf_all + (size_t)c.wf_off * m->es;
+    const auto stem_fwd = c.k == 6 ? ys_stem6_fwd_launch : ys_stem_fwd_launch;      // Yolov5u's 6x6 stem (conv_stem6.hip): the same contract
     if (m->training) {
       void* y = y_ptr(m, c);
       int gm = 0;
       const bool atomic = m->bn_atomic && c.acc_off >= 0;
-      YS_TRY(ys_stem_fwd_launch(st, m->in_f32, B, c.Hin, c.Win, wf, c.cout, y, c.cout, 0, (long)c.Hout * c.Wout, stat_partial, nullptr, nullptr, 0, &gm,
+      YS_TRY(stem_fwd(st, m->in_f32, B, c.Hin, c.Win, wf, c.cout, y, c.cout, 0, (long)c.Hout * c.Wout, stat_partial, nullptr, nullptr, 0, &gm,
                                 atomic ? m->stat_acc_all + c.acc_off : nullptr));
       if (atomic) {
         YS_TRY(ys_bn_fin_apply_launch(st, m->dtype, y, Ms, c.cout, bn_acc_fin(m, c, Ms), c.act ? 1 : 0, nullptr, 0, 0, ob.act, ob.ldc, c.out.coff));
@@ -141,8 +142,8 @@ static int run_conv_fwd(ys_model* m, const ConvL& c, int B, const ConvL* next = 
                                       ob.act, ob.ldc, c.out.coff, nullptr));
       }
     } else {
-      YS_TRY(ys_stem_fwd_launch(st, m->in_f32, B, c.Hin, c.Win, wf, c.cout, ob.act, ob.ldc, c.out.coff, ob.rows_per_b, nullptr,
-                                chan_ptr(m, c, 0), chan_ptr(m, c, 1), c.act ? 1 : 0, nullptr));
+      YS_TRY(stem_fwd(st, m->in_f32, B, c.Hin, c.Win, wf, c.cout, ob.act, ob.ldc, c.out.coff, ob.rows_per_b, nullptr,
+                      chan_ptr(m, c, 0), chan_ptr(m, c, 1), c.act ? 1 : 0, nullptr, nullptr));
     }
     return YS_OK;
   }
@@ -201,16 +202,23 @@ static int run_conv_fwd_group(ys_model* m, ConvL* const* cs, int n, int B) {
   }
   if (!ok) { for (int i = 0; i < n; i++) YS_TRY(run_conv_fwd(m, *cs[i], B)); return YS_OK; }
   ConvArgs a[YS_GROUP_MAX];
-  int rows[YS_GROUP_MAX] = {0, 0, 0};
+  int rows[YS_GROUP_MAX] = {0, 0, 0}, cap[YS_GROUP_MAX] = {0, 0, 0};
   const bool bn_train = cs[0]->bn && m->training;
   for (int i = 0; i < n; i++) {
     a[i] = fwd_args(m, *cs[i], B);
     fwd_out_operands(m, *cs[i], a[i]);
     if (bn_train) a[i].stats = m->stat_group + cs[i]->gstat_off;
+    // a unit's statistics region holds 2 * ceil(M / 64) rows (plan.hip allocate).  A map smaller than one pixel tile has one tile per IMAGE -- three images of
+    // a 3 x 5 map are 3 tiles for M = 45 -- so the persistent grid is held to the rows there are: its workgroups walk the tiles between them
+    cap[i] = (int)(2 * ys_cdiv((long)a[i].M, 64));
   }
-  int rc = m->dtype == YS_BF16 ? ys_conv_p2_group_launch(st, a, n, nullptr, rows) : YS_ERR_UNSUPPORTED;
+  int rc = m->dtype == YS_BF16 ? ys_conv_p2_group_launch(st, a, n, bn_train ? cap : nullptr, rows) : YS_ERR_UNSUPPORTED;
   if (rc == YS_ERR_UNSUPPORTED) {
-    for (int i = 0; i < n; i++) { YS_TRY(ys_conv_launch(st, m->dtype, a[i])); rows[i] = ys_conv_grid_m(a[i], m->dtype); }
+    for (int i = 0; i < n; i++) rows[i] = ys_conv_grid_m(a[i], m->dtype);
+    bool fits = true;
+    for (int i = 0; i < n; i++) fits = fits && (!bn_train || rows[i] <= cap[i]);
+    if (!fits) { for (int i = 0; i < n; i++) YS_TRY(run_conv_fwd(m, *cs[i], B)); return YS_OK; }     // (single launches cannot be capped: the shared statistics scratch)
+    for (int i = 0; i < n; i++) YS_TRY(ys_conv_launch(st, m->dtype, a[i]));
   } else if (rc != YS_OK) return rc;
   if (!bn_train) return YS_OK;
   BnFinProb fp[YS_GROUP_MAX];
@@ -380,7 +388,7 @@ ConvArgs dgrad_args(ys_model* m, const ConvL& c, int B, const void* dy, int dy_l
   a.x = dy; a.w = (char*)m->wd_all + (size_t)c.wd_off * m->es;
   a.y = ib.grad;
   a.B = B; a.Hin = c.Hout; a.Win = c.Wout; a.Cin = c.cout_ld; a.Hout = c.Hin; a.Wout = c.Win; a.Cout = c.cin_pad; a.KH = a.KW = c.k;
-  a.SA = 1; a.DIVS = c.s == 2 ? 1 : 0; a.DIVM = c.s - 1; a.PAD = c.k - 1 - c.k / 2;
+  a.SA = 1; a.DIVS = c.s == 2 ? 1 : 0; a.DIVM = c.s - 1; a.PAD = c.k - 1 - c.pad;
   a.in_ldc = dy_ldc; a.in_coff = dy_coff; a.in_bstride = dy_bstride;
   a.out_ldc = ib.ldc; a.out_coff = c.in.coff; a.out_bstride = ib.rows_per_b;
   a.vec_ok = (ib.ldc % 4 == 0 && c.in.coff % 4 == 0) ? 1 : 0;
@@ -403,6 +411,10 @@ static int launch_wgrad(ys_model* m, ConvL& c, int B, const void* dy, int dy_ldc
     // bnb: dy is the gradient of the unit's output and the kernel runs the BatchNorm backward itself (run_conv_bwd: stem_fused)
     const StemBnb sb{y_ptr(m, c), chan_ptr(m, c, 0), chan_ptr(m, c, 1), chan_ptr(m, c, 4), chan_ptr(m, c, 5), c.act ? 1 : 0};
     a.partial = m->wg_partial + c.wgp_off;
+    if (c.k == 6) {          // Yolov5u's 6x6 stem (conv_stem6.hip) has no fused form: stem_bnb_planned answers false for it
+      if (bnb) { ys_set_error("backward: %s was queued without its dy", c.name.c_str()); return YS_ERR_STATE; }
+      YS_TRY(ys_stem6_wgrad_launch(sw, m->in_f32, B, c.Hin, c.Win, dy, dy_ldc, dy_coff, dy_bstride, c.cout, a.partial, c.wgp_splits, &used));
+    } else
     YS_TRY(ys_stem_wgrad_launch(sw, m->in_f32, B, c.Hin, c.Win, dy, dy_ldc, dy_coff, dy_bstride, c.cout, a.partial, c.wgp_splits, &used,
                                 bnb ? &sb : nullptr));
   } else {

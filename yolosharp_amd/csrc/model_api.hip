@@ -51,8 +51,16 @@ extern "C" {
 int ys_model_create(ys_ctx* ctx, const ys_model_desc* desc, ys_model** out) {
   YS_REQUIRE(ctx && desc && out, "ys_model_create: null argument");
   YS_REQUIRE(desc->dtype == YS_F32 || desc->dtype == YS_BF16 || desc->dtype == YS_FP8, "ys_model_create: dtype %d unsupported", desc->dtype);
-  if ((desc->family != YS_YOLOV8 && desc->family != YS_YOLOV11) || desc->task < YS_DETECT || desc->task > YS_CLASSIFY) {
-    ys_set_error("ys_model_create: YOLOv8 / YOLOv11 detect, segment, obb, pose and classify are built (family %d task %d)", desc->family, desc->task);
+  if ((desc->family != YS_YOLOV8 && desc->family != YS_YOLOV11 && desc->family != YS_YOLOV5U) || desc->task < YS_DETECT || desc->task > YS_CLASSIFY) {
+    ys_set_error("ys_model_create: YOLOv8 / YOLOv11 detect, segment, obb, pose and classify and YOLOv5u detect are built (family %d task %d)", desc->family, desc->task);
+    return YS_ERR_UNSUPPORTED;
+  }
+  if (desc->family == YS_YOLOV5U && desc->task != YS_DETECT) {
+    ys_set_error("ys_model_create: YOLOv5u is built for the detect task (with End2End); its segment, obb, pose and classify graphs are not (task %d)", desc->task);
+    return YS_ERR_UNSUPPORTED;
+  }
+  if (desc->family == YS_YOLOV5U && desc->dtype == YS_FP8) {
+    ys_set_error("ys_model_create: YOLOv5u runs in YS_F32 or YS_BF16; YS_FP8 is not built for this family");
     return YS_ERR_UNSUPPORTED;
   }
   if (desc->task == YS_CLASSIFY && desc->dtype == YS_FP8) {
@@ -69,7 +77,7 @@ int ys_model_create(ys_ctx* ctx, const ys_model_desc* desc, ys_model** out) {
   m->d = *desc;
   for (int j = 0; j < 64; j++) m->dfl_w[j] = (float)j;
   const int st = desc->task == YS_CLASSIFY ? (desc->family == YS_YOLOV11 ? build_v11_classify(m) : build_v8_classify(m))
-                                           : (desc->family == YS_YOLOV11 ? build_v11_detect(m) : build_v8_detect(m));
+                                           : (desc->family == YS_YOLOV11 ? build_v11_detect(m) : desc->family == YS_YOLOV5U ? build_v5u_detect(m) : build_v8_detect(m));
   return finish_handle(m, st, nullptr, out);
 }
 

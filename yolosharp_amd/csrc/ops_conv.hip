@@ -302,6 +302,117 @@ extern "C" int ys_conv_f8_dgrad(ys_ctx* ctx, int B, int Cin, int H, int W, const
   return conv_bwd_impl(ctx, YS_FP8, nullptr, B, Cin, H, W, w_oihw, Cout, k, stride, dy_nchw, dx_nchw, nullptr, prev_amax, scales, amax);
 }
 
+// ---- Yolov5u's stem Conv(3, Cout, 6, 2, 2) on the kernels of conv_stem6.hip alone (a model's bf16 model.0): the image stays fp32 NCHW on the device, the
+// weights go through the model's weight prep ([Cout][36][8] bf16), the outputs sit in sentinel-guarded buffers
+static int stem6_stage(hipStream_t st, const float* x_nchw, int B, int H, int W, DevBuf& dx) {
+  YS_TRY(dx.alloc((size_t)B * 3 * H * W * 4));
+  return h2d(st, dx.p, x_nchw, (size_t)B * 3 * H * W * 4);
+}
+
+extern "C" int ys_stem6_fwd(ys_ctx* ctx, const float* x_nchw, int B, int H, int W, const float* w_oihw, int Cout, int stat_mode,
+                            const float* scale, const float* shift, int act, float* y_nchw, double* stats) {
+  YS_REQUIRE(ctx && x_nchw && w_oihw && y_nchw, "ys_stem6_fwd: null argument");
+  YS_REQUIRE(stat_mode == 0 || stat_mode == 1, "ys_stem6_fwd: stat_mode %d", stat_mode);
+  const bool train = scale == nullptr;
+  YS_REQUIRE(train ? stats != nullptr : shift != nullptr, "ys_stem6_fwd: %s", train ? "the training form returns stats" : "eval needs scale and shift");
+  if (!ys_stem6_eligible(YS_BF16, 3, Cout, 6, 2, 2) || B < 1 || H < 2 || W < 2 || (long)B * 3 * H * W >= (1L << 31)) {
+    ys_set_error("ys_stem6_fwd: the 6x6 stem kernels take Cout in {16, 32, 48, 64, 80} and images of at least 2 x 2 (Cout %d, B %d, %d x %d)", Cout, B, H, W);
+    return YS_ERR_UNSUPPORTED;
+  }
+  YS_CHECK_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  const int Ho = (H - 2) / 2 + 1, Wo = (W - 2) / 2 + 1;
+  const long M = (long)B * Ho * Wo;
+  const std::vector<float> wint = weights_to_tap_major(w_oihw, Cout, 3, 36);
+  DevBuf dx, dwm, dwf, dy, dout, dstat, dacc, dpar;
+  YS_TRY(stem6_stage(st, x_nchw, B, H, W, dx));
+  YS_TRY(dwm.alloc(wint.size() * 4));
+  YS_TRY(dwf.alloc((size_t)Cout * 36 * 8 * 2));
+  YS_TRY(h2d(st, dwm.p, wint.data(), wint.size() * 4));
+  YS_TRY(ys_weight_prep_launch(st, YS_BF16, (const float*)dwm.p, Cout, 36, 3, 8, Cout, dwf.p, nullptr, 0));
+  const size_t yb = (size_t)M * Cout * 2;
+  YS_TRY(alloc_filled(dy, yb + kGuardFloats * 4, st));
+  YS_TRY(dout.alloc((size_t)M * Cout * 4));
+  int rows = ys_stem6_fwd_rows(B, Ho, Wo), ok = 1;
+  const size_t accb = (size_t)YS_STAT_SHARDS * Cout * 2 * sizeof(unsigned long long), rowb = (size_t)rows * 2 * Cout * 4;
+  if (train) {
+    YS_TRY(alloc_filled(dstat, rowb + kGuardFloats * 4, st));
+    if (stat_mode == 1) { YS_TRY(dacc.alloc(accb)); YS_CHECK_HIP(hipMemsetAsync(dacc.p, 0, accb, st)); }
+    YS_TRY(ys_stem6_fwd_launch(st, (const float*)dx.p, B, H, W, dwf.p, Cout, dy.p, Cout, 0, (long)Ho * Wo, (float*)dstat.p, nullptr, nullptr, 0, &rows,
+                               stat_mode == 1 ? (unsigned long long*)dacc.p : nullptr));
+    if (stat_mode == 1) {
+      std::vector<long long> h((size_t)YS_STAT_SHARDS * Cout * 2);
+      YS_TRY(d2h(st, h.data(), dacc.p, accb));
+      YS_CHECK_HIP(hipStreamSynchronize(st));
+      for (int c = 0; c < Cout; c++)
+        for (int w = 0; w < 2; w++) {
+          long long s = 0;
+          for (int sh = 0; sh < YS_STAT_SHARDS; sh++) s += h[((size_t)sh * Cout + c) * 2 + w];
+          stats[(size_t)w * Cout + c] = (double)s / (double)YS_STAT_FIX;
+        }
+    } else {
+      std::vector<float> h((size_t)rows * 2 * Cout);
+      YS_TRY(d2h(st, h.data(), dstat.p, rowb));
+      YS_CHECK_HIP(hipStreamSynchronize(st));
+      for (int i = 0; i < 2 * Cout; i++) stats[i] = 0.0;
+      for (int r = 0; r < rows; r++) for (int i = 0; i < 2 * Cout; i++) stats[i] += (double)h[(size_t)r * 2 * Cout + i];
+    }
+    YS_TRY(check_guard(st, dstat.p, rowb, &ok));
+  } else {
+    YS_TRY(dpar.alloc((size_t)Cout * 2 * 4));
+    YS_TRY(h2d(st, dpar.p, scale, (size_t)Cout * 4));
+    YS_TRY(h2d(st, (float*)dpar.p + Cout, shift, (size_t)Cout * 4));
+    YS_TRY(ys_stem6_fwd_launch(st, (const float*)dx.p, B, H, W, dwf.p, Cout, dy.p, Cout, 0, (long)Ho * Wo, nullptr, (const float*)dpar.p, (const float*)dpar.p + Cout,
+                               act ? 1 : 0, nullptr, nullptr));
+  }
+  YS_TRY(ys_unpack_nchw_launch(st, YS_BF16, dy.p, Cout, 0, B, Cout, (long)Ho * Wo, (float*)dout.p));
+  YS_TRY(d2h(st, y_nchw, dout.p, (size_t)M * Cout * 4));
+  YS_TRY(check_guard(st, dy.p, yb, &ok));
+  YS_CHECK_HIP(hipStreamSynchronize(st));
+  YS_CHECK_HIP(hipGetLastError());
+  YS_REQUIRE(ok, "ys_stem6_fwd: the kernel wrote behind its arrays");
+  return YS_OK;
+}
+
+extern "C" int ys_stem6_wgrad(ys_ctx* ctx, const float* x_nchw, int B, int H, int W, const float* dy_nchw, int Cout, float* dw_oihw) {
+  YS_REQUIRE(ctx && x_nchw && dy_nchw && dw_oihw, "ys_stem6_wgrad: null argument");
+  if (!ys_stem6_eligible(YS_BF16, 3, Cout, 6, 2, 2) || B < 1 || H < 2 || W < 2 || (long)B * 3 * H * W >= (1L << 31)) {
+    ys_set_error("ys_stem6_wgrad: the 6x6 stem kernels take Cout in {16, 32, 48, 64, 80} and images of at least 2 x 2 (Cout %d, B %d, %d x %d)", Cout, B, H, W);
+    return YS_ERR_UNSUPPORTED;
+  }
+  YS_CHECK_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  const int Ho = (H - 2) / 2 + 1, Wo = (W - 2) / 2 + 1;
+  const long M = (long)B * Ho * Wo, n = (long)Cout * 36 * 8;
+  DevBuf dx, ddy, ddyn, dpart, dgw, ddesc;
+  YS_TRY(stem6_stage(st, x_nchw, B, H, W, dx));
+  YS_TRY(ddy.alloc((size_t)M * Cout * 4));
+  YS_TRY(ddyn.alloc((size_t)M * Cout * 2));
+  YS_TRY(h2d(st, ddy.p, dy_nchw, (size_t)M * Cout * 4));
+  YS_TRY(ys_pack_input_launch(st, YS_BF16, (const float*)ddy.p, B, Cout, Ho, Wo, Cout, ddyn.p));
+  const int splits = ys_stem6_wgrad_splits(B, H, W);
+  const size_t pb = (size_t)splits * n * 4;
+  YS_TRY(alloc_filled(dpart, pb + kGuardFloats * 4, st));
+  YS_TRY(dgw.alloc((size_t)Cout * 36 * 3 * 4));
+  YS_CHECK_HIP(hipMemsetAsync(dgw.p, 0, (size_t)Cout * 36 * 3 * 4, st));
+  int used = 0, ok = 1;
+  YS_TRY(ys_stem6_wgrad_launch(st, (const float*)dx.p, B, H, W, ddyn.p, Cout, 0, (long)Ho * Wo, Cout, (float*)dpart.p, splits, &used));
+  // the split reduction of a backward segment (model.hip reduce_range), with this layer as its only descriptor
+  WgRedDesc d{};
+  d.partial = (const float*)dpart.p; d.grad = (float*)dgw.p; d.n = n; d.blk0 = 0; d.splits = used; d.cin_pad = 8; d.cin_real = 3;
+  YS_TRY(ddesc.alloc(sizeof d));
+  YS_TRY(h2d(st, ddesc.p, &d, sizeof d));
+  YS_TRY(ys_wgrad_reduce_batched_launch(st, (const WgRedDesc*)ddesc.p, 1, (n + YS_WGRED_OUT_PER_BLOCK - 1) / YS_WGRED_OUT_PER_BLOCK));
+  std::vector<float> gw((size_t)Cout * 36 * 3);
+  YS_TRY(d2h(st, gw.data(), dgw.p, gw.size() * 4));
+  YS_TRY(check_guard(st, dpart.p, pb, &ok));
+  YS_CHECK_HIP(hipStreamSynchronize(st));
+  YS_CHECK_HIP(hipGetLastError());
+  YS_REQUIRE(ok, "ys_stem6_wgrad: the kernel wrote behind its arrays");
+  weights_to_oihw(gw, Cout, 3, 36, dw_oihw);
+  return YS_OK;
+}
+
 // ---- scaling machinery of the fp8 path (f8.hip), one call per kernel
 extern "C" int ys_f8_quant(ys_ctx* ctx, int kind, const float* x, int rows, int C, int coff, int pad, float qscale, uint8_t* q8, float* amax, float* slots,
                            int32_t* view_intact) {

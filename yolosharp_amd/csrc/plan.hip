@@ -346,12 +346,12 @@ static int alloc_f8(ys_model* m, const std::vector<PrepDesc>& pd) {
   return YS_OK;
 }
 
-// model.0 of a whole-model handle on the bf16 path, when the stem kernels take its shape (conv_stem.hip): what both stem routes ask for
+// model.0 of a whole-model handle on the bf16 path, when the stem kernels take its shape (conv_stem.hip: 3x3; conv_stem6.hip: Yolov5u's 6x6): what both stem routes ask for
 static const ConvL* stem_unit(const ys_model* m) {
   if (!m->stem_on || m->is_block || m->is_head || m->dtype != YS_BF16 || m->convs.empty()) return nullptr;
   const ConvL& c = m->convs[0];
   if (!c.first || !c.bn || c.dw || c.ct || c.has_res || c.in.buf != m->in_buf) return nullptr;
-  return ys_stem_eligible(m->dtype, c.cin, c.cout, c.k, c.s) ? &c : nullptr;
+  return (ys_stem_eligible(m->dtype, c.cin, c.cout, c.k, c.s) && c.pad == 1) || ys_stem6_eligible(m->dtype, c.cin, c.cout, c.k, c.s, c.pad) ? &c : nullptr;
 }
 // ... with its own weight-gradient partial region (deferred split reduction)
 bool stem_direct(const ys_model* m) {
@@ -364,7 +364,7 @@ bool stem_direct(const ys_model* m) {
 // creation (no dy buffer is allocated for the unit then); a step whose forward did not read the fp32 image (ys_model_forward_u8) takes the separate pass.
 bool stem_bnb_planned(const ys_model* m) {
   const ConvL* c = m->stem_bnb_fuse ? stem_unit(m) : nullptr;
-  if (!c || c->pool_next || c->cout_ld != c->cout || c->cout != 16) return false;   // 16 channels: the width the fused kernel is built and measured for (conv_stem.hip)
+  if (!c || c->k != 3 || c->pool_next || c->cout_ld != c->cout || c->cout != 16) return false;   // 16 channels: the width the fused kernel is built and measured for (conv_stem.hip)
   const Buf& ob = m->bufs[c->out.buf];
   return (ob.ldc & 7) == 0 && (c->out.coff & 7) == 0 && ob.rows_per_b == (long)c->Hout * c->Wout;
 }
@@ -534,7 +534,8 @@ int allocate(ys_model* m) {
     if (c.dw) continue;
     const Buf& ob = m->bufs[c.out.buf];     // the view geometry the launch will see (the blocked-GEMM plan depends on it): a BN unit's dy is dense, a plain one's the output view
     const WgradArgs a = c.bn ? wgrad_args(m, c, B, c.cout, 0, (long)c.Hout * c.Wout) : wgrad_args(m, c, B, ob.ldc, c.out.coff, ob.rows_per_b, c.ct ? 0 : -1);
-    const int sp = ys_wgrad_splits(a, m->dtype);
+    int sp = ys_wgrad_splits(a, m->dtype);
+    if (c.k == 6 && &c == stem_unit(m)) sp = std::max(sp, ys_stem6_wgrad_splits(B, c.Hin, c.Win));   // the 6x6 stem kernel leaves one slab per workgroup (the generic route keeps its own count)
     need[c.idx] = (long)sp * c.cout * c.k * c.k * c.cin_pad;
     wgp = std::max(wgp, need[c.idx]);
     if (m->defer_wgred && !c.ct) { c.wgp_splits = sp; wgp_regions += (need[c.idx] + 63) / 64 * 64; }
@@ -598,7 +599,7 @@ WgradArgs wgrad_args(const ys_model* m, const ConvL& c, int B, int dy_ldc, int d
   const Buf& ib = m->bufs[c.in.buf];
   WgradArgs a{};
   a.B = B; a.Hin = c.Hin; a.Win = c.Win; a.Cin = c.cin_pad; a.Hout = c.Hout; a.Wout = c.Wout; a.Cout = c.cout;
-  a.KH = a.KW = c.k; a.stride = c.s; a.pad = c.k / 2;               // (a ConvTranspose unit is recorded with k = 1, s = 1: its phases are 1x1 GEMMs)
+  a.KH = a.KW = c.k; a.stride = c.s; a.pad = c.pad;               // (a ConvTranspose unit is recorded with k = 1, s = 1: its phases are 1x1 GEMMs)
   a.in_ldc = ib.ldc; a.in_coff = c.in.coff; a.in_bstride = ib.rows_per_b;
   a.dy_ldc = dy_ldc; a.dy_coff = dy_coff; a.dy_bstride = dy_bstride;
   if (phase >= 0) { a.Hout = c.Hin; a.Wout = c.Win; a.dy_rh = 4 * c.Win; a.dy_rw = 2; a.dy_r0 = (long)(phase >> 1) * 2 * c.Win + (phase & 1); }

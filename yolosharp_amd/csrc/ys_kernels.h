@@ -117,6 +117,15 @@ int ys_stem_fwd_launch(hipStream_t st, const float* x, int B, int H, int W, cons
 struct StemBnb { const void* y; const float *scale, *shift, *k2, *k3; int act; };
 int ys_stem_wgrad_launch(hipStream_t st, const float* x, int B, int H, int W, const void* dy, int dy_ldc, int dy_coff, long dy_bstride,
                          int Cout, float* partial, int max_splits, int* used, const StemBnb* bnb = nullptr);
+// The same pair for Yolov5u's model.0 = Conv(3, c, k = 6, s = 2, p = 2) (conv_stem6.hip): partial slabs [Cout][36][8].  No fused BatchNorm backward: the separate
+// apply pass runs.  ys_stem6_wgrad_splits: the slabs the weight gradient wants (the plan sizes the layer's partial region for them)
+bool ys_stem6_eligible(int dtype, int cin, int cout, int k, int s, int pad);
+int ys_stem6_fwd_rows(int B, int Hout, int Wout);
+int ys_stem6_fwd_launch(hipStream_t st, const float* x, int B, int H, int W, const void* wf, int Cout, void* y, int out_ldc, int out_coff,
+                        long out_bstride, float* stats, const float* scale, const float* shift, int act, int* rows, unsigned long long* stat_acc = nullptr);
+int ys_stem6_wgrad_splits(int B, int H, int W);
+int ys_stem6_wgrad_launch(hipStream_t st, const float* x, int B, int H, int W, const void* dy, int dy_ldc, int dy_coff, long dy_bstride,
+                          int Cout, float* partial, int max_splits, int* used);
 int ys_conv_grid_m(const ConvArgs& a, int dtype);
 int ys_conv_is_p2(const ConvArgs& a);
 // partial rows a launch of `a` (a dgrad with a.nred segments) writes per segment when every kernel it dispatches to supports the fused

@@ -18,6 +18,7 @@ struct Buf {
 struct ConvL {
   std::string name;      // state_dict prefix
   int cin = 0, cout = 0, k = 1, s = 1;
+  int pad = 0;           // zero padding on every side: k / 2 (autopad) unless the module names it (Yolov5u model.0: k 6, p 2)
   int cin_pad = 0;       // channels of the input view (first layer: 3 -> EPL)
   int cout_ld = 0;       // channels incl. padding in the dgrad weight matrix / dy rows
   int cout_real = 0;     // output channels of the reference module.  cout > cout_real only for the Pose towers (51 -> next 16-byte
@@ -219,6 +220,7 @@ int add_classify(ys_model* m, const std::string& hp, View in, int c1, int H, int
 int build_v8_detect(ys_model* m);
 int build_v8_classify(ys_model* m);
 int build_v11_detect(ys_model* m);
+int build_v5u_detect(ys_model* m);
 int build_v11_classify(ys_model* m);
 int build_block(ys_model* m, const ys_block_desc& bd);
 

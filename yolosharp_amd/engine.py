@@ -566,6 +566,32 @@ class Engine:
                                                        C.byref(amax)))
         return dict(dx=dx, scales=scales, amax=np.float32(amax.value))
 
+    def stem6_fwd(self, x, weight, scale=None, shift=None, act=True, stat_mode=0):
+        """Yolov5u's stem Conv(3, Cout, 6, 2, 2) on the 6x6 stem forward kernel alone (ys_stem6_fwd).  scale None: the training form -> (y as the stored bf16
+        values, stats [2, Cout] float64 = the kernel's per-channel sum and sum of squares); else eval -> (act(scale * conv + shift), None)."""
+        x = np.ascontiguousarray(x, np.float32)
+        w = np.ascontiguousarray(weight, np.float32)
+        B, _, H, W = x.shape
+        Cout = w.shape[0]
+        y = np.full((B, Cout, (H - 2) // 2 + 1, (W - 2) // 2 + 1), np.nan, np.float32)
+        train = scale is None
+        stats = np.full((2, Cout), np.nan, np.float64) if train else None
+        sc = None if train else np.ascontiguousarray(scale, np.float32)
+        sh = None if train else np.ascontiguousarray(shift, np.float32)
+        _lib.check(self.lib, self.lib.ys_stem6_fwd(self.ctx, _ptr(x), B, H, W, _ptr(w), Cout, int(stat_mode), _ptr(sc), _ptr(sh), int(bool(act)), _ptr(y),
+                                                   _ptr(stats)))
+        return y, stats
+
+    def stem6_wgrad(self, x, dy):
+        """The weight gradient [Cout, 3, 6, 6] of the same convolution on the 6x6 stem weight-gradient kernel + the split reduction (ys_stem6_wgrad)."""
+        x = np.ascontiguousarray(x, np.float32)
+        dy = np.ascontiguousarray(dy, np.float32)
+        B, _, H, W = x.shape
+        Cout = dy.shape[1]
+        dw = np.full((Cout, 3, 6, 6), np.nan, np.float32)
+        _lib.check(self.lib, self.lib.ys_stem6_wgrad(self.ctx, _ptr(x), B, H, W, _ptr(dy), Cout, _ptr(dw)))
+        return dw
+
     def conv_labels(self, fn):
         """fn() with the per-launch profile on -> (its result, the labels of the convolution launches it made, in order per class)."""
         import os

@@ -196,6 +196,8 @@ class Yolov8:
             C_ = 4 * self.reg_max if key.endswith("boxes") else (self.NM if key.endswith(("mask_coefficient", "angle", "kpts")) else self.nc)
         if key in ("proto", "dproto"):
             a = np.empty((B, self.NM, self.height // 4, self.width // 4), np.float32)
+        elif key in ("model0_raw", "model0_dy"):
+            a = np.empty((B, self.tensor_info()[0][1][0], self.height // 2, self.width // 2), np.float32)
         elif key == "det":
             a = np.empty((B, min(self.max_det, self.A), 6 + (self.NM if self.TASK in (1, 2, 3) else 0)), np.float32)
         else:
@@ -286,6 +288,12 @@ class Yolov8:
 class Yolov11(Yolov8):
     """Models/Yolo.cs:200-258: C3k2 / C2PSA graph with Detect(legacy=false)."""
     FAMILY = 11
+
+
+class Yolov5u(Yolov8):
+    """Models/Yolo.cs:137-198: Conv(3, c, 6, 2, 2) stem, C3 backbone / neck, SPPF, the Yolov8 Detect head as model.24.  The detect task only (with
+    `end2end=`); the engine refuses the family's other tasks and the fp8 dtype."""
+    FAMILY = 5
 
 
 class _SegmentMixin:

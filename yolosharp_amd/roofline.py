@@ -24,6 +24,7 @@ KERNELS = {   # label prefix -> (kernel symbol, operand type of its MFMAs)
     "halo": ("conv_halo_kernel", "bf16"),          # round 5: halo-patch form of the 3x3 stride-1 wide layers (csrc/conv_halo.h)
     "direct": ("conv_igemm_kernel", "bf16"), "patch": ("conv3x3_tile_kernel", "bf16"),
     "stem": ("stem_fwd_kernel", "bf16"), "wstem": ("stem_wgrad_kernel", "bf16"),   # model.0 straight from the fp32 NCHW image (conv_stem.hip)
+    "stem6": ("stem6_fwd_kernel", "bf16"), "wstem6": ("stem6_wgrad_kernel", "bf16"),   # Yolov5u's 6x6 model.0, the same way (conv_stem6.hip)
     "wgrad_tr": ("conv_wgrad_tr_kernel", "bf16"), "wgemm": ("conv_wgrad_gemm_kernel", "bf16"), "wgrad": ("conv_wgrad_kernel", "bf16"),
 }
 _LAB = re.compile(r"^(\w+) k(\d+) s(\d+) (?:div(\d+) )?cin(\d+) cout(\d+) M(\d+)")
@@ -40,7 +41,7 @@ def launch_work(label, elem_bytes=2):
     in_px = M * s * s / (div * div)
     cin_alg = 3 if (cin == 8 and kh == 3 and s == 2) else cin   # the stem's 3 input channels are padded to 8 in memory
     flop = 2.0 * M * cout * cin_alg * kh * kw / (div * div)
-    if kind in ("stem", "wstem"):                               # the image is fp32 in HBM (the boundary's own tensor), the output / dy bf16
+    if kind in ("stem", "wstem", "stem6", "wstem6"):                              # the image is fp32 in HBM (the boundary's own tensor), the output / dy bf16
         byt = in_px * cin_alg * 4 + M * cout * elem_bytes
     elif kind.startswith("w"):                                  # weight gradient: reads x (in_px * cin) and dy (M * cout)
         byt = (in_px * cin_alg + M * cout) * elem_bytes
