@@ -62,6 +62,7 @@ namespace YoloSharp.Native
         [DllImport(Lib)] internal static extern int ys_loss_read(IntPtr model, [Out] float[] items3, out float lossSum);
         // criterion on caller-supplied preds (Loss.cs:411 forward(preds, batch)); device-label callers reserve the per-image label capacity
         [DllImport(Lib)] internal static extern int ys_model_set_preds(IntPtr model, int batch, float[] boxes, float[] scores, float[] maskCoefficient, float[] proto);
+        [DllImport(Lib)] internal static extern int ys_model_decode_preds(IntPtr model);
         [DllImport(Lib)] internal static extern int ys_model_reserve_labels(IntPtr model, int perImage);
         // End2End (Config.End2End = true, the reference's default): YoloBaseTaskModel.One2one_Init; outputs "one2one_boxes" / "one2one_scores" / "one2one_dboxes" /
         // "one2one_dscores" / "det" through ys_model_get_output; ys_loss_detect is then E2EDetectLoss; rows [B,k,6] of the eval forward stay on the device

@@ -130,6 +130,11 @@ YS_API int ys_model_get_output(ys_model* m, const char* key, float* host, size_t
  * is refused (there is no graph state behind such preds). */
 YS_API int ys_model_set_preds(ys_model* m, int batch, const float* boxes, const float* scores,
                               const float* mask_coefficient, const float* proto);
+/* The tail of an eval forward alone: Detect._inference (and the Segment / Obb / Pose forms; End2End: the top-k post-process too) on the head
+ * buffers as they stand, for the batch of the last ys_model_set_preds / forward -> "pred" (and "det").  After ys_model_set_preds: the decode of the
+ * caller's values; after an eval forward: the same "pred" again, bit for bit.  Needs eval mode, a Detect / Segment / OBB / Pose model (or head
+ * handle) and a prior ys_model_set_preds or forward: YS_ERR_INVALID_ARG otherwise.  Asynchronous. */
+YS_API int ys_model_decode_preds(ys_model* m);
 /* Device pointer of the eval prediction [B,4+nc,A] fp32 (input of ys_nms_batched); classify models: the eval probabilities [B,nc]. */
 YS_API int ys_model_pred_device(ys_model* m, float** dptr);
 

@@ -16,7 +16,7 @@ import pytest
 import torch
 
 from oracle import yolo_oracle as O
-from test_model import make_ref, relerr
+from test_model import assert_pred_blocks, make_ref, relerr
 from test_nms import oracle_nms
 
 pytestmark = pytest.mark.gpu
@@ -58,6 +58,7 @@ def test_c1_bus_predict(eng, oracle_lib, canvas):
     with torch.no_grad():
         rinf, _ = ref(torch.from_numpy(x))
     assert relerr(inf["boxes"], rinf["boxes"]) < 1e-3
+    assert_pred_blocks(inf["boxes"], rinf["boxes"], nc, 1e-3, tag="c1 f32 %dx%d" % canvas)
     # NMS at the demo's thresholds (Program.cs:36-37) and at validation's: bit-exact vs the C oracle on the same tensor
     for conf, iou in ((0.3, 0.5), (0.001, 0.7)):
         ref_p, ref_rows, ref_keep = oracle_nms(oracle_lib, inf["boxes"], conf, iou)
@@ -71,6 +72,7 @@ def test_c1_bus_predict(eng, oracle_lib, canvas):
     mb.eval()
     infb, _ = mb.forward_u8(img[None])
     assert relerr(infb["boxes"], rinf["boxes"]) < 2e-2
+    assert_pred_blocks(infb["boxes"], rinf["boxes"], nc, 2e-2, tag="c1 bf16 %dx%d" % canvas)
     if W == 480:
         res = Detector(m).ImagePredict(img.astype(np.float32), 0.001, 0.7)
         assert len(res) == len(keepi[0])

@@ -12,7 +12,7 @@ import torch
 import e2e_ref as R
 from conftest import BACKENDS
 from oracle import yolo_oracle as O
-from test_model import make_ref, make_ref11, relerr
+from test_model import assert_pred_blocks, make_ref, make_ref11, relerr
 
 B, H, W, NC = 2, 64, 64, 7          # A = 84; nc = 7 is not a multiple of the 16-byte channel unit
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -256,6 +256,7 @@ def test_eval_forward(backend, engine, family):
     inf, preds = m.forward(c["x"])
     assert inf["pred"].shape == (B, 4 + NC, m.A) and inf["boxes"].shape == (B, min(300, m.A), 6)
     assert relerr(inf["pred"], c["pred"]) < 1e-3                                        # xyxy * stride | sigmoid
+    assert_pred_blocks(inf["pred"], c["pred"], NC, 1e-3, tag="e2e v%d" % family)        # ... and boxes and probabilities each on their own
     assert np.all(inf["pred"][:, 2] > inf["pred"][:, 0]) and np.all(inf["pred"][:, 3] > inf["pred"][:, 1])
     # "det" = the restatement applied to the ENGINE's own pred, exactly (a 1e-3 forward difference may reorder near-equal scores)
     rrows, _ = R.postprocess(torch.from_numpy(inf["pred"]))

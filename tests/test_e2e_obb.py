@@ -13,7 +13,7 @@ import e2e_obb_ref as R
 import e2e_seg_ref as S
 from conftest import BACKENDS
 from oracle import yolo_oracle as O
-from test_model import relerr
+from test_model import assert_pred_blocks, relerr
 from test_obb_pose import make_ref
 
 B, H, W, NC = 2, 64, 64, 15               # A = 84
@@ -292,6 +292,7 @@ def test_eval_forward(backend, engine, family):
         assert inf["pred"].shape == (B, 4 + NC + 1, m.A) and inf["boxes"].shape == (B, k, 7)
         assert np.array_equal(inf["pred"].view(np.uint32), pinf["boxes"].view(np.uint32))       # Obb.decode_bboxes ignores end2end: xywh, bit for bit
         assert relerr(inf["pred"], c["pred"]) < 1e-3
+        assert_pred_blocks(inf["pred"], c["pred"], NC, 1e-3, tag="e2e obb v%d" % family)            # boxes, probabilities and the angle each on their own
         rrows, _ = S.postprocess(torch.from_numpy(inf["pred"]), NC, max_det)
         assert np.array_equal(inf["boxes"].view(np.uint32), rrows.numpy().view(np.uint32))
         rows, _ = engine.e2e_topk(inf["pred"], max_det, extra=1)

@@ -15,7 +15,7 @@ import e2e_pose_ref as R
 import e2e_seg_ref as S
 from conftest import BACKENDS
 from oracle import yolo_oracle as O
-from test_model import relerr
+from test_model import assert_pred_blocks, relerr
 from test_obb_pose import make_ref
 
 B, H, W = 2, 64, 64                        # A = 84
@@ -362,6 +362,7 @@ def test_eval_forward(backend, engine, cfg):
         assert inf["pred"].shape == (B, 4 + nc + nk, m.A) and inf["boxes"].shape == (B, k, 6 + nk)
         assert relerr(inf["pred"][:, :4], c["pred"][:, :4]) < 1e-3 and relerr(inf["pred"][:, 4:4 + nc], c["pred"][:, 4:4 + nc]) < 1e-3
         assert relerr(inf["pred"][:, 4 + nc:], c["pred"][:, 4 + nc:]) < 1e-3
+        assert_pred_blocks(inf["pred"], c["pred"], nc, 1e-3, kdim=c["D"], tag="e2e pose %s" % (cfg,))     # keypoint xy (pixels) and the visibility sigmoid apart
         # xyxy boxes: the plain model's xywh converted; classes and decoded keypoints are the plain model's, bit for bit
         xywh = pinf["boxes"][:, :4]
         assert np.allclose(inf["pred"][:, :2], xywh[:, :2] - xywh[:, 2:4] / 2, rtol=1e-4, atol=1e-3)
@@ -380,6 +381,7 @@ def test_eval_forward(backend, engine, cfg):
     with torch.no_grad():
         rplain, _ = make_ref(getattr(O, f"Yolov{c['family']}Pose"), nc, "n", seed=c["wseed"], kpt_num=c["K"], kpt_dim=c["D"]).eval()(torch.from_numpy(c["x"]))
     assert relerr(pinf["boxes"], rplain["boxes"].numpy()) < 1e-3
+    assert_pred_blocks(pinf["boxes"], rplain["boxes"], nc, 1e-3, kdim=c["D"], tag="plain pose %s" % (cfg,))
     p.close()
 
 

@@ -12,7 +12,7 @@ import torch
 import e2e_seg_ref as R
 from conftest import BACKENDS
 from oracle import yolo_oracle as O
-from test_model import relerr
+from test_model import assert_pred_blocks, relerr
 from test_segment import make_ref
 
 B, H, W, NC, NM = 2, 64, 64, 80, 32      # the tests/test_segment.py case: A = 84
@@ -411,6 +411,7 @@ def test_eval_forward(backend, engine, family):
     assert set(inf) == {"boxes", "pred", "proto"} and set(preds) == {"one2many", "one2one"}
     assert inf["pred"].shape == (B, 4 + NC + NM, m.A) and inf["boxes"].shape == (B, k, 6 + NM)
     assert relerr(inf["pred"][:, :4 + NC], c["pred"][:, :4 + NC]) < 1e-3 and relerr(inf["pred"][:, 4 + NC:], c["pred"][:, 4 + NC:]) < 1e-3
+    assert_pred_blocks(inf["pred"], c["pred"], NC, 1e-3, tag="e2e seg v%d" % family)        # boxes and probabilities apart too
     assert np.all(inf["pred"][:, 2] > inf["pred"][:, 0]) and np.all(inf["pred"][:, 3] > inf["pred"][:, 1])      # xyxy
     rows, _ = engine.e2e_topk(inf["pred"], 300, extra=NM)                      # "det" IS ys_e2e_topk_ex of the engine's own pred ...
     assert np.array_equal(inf["boxes"].view(np.uint32), rows.view(np.uint32))

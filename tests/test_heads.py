@@ -66,6 +66,8 @@ def test_detect_head_module(backend, engine, legacy):
     inf, _ = m([x.detach().numpy() for x in xs])
     r = rinf["boxes"].numpy()
     assert np.abs(inf["boxes"] - r).max() <= 1e-3 * np.abs(r).max()
+    for lo, hi in ((0, 4), (4, 4 + nc)):                         # boxes (pixels) and class probabilities apart: each against its own largest magnitude
+        assert np.abs(inf["boxes"][:, lo:hi] - r[:, lo:hi]).max() <= 1e-3 * np.abs(r[:, lo:hi]).max(), (lo, hi)
     m.close()
 
 

@@ -38,6 +38,29 @@ def relerr(a, b):
     return float((np.abs(a - b) / (np.abs(b) + rms)).max())
 
 
+def pred_block_errs(a, b, nc, kdim=0, tag=""):
+    """relerr per block of an eval prediction [B, 4 + nc (+ extra), A]: "boxes" (pixels, in the hundreds), "probs" (class probabilities, below 1) and the extra
+    channels ("extra"; a Pose head with kdim 3: "kxy" in pixels and "kvis", a sigmoid, apart).  One relerr over the whole tensor takes its rms from the pixel
+    coordinates, and a class probability wrong by 0.1 passes it at 1e-3; per block it does not."""
+    b = b.detach().numpy() if hasattr(b, "detach") else np.asarray(b)
+    a = np.asarray(a)
+    out = {"boxes": relerr(a[:, :4], b[:, :4]), "probs": relerr(a[:, 4:4 + nc], b[:, 4:4 + nc])}
+    xa, xb = a[:, 4 + nc:], b[:, 4 + nc:]
+    if xa.shape[1] and kdim == 3:
+        vis = np.arange(xa.shape[1]) % 3 == 2
+        out["kxy"], out["kvis"] = relerr(xa[:, ~vis], xb[:, ~vis]), relerr(xa[:, vis], xb[:, vis])
+    elif xa.shape[1]:
+        out["extra"] = relerr(xa, xb)
+    print("MEASURE pred blocks %s %s" % (tag, {k: "%.3g" % v for k, v in out.items()}))
+    return out
+
+
+def assert_pred_blocks(a, b, nc, tol, kdim=0, tag=""):
+    errs = pred_block_errs(a, b, nc, kdim, tag)
+    for k, v in errs.items():
+        assert v < tol, (tag, k, v, tol)
+
+
 @pytest.mark.parametrize("backend", BACKENDS)
 def test_state_dict_surface(backend, engine):
     """Names, shapes and parameter order equal TorchSharp/PyTorch registration order (Yolo.cs:10-39, 'model.{i}...')."""
@@ -74,6 +97,7 @@ def test_forward_loss_backward_adamw_f32(backend, engine):
         rinf, rpreds = ref(x)
     assert relerr(preds["boxes"], rpreds["boxes"]) < 1e-3 and relerr(preds["scores"], rpreds["scores"]) < 1e-3
     assert relerr(inf["boxes"], rinf["boxes"]) < 1e-3
+    assert_pred_blocks(inf["boxes"], rinf["boxes"], nc, 1e-3, tag="v8n f32")
     assert np.abs(inf["boxes"] - g["pred_eval"].astype(np.float32)).max() < 2e-3 * np.abs(g["pred_eval"]).max()   # fp16-stored fixture
     # ---- train forward (batch statistics), loss, backward
     m.train(); ref.train()
@@ -245,6 +269,7 @@ def test_bf16_path_tracks_f32(backend, engine):
         rinf, rpreds = ref(x)
     assert relerr(preds["boxes"], rpreds["boxes"]) < 3e-2 and relerr(preds["scores"], rpreds["scores"]) < 3e-2
     assert relerr(inf["boxes"], rinf["boxes"]) < 1e-2
+    assert_pred_blocks(inf["boxes"], rinf["boxes"], nc, 1e-2, tag="v8n bf16")
     m.close()
 
 
@@ -400,6 +425,7 @@ def _v11_parity(engine, size, B, H, W, tol_fwd, tol_grad):
         rinf, rpreds = ref(x)
     assert relerr(preds["boxes"], rpreds["boxes"]) < tol_fwd and relerr(preds["scores"], rpreds["scores"]) < tol_fwd
     assert relerr(inf["boxes"], rinf["boxes"]) < tol_fwd
+    assert_pred_blocks(inf["boxes"], rinf["boxes"], nc, tol_fwd, tag="v11%s f32" % size)
     m.train(); ref.train()
     _, preds = m.forward(x.numpy())
     _, rpreds = ref(x)

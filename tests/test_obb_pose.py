@@ -7,7 +7,7 @@ import torch
 
 from conftest import BACKENDS
 from oracle import yolo_oracle as O
-from test_model import relerr
+from test_model import assert_pred_blocks, relerr
 
 
 def make_ref(cls, nc, size, seed=0, **kw):
@@ -53,6 +53,7 @@ def _head_parity(engine, task, family, size, B, H, W, tol, nc=5, **kw):
     assert relerr(inf["boxes"][:, :4], r[:, :4]) < tol
     assert relerr(inf["boxes"][:, 4:4 + nc], r[:, 4:4 + nc]) < tol
     assert relerr(inf["boxes"][:, 4 + nc:], r[:, 4 + nc:]) < tol
+    assert_pred_blocks(inf["boxes"], r, nc, tol, kdim=kw.get("kpt_dim", 3) if task == "Pose" else 0, tag="%s%s%s" % (family, task, size))   # Pose: keypoint xy (pixels) and the visibility sigmoid apart
     if task == "Obb":                                              # angle range of Head.cs:429
         a = inf["boxes"][:, 4 + nc]
         assert a.min() >= -np.pi / 4 - 1e-6 and a.max() <= 3 * np.pi / 4 + 1e-6

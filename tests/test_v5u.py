@@ -16,7 +16,7 @@ import e2e_ref as R
 import v5u_ref as V
 from conftest import BACKENDS
 from oracle import yolo_oracle as O
-from test_model import relerr
+from test_model import assert_pred_blocks, relerr
 from test_stem6_kernels import bf16r
 
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
@@ -156,6 +156,7 @@ def test_forward_loss_backward_adamw_f32(backend, engine):
         rinf, rpreds = ref(x)
     assert relerr(preds["boxes"], rpreds["boxes"]) < 1e-3 and relerr(preds["scores"], rpreds["scores"]) < 1e-3
     assert relerr(inf["boxes"], rinf["boxes"]) < 1e-3
+    assert_pred_blocks(inf["boxes"], rinf["boxes"], nc, 1e-3, tag="v5un f32")
     m.train(); ref.train()
     _, preds = m.forward(x.numpy())
     _, rpreds = ref(x)

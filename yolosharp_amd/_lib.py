@@ -190,6 +190,7 @@ PROTOTYPES = {
     "ys_block_create": (C.c_int, [C.c_void_p, C.POINTER(BlockDesc), C.POINTER(C.c_void_p)]),
     "ys_block_output_shape": (C.c_int, [C.c_void_p, c_i32_p]),
     "ys_model_set_preds": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ys_model_decode_preds": (C.c_int, [C.c_void_p]),
     "ys_model_reserve_labels": (C.c_int, [C.c_void_p, C.c_int]),
     "ys_model_one2one_init": (C.c_int, [C.c_void_p, C.c_int]),
     "ys_model_e2e_init": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),

@@ -144,6 +144,19 @@ int ys_model_set_preds(ys_model* m, int batch, const float* boxes, const float* 
   return YS_OK;
 }
 
+// The tail of an eval forward alone (ysm::eval_tail): `pred` (and "det") from the head buffers as they stand -- after ys_model_set_preds the decode of
+// values the caller chose, after an eval forward the same `pred` again.
+int ys_model_decode_preds(ys_model* m) {
+  YS_REQUIRE(m, "ys_model_decode_preds: null argument");
+  YS_REQUIRE(!m->is_block && !m->cls && m->pd_buf >= 0, "ys_model_decode_preds: not a detection-family model (block handles and classify models have no decode)");
+  YS_REQUIRE(!m->training, "ys_model_decode_preds: model is in training mode (Detect returns preds only, Head.cs:103-106)");
+  YS_REQUIRE(m->have_fwd, "ys_model_decode_preds: needs ys_model_set_preds or a forward first");
+  YS_CHECK_HIP(hipSetDevice(m->ctx->device));
+  YS_TRY(ysm::eval_tail(m, m->B));
+  YS_CHECK_HIP(hipGetLastError());
+  return YS_OK;
+}
+
 int ys_model_pred_device(ys_model* m, float** dptr) {
   YS_REQUIRE(m && dptr, "null argument");
   *dptr = m->pred;

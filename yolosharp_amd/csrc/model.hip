@@ -343,20 +343,26 @@ int forward_impl(ys_model* m, int B) {
       so += m->hstate_rng[r].count;
     }
   }
-  if (!m->training && m->pd_buf >= 0) {
-    YS_TRY(ys_detect_decode_launch(st, m->dtype, m->bufs[m->pd_buf].act, m->ld_pd, m->bufs[m->ps_buf].act, m->ld_ps, B, m->A,
-                                   m->d.nc, m->d.reg_max, m->nl, m->lvl_off, m->lvl_w, m->lvl_stride, m->pred, 4 + m->d.nc + m->nm,
-                                   m->xkind >= 2 ? m->bufs[m->mc_buf].act : nullptr, m->ld_mc, m->xkind, m->nm, m->kdim, m->e2e && m->xkind != 2 ? 1 : 0));
-    if (m->segment)   // Segment._inference: cat(preds, mask_coefficient) (Head.cs:309-313), raw coefficients
-      YS_TRY(ys_unpack_nchw_strided_launch(st, m->dtype, m->bufs[m->mc_buf].act, m->ld_mc, 0, B, m->nm, m->A, m->pred,
-                                           (long)(4 + m->d.nc + m->nm) * m->A, (long)(4 + m->d.nc) * m->A));
-    if (m->e2e)   // Detect.postprocess on the one2one branch (same values as the one2many branch): [B][k][6] (Head.cs:107-127).  Segment.postprocess (Head.cs:321-339):
-                  // the same selection, the nm coefficients gathered by the same anchor index: [B][k][6 + nm]; Obb.postprocess (Head.cs:439-452): the angle channel
-                  // rides the same way, rows (cx, cy, w, h, score, class, angle); Pose.postprocess (Head.cs:550-563): the nk decoded keypoint values, rows
-                  // (x1, y1, x2, y2, score, class, keypoints) -- the decode above wrote xyxy (Detect.decode_bboxes, Head.cs:201).  A Detect model has nm = 0
-      YS_TRY(ys_e2e_topk_launch(st, m->pred, B, m->d.nc, m->A, m->max_det, m->det_ws, m->det_rows, m->det_anchor, m->nm));
-  }
+  if (!m->training && m->pd_buf >= 0) YS_TRY(eval_tail(m, B));
   YS_CHECK_HIP(hipGetLastError());
+  return YS_OK;
+}
+
+// The tail of an eval forward of a detection-family model: the head buffers of B images -> `pred` (and, End2End, "det").  forward_impl ends with it;
+// ys_model_decode_preds runs it alone on head buffers a caller supplied (ys_model_set_preds)
+int eval_tail(ys_model* m, int B) {
+  hipStream_t st = m->ctx->stream;
+  YS_TRY(ys_detect_decode_launch(st, m->dtype, m->bufs[m->pd_buf].act, m->ld_pd, m->bufs[m->ps_buf].act, m->ld_ps, B, m->A,
+                                 m->d.nc, m->d.reg_max, m->nl, m->lvl_off, m->lvl_w, m->lvl_stride, m->pred, 4 + m->d.nc + m->nm,
+                                 m->xkind >= 2 ? m->bufs[m->mc_buf].act : nullptr, m->ld_mc, m->xkind, m->nm, m->kdim, m->e2e && m->xkind != 2 ? 1 : 0));
+  if (m->segment)   // Segment._inference: cat(preds, mask_coefficient) (Head.cs:309-313), raw coefficients
+    YS_TRY(ys_unpack_nchw_strided_launch(st, m->dtype, m->bufs[m->mc_buf].act, m->ld_mc, 0, B, m->nm, m->A, m->pred,
+                                         (long)(4 + m->d.nc + m->nm) * m->A, (long)(4 + m->d.nc) * m->A));
+  if (m->e2e)   // Detect.postprocess on the one2one branch (same values as the one2many branch): [B][k][6] (Head.cs:107-127).  Segment.postprocess (Head.cs:321-339):
+                // the same selection, the nm coefficients gathered by the same anchor index: [B][k][6 + nm]; Obb.postprocess (Head.cs:439-452): the angle channel
+                // rides the same way, rows (cx, cy, w, h, score, class, angle); Pose.postprocess (Head.cs:550-563): the nk decoded keypoint values, rows
+                // (x1, y1, x2, y2, score, class, keypoints) -- the decode above wrote xyxy (Detect.decode_bboxes, Head.cs:201).  A Detect model has nm = 0
+    YS_TRY(ys_e2e_topk_launch(st, m->pred, B, m->d.nc, m->A, m->max_det, m->det_ws, m->det_rows, m->det_anchor, m->nm));
   return YS_OK;
 }
 

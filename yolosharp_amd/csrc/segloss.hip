@@ -76,8 +76,14 @@ struct SegArgs {
 };
 
 __device__ inline void seg_crop_bounds(const float* e, int mw, int mh, int trunc, int n_rows, int& c0, int& c1, int& r0, int& r1) {
-  if (trunc && n_rows < 50) {          // Ops.cs:421-435 (C# ToInt32 truncation toward zero)
+  if (trunc && n_rows < 50) {          // Ops.cs:421-435 (C# ToInt32 truncation toward zero), then slice semantics: the reference zeroes [0:y1], [y2:],
+    // [0:x1], [x2:], and a negative slice bound counts from the far edge (-k -> size - k, below -size -> 0).  What is kept is still one interval
     c0 = (int)e[0]; r0 = (int)e[1]; c1 = (int)e[2]; r1 = (int)e[3];
+    if (c0 < 0) c0 += mw;
+    if (c1 < 0) c1 += mw;
+    if (r0 < 0) r0 += mh;
+    if (r1 < 0) r1 += mh;
+    c1 = c1 < 0 ? 0 : c1; r1 = r1 < 0 ? 0 : r1;
   } else {                             // Ops.cs:437-447: x1 <= col < x2
     c0 = (int)ceilf(e[0]); c1 = (int)ceilf(e[2]); r0 = (int)ceilf(e[1]); r1 = (int)ceilf(e[3]);
   }

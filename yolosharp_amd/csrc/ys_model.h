@@ -242,6 +242,7 @@ ConvArgs dgrad_args(ys_model* m, const ConvL& c, int B, const void* dy, int dy_l
 void f8_dgrad_operands(const ys_model* m, const ConvL& c, ConvArgs& a);   // fp8 dgrad: e4m3 dgrad weights and the unit's gradient scale pair (plan_bnred predicts with the same)
 int join_wgrad_stream(ys_model* m);        // order the main stream behind the weight-gradient stream
 int forward_impl(ys_model* m, int B);
+int eval_tail(ys_model* m, int B);         // decode + Segment coefficient append + End2End top-k on the head buffers of B images
 void reset_grad_state(ys_model* m);
 // async_end: leave the weight-gradient stream unjoined (its split reduction runs there too) and record the segment's completion events
 int backward_range(ys_model* m, int seg_lo, int seg_hi, bool async_end = false, bool seg_events = true);

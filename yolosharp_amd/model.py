@@ -207,13 +207,17 @@ class Yolov8:
 
     def set_preds(self, preds):
         """The criterion's `preds` supplied by the caller (Loss.cs:411): {"boxes": [B,4*reg_max,A], "scores": [B,nc,A]} (+
-        "mask_coefficient" [B,nm,A], "proto" [B,nm,H/4,W/4] for Segment models) become the head outputs the loss reads."""
+        "mask_coefficient" [B,nm,A], "proto" [B,nm,H/4,W/4] for Segment models) become the head outputs the loss reads.  An OBB model takes
+        "angle" [B,1,A] (turned into the logit the engine keeps, through a clip) or "angle_logit" [B,1,A], the logit itself, which arrives unchanged."""
         bx = np.ascontiguousarray(preds["boxes"], np.float32)
         sc = np.ascontiguousarray(preds["scores"], np.float32)
         B = bx.shape[0]
         assert bx.shape == (B, 4 * self.reg_max, self.A) and sc.shape == (B, self.nc, self.A), (bx.shape, sc.shape)
         mc = None
-        if self.TASK == 2:      # the engine keeps the angle head as logits: invert angle = (sigmoid(z) - 0.25) * pi (Head.cs:429)
+        if self.TASK == 2 and "angle_logit" in preds:
+            mc = np.ascontiguousarray(preds["angle_logit"], np.float32)
+            assert mc.shape == (B, 1, self.A), mc.shape
+        elif self.TASK == 2:    # the engine keeps the angle head as logits: invert angle = (sigmoid(z) - 0.25) * pi (Head.cs:429)
             p = np.clip(np.asarray(preds["angle"], np.float64) / np.pi + 0.25, 1e-7, 1 - 1e-7)
             mc = np.ascontiguousarray(np.log(p / (1 - p)), np.float32)
         elif self.TASK in (1, 3):
@@ -221,6 +225,11 @@ class Yolov8:
         pr = np.ascontiguousarray(preds["proto"], np.float32) if self.TASK == 1 else None
         _lib.check(self.lib, self.lib.ys_model_set_preds(self.handle, B, _ptr(bx), _ptr(sc), _ptr(mc), _ptr(pr)))
         self._batch = B
+
+    def decode_preds(self):
+        """The tail of an eval forward alone (ys_model_decode_preds): "pred" (End2End: and "det") from the head outputs as they stand -- after set_preds the
+        decode of the caller's values, after an eval forward the same "pred" again."""
+        _lib.check(self.lib, self.lib.ys_model_decode_preds(self.handle))
 
     def reserve_labels(self, per_image):
         _lib.check(self.lib, self.lib.ys_model_reserve_labels(self.handle, int(per_image)))
